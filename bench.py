@@ -8,7 +8,7 @@ Inputs (token ids / masks of every step's batch, weights, trie) are resident in 
 timed region. value = queries/s over all ranks (weak scaling: every rank runs K steps of Q queries
 on its own shard, model + trie replicated, one RCCL all_gather of the ranked results at the end).
 
-  python bench.py [--gpus N --steps K --warmup W --batch Q --beams B --len L --docs N_DOCS]
+  python bench.py [--gpus N --steps K --warmup W --batch Q --beams B --len L --docs N_DOCS --dump-outputs DIR]
 
 Extra legs on rank 0 (outside the timed region):
   roofline     one eager step of the TIMED configuration with hipEvents around every launch on the stream it is
@@ -592,6 +592,32 @@ def secondary_train_step(E, synth, ctx, dev, world, rank, bz=128, L=32, steps=5,
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, limit=DUMP_LIMIT_BYTES):
+    """Write what a caller of the search receives (engine.SearchResult) as DIR/<name>.npy: tokens and scores as float32
+    (token ids < 2^24 are exact), the sorted-row ranges as float64. Query rows beyond `limit` bytes are replaced by a fixed
+    seeded sample of the queries, the same rows for every array and every run. Returns {name: shape}."""
+    arrays = {"tokens": (res.tokens, np.float32), "scores": (res.scores, np.float32),
+              "row_lo": (res.row_lo, np.float64), "row_hi": (res.row_hi, np.float64)}
+    Q = int(res.tokens.shape[0])
+    per_query = sum(int(t[0].numel()) * np.dtype(dt).itemsize for t, dt in arrays.values())
+    keep = min(Q, limit // per_query)
+    rows = None if keep == Q else np.sort(np.random.default_rng(0).choice(Q, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, (t, dt) in arrays.items():
+        a = t.detach().cpu().numpy()
+        if rows is not None:
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(dt))
+        shapes[name] = list(a.shape)
+    log(f"[bench] outputs of the last timed step -> {out_dir}: {shapes}"
+        + ("" if rows is None else f" (seeded sample of {keep} of {Q} queries)"))
+    return shapes
+
+
 def launch_command(gpus, env, argv):
     """The N>1 contract is one process per GPU under torch.distributed.run. When --gpus N > 1 is given without a
     launcher (no WORLD_SIZE in the environment), return the command that re-runs this script as N ranks on
@@ -636,7 +662,14 @@ def main():
     ap.add_argument("--precision", default="f16x2", choices=["f16x2", "f32"],
                     help="GEMM arithmetic: f16x2 = fp32 operands as two f16 planes, 3 f16 MFMAs per product "
                          "(fp32-equivalent to ~2^-22); f32 = exact fp32 MFMA")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="after the timed steps, write the search result of rank 0's last timed step (tokens, scores, "
+                         "row_lo, row_hi) to DIR/<name>.npy as float32 / float64, at most 64 MB (a seeded sample of the "
+                         "queries beyond that); the inputs depend on the arguments only, so two builds compare output "
+                         "for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     relaunch = launch_command(args.gpus, os.environ, sys.argv)
     if relaunch is not None:   # `python bench.py --gpus N` without a launcher: become N ranks (one per GPU)
@@ -819,6 +852,8 @@ def main():
     if rank == 0:
         log(f"[bench] last step: {n_leaf}/{Q * B} returned smtids are valid trie leaves; "
             f"workspace {ctx.workspace_bytes() / 2**30:.2f} GiB")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
 
     out = None
     if rank == 0:

@@ -112,7 +112,7 @@ def _cli_worker(rank, world, port, out_dir):
         dist.destroy_process_group()
 
 
-def test_cli_gathered_run_json_equals_single_process(tmp_path):
+def test_cli_gathered_run_json_equals_single_process(tmp_path, monkeypatch):
     import json
     from ripor_amd import evaluate as ev
     with socket.socket() as s:
@@ -132,7 +132,7 @@ def test_cli_gathered_run_json_equals_single_process(tmp_path):
     # single process, file path
     single_dir = tmp_path / "single"
     single_dir.mkdir()
-    ev.generate_for_constrained_prefix_beam_search = _fake_generate
+    monkeypatch.setattr(ev, "generate_for_constrained_prefix_beam_search", _fake_generate)   # undone after the test
     batches = [{"input_ids": torch.tensor([[200 + i, 1]]), "attention_mask": torch.ones((1, 2), dtype=torch.long),
                 "id": torch.tensor([200 + i])} for i in range(N_QUERIES)]
     table = ev.DocidTable([f"D{j}" for j in range(64)])
