@@ -128,15 +128,10 @@ void linear(Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, 
     for (int i = 0; i < 3; ++i) { g.out[i] = O.f[i]; g.ldo[i] = O.ldo[i]; }
     g.split_n = O.split_n; g.out_h = O.h; g.o_ps = O.ps; g.ldoh = O.ldh;
     g.M = M; g.N = W.N; g.K = W.K; g.relu = O.relu;
-    g.trace = L.c->trace_buf;
     g.rm_B = O.rm_B; g.rm_stride = O.rm_stride; g.rm_slot = O.rm_slot; g.rm_head = O.rm_head; g.rm_dshift = O.rm_dshift;
     g.m_dev = m_dev; g.acc_scale = 1.0f / (W_PLANE_SCALE * A.scale); g.plane_scale = O.plane_scale;
     g.row_ssq = A.ssq; g.inv_d_fix = A.inv_d_fix; g.eps = A.eps;
     g.resid_h = O.resid_h; g.r_ps = O.ps; g.ldrh = O.ldh; g.ssq_out = O.ssq_out;
-    // timing ablations (results are wrong with any bit set): 1 = no row-sum atomics, 2 = no consumer row scale
-    static const int dbg = [] { const char* e = dev_getenv("RPR_DEBUG_FUSED"); return e ? atoi(e) : 0; }();
-    if (dbg & 1) g.ssq_out = nullptr;
-    if (dbg & 2) g.row_ssq = nullptr;
     g.sat = L.c->status;
     g.cus = L.c->cur_cus;
     g.small_live = m_dev ? L.c->cur_small_live : 0;
@@ -357,7 +352,7 @@ struct SearchDims { int Q, Lq, B, L, xld; bool packed; unsigned flags; };
 // Decoder steps [t0, t1) of one stage: embed, nd x {self-attention over the beam's ancestry, cross-attention, FF},
 // logits of position t, fused trie mask / top-B / beam expand (reference generation.py:423-526, one iteration per step).
 void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchDims& sd, const StageView& sv,
-                   int t0, int t1, bool shared0, const rpr_debug_taps* taps, unsigned long long* sel_clk) {
+                   int t0, int t1, bool shared0, const rpr_debug_taps* taps) {
   const auto& d = m->d;
   Workspace& w = c->ws;
   const int Q = sv.Qcap, B = sd.B, L = sd.L, Lq = sd.Lq, R = Q * B, inner = m->inner(), dm = d.d_model, dff = d.d_ff, H = d.num_heads;
@@ -467,7 +462,6 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
       sa.tap_parent = taps->step_parent ? taps->step_parent + (size_t)t * R : nullptr;
       sa.tap_valid = taps->step_valid ? reinterpret_cast<unsigned long long*>(taps->step_valid) + (size_t)t * ((size_t)R * V / 64) : nullptr;
     }
-    if (sel_clk) sa.clk = sel_clk + (size_t)t * 8;
     Ln.run(RPR_K_SELECT, 0, (double)Ma * V * 4 + (double)Ma * 40, [&] { return launch_select(sa, s); });
   }
   Ln.account_live(nullptr, 0);   // the live counter of this stage scales THIS stage's records only (fork, tail, finalize follow)
@@ -628,19 +622,9 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
   const int T = Q * Lq, inner = m->inner(), dm = d.d_model;
   const int nd = d.num_decoder_layers;
   hipStream_t s = Ln.s;
-  // debug: RPR_SELECT_CLOCK=1 prints the phase durations of the selection kernel (eager launches only)
-  unsigned long long* sel_clk = nullptr;
-  {
-    static const bool clk_env = [] { const char* e = dev_getenv("RPR_SELECT_CLOCK"); return e && atoi(e) != 0; }();
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (clk_env && hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone &&
-        hipMalloc(&sel_clk, (size_t)L * 8 * sizeof(unsigned long long)) == hipSuccess)
-      (void)hipMemset(sel_clk, 0, (size_t)L * 8 * sizeof(unsigned long long));
-  }
   // index of the last attended key + 1 per query: row packing of the encoder and the cross-attention loop bound
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_mask_lengths(P<int32_t>(w.mask), P<int32_t>(w.last), Q, Lq, s, c->status + 1); });
-  static const bool packed_env = [] { const char* e = dev_getenv("RPR_PACKED_ENCODER"); return !(e && atoi(e) == 0); }();
-  const bool packed = packed_env && !taps;   // taps return the padded [Q, Lq, d] encoder output
+  const bool packed = !taps;   // taps return the padded [Q, Lq, d] encoder output
   c->cur_no_row_split = packed ? 1 : 0;   // the packed rows' capacity says nothing about the live rows (reset below, after the cross-K/V product)
   enqueue_encoder(Ln, c, m, Q, Lq, packed);
   if (taps && taps->encoder_out && !Ln.err) {
@@ -673,21 +657,20 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
   // decoder pass is computed once per query (Q rows, "one beam") and select reads the shared logits row; the
   // position-0 K/V exist in slot 0 only and every beam's ancestry points there. (The reference recomputes
   // the B identical rows; beams 1..B-1 differ only by their -1e9 initial score, generation.py:418-420.)
-  // Off when debug taps are requested (they expect [Q*B, V] logits per step) or RPR_STEP0_SHARED=0.
-  static const bool step0_env = [] { const char* e = dev_getenv("RPR_STEP0_SHARED"); return !(e && atoi(e) == 0); }();
-  const bool shared0 = step0_env && !taps && B > 1;
+  // Off when debug taps are requested (they expect [Q*B, V] logits per step).
+  const bool shared0 = !taps && B > 1;
   // Stages: stage 0 (all queries) walks steps [0, forks[0]); at every fork the forced queries get their tail pass and
   // the others are compacted into the next stage, which walks on to the next fork (or to L); finalize ranks whoever is
   // still stepping at L. Without forks this is the plain loop of the reference.
   // Everything after the first fork works on what that fork left over — usually a handful of queries in buffers sized for
   // all of them: those GEMMs are enqueued as large-tile / small-tile pairs gated on the live count (GemmH2Args.small_live)
   struct SmallLive { rpr_ctx* c; ~SmallLive() { c->cur_small_live = 0; } } small_guard{c};
-  static const int small_live_rows = [] { const char* e = dev_getenv("RPR_SMALL_LIVE"); return e ? atoi(e) : 1024; }();
+  constexpr int small_live_rows = 1024;
   int t0 = 0;
   for (size_t k = 0; k <= forks.size(); ++k) {
     const int t1 = k < forks.size() ? forks[k] : L;
     c->cur_small_live = k >= 1 ? small_live_rows : 0;
-    enqueue_steps(Ln, c, m, tr, sd, sv, t0, t1, shared0, taps, sel_clk);
+    enqueue_steps(Ln, c, m, tr, sd, sv, t0, t1, shared0, taps);
     if (k < forks.size()) {
       const int next_depth = k + 1 < forks.size() ? forks[k + 1] : L;
       const bool last_dropped = drop_last && k + 1 == forks.size();
@@ -697,17 +680,6 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
       sv = nv;
     }
     t0 = t1;
-  }
-  if (sel_clk) {   // debug: phase durations of the selection kernel (block 0), 100 MHz wall clock
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> hb((size_t)L * 8);
-    (void)hipMemcpy(hb.data(), sel_clk, hb.size() * 8, hipMemcpyDeviceToHost);
-    for (int t = 0; t < L; ++t) {
-      fprintf(stderr, "[select t=%2d] us:", t);
-      for (int k = 0; k < 6; ++k) fprintf(stderr, " %7.1f", (double)(hb[t * 8 + k + 1] - hb[t * 8 + k]) * 0.01);
-      fprintf(stderr, "  rounds=%llu\n", hb[t * 8 + 7]);
-    }
-    (void)hipFree(sel_clk);
   }
   FinalizeArgs fa{sv.st[L & 1], sv.Qcap, B, L, P<int32_t>(w.o_tokens), P<float>(w.o_scores),
                   P<int64_t>(w.o_lo), P<int64_t>(w.o_hi), sv.nq_dev, sv.io.qmap};
@@ -835,10 +807,6 @@ int rpr_init(int device, rpr_ctx** out_ctx) {
       if (*p == ',') ++p;
     }
   }
-  if (dev_getenv("RPR_GEMM_TRACE")) {
-    void* p = nullptr;
-    if (hipMalloc(&p, 2 << 20) == hipSuccess) { (void)hipMemset(p, 0, 2 << 20); c->trace_buf = (unsigned long long*)p; }
-  }
   std::memset(c->done, 0, sizeof(c->done));
   hipError_t e = hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->status), 256);
@@ -873,7 +841,6 @@ void rpr_free_ctx(rpr_ctx* c) {
   free_train_ws(c);
   if (c->status) (void)hipFree(c->status);
   if (c->status_host) (void)hipHostFree(c->status_host);
-  if (c->trace_buf) (void)hipFree(c->trace_buf);
   for (auto& r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : c->pool) (void)hipEventDestroy(e);
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
@@ -1588,25 +1555,6 @@ int rpr_op_linear(rpr_ctx* c, const float* A, const float* W, const float* resid
   }
   linear(Ln, {A, At.as<__half>(), (size_t)M * K, K, 1.0f}, {W, Wt.as<__half>(), N, K}, M, out_f32(C, N, N, residual, relu));
   if (At.p) RPR_HIP(hipStreamSynchronize(s));   // the temporaries are freed when this scope ends
-  if (c->trace_buf) {  // dump the stamps of this launch: K/32 tiles x 8 waves x 18 slots (gemm_h2_pp_kernel<.., TRACE>)
-    const char* we = dev_getenv("RPR_GEMM_TRACE_W");
-    const size_t tw = we ? (size_t)atoi(we) : 18;
-    const size_t n = (size_t)(K / 32) * 8 * tw;
-    std::vector<unsigned long long> hbuf(n);
-    RPR_HIP(hipMemcpy(hbuf.data(), c->trace_buf, n * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(dev_getenv("RPR_GEMM_TRACE"), "w")) {
-      for (size_t i = 0; i < n; ++i) fprintf(f, "%llu%c", hbuf[i], (i % tw == tw - 1) ? '\n' : ' ');
-      fclose(f);
-    }
-    // per-tile wall-clock stamps of block 0 (persistent kernel): start, first K-tile landed, K-loop done, epilogue issued
-    std::vector<unsigned long long> tb(4 * 4096);
-    RPR_HIP(hipMemcpy(tb.data(), c->trace_buf + 100000, tb.size() * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen((std::string(dev_getenv("RPR_GEMM_TRACE")) + ".tiles").c_str(), "w")) {
-      for (size_t i = 0; i + 3 < tb.size() && tb[i]; i += 4) fprintf(f, "%llu %llu %llu %llu\n", tb[i], tb[i + 1], tb[i + 2], tb[i + 3]);
-      fclose(f);
-    }
-    RPR_HIP(hipMemset(c->trace_buf + 100000, 0, tb.size() * 8));
-  }
   return Ln.err;
 }
 

@@ -121,7 +121,6 @@ struct GemmH2Args {
   __half* out_h; size_t o_ps; int ldoh;    // f16-plane output [2][M][ldoh] (feeds the next GEMM)
   int M, N, K;
   int relu;
-  unsigned long long* trace;               // diagnostic cycle stamps of block 0 (nullptr in production)
   int rm_B; size_t rm_stride, rm_slot, rm_head;  // KV-cache element map for out[1], out[2] (see GemmArgs)
   int rm_dshift;                           // log2(d_kv) of that map (0 = 6)
   const int* m_dev;                        // nullable: live row count on the device (see GemmArgs)
@@ -154,8 +153,6 @@ struct GemmH2Args {
   // hipGraph is static, the number of queries a fork leaves over is not).
   int live_lo, live_hi, small_live;
   int bf16;                                // 1: A and W are single bf16 planes (training GEMMs, RPR_PREC_BF16); fp32 output only
-  int prefer_pp;                           // 1: the 256x256 ping-pong kernel whatever the tile count, one K-loop per tile (weight gradients:
-                                           // few tiles, thousands of K rows, several launches side by side on separate streams)
   int no_row_split;                        // 1: never split the rows of this launch over two kernels (packed encoder: M is a capacity far above
                                            // the live row count, which only the device knows)
   int kernel_cls;                          // out (host side): profile class of the kernel chosen (RPR_K_GEMM = 256x256 ping-pong, RPR_K_GEMM_SMALL = the others)
@@ -355,7 +352,6 @@ struct SelectArgs {
   // debug taps for step t (nullable)
   double* tap_scores; int32_t* tap_tokens; int32_t* tap_parent;   // [Q, B]
   unsigned long long* tap_valid;                                   // [Q, B*V/64] phase-A child bitmap (bit = beam*V + token)
-  unsigned long long* clk;   // debug (RPR_SELECT_CLOCK=1, eager mode): 8 wall-clock stamps of block 0 at the phase boundaries
   const int* nq_dev;         // nullable: live query count on the device; blocks past it exit
 };
 hipError_t launch_select(const SelectArgs& a, hipStream_t s);
@@ -535,9 +531,7 @@ hipError_t launch_margin_mse_bwd(const float* margins, const float* teacher_pos,
 hipError_t launch_gold_score_bwd(const float* x, const float* ln, const float* out_embeds, const int32_t* out_idx, const float* dscores,
                                  float* dh, float* de, int rows, int d, float eps, float post, hipStream_t s);
 hipError_t launch_grad_norm(const float* g, size_t n, double* part, int nparts, float max_norm, float* out, hipStream_t s);
-hipError_t launch_adamw(float* p, const float* g, float* m, float* v, size_t n, const float* clip, float lr, float b1, float b2,
-                        float eps, float wd, float bc1, float bc2_sqrt, hipStream_t s);
-// every parameter tensor in one launch: segs[i] = {tensor, offset of its gradient / moments in the flat buffers, elements,
+// AdamW over every parameter tensor in one launch: segs[i] = {tensor, offset of its gradient / moments in the flat buffers, elements,
 // decays?}; pref = exclusive prefix sums of ceil(n / 4096)
 struct AdamSeg { float* p; unsigned long long off, n; int decay; };
 hipError_t launch_adamw_multi(const AdamSeg* segs, const int* pref, int nseg, int nchunks, const float* g, float* m, float* v,

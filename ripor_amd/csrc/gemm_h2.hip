@@ -582,14 +582,12 @@ __device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, f32x16 (&ac
 // BF16 = true (training GEMMs, RPR_PREC_BF16): one bf16 plane per operand; the LDS rows of the lo planes hold the NEXT
 // 32 columns of K instead, a K-tile is 64 deep and a phase issues 8 v_mfma_f32_32x32x16_bf16 (slice 0 x slice 0 and
 // slice 1 x slice 1) on the same fragment reads — see gemm_h2_dma_kernel.
-// TRACE = true: diagnostic instantiation (tools/gemm_trace_pp.py, tools/gemm_tile_timeline.py) that stamps cycle counters
-// of block 0 into g.trace; never launched by a search.
 // Schedules that were measured and removed (DESIGN.md "tried and rejected"; the code is in the history): a phase skew
 // between the persistent blocks, a per-round barrier between the blocks of an XCD, and the next tile's first K-tile
 // prefetched under the epilogue — all of them slower or equal on the power-capped headline step.
 // The body is textually shared by two kernels (gemm_h2_pp_body.inc): gemm_h2_pp_kernel (one product, its arguments by value)
 // and gemm_h2_pp_group_kernel (a table of products in device memory, blockIdx.y = product; see there).
-template <bool FULL, bool TRACE = false, bool BF16 = false>
+template <bool FULL, bool BF16 = false>
 __global__ __launch_bounds__(512, 2) void gemm_h2_pp_kernel(GemmH2Args g, int tiles_m, int tiles_n) {
 #include "gemm_h2_pp_body.inc"
 }
@@ -612,7 +610,7 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_pp_kernel(GemmH2Args g, int ti
 // (rocprofv3 FETCH_SIZE; 1.03 GB go through LDS).
 template <bool FULL>
 __global__ __launch_bounds__(512, 2) void gemm_h2_pp_group_kernel(const GemmH2Args* __restrict__ table, const int* __restrict__ assign) {
-  constexpr bool TRACE = false, BF16 = true;
+  constexpr bool BF16 = true;
   const int asg = assign[blockIdx.x];
   if (asg < 0) return;
   const GemmH2Args& g = table[asg >> 16];
@@ -1157,8 +1155,7 @@ static hipError_t launch_wsplit_cfg(const GemmH2Args& k, hipStream_t s) {
 // cfg 0: 32 x 32 (four stages), 1: 64 x 32 (three), 2: 64 x 64 (two).
 struct WsplitChoice { int cfg, ks; double us; long rounds; };
 static WsplitChoice choose_wsplit(int M, int N, int K, int cus, bool can_split, size_t part_cap) {
-  static const double lat_us = [] { const char* e = dev_getenv("RPR_WSPLIT_LAT_US"); return e ? atof(e) : 3.0; }();
-  static const double split_us = [] { const char* e = dev_getenv("RPR_WSPLIT_SPLIT_US"); return e ? atof(e) : 4.5; }();
+  constexpr double lat_us = 3.0, split_us = 4.5;   // per round of blocks; the reduction launch of a K split
   const int bm[3] = {32, 64, 64}, bn[3] = {32, 32, 64};
   const double rate_gbs[3] = {48.0, 48.0, 41.0};
   WsplitChoice best{0, 1, 1e30, 1};
@@ -1183,7 +1180,7 @@ static hipError_t launch_cfg(const GemmH2Args& a, hipStream_t s) {
   const bool full = (a.M % BM == 0) && (a.N % BN == 0) && !a.m_dev;
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
   const dim3 grid(tiles_m * tiles_n, ks), blk(64 * WM * WN);
-  static const int deep_max = [] { const char* e = dev_getenv("RPR_GEMM_DEEP"); return e ? atoi(e) : 128; }();
+  constexpr int deep_max = 128;   // (blocks up to which the 128-row tiles run 4 stages deep)
   if ((tiles_m * tiles_n * ks <= deep_max || BM < 128) && (!a.m_dev || a.live_hi > 0)) {   // fewer tiles than CUs: one block per CU, 3 K-tiles in flight
     if (full)
       hipLaunchKernelGGL((gemm_h2_dma_kernel<BM, BN, WM, WN, true, 4, BF16>), grid, blk, 0, s, a, tiles_m, tiles_n);
@@ -1218,13 +1215,11 @@ static hipError_t launch_256(const GemmH2Args& a_in, hipStream_t s) {
     a.tile_rb = std::max(1, (grid / 8) / a.tile_cw);
   }
   if (a.bf16) {
-    if (full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true, false, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
-    else hipLaunchKernelGGL((gemm_h2_pp_kernel<false, false, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
+    if (full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
+    else hipLaunchKernelGGL((gemm_h2_pp_kernel<false, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
     return hipGetLastError();
   }
-  if (full && a.trace)
-    hipLaunchKernelGGL((gemm_h2_pp_kernel<true, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
-  else if (full)
+  if (full)
     hipLaunchKernelGGL((gemm_h2_pp_kernel<true>), gr, bl, 0, s, a, tiles_m, tiles_n);
   else
     hipLaunchKernelGGL((gemm_h2_pp_kernel<false>), gr, bl, 0, s, a, tiles_m, tiles_n);
@@ -1382,14 +1377,55 @@ __global__ __launch_bounds__(256) void splitk_epilogue4_kernel(GemmH2Args g, con
   }
 }
 
+// Largest split count <= ks in which every split owns at least one of the nkt K-tiles.
+static long trim_ks(long ks, int nkt) {
+  while (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) --ks;
+  return ks;
+}
+
+// splitk_epilogue4_kernel applies: N % 256 == 0 and every column split and leading dimension a multiple of 4.
+static bool epilogue_vec4(const GemmH2Args& a) {
+  return (a.N & 255) == 0 && (a.split_n & 3) == 0 && (a.ldo[0] & 3) == 0 && (a.ldo[1] & 3) == 0 && (a.ldo[2] & 3) == 0 &&
+         (!a.resid || (a.ldr & 3) == 0) && (!a.resid_h || (a.ldrh & 3) == 0) && (!a.out_h || (a.ldoh & 3) == 0);
+}
+
+using TileLaunch = hipError_t (*)(const GemmH2Args&, hipStream_t);
+
+// Split-K over blockIdx.y: `tiles` writes the fp32 partial sums of the ks K ranges to the caller's scratch a.part, then one
+// launch combines them in split order (bitwise reproducible). fused = false: splitk_reduce_kernel adds them to the fp32
+// residual (a plain sum into out[0]); fused = true: splitk_epilogue{,4}_kernel applies a's whole epilogue to the sum, so
+// the tile launch runs with every epilogue field cleared.
+static hipError_t launch_splitk(const GemmH2Args& a, int ks, bool fused, TileLaunch tiles, hipStream_t s) {
+  GemmH2Args p = a;
+  p.ksplit = ks; p.part_stride = (size_t)a.M * a.N;
+  p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N; p.resid = nullptr;
+  if (fused) {
+    p.out_h = nullptr; p.resid_h = nullptr; p.relu = 0; p.row_ssq = nullptr; p.ssq_out = nullptr;
+    p.rm_B = 0; p.acc_scale = 1.0f; p.dyn_a = p.dyn_b = nullptr;
+  }
+  hipError_t e = tiles(p, s);
+  if (e != hipSuccess) return e;
+  const size_t n = (size_t)a.M * a.N, n4 = (size_t)a.M * (a.N >> 2);
+  if (!fused)
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.part, ks, p.part_stride, a.M, a.N,
+                       a.out[0], a.ldo[0], a.resid, a.ldr);
+  else if (epilogue_vec4(a))
+    hipLaunchKernelGGL(splitk_epilogue4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, a, a.part, ks, p.part_stride);
+  else
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, a.part, ks, p.part_stride);
+  return hipGetLastError();
+}
+
+// Partial tiles per split-K launch that the 128 x 64 routes aim for.
+constexpr int SPLITK_TARGET = 640;
+
 // Split-K through the 256x256 ping-pong kernel (weight gradients of the training step: dW[N, K] = dY^T X reduces over the
 // 8192 rows of the batch into 9 .. 36 output tiles): blockIdx.y = K range, partial tiles to the caller's scratch,
 // splitk_reduce_kernel adds them in split order (bitwise reproducible). Returns hipErrorNotSupported when the shape does
 // not qualify (the caller falls back to the 128x64 split-K route).
 static hipError_t launch_256_splitk(const GemmH2Args& a, hipStream_t s) {
-  static const int on = [] { const char* e = dev_getenv("RPR_GEMM_PP_SPLITK"); return e ? atoi(e) : 1; }();
   const int kstep = a.bf16 ? 2 * HBK : HBK;
-  if (!on || !a.part || (a.M & 255) || (a.N & 255) || (a.K % kstep) || a.relu || a.out_h || a.row_ssq || a.ssq_out || a.resid_h ||
+  if (!a.part || (a.M & 255) || (a.N & 255) || (a.K % kstep) || a.relu || a.out_h || a.row_ssq || a.ssq_out || a.resid_h ||
       a.m_dev || a.rm_B || a.split_n < a.N || (a.ldo[0] & 3) || (a.resid && (a.ldr & 3)))
     return hipErrorNotSupported;
   const long tiles = (long)(a.M / 256) * (a.N / 256);
@@ -1397,17 +1433,9 @@ static hipError_t launch_256_splitk(const GemmH2Args& a, hipStream_t s) {
   long ks = cus / tiles;                                        // one round of (tile, K range) blocks on the chip
   ks = std::min<long>(ks, nkt / 4);                             // at least 4 K-tiles per block
   ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-  while (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) --ks;
+  ks = trim_ks(ks, nkt);
   if (tiles > 64 || ks < 2) return hipErrorNotSupported;
-  GemmH2Args p = a;
-  p.ksplit = (int)ks; p.part_stride = (size_t)a.M * a.N;
-  p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N; p.resid = nullptr;
-  hipError_t e = launch_256(p, s);
-  if (e != hipSuccess) return e;
-  const size_t n4 = (size_t)a.M * (a.N >> 2);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.part, (int)ks, p.part_stride, a.M, a.N,
-                     a.out[0], a.ldo[0], a.resid, a.ldr);
-  return hipGetLastError();
+  return launch_splitk(a, (int)ks, false, launch_256, s);
 }
 
 hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
@@ -1417,10 +1445,9 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
   a_in.kernel_cls = RPR_K_GEMM_SMALL;
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
   if (a.K % HBK != 0 || a.K <= 0 || (a.lda & 7) || (a.ldw & 7)) return hipErrorInvalidValue;
-  static const int skinny = [] { const char* e = dev_getenv("RPR_GEMM_SKINNY"); return e ? atoi(e) : 352; }();   // max rows (measured per search: 320 rows skinny 66.0 vs split-K route 68.5 ms, 400 rows 95.5 vs 71.8)
-  static const int skinny16 = [] { const char* e = dev_getenv("RPR_GEMM_SKINNY16"); return e ? atoi(e) : 1; }();
+  constexpr int skinny = 352;   // max rows (measured per search: 320 rows skinny 66.0 vs split-K route 68.5 ms, 400 rows 95.5 vs 71.8)
   auto launch_skinny = [&](const GemmH2Args& k) {
-    if (skinny16 && k.M <= 32 && (k.N & 15) == 0) {   // one query in flight: 16 x 16 tiles, all of K = 768 in flight
+    if (k.M <= 32 && (k.N & 15) == 0) {   // one query in flight: 16 x 16 tiles, all of K = 768 in flight
       const int tiles_n = k.N / 16;
       const dim3 grid(tiles_n, (k.M + 15) / 16);
       if (!k.m_dev) hipLaunchKernelGGL((gemm_h2_skinny16_kernel<true>), grid, dim3(256), 0, s, k, tiles_n);
@@ -1470,39 +1497,21 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
     // and 60-65 us against 54-58 on the ping-pong kernel. With ONE wave per SIMD the 16 LDS-DMA pieces and 32 fragment reads
     // of a K-tile are issued by the wave that also issues the 64 MFMAs, in series: ~2.2 us per K-tile again. Source kept
     // as tools/gemm_bf16_w128.hip.txt; HISTORY.md.)
-    if (a.prefer_pp) {
-      static const int dwk = [] { const char* e = dev_getenv("RPR_TRAIN_DW_TILE"); return e ? atoi(e) : 256; }();   // experiment: 128 / 64
-      if (dwk == 128) return launch_cfg<128, 128, 2, 2, true>(a, s);
-      if (dwk == 64) return launch_cfg<128, 64, 2, 2, true>(a, s);
-      a_in.kernel_cls = RPR_K_GEMM;
-      return launch_256(a, s);
-    }
     if (a.K >= 2048) {
       const hipError_t e = launch_256_splitk(a, s);
       if (e != hipErrorNotSupported) { if (e == hipSuccess) a_in.kernel_cls = RPR_K_GEMM; return e; }
     }
-    if (a.part && a.K >= 2048 && t128b * 2 < 640 && !a.relu && a.split_n >= a.N && (a.N & 3) == 0 && (a.ldo[0] & 3) == 0 &&
+    if (a.part && a.K >= 2048 && t128b * 2 < SPLITK_TARGET && !a.relu && a.split_n >= a.N && (a.N & 3) == 0 && (a.ldo[0] & 3) == 0 &&
         (!a.resid || (a.ldr & 3) == 0)) {
       const long t = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-      long ks = std::min<long>((640 + t - 1) / t, a.K / 1024);
+      long ks = std::min<long>((SPLITK_TARGET + t - 1) / t, a.K / 1024);
       ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-      const int nkt = a.K / (2 * HBK);
-      while (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) --ks;
-      if (ks > 1) {
-        GemmH2Args p = a;
-        p.ksplit = (int)ks; p.part_stride = (size_t)a.M * a.N;
-        p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N; p.resid = nullptr;
-        hipError_t e = launch_cfg<128, 64, 2, 2, true>(p, s);
-        if (e != hipSuccess) return e;
-        const size_t n4 = (size_t)a.M * (a.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.part, (int)ks, p.part_stride, a.M,
-                           a.N, a.out[0], a.ldo[0], a.resid, a.ldr);
-        return hipGetLastError();
-      }
+      ks = trim_ks(ks, a.K / (2 * HBK));
+      if (ks > 1) return launch_splitk(a, (int)ks, false, launch_cfg<128, 64, 2, 2, true>, s);
     }
     const long t256b = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    static const int bf_pp = [] { const char* e = dev_getenv("RPR_BF16_PP"); return e ? atoi(e) : 200; }();   // min tiles of 256^2 (0 = never)
-    if (bf_pp > 0 && t256b >= bf_pp) return launch_256(a, s);     // ping-pong 256x256 tiles when they fill the chip
+    constexpr int bf_pp = 200;   // min tiles of 256^2
+    if (t256b >= bf_pp) return launch_256(a, s);     // ping-pong 256x256 tiles when they fill the chip
     return t128b < 256 ? launch_cfg<128, 64, 2, 2, true>(a, s) : launch_cfg<128, 128, 2, 2, true>(a, s);
   }
   static const int force = [] { const char* e = dev_getenv("RPR_GEMM_TILE"); return e ? atoi(e) : 0; }();
@@ -1511,7 +1520,7 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
   // chip idle in its last round; the 128-tile kernels quantise finer (measured M = 8192, N = 2304: 135 vs 151 us)
   const int cus = a.cus > 0 ? a.cus : 256;         // a lane stream owns part of the chip: thresholds scale with it
   const double round_eff = (double)t256 / (double)(((t256 + cus - 1) / cus) * cus);
-  if (force == 256 || a.prefer_pp || (force == 0 && t256 >= 112L * cus / 256 && (round_eff >= 0.6 || a.out_h || a.row_ssq))) {
+  if (force == 256 || (force == 0 && t256 >= 112L * cus / 256 && (round_eff >= 0.6 || a.out_h || a.row_ssq))) {
     a_in.kernel_cls = RPR_K_GEMM;
     // Row split of a launch just over a whole number of rounds (beam 1000 with one query: 318 tiles of 256^2 for the
     // N = 768 products = 1.24 rounds, the second one with 62 of 256 CUs busy): the row tiles that fill whole rounds go to
@@ -1523,7 +1532,7 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
     // row tiles is split in the middle.
     static const int row_split = [] { const char* e = dev_getenv("RPR_GEMM_ROWSPLIT"); return e ? atoi(e) : 1; }();
     const bool split_all = row_split == 2 && a.M > 256;
-    if (row_split && (force == 0 || split_all) && !a.prefer_pp && !a.rm_B && a.ksplit <= 1 && !a.trace && a.small_live == 0 && (!a.no_row_split || split_all) &&
+    if (row_split && (force == 0 || split_all) && !a.rm_B && a.ksplit <= 1 && a.small_live == 0 && (!a.no_row_split || split_all) &&
         (t256 > cus || split_all)) {
       const int tiles_n = (a.N + 255) / 256;
       const long rounds = t256 / cus;
@@ -1568,80 +1577,35 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
     const bool take = a.M <= skinny || ch.rounds <= 1 || wsplit_cfg >= 0;
     if (wsplit_cfg >= 0 && wsplit_cfg <= 2) ch.cfg = wsplit_cfg;
     if (wsplit_ks > 0 && (wsplit_ks == 1 || (can_split && (size_t)a.M * a.N * wsplit_ks <= a.part_cap && a.K / wsplit_ks >= 64))) ch.ks = wsplit_ks;
-    auto go = [&](const GemmH2Args& k) {
-      return ch.cfg == 0 ? launch_wsplit_cfg<1, 1, 4>(k, s) : ch.cfg == 1 ? launch_wsplit_cfg<2, 1, 3>(k, s) : launch_wsplit_cfg<2, 2, 2>(k, s);
-    };
-    if (take && ch.ks <= 1) return ch.cfg == 0 ? launch_skinny(a) : go(a);
-    if (take) {
-    GemmH2Args p = a;
-    p.ksplit = ch.ks; p.part_stride = (size_t)a.M * a.N;
-    p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N;
-    p.out_h = nullptr; p.resid = nullptr; p.resid_h = nullptr; p.relu = 0; p.row_ssq = nullptr; p.ssq_out = nullptr;
-    p.rm_B = 0; p.acc_scale = 1.0f; p.dyn_a = p.dyn_b = nullptr;
-    hipError_t e = go(p);
-    if (e != hipSuccess) return e;
-    const size_t n = (size_t)a.M * a.N;
-    const bool vec4 = (a.N & 255) == 0 && (a.split_n & 3) == 0 && (a.ldo[0] & 3) == 0 && (a.ldo[1] & 3) == 0 && (a.ldo[2] & 3) == 0 &&
-                      (!a.resid || (a.ldr & 3) == 0) && (!a.resid_h || (a.ldrh & 3) == 0) && (!a.out_h || (a.ldoh & 3) == 0);
-    if (vec4) hipLaunchKernelGGL(splitk_epilogue4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, a, a.part, ch.ks, p.part_stride);
-    else hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, a.part, ch.ks, p.part_stride);
-    return hipGetLastError();
-    }
+    const TileLaunch go = ch.cfg == 0 ? launch_wsplit_cfg<1, 1, 4> : ch.cfg == 1 ? launch_wsplit_cfg<2, 1, 3> : launch_wsplit_cfg<2, 2, 2>;
+    if (take && ch.ks <= 1) return ch.cfg == 0 ? launch_skinny(a) : go(a, s);
+    if (take) return launch_splitk(a, ch.ks, true, go, s);
   }
   if (force == 0 && a.M <= skinny) return launch_skinny(a);   // (with m_dev: row tiles past the live rows exit)
   const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
   // A few hundred to a few thousand rows in flight (beam 1000 with one query, beam 100 with a dozen, beam 10 with
   // 40-400): the 128x64 launch has fewer blocks than CUs and each walks all of K alone (24-96 K-tiles at ~1 us).
   // Split K over blockIdx.y into the caller's scratch and run the fused epilogue as its own launch.
-  static const int mid_split = [] { const char* e = dev_getenv("RPR_GEMM_MIDSPLIT"); return e ? atoi(e) : 1; }();
-  if (mid_split && force == 0 && a.part && a.mid_split && !a.m_dev && (a.N & 63) == 0 && a.K >= 512) {
+  if (force == 0 && a.part && a.mid_split && !a.m_dev && (a.N & 63) == 0 && a.K >= 512) {
     const long t = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-    const int cus = a.cus > 0 ? a.cus : 256;
-    static const int ks_cap = [] { const char* e = dev_getenv("RPR_GEMM_MIDSPLIT_CAP"); return e ? atoi(e) : 4; }();
+    constexpr int ks_cap = 4;
     long ks = std::min<long>(std::min<long>((3L * cus / 2 + t - 1) / t, ks_cap), a.K / 128);
     ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-    const int nkt = a.K / HBK;
-    while (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) --ks;
-    if (ks > 1 && t < cus) {
-      GemmH2Args p = a;
-      p.ksplit = (int)ks; p.part_stride = (size_t)a.M * a.N;
-      p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N;
-      p.out_h = nullptr; p.resid = nullptr; p.resid_h = nullptr; p.relu = 0; p.row_ssq = nullptr; p.ssq_out = nullptr;
-      p.rm_B = 0; p.acc_scale = 1.0f; p.dyn_a = p.dyn_b = nullptr;
-      hipError_t e = launch_cfg<128, 64>(p, s);
-      if (e != hipSuccess) return e;
-      const size_t n = (size_t)a.M * a.N;
-      const bool vec4 = (a.N & 255) == 0 && (a.split_n & 3) == 0 && (a.ldo[0] & 3) == 0 && (a.ldo[1] & 3) == 0 && (a.ldo[2] & 3) == 0 &&
-                        (!a.resid || (a.ldr & 3) == 0) && (!a.resid_h || (a.ldrh & 3) == 0) && (!a.out_h || (a.ldoh & 3) == 0);
-      if (vec4) hipLaunchKernelGGL(splitk_epilogue4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, a, a.part, (int)ks, p.part_stride);
-      else hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, a.part, (int)ks, p.part_stride);
-      return hipGetLastError();
-    }
+    ks = trim_ks(ks, a.K / HBK);
+    if (ks > 1 && t < cus) return launch_splitk(a, (int)ks, true, launch_cfg<128, 64>, s);
   }
   // split-K: the caller lent scratch for partial results and the launch is a long reduction into few tiles
-  static const int split_target = [] { const char* e = dev_getenv("RPR_GEMM_SPLITK"); return e ? atoi(e) : 640; }();
-  if (a.part && split_target > 0 && a.K >= 2048 && t128 * 2 < split_target && !a.mid_split) {
+  if (a.part && a.K >= 2048 && t128 * 2 < SPLITK_TARGET && !a.mid_split) {
     const hipError_t e = launch_256_splitk(a, s);
     if (e != hipErrorNotSupported) { if (e == hipSuccess) a_in.kernel_cls = RPR_K_GEMM; return e; }
   }
-  if (a.part && split_target > 0 && a.K >= 2048 && t128 * 2 < split_target && !a.out_h && !a.ssq_out && !a.row_ssq && !a.relu && !a.resid_h &&
+  if (a.part && a.K >= 2048 && t128 * 2 < SPLITK_TARGET && !a.out_h && !a.ssq_out && !a.row_ssq && !a.relu && !a.resid_h &&
       !a.m_dev && a.split_n >= a.N && (a.N & 3) == 0 && (a.ldo[0] & 3) == 0 && (!a.resid || (a.ldr & 3) == 0)) {
     const long t = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-    long ks = std::min<long>((split_target + t - 1) / t, a.K / 1024);
+    long ks = std::min<long>((SPLITK_TARGET + t - 1) / t, a.K / 1024);
     ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-    const int nkt = a.K / HBK;
-    while (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) --ks;   // every split owns at least one K-tile
-    if (ks > 1) {
-      GemmH2Args p = a;
-      p.ksplit = (int)ks; p.part_stride = (size_t)a.M * a.N;
-      p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N; p.resid = nullptr;
-      hipError_t e = launch_cfg<128, 64>(p, s);
-      if (e != hipSuccess) return e;
-      const size_t n4 = (size_t)a.M * (a.N >> 2);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.part, (int)ks, p.part_stride, a.M,
-                         a.N, a.out[0], a.ldo[0], a.resid, a.ldr);
-      return hipGetLastError();
-    }
+    ks = trim_ks(ks, a.K / HBK);
+    if (ks > 1) return launch_splitk(a, (int)ks, false, launch_cfg<128, 64>, s);
   }
   const bool narrow = force ? (force == 64) : (t128 < 256);
   return narrow ? launch_cfg<128, 64>(a, s) : launch_cfg<128, 128>(a, s);

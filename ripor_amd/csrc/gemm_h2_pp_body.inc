@@ -1,7 +1,7 @@
 // Body of the 256x256 ping-pong GEMM kernels (see gemm_h2.hip): textually included by gemm_h2_pp_kernel (one product, its
 // arguments `g` by value) and gemm_h2_pp_group_kernel (`g` = an entry of a table in device memory), so that the single-product
 // kernel of the search path compiles exactly as it did as a self-contained kernel (a shared device function taking the
-// arguments by reference changed its register allocation). Expects: FULL, TRACE, BF16 (template parameters), g, tiles_m, tiles_n.
+// arguments by reference changed its register allocation). Expects: FULL, BF16 (template parameters), g, tiles_m, tiles_n.
   // per-tensor dynamic plane scales (training): read from the device; g itself must stay untouched — a kernel that writes
   // to its by-value argument struct gets a private copy of all 320 bytes in scratch (measured: +20 % per launch)
   const float acc_scale = g.dyn_a ? 1.0f / (dyn_plane_scale(*g.dyn_a) * dyn_plane_scale(*g.dyn_b)) : g.acc_scale;
@@ -46,10 +46,6 @@
     tm = band * g.tile_rb + pr; tn = c0 + (r2 - pr * cwg);
   }
   const int bm = tm * BM, bn = tn * BN;
-  // TRACE: wall-clock stamps (100 MHz) of block 0 per tile: start, first K-tile landed, K-loop done, epilogue issued
-  const bool tl = TRACE && g.trace != nullptr && blockIdx.x == 0 && tid == 0 && round < 4096;
-#define PP_TILE_STAMP(k) if (TRACE) { if (tl) g.trace[100000 + round * 4 + (k)] = __builtin_amdgcn_s_memrealtime(); }
-  PP_TILE_STAMP(0);
   if (g.row_ssq && tid < BM) {   // one dependent load + rsqrt per row, hidden behind the first K-tile's DMA; the epilogue
     const int m = bm + tid;      // (after the K-loop's barriers) reads the scales from LDS instead of global memory
     rs_tile[tid] = (m < g.M) ? ssq_rsqrt(g.row_ssq[m], g.inv_d_fix, g.eps) : 1.f;
@@ -194,24 +190,17 @@
 #define PP_L_END(waitimm, ph)                                                                           \
   __builtin_amdgcn_sched_barrier(0);                                                                    \
   __builtin_amdgcn_s_waitcnt(waitimm);                                                                  \
-  PP_STAMP((ph) * 4 + 1);                                                                               \
   __builtin_amdgcn_s_barrier();                                                                         \
-  PP_STAMP((ph) * 4 + 2);                                                                               \
   __builtin_amdgcn_sched_barrier(0);                                                                    \
   __builtin_amdgcn_s_setprio(1)
 #define PP_M_END(ph)                                                                                    \
   __builtin_amdgcn_sched_barrier(0);                                                                    \
   __builtin_amdgcn_s_setprio(0);                                                                        \
-  PP_STAMP((ph) * 4 + 3);                                                                               \
   __builtin_amdgcn_s_barrier();                                                                         \
   __builtin_amdgcn_sched_barrier(0)
   constexpr int WAIT_LGKM = 0xc07f, WAIT_ALL = 0x0070;   // lgkmcnt(0) | vmcnt(0) lgkmcnt(0)
   constexpr int WAIT_VM4 = 0x0074;                       // vmcnt(4) lgkmcnt(0)
 
-  // TRACE: block 0 stamps s_memtime (shader cycles) at the 4 segment edges of each phase -> 16 per (K-tile, wave),
-  // slot 16 = s_memrealtime (100 MHz) at the start of the tile, so the sustained shader clock can be derived
-  const bool tr = TRACE && g.trace != nullptr && blockIdx.x == 0 && lane == 0;
-#define PP_STAMP(slot) if (TRACE) { if (tr) g.trace[((size_t)kt * NW + wave) * 18 + (slot)] = __builtin_readcyclecounter(); }
 #pragma unroll
   for (int j = 0; j < PER_WAVE; ++j) PP_PIECE(0, 0, j);
   if (BF16 && nkt > 1) {   // BF16 schedule (below): the first 32-column slice of tile 1 is already on its way
@@ -222,7 +211,6 @@
   }
   __builtin_amdgcn_s_barrier();                      // tile 0 landed for everyone
   __builtin_amdgcn_sched_barrier(0);
-  PP_TILE_STAMP(1);
   if (wm == 1) __builtin_amdgcn_s_barrier();         // group 1 runs one barrier behind
   __builtin_amdgcn_sched_barrier(0);
   if (BF16) {
@@ -258,14 +246,12 @@
   }
 #define PP_DMA1(j) if (more1) PP_PIECE(nxt, k1, j)
 #define PP_DMA2(j) if (more2) PP_PIECE(cur, k2, j)
-      PP_STAMP(0);
       PP_LOAD_SLICE(cur, 0);
       __builtin_amdgcn_sched_barrier(0);
       if (more1) __builtin_amdgcn_s_waitcnt(WAIT_VM4); else __builtin_amdgcn_s_waitcnt(WAIT_ALL);   // slice 1 of this tile
       PP_L_END(WAIT_LGKM, 0);
       PP_MMA24(PP_DMA1(2), (void)0, PP_DMA1(3), (void)0, (void)0, PP_DMA1(6), (void)0, PP_DMA1(7));
       PP_M_END(0);
-      PP_STAMP(4);
       PP_LOAD_SLICE(cur, 1);
       __builtin_amdgcn_sched_barrier(0);
       if (more1) __builtin_amdgcn_s_waitcnt(WAIT_VM4); else __builtin_amdgcn_s_waitcnt(WAIT_ALL);   // slice 0 of the next tile
@@ -286,15 +272,12 @@
     // (a phase per k-chunk and half of the A rows) cost twice the barriers: per-segment stamps showed every one of the 8
     // barrier intervals of a K-tile at ~630 cycles for 384 of MFMA issue (M 460-550 with the DMA pieces and fixed costs,
     // ~100 of barrier latency): 5076 cycles per K-tile against 3072 of matrix-pipe time.
-    if (TRACE) { if (tr) g.trace[((size_t)kt * NW + wave) * 18 + 16] = __builtin_amdgcn_s_memrealtime(); }
-    PP_STAMP(0);
     PP_LOAD_W(cur, so0);
     PP_LOAD_A4(cur, so0);
     PP_L_END(WAIT_LGKM, 0);
     PP_MMA24(PP_DMA_M(0), PP_DMA_M(1), PP_DMA_M(2), PP_DMA_M(3), PP_DMA_M(4), PP_DMA_M(5), PP_DMA_M(6), PP_DMA_M(7));
     PP_M_END(0);
     // phase 1: chunk 1; tile kt+1 must have landed before anyone's next L_0
-    PP_STAMP(4);
     PP_LOAD_W(cur, so1);
     PP_LOAD_A4(cur, so1);
     PP_L_END(WAIT_ALL, 1);
@@ -303,7 +286,6 @@
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();         // group 0 catches the extra barrier of group 1
   __builtin_amdgcn_sched_barrier(0);
-  PP_TILE_STAMP(2);
 #undef PP_LOAD_W
 #undef PP_LOAD_A
 #undef PP_MFMA
@@ -316,7 +298,6 @@
 #undef PP_DMA_M
 #undef PP_L_END
 #undef PP_M_END
-#undef PP_STAMP
 
   int lane_e = lane;   // laundered like lane_t: the epilogue's per-lane offsets must not live through the K-loop
   asm volatile("" : "+v"(lane_e));
@@ -329,8 +310,6 @@
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  PP_TILE_STAMP(3);
-#undef PP_TILE_STAMP
 #undef PP_PIECE
 #undef PP_SRC_SETUP
   }

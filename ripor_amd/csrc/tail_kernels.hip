@@ -206,7 +206,7 @@ hipError_t launch_tail_embed(const float* in_embeds, const uint16_t* tokens, flo
 // positions T + wave, T + wave + 4, ...: lane j scores key j (L <= 64), the q row is broadcast with v_readlane,
 // softmax across the wave, P.V with lane = output dim. Arithmetic of dec_self_attn_fast_kernel / enc_attn_kernel
 // (unscaled scores + unidirectional relative bias, fp32 softmax normalised before P.V).
-// D = head dim: 64, or 128 (t5-3b; two q / output values per lane) — the fp32-MFMA tiles below are written for 64.
+// D = head dim; launched for 128 only (t5-3b; two q / output values per lane): 64-dim heads take the fp32-MFMA tiles below.
 template <int D>
 __global__ __launch_bounds__(256) void tail_self_attn_kernel(TailSelfAttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1069,8 +1069,6 @@ __global__ __launch_bounds__(256, 4) void step_cross_attn_mfma16_kernel(DecCross
 // Which generation of the fp32-MFMA tail attention runs: 1 = direct K / Q loads and V through LDS, 2 = K (and Q) through
 // LDS-DMA, V direct (bit-identical results). RPR_TAIL_ATTN_GEN; tools/tail_attn_probe.hip switches it per launch.
 int g_tail_attn_gen = [] { const char* e = dev_getenv("RPR_TAIL_ATTN_GEN"); return e ? atoi(e) : 2; }();
-int g_tail_attn_opt = [] { const char* e = dev_getenv("RPR_TAIL_ATTN_OPT"); return e ? atoi(e) : 0; }();
-int g_tail_cross_tpw = [] { const char* e = dev_getenv("RPR_TAIL_CROSS_TPW"); return e ? atoi(e) : 0; }();   // 0 = by size
 
 // the search encoder's attention on the MFMA tile (launch_enc_attn asks); false = not taken
 bool launch_enc_attn_mfma_v2(const EncAttnArgs& a, hipStream_t s, hipError_t* err) {
@@ -1083,25 +1081,20 @@ bool launch_enc_attn_mfma_v2(const EncAttnArgs& a, hipStream_t s, hipError_t* er
 }
 
 hipError_t launch_tail_cross_attn(const DecCrossAttnArgs& a, hipStream_t s) {
-  static const bool off = [] { const char* e = dev_getenv("RPR_TAIL_ATTN_MFMA"); return e && atoi(e) == 0; }();
-  if (off || a.Lq > 64 || a.dkv == 128) return launch_dec_cross_attn(a, s);   // long queries, 128-dim heads: the block kernel (any Lq <= 256)
+  if (a.Lq > 64 || a.dkv == 128) return launch_dec_cross_attn(a, s);   // long queries, 128-dim heads: the block kernel (any Lq <= 256)
   const int tiles = (a.B + 31) / 32;
   if (g_tail_attn_gen == 2 && a.Lq <= 32) {
     // tiles per wave: many tiles -> a wave keeps K / V for nine of them (fewer, longer waves: better on a lane's half of
     // the chip); few -> one tile per wave (more waves to fill the chip)
-    const int want = g_tail_cross_tpw > 0 ? g_tail_cross_tpw : ((long)a.Q * a.H * tiles >= 32768 ? 9 : 1);
-    const int tpw = want >= 9 ? 9 : want >= 3 ? 3 : 1;
+    const int tpw = (long)a.Q * a.H * tiles >= 32768 ? 9 : 1;
     const int groups = (tiles + tpw - 1) / tpw, HB = (a.H + 3) / 4;
     const long blocks = (long)a.Q * groups * HB;
     if (blocks < (1l << 31) / HB && (long)a.Q * groups < (1l << 32) / groups && (long)a.B * a.H * DKV < (1l << 29)) {   // udiv_magic / 32-bit offsets
       const dim3 grid((unsigned)blocks), blk(256);
       const size_t smem = 4 * (32 * 64) * sizeof(float);
       const unsigned hm = div_magic(HB), gm = div_magic(groups);
-      const bool o3 = !(g_tail_attn_opt & 2);   // default: three waves per SIMD, no second Q register set (658 vs 673 us per lane launch)
-      if (tpw == 9 && o3) hipLaunchKernelGGL((tail_cross_attn_mfma_v2_kernel<9, 3, false>), grid, blk, smem, s, a, groups, HB, hm, gm);
-      else if (tpw == 9) hipLaunchKernelGGL((tail_cross_attn_mfma_v2_kernel<9, 2>), grid, blk, smem, s, a, groups, HB, hm, gm);
-      else if (tpw == 3 && o3) hipLaunchKernelGGL((tail_cross_attn_mfma_v2_kernel<3, 3, false>), grid, blk, smem, s, a, groups, HB, hm, gm);
-      else if (tpw == 3) hipLaunchKernelGGL((tail_cross_attn_mfma_v2_kernel<3, 2>), grid, blk, smem, s, a, groups, HB, hm, gm);
+      // nine tiles per wave: three waves per SIMD, no second Q register set (658 vs 673 us per lane launch)
+      if (tpw == 9) hipLaunchKernelGGL((tail_cross_attn_mfma_v2_kernel<9, 3, false>), grid, blk, smem, s, a, groups, HB, hm, gm);
       else hipLaunchKernelGGL((tail_cross_attn_mfma_v2_kernel<1, 4>), grid, blk, smem, s, a, groups, HB, hm, gm);
       return hipGetLastError();
     }
@@ -1373,7 +1366,7 @@ hipError_t launch_train_self_attn_bwd_mfma(const float* qkv, const float* dO, co
   return hipGetLastError();
 }
 
-static size_t tail_self_attn_smem(int L, int D = 64) { return ((size_t)L * (D + 1) + (size_t)L * D + 4 * 64 + 64) * sizeof(float); }
+static size_t tail_self_attn_smem(int L, int D) { return ((size_t)L * (D + 1) + (size_t)L * D + 4 * 64 + 64) * sizeof(float); }
 
 hipError_t launch_tail_self_attn(const TailSelfAttnArgs& a, hipStream_t s) {
   if (a.L > MAX_DEC_LEN || a.T < 1 || a.T >= a.L) return hipErrorInvalidValue;
@@ -1381,28 +1374,20 @@ hipError_t launch_tail_self_attn(const TailSelfAttnArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(tail_self_attn_kernel<128>, dim3((unsigned)a.nseq_cap * a.H), dim3(256), tail_self_attn_smem(a.L, 128), s, a);
     return hipGetLastError();
   }
-  static const bool off = [] { const char* e = dev_getenv("RPR_TAIL_ATTN_MFMA"); return e && atoi(e) == 0; }();
-  if (!off) {
-    const long waves = (long)a.nseq_cap * a.H;
-    const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
-    static const int occ = [] { const char* e = dev_getenv("RPR_TAIL_ATTN_OCC"); return e ? atoi(e) : 2; }();
-    if (g_tail_attn_gen == 2 && a.L <= 32 && a.T <= 8) {
-      const int HB = (a.H + 3) / 4;
-      const long blocks = (long)a.nseq_cap * HB;
-      if (blocks < (1l << 31) / HB && (long)a.nseq_cap < (1l << 32) / a.B) {   // udiv_magic's exact range
-        const dim3 g2((unsigned)blocks);
-        const unsigned hm = div_magic(HB), bm = div_magic(a.B);
-        if (g_tail_attn_opt & 1) hipLaunchKernelGGL(tail_self_attn_mfma_v2_kernel<3>, g2, blk, 4 * (32 * 64) * sizeof(float), s, a, HB, hm, bm);
-        else hipLaunchKernelGGL(tail_self_attn_mfma_v2_kernel<4>, g2, blk, 4 * (32 * 64) * sizeof(float), s, a, HB, hm, bm);
-        return hipGetLastError();
-      }
+  const long waves = (long)a.nseq_cap * a.H;
+  const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
+  if (g_tail_attn_gen == 2 && a.L <= 32 && a.T <= 8) {
+    const int HB = (a.H + 3) / 4;
+    const long blocks = (long)a.nseq_cap * HB;
+    if (blocks < (1l << 31) / HB && (long)a.nseq_cap < (1l << 32) / a.B) {   // udiv_magic's exact range
+      const dim3 g2((unsigned)blocks);
+      const unsigned hm = div_magic(HB), bm = div_magic(a.B);
+      hipLaunchKernelGGL(tail_self_attn_mfma_v2_kernel<4>, g2, blk, 4 * (32 * 64) * sizeof(float), s, a, HB, hm, bm);
+      return hipGetLastError();
     }
-    if (a.L <= 32 && occ == 3) hipLaunchKernelGGL((tail_self_attn_mfma_kernel<1, 3>), grid, blk, 4 * (32 * 64 + 64) * sizeof(float), s, a);
-    else if (a.L <= 32) hipLaunchKernelGGL(tail_self_attn_mfma_kernel<1>, grid, blk, 4 * (32 * 64 + 64) * sizeof(float), s, a);
-    else hipLaunchKernelGGL(tail_self_attn_mfma_kernel<2>, grid, blk, 4 * (64 * 64 + 64 + 32 * 64) * sizeof(float), s, a);
-    return hipGetLastError();
   }
-  hipLaunchKernelGGL(tail_self_attn_kernel<64>, dim3((unsigned)a.nseq_cap * a.H), dim3(256), tail_self_attn_smem(a.L), s, a);
+  if (a.L <= 32) hipLaunchKernelGGL(tail_self_attn_mfma_kernel<1>, grid, blk, 4 * (32 * 64 + 64) * sizeof(float), s, a);
+  else hipLaunchKernelGGL(tail_self_attn_mfma_kernel<2>, grid, blk, 4 * (64 * 64 + 64 + 32 * 64) * sizeof(float), s, a);
   return hipGetLastError();
 }
 
@@ -1604,11 +1589,8 @@ hipError_t launch_max_row_norm(const float* E, const float* w, int rows, int d, 
 }
 
 hipError_t init_tail_kernel_attributes() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_self_attn_kernel<64>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_self_attn_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)tail_self_attn_smem(MAX_DEC_LEN, 128));
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_self_attn_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)tail_self_attn_smem(MAX_DEC_LEN, 128));
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_self_attn_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);
   if (e != hipSuccess) return e;

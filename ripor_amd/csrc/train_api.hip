@@ -24,14 +24,12 @@ struct TrainWs {
   DevBuf enc_act, dec_act, enc_out, xkv, x_last, scores, margins, dscores, in_idx, out_idx, tok_idx;
   // scratch
   DevBuf h, dxa, dxb, dbig, dattn, dxkv, denc, tA, wT, w_part, bias_part, fix, gn_part, gn_out, amax, part, part2;
-  // The weight-gradient GEMMs run on side streams beside the input-gradient chain. dW[N, K] = dY^T X reduces over all
-  // rows of the batch into 9 .. 36 tiles of 256 x 256: one launch cannot fill the chip, so the launches of consecutive
-  // sites go round-robin to NSIDE streams and run next to each other, each walking the whole reduction in one K-loop
-  // (no split-K partials, no reduce pass). One set of transposed-operand scratch per stream: a set is reused NSIDE
-  // dxdw calls later, after its product has finished (ev_done).
+  // The weight-gradient GEMMs run on a side stream beside the input-gradient chain. dW[N, K] = dY^T X reduces over all
+  // rows of the batch into 9 .. 36 tiles of 256 x 256: split-K over the rows and a reduce pass (Bwd). The transposed-operand
+  // scratch rotates over NSIDE sets: a set is reused NSIDE dxdw calls later, after its product has finished (ev_done).
   static constexpr int NSIDE = 4;
   DevBuf tB[NSIDE], tC[NSIDE];
-  hipStream_t side[NSIDE] = {};
+  hipStream_t side = nullptr;
   hipEvent_t ev_fork[NSIDE] = {}, ev_done[NSIDE] = {};
   bool done_pending[NSIDE] = {};
   int flip = 0;
@@ -153,7 +151,7 @@ void amax_reset(Launcher& Ln) {
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_zero_u64(P<unsigned long long>(w.amax), AMAX_SLOTS / 2, Ln.s); });
 }
 void gemm_planes(Launcher& Ln, const Planes& A, const Planes& B, float* C, int ldc, int M, int N, int K, const float* resid, int relu,
-                 DevBuf* part = nullptr, bool whole_k = false) {
+                 DevBuf* part = nullptr) {
   GemmH2Args g{};
   g.A = A.p; g.a_ps = A.ps; g.lda = A.ld; g.W = B.p; g.w_ps = B.ps; g.ldw = B.ld;
   g.resid = resid; g.ldr = ldc;
@@ -161,8 +159,7 @@ void gemm_planes(Launcher& Ln, const Planes& A, const Planes& B, float* C, int l
   g.M = M; g.N = N; g.K = K; g.relu = relu; g.acc_scale = 1.0f; g.sat = Ln.c->status;
   g.dyn_a = A.amax; g.dyn_b = B.amax;
   if (!part) part = &Ln.c->tws->part;
-  if (whole_k) g.prefer_pp = 1;        // one K-loop per tile on the 256 x 256 kernel, no split-K (weight gradients)
-  else { g.part = P<float>(*part); g.part_cap = part->cap / sizeof(float); }
+  g.part = P<float>(*part); g.part_cap = part->cap / sizeof(float);
   Ln.run(RPR_K_GEMM, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), [&] { return launch_gemm_h2(g, Ln.s); },
          &g.kernel_cls);
 }
@@ -182,7 +179,7 @@ bool fused_ok(const rpr_ctx* c, int M, int N) {
   return on && c->precision == RPR_PREC_BF16 && M % 256 == 0 && N % 256 == 0 && (long)(M / 256) * (N / 256) >= 200;
 }
 void gemm_bf16(Launcher& Ln, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, const float* resid,
-               int relu, DevBuf* part = nullptr, bool whole_k = false, const BOut* bo = nullptr) {
+               int relu, DevBuf* part = nullptr, const BOut* bo = nullptr) {
   GemmH2Args g{};
   g.A = reinterpret_cast<const __half*>(A); g.lda = lda; g.W = reinterpret_cast<const __half*>(B); g.ldw = ldb;
   g.resid = resid; g.ldr = ldc;
@@ -190,8 +187,7 @@ void gemm_bf16(Launcher& Ln, const void* A, int lda, const void* B, int ldb, flo
   g.M = M; g.N = N; g.K = K; g.relu = relu; g.acc_scale = 1.0f; g.bf16 = 1;
   if (bo) { g.out_b = bo->rows; g.ldob = N; g.out_bt = bo->tr; g.ldobt = bo->ldt; g.mask_src = bo->mask; g.ldmask = N; }
   if (!part) part = &Ln.c->tws->part;
-  if (whole_k) g.prefer_pp = 1;
-  else { g.part = P<float>(*part); g.part_cap = part->cap / sizeof(float); }
+  g.part = P<float>(*part); g.part_cap = part->cap / sizeof(float);
   Ln.run(RPR_K_GEMM, 2.0 * M * (double)N * K, 2.0 * ((double)M * K + (double)N * K) + 4.0 * (double)M * N, [&] { return launch_gemm_h2(g, Ln.s); },
          &g.kernel_cls);
 }
@@ -324,33 +320,19 @@ int refresh_weight_cache(Launcher& Ln, rpr_ctx* c, rpr_model* m) {
 
 struct Bwd {
   Launcher& Ln; rpr_ctx* c; TrainWs& w; const Dims& D;
-  // RPR_TRAIN_DW_SPLITK=1: one side stream, split-K over the rows + a reduce pass per weight gradient; =0: NSIDE streams,
-  // one K-loop per tile
-  // Measured, t5-base bz 128: bf16 32.4 ms whole-K on 2-4 streams vs 32.7 split-K on one; f16x2 56.3 vs 52.3 (a lone
-  // 256 x 256 block walks 256 K-tiles of the two-plane operands in 670 us and the side streams fall behind the main chain).
-  // And once the search path's two CU-masked lane streams exist in the process, a second side stream lands on the main
-  // stream's hardware queue and the step serialises (bf16 50 ms). The split-K route on ONE side stream does not depend on
-  // how the runtime maps streams to queues: it is the default, RPR_TRAIN_DW_SPLITK=0 selects the whole-K route.
-  static bool whole_k() {
-    static const int v = [] { const char* e = dev_getenv("RPR_TRAIN_DW_SPLITK"); return e ? atoi(e) : 1; }();
-    return v == 0;
-  }
-  static int side_streams() {   // streams the whole-K products rotate over (the scratch sets always rotate over NSIDE)
-    static const int v = [] { const char* e = dev_getenv("RPR_TRAIN_SIDE_STREAMS"); const int n = e ? atoi(e) : 2;
-                              return n < 1 ? 1 : (n > TrainWs::NSIDE ? TrainWs::NSIDE : n); }();
-    return whole_k() ? v : 1;
-  }
-  // bf16 mode: the weight gradients of a layer as one grouped launch (gemm_h2_pp_group_kernel); RPR_TRAIN_DW_GROUP=0 selects
-  // the per-product routes above. Measured, t5-base bz 128: see DESIGN.md section 9.
-  static bool grouped() {
-    static const int v = [] { const char* e = dev_getenv("RPR_TRAIN_DW_GROUP"); return e ? atoi(e) : 1; }();
-    return v != 0;
-  }
+  // Weight gradients: one side stream, split-K over the rows + a reduce pass per product.
+  // Measured, t5-base bz 128, against a whole-K route (one K-loop per 256 x 256 tile, products round-robin on 2-4 side
+  // streams; removed): bf16 32.4 ms whole-K vs 32.7 split-K; f16x2 56.3 vs 52.3 (a lone 256 x 256 block walks 256 K-tiles
+  // of the two-plane operands in 670 us and the side streams fall behind the main chain). And once the search path's two
+  // CU-masked lane streams exist in the process, a second side stream lands on the main stream's hardware queue and the
+  // step serialises (bf16 50 ms). The split-K route on ONE side stream does not depend on how the runtime maps streams to
+  // queues.
+  // bf16 mode: the weight gradients of a layer as one grouped launch (gemm_h2_pp_group_kernel) where the shapes allow it,
+  // else the per-product route. Measured, t5-base bz 128: see DESIGN.md section 9.
   // enqueue the products collected since the last flush on the side stream; the main stream goes on
   void flush_group() {
     if (w.grp.n == 0 || Ln.err) return;
-    static const bool side_on = [] { const char* e = dev_getenv("RPR_TRAIN_SIDE"); return !(e && atoi(e) == 0); }();   // 0: in line on the main stream (diagnostic)
-    hipStream_t s = Ln.s, side = side_on ? w.side[0] : Ln.s;
+    hipStream_t s = Ln.s, side = w.side;
     const int gs = w.gset;
     if (hipEventRecord(w.ev_gfork[gs], s) != hipSuccess || hipStreamWaitEvent(side, w.ev_gfork[gs], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
     Launcher L2{c, side};
@@ -386,13 +368,13 @@ struct Bwd {
       const int ptiles = ((N + 255) / 256) * ((K + 255) / 256);
       // a dY the previous call's dX product left converted (rows + transposed copy in this group's set): nothing to convert,
       // and the group has room (checked when the slot was reserved)
-      const bool pre = w.pre.dY == dY && w.pre.gset == w.gset && grouped() && saved_xt && wit_g != w.wc_off.end() && w.wcT.p;
+      const bool pre = w.pre.dY == dY && w.pre.gset == w.gset && saved_xt && wit_g != w.wc_off.end() && w.wcT.p;
       if (w.pre.dY && !pre) { Ln.err = RPR_ERR_INVALID; set_error("dxdw: a pre-converted gradient was not consumed by the next product"); return; }
-      if (!pre && grouped() && saved_xt && wit_g != w.wc_off.end() && w.wcT.p && w.dyT[w.gset].p && ptiles <= GemmGroupArgs::MAX_TILES &&
+      if (!pre && saved_xt && wit_g != w.wc_off.end() && w.wcT.p && w.dyT[w.gset].p && ptiles <= GemmGroupArgs::MAX_TILES &&
           (w.grp.n == 0 || w.grp.K != Mp || w.grp.n >= GemmGroupArgs::MAXP || w.grp_tiles + ptiles > GemmGroupArgs::MAX_TILES ||
            w.dyT_used + need > w.dyT[w.gset].cap))
         flush_group();   // the product does not fit the group being collected: send that one off, start the next
-      if (pre || (grouped() && saved_xt && wit_g != w.wc_off.end() && w.wcT.p && w.dyT[w.gset].p && w.dyT_used + need <= w.dyT[w.gset].cap &&
+      if (pre || (saved_xt && wit_g != w.wc_off.end() && w.wcT.p && w.dyT[w.gset].p && w.dyT_used + need <= w.dyT[w.gset].cap &&
                   ptiles <= GemmGroupArgs::MAX_TILES)) {
         // grouped route: dY^T into this layer's set, the product into the group, dX on the main stream at once
         const void* py = w.tA.p;
@@ -421,7 +403,7 @@ struct Bwd {
           __half* pyt2 = reinterpret_cast<__half*>(static_cast<char*>(w.dyT[w.gset].p) + w.dyT_used);
           w.dyT_used += need2;
           const BOut bo{w.bfb.p, pyt2, Ml, fuse_mask};
-          gemm_bf16(Ln, py, N, pwt, N, nullptr, K, M, K, N, nullptr, 0, nullptr, false, &bo);
+          gemm_bf16(Ln, py, N, pwt, N, nullptr, K, M, K, N, nullptr, 0, nullptr, &bo);
           w.pre.dY = dX; w.pre.py = w.bfb.p; w.pre.pyt = pyt2; w.pre.gset = w.gset;
           return;
         }
@@ -430,7 +412,7 @@ struct Bwd {
       }
       flush_group();   // (a product the group cannot take: keep the order of the side stream's work)
       const int f = w.flip; w.flip = (w.flip + 1) % TrainWs::NSIDE;
-      hipStream_t side = whole_k() ? w.side[f % side_streams()] : w.side[0];
+      hipStream_t side = w.side;
       void *py = w.tA.p, *pyt = w.tC[f].p;
       const void *pxt = w.tB[f].p, *pwt = w.wT.p;
       if (w.done_pending[f]) {
@@ -446,12 +428,11 @@ struct Bwd {
       if (hipEventRecord(w.ev_fork[f], s) != hipSuccess || hipStreamWaitEvent(side, w.ev_fork[f], 0) != hipSuccess) {
         Ln.err = RPR_ERR_HIP; return;
       }
-      static const bool side_on_b = [] { const char* e = dev_getenv("RPR_TRAIN_SIDE"); return !(e && atoi(e) == 0); }();
       {
-        Launcher L2{c, side_on_b ? side : s};
-        gemm_bf16(L2, pyt, Mp, pxt, saved_xt ? Ml : Mp, dW, K, N, K, Mp, nullptr, 0, &w.part2, whole_k());
+        Launcher L2{c, side};
+        gemm_bf16(L2, pyt, Mp, pxt, saved_xt ? Ml : Mp, dW, K, N, K, Mp, nullptr, 0, &w.part2);
         if (L2.err) { Ln.err = L2.err; return; }
-        if (hipEventRecord(w.ev_done[f], side_on_b ? side : s) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
+        if (hipEventRecord(w.ev_done[f], side) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
         w.done_pending[f] = true;
       }
       gemm_bf16(Ln, py, N, pwt, N, dX, K, M, K, N, nullptr, 0);
@@ -463,7 +444,7 @@ struct Bwd {
       float* am = amax_slots(c, 3);
       if (!am) { Ln.err = RPR_ERR_INVALID; return; }
       const int f = w.flip; w.flip = (w.flip + 1) % TrainWs::NSIDE;
-      hipStream_t side = whole_k() ? w.side[f % side_streams()] : w.side[0];
+      hipStream_t side = w.side;
       __half *py = P<__half>(w.tA), *pyt = P<__half>(w.tC[f]), *pxt = P<__half>(w.tB[f]), *pwt = P<__half>(w.wT);
       if (w.done_pending[f]) {   // the dW product that last read this scratch set (NSIDE calls ago) must be over
         if (hipStreamWaitEvent(s, w.ev_done[f], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
@@ -485,12 +466,11 @@ struct Bwd {
       if (hipEventRecord(w.ev_fork[f], s) != hipSuccess || hipStreamWaitEvent(side, w.ev_fork[f], 0) != hipSuccess) {
         Ln.err = RPR_ERR_HIP; return;
       }
-      static const bool side_on = [] { const char* e = dev_getenv("RPR_TRAIN_SIDE"); return !(e && atoi(e) == 0); }();
       {
-        Launcher L2{c, side_on ? side : s};
-        gemm_planes(L2, {pyt, (size_t)N * Mp, Mp, am}, {pxt, (size_t)K * Mp, Mp, am_x}, dW, K, N, K, Mp, nullptr, 0, &w.part2, whole_k());
+        Launcher L2{c, side};
+        gemm_planes(L2, {pyt, (size_t)N * Mp, Mp, am}, {pxt, (size_t)K * Mp, Mp, am_x}, dW, K, N, K, Mp, nullptr, 0, &w.part2);
         if (L2.err) { Ln.err = L2.err; return; }
-        if (hipEventRecord(w.ev_done[f], side_on ? side : s) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
+        if (hipEventRecord(w.ev_done[f], side) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
         w.done_pending[f] = true;
       }
       gemm_planes(Ln, {py, (size_t)M * N, N, am}, {pwt, (size_t)K * N, N, am_w}, dX, K, M, K, N, nullptr, 0);
@@ -547,25 +527,23 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
   for (int i = 0; i < TrainWs::NSIDE; ++i) { E(w.tB[i], wide * rp * f); E(w.tC[i], wide * rp * f); }
   if (c->precision == RPR_PREC_BF16) {
     E(w.xT, XtLayout(D).total * sizeof(__half));
-    if (Bwd::grouped()) {
-      // dY^T of one layer's products: [N_out][pad64(rows)] bf16 each, 256-byte aligned
-      const size_t Rp = ldT(D.R), Tp = ldT(D.T);
-      const size_t dec = (3 * dm + dff + 4 * inner) * Rp, enc = (2 * dm + dff + 3 * inner) * Tp, xkv = (size_t)D.xld * Tp;
-      const size_t need = std::max(std::max(dec, enc), xkv) * sizeof(__half) + 8 * 256;
-      E(w.dyT[0], need); E(w.dyT[1], need);
-      E(w.bfb, rp * dff * sizeof(__half));
-      static_assert(GemmGroupArgs::MAXP * sizeof(GemmH2Args) <= GemmGroupArgs::TABLE_BYTES, "argument table");
-      E(w.gtab, GemmGroupArgs::SCRATCH_BYTES);
-    }
+    // grouped weight gradients: dY^T of one layer's products, [N_out][pad64(rows)] bf16 each, 256-byte aligned
+    const size_t Rp = ldT(D.R), Tp = ldT(D.T);
+    const size_t dec = (3 * dm + dff + 4 * inner) * Rp, enc = (2 * dm + dff + 3 * inner) * Tp, xkv = (size_t)D.xld * Tp;
+    const size_t need = std::max(std::max(dec, enc), xkv) * sizeof(__half) + 8 * 256;
+    E(w.dyT[0], need); E(w.dyT[1], need);
+    E(w.bfb, rp * dff * sizeof(__half));
+    static_assert(GemmGroupArgs::MAXP * sizeof(GemmH2Args) <= GemmGroupArgs::TABLE_BYTES, "argument table");
+    E(w.gtab, GemmGroupArgs::SCRATCH_BYTES);
   }
   E(w.wT, std::max<size_t>(std::max<size_t>(dff * dm, 3 * inner * dm), (size_t)D.xld * dm) * f);
   E(w.w_part, ColsumSites::MAXS * ((rows + 3) / 4) * dm * f);   // the partials of up to four norm sites (Bwd::norm_bwd)
   E(w.bias_part, std::max<size_t>((size_t)D.S, (size_t)D.bz) * D.H * D.buckets * f);
   E(w.fix, std::max<size_t>((size_t)m->d.vocab_size, (size_t)m->d.L * D.V) * dm * 8);
   E(w.gn_part, 1024 * 8); E(w.gn_out, 16); E(w.amax, AMAX_SLOTS * f); E(w.part, (size_t)16 << 20 << 2); E(w.part2, (size_t)16 << 20 << 2);   // split-K partials: 16 M floats per stream
-  if (!e && !w.side[0]) {
+  if (!e && !w.side) {
+    RPR_HIP(hipStreamCreateWithFlags(&w.side, hipStreamNonBlocking));
     for (int i = 0; i < TrainWs::NSIDE; ++i) {
-      if (i < Bwd::side_streams()) RPR_HIP(hipStreamCreateWithFlags(&w.side[i], hipStreamNonBlocking));   // only the streams in use
       RPR_HIP(hipEventCreateWithFlags(&w.ev_fork[i], hipEventDisableTiming));
       RPR_HIP(hipEventCreateWithFlags(&w.ev_done[i], hipEventDisableTiming));
     }
@@ -606,20 +584,19 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const 
   };
   const XtSlots xt{c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr, XtLayout(D)};
   // out = act(norm(x) W^T): in bf16 mode the norm writes the product's bf16 operand and its transposed copy itself
-  // (rmsnorm_bf16_T_kernel); otherwise norm into h, then gemm() converts. RPR_TRAIN_NORM_FUSE=0: the two-kernel route.
-  static const bool norm_fuse = [] { const char* e = dev_getenv("RPR_TRAIN_NORM_FUSE"); return !(e && atoi(e) == 0); }();
+  // (rmsnorm_bf16_T_kernel); otherwise norm into h, then gemm() converts.
   // next_xt: where the NEXT product (the one that reads C) wants C's transposed bf16 copy; when the shapes allow it (fused_ok)
   // this product's epilogue writes it, and C's bf16 rows into w.bfb: returns those rows (the next gemm()'s a_ready) or null
   auto norm_gemm = [&](const float* x, const float* ln, const float* W, float* C, int rows, int N, int relu, void* save_xt,
                        void* next_xt = nullptr) -> const void* {
     auto it = w.wc_off.find(W);
-    if (norm_fuse && c->precision == RPR_PREC_BF16 && save_xt && it != w.wc_off.end() && w.wc.p && dm <= 1024 && (dm & 63) == 0) {
+    if (c->precision == RPR_PREC_BF16 && save_xt && it != w.wc_off.end() && w.wc.p && dm <= 1024 && (dm & 63) == 0) {
       Ln.run(RPR_K_RMSNORM, 0, 8.0 * rows * dm, [&] {
         return launch_rmsnorm_bf16_T(x, ln, rows, dm, D.eps, 1.0f, w.tA.p, save_xt, pad64(rows), ldT(rows), s);
       });
       const bool fuse = next_xt && fused_ok(c, rows, N) && w.bfb.p && w.bfb.cap >= (size_t)rows * N * sizeof(__half) && pad64(rows) == rows;
       const BOut bo{w.bfb.p, next_xt, ldT(rows), nullptr};
-      gemm_bf16(Ln, w.tA.p, dm, reinterpret_cast<const __half*>(w.wc.p) + it->second, dm, C, N, rows, N, dm, nullptr, relu, nullptr, false,
+      gemm_bf16(Ln, w.tA.p, dm, reinterpret_cast<const __half*>(w.wc.p) + it->second, dm, C, N, rows, N, dm, nullptr, relu, nullptr,
                 fuse ? &bo : nullptr);
       return fuse ? w.bfb.p : nullptr;
     }
@@ -845,8 +822,8 @@ void rpr::free_train_ws(rpr_ctx* c) {
     if (w.tC[i].p) (void)hipFree(w.tC[i].p);
     if (w.ev_fork[i]) (void)hipEventDestroy(w.ev_fork[i]);
     if (w.ev_done[i]) (void)hipEventDestroy(w.ev_done[i]);
-    if (w.side[i]) (void)hipStreamDestroy(w.side[i]);
   }
+  if (w.side) (void)hipStreamDestroy(w.side);
   for (hipEvent_t e : w.bucket_ev) (void)hipEventDestroy(e);
   delete c->tws;
   c->tws = nullptr;
@@ -944,36 +921,27 @@ int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp
   // not an nn.LayerNorm in that version, so the T5 layer-norm weights DO decay; `relative_attention_bias.weight` is
   // excluded by its name. (Restated from memory of transformers 4.17 — its source is not available offline; the
   // reference's default weight_decay is 0, where the rule is moot.)
-  static const bool per_tensor = [] { const char* e = dev_getenv("RPR_ADAMW_PER_TENSOR"); return e && atoi(e) != 0; }();
-  if (per_tensor) {
+  if (w.aw_model != m) {   // tensor table: pointer, offset in the flat buffers, elements, decays?
+    std::vector<AdamSeg> segs;
+    std::vector<int> pref;
+    int chunks = 0;
     for (const auto& p : m->params) {
-      const float wd = (p.kind == K_ENC_REL || p.kind == K_DEC_REL) ? 0.0f : weight_decay;
-      RPR_HIP(launch_adamw(p.ptr, flat_grads + p.offset, exp_avg + p.offset, exp_avg_sq + p.offset, p.numel, P<float>(w.gn_out), lr, beta1,
-                           beta2, eps, wd, bc1, bc2s, s));
+      if (!p.numel) continue;
+      segs.push_back(AdamSeg{p.ptr, (unsigned long long)p.offset, (unsigned long long)p.numel,
+                             (p.kind == K_ENC_REL || p.kind == K_DEC_REL) ? 0 : 1});
+      pref.push_back(chunks);
+      chunks += (int)((p.numel + 4095) / 4096);
     }
-  } else {
-    if (w.aw_model != m) {   // tensor table: pointer, offset in the flat buffers, elements, decays?
-      std::vector<AdamSeg> segs;
-      std::vector<int> pref;
-      int chunks = 0;
-      for (const auto& p : m->params) {
-        if (!p.numel) continue;
-        segs.push_back(AdamSeg{p.ptr, (unsigned long long)p.offset, (unsigned long long)p.numel,
-                               (p.kind == K_ENC_REL || p.kind == K_DEC_REL) ? 0 : 1});
-        pref.push_back(chunks);
-        chunks += (int)((p.numel + 4095) / 4096);
-      }
-      e = tensure(c, w.aseg, segs.size() * sizeof(AdamSeg));
-      if (!e) e = tensure(c, w.apref, pref.size() * sizeof(int));
-      if (e) return e;
-      RPR_HIP(hipMemcpyAsync(w.aseg.p, segs.data(), segs.size() * sizeof(AdamSeg), hipMemcpyHostToDevice, s));
-      RPR_HIP(hipMemcpyAsync(w.apref.p, pref.data(), pref.size() * sizeof(int), hipMemcpyHostToDevice, s));
-      RPR_HIP(hipStreamSynchronize(s));              // the host vectors go out of scope
-      w.aw_model = m; w.aw_nseg = (int)segs.size(); w.aw_chunks = chunks;
-    }
-    RPR_HIP(launch_adamw_multi(P<AdamSeg>(w.aseg), P<int>(w.apref), w.aw_nseg, w.aw_chunks, flat_grads, exp_avg, exp_avg_sq,
-                               P<float>(w.gn_out), lr, beta1, beta2, eps, weight_decay, bc1, bc2s, s));
+    e = tensure(c, w.aseg, segs.size() * sizeof(AdamSeg));
+    if (!e) e = tensure(c, w.apref, pref.size() * sizeof(int));
+    if (e) return e;
+    RPR_HIP(hipMemcpyAsync(w.aseg.p, segs.data(), segs.size() * sizeof(AdamSeg), hipMemcpyHostToDevice, s));
+    RPR_HIP(hipMemcpyAsync(w.apref.p, pref.data(), pref.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    RPR_HIP(hipStreamSynchronize(s));              // the host vectors go out of scope
+    w.aw_model = m; w.aw_nseg = (int)segs.size(); w.aw_chunks = chunks;
   }
+  RPR_HIP(launch_adamw_multi(P<AdamSeg>(w.aseg), P<int>(w.apref), w.aw_nseg, w.aw_chunks, flat_grads, exp_avg, exp_avg_sq,
+                             P<float>(w.gn_out), lr, beta1, beta2, eps, weight_decay, bc1, bc2s, s));
   if (out_grad_norm) RPR_HIP(hipMemcpyAsync(out_grad_norm, w.gn_out.p, 4, hipMemcpyDeviceToDevice, s));
   // the search / inference paths read the f16 planes of the weights: they are stale now and are re-split by the next call
   // that needs them (ensure_weight_planes) — a training loop never does, and the refresh costs a pass over every weight

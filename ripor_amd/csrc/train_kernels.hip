@@ -568,8 +568,7 @@ hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t
                                 hipStream_t s) {
   const size_t smem = self_attn_bwd_smem(Ls, buckets);
   if (smem > 160 * 1024 || buckets > 64) return hipErrorInvalidValue;
-  static const bool mfma_off = [] { const char* e = dev_getenv("RPR_TRAIN_ATTN_MFMA"); return e && atoi(e) == 0; }();
-  if (Ls <= 32 && !mfma_off) {   // one wave per (sequence, head) on the fp32 matrix cores (tail_kernels.hip)
+  if (Ls <= 32) {   // one wave per (sequence, head) on the fp32 matrix cores (tail_kernels.hip)
     const hipError_t e = launch_train_self_attn_bwd_mfma(qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, s);
     if (e != hipSuccess) return e;
   } else
@@ -816,28 +815,7 @@ hipError_t launch_grad_norm(const float* g, size_t n, double* part, int nparts, 
 
 // torch.optim.AdamW (decoupled weight decay, no amsgrad), gradient scaled by the clip coefficient on the device:
 //   p *= 1 - lr * wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                     float* __restrict__ v, size_t n, const float* __restrict__ clip, float lr,
-                                                     float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float gi = g[i] * clip[1];
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi; v[i] = vi;
-  float pi = p[i] * (1.f - lr * wd);
-  pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-  p[i] = pi;
-}
-hipError_t launch_adamw(float* p, const float* g, float* m, float* v, size_t n, const float* clip, float lr, float b1, float b2,
-                        float eps, float wd, float bc1, float bc2_sqrt, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, clip, lr, b1, b2, eps, wd, bc1,
-                     bc2_sqrt);
-  return hipGetLastError();
-}
-
-// The same update for every parameter tensor in ONE launch (189 tensors of t5-base: 189 launches of 9 us before). A block
+// for every parameter tensor in ONE launch (189 tensors of t5-base: 189 launches of 9 us with a launch per tensor). A block
 // owns one chunk of 4096 consecutive elements of one tensor: block -> tensor by binary search over the prefix sums of the
 // tensors' chunk counts; gradients and moments live at the tensor's offset of the flat buffers.
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamSeg* __restrict__ segs, const int* __restrict__ pref, int nseg,

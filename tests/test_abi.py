@@ -72,11 +72,11 @@ def test_no_gpu_fails_loudly(lib):
                                                     return_dict_in_generate=True, output_scores=True)
 
 
-def test_environment_variables_the_product_library_reads():
+def test_environment_variables_each_library_reads():
     """The product library reads eight environment variables (README): the documented knobs and the three selectors the
-    GPU suite compares bit for bit with the default path. Every other switch of the sources (A/B routes, kernel
-    generations, tuning constants, traces) goes through dev_getenv (csrc/common.h), which is compiled out of the product
-    build — its name is not even in the binary. The development build of the same sources carries them all."""
+    GPU suite compares bit for bit with the default path. The other switches of the sources (the kernel routes and
+    generations the GPU tests compare against) go through dev_getenv (csrc/common.h), which is compiled out of the product
+    build — their names are not even in the binary. The development build of the same sources carries exactly those."""
     import __graft_entry__ as ge
 
     def names(path):
@@ -86,7 +86,9 @@ def test_environment_variables_the_product_library_reads():
     assert got == {"RPR_PRECISION", "RPR_FORCED_TAIL", "RPR_FORK_DEPTHS", "RPR_LANE_MIN_ROWS", "RPR_TRIE_THREADS", "RPR_SELECT_RADIX",
                    "RPR_SELECT_LEVELS", "RPR_TAIL_RANK_REPLAY"}, sorted(got)
     dev = {n.decode() for n in names(ge.LIB_DEV)}
-    assert got < dev and len(dev) >= 40, sorted(dev)
+    assert dev == got | {"RPR_ENC_ATTN_MFMA", "RPR_STEP_CROSS_MFMA", "RPR_TAIL_ATTN_GEN", "RPR_GEMM_TILE", "RPR_GEMM_ROWSPLIT",
+                         "RPR_GEMM_ROWSPLIT_LOG", "RPR_GEMM_WSPLIT_MAX", "RPR_WSPLIT_CFG", "RPR_WSPLIT_KS", "RPR_PP_SUPERTILE",
+                         "RPR_TRAIN_FUSE_FF"}, sorted(dev)
     srcs = b"".join(open(os.path.join(ge.CSRC, f), "rb").read() for f in ge.SOURCES)
     in_src = {m.decode() for m in re.findall(rb'getenv\("(RPR_[A-Z0-9_]+)"\)', srcs)}
     assert in_src <= dev, sorted(in_src - dev)
