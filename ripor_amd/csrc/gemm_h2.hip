@@ -634,206 +634,95 @@ __global__ void gemm_group_table_kernel(GemmGroupArgs p, GroupAssign a, GemmH2Ar
   table[i] = g;
 }
 
-// ---- skinny variant: M <= 400 rows (one to a few dozen queries in flight) ---------------------------------------
-// Such a launch is a weight stream: 2.4 MB of W for 10 live rows. The tile kernels give it N/64..N/32 blocks
-// that each walk all of K through ONE LDS-DMA stream (~25 GB/s per CU): 18-29 us per launch, 2385 launches per
-// search. Here a block is a 32x32 output tile whose four waves split K between them (wave w takes K-tiles
-// w, w+4, ...), each with a private 4-stage LDS ring fed by its own LDS-DMA stream and no block barrier in the
-// loop (a wave only reads what it loaded itself: s_waitcnt vmcnt is the whole synchronisation). The four partial
-// accumulators are added in the fixed order 0..3 through LDS and wave 0 runs the epilogue — deterministic.
-template <bool FULL>
-__global__ __launch_bounds__(256, 1) void gemm_h2_skinny_kernel(GemmH2Args g, int tiles_m, int tiles_n) {
-  // per-tensor dynamic plane scales (training): read from the device; g itself must stay untouched — a kernel that writes
-  // to its by-value argument struct gets a private copy of all 320 bytes in scratch (measured: +20 % per launch)
-  const float acc_scale = g.dyn_a ? 1.0f / (dyn_plane_scale(*g.dyn_a) * dyn_plane_scale(*g.dyn_b)) : g.acc_scale;
-  constexpr int BM = 32, BN = 32, ST = 4, ROWS = 2 * (BM + BN), PIECES = ROWS / 16;   // 8 KB per stage, 8 pieces
-  __shared__ __attribute__((aligned(16))) __half smem[4 * ST * ROWS * HBK];             // 128 KB
-  const int tile = blockIdx.x, tm = tile / tiles_n, tn = tile - tm * tiles_n;
-  const int bm = tm * BM, bn = tn * BN;
-  // compacted stage / tail job: M is the capacity, the live row count is on the device (and, for one kernel of a gated
-  // group, decides whether this kernel runs at all); row tiles past the live rows exit at once
-  int Mlive = g.M;
-  if (g.m_dev) {
-    const int md = *g.m_dev;
-    if (g.live_hi > 0 && (md <= g.live_lo || md > g.live_hi)) return;
-    Mlive = min(md, g.M);
-  }
-  if (bm >= Mlive) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  __half* wsm = smem + (size_t)wave * ST * ROWS * HBK;
-  // Epilogue operands of wave 0, requested BEFORE the K walk so that their memory latency passes under it (a launch of
-  // this kernel is a chain of latencies: ~1.5 us each for the row scales and for the residual planes when they were
-  // loaded after the reduction): the fused-RMSNorm sums of squares of the lane's 16 rows and the residual of its 16
-  // outputs (column bn + lane % 32, rows 4 * (lane / 32) + (r & 3) + 8 * (r >> 2)).
-  unsigned long long e_ssq[16];
-  unsigned int e_rh[16], e_rl[16];   // raw f16 bits, one 32-bit register each: as __half pairs the compiler packed them on arrival,
-                                          // i.e. waited for every pair of loads before requesting the next (16 serial latencies in front of the K walk)
-  float e_rf[16];
-  if (wave == 0) {
-    const int n = bn + (lane & 31), rsub = 4 * (lane >> 5);
-    const bool nok = FULL || n < g.N;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = bm + rsub + (r & 3) + 8 * (r >> 2);
-      const bool mok = m < Mlive;
-      e_ssq[r] = (g.row_ssq && mok) ? g.row_ssq[m] : 0ull;
-      e_rf[r] = (g.resid && mok && nok) ? g.resid[(size_t)m * g.ldr + n] : 0.f;
-      e_rh[r] = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[(size_t)m * g.ldrh + n] : 0u;
-      e_rl[r] = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[g.r_ps + (size_t)m * g.ldrh + n] : 0u;
-    }
-  }
+// ---- pieces shared by the small-tile kernels (gemm_h2_skinny16_kernel, gemm_h2_wsplit_kernel, splitk_epilogue_kernel) ----
+// Live rows of a launch: M, or for a compacted stage / tail job (m_dev) the device-side live count capped at M. -1: this
+// kernel of a gated group does not run (the count is outside (live_lo, live_hi]), so every row tile exits.
+__device__ __forceinline__ int live_rows(const GemmH2Args& g) {
+  if (!g.m_dev) return g.M;
+  const int md = *g.m_dev;
+  if (g.live_hi > 0 && (md <= g.live_lo || md > g.live_hi)) return -1;
+  return min(md, g.M);
+}
 
-  const __half* src[PIECES];
+// Epilogue operands of one output: the fused-RMSNorm sum of squares of its row and its residual (the planes as raw f16 bits).
+struct EpiIn { unsigned long long ssq; float rf; unsigned int rh, rl; };
+
+// mok / nok: row m / column n exists (what does not exist reads as 0). g by value, here and in epi_fetch: through a reference
+// hipcc re-read ldr / ldrh / r_ps from the kernel arguments in every row's load block, one scalar-load wait each.
+__device__ __forceinline__ EpiIn epi_load(const GemmH2Args g, int m, int n, bool mok, bool nok) {
+  EpiIn e;
+  e.ssq = (g.row_ssq && mok) ? g.row_ssq[m] : 0ull;
+  e.rf = (g.resid && mok && nok) ? g.resid[(size_t)m * g.ldr + n] : 0.f;
+  e.rh = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[(size_t)m * g.ldrh + n] : 0u;
+  e.rl = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[g.r_ps + (size_t)m * g.ldrh + n] : 0u;
+  return e;
+}
+
+// The operands of the R outputs of column n in rows row(0) .. row(R - 1). The tile kernels request them BEFORE the K walk
+// so that the memory latency passes under it (a launch is a chain of latencies: ~1.5 us each for the row scales and for the
+// residual planes when they were loaded after the reduction). One plain array per operand, the residual planes in one
+// 32-bit register each: as __half pairs, as an array of EpiIn or as one struct of the four arrays, hipcc converted every
+// operand on arrival, i.e. waited for each load before requesting the next (R serial latencies in front of the K walk).
+template <int R, typename RowOf>
+__device__ __forceinline__ void epi_fetch(const GemmH2Args g, unsigned long long (&ssq)[R], float (&rf)[R], unsigned int (&rh)[R],
+                                          unsigned int (&rl)[R], int n, bool nok, int Mlive, RowOf row) {
 #pragma unroll
-  for (int j = 0; j < PIECES; ++j) {
-    const int lrow = 16 * j + (lane >> 2);
-    const int seg = (lane & 3) ^ ((lrow >> 2) & 3);
-    const __half* base;
-    int trow, limit;
-    size_t ld;
-    if (lrow < BM) { base = g.A; trow = bm + lrow; limit = g.M; ld = g.lda; }
-    else if (lrow < 2 * BM) { base = g.A + g.a_ps; trow = bm + lrow - BM; limit = g.M; ld = g.lda; }
-    else if (lrow < 2 * BM + BN) { base = g.W; trow = bn + lrow - 2 * BM; limit = g.N; ld = g.ldw; }
-    else { base = g.W + g.w_ps; trow = bn + lrow - 2 * BM - BN; limit = g.N; ld = g.ldw; }
-    if (!FULL && trow >= limit) trow = limit - 1;
-    src[j] = base + (size_t)trow * ld + seg * 8;
-  }
-  auto stage = [&](int buf, int k0) {
-#pragma unroll
-    for (int j = 0; j < PIECES; ++j)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + k0),
-                                       (__attribute__((address_space(3))) void*)(wsm + (size_t)buf * ROWS * HBK + 16 * j * HBK),
-                                       16, 0, 0);
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const int frow = lane & 31, sw = (lane >> 2) & 3, hf = lane >> 5;
-  auto compute = [&](int buf) {
-    const __half* base = wsm + (size_t)buf * ROWS * HBK;
-#pragma unroll
-    for (int c = 0; c < HBK / 16; ++c) {
-      const int so = ((2 * c + hf) ^ sw) * 8;
-      const f16x8 ah = *reinterpret_cast<const f16x8*>(base + frow * HBK + so);
-      const f16x8 al = *reinterpret_cast<const f16x8*>(base + (BM + frow) * HBK + so);
-      const f16x8 bh = *reinterpret_cast<const f16x8*>(base + (2 * BM + frow) * HBK + so);
-      const f16x8 bl = *reinterpret_cast<const f16x8*>(base + (2 * BM + BN + frow) * HBK + so);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-    }
-  };
-  const int nkt = g.K / HBK;
-  const int mine = wave < nkt ? (nkt - wave + 3) / 4 : 0;         // K-tiles wave, wave + 4, ...
-  constexpr int KEEP = PIECES * (ST - 2);                         // 16 pieces of the two younger tiles may be pending
-  constexpr int WAIT_KEEP = (KEEP & 15) | ((KEEP >> 4) << 14) | 0x0f70, WAIT_NONE = 0x0f70;
-#pragma unroll
-  for (int t = 0; t < ST - 1; ++t)
-    if (t < mine) stage(t, (wave + 4 * t) * HBK);
-  for (int i = 0; i < mine; ++i) {
-    if (i + ST - 2 < mine) __builtin_amdgcn_s_waitcnt(WAIT_KEEP); else __builtin_amdgcn_s_waitcnt(WAIT_NONE);
-    __builtin_amdgcn_sched_barrier(0);
-    if (i + ST - 1 < mine) stage((i + ST - 1) % ST, (wave + 4 * (i + ST - 1)) * HBK);   // buffer of tile i-1: its reads are done
-    compute(i % ST);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // reduce the four waves' partial tiles in fixed order through LDS (the operand rings are idle now)
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[r];
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    acc[r] = ((red[(0 * 16 + r) * 64 + lane] + red[(1 * 16 + r) * 64 + lane]) + red[(2 * 16 + r) * 64 + lane]) +
-             red[(3 * 16 + r) * 64 + lane];
-  const int n = bn + (lane & 31), rsub = 4 * (lane >> 5);
-  const bool nok = FULL || n < g.N;
-  const int oi = nok ? n / g.split_n : 0, on = n - oi * g.split_n;
-  float* outp = g.out[oi];
-  const int ldo = g.ldo[oi];
-  float ssr[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int m = bm + rsub + (r & 3) + 8 * (r >> 2);
-    const bool mok = m < Mlive, ok = nok && mok;
-    float v = acc[r] * acc_scale;
-    if (g.row_ssq && mok) v *= ssq_rsqrt(e_ssq[r], g.inv_d_fix, g.eps);
-    if (g.relu) v = fmaxf(v, 0.f);
-    if (g.resid && ok) v = e_rf[r] + v;
-    if (g.resid_h && ok) v = x_from_planes(__ushort_as_half((unsigned short)e_rh[r]), __ushort_as_half((unsigned short)e_rl[r])) + v;
-    if (ok) {
-      if (g.out_h) {
-        __half hi, lo;
-        split_f16(v * g.plane_scale, hi, lo, g.sat);
-        g.out_h[(size_t)m * g.ldoh + n] = hi;
-        g.out_h[g.o_ps + (size_t)m * g.ldoh + n] = lo;
-        v = (__half2float(hi) + __half2float(lo)) / g.plane_scale;
-      } else {
-        outp[out_off(g, oi, m, ldo, on)] = v;
-      }
-    }
-    ssr[r] = ok ? v * v : 0.f;
-  }
-  if (g.ssq_out) {   // wave-uniform branch. The 16 butterflies are independent: issued level by level they overlap
-                     // (one chain after the other cost ~4 us per launch — 12 % of a single-query search)
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ssr[r] += __shfl_xor(ssr[r], o, 64);
-    if ((lane & 31) == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = bm + rsub + (r & 3) + 8 * (r >> 2);
-        if (m < Mlive) atomicAdd(g.ssq_out + m, ssq_to_fix(ssr[r], g.sat));
-      }
-    }
+  for (int r = 0; r < R; ++r) {
+    const EpiIn x = epi_load(g, row(r), n, row(r) < Mlive, nok);
+    ssq[r] = x.ssq; rf[r] = x.rf; rh[r] = x.rh; rl[r] = x.rl;
   }
 }
 
+// The fused epilogue of output (m, n) = column on of out[oi] (outp = out[oi], ldo = ldo[oi]: read once by the caller, not
+// per element): accumulator scale, fused-RMSNorm row scale, ReLU, fp32 residual, residual planes, then an f16-plane or fp32
+// store (ok: the output exists). Returns the value stored — for planes the value they carry — for the caller's row sums.
+__device__ __forceinline__ float epi_apply(const GemmH2Args& g, float acc, float acc_scale, const EpiIn& e, int m, int n, bool mok,
+                                           bool ok, float* outp, int ldo, int oi, int on) {
+  float v = acc * acc_scale;
+  if (g.row_ssq && mok) v *= ssq_rsqrt(e.ssq, g.inv_d_fix, g.eps);
+  if (g.relu) v = fmaxf(v, 0.f);
+  if (g.resid && ok) v = e.rf + v;
+  if (g.resid_h && ok) v = x_from_planes(__ushort_as_half((unsigned short)e.rh), __ushort_as_half((unsigned short)e.rl)) + v;
+  if (ok) {
+    if (g.out_h) {
+      __half hi, lo;
+      split_f16(v * g.plane_scale, hi, lo, g.sat);
+      g.out_h[(size_t)m * g.ldoh + n] = hi;
+      g.out_h[g.o_ps + (size_t)m * g.ldoh + n] = lo;
+      v = (__half2float(hi) + __half2float(lo)) / g.plane_scale;
+    } else {
+      outp[out_off(g, oi, m, ldo, on)] = v;
+    }
+  }
+  return v;
+}
+
 // ---- skinny variant for at most 32 rows (ONE query in flight: the beams of a step, its encoder tokens) ------------------
-// The 32-row skinny kernel gives a 768 x 768 weight 24 blocks, and a wave's ring holds three of its six K-tiles (8-KB
-// stages: 32 activation + 32 weight rows, two planes): two memory round trips per launch, 11 us, 413 launches = 85 % of a
-// single-query search. Here a block is a 16 x 16 output tile (v_mfma_f32_16x16x32_f16: a K-tile of 32 is ONE MFMA per
-// product term): twice the blocks, 4-KB stages, six stages per wave = all of K = 768 in flight at once (K = 3072: a ring of
-// six). blockIdx.y = 16-row tile (one for a step's 10 beams, two for an encoder of 17 .. 32 tokens). Same K split over the
-// four waves, same fixed-order reduction, same fused epilogue arithmetic as the 32-row kernel.
+// The 32 x 32 wave-split tile (gemm_h2_wsplit_kernel<1, 1, 4>) gives a 768 x 768 weight 24 blocks, and a wave's ring holds
+// three of its six K-tiles (8-KB stages: 32 activation + 32 weight rows, two planes): two memory round trips per launch,
+// 11 us, 413 launches = 85 % of a single-query search. Here a block is a 16 x 16 output tile (v_mfma_f32_16x16x32_f16: a
+// K-tile of 32 is ONE MFMA per product term): twice the blocks, 4-KB stages, six stages per wave = all of K = 768 in flight
+// at once (K = 3072: a ring of six). blockIdx.y = 16-row tile (one for a step's 10 beams, two for an encoder of 17 .. 32
+// tokens). Same K split over the four waves, same fixed-order reduction, same fused epilogue (epi_apply) as the 32-row tile.
 template <bool FULL>
 __global__ __launch_bounds__(256, 1) void gemm_h2_skinny16_kernel(GemmH2Args g, int tiles_n) {
   const float acc_scale = g.dyn_a ? 1.0f / (dyn_plane_scale(*g.dyn_a) * dyn_plane_scale(*g.dyn_b)) : g.acc_scale;
   constexpr int BT = 16, ST = 6, ROWS = 4 * BT, PIECES = ROWS / 16;   // 4 KB per stage: A hi, A lo, W hi, W lo x 16 rows
   __shared__ __attribute__((aligned(16))) __half smem[4 * ST * ROWS * HBK];   // 96 KB
   const int bn = blockIdx.x * BT, bm = blockIdx.y * BT;
-  int Mlive = g.M;
-  if (g.m_dev) {
-    const int md = *g.m_dev;
-    if (g.live_hi > 0 && (md <= g.live_lo || md > g.live_hi)) return;
-    Mlive = min(md, g.M);
-  }
+  const int Mlive = live_rows(g);
   if (bm >= Mlive) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __half* wsm = smem + (size_t)wave * ST * ROWS * HBK;
   // epilogue operands of wave 0, requested before the K walk: lane = column bn + lane % 16, rows 4 (lane / 16) + r
+  const int n = bn + (lane & 15), rsub = 4 * (lane >> 4);
+  const bool nok = FULL || n < g.N;
+  const auto row = [&](int r) { return bm + rsub + r; };
   unsigned long long e_ssq[4];
-  unsigned int e_rh[4], e_rl[4];   // raw f16 bits, one 32-bit register each: as __half pairs the compiler packed them on arrival,
-                                          // i.e. waited for every pair of loads before requesting the next (16 serial latencies in front of the K walk)
   float e_rf[4];
-  if (wave == 0) {
-    const int n = bn + (lane & 15), rsub = 4 * (lane >> 4);
-    const bool nok = FULL || n < g.N;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = bm + rsub + r;
-      const bool mok = m < Mlive;
-      e_ssq[r] = (g.row_ssq && mok) ? g.row_ssq[m] : 0ull;
-      e_rf[r] = (g.resid && mok && nok) ? g.resid[(size_t)m * g.ldr + n] : 0.f;
-      e_rh[r] = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[(size_t)m * g.ldrh + n] : 0u;
-      e_rl[r] = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[g.r_ps + (size_t)m * g.ldrh + n] : 0u;
-    }
-  }
+  unsigned int e_rh[4], e_rl[4];
+  if (wave == 0) epi_fetch(g, e_ssq, e_rf, e_rh, e_rl, n, nok, Mlive, row);
   const __half* src[PIECES];
 #pragma unroll
   for (int j = 0; j < PIECES; ++j) {
@@ -892,32 +781,15 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_skinny16_kernel(GemmH2Args g, 
 #pragma unroll
   for (int r = 0; r < 4; ++r)
     acc[r] = ((red[(0 * 4 + r) * 64 + lane] + red[(1 * 4 + r) * 64 + lane]) + red[(2 * 4 + r) * 64 + lane]) + red[(3 * 4 + r) * 64 + lane];
-  const int n = bn + (lane & 15), rsub = 4 * (lane >> 4);
-  const bool nok = FULL || n < g.N;
   const int oi = nok ? n / g.split_n : 0, on = n - oi * g.split_n;
   float* outp = g.out[oi];
   const int ldo = g.ldo[oi];
   float ssr[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int m = bm + rsub + r;
+    const int m = row(r);
     const bool mok = m < Mlive, ok = nok && mok;
-    float v = acc[r] * acc_scale;
-    if (g.row_ssq && mok) v *= ssq_rsqrt(e_ssq[r], g.inv_d_fix, g.eps);
-    if (g.relu) v = fmaxf(v, 0.f);
-    if (g.resid && ok) v = e_rf[r] + v;
-    if (g.resid_h && ok) v = x_from_planes(__ushort_as_half((unsigned short)e_rh[r]), __ushort_as_half((unsigned short)e_rl[r])) + v;
-    if (ok) {
-      if (g.out_h) {
-        __half hi, lo;
-        split_f16(v * g.plane_scale, hi, lo, g.sat);
-        g.out_h[(size_t)m * g.ldoh + n] = hi;
-        g.out_h[g.o_ps + (size_t)m * g.ldoh + n] = lo;
-        v = (__half2float(hi) + __half2float(lo)) / g.plane_scale;
-      } else {
-        outp[out_off(g, oi, m, ldo, on)] = v;
-      }
-    }
+    const float v = epi_apply(g, acc[r], acc_scale, {e_ssq[r], e_rf[r], e_rh[r], e_rl[r]}, m, n, mok, ok, outp, ldo, oi, on);
     ssr[r] = ok ? v * v : 0.f;
   }
   if (g.ssq_out) {   // the 16 lanes of a row group hold this block's 16 columns of rows rsub .. rsub + 3
@@ -933,19 +805,25 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_skinny16_kernel(GemmH2Args g, 
   }
 }
 
-// ---- wave-split tiles for a few dozen to ~1500 rows (round 5) ------------------------------------------------------------------
-// The skinny kernel's scheme (four waves split K, private LDS rings, no block barrier in the K walk, fixed-order reduction
-// through LDS) on larger output tiles: (32 TM) x (32 TN) per block. Why: such a launch is bound by what ONE CU can keep in
-// flight between L2 and its LDS (ring bytes / memory latency ~ 60-85 GB/s per CU), and with 32 x 32 tiles every column tile
-// re-streams its activation rows and every row tile the weights: a 280 x 3072 x 768 product moved 165 MB through LDS-DMA
-// (24 us per launch, 121 launches = the tail pass of a single-query search), 640 rows went to 128 x 64 tiles with split-K
-// over blocks plus a separate epilogue launch (17 + 6 us). 64 x 32 and 64 x 64 tiles move 1/2 .. 1/3 of the bytes with the
-// same number of bytes in flight per CU: ST stages of 2 (BM + BN) rows x 64 B per wave = 144 KB (64 x 32, three stages) or
-// 128 KB (64 x 64, two stages) per block. The waves of quadrant (i, j) run the fused epilogue of their 32 x 32 part (the
-// skinny kernel's arithmetic, in the same order: bit-identical results for every tile shape).
-// blockIdx.y = K range of a split-K launch (ksplit > 1: raw partial sums to out[0] + y * part_stride, the caller runs
-// splitk_epilogue*_kernel behind it).
-template <bool FULL, int TM, int TN, int ST>
+// ---- wave-split tiles for 33 to ~1500 rows (one to ~150 queries in flight) ---------------------------------------------------
+// Such a launch is a weight stream: 2.4 MB of W for 10 live rows. The 128-row tile kernels give it N/64..N/32 blocks that
+// each walk all of K through ONE LDS-DMA stream (~25 GB/s per CU): 18-29 us per launch, 2385 launches per search. Here a
+// block is a (32 TM) x (32 TN) output tile whose four waves split K between them (wave w takes K-tiles w, w+4, ...), each
+// with a private ST-stage LDS ring fed by its own LDS-DMA stream and no block barrier in the loop (a wave only reads what it
+// loaded itself: s_waitcnt vmcnt is the whole synchronisation). The four partial accumulators are added in the fixed order
+// 0..3 through LDS and the waves of quadrant (i, j) run the fused epilogue of their 32 x 32 part — deterministic, and the
+// same arithmetic in the same order for every tile shape: bit-identical results.
+// 32 x 32 tiles (TM = TN = 1, four 8-KB stages) serve up to 352 rows. Beyond that a launch is bound by what ONE CU can keep
+// in flight between L2 and its LDS (ring bytes / memory latency ~ 60-85 GB/s per CU), and with 32 x 32 tiles every column
+// tile re-streams its activation rows and every row tile the weights: a 280 x 3072 x 768 product moved 165 MB through
+// LDS-DMA (24 us per launch, 121 launches = the tail pass of a single-query search), 640 rows went to 128 x 64 tiles with
+// split-K over blocks plus a separate epilogue launch (17 + 6 us). 64 x 32 and 64 x 64 tiles move 1/2 .. 1/3 of the bytes
+// with the same number of bytes in flight per CU: ST stages of 2 (BM + BN) rows x 64 B per wave = 144 KB (64 x 32, three
+// stages) or 128 KB (64 x 64, two stages) per block.
+// SPLIT (ksplit > 1): blockIdx.y = K range, raw partial sums to out[0] + y * part_stride, the caller runs
+// splitk_epilogue*_kernel behind it. A compile-time flag: with the split decided at run time the 32 x 32 tile took ~3 % more
+// time per decoder layer at 64 rows than the separate 32 x 32 kernel it replaced (tools/gemm_bench.py 64 160 320).
+template <bool FULL, int TM, int TN, int ST, bool SPLIT>
 __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, int tiles_m, int tiles_n) {
   const float acc_scale = g.dyn_a ? 1.0f / (dyn_plane_scale(*g.dyn_a) * dyn_plane_scale(*g.dyn_b)) : g.acc_scale;
   constexpr int BM = 32 * TM, BN = 32 * TN, ROWS = 2 * (BM + BN), PIECES = ROWS / 16, NQ = TM * TN;
@@ -954,39 +832,23 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, in
   __shared__ __attribute__((aligned(16))) __half smem[4 * ST * ROWS * HBK];
   const int tile = blockIdx.x, tm = tile / tiles_n, tn = tile - tm * tiles_n;
   const int bm = tm * BM, bn = tn * BN;
-  int Mlive = g.M;
-  if (g.m_dev) {
-    const int md = *g.m_dev;
-    if (g.live_hi > 0 && (md <= g.live_lo || md > g.live_hi)) return;
-    Mlive = min(md, g.M);
-  }
+  const int Mlive = live_rows(g);
   if (bm >= Mlive) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __half* wsm = smem + (size_t)wave * ST * ROWS * HBK;
   const int qi = wave / TN, qj = wave - qi * TN;            // the quadrant this wave finishes (waves >= NQ: none)
-  const bool fused = g.ksplit <= 1;                          // split-K launches store raw partial sums
-  // epilogue operands of the quadrant waves, requested before the K walk (see gemm_h2_skinny_kernel)
+  // epilogue operands of the quadrant waves, requested before the K walk: lane = column n, rows rsub + (r & 3) + 8 (r >> 2)
+  const int n = bn + 32 * qj + (lane & 31), rsub = bm + 32 * qi + 4 * (lane >> 5);
+  const bool nok = FULL || n < g.N;
+  const auto row = [&](int r) { return rsub + (r & 3) + 8 * (r >> 2); };
   unsigned long long e_ssq[16];
-  unsigned int e_rh[16], e_rl[16];   // raw f16 bits, one 32-bit register each: as __half pairs the compiler packed them on arrival,
-                                          // i.e. waited for every pair of loads before requesting the next (16 serial latencies in front of the K walk)
   float e_rf[16];
-  if (wave < NQ && fused) {
-    const int n = bn + 32 * qj + (lane & 31), rsub = bm + 32 * qi + 4 * (lane >> 5);
-    const bool nok = FULL || n < g.N;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = rsub + (r & 3) + 8 * (r >> 2);
-      const bool mok = m < Mlive;
-      e_ssq[r] = (g.row_ssq && mok) ? g.row_ssq[m] : 0ull;
-      e_rf[r] = (g.resid && mok && nok) ? g.resid[(size_t)m * g.ldr + n] : 0.f;
-      e_rh[r] = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[(size_t)m * g.ldrh + n] : 0u;
-      e_rl[r] = (g.resid_h && mok && nok) ? (unsigned int)reinterpret_cast<const unsigned short*>(g.resid_h)[g.r_ps + (size_t)m * g.ldrh + n] : 0u;
-    }
-  }
+  unsigned int e_rh[16], e_rl[16];
+  if (wave < NQ && !SPLIT) epi_fetch(g, e_ssq, e_rf, e_rh, e_rl, n, nok, Mlive, row);
   // K range of this block, then K-tiles wave, wave + 4, ... of it
   int nkt = g.K / HBK, kbeg = 0;
-  if (g.ksplit > 1) {
+  if (SPLIT) {
     const int per = (nkt + g.ksplit - 1) / g.ksplit;
     kbeg = blockIdx.y * per;
     nkt = min(per, nkt - kbeg);
@@ -1038,7 +900,7 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, in
         bh[j] = *reinterpret_cast<const f16x8*>(base + (2 * BM + 32 * j + frow) * HBK + so);
         bl[j] = *reinterpret_cast<const f16x8*>(base + (2 * BM + BN + 32 * j + frow) * HBK + so);
       }
-      // per accumulator the skinny kernel's order of the three terms (lo x hi, hi x lo, hi x hi)
+      // per accumulator the same order of the three terms for every tile shape (lo x hi, hi x lo, hi x hi)
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1084,13 +946,11 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, in
     const float* q = red + ((size_t)(wave * 4) * 16 + r) * 64 + lane;
     sum[r] = ((q[0] + q[16 * 64]) + q[2 * 16 * 64]) + q[3 * 16 * 64];
   }
-  const int n = bn + 32 * qj + (lane & 31), rsub = bm + 32 * qi + 4 * (lane >> 5);
-  const bool nok = FULL || n < g.N;
-  if (!fused) {
+  if (SPLIT) {   // raw partial sums
     float* outp = g.out[0] + (size_t)blockIdx.y * g.part_stride;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = rsub + (r & 3) + 8 * (r >> 2);
+      const int m = row(r);
       if (nok && m < Mlive) outp[(size_t)m * g.ldo[0] + n] = sum[r];
     }
     return;
@@ -1101,27 +961,13 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, in
   float ssr[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = rsub + (r & 3) + 8 * (r >> 2);
+    const int m = row(r);
     const bool mok = m < Mlive, ok = nok && mok;
-    float v = sum[r] * acc_scale;
-    if (g.row_ssq && mok) v *= ssq_rsqrt(e_ssq[r], g.inv_d_fix, g.eps);
-    if (g.relu) v = fmaxf(v, 0.f);
-    if (g.resid && ok) v = e_rf[r] + v;
-    if (g.resid_h && ok) v = x_from_planes(__ushort_as_half((unsigned short)e_rh[r]), __ushort_as_half((unsigned short)e_rl[r])) + v;
-    if (ok) {
-      if (g.out_h) {
-        __half hi, lo;
-        split_f16(v * g.plane_scale, hi, lo, g.sat);
-        g.out_h[(size_t)m * g.ldoh + n] = hi;
-        g.out_h[g.o_ps + (size_t)m * g.ldoh + n] = lo;
-        v = (__half2float(hi) + __half2float(lo)) / g.plane_scale;
-      } else {
-        outp[out_off(g, oi, m, ldo, on)] = v;
-      }
-    }
+    const float v = epi_apply(g, sum[r], acc_scale, {e_ssq[r], e_rf[r], e_rh[r], e_rl[r]}, m, n, mok, ok, outp, ldo, oi, on);
     ssr[r] = ok ? v * v : 0.f;
   }
-  if (g.ssq_out) {
+  if (g.ssq_out) {   // wave-uniform branch. The 16 butterflies are independent: issued level by level they overlap
+                     // (one chain after the other cost ~4 us per launch — 12 % of a single-query search)
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1)
 #pragma unroll
@@ -1129,7 +975,7 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, in
     if ((lane & 31) == 0) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = rsub + (r & 3) + 8 * (r >> 2);
+        const int m = row(r);
         if (m < Mlive) atomicAdd(g.ssq_out + m, ssq_to_fix(ssr[r], g.sat));
       }
     }
@@ -1141,9 +987,12 @@ static hipError_t launch_wsplit_cfg(const GemmH2Args& k, hipStream_t s) {
   constexpr int BM = 32 * TM, BN = 32 * TN;
   const int tiles_m = (k.M + BM - 1) / BM, tiles_n = (k.N + BN - 1) / BN;
   const bool full = (k.M % BM == 0) && (k.N % BN == 0) && !k.m_dev;
-  const dim3 grid(tiles_m * tiles_n, k.ksplit > 1 ? k.ksplit : 1);
-  if (full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
-  else hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
+  const bool split = k.ksplit > 1;
+  const dim3 grid(tiles_m * tiles_n, split ? k.ksplit : 1);
+  if (split && full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST, true>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
+  else if (split) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST, true>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
+  else if (full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST, false>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
+  else hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST, false>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
   return hipGetLastError();
 }
 
@@ -1290,9 +1139,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 // Fused epilogue of a split-K launch whose consumer needs more than a sum (search path, a few hundred to a few thousand
 // rows in flight): out = epilogue(sum over the splits, in split order). One thread per output element, a wave covers 64
-// consecutive columns of one row (N % 64 == 0). Same per-element arithmetic as the tile kernels' epilogues: accumulator
-// scale, fused-RMSNorm row scale, ReLU, residual (fp32 or planes), f16-plane or fp32 output (K/V-cache layout included),
-// fixed-point row sums of squares.
+// consecutive columns of one row (N % 64 == 0). The small-tile kernels' per-element epilogue (epi_apply: accumulator
+// scale, fused-RMSNorm row scale, ReLU, residual (fp32 or planes), f16-plane or fp32 output, K/V-cache layout included),
+// then fixed-point row sums of squares.
 __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmH2Args g, const float* __restrict__ part, int ks, size_t stride) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)g.M * g.N) return;                  // N % 64 == 0: a wave is inside or outside as a whole
@@ -1300,21 +1149,8 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmH2Args g, cons
   float acc = 0.f;
   for (int k = 0; k < ks; ++k) acc += part[(size_t)k * stride + idx];
   const float acc_scale = g.dyn_a ? 1.0f / (dyn_plane_scale(*g.dyn_a) * dyn_plane_scale(*g.dyn_b)) : g.acc_scale;
-  float v = acc * acc_scale;
-  if (g.row_ssq) v *= ssq_rsqrt(g.row_ssq[m], g.inv_d_fix, g.eps);
-  if (g.relu) v = fmaxf(v, 0.f);
-  if (g.resid) v = g.resid[(size_t)m * g.ldr + n] + v;
-  if (g.resid_h) v = x_from_planes(g.resid_h[(size_t)m * g.ldrh + n], g.resid_h[g.r_ps + (size_t)m * g.ldrh + n]) + v;
-  if (g.out_h) {
-    __half hi, lo;
-    split_f16(v * g.plane_scale, hi, lo, g.sat);
-    g.out_h[(size_t)m * g.ldoh + n] = hi;
-    g.out_h[g.o_ps + (size_t)m * g.ldoh + n] = lo;
-    v = (__half2float(hi) + __half2float(lo)) / g.plane_scale;   // the value the planes carry (row sums below)
-  } else {
-    const int oi = n / g.split_n, on = n - oi * g.split_n;
-    g.out[oi][out_off(g, oi, m, g.ldo[oi], on)] = v;
-  }
+  const int oi = n / g.split_n, on = n - oi * g.split_n;
+  const float v = epi_apply(g, acc, acc_scale, epi_load(g, m, n, true, true), m, n, true, true, g.out[oi], g.ldo[oi], oi, on);
   if (g.ssq_out) {   // grid-uniform branch: all 64 lanes of the wave hold columns of row m
     float ss = v * v;
 #pragma unroll
@@ -1454,17 +1290,13 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
       else hipLaunchKernelGGL((gemm_h2_skinny16_kernel<false>), grid, dim3(256), 0, s, k, tiles_n);
       return hipGetLastError();
     }
-    const int tiles_m = (k.M + 31) / 32, tiles_n = (k.N + 31) / 32;
-    const bool full = (k.M % 32 == 0) && (k.N % 32 == 0) && !k.m_dev;
-    if (full) hipLaunchKernelGGL((gemm_h2_skinny_kernel<true>), dim3(tiles_m * tiles_n), dim3(256), 0, s, k, tiles_m, tiles_n);
-    else hipLaunchKernelGGL((gemm_h2_skinny_kernel<false>), dim3(tiles_m * tiles_n), dim3(256), 0, s, k, tiles_m, tiles_n);
-    return hipGetLastError();
+    return launch_wsplit_cfg<1, 1, 4>(k, s);   // 32 x 32 wave-split tiles
   };
   if (a.m_dev && a.small_live > 0 && a.M > a.small_live && !a.bf16) {
     // a compacted stage: capacity M rows, usually a handful alive. The large-tile kernel would walk all of K with the
     // one or two blocks that hold live rows (60-250 us per launch). The launch is enqueued as a group of three, each
     // gated on the device-side live count (two of them exit at once): the large-tile kernel for more than small_live
-    // rows, a 128x64 launch sized for small_live rows, and the skinny kernel for at most `skinny` rows (a few leftover
+    // rows, a 128x64 launch sized for small_live rows, and the skinny tiles for at most `skinny` rows (a few leftover
     // queries: 10 us instead of 17-20 for the 128x64 tile walking K alone).
     GemmH2Args big = a, mid = a, sk = a;
     const int sk_rows = std::min(skinny, a.small_live);
@@ -1572,13 +1404,13 @@ hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
   if (force == 0 && a.M > 32 && a.M <= wsplit_max) {
     const bool can_split = a.part && a.mid_split && !a.m_dev && (a.N & 63) == 0;
     WsplitChoice ch = choose_wsplit(a.M, a.N, a.K, a.cus > 0 ? a.cus : 256, can_split, a.part_cap);
-    // beyond the skinny kernel's old range the 128 x 64 split-K route is as fast once the best wave-split shape needs a second
+    // beyond the 32 x 32 tile's old range the 128 x 64 split-K route is as fast once the best wave-split shape needs a second
     // round of blocks (measured at 640 rows: N = 2304 / 3072 27.8 / 28.9 us against 28.9 / 30.0): those launches stay where they were
     const bool take = a.M <= skinny || ch.rounds <= 1 || wsplit_cfg >= 0;
     if (wsplit_cfg >= 0 && wsplit_cfg <= 2) ch.cfg = wsplit_cfg;
     if (wsplit_ks > 0 && (wsplit_ks == 1 || (can_split && (size_t)a.M * a.N * wsplit_ks <= a.part_cap && a.K / wsplit_ks >= 64))) ch.ks = wsplit_ks;
     const TileLaunch go = ch.cfg == 0 ? launch_wsplit_cfg<1, 1, 4> : ch.cfg == 1 ? launch_wsplit_cfg<2, 1, 3> : launch_wsplit_cfg<2, 2, 2>;
-    if (take && ch.ks <= 1) return ch.cfg == 0 ? launch_skinny(a) : go(a, s);
+    if (take && ch.ks <= 1) return go(a, s);
     if (take) return launch_splitk(a, ch.ks, true, go, s);
   }
   if (force == 0 && a.M <= skinny) return launch_skinny(a);   // (with m_dev: row tiles past the live rows exit)

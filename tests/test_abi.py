@@ -141,7 +141,7 @@ def test_docid_to_smtid_streaming_reader(lib, tmp_path):
 
 
 def test_hot_gemm_kernels_use_no_scratch():
-    """The 256 x 256 ping-pong GEMM and the skinny GEMM must compile without scratch: twice in round 4 (and once in round 2)
+    """The 256 x 256 ping-pong GEMM and the small-tile GEMMs must compile without scratch: twice in round 4 (and once in round 2)
     a harmless-looking edit made hipcc keep the accumulators or a private copy of the 336-byte argument struct in scratch —
     correct results, +20 % per launch, no warning. Cross-compiles gemm_h2.hip for gfx950 (no GPU needed, ~1 min)."""
     import re
@@ -163,8 +163,11 @@ def test_hot_gemm_kernels_use_no_scratch():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and name:
             seen[name] = int(m.group(1))
-    # every ping-pong instantiation (search and grouped), the skinny kernels (32- and 16-row) and the FULL-tile instantiations
-    # of the 128-row LDS-DMA kernel (two definitions of this test once shadowed each other: the second one had dropped these)
-    hot = {k: v for k, v in seen.items() if "gemm_h2_pp_" in k or "gemm_h2_skinny" in k or ("gemm_h2_dma_kernel" in k and "Lb1E" in k)}
+    # every ping-pong instantiation (search and grouped), the 16-row skinny kernel, every wave-split instantiation (the 32 x 32
+    # one serves 33 .. 352 rows) and the FULL-tile instantiations of the 128-row LDS-DMA kernel (two definitions of this test
+    # once shadowed each other: the second one had dropped these)
+    hot = {k: v for k, v in seen.items()
+           if "gemm_h2_pp_" in k or "gemm_h2_skinny" in k or "gemm_h2_wsplit_kernel" in k or ("gemm_h2_dma_kernel" in k and "Lb1E" in k)}
     assert len(hot) >= 8 and any("skinny16" in k for k in hot) and any("gemm_h2_dma_kernel" in k for k in hot), sorted(seen)
+    assert sum("gemm_h2_wsplit_kernel" in k for k in hot) == 12, sorted(seen)   # {ragged, FULL} x {K split or not} x 3 shapes
     assert all(v == 0 for v in hot.values()), {k: v for k, v in hot.items() if v}

@@ -304,12 +304,14 @@ def test_rmsnorm_kernel_against_torch_fp32(engine):
         torch.testing.assert_close(out, ref, atol=1e-5, rtol=1e-5)
 
 
-@pytest.mark.parametrize("M,N,K", [(20480, 768, 768), (5120, 2304, 768), (640, 768, 3072), (10, 768, 768), (2050, 832, 768),
-                                   (12800, 1024, 4096), (12800, 4096, 1024), (23040, 768, 768), (22016, 768, 3072)])
+@pytest.mark.parametrize("M,N,K", [(20480, 768, 768), (5120, 2304, 768), (640, 768, 3072), (10, 768, 768), (160, 768, 768),
+                                   (300, 768, 768), (2050, 832, 768), (12800, 1024, 4096), (12800, 4096, 1024), (23040, 768, 768),
+                                   (22016, 768, 3072)])
 def test_gemm_kernels_are_repeatable_bitwise(engine, M, N, K):
-    """Race screen of the three split-precision GEMM kernels (ping-pong 256x256, LDS-DMA 128-row with deep prefetch,
-    skinny): LDS-DMA ordering bugs show up as rare timing-dependent wrong tiles, so the same launch is repeated and
-    must reproduce its first result bit for bit (tools/gemm_race_screen.py runs the long version)."""
+    """Race screen of the split-precision GEMM kernels (ping-pong 256x256, LDS-DMA 128-row with deep prefetch, wave-split
+    tiles — 32 x 32 for 160 and 300 rows, wider for 640 — and the 16-row skinny kernel for 10): LDS-DMA ordering bugs show up
+    as rare timing-dependent wrong tiles, so the same launch is repeated and must reproduce its first result bit for bit
+    (tools/gemm_race_screen.py runs the long version)."""
     ctx = engine.Context.get(0)
     torch.manual_seed(M + N + K)
     A = torch.randn(M, K, device="cuda")
@@ -356,8 +358,8 @@ def _wsplit_run(env):
 
 
 def test_wave_split_gemm_tiles_agree_with_each_other_and_with_fp64():
-    """Round 5: gemm_h2_wsplit_kernel (64 x 32 and 64 x 64 tiles next to the 32 x 32 skinny tile, optional K split over blocks
-    with the fused reduction launch) for 33 .. 768 rows. Forced through RPR_WSPLIT_CFG / RPR_WSPLIT_KS in subprocesses (the
+    """Round 5: gemm_h2_wsplit_kernel (64 x 32 and 64 x 64 tiles next to the 32 x 32 tile wsplit<1, 1, 4>, optional K split
+    over blocks with the fused reduction launch) for 33 .. 768 rows. Forced through RPR_WSPLIT_CFG / RPR_WSPLIT_KS in subprocesses (the
     route is read once per process): every shape within the split-precision bar of the fp64 product and repeatable; without a
     K split over blocks the three tile shapes sum every output in the same order and must agree BIT FOR BIT (ragged M / N,
     residual, ReLU included); the automatic choice must be one of them."""

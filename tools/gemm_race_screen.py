@@ -1,4 +1,4 @@
-"""Race screen of the split-precision GEMM kernels (ping-pong 256x256, LDS-DMA 128-row, skinny): the same launch is
+"""Race screen of the split-precision GEMM kernels (ping-pong 256x256, LDS-DMA 128-row, wave-split, 16-row skinny): the same launch is
 repeated and every output must be bitwise identical to the first, which itself is checked against fp64.
 (LDS-DMA ordering bugs show up as rare wrong tiles that depend on timing.)  GPU box."""
 import os, sys
