@@ -136,7 +136,7 @@ enum { RPR_K_GEMM = 0, RPR_K_DEC_SELF_ATTN = 1, RPR_K_DEC_CROSS_ATTN = 2, RPR_K_
 int rpr_init(int device, rpr_ctx** out_ctx);
 void rpr_free_ctx(rpr_ctx* ctx);
 const char* rpr_last_error(void);
-/* Library/ABI version; bumped when a signature changes. */
+/* Library/ABI version; bumped when a signature changes or a symbol is added (4: the seq2seq step). */
 int rpr_abi_version(void);
 /* Select the GEMM arithmetic (RPR_PREC_*); default RPR_PREC_F16X2, or RPR_PRECISION=f32|f16x2 in the
  * environment at rpr_init. Takes effect on the next rpr_search/rpr_encode/rpr_op_linear. */
@@ -335,6 +335,29 @@ int rpr_lngknp_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* i
                                 int32_t bz, int32_t Lq, const int32_t* doc_codes, int32_t L, const float* teacher_pos,
                                 const float* teacher_neg, const int32_t* prefix_lens, int32_t n_prefix, float* out_losses,
                                 float* flat_grads, void* stream, void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user);
+/* ---- the seq2seq docid cross-entropy step (loss_type t5seq_aq_encoder_seq2seq; the first stage of RIPOR's docid training) --
+ * Replaces T5SeqAQEncoderForSeq2Seq (modeling/t5_generative_retriever.py:968-1019): the teacher-forced decoder over ONE
+ * sequence per query, decoder_input_ids = [-1, labels[:, :-1]] (dataset/dataset.py:527-550), logits[:, i] = h[:, i] E_i^T with
+ * h = decoder_last_hidden_state (final RMSNorm, scaleup_output_hidden included) and E_i the output codebook of position i (the
+ * input codebook when shared), loss = nn.CrossEntropyLoss over the bz * L rows (their mean). The encoder / decoder GEMMs follow
+ * rpr_set_precision like rpr_lngknp_backward; the head (logits, log-softmax, cross-entropy, its gradients) is exact fp32 in
+ * every mode. Deterministic: two identical calls give bit-identical losses and gradients.
+ *   input_ids, attention_mask: [dev] int32 [bz, Lq]   (Lq <= 128)
+ *   labels:      [dev] int32 [bz, L]   codes in [0, V): a label outside is RPR_ERR_INVALID (checked on the host before anything
+ *                is enqueued: one copy of bz * L labels and a synchronisation of `stream`)
+ *   out_loss:    [dev] float [1]
+ *   out_label_logprob: [dev] float [bz, L], nullable: log-softmax of each position's logits at its label
+ * Limits: d_kv == 64, L <= the model's L, V % 64 == 0 and V <= 1024, d_model % 32 == 0.
+ * rpr_seq2seq_forward: the forward and the head only. rpr_seq2seq_backward: forward + backward, overwrites flat_grads
+ * [dev, rpr_param_total] (same layout and optimizer step as the ranking step: rpr_adamw_step).
+ * rpr_seq2seq_backward_buckets: the same with the gradient buckets of rpr_lngknp_backward_buckets (same order, same layout). */
+int rpr_seq2seq_forward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+                        int32_t Lq, const int32_t* labels, int32_t L, float* out_loss, float* out_label_logprob, void* stream);
+int rpr_seq2seq_backward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+                         int32_t Lq, const int32_t* labels, int32_t L, float* out_loss, float* flat_grads, void* stream);
+int rpr_seq2seq_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
+                                 int32_t bz, int32_t Lq, const int32_t* labels, int32_t L, float* out_loss, float* flat_grads,
+                                 void* stream, void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user);
 int rpr_adamw_step(rpr_ctx* ctx, rpr_model* model, const float* flat_grads, float* exp_avg, float* exp_avg_sq, int64_t step,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
                    float* out_grad_norm, void* stream);

@@ -771,7 +771,7 @@ int alloc_train_workspace(rpr_ctx* c, const rpr_model* m, int bz, int Lq, int nd
 
 extern "C" {
 
-int rpr_abi_version(void) { return 3; }
+int rpr_abi_version(void) { return 4; }
 const char* rpr_last_error(void) { return g_err.c_str(); }
 
 int rpr_rel_bucket(int rel, int bidirectional, int num_buckets, int max_distance) {

@@ -530,6 +530,15 @@ hipError_t launch_margin_mse_bwd(const float* margins, const float* teacher_pos,
                                  int n_prefix, int bz, int L, float* dscores, hipStream_t s);
 hipError_t launch_gold_score_bwd(const float* x, const float* ln, const float* out_embeds, const int32_t* out_idx, const float* dscores,
                                  float* dh, float* de, int rows, int d, float eps, float post, hipStream_t s);
+// seq2seq docid cross-entropy head (exact fp32): hF [bz*L, d] rows (b, i), E [L][V][d], labels [bz*L] in [0, V) (checked by the
+// caller). Forward: dlogits [bz*L, V] = (softmax - onehot) / (bz L), row_loss [bz*L], label_lp [bz*L] (nullable), loss[0] = mean.
+// Backward: dH [bz*L, d] = dlogits_i E_i, dE [L][V][d] = dlogits_i^T hF_i (stored, not accumulated). V % 64 == 0, V <= 1024,
+// d % 32 == 0 (s2s_head_smem_ok).
+int s2s_head_smem_ok(int V);
+hipError_t launch_s2s_head_fwd(const float* hF, const float* E, const int32_t* labels, float* dlogits, float* row_loss, float* label_lp,
+                               float* loss, int bz, int L, int d, int V, hipStream_t s);
+hipError_t launch_s2s_head_bwd(const float* hF, const float* E, const float* dlogits, float* dH, float* dE, int bz, int L, int d, int V,
+                               hipStream_t s);
 hipError_t launch_grad_norm(const float* g, size_t n, double* part, int nparts, float max_norm, float* out, hipStream_t s);
 // AdamW over every parameter tensor in one launch: segs[i] = {tensor, offset of its gradient / moments in the flat buffers, elements,
 // decays?}; pref = exclusive prefix sums of ceil(n / 4096)

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstring>
 #include <unordered_map>
+#include <vector>
 
 #include "internal.h"
 
@@ -22,6 +23,8 @@ using namespace rpr;
 struct TrainWs {
   // saved forward activations
   DevBuf enc_act, dec_act, enc_out, xkv, x_last, scores, margins, dscores, in_idx, out_idx, tok_idx;
+  // seq2seq head: the decoder's last hidden state (after the final norm), dlogits of every row, the row losses
+  DevBuf hF, dlog, row_loss;
   // scratch
   DevBuf h, dxa, dxb, dbig, dattn, dxkv, denc, tA, wT, w_part, bias_part, fix, gn_part, gn_out, amax, part, part2;
   // The weight-gradient GEMMs run on a side stream beside the input-gradient chain. dW[N, K] = dY^T X reduces over all
@@ -127,7 +130,7 @@ inline int pad64(int n) { return (n + 63) & ~63; }
 inline int ldT(int rows) { return pad64(rows); }
 
 struct Dims {
-  int bz, Lq, L, S, R, T, dm, inner, dff, H, ne, nd, V, xld, buckets;
+  int bz, Lq, L, docs, S, R, T, dm, inner, dff, H, ne, nd, V, xld, buckets;   // docs: decoder sequences per query (S = bz docs)
   float eps, post;
   size_t enc_stride, dec_stride;   // floats per saved layer
 };
@@ -520,6 +523,7 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
   E(w.enc_out, T * dm * f); E(w.xkv, T * (size_t)D.xld * f); E(w.x_last, R * dm * f);
   E(w.scores, R * f); E(w.margins, 8 * (size_t)D.bz * f); E(w.dscores, R * f);
   E(w.in_idx, R * 4); E(w.out_idx, R * 4); E(w.tok_idx, T * 4);
+  if (D.docs == 1) { E(w.hF, R * dm * f); E(w.dlog, R * (size_t)D.V * f); E(w.row_loss, R * f); }   // the seq2seq head
   E(w.h, rows * dm * f); E(w.dxa, rows * dm * f); E(w.dxb, rows * dm * f); E(w.dbig, rows * wide * f);
   E(w.dattn, rows * inner * f); E(w.dxkv, T * (size_t)D.xld * f); E(w.denc, T * dm * f);
   E(w.tA, wide * rp * f);
@@ -572,8 +576,10 @@ DecAct dec_act(const TrainWs& w, const Dims& D, int i) {
   return a;
 }
 
+// gold: end with the gold-code scores of the ranking step (w.scores); else the decoder stream is left in w.x_last for the
+// seq2seq head
 void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const int32_t* ids, const int32_t* mask,
-             const int32_t* codes, int32_t* last) {
+             const int32_t* codes, int32_t* last, bool gold = true) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
@@ -621,7 +627,7 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const 
   }
   norm(xe_last, d.enc_final_ln, P<float>(w.enc_out), T);
   gemm(Ln, P<float>(w.enc_out), dm, d.dec_xkv, dm, P<float>(w.xkv), D.xld, T, D.xld, dm, nullptr, 0, xt.xkv());
-  // ---- teacher-forced decoder over all positions of the positive and the negative smtid
+  // ---- teacher-forced decoder over all positions of every smtid (ranking step: the positive and the negative)
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_train_indices(codes, P<int32_t>(w.in_idx), P<int32_t>(w.out_idx), D.S, D.L, D.V, s); });
   Ln.run(RPR_K_OTHER, 0, 8.0 * R * dm, [&] { return launch_train_dec_embed(d.start_embed, d.in_embeds, codes, dec_act(w, D, 0).x0, D.S, D.L, dm, D.V, s); });
   for (int i = 0; i < D.nd; ++i) {
@@ -634,16 +640,33 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const 
     gemm(Ln, a.a0, inner, m->dec_o[i], inner, a.x1, dm, R, dm, inner, a.x0, 0, xt.dec(i, XT_O));
     norm_gemm(a.x1, m->dec_ln1[i], m->dec_xq[i], a.qx, R, inner, 0, xt.dec(i, XT_XQ));
     const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
-    DecCrossAttnArgs ca{a.qx, xk, xk + inner, D.xld, mask, a.a1, D.bz, 2 * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr};
-    // (the query's 2 L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64)
+    DecCrossAttnArgs ca{a.qx, xk, xk + inner, D.xld, mask, a.a1, D.bz, D.docs * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr};
+    // (the query's docs L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64)
     Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] { return launch_tail_cross_attn(ca, s); });
     gemm(Ln, a.a1, inner, m->dec_xo[i], inner, a.x2, dm, R, dm, inner, a.x1, 0, xt.dec(i, XT_XO));
     const void* ffb = norm_gemm(a.x2, m->dec_ln2[i], m->dec_wi[i], a.ff, R, dff, 1, xt.dec(i, XT_WI), xt.dec(i, XT_WO));
     gemm(Ln, a.ff, dff, m->dec_wo[i], dff, xnext, dm, R, dm, dff, a.x2, 0, xt.dec(i, XT_WO), ffb);
   }
+  if (!gold) return;
   Ln.run(RPR_K_OTHER, 0, 0, [&] {
     return launch_gold_scores(P<float>(w.x_last), d.dec_final_ln, d.out_embeds, codes, P<float>(w.scores), D.S, D.L, dm, D.V, D.eps,
                               D.post, s);
+  });
+}
+
+// The seq2seq head after forward(gold = false): hF = the final RMSNorm of the decoder stream (times d^-0.5 under
+// scaleup_output_hidden), then logits, log-softmax, cross-entropy and dlogits (train_kernels.hip, exact fp32 in every mode)
+void s2s_head_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const int32_t* labels, float* out_loss,
+                      float* out_label_lp) {
+  TrainWs& w = *c->tws;
+  const auto& d = m->d;
+  hipStream_t s = Ln.s;
+  Ln.run(RPR_K_RMSNORM, 0, 8.0 * D.R * D.dm, [&] {
+    return launch_rmsnorm(P<float>(w.x_last), d.dec_final_ln, P<float>(w.hF), D.R, D.dm, D.eps, s, D.post);
+  });
+  Ln.run(RPR_K_OTHER, 2.0 * D.R * (double)D.V * D.dm, 4.0 * ((double)D.R * D.dm + (double)D.L * D.V * D.dm + (double)D.R * D.V), [&] {
+    return launch_s2s_head_fwd(P<float>(w.hF), d.out_embeds, labels, P<float>(w.dlog), P<float>(w.row_loss), out_label_lp, out_loss,
+                               D.bz, D.L, D.dm, D.V, s);
   });
 }
 
@@ -658,8 +681,9 @@ struct BucketHook {
   rpr_grad_bucket_cb cb; void* user; hipStream_t comm; int next = 0;
 };
 
+// ce_head: the seq2seq cross-entropy head (s2s_head_forward ran) instead of the ranking step's gold scores
 void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32_t* ids, const int32_t* mask, float* G,
-              BucketHook* hook = nullptr) {
+              BucketHook* hook = nullptr, bool ce_head = false) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
@@ -698,14 +722,22 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
   float *dxa = P<float>(w.dxa), *dxb = P<float>(w.dxb), *dbig = P<float>(w.dbig), *dattn = P<float>(w.dattn), *h = P<float>(w.h);
   unsigned long long* fix = P<unsigned long long>(w.fix);
 
-  // ---- gold scores: dscore -> (dE rows, dhF) -> final RMSNorm backward
-  Ln.run(RPR_K_OTHER, 0, 0, [&] {   // dE rows go to dxb, dhF to dxa
-    return launch_gold_score_bwd(P<float>(w.x_last), d.dec_final_ln, d.out_embeds, P<int32_t>(w.out_idx), P<float>(w.dscores), dxa, dxb,
-                                 R, dm, D.eps, D.post, s);
-  });
   float* g_out = d.out_embeds != d.in_embeds ? g(K_OUT_EMB) : g(K_IN_EMB);
-  Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dxb, P<int32_t>(w.out_idx), fix, R, dm, s); });
-  Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g_out, (size_t)d.L * D.V * dm, s); });
+  if (ce_head) {
+    // ---- cross-entropy head: dhF_i = dlogits_i E_i -> dxa, dE_i = dlogits_i^T hF_i stored into the codebook gradient (the
+    // flat buffer is zero; with shared codebooks the input-embedding rows are added to it later) -> final RMSNorm backward
+    Ln.run(RPR_K_OTHER, 4.0 * R * (double)D.V * dm, 4.0 * (2.0 * R * D.V + 2.0 * R * dm + 2.0 * (double)D.L * D.V * dm), [&] {
+      return launch_s2s_head_bwd(P<float>(w.hF), d.out_embeds, P<float>(w.dlog), dxa, g_out, D.bz, D.L, dm, D.V, s);
+    });
+  } else {
+    // ---- gold scores: dscore -> (dE rows, dhF) -> final RMSNorm backward
+    Ln.run(RPR_K_OTHER, 0, 0, [&] {   // dE rows go to dxb, dhF to dxa
+      return launch_gold_score_bwd(P<float>(w.x_last), d.dec_final_ln, d.out_embeds, P<int32_t>(w.out_idx), P<float>(w.dscores), dxa, dxb,
+                                   R, dm, D.eps, D.post, s);
+    });
+    Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dxb, P<int32_t>(w.out_idx), fix, R, dm, s); });
+    Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g_out, (size_t)d.L * D.V * dm, s); });
+  }
   B.norm_bwd(P<float>(w.x_last), d.dec_final_ln, dxa, nullptr, dxb, g(K_DEC_FLN), R, D.post);
   float *dx = dxb, *dx2 = dxa;   // dx = gradient w.r.t. the current layer's output stream
   // ---- decoder layers, last to first
@@ -725,7 +757,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
       const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
       float* dxk = P<float>(w.dxkv) + (size_t)i * 2 * inner;
       Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {   // dq into dbig (as [R, inner])
-        return launch_cross_attn_bwd(a.qx, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, 2 * D.L, D.Lq, H, s);
+        return launch_cross_attn_bwd(a.qx, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, D.docs * D.L, D.Lq, H, s);
       });
     }
     if (!saved) B.norm(a.x1, m->dec_ln1[i], R);
@@ -797,6 +829,39 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
   bucket(0, param_offset(m, K_ENC_LN0, 0));   // everything in front of the first layer: final only now
 }
 
+// Checks and workspaces shared by the training passes: docs decoder sequences of L positions per query
+int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, Dims& D) {
+  RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
+  RPR_REQUIRE(bz >= 1 && Lq >= 1 && Lq <= 128, "bz or Lq out of range (the training kernels hold Lq <= 128 keys in LDS)");
+  RPR_REQUIRE(m->d.d_kv == DKV, "the training kernels are written for d_kv == 64 (t5-base / t5-large)");
+  RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_DEC_LEN, "smtid length exceeds the model's decoder length");
+  RPR_HIP(hipSetDevice(c->device));
+  build_params(m);
+  const auto& d = m->d;
+  D.bz = bz; D.Lq = Lq; D.L = L; D.docs = docs; D.S = bz * docs; D.R = D.S * L; D.T = bz * Lq; D.dm = d.d_model; D.inner = m->inner();
+  D.dff = d.d_ff; D.H = d.num_heads; D.ne = d.num_layers; D.nd = d.num_decoder_layers; D.V = d.V; D.xld = D.nd * 2 * D.inner;
+  D.buckets = d.rel_buckets;
+  D.eps = d.layer_norm_eps; D.post = d.scaleup_output_hidden ? (float)pow((double)D.dm, -0.5) : 1.0f;
+  D.enc_stride = (size_t)D.T * (2 * D.dm + 4 * D.inner + D.dff);
+  D.dec_stride = (size_t)D.R * (3 * D.dm + 6 * D.inner + D.dff);
+  RPR_REQUIRE(self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024,
+              "sequence lengths too large for the LDS-resident attention backward");
+  int e = alloc_train(c, m, D);
+  if (e) return e;
+  // the forward's cross-attention kernel needs the per-query key counts: reuse the search workspace's small buffers
+  return ensure(c, c->ws.last, (size_t)bz * 4);
+}
+
+// per pass: fixed-point accumulators and amax slots zeroed, the bf16 weight copies refreshed (bf16 mode)
+int train_begin(Launcher& Ln, rpr_ctx* c, rpr_model* m) {
+  TrainWs& w = *c->tws;
+  RPR_HIP(hipMemsetAsync(w.fix.p, 0, w.fix.cap, Ln.s));
+  amax_reset(Ln);
+  if (c->precision == RPR_PREC_BF16) return refresh_weight_cache(Ln, c, m);
+  w.wc_off.clear(); w.wc_model = nullptr;   // the other modes convert per call
+  return Ln.err;
+}
+
 }  // namespace
 
 void rpr::train_forget_model(rpr_ctx* c, const rpr_model* m) {
@@ -807,7 +872,7 @@ void rpr::train_forget_model(rpr_ctx* c, const rpr_model* m) {
 void rpr::free_train_ws(rpr_ctx* c) {
   if (!c->tws) return;
   TrainWs& w = *c->tws;
-  DevBuf* all[] = {&w.enc_act, &w.dec_act, &w.enc_out, &w.xkv, &w.x_last, &w.scores, &w.margins, &w.dscores, &w.in_idx, &w.out_idx,
+  DevBuf* all[] = {&w.hF, &w.dlog, &w.row_loss, &w.enc_act, &w.dec_act, &w.enc_out, &w.xkv, &w.x_last, &w.scores, &w.margins, &w.dscores, &w.in_idx, &w.out_idx,
                    &w.tok_idx, &w.h, &w.dxa, &w.dxb, &w.dbig, &w.dattn, &w.dxkv, &w.denc, &w.tA, &w.wT, &w.w_part, &w.bias_part,
                    &w.fix, &w.gn_part, &w.gn_out, &w.amax, &w.part, &w.part2, &w.wc, &w.wcT, &w.wseg, &w.wpref, &w.xT, &w.aseg, &w.apref, &w.bfb};
   for (DevBuf* b : all) if (b->p) (void)hipFree(b->p);
@@ -857,39 +922,16 @@ int rpr_lngknp_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_i
                                 void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user) {
   RPR_REQUIRE(c && m && input_ids && attention_mask && doc_codes && teacher_pos && teacher_neg && prefix_lens && out_losses &&
                   flat_grads, "NULL argument");
-  RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
-  RPR_REQUIRE(bz >= 1 && Lq >= 1 && Lq <= 128, "bz or Lq out of range (the training kernels hold Lq <= 128 keys in LDS)");
-  RPR_REQUIRE(m->d.d_kv == DKV, "the training kernels are written for d_kv == 64 (t5-base / t5-large)");
-  RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_DEC_LEN, "smtid length exceeds the model's decoder length");
   RPR_REQUIRE(n_prefix >= 1 && n_prefix <= 8, "n_prefix out of range (1..8)");
-  RPR_HIP(hipSetDevice(c->device));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  build_params(m);
-  const auto& d = m->d;
   Dims D{};
-  D.bz = bz; D.Lq = Lq; D.L = L; D.S = bz * 2; D.R = D.S * L; D.T = bz * Lq; D.dm = d.d_model; D.inner = m->inner(); D.dff = d.d_ff;
-  D.H = d.num_heads; D.ne = d.num_layers; D.nd = d.num_decoder_layers; D.V = d.V; D.xld = D.nd * 2 * D.inner; D.buckets = d.rel_buckets;
-  D.eps = d.layer_norm_eps; D.post = d.scaleup_output_hidden ? (float)pow((double)D.dm, -0.5) : 1.0f;
-  D.enc_stride = (size_t)D.T * (2 * D.dm + 4 * D.inner + D.dff);
-  D.dec_stride = (size_t)D.R * (3 * D.dm + 6 * D.inner + D.dff);
-  RPR_REQUIRE(self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(2 * L, Lq) <= 160 * 1024,
-              "sequence lengths too large for the LDS-resident attention backward");
-  int e = alloc_train(c, m, D);
+  int e = train_setup(c, m, bz, Lq, L, 2, D);
   if (e) return e;
-  // the forward's cross-attention kernel needs the per-query key counts: reuse the search workspace's small buffers
-  e = ensure(c, c->ws.last, (size_t)bz * 4);
-  if (e) return e;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   TrainWs& w = *c->tws;
   RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params_total * sizeof(float), s));
-  RPR_HIP(hipMemsetAsync(w.fix.p, 0, w.fix.cap, s));
   Launcher Ln{c, s};
-  amax_reset(Ln);
-  if (c->precision == RPR_PREC_BF16) {
-    e = refresh_weight_cache(Ln, c, m);
-    if (e) return e;
-  } else {
-    w.wc_off.clear(); w.wc_model = nullptr;   // the other modes convert per call
-  }
+  e = train_begin(Ln, c, m);
+  if (e) return e;
   forward(Ln, c, m, D, input_ids, attention_mask, doc_codes, P<int32_t>(c->ws.last));
   if (Ln.err) return Ln.err;
   RPR_HIP(launch_margin_mse(P<float>(w.scores), teacher_pos, teacher_neg, prefix_lens, n_prefix, bz, L, out_losses, P<float>(w.margins), s));
@@ -898,6 +940,57 @@ int rpr_lngknp_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_i
   BucketHook hook{on_bucket, user, reinterpret_cast<hipStream_t>(comm_stream)};
   backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, on_bucket ? &hook : nullptr);
   return Ln.err;
+}
+
+// ---- seq2seq docid cross-entropy step (reference T5SeqAQEncoderForSeq2Seq, modeling/t5_generative_retriever.py:968-1019) ----
+// The same teacher-forced pass with one decoder sequence per query (decoder_input_ids = [-1, labels[:, :-1]]: the labels are the
+// doc codes of the ranking step) and the cross-entropy head in place of the gold scores.
+static int seq2seq_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lq,
+                       const int32_t* labels, int32_t L, float* out_loss, float* out_label_lp, float* flat_grads, void* stream,
+                       void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user) {
+  RPR_REQUIRE(c && m && input_ids && attention_mask && labels && out_loss, "NULL argument");
+  RPR_REQUIRE(s2s_head_smem_ok(m->d.V) && m->d.d_model % 32 == 0,
+              "the cross-entropy head needs a codebook size V with V % 64 == 0 and V <= 1024, and d_model % 32 == 0");
+  Dims D{};
+  int e = train_setup(c, m, bz, Lq, L, 1, D);
+  if (e) return e;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  {  // labels outside [0, V) would index past a codebook: refused before anything is enqueued (one small copy + synchronisation)
+    std::vector<int32_t> h((size_t)bz * L);
+    RPR_HIP(hipMemcpyAsync(h.data(), labels, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RPR_HIP(hipStreamSynchronize(s));
+    for (int32_t v : h) RPR_REQUIRE(v >= 0 && v < m->d.V, "a label is outside [0, V) of the codebooks");
+  }
+  if (flat_grads) RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params_total * sizeof(float), s));
+  Launcher Ln{c, s};
+  e = train_begin(Ln, c, m);
+  if (e) return e;
+  forward(Ln, c, m, D, input_ids, attention_mask, labels, P<int32_t>(c->ws.last), false);
+  s2s_head_forward(Ln, c, m, D, labels, out_loss, out_label_lp);
+  if (Ln.err || !flat_grads) return Ln.err;
+  BucketHook hook{on_bucket, user, reinterpret_cast<hipStream_t>(comm_stream)};
+  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, on_bucket ? &hook : nullptr, true);
+  return Ln.err;
+}
+
+int rpr_seq2seq_forward(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lq,
+                        const int32_t* labels, int32_t L, float* out_loss, float* out_label_logprob, void* stream) {
+  return seq2seq_run(c, m, input_ids, attention_mask, bz, Lq, labels, L, out_loss, out_label_logprob, nullptr, stream, nullptr, nullptr,
+                     nullptr);
+}
+
+int rpr_seq2seq_backward(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lq,
+                         const int32_t* labels, int32_t L, float* out_loss, float* flat_grads, void* stream) {
+  RPR_REQUIRE(flat_grads, "NULL argument");
+  return seq2seq_run(c, m, input_ids, attention_mask, bz, Lq, labels, L, out_loss, nullptr, flat_grads, stream, nullptr, nullptr, nullptr);
+}
+
+int rpr_seq2seq_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+                                 int32_t Lq, const int32_t* labels, int32_t L, float* out_loss, float* flat_grads, void* stream,
+                                 void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user) {
+  RPR_REQUIRE(flat_grads, "NULL argument");
+  return seq2seq_run(c, m, input_ids, attention_mask, bz, Lq, labels, L, out_loss, nullptr, flat_grads, stream, comm_stream, on_bucket,
+                     user);
 }
 
 int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp_avg, float* exp_avg_sq, int64_t step, float lr,

@@ -1179,10 +1179,193 @@ hipError_t launch_weights_bf16(const WSeg* segs, const int* pref, int nseg, int 
   return hipGetLastError();
 }
 
+// ==== seq2seq docid cross-entropy head (reference T5SeqAQEncoderForSeq2Seq, modeling/t5_generative_retriever.py:968-1019) ====
+// logits[b, i, :] = hF[b, i] E_i^T with hF the decoder's last hidden state (final RMSNorm, times d^-0.5 under
+// scaleup_output_hidden) and E_i the output codebook of position i (the input codebook when shared); loss = mean over the
+// bz * L rows of logsumexp(logits) - logits[label] (nn.CrossEntropyLoss). The head runs in exact fp32 in every precision mode
+// (f32-input MFMA: a k-ordered fmaf chain), the more precise side of the reference's bf16 autocast, as the gold scores of the
+// ranking step. Everything is deterministic: fixed k order in the matrix cores, butterfly wave reductions (every lane ends
+// with the same bits), one block adding the row losses in a fixed order.
+typedef float s2s_f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Forward: one block per (16 rows of position i, position i). Wave w owns columns [w V/4, (w+1) V/4) as NT tiles of 16; the
+// 16 x V logits meet in LDS (64 KB at V = 1024), then every wave takes four rows: max, log-sum-exp, the row loss, the label's
+// log-probability and dlogits = (softmax - onehot) * inv_n. Lane (r = l & 15, q = l >> 4) feeds k = k0 + 4q + j to the j-th
+// MFMA of a 16-wide k step, so A and B are read as float4 along k (the reduction is a sum over all k: any fixed assignment of
+// k to the instruction slots is valid). Requires d % 32 == 0, V % 64 == 0, V / 64 <= NT.
+template <int NT>
+__global__ __launch_bounds__(256) void s2s_head_fwd_kernel(const float* __restrict__ hF, const float* __restrict__ E,
+                                                            const int32_t* __restrict__ labels, float* __restrict__ dlogits,
+                                                            float* __restrict__ row_loss, float* __restrict__ label_lp, int bz, int L,
+                                                            int d, int V, float inv_n) {
+  extern __shared__ __attribute__((aligned(16))) float lg[];   // [16][V + 1]
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, kq = lane >> 4;
+  const int i = blockIdx.y, b0 = blockIdx.x * 16, nt = V >> 6, LD = V + 1;
+  const int b = b0 + r16;
+  const bool rok = b < bz;
+  const float* arow = hF + ((size_t)(rok ? b : 0) * L + i) * d + 4 * kq;
+  const float* Ei = E + (size_t)i * V * d + 4 * kq;
+  s2s_f4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = s2s_f4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < d; k0 += 32) {
+    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+    if (rok) { a0 = *reinterpret_cast<const float4*>(arow + k0); a1 = *reinterpret_cast<const float4*>(arow + k0 + 16); }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (t < nt) {
+        const float* er = Ei + (size_t)((wv * nt + t) * 16 + r16) * d + k0;
+        const float4 e0 = *reinterpret_cast<const float4*>(er), e1 = *reinterpret_cast<const float4*>(er + 16);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, e0.x, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, e0.y, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, e0.z, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, e0.w, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, e1.x, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, e1.y, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, e1.z, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, e1.w, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  // C/D map of the 16 x 16 tile: col = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t < nt) {
+      const int col = (wv * nt + t) * 16 + r16;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lg[(4 * kq + j) * LD + col] = acc[t][j];
+    }
+  }
+  __syncthreads();
+  for (int r = wv; r < 16; r += 4) {
+    const int bb = b0 + r;
+    if (bb >= bz) break;
+    const size_t row = (size_t)bb * L + i;
+    const float* x = lg + r * LD;
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+    m = wave_max_f(m);
+    float se = 0.f;
+    for (int v = lane; v < V; v += 64) se += expf(x[v] - m);
+    se = wave_sum_f(se);
+    const float lse = m + logf(se);
+    int lab = labels[row];
+    lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);   // out-of-range labels are refused by the caller; never read out of bounds
+    float* dl = dlogits + row * V;
+    for (int v = lane; v < V; v += 64) dl[v] = (expf(x[v] - lse) - (v == lab ? 1.f : 0.f)) * inv_n;
+    if (lane == 0) {
+      row_loss[row] = lse - x[lab];
+      if (label_lp) label_lp[row] = x[lab] - lse;
+    }
+  }
+}
+
+// out[0] = (sum of the n row losses in a fixed order) * inv_n: 256 threads add strided shares in double, then a fixed tree
+__global__ __launch_bounds__(256) void s2s_loss_sum_kernel(const float* __restrict__ row_loss, int n, float inv_n, float* __restrict__ out) {
+  __shared__ double part[256];
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < n; r += 256) acc += (double)row_loss[r];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)(part[0] * (double)inv_n);
+}
+
+int s2s_head_smem_ok(int V) { return V % 64 == 0 && V >= 64 && V <= 1024; }
+
+hipError_t launch_s2s_head_fwd(const float* hF, const float* E, const int32_t* labels, float* dlogits, float* row_loss, float* label_lp,
+                               float* loss, int bz, int L, int d, int V, hipStream_t s) {
+  if (!s2s_head_smem_ok(V) || d % 32 != 0 || bz <= 0 || L <= 0) return hipErrorInvalidValue;
+  const float inv_n = 1.0f / (float)((long)bz * L);
+  const dim3 grid((bz + 15) / 16, L);
+  const size_t smem = (size_t)16 * (V + 1) * sizeof(float);
+  if (V <= 256) hipLaunchKernelGGL(s2s_head_fwd_kernel<4>, grid, dim3(256), smem, s, hF, E, labels, dlogits, row_loss, label_lp, bz, L, d, V, inv_n);
+  else hipLaunchKernelGGL(s2s_head_fwd_kernel<16>, grid, dim3(256), smem, s, hF, E, labels, dlogits, row_loss, label_lp, bz, L, d, V, inv_n);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(s2s_loss_sum_kernel, dim3(1), dim3(256), 0, s, row_loss, bz * L, 1.0f / (float)((long)bz * L), loss);
+  return hipGetLastError();
+}
+
+// Backward products of the head, batched over the L positions (blockIdx.z = position): C_z[m][n] = sum_k A_z(m, k) B_z(k, n),
+// A_z(m, k) = A[z sa_z + m sa_m + k sa_k], B_z(k, n) = B[z sb_z + k sb_k + n] (n contiguous), C_z[m][n] = C[z sc_z + m sc_m + n].
+//   dH_i = dlogits_i E_i:    m = query b, k = code v, n = feature c (A rows are contiguous in k: AK = true)
+//   dE_i = dlogits_i^T hF_i: m = code v, k = query b, n = feature c (A contiguous in m)
+// A block is 32 x 128 of C (2 x 2 waves of 16 x 64, four 16 x 16 tiles each); lane (r, q) feeds k = k0 + 4q + j to the j-th
+// MFMA of a 16-wide k step. Every element of C is written by exactly one lane (a store, no accumulation): deterministic.
+template <bool AK>
+__global__ __launch_bounds__(256) void s2s_head_bwd_gemm_kernel(const float* __restrict__ A, size_t sa_z, size_t sa_m, size_t sa_k,
+                                                                 const float* __restrict__ B, size_t sb_z, size_t sb_k,
+                                                                 float* __restrict__ C, size_t sc_z, size_t sc_m, int M, int N, int K) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, kq = lane >> 4;
+  const int z = blockIdx.z, m = blockIdx.y * 32 + (wv >> 1) * 16 + r16, n0 = blockIdx.x * 128 + (wv & 1) * 64;
+  const bool mok = m < M;
+  const float* a = A + (size_t)z * sa_z + (size_t)(mok ? m : 0) * sa_m;
+  const float* bz_ = B + (size_t)z * sb_z;
+  s2s_f4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = s2s_f4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < K; k0 += 16) {
+    const int kb = k0 + 4 * kq;
+    float av[4];
+    if (AK && kb + 3 < K) {
+      const float4 a4 = mok ? *reinterpret_cast<const float4*>(a + kb) : make_float4(0.f, 0.f, 0.f, 0.f);
+      av[0] = a4.x; av[1] = a4.y; av[2] = a4.z; av[3] = a4.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) av[j] = (mok && kb + j < K) ? a[(size_t)(kb + j) * sa_k] : 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int n = n0 + t * 16 + r16;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float bv = (n < N && kb + j < K) ? bz_[(size_t)(kb + j) * sb_k + n] : 0.f;
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  const int mr = blockIdx.y * 32 + (wv >> 1) * 16 + 4 * kq;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int n = n0 + t * 16 + r16;
+    if (n >= N) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (mr + j < M) C[(size_t)z * sc_z + (size_t)(mr + j) * sc_m + n] = acc[t][j];
+  }
+}
+
+hipError_t launch_s2s_head_bwd(const float* hF, const float* E, const float* dlogits, float* dH, float* dE, int bz, int L, int d, int V,
+                               hipStream_t s) {
+  if (!s2s_head_smem_ok(V) || d % 32 != 0 || bz <= 0 || L <= 0) return hipErrorInvalidValue;
+  const size_t Ld = (size_t)L * d, LV = (size_t)L * V, Vd = (size_t)V * d;
+  // dH[b L + i][c] = sum_v dlogits[b L + i][v] E_i[v][c]
+  hipLaunchKernelGGL(s2s_head_bwd_gemm_kernel<true>, dim3((d + 127) / 128, (bz + 31) / 32, L), dim3(256), 0, s, dlogits, (size_t)V, LV,
+                     (size_t)1, E, Vd, (size_t)d, dH, (size_t)d, Ld, bz, d, V);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // dE_i[v][c] = sum_b dlogits[b L + i][v] hF[b L + i][c]
+  hipLaunchKernelGGL(s2s_head_bwd_gemm_kernel<false>, dim3((d + 127) / 128, (V + 31) / 32, L), dim3(256), 0, s, dlogits, (size_t)V,
+                     (size_t)1, LV, hF, (size_t)d, Ld, dE, Vd, (size_t)d, V, d, bz);
+  return hipGetLastError();
+}
+
 hipError_t init_train_kernel_attributes() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(rmsnorm_bf16_T_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(s2s_head_fwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }

@@ -876,6 +876,70 @@ def lngknp_backward(model: DeviceModel, state: TrainState, input_ids, attention_
     return losses
 
 
+# ---- seq2seq docid cross-entropy step (loss_type t5seq_aq_encoder_seq2seq; reference T5SeqAQEncoderForSeq2Seq) -----------
+def _s2s_args(model: DeviceModel, input_ids, attention_mask, labels):
+    dev = model.ctx.device
+    ids = input_ids.to(device=dev, dtype=torch.int32).contiguous()
+    mask = attention_mask.to(device=dev, dtype=torch.int32).contiguous()
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    bz, Lq = ids.shape
+    if lab.dim() != 2 or lab.shape[0] != bz:
+        raise ValueError(f"labels must be [bz, L] with bz = {bz}, got {tuple(lab.shape)}")
+    if Lq > 128:
+        raise ValueError(f"queries of {Lq} tokens: the training kernels hold at most 128 encoder positions (use max_length <= 128)")
+    return ids, mask, lab, bz, Lq, int(lab.shape[1])
+
+
+def seq2seq_forward(model: DeviceModel, input_ids: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor):
+    """Forward of the seq2seq docid step (``rpr_seq2seq_forward``): teacher-forced decoder over ``[-1, labels[:, :-1]]``,
+    per-position codebook logits, cross-entropy. Returns ``(loss float32 [1], label_logprobs float32 [bz, L])``, device
+    tensors, asynchronous on the current stream (after the host-side label check, which synchronises it)."""
+    ctx = model.ctx
+    ids, mask, lab, bz, Lq, L = _s2s_args(model, input_ids, attention_mask, labels)
+    loss = torch.empty((1,), dtype=torch.float32, device=ctx.device)
+    lp = torch.empty((bz, L), dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.rpr_seq2seq_forward(ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lq, lab.data_ptr(), L,
+                                      loss.data_ptr(), lp.data_ptr(), _stream_ptr(ctx.device)), "rpr_seq2seq_forward")
+    return loss, lp
+
+
+def seq2seq_backward(model: DeviceModel, state: TrainState, input_ids, attention_mask, labels,
+                     exchange: Optional[GradExchange] = None) -> torch.Tensor:
+    """Forward + backward of the seq2seq cross-entropy (``rpr_seq2seq_backward``): fills ``state.grads`` and returns the loss
+    ``[1]`` (device tensor). With ``exchange`` the gradient buckets are handed over as in :func:`lngknp_backward`."""
+    ctx = model.ctx
+    ids, mask, lab, bz, Lq, L = _s2s_args(model, input_ids, attention_mask, labels)
+    loss = torch.empty((1,), dtype=torch.float32, device=ctx.device)
+    if exchange is not None and exchange.active:
+        check(ctx.lib.rpr_seq2seq_backward_buckets(ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lq, lab.data_ptr(), L,
+                                                   loss.data_ptr(), state.grads.data_ptr(), _stream_ptr(ctx.device),
+                                                   exchange.comm_stream_ptr(), exchange.callback(), None),
+              "rpr_seq2seq_backward_buckets")
+        exchange.raise_pending()
+    else:
+        check(ctx.lib.rpr_seq2seq_backward(ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lq, lab.data_ptr(), L,
+                                           loss.data_ptr(), state.grads.data_ptr(), _stream_ptr(ctx.device)), "rpr_seq2seq_backward")
+    return loss
+
+
+def seq2seq_train_step(model: DeviceModel, state: TrainState, input_ids, attention_mask, labels, lr: float, betas=(0.9, 0.999),
+                       eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 1.0) -> torch.Tensor:
+    """:func:`train_step` for the seq2seq cross-entropy: backward with the gradient exchange (bucketed and overlapped unless
+    ``RPR_GRAD_OVERLAP=0``), clip_grad_norm_, AdamW. Returns the loss ``[1]`` before the update."""
+    import os
+    if os.environ.get("RPR_GRAD_OVERLAP", "1") == "0":
+        loss = seq2seq_backward(model, state, input_ids, attention_mask, labels)
+        allreduce_grads(state)
+    else:
+        ex = getattr(state, "_exchange", None)
+        if ex is None or ex.grads is not state.grads:
+            ex = state._exchange = GradExchange(state.grads)
+        loss = seq2seq_backward(model, state, input_ids, attention_mask, labels, exchange=ex)
+        ex.finish()
+    adamw_step(model, state, lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    return loss
+
+
 def allreduce_grads(state: TrainState, bucket_elems: int = 64 << 20) -> None:
     """Serial data-parallel gradient exchange (``RPR_GRAD_OVERLAP=0``; the default is :class:`GradExchange`, overlapped
     with the backward pass): sum ``state.grads`` over the ranks in a few large chunks after the backward and divide by

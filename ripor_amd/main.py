@@ -1,7 +1,9 @@
-"""``python -m t5_pretrainer.main`` for the one training task on this repository's path: the prefix-oriented ranking
+"""``python -m t5_pretrainer.main`` for the two training tasks on this repository's path: the prefix-oriented ranking
 fine-tune (``--loss_type=t5seq_aq_encoder_lng_knp_margin_mse``; reference main.py:68-74, 93-94, 127-186 and
-full_scripts/full_lng_knp_train_pipline.sh:80-99). Same flags as the reference's ``Arguments`` as far as that task reads
-them; every other loss type is out of scope and refused.
+full_scripts/full_lng_knp_train_pipline.sh:80-99) and the seq2seq docid step that teaches the model to generate docids
+(``--loss_type=t5seq_aq_encoder_seq2seq``; reference main.py:75-79, 91-92 and full_16_1024_scripts/full_train_t5seq_aq_encoder.sh).
+Same flags as the reference's ``Arguments`` as far as those tasks read them; every other loss type is out of scope
+ and refused.
 
 One process per GPU (``torchrun --nproc-per-node N -m t5_pretrainer.main ...``): ``torch.distributed`` backend "nccl" = RCCL;
 the gradient exchange is bucketed and overlapped with the backward inside ``training_step``."""
@@ -20,9 +22,12 @@ def get_args(argv=None):
     ap.add_argument("--model_type", default="t5_docid_gen_encoder")
     ap.add_argument("--model_name_or_path", default="t5-base", help="tokenizer source (a directory works offline)")
     ap.add_argument("--pretrained_path", required=True)
-    ap.add_argument("--teacher_score_path", required=True)
+    ap.add_argument("--teacher_score_path", default=None, help="lng_knp: the examples with teacher scores (required there)")
     ap.add_argument("--collection_path", default=None)
-    ap.add_argument("--queries_path", required=True)
+    ap.add_argument("--queries_path", default=None, help="lng_knp: the query collection directory (required there)")
+    ap.add_argument("--query_to_docid_path", default=None, help="seq2seq: jsonl of {\"docid\", \"query\"} (required there)")
+    ap.add_argument("--multi_vocab_sizes", action="store_true",
+                    help="seq2seq: per-position mean of the cross-entropy (the same value with one codebook size for every position)")
     ap.add_argument("--docid_to_smtid_path", default=None)
     ap.add_argument("--smtid_as_docid", action="store_true")
     ap.add_argument("--output_dir", required=True)
@@ -49,22 +54,37 @@ def get_args(argv=None):
 def main(argv=None):
     import torch.distributed as dist
     from .dataset.lng_knp import LngKnpMarginMSEforT5SeqAQCollator, LngKnpMarginMSEforT5SeqAQDataset
-    from .modeling.t5_generative_retriever import T5SeqAQEncoderForLngKnpMarginMSE
+    from .modeling.t5_generative_retriever import T5SeqAQEncoderForLngKnpMarginMSE, T5SeqAQEncoderForSeq2Seq
     from .tasks.trainer import LngKnpTrainer, LngKnpTrainingArgs
     args = get_args(argv)
-    if args.loss_type != "t5seq_aq_encoder_lng_knp_margin_mse" or args.model_type != "t5_docid_gen_encoder":
+    built = ("t5seq_aq_encoder_lng_knp_margin_mse", "t5seq_aq_encoder_seq2seq")
+    if args.loss_type not in built or args.model_type != "t5_docid_gen_encoder":
         raise NotImplementedError(f"loss_type {args.loss_type!r} is outside this repository's path (SURVEY.md §2); "
-                                  "built: t5seq_aq_encoder_lng_knp_margin_mse")
+                                  f"built: {', '.join(built)}")
+    seq2seq = args.loss_type == "t5seq_aq_encoder_seq2seq"
+    need = ("query_to_docid_path", "docid_to_smtid_path") if seq2seq else ("teacher_score_path", "queries_path")
+    missing = [f"--{n}" for n in need if not getattr(args, n)]
+    if missing:
+        raise SystemExit(f"{args.loss_type} needs {' and '.join(missing)}")
     local_rank = max(0, int(args.local_rank if args.local_rank >= 0 else os.environ.get("LOCAL_RANK", 0)))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local_rank)
         dist.init_process_group(backend=os.environ.get("RPR_DIST_BACKEND", "nccl"))
-    dataset = LngKnpMarginMSEforT5SeqAQDataset(dataset_path=args.teacher_score_path, document_dir=args.collection_path,
-                                               query_dir=args.queries_path, docid_to_smtid_path=args.docid_to_smtid_path,
-                                               smtid_as_docid=args.smtid_as_docid)
-    collator = LngKnpMarginMSEforT5SeqAQCollator(args.model_name_or_path, max_length=args.max_length)
-    model = T5SeqAQEncoderForLngKnpMarginMSE.from_pretrained(args.resume_from_checkpoint or args.pretrained_path)
+    if seq2seq:
+        from .dataset.seq2seq import Seq2SeqForT5SeqAQCollator, Seq2SeqForT5SeqAQDataset
+        if args.max_length > 128:
+            raise SystemExit(f"--max_length {args.max_length}: the training kernels hold at most 128 query tokens")
+        dataset = Seq2SeqForT5SeqAQDataset(example_path=args.query_to_docid_path, docid_to_smtid_path=args.docid_to_smtid_path)
+        collator = Seq2SeqForT5SeqAQCollator(args.model_name_or_path, max_length=args.max_length)
+        model = T5SeqAQEncoderForSeq2Seq.from_pretrained(args.resume_from_checkpoint or args.pretrained_path,
+                                                         multi_vocab_sizes=args.multi_vocab_sizes)
+    else:
+        dataset = LngKnpMarginMSEforT5SeqAQDataset(dataset_path=args.teacher_score_path, document_dir=args.collection_path,
+                                                   query_dir=args.queries_path, docid_to_smtid_path=args.docid_to_smtid_path,
+                                                   smtid_as_docid=args.smtid_as_docid)
+        collator = LngKnpMarginMSEforT5SeqAQCollator(args.model_name_or_path, max_length=args.max_length)
+        model = T5SeqAQEncoderForLngKnpMarginMSE.from_pretrained(args.resume_from_checkpoint or args.pretrained_path)
     model.to(local_rank)
     targs = LngKnpTrainingArgs(output_dir=args.output_dir, learning_rate=args.learning_rate, warmup_ratio=args.warmup_ratio,
                                per_device_train_batch_size=args.per_device_train_batch_size, num_train_epochs=args.epochs,
@@ -74,7 +94,8 @@ def main(argv=None):
     os.makedirs(args.output_dir, exist_ok=True)
     trainer = LngKnpTrainer(model, dataset, collator, targs)
     if trainer.rank == 0:
-        print(f"lng_knp fine-tune: {len(dataset)} examples, {trainer.world} rank(s) x {targs.per_device_train_batch_size}, "
+        what = "seq2seq docid step" if seq2seq else "lng_knp fine-tune"
+        print(f"{args.loss_type} ({what}): {len(dataset)} examples, {trainer.world} rank(s) x {targs.per_device_train_batch_size}, "
               f"{trainer.max_steps} steps ({trainer.warmup_steps} warm-up), lr {targs.learning_rate}, "
               f"{'bf16' if targs.bf16 else 'fp32-equivalent'} GEMMs")
     trainer.train(resume_from_checkpoint=args.resume_from_checkpoint or None)

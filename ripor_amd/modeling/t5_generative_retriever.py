@@ -331,3 +331,62 @@ class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
                               max_grad_norm=max_grad_norm)
         losses = {n: losses[i] for i, n in enumerate(names)}
         return losses
+
+
+class T5SeqAQEncoderForSeq2Seq(T5SeqAQEncoder):
+    """reference :968-1019 — the seq2seq docid step (loss_type ``t5seq_aq_encoder_seq2seq``, the first stage of RIPOR's docid
+    training): cross-entropy of the per-position codebook logits ``h[:, i] @ E_i^T`` against the docid codes, ``forward(**inputs)
+    -> {"rank": loss}`` on the batches of ``Seq2SeqForT5SeqAQCollator``. The whole pass runs in ``rpr_seq2seq_forward`` /
+    ``rpr_seq2seq_backward`` (engine.py); no autograd graph is attached to the returned loss. ``multi_vocab_sizes`` is accepted:
+    every position has the same codebook size here, where the reference's per-position mean divided by L is the same value."""
+
+    def __init__(self, model_name_or_path, shared_output_input_embeds=None, multi_vocab_sizes=False):
+        super().__init__(model_name_or_path, shared_output_input_embeds, multi_vocab_sizes)
+        self.multi_vocab_sizes = bool(multi_vocab_sizes)
+
+    def _batch(self, inputs):
+        tq, labels = inputs["tokenized_query"], inputs["labels"]
+        if labels.dim() != 2:
+            raise ValueError(f"labels must be [bz, smtid_length], got {tuple(labels.shape)}")
+        V = list(self.config.decoder_vocab_sizes)
+        if labels.size(1) > len(V):
+            raise ValueError(f"smtid length {labels.size(1)} exceeds the model's {len(V)} codebooks")
+        if int(labels.min()) < 0 or int(labels.max()) >= min(V[: labels.size(1)]):
+            raise ValueError(f"labels outside [0, {min(V[: labels.size(1)])}) of the codebooks")
+        di = tq["decoder_input_ids"]
+        start = torch.full((labels.size(0), 1), -1, dtype=labels.dtype)
+        if tuple(di.shape) != tuple(labels.shape) or not torch.equal(di.cpu().long(),
+                                                                     torch.cat([start, labels[:, :-1]], 1).cpu().long()):
+            raise ValueError("decoder_input_ids must be [-1, labels[:, :-1]] (dataset.py:527-550)")
+        return tq["input_ids"], tq["attention_mask"], labels
+
+    def forward(self, **inputs):
+        from .. import engine as E
+        ids, mask, labels = self._batch(inputs)
+        loss, self.last_label_logprobs = E.seq2seq_forward(self.base_model.engine_model(), ids, mask, labels)
+        return {"rank": loss[0]}
+
+    __call__ = forward
+
+    def train_state(self):
+        from .. import engine as E
+        if getattr(self, "_train_state", None) is None or self._train_state.model is not self.base_model.engine_model():
+            self._train_state = E.TrainState(self.base_model.engine_model())
+        return self._train_state
+
+    def backward(self, **inputs):
+        """loss.backward() of ``forward``: fills ``train_state().grads``; returns ``{"rank": loss}``."""
+        from .. import engine as E
+        ids, mask, labels = self._batch(inputs)
+        loss = E.seq2seq_backward(self.base_model.engine_model(), self.train_state(), ids, mask, labels)
+        return {"rank": loss[0]}
+
+    def training_step(self, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **inputs):
+        """One optimisation step (same contract as ``T5SeqAQEncoderForLngKnpMarginMSE.training_step``): backward with the
+        data-parallel gradient exchange overlapped, clip_grad_norm_, AdamW in place on the device. Returns ``{"rank": loss}``
+        of the batch before the update."""
+        from .. import engine as E
+        ids, mask, labels = self._batch(inputs)
+        loss = E.seq2seq_train_step(self.base_model.engine_model(), self.train_state(), ids, mask, labels, lr, betas=betas, eps=eps,
+                                    weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        return {"rank": loss[0]}

@@ -1,1 +1,2 @@
 from ripor_amd.dataset.lng_knp import *  # noqa: F401,F403
+from ripor_amd.dataset.seq2seq import Seq2SeqForT5SeqAQDataset  # noqa: F401

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Time the ranking fine-tune step (BASELINE config 5): t5-base dims, bz examples per step PER GPU, two teacher-forced
 passes of L = 32 positions over queries of ~16 tokens, backward, gradient all-reduce (RCCL when launched on several
-ranks), AdamW. Rank 0 prints one JSON line (examples/s of the whole job, max step time over the ranks).
-Usage: python tools/train_bench.py [--bz 128] [--steps 5]
+ranks), AdamW. --loss seq2seq: the seq2seq docid cross-entropy step instead (one teacher-forced pass per query, the
+codebook-logit head). Rank 0 prints one JSON line (examples/s of the whole job, max step time over the ranks).
+Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq]
        python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/train_bench.py"""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -15,6 +16,7 @@ ap.add_argument("--bz", type=int, default=128)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--len", type=int, default=32, dest="L")
 ap.add_argument("--precision", default="f16x2", choices=["f16x2", "f32", "bf16"])
+ap.add_argument("--loss", default="lngknp", choices=["lngknp", "seq2seq"])
 args = ap.parse_args()
 L, V, bz = args.L, 256, args.bz
 dims = synth.t5_base_dims(L=L, V=V)
@@ -39,7 +41,12 @@ tn = torch.from_numpy(np.stack([synth.uniform_f32(f"tb/n{k}", (bz,), 30.0) for k
 ids_t, mask_t, codes_t = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cuda(), torch.from_numpy(codes).cuda()
 
 
+labels_t = codes_t[:, 0].contiguous()   # seq2seq: one smtid per query
+
+
 def step():   # backward with the bucketed gradient exchange overlapped (RPR_GRAD_OVERLAP=0: serial), clip, AdamW
+    if args.loss == "seq2seq":
+        return E.seq2seq_train_step(model, state, ids_t, mask_t, labels_t, lr=1e-6)
     return E.train_step(model, state, ids_t, mask_t, codes_t, tp, tn, prefix, lr=1e-6)
 
 
@@ -56,12 +63,18 @@ dt = (time.perf_counter() - t0) / args.steps
 if world > 1:
     t = torch.tensor([dt], device="cuda"); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t)
 ctx.profile_reset(); ctx.profile_enable(True)
-E.lngknp_backward(model, state, ids_t, mask_t, codes_t, tp, tn, prefix); torch.cuda.synchronize()
+if args.loss == "seq2seq":
+    E.seq2seq_backward(model, state, ids_t, mask_t, labels_t)
+else:
+    E.lngknp_backward(model, state, ids_t, mask_t, codes_t, tp, tn, prefix)
+torch.cuda.synchronize()
 st = ctx.profile_get(); ctx.profile_enable(False)
 flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * 768 * 768 + 2 * 768 * 3072) + 12 * 2 * 768 * 768)
-                   + bz * 2 * L * 12 * (6 * 768 * 768 + 2 * 768 * 3072))
+                   + bz * (1 if args.loss == "seq2seq" else 2) * L * 12 * (6 * 768 * 768 + 2 * 768 * 3072)
+                   + (bz * L * V * 768 if args.loss == "seq2seq" else 0))
 if rank == 0:
-  print(json.dumps({"task": "lng_knp margin-MSE fine-tune step (forward + backward + gradient all-reduce + AdamW), t5-base dims",
+  task = ("seq2seq docid cross-entropy step" if args.loss == "seq2seq" else "lng_knp margin-MSE fine-tune step")
+  print(json.dumps({"task": task + " (forward + backward + gradient all-reduce + AdamW), t5-base dims", "loss": args.loss,
                   "gemm_precision": args.precision, "n_gpus": world, "scaling": "weak", "bz_per_gpu": bz,
                   "bz": bz, "L": L, "enc_len_padded": int(Lq), "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
                   "loss_first": [float(x) for x in first], "loss_last": [float(x) for x in last],
