@@ -8,9 +8,14 @@ Inputs (token ids / masks of every step's batch, weights, trie) are resident in 
 timed region. value = queries/s over all ranks (weak scaling: every rank runs K steps of Q queries
 on its own shard, model + trie replicated, one RCCL all_gather of the ranked results at the end).
 
-  python bench.py [--gpus N --steps K --warmup W --batch Q --beams B --len L --docs N_DOCS --dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W --batch Q --beams B --len L --docs N_DOCS --dump-outputs DIR] [--full]
 
-Extra legs on rank 0 (outside the timed region):
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the JSON line. --full adds
+everything else, all outside the timed region: the same K steps again with the PCIe legs inside (value_pcie_inclusive),
+the exact-fp32 step, the secondary legs (--secondary) and the two legs below; --no-roofline, --no-exact-fp32 and
+--no-cpu-baseline leave single ones out.
+
+Extra legs of --full on rank 0:
   roofline     one eager step of the TIMED configuration with hipEvents around every launch on the stream it is
                launched on (the library's profile mode; nothing synchronises while the step is enqueued, so the two
                lanes run side by side as in the timed region); the dominant kernel is the split-precision 256x256
@@ -592,6 +597,7 @@ def secondary_train_step(E, synth, ctx, dev, world, rank, bz=128, L=32, steps=5,
     return out
 
 
+DEFAULT_SECONDARY = "train,config4,f2,rankdata_ref_flags,skew,latency,beam1000,small_batch,heavy_tail,v1024"
 DUMP_LIMIT_BYTES = 64 << 20
 
 
@@ -648,8 +654,13 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--train-steps", type=int, default=5, dest="train_steps", help="timed steps of the secondary train legs")
     ap.add_argument("--train-bz", type=int, default=128, dest="train_bz", help="examples per GPU and step of the secondary train legs")
-    ap.add_argument("--secondary", default="train,config4,f2,rankdata_ref_flags,skew,latency,beam1000,small_batch,heavy_tail,v1024",
-                    help="comma list of secondary legs to append to the JSON line (train = BASELINE config 5 step, config4 = "
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg as well: the PCIe-inclusive timed loop, the roofline / per-kernel "
+                         "profile passes and board power, the exact-fp32 step, the CPU baseline and the secondary legs; off by "
+                         "default, so that a plain run does only what its headline figure needs")
+    ap.add_argument("--secondary", default=None,
+                    help="with --full: comma list of secondary legs to append to the JSON line (default "
+                         f"{DEFAULT_SECONDARY}; train = BASELINE config 5 step, config4 = "
                          "t5-large beam 100, f2 = prefix search at topk 100, skew = clustered trie, latency = one query at beams 10 and "
                          "1000, t5_3b = opt-in: t5-3b dims at beam 10); '' = none. config4 / f2 / skew / latency run at --gpus 1 only, train on every rank (its gradient all-reduce is the RCCL leg)")
     ap.add_argument("--log-softmax", action="store_true", dest="log_softmax",
@@ -670,6 +681,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.secondary and not args.full:
+        ap.error("--secondary needs --full: a plain run stops at the headline")
 
     relaunch = launch_command(args.gpus, os.environ, sys.argv)
     if relaunch is not None:   # `python bench.py --gpus N` without a launcher: become N ranks (one per GPU)
@@ -796,9 +809,13 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
 
-        # Second timed loop, same K steps, with the boundary's PCIe legs inside (SURVEY §8d wording of the metric): ids and
-        # mask start in pinned host memory, results end in pinned host memory. Reported as value_pcie_inclusive; `value`
-        # stays the resident-input rate.
+        if not args.full:
+            status_flags = ctx.status(clear=True)   # sticky saturation / empty-query word over everything run so far
+            return elapsed, None, status_flags, results, (tok if world > 1 else None), (sc if world > 1 else None)
+
+        # Second timed loop (--full), same K steps, with the boundary's PCIe legs inside (SURVEY §8d wording of the metric):
+        # ids and mask start in pinned host memory, results end in pinned host memory. Reported as value_pcie_inclusive;
+        # `value` stays the resident-input rate.
         host_in = [(b[0].cpu().pin_memory(), b[1].cpu().pin_memory()) for b in batches[W:W + K]]
         host_out = None
         torch.cuda.synchronize()
@@ -845,7 +862,7 @@ def main():
         ctx.set_forced_tail(1)
         elapsed, elapsed_pcie, status_flags, results, tok, sc = timed_region()
 
-    fork_stats = ctx.last_fork_stats()   # of the last search (the PCIe-inclusive loop's last step: same shapes)
+    fork_stats = ctx.last_fork_stats()   # of the last search (the last timed step, or with --full the PCIe-inclusive loop's: same inputs)
     # sanity on the timed outputs: every returned smtid of the last step is a trie leaf range
     last = results[-1]
     n_leaf = int((last.row_hi > last.row_lo).sum().item())
@@ -869,7 +886,7 @@ def main():
             "value": value, "unit": "queries/s", "n_gpus": world, "steps": K, "warmup": W,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32" if args.precision == "f32" else "f32 via f16x2-split MFMA (fp32 accumulate)", "data": "synthetic",
-            "value_pcie_inclusive": world * Q * K / elapsed_pcie,
+            "full": args.full,
             "rccl_world_size": dist.get_world_size() if world > 1 else 1,
             "dist_backend": dist.get_backend() if world > 1 else None,
             "gather_bytes_per_rank": int(tok.numel() * tok.element_size() + sc.numel() * sc.element_size()) if world > 1 else 0,
@@ -897,6 +914,8 @@ def main():
                             "note": "vs_native_f32_mfma_peak > 1: the 3-pass f16 split runs fp32-equivalent products faster than "
                                     "v_mfma_f32_32x32x2_f32 could at its 157 TF/s peak"},
         }
+        if elapsed_pcie is not None:
+            out["value_pcie_inclusive"] = world * Q * K / elapsed_pcie
         fk = out["forced_tail"].get("forks_last_step") or []
         if args.forced_tail and fk:
             fb, ff = algorithmic_forced_tail_per_query(dims, Q, B, L, lq_alg, fk[0]["depth"])
@@ -906,7 +925,7 @@ def main():
                 "note": "the algorithm the timed region runs (first fork only): fewer bytes than §8(d) — no per-step self-KV "
                         "re-reads past the fork, the decoder weights streamed fork_depth + 1 times instead of len times"}
         log(f"[bench] timed region done: {value:.1f} queries/s, {ms_per_step:.1f} ms/step")
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             def profiled_step():
                 ctx.profile_reset()
                 ctx.profile_enable(True)
@@ -1089,7 +1108,7 @@ def main():
                 except Exception:
                     pass
                 out["roofline_hbm_attention"] = hk
-        if world == 1 and not args.no_roofline:
+        if args.full and world == 1 and not args.no_roofline:
             try:
                 out["board_power"] = board_power_under(lambda: run_step(W))
                 if out["board_power"]:
@@ -1099,7 +1118,7 @@ def main():
                     out["board_power"]["energy_note"] = "power_w_mean x ms_per_step / queries per step (sampled power, not an energy counter)"
             except Exception as e:
                 out["board_power"] = {"error": repr(e)}
-        if world == 1 and args.precision != "f32" and not args.no_exact_fp32:
+        if args.full and world == 1 and args.precision != "f32" and not args.no_exact_fp32:
             # secondary figure: the same step on the exact fp32 MFMA GEMMs (v_mfma_f32_32x32x2_f32), 1 warm-up + 5 timed
             ctx.set_precision("f32")
             run_step(W); torch.cuda.synchronize()
@@ -1112,15 +1131,15 @@ def main():
             ctx.set_precision("f16x2")
             out["exact_fp32"] = {"value": Q / dt, "unit": "queries/s", "ms_per_step": dt * 1e3, "steps": n_fp32,
                                  "dtype": "f32 (exact fp32 MFMA GEMMs)", "tail_leftover": bool(ctx.status(clear=True) & 4)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(sd, dims, B, L)
             except Exception as e:  # the baseline is reported, never required for the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "queries/s", "cores": len(os.sched_getaffinity(0)),
                                        "kind": "port", "sample": f"failed: {e!r}"}
-    # ---- secondary legs: the other BASELINE configurations (see the helpers above). `train` runs on every rank (its
+    # ---- secondary legs (--full): the other BASELINE configurations (see the helpers above). `train` runs on every rank (its
     # gradient all-reduce is a collective), the search legs on a single-GPU run only.
-    legs = [x for x in args.secondary.split(",") if x]
+    legs = [x for x in (DEFAULT_SECONDARY if args.secondary is None else args.secondary).split(",") if x] if args.full else []
     sec = {}
 
     def leg(name, fn):
@@ -1160,7 +1179,8 @@ def main():
         if "t5_3b" in legs and args.model == "t5-base":
             leg("t5_3b", lambda: secondary_t5_3b(E, synth, ctx, trie, dev, L))
     if rank == 0:
-        out["secondary"] = sec
+        if args.full:
+            out["secondary"] = sec
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

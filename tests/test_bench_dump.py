@@ -64,3 +64,9 @@ def test_dump_samples_the_same_queries_under_the_size_limit(tmp_path):
 def test_bench_refuses_an_empty_timed_region(flags):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + flags, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_bench_secondary_legs_need_full():
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--secondary", "latency"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0 and "--secondary needs --full" in r.stderr

@@ -141,6 +141,20 @@ def test_bench_two_ranks_on_one_gpu_through_gloo():
     print("[bench x2 gloo]", d["value"], d["forced_tail"])
 
 
+def test_plain_bench_run_stops_at_the_headline(tmp_path):
+    """Without --full, bench.py times the steps, dumps the outputs and prints the line: none of the legs of --full run."""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--docs", "200000",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["full"] is False and d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1
+    moved = ("value_pcie_inclusive", "roofline", "kernel_breakdown_ms", "board_power", "exact_fp32", "cpu_baseline", "secondary")
+    assert not [k for k in moved if k in d], d.keys()
+    assert "[bench] secondary" not in r.stderr and "[bench] roofline leg done" not in r.stderr
+    assert np.load(tmp_path / "tokens.npy").shape == (64, 10, 32)
+
+
 # Ranks of the multi-rank rehearsal. They all share the one GPU of the test box, and so does this pytest process: at most six
 # processes may have the device open at a time, so the rehearsal runs 4 ranks (5 processes) instead of a node's 8.
 RANKS = 4
@@ -164,7 +178,7 @@ def test_multi_rank_rehearsal_of_the_scaling_bench_and_the_cli(tmp_path):
     env = dict(os.environ, RPR_BENCH_BACKEND="gloo", RPR_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={RANKS}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(repo, "bench.py"), "--gpus", str(RANKS), "--steps", "1", "--warmup", "1",
-           "--batch", "64", "--docs", "200000", "--no-roofline", "--no-cpu-baseline", "--no-exact-fp32",
+           "--batch", "64", "--docs", "200000", "--full", "--no-roofline", "--no-cpu-baseline", "--no-exact-fp32",
            "--secondary", "train,train_f16x2_only", "--train-steps", "1", "--train-bz", "8"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=repo)
     assert r.returncode == 0, r.stderr[-3000:]

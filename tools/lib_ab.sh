@@ -9,7 +9,7 @@ for rep in 1 2; do
   for which in new old; do
     if [ $which = old ]; then cp $OLD ripor_amd/libripor_hip.so; else cp /tmp/new.so ripor_amd/libripor_hip.so; fi
     echo "== $which rep$rep: $(timeout 300 python tools/gemm_bench.py 21760 2>/dev/null | tail -1)"
-    timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-exact-fp32 --secondary "" 2>/dev/null | tail -1 | python -c "
+    timeout 600 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-exact-fp32 --secondary "" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('   bench', round(d['value'],1), 'q/s', round(d['roofline']['avg_launch_us'],1), 'us/launch')"
   done

@@ -2,12 +2,13 @@
 # Run on the GPU box (via gpurun) from the repo root: bench line, rocprofv3 kernel stats, HBM traffic PMC passes.
 # Usage: tools/profile_round.sh rNN [extra bench args]
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-rXX}; shift || true
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py $*"
-# 1. plain bench (with cpu_baseline)
+B="python $REPO/bench.py --full $*"   # --full: every pass below also times the PCIe-inclusive loop (steps_in_pmc_pass)
+# 1. bench with every leg (cpu_baseline, roofline, secondary)
 timeout 600 $B > $OUT/bench.json 2> $OUT/bench.log
 # 2. same command under rocprofv3 --kernel-trace --stats; --no-roofline --secondary "": the trace holds the graph-replayed
 #    timed region only, so the CSV average of gemm_h2_pp_kernel is that of the timed configuration's lane launches

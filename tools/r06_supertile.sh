@@ -11,7 +11,7 @@ for rep in 1 2; do
   for v in 0 1; do
     echo "== supertile=$v rep$rep"
     RPR_DEV_LIB=1 RPR_PP_SUPERTILE=$v timeout 300 python tools/gemm_bench.py 53760 2>/dev/null | tail -6
-    RPR_DEV_LIB=1 RPR_PP_SUPERTILE=$v timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-exact-fp32 --secondary "" 2>/dev/null | tail -1 | python -c "
+    RPR_DEV_LIB=1 RPR_PP_SUPERTILE=$v timeout 600 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-exact-fp32 --secondary "" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('   bench', round(d['value'],1), 'q/s', round(d['roofline']['avg_launch_us'],1), 'us/launch', 'board', d.get('board_power'))"
   done

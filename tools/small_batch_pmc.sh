@@ -3,11 +3,12 @@
 # separate passes (TCC slots), summed over every rpr:: kernel -> gpurun_out/TAG/small_batch_pmc.json (copy to
 # profiles/latest_small_batch_pmc.json: bench.py's small_batch leg reads it for roofline.traffic). Usage: tools/small_batch_pmc.sh TAG
 TAG=${1:-sbpmc}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for cfg in "1 10" "8 10" "64 10"; do
   set -- $cfg
-  B="python $GRAFT_REPO_ROOT/bench.py --batch $1 --beams $2 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-exact-fp32 --secondary ''"
+  B="python $REPO/bench.py --batch $1 --beams $2 --steps 1 --warmup 0 --full --no-cpu-baseline --no-roofline --no-exact-fp32 --secondary ''"
   for c in FETCH_SIZE WRITE_SIZE; do
     eval timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/q$1_b$2_$c -o p -- $B > /dev/null 2> $O/q$1_b$2_$c.log
   done
