@@ -415,6 +415,26 @@ int rpr_op_rmsnorm(rpr_ctx* ctx, const float* x, const float* w, float* out, int
 int rpr_encode(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
                int32_t Q, int32_t Lq, float* out, void* stream);
 
+/* ---- residual quantization: docid creation (reference: faiss.IndexResidualQuantizer trained and applied by
+ * tasks/evaluator.py:405-421 and aq_preprocess/create_customized_smtid_file.py) ----
+ * Greedy residual k-means, M levels of K codewords (DESIGN.md "Residual quantization"): per level, K initial centroids
+ * are rows of the level's residuals, then niter Lloyd iterations (assign = argmin_k |c_k|^2 - 2 r.c_k in fp32, smallest k
+ * on ties; centroid = fp64 mean of its rows in row order, rounded to fp32 once; a centroid without rows keeps its value),
+ * then a last assignment and r -= c_m[code]. Deterministic: no float atomics, two runs are bit-identical.
+ * d % 32 == 0, K % 64 == 0, 64 <= K <= 1024, 1 <= n <= 2^30; anything else is RPR_ERR_INVALID. */
+/* x:          [dev] fp32 [n, d] training rows (the caller samples them; n >= K); not modified
+ * init_idx:   [host] int32 [M, K] initial centroid rows of every level, indices into the level's residual rows
+ * codebooks:  [dev] fp32 [M, K, d] out
+ * level_mse:  [host] fp64 [M] or NULL: mean |r|^2 of the training rows after level m (synchronises the stream) */
+int rpr_rq_train(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, int32_t M, int32_t K, int32_t niter,
+                 const int32_t* init_idx, float* codebooks, double* level_mse, void* stream);
+/* Encodes one device chunk with trained codebooks: codes [dev] uint16 [n, M]; level_sse [host] fp64 [M] or NULL: sum of
+ * |r|^2 over the chunk's rows after level m (synchronises the stream). x is not modified (the residuals live in the ctx
+ * workspace: n * d * 4 bytes); larger inputs are streamed chunk by chunk by the caller, the codes do not depend on the
+ * chunking. */
+int rpr_rq_encode(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K,
+                  uint16_t* codes, double* level_sse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

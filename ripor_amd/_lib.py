@@ -139,6 +139,10 @@ SIGNATURES = {
                                  C.c_void_p]),
     "rpr_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                              C.c_void_p]),
+    "rpr_rq_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                               C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "rpr_rq_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

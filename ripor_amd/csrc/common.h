@@ -112,6 +112,27 @@ struct GemmArgs {
 };
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 
+// ---- residual quantization (gemm_f32.hip; rpr_rq_train / rpr_rq_encode in train_api.hip) ----------------------------
+// Greedy residual k-means (DESIGN.md "Residual quantization"). Row tile of the assign kernel: 128 rows; d % 32 == 0,
+// K % 64 == 0, K <= 1024.
+constexpr int RQ_BM = 128, RQ_SORT_ROWS = 256, RQ_MAX_K = 1024;
+struct RqAssignArgs {
+  float* R; int n, d;            // [n, d] residuals (updated in place when part != nullptr)
+  const float* C; const float* cnorm; int K;   // [K, d] codebook and its squared row norms
+  uint16_t* code; int code_stride;             // code of row i -> code[i * code_stride]
+  double* part;                  // nullable: encode mode, R -= C[code] and part[block] = sum of the new |r|^2 of its rows
+};
+hipError_t launch_rq_assign(const RqAssignArgs& a, hipStream_t s);
+// cnorm[k] = |C[k]|^2 for rows k < rows of C [rows, d] (fixed-order fp32 sum)
+hipError_t launch_rq_norms(const float* C, int rows, int d, float* cnorm, hipStream_t s);
+// C[k] = R[idx[k]] for k < K
+hipError_t launch_rq_gather(const float* R, int d, const int* idx, int K, float* C, hipStream_t s);
+// One deterministic centroid update: a stable counting sort of the rows by code (hist [K * nb + 1], order [n] scratch;
+// nb = ceil(n / RQ_SORT_ROWS)), then every centroid with rows = the fp64 mean of its rows in row order, rounded once;
+// a centroid without rows keeps its value. cnorm is refreshed.
+hipError_t launch_rq_update(const float* R, int n, int d, const uint16_t* code, int K, int* hist, int* order, float* C,
+                            float* cnorm, hipStream_t s);
+
 // ---- split-precision GEMM: operands as two f16 planes (hi, lo), 3 f16 MFMAs per product ---------
 struct GemmH2Args {
   const __half* A; size_t a_ps; int lda;   // planes [2][M][lda], plane stride a_ps elements

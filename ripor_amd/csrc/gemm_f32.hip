@@ -202,4 +202,282 @@ hipError_t launch_gemm(const GemmArgs& a, hipStream_t s) {
   return narrow ? launch_cfg<128, 64>(a, s) : launch_cfg<128, 128>(a, s);
 }
 
+
+// ---- residual quantization: nearest codeword of every residual row (rpr_rq_train / rpr_rq_encode) ---------------------
+//
+// score(i, k) = |c_k|^2 - 2 r_i . c_k in fp32, argmin over k with the smallest k on ties. The dot products are the GEMM
+// above (same 128-row tiles, LDS layout, fragment trick and double buffering), but a block walks ALL codeword tiles of
+// BN rows for its 128 residual rows and keeps, per accumulator register, the running minimum and its codeword in
+// registers: no N x K distance matrix exists anywhere (at 8.8 M rows x 256 codewords it would be 9 GB per level).
+// Each lane sees the codewords of one column of every 32 x 32 block in increasing order (tiles, then j), so a strict '<'
+// keeps the smallest index within the lane; the 32 lanes of a row and the two column waves are merged with the
+// lexicographic (score, index) order. Encode mode then subtracts the chosen codeword from the row in place and writes the
+// fixed-order sum of the new |r|^2 over the block's rows (fp64) to part[block].
+template <int BN, bool FULL, bool ENCODE>
+__global__ __launch_bounds__(256, 2) void rq_assign_kernel(RqAssignArgs g) {
+  constexpr int BM = RQ_BM;
+  constexpr int TM = BM / 64, TN = BN / 64;
+  constexpr int PA = BM / 32, PW = BN / 32;
+  constexpr int TILE = (BM + BN) * LDSP;
+  __shared__ __attribute__((aligned(16))) float smem[2 * TILE];
+
+  const int bm = blockIdx.x * BM;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int c4 = (tid & 7) * 4, r0 = tid >> 3;
+  const int frow = lane & 31, fk = (lane >> 5) * 4;
+  const int a_off = (wm * (BM / 2) + frow) * LDSP + fk;
+  const int w_off = (BM + wn * (BN / 2) + frow) * LDSP + fk;
+  const size_t step = (size_t)32 * g.d;
+  const float* Ab = g.R + (size_t)(bm + r0) * g.d + c4;
+  const int nkt = g.d / BK;
+
+  float best_v[TM][16];
+  int best_i[TM][16];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { best_v[i][r] = INFINITY; best_i[i][r] = 0; }
+
+  for (int bn = 0; bn < g.K; bn += BN) {   // K % BN == 0: every codeword tile is full
+    const float* Wb = g.C + (size_t)(bn + r0) * g.d + c4;
+    float4 ra[PA], rw[PW];
+    auto gload = [&](int k0) {
+#pragma unroll
+      for (int i = 0; i < PA; ++i) {
+        if (FULL || bm + r0 + 32 * i < g.n) ra[i] = *reinterpret_cast<const float4*>(Ab + i * step + k0);
+        else ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < PW; ++i) rw[i] = *reinterpret_cast<const float4*>(Wb + i * step + k0);
+    };
+    auto lstore = [&](float* buf) {
+#pragma unroll
+      for (int i = 0; i < PA; ++i) *reinterpret_cast<float4*>(&buf[(r0 + 32 * i) * LDSP + c4]) = ra[i];
+#pragma unroll
+      for (int i = 0; i < PW; ++i) *reinterpret_cast<float4*>(&buf[(BM + r0 + 32 * i) * LDSP + c4]) = rw[i];
+    };
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    auto compute = [&](const float* cur) {
+#pragma unroll
+      for (int kk = 0; kk < BK / 8; ++kk) {
+        float4 a[TM], b[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4*>(cur + a_off + i * 32 * LDSP + kk * 8);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4*>(cur + w_off + j * 32 * LDSP + kk * 8);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
+          }
+      }
+    };
+    gload(0);
+    lstore(smem);
+    __syncthreads();
+    for (int kt = 0; kt + 1 < nkt; ++kt) {
+      gload((kt + 1) * BK);
+      compute(smem + (kt & 1) * TILE);
+      lstore(smem + ((kt + 1) & 1) * TILE);
+      __syncthreads();
+    }
+    compute(smem + ((nkt - 1) & 1) * TILE);
+    __syncthreads();   // the next codeword tile overwrites both operand buffers
+    // running minimum: this lane's codeword of block j is bn + wn * BN/2 + 32 j + (lane & 31), increasing in (bn, j)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int k = bn + wn * (BN / 2) + j * 32 + frow;
+      const float cn = g.cnorm[k];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = cn - 2.0f * acc[i][j][r];
+          if (v < best_v[i][r]) { best_v[i][r] = v; best_i[i][r] = k; }
+        }
+    }
+  }
+
+  // merge the 32 lanes of a row (lanes l and l ^ m, m < 32, hold the same rows), then the two column waves through LDS
+  float* red_v = smem;                                   // [2][BM]
+  int* red_i = reinterpret_cast<int*>(smem + 2 * BM);    // [2][BM]
+  int* row_code = red_i + 2 * BM;                        // [BM]
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float v = best_v[i][r];
+      int k = best_i[i][r];
+#pragma unroll
+      for (int m = 16; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(v, m);
+        const int ok = __shfl_xor(k, m);
+        if (ov < v || (ov == v && ok < k)) { v = ov; k = ok; }
+      }
+      if (frow == 0) {
+        const int row = wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        red_v[wn * BM + row] = v;
+        red_i[wn * BM + row] = k;
+      }
+    }
+  __syncthreads();
+  if (tid < BM) {
+    float v = red_v[tid];
+    int k = red_i[tid];
+    const float ov = red_v[BM + tid];
+    const int ok = red_i[BM + tid];
+    if (ov < v || (ov == v && ok < k)) k = ok;
+    row_code[tid] = k;
+    if (bm + tid < g.n) g.code[(size_t)(bm + tid) * g.code_stride] = (uint16_t)k;
+  }
+  if (!ENCODE) return;
+  __syncthreads();
+  // r -= c[code], new |r|^2: one wave per row, 16-byte pieces; the block's sum in a fixed order
+  double* wsum = reinterpret_cast<double*>(smem + 2 * TILE - 2 * 4);   // [4], past everything above
+  double acc_w = 0.0;
+  for (int row = wave; row < BM; row += 4) {
+    if (!FULL && bm + row >= g.n) break;
+    float* rp = g.R + (size_t)(bm + row) * g.d;
+    const float* cp = g.C + (size_t)row_code[row] * g.d;
+    float ss = 0.f;
+    for (int off = lane * 4; off < g.d; off += 256) {
+      float4 x = *reinterpret_cast<const float4*>(rp + off);
+      const float4 c = *reinterpret_cast<const float4*>(cp + off);
+      x.x -= c.x; x.y -= c.y; x.z -= c.z; x.w -= c.w;
+      *reinterpret_cast<float4*>(rp + off) = x;
+      ss = fmaf(x.x, x.x, ss); ss = fmaf(x.y, x.y, ss); ss = fmaf(x.z, x.z, ss); ss = fmaf(x.w, x.w, ss);
+    }
+    double sd = ss;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) sd += __shfl_xor(sd, m);
+    acc_w += sd;
+  }
+  if (lane == 0) wsum[wave] = acc_w;
+  __syncthreads();
+  if (tid == 0) g.part[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+template <int BN>
+static hipError_t launch_rq_assign_bn(const RqAssignArgs& a, hipStream_t s) {
+  const int blocks = (a.n + RQ_BM - 1) / RQ_BM;
+  const bool full = a.n % RQ_BM == 0;
+  if (a.part) {
+    if (full) hipLaunchKernelGGL((rq_assign_kernel<BN, true, true>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((rq_assign_kernel<BN, false, true>), dim3(blocks), dim3(256), 0, s, a);
+  } else {
+    if (full) hipLaunchKernelGGL((rq_assign_kernel<BN, true, false>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((rq_assign_kernel<BN, false, false>), dim3(blocks), dim3(256), 0, s, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_rq_assign(const RqAssignArgs& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.d <= 0 || a.d % BK || a.K <= 0 || a.K % 64 || a.K > RQ_MAX_K) return hipErrorInvalidValue;
+  return a.K % 128 == 0 ? launch_rq_assign_bn<128>(a, s) : launch_rq_assign_bn<64>(a, s);
+}
+
+// |c_k|^2: one wave per row, lane-strided fp32 partial sums, butterfly reduction (fixed order)
+__global__ __launch_bounds__(64) void rq_norm_kernel(const float* C, int d, float* cnorm) {
+  const float* cp = C + (size_t)blockIdx.x * d;
+  float ss = 0.f;
+  for (int off = threadIdx.x; off < d; off += 64) ss = fmaf(cp[off], cp[off], ss);
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m);
+  if (threadIdx.x == 0) cnorm[blockIdx.x] = ss;
+}
+
+hipError_t launch_rq_norms(const float* C, int rows, int d, float* cnorm, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rq_norm_kernel, dim3(rows), dim3(64), 0, s, C, d, cnorm);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void rq_gather_kernel(const float* R, int d, const int* idx, float* C) {
+  const float* src = R + (size_t)idx[blockIdx.x] * d;
+  float* dst = C + (size_t)blockIdx.x * d;
+  for (int off = threadIdx.x; off < d; off += 256) dst[off] = src[off];
+}
+
+hipError_t launch_rq_gather(const float* R, int d, const int* idx, int K, float* C, hipStream_t s) {
+  hipLaunchKernelGGL(rq_gather_kernel, dim3(K), dim3(256), 0, s, R, d, idx, C);
+  return hipGetLastError();
+}
+
+// counting sort, pass 1: hist[k * nb + b] = rows of chunk b (RQ_SORT_ROWS rows) with code k (integer counts: exact)
+__global__ __launch_bounds__(256) void rq_hist_kernel(const uint16_t* code, int n, int K, int nb, int* hist) {
+  __shared__ int h[RQ_MAX_K];
+  for (int k = threadIdx.x; k < K; k += 256) h[k] = 0;
+  __syncthreads();
+  const int row = blockIdx.x * RQ_SORT_ROWS + threadIdx.x;
+  if (row < n) atomicAdd(&h[code[row]], 1);
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += 256) hist[(size_t)k * nb + blockIdx.x] = h[k];
+}
+
+// pass 2: exclusive scan of hist[0 .. total) in place, hist[total] = the sum (one block of 1024 threads, a contiguous
+// piece each)
+__global__ __launch_bounds__(1024) void rq_scan_kernel(int* hist, int total) {
+  __shared__ int sums[1024];
+  const int t = threadIdx.x, per = (total + 1023) / 1024;
+  const int lo = min(t * per, total), hi = min(lo + per, total);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += hist[i];
+  sums[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {   // Hillis-Steele inclusive scan
+    const int v = t >= o ? sums[t - o] : 0;
+    __syncthreads();
+    sums[t] += v;
+    __syncthreads();
+  }
+  int run = sums[t] - s;
+  for (int i = lo; i < hi; ++i) { const int v = hist[i]; hist[i] = run; run += v; }
+  if (t == 1023) hist[total] = sums[1023];
+}
+
+// pass 3: stable scatter; a row's rank among the rows of its chunk with the same code is the count of earlier ones
+__global__ __launch_bounds__(256) void rq_scatter_kernel(const uint16_t* code, int n, int nb, const int* offs, int* order) {
+  __shared__ int cs[RQ_SORT_ROWS];
+  const int t = threadIdx.x, row = blockIdx.x * RQ_SORT_ROWS + t;
+  const int c = row < n ? code[row] : -1;
+  cs[t] = c;
+  __syncthreads();
+  if (row >= n) return;
+  int rank = 0;
+  for (int j = 0; j < t; ++j) rank += cs[j] == c;
+  order[offs[(size_t)c * nb + blockIdx.x] + rank] = row;
+}
+
+// pass 4: centroid k, dimensions [256 y, 256 y + 256): fp64 sum over its rows in row order, one rounding to fp32
+__global__ __launch_bounds__(256) void rq_mean_kernel(const float* R, int d, const int* offs, int nb, const int* order, float* C) {
+  const int k = blockIdx.x, dim = blockIdx.y * 256 + threadIdx.x;
+  const int lo = offs[(size_t)k * nb], hi = offs[(size_t)(k + 1) * nb];
+  if (dim >= d || hi == lo) return;   // no rows: the centroid keeps its value
+  double s = 0.0;
+  for (int p = lo; p < hi; ++p) s += (double)R[(size_t)order[p] * d + dim];
+  C[(size_t)k * d + dim] = (float)(s / (double)(hi - lo));
+}
+
+hipError_t launch_rq_update(const float* R, int n, int d, const uint16_t* code, int K, int* hist, int* order, float* C,
+                            float* cnorm, hipStream_t s) {
+  const int nb = (n + RQ_SORT_ROWS - 1) / RQ_SORT_ROWS;
+  hipLaunchKernelGGL(rq_hist_kernel, dim3(nb), dim3(256), 0, s, code, n, K, nb, hist);
+  hipLaunchKernelGGL(rq_scan_kernel, dim3(1), dim3(1024), 0, s, hist, K * nb);
+  hipLaunchKernelGGL(rq_scatter_kernel, dim3(nb), dim3(256), 0, s, code, n, nb, (const int*)hist, order);
+  hipLaunchKernelGGL(rq_mean_kernel, dim3(K, (d + 255) / 256), dim3(256), 0, s, R, d, (const int*)hist, nb, (const int*)order, C);
+  return launch_rq_norms(C, K, d, cnorm, s);
+}
+
 }  // namespace rpr

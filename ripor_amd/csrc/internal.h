@@ -152,6 +152,9 @@ struct Workspace {
   TailBufs tail[MAX_FORKS];
   DevBuf t_x, t_h, t_qkv, t_q, t_attn, t_ff, t_x_h, t_attn_h, t_ff_h, t_ssq;
   DevBuf t_logits;        // log-softmax mode: the V logits of every tail row (fp32)
+  // residual quantization (rpr_rq_train / rpr_rq_encode, train_api.hip): residuals [n, d], codes, counting-sort
+  // histogram / row order, codeword norms, per-block fp64 sums of |r|^2, initial centroid rows
+  DevBuf rq_r, rq_code, rq_hist, rq_order, rq_cnorm, rq_part, rq_idx;
 };
 
 static_assert(sizeof(Workspace) % sizeof(DevBuf) == 0 && std::is_standard_layout<Workspace>::value,

@@ -6,6 +6,7 @@ ABI) and for the current HIP stream handle. All compute happens in ``libripor_hi
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -993,3 +994,112 @@ def adamw_step(model: DeviceModel, state: TrainState, lr: float, betas=(0.9, 0.9
     check(ctx.lib.rpr_adamw_step(ctx.handle, model.handle, state.grads.data_ptr(), state.exp_avg.data_ptr(),
                                  state.exp_avg_sq.data_ptr(), state.step, lr, betas[0], betas[1], eps, weight_decay,
                                  max_grad_norm, state.grad_norm.data_ptr(), _stream_ptr(ctx.device)), "rpr_adamw_step")
+
+
+# ---- residual quantization: docid creation (rpr_rq_train / rpr_rq_encode; DESIGN.md "Residual quantization") ----
+RQ_NITER, RQ_SEED, RQ_MAX_POINTS_PER_CENTROID = 25, 1234, 256   # faiss's k-means defaults
+
+
+def rq_training_plan(N: int, M: int, K: int, seed: int = RQ_SEED):
+    """HOST ONLY: the training rows and the initial centroids of every level, drawn from one numpy generator.
+    -> (S: sorted int64 row indices into X [n_train], init_idx: int32 [M, K] indices into the training rows)."""
+    rng = np.random.default_rng(seed)
+    n_train = min(int(N), RQ_MAX_POINTS_PER_CENTROID * int(K))
+    S = np.sort(rng.permutation(int(N))[:n_train])
+    init = np.stack([rng.permutation(n_train)[:K] for _ in range(M)]).astype(np.int32) if n_train >= K else None
+    return S, init
+
+
+def rq_train(ctx: Context, x_train: torch.Tensor, M: int, K: int, init_idx: np.ndarray, niter: int = RQ_NITER):
+    """Greedy residual k-means on the device over the training rows ``x_train`` (fp32 [n, d], on ctx's device).
+    -> (codebooks: fp32 [M, K, d] on the device, level_mse: float64 [M], the mean |r|^2 of the training rows after each level)."""
+    assert x_train.is_cuda and x_train.dtype == torch.float32 and x_train.dim() == 2
+    x_train = x_train.contiguous()
+    n, d = x_train.shape
+    init = np.ascontiguousarray(init_idx, dtype=np.int32)
+    if init.shape != (M, K):
+        raise ValueError(f"init_idx must be [M, K] = [{M}, {K}], got {init.shape}")
+    books = torch.empty((M, K, d), dtype=torch.float32, device=x_train.device)
+    mse = (C.c_double * M)()
+    check(ctx.lib.rpr_rq_train(ctx.handle, x_train.data_ptr(), n, d, M, K, int(niter),
+                               init.ctypes.data_as(C.POINTER(C.c_int32)), books.data_ptr(), mse, _stream_ptr(x_train.device)),
+          "rpr_rq_train")
+    return books, np.asarray(list(mse), dtype=np.float64)
+
+
+def rq_encode(ctx: Context, x, codebooks: torch.Tensor, chunk_rows: int = 1 << 20):
+    """Greedy residual encoding of every row of ``x`` with trained codebooks (fp32 [M, K, d] on the device).
+    ``x``: a device tensor (encoded chunk by chunk in place), or a host array / np.memmap [N, d] streamed through two pinned
+    buffers (the copy of chunk i + 1 runs while chunk i is encoded). -> (codes: uint16 [N, M] host array,
+    level_mse: float64 [M], the mean |r|^2 of all rows after each level). The codes do not depend on chunk_rows."""
+    assert codebooks.is_cuda and codebooks.dtype == torch.float32 and codebooks.dim() == 3
+    books = codebooks.contiguous()
+    M, K, d = books.shape
+    dev = books.device
+    N = int(x.shape[0])
+    if x.shape[1] != d:
+        raise ValueError(f"rows of width {x.shape[1]} against codebooks of width {d}")
+    codes = np.empty((N, M), dtype=np.uint16)
+    sse = np.zeros(M, dtype=np.float64)
+    part = (C.c_double * M)()
+    stream = torch.cuda.current_stream(dev)
+    chunk_rows = max(1, min(int(chunk_rows), max(N, 1)))
+    codes_dev = torch.empty((chunk_rows, M), dtype=torch.int16, device=dev)
+
+    def run(xc: torch.Tensor, lo: int):
+        n = xc.shape[0]
+        check(ctx.lib.rpr_rq_encode(ctx.handle, xc.data_ptr(), n, d, books.data_ptr(), M, K, codes_dev.data_ptr(), part,
+                                    C.c_void_p(stream.cuda_stream)), "rpr_rq_encode")   # synchronises the stream (level sums)
+        sse[:] += np.asarray(list(part))
+        with torch.cuda.stream(stream):
+            codes[lo:lo + n] = codes_dev[:n].cpu().numpy().view(np.uint16)
+
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        assert x.dtype == torch.float32
+        for lo in range(0, N, chunk_rows):
+            run(x[lo:lo + chunk_rows].contiguous(), lo)
+    else:
+        host = [torch.empty((chunk_rows, d), dtype=torch.float32).pin_memory() for _ in range(2)]
+        devb = [torch.empty((chunk_rows, d), dtype=torch.float32, device=dev) for _ in range(2)]
+        copy_stream = torch.cuda.Stream(dev)
+        done = [None, None]
+        starts = list(range(0, N, chunk_rows))
+
+        def stage(i: int):
+            lo = starts[i]
+            n = min(chunk_rows, N - lo)
+            b = i & 1
+            if done[b] is not None:
+                done[b].synchronize()        # the pinned buffer's previous copy has finished
+            host[b][:n].numpy()[:] = np.asarray(x[lo:lo + n], dtype=np.float32)
+            with torch.cuda.stream(copy_stream):
+                devb[b][:n].copy_(host[b][:n], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(copy_stream)
+            done[b] = ev
+            return n
+
+        if starts:
+            n_next = stage(0)
+        for i, lo in enumerate(starts):   # chunk i is encoded on a helper thread (ctypes drops the GIL) while i + 1 is read
+            n = n_next
+            b = i & 1
+            stream.wait_event(done[b])
+            err: List[BaseException] = []
+
+            def work(xc=devb[b][:n], lo=lo):
+                try:
+                    run(xc, lo)
+                except BaseException as e:  # re-raised on the caller's thread
+                    err.append(e)
+
+            t = threading.Thread(target=work)
+            t.start()
+            try:
+                if i + 1 < len(starts):
+                    n_next = stage(i + 1)
+            finally:
+                t.join()
+            if err:
+                raise err[0]
+    return codes, sse / max(N, 1)

@@ -613,6 +613,21 @@ def evaluate(args):
     return res_all
 
 
+def mmap_2(args):
+    """reference evaluate.py:293-294 (DenseIndexing.aggregate_embs_to_mmap)."""
+    from .tasks.rq_indexer import aggregate_embs_to_mmap
+    if args.index_dir and args.mmap_dir != args.index_dir:
+        raise ValueError(f"--mmap_dir {args.mmap_dir} and --index_dir {args.index_dir} must be the same directory")
+    aggregate_embs_to_mmap(args.mmap_dir)
+
+
+def aq_index(args):
+    """reference evaluate.py:296-300: trains the residual quantizer of the docids on the device (greedy residual k-means,
+    no faiss): index_dir/rq_codebooks.npy + rq.json."""
+    from .tasks.rq_indexer import train_index
+    return train_index(args.mmap_dir, args.index_dir, args.num_subvectors_for_pq, args.codebook_bits)
+
+
 def get_args(argv=None):
     """EvalArguments fields used by the generative-retrieval branch (reference arguments.py:145-212)."""
     ap = argparse.ArgumentParser()
@@ -636,6 +651,10 @@ def get_args(argv=None):
     ap.add_argument("--local_rank", "--local-rank", type=int, default=-1)
     ap.add_argument("--max_new_token", type=int, default=None)
     ap.add_argument("--train_query_dir", default=None)
+    ap.add_argument("--mmap_dir", default=None)
+    ap.add_argument("--index_dir", default=None)
+    ap.add_argument("--num_subvectors_for_pq", type=int, default=32)
+    ap.add_argument("--codebook_bits", type=int, default=8)
     ap.add_argument("--apply_log_softmax_for_scores", type=lambda s: str(s).lower() in ("1", "true", "yes"),
                     default=False)
     return ap.parse_args(argv)
@@ -653,6 +672,10 @@ def main(argv=None):
         t5seq_aq_get_qid_to_smtid_rankdata_2(args)
     elif args.task == "evaluate":
         evaluate(args)
+    elif args.task == "mmap_2":
+        mmap_2(args)
+    elif args.task == "aq_index":
+        aq_index(args)
     else:
         raise ValueError(f"task: {args.task} is not valid.")
 

@@ -1,0 +1,96 @@
+"""Docid creation without faiss: the dense document embeddings are gathered into one memmap (reference
+``DenseIndexing.aggregate_embs_to_mmap``, tasks/evaluator.py:637-690), a residual quantizer is trained on the device
+(replaces ``AddictvieQuantizeIndexer.index``, tasks/evaluator.py:405-421, faiss.IndexResidualQuantizer) and every
+document is encoded into its smtid (aq_preprocess/create_customized_smtid_file.py).
+
+The quantizer is greedy residual k-means (DESIGN.md "Residual quantization"): its codes are not faiss's codes, and the
+index directory holds ``rq_codebooks.npy`` + ``rq.json`` instead of faiss's ``model.index``."""
+from __future__ import annotations
+
+import json
+import os
+import pickle
+
+import numpy as np
+
+
+def aggregate_embs_to_mmap(mmap_dir: str) -> None:
+    """``embs_{rank}_{chunk}.npy`` / ``ids_{rank}_{chunk}.npy`` (layout in ``plan.json``) -> ``doc_embeds.mmap`` (raw fp32
+    [N, d]), ``text_ids.tsv``, ``meta.pkl``; the chunk files are removed (reference tasks/evaluator.py:637-690)."""
+    with open(os.path.join(mmap_dir, "plan.json")) as fin:
+        plan = json.load(fin)
+    print("mmap_dir is: {}".format(mmap_dir))
+    print("plan: ", plan)
+    nranks, num_chunks = plan["nranks"], plan["num_chunks"]
+    names = [(f"embs_{i}_{c}.npy", f"ids_{i}_{c}.npy") for i in range(nranks) for c in range(num_chunks)]
+    embs = [np.load(os.path.join(mmap_dir, e), mmap_mode="r") for e, _ in names]
+    text_ids = np.concatenate([np.load(os.path.join(mmap_dir, i)) for _, i in names])
+    N = sum(len(e) for e in embs)
+    assert N == len(text_ids), (N, len(text_ids))
+    assert text_ids.ndim == 1, text_ids.shape
+    d = embs[0].shape[1]
+    print("embs size: ", (N, d), "ids dtype: ", text_ids.dtype)
+    fp = np.memmap(os.path.join(mmap_dir, "doc_embeds.mmap"), dtype=np.float32, mode="w+", shape=(N, d))
+    lo = 0
+    for e in embs:   # chunk by chunk: the collection never has to fit the host memory twice
+        fp[lo:lo + len(e)] = np.asarray(e, dtype=np.float32)
+        lo += len(e)
+    fp.flush()
+    del fp
+    with open(os.path.join(mmap_dir, "text_ids.tsv"), "w") as fout:
+        for tid in text_ids:
+            fout.write(f"{tid}\n")
+    meta = {"text_ids": text_ids, "num_embeddings": len(text_ids)}
+    with open(os.path.join(mmap_dir, "meta.pkl"), "wb") as f:
+        pickle.dump(meta, f)
+    del embs
+    for e, i in names:
+        os.remove(os.path.join(mmap_dir, e))
+        os.remove(os.path.join(mmap_dir, i))
+
+
+def load_doc_embeds(mmap_dir: str) -> np.memmap:
+    """``doc_embeds.mmap`` as a read-only [N, d] memmap (N from ``meta.pkl``)."""
+    with open(os.path.join(mmap_dir, "meta.pkl"), "rb") as f:
+        n = int(pickle.load(f)["num_embeddings"])
+    path = os.path.join(mmap_dir, "doc_embeds.mmap")
+    total = os.path.getsize(path) // 4
+    if n <= 0 or total % n:
+        raise ValueError(f"{path}: {total} floats do not divide into {n} rows")
+    return np.memmap(path, dtype=np.float32, mode="r", shape=(n, total // n))
+
+
+def train_index(mmap_dir: str, index_dir: str, M: int, bits: int, niter: int = None, seed: int = None, device=None) -> dict:
+    """Trains the M x 2^bits residual quantizer on the device and writes ``rq_codebooks.npy`` and ``rq.json``."""
+    import torch
+    from .. import engine as E
+    niter = E.RQ_NITER if niter is None else niter
+    seed = E.RQ_SEED if seed is None else seed
+    K = 1 << int(bits)
+    X = load_doc_embeds(mmap_dir)
+    N, d = X.shape
+    S, init = E.rq_training_plan(N, M, K, seed)
+    if init is None:
+        raise ValueError(f"{N} documents are fewer than the {K} codewords of a level")
+    ctx = E.Context.get(device)
+    x_train = torch.from_numpy(np.ascontiguousarray(X[S])).to(ctx.device)
+    print(f"Training residual quantizer: M = {M}, K = {K}, d = {d}, {len(S)} training points of {N}, niter = {niter}")
+    books, mse = E.rq_train(ctx, x_train, M, K, init, niter=niter)
+    for m, v in enumerate(mse):
+        print(f"[level {m}] training MSE after the level: {v:.6g}")
+    os.makedirs(index_dir, exist_ok=True)
+    np.save(os.path.join(index_dir, "rq_codebooks.npy"), books.cpu().numpy())
+    info = dict(M=int(M), K=int(K), d=int(d), niter=int(niter), seed=int(seed), n_train=int(len(S)), num_embeddings=int(N),
+                level_mse=[float(v) for v in mse], method="greedy residual k-means")
+    with open(os.path.join(index_dir, "rq.json"), "w") as f:
+        json.dump(info, f, indent=2)
+    return info
+
+
+def load_index(index_dir: str):
+    """-> (codebooks fp32 [M, K, d], rq.json dict)."""
+    with open(os.path.join(index_dir, "rq.json")) as f:
+        info = json.load(f)
+    books = np.load(os.path.join(index_dir, "rq_codebooks.npy"))
+    assert books.shape == (info["M"], info["K"], info["d"]), (books.shape, info)
+    return books, info
