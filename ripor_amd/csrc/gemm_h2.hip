@@ -28,6 +28,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "gemm_route.h"
 
 #include <algorithm>
 #include <vector>
@@ -45,7 +46,6 @@ template <bool FULL, int TM, int TN, int WM, int WN, int BM, int BN, bool BOUT =
 __device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, f32x16 (&acc)[TM][TN], __half* smem, int wave, int lane, int bm,
                                                 int bn, int wm, int wn, const float* rs_tile, float acc_scale);
 
-constexpr int HBK = 32;  // K-tile depth = halves per LDS row (64 B, unpadded)
 
 
 // ---- LDS-DMA variant -------------------------------------------------------------------------------
@@ -982,97 +982,32 @@ __global__ __launch_bounds__(256, 1) void gemm_h2_wsplit_kernel(GemmH2Args g, in
   }
 }
 
+// The launchers pick the instantiation that a step of the plan (gemm_route.h) names and launch it on the step's grid.
 template <int TM, int TN, int ST>
-static hipError_t launch_wsplit_cfg(const GemmH2Args& k, hipStream_t s) {
-  constexpr int BM = 32 * TM, BN = 32 * TN;
-  const int tiles_m = (k.M + BM - 1) / BM, tiles_n = (k.N + BN - 1) / BN;
-  const bool full = (k.M % BM == 0) && (k.N % BN == 0) && !k.m_dev;
-  const bool split = k.ksplit > 1;
-  const dim3 grid(tiles_m * tiles_n, split ? k.ksplit : 1);
-  if (split && full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST, true>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
-  else if (split) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST, true>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
-  else if (full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST, false>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
-  else hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST, false>), grid, dim3(256), 0, s, k, tiles_m, tiles_n);
-  return hipGetLastError();
+static void launch_wsplit_cfg(const GemmStep& p, const GemmH2Args& k, hipStream_t s) {
+  const dim3 grid(p.grid_x, p.grid_y);
+  const bool split = p.ksplit > 1;
+  if (split && p.full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST, true>), grid, dim3(256), 0, s, k, p.tiles_m, p.tiles_n);
+  else if (split) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST, true>), grid, dim3(256), 0, s, k, p.tiles_m, p.tiles_n);
+  else if (p.full) hipLaunchKernelGGL((gemm_h2_wsplit_kernel<true, TM, TN, ST, false>), grid, dim3(256), 0, s, k, p.tiles_m, p.tiles_n);
+  else hipLaunchKernelGGL((gemm_h2_wsplit_kernel<false, TM, TN, ST, false>), grid, dim3(256), 0, s, k, p.tiles_m, p.tiles_n);
 }
 
-// Tile shape and K split of a wave-split launch. These launches are latency-bound by LDS capacity: a block keeps at most its
-// rings in flight (64-96 KB) against a loaded L2 / Infinity-Cache latency of ~3 us, i.e. 40-50 GB/s per CU whatever the tile
-// (tools/attic/fill_probe.hip: the LDS-DMA path itself sustains > 100 GB/s per CU from L2), one block per CU (128-144 KB of LDS).
-// Model fitted to tools/wsplit_bench.sh on MI355X (profiles/archive/r05d_wsplit_gemm_bench.txt): launch = 5 us + rounds of blocks over
-// the CUs x (3 us + KB per block / rate), + one reduction launch for a K split over blocks.
-// cfg 0: 32 x 32 (four stages), 1: 64 x 32 (three), 2: 64 x 64 (two).
-struct WsplitChoice { int cfg, ks; double us; long rounds; };
-static WsplitChoice choose_wsplit(int M, int N, int K, int cus, bool can_split, size_t part_cap) {
-  constexpr double lat_us = 3.0, split_us = 4.5;   // per round of blocks; the reduction launch of a K split
-  const int bm[3] = {32, 64, 64}, bn[3] = {32, 32, 64};
-  const double rate_gbs[3] = {48.0, 48.0, 41.0};
-  WsplitChoice best{0, 1, 1e30, 1};
-  for (int c = 0; c < 3; ++c) {
-    const long tiles = (long)((M + bm[c] - 1) / bm[c]) * ((N + bn[c] - 1) / bn[c]);
-    for (int ks = 1; ks <= 4; ++ks) {
-      if (ks > 1 && (!can_split || K / ks < 256 || (size_t)M * N * ks > part_cap)) break;
-      const int nkt = K / HBK;
-      if (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) continue;
-      const long blocks = tiles * ks, rounds = (blocks + cus - 1) / cus;
-      const double kb = (double)(bm[c] + bn[c]) * ((double)K / ks) * 4.0 * 1e-3;
-      const double us = 5.0 + rounds * (lat_us + kb / rate_gbs[c]) + (ks > 1 ? split_us : 0.0);
-      if (us < best.us) best = {c, ks, us, rounds};
-    }
-  }
-  return best;
+template <int BN, bool BF16 = false>
+static void launch_cfg(const GemmStep& p, const GemmH2Args& a, hipStream_t s) {
+  const dim3 grid(p.grid_x, p.grid_y), blk(256);
+  if (p.stages == 4 && p.full) hipLaunchKernelGGL((gemm_h2_dma_kernel<128, BN, 2, 2, true, 4, BF16>), grid, blk, 0, s, a, p.tiles_m, p.tiles_n);
+  else if (p.stages == 4) hipLaunchKernelGGL((gemm_h2_dma_kernel<128, BN, 2, 2, false, 4, BF16>), grid, blk, 0, s, a, p.tiles_m, p.tiles_n);
+  else if (p.full) hipLaunchKernelGGL((gemm_h2_dma_kernel<128, BN, 2, 2, true, 2, BF16>), grid, blk, 0, s, a, p.tiles_m, p.tiles_n);
+  else hipLaunchKernelGGL((gemm_h2_dma_kernel<128, BN, 2, 2, false, 2, BF16>), grid, blk, 0, s, a, p.tiles_m, p.tiles_n);
 }
 
-template <int BM, int BN, int WM = 2, int WN = 2, bool BF16 = false>
-static hipError_t launch_cfg(const GemmH2Args& a, hipStream_t s) {
-  const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-  const bool full = (a.M % BM == 0) && (a.N % BN == 0) && !a.m_dev;
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  const dim3 grid(tiles_m * tiles_n, ks), blk(64 * WM * WN);
-  constexpr int deep_max = 128;   // (blocks up to which the 128-row tiles run 4 stages deep)
-  if ((tiles_m * tiles_n * ks <= deep_max || BM < 128) && (!a.m_dev || a.live_hi > 0)) {   // fewer tiles than CUs: one block per CU, 3 K-tiles in flight
-    if (full)
-      hipLaunchKernelGGL((gemm_h2_dma_kernel<BM, BN, WM, WN, true, 4, BF16>), grid, blk, 0, s, a, tiles_m, tiles_n);
-    else
-      hipLaunchKernelGGL((gemm_h2_dma_kernel<BM, BN, WM, WN, false, 4, BF16>), grid, blk, 0, s, a, tiles_m, tiles_n);
-    return hipGetLastError();
-  }
-  if (full)
-    hipLaunchKernelGGL((gemm_h2_dma_kernel<BM, BN, WM, WN, true, 2, BF16>), grid, blk, 0, s, a, tiles_m, tiles_n);
-  else
-    hipLaunchKernelGGL((gemm_h2_dma_kernel<BM, BN, WM, WN, false, 2, BF16>), grid, blk, 0, s, a, tiles_m, tiles_n);
-  return hipGetLastError();
-}
-
-// 256x256 tile, 8 waves (2x4) of 128x64, ping-pong schedule: half the staged bytes per MFMA of the 128x128 tile;
-// >= ~112 tiles to beat the 128x128 kernel (measured), i.e. M = Q*B >= ~10k rows for N = 768
-static hipError_t launch_256(const GemmH2Args& a_in, hipStream_t s) {
-  GemmH2Args a = a_in;
-  const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
-  const bool full = (a.M % 256 == 0) && (a.N % 256 == 0) && !a.m_dev;
-  // persistent blocks: one per CU of the stream (a whole number per XCD), fewer when the launch has fewer tiles
-  const int cus = a.cus > 0 ? a.cus : 256, nt = tiles_m * tiles_n;
-  const int grid = nt > cus ? cus : nt;
-  const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  const dim3 gr(ks > 1 ? nt : grid, ks), bl(512);      // split-K launches are not persistent: one block per (tile, K range)
-  // super-tile order for products more than four column tiles wide (N = 2304, 3072): column groups of 3 or 4 tiles, bands of
-  // as many row panels as the blocks of one XCD fill with such a group. RPR_PP_SUPERTILE=0 (development builds): row-major
-  static const int sup = [] { const char* e = dev_getenv("RPR_PP_SUPERTILE"); return e ? atoi(e) : 1; }();
-  a.tile_cw = a.tile_rb = 0;
-  if (sup && ks == 1 && tiles_n > 4 && nt > grid) {
-    a.tile_cw = sup > 1 ? sup : (tiles_n % 4 == 0 ? 4 : (tiles_n % 3 == 0 ? 3 : 4));
-    a.tile_rb = std::max(1, (grid / 8) / a.tile_cw);
-  }
-  if (a.bf16) {
-    if (full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
-    else hipLaunchKernelGGL((gemm_h2_pp_kernel<false, true>), gr, bl, 0, s, a, tiles_m, tiles_n);
-    return hipGetLastError();
-  }
-  if (full)
-    hipLaunchKernelGGL((gemm_h2_pp_kernel<true>), gr, bl, 0, s, a, tiles_m, tiles_n);
-  else
-    hipLaunchKernelGGL((gemm_h2_pp_kernel<false>), gr, bl, 0, s, a, tiles_m, tiles_n);
-  return hipGetLastError();
+static void launch_256(const GemmStep& p, const GemmH2Args& a, hipStream_t s) {
+  const dim3 gr(p.grid_x, p.grid_y), bl(512);
+  if (p.bf16 && p.full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true, true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
+  else if (p.bf16) hipLaunchKernelGGL((gemm_h2_pp_kernel<false, true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
+  else if (p.full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
+  else hipLaunchKernelGGL((gemm_h2_pp_kernel<false>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
 }
 
 hipError_t launch_gemm_h2_group(const GemmGroupArgs& p, void* scratch, hipStream_t s) {
@@ -1080,39 +1015,17 @@ hipError_t launch_gemm_h2_group(const GemmGroupArgs& p, void* scratch, hipStream
   if (!scratch || p.n > GemmGroupArgs::MAXP || p.K <= 0 || (p.K & 63) || (p.lda & 7) || (p.ldw & 7)) return hipErrorInvalidValue;
   bool full = true;
   int total = 0;
-  struct Super { int p, tm0, tn0, rm, rn; };
-  std::vector<Super> sup;
   for (int i = 0; i < p.n; ++i) {
     if (!p.A[i] || !p.W[i] || !p.out[i] || p.M[i] <= 0 || p.N[i] <= 0 || (p.ldo[i] & 3) || (p.N[i] & 3)) return hipErrorInvalidValue;
-    const int tm = (p.M[i] + 255) / 256, tn = (p.N[i] + 255) / 256;
-    total += tm * tn;
+    total += ((p.M[i] + 255) / 256) * ((p.N[i] + 255) / 256);
     full = full && (p.M[i] % 256 == 0) && (p.N[i] % 256 == 0);
-    // nearly equal parts of at most 4 tile rows / columns
-    const int pm = (tm + 3) / 4, pn = (tn + 3) / 4, sm = (tm + pm - 1) / pm, sn = (tn + pn - 1) / pn;
-    for (int a = 0; a < tm; a += sm)
-      for (int b = 0; b < tn; b += sn) sup.push_back({i, a, b, std::min(sm, tm - a), std::min(sn, tn - b)});
   }
   if (total > GemmGroupArgs::MAX_TILES || total >= 65536) return hipErrorInvalidValue;
-  // the tiles in super-tile order, cut into 8 equal runs: every XCD gets the same number of tiles (the main stream's kernels
-  // run beside this launch and are spread evenly over the XCDs: whole super-tiles per XCD, 21 blocks on one XCD and 12 on
-  // another, slowed those by 10 %), a run is one or two super-tiles plus parts of its neighbours
-  std::vector<int> order;
-  for (const Super& u : sup) {
-    const int tn = (p.N[u.p] + 255) / 256;
-    for (int a = 0; a < u.rm; ++a)
-      for (int b = 0; b < u.rn; ++b) order.push_back((u.p << 16) | ((u.tm0 + a) * tn + u.tn0 + b));
-  }
-  std::vector<int> per_xcd[8];
-  for (int x = 0; x < 8; ++x)
-    for (size_t k = (size_t)x * order.size() / 8; k < (size_t)(x + 1) * order.size() / 8; ++k) per_xcd[x].push_back(order[k]);
-  size_t slots = 0;
-  for (int x = 0; x < 8; ++x) slots = std::max(slots, per_xcd[x].size());
+  const std::vector<int> order = group_tile_order(p.M, p.N, p.n);
   GroupAssign asg;
-  asg.n = (int)slots * 8;
+  asg.n = (int)order.size();
   if (asg.n > GemmGroupArgs::MAX_BLOCKS) return hipErrorInvalidValue;
-  for (int i = 0; i < asg.n; ++i) asg.v[i] = -1;
-  for (int x = 0; x < 8; ++x)
-    for (size_t k = 0; k < per_xcd[x].size(); ++k) asg.v[x + 8 * k] = per_xcd[x][k];
+  std::copy(order.begin(), order.end(), asg.v);
   GemmH2Args* table = reinterpret_cast<GemmH2Args*>(scratch);
   int* assign = reinterpret_cast<int*>(static_cast<char*>(scratch) + GemmGroupArgs::TABLE_BYTES);
   hipLaunchKernelGGL(gemm_group_table_kernel, dim3(1), dim3(256), 0, s, p, asg, table, assign);
@@ -1213,234 +1126,113 @@ __global__ __launch_bounds__(256) void splitk_epilogue4_kernel(GemmH2Args g, con
   }
 }
 
-// Largest split count <= ks in which every split owns at least one of the nkt K-tiles.
-static long trim_ks(long ks, int nkt) {
-  while (ks > 1 && (ks - 1) * ((nkt + ks - 1) / ks) >= nkt) --ks;
-  return ks;
+// The route thresholds; in a development build with the switches of the environment (read once).
+static const GemmTuning& gemm_tuning() {
+  static const GemmTuning tuning = [] {
+    GemmTuning t;
+    const auto sw = [](const char* e, int& v) { if (e) v = atoi(e); };
+    sw(dev_getenv("RPR_GEMM_TILE"), t.force_tile);
+    sw(dev_getenv("RPR_GEMM_ROWSPLIT"), t.row_split);
+    sw(dev_getenv("RPR_GEMM_ROWSPLIT_LOG"), t.row_split_log);
+    sw(dev_getenv("RPR_GEMM_WSPLIT_MAX"), t.wsplit_max);
+    sw(dev_getenv("RPR_WSPLIT_CFG"), t.wsplit_cfg);
+    sw(dev_getenv("RPR_WSPLIT_KS"), t.wsplit_ks);
+    sw(dev_getenv("RPR_PP_SUPERTILE"), t.supertile);
+    return t;
+  }();
+  return tuning;
 }
 
-// splitk_epilogue4_kernel applies: N % 256 == 0 and every column split and leading dimension a multiple of 4.
-static bool epilogue_vec4(const GemmH2Args& a) {
-  return (a.N & 255) == 0 && (a.split_n & 3) == 0 && (a.ldo[0] & 3) == 0 && (a.ldo[1] & 3) == 0 && (a.ldo[2] & 3) == 0 &&
-         (!a.resid || (a.ldr & 3) == 0) && (!a.resid_h || (a.ldrh & 3) == 0) && (!a.out_h || (a.ldoh & 3) == 0);
+static GemmRouteIn route_inputs(const GemmH2Args& a) {
+  GemmRouteIn r;
+  r.M = a.M; r.N = a.N; r.K = a.K; r.cus = a.cus;
+  r.split_n = a.split_n; r.rm_B = a.rm_B; r.ksplit = a.ksplit; r.small_live = a.small_live; r.live_lo = a.live_lo; r.live_hi = a.live_hi;
+  r.part_cap = a.part_cap;
+  r.part = a.part; r.mid_split = a.mid_split; r.m_dev = a.m_dev; r.bf16 = a.bf16; r.no_row_split = a.no_row_split;
+  r.out_h = a.out_h; r.row_ssq = a.row_ssq; r.ssq_out = a.ssq_out; r.resid = a.resid; r.resid_h = a.resid_h; r.relu = a.relu;
+  r.out_b = a.out_b; r.out_bt = a.out_bt;
+  r.ab_al8 = !(a.lda & 7) && !(a.ldw & 7);
+  r.ldo0_al4 = !(a.ldo[0] & 3);
+  r.ldr_al4 = !a.resid || !(a.ldr & 3);
+  r.epi_al4 = !(a.ldo[0] & 3) && !(a.ldo[1] & 3) && !(a.ldo[2] & 3) && r.ldr_al4 && (!a.resid_h || !(a.ldrh & 3)) && (!a.out_h || !(a.ldoh & 3));
+  r.outb_al = !(a.out_b && (a.ldob & 7)) && !(a.out_bt && ((a.ldobt & 7) || a.ldobt < a.M)) && !(a.mask_src && (a.ldmask & 3));
+  return r;
 }
 
-using TileLaunch = hipError_t (*)(const GemmH2Args&, hipStream_t);
-
-// Split-K over blockIdx.y: `tiles` writes the fp32 partial sums of the ks K ranges to the caller's scratch a.part, then one
-// launch combines them in split order (bitwise reproducible). fused = false: splitk_reduce_kernel adds them to the fp32
-// residual (a plain sum into out[0]); fused = true: splitk_epilogue{,4}_kernel applies a's whole epilogue to the sum, so
-// the tile launch runs with every epilogue field cleared.
-static hipError_t launch_splitk(const GemmH2Args& a, int ks, bool fused, TileLaunch tiles, hipStream_t s) {
-  GemmH2Args p = a;
-  p.ksplit = ks; p.part_stride = (size_t)a.M * a.N;
-  p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N; p.resid = nullptr;
-  if (fused) {
-    p.out_h = nullptr; p.resid_h = nullptr; p.relu = 0; p.row_ssq = nullptr; p.ssq_out = nullptr;
-    p.rm_B = 0; p.acc_scale = 1.0f; p.dyn_a = p.dyn_b = nullptr;
+// (The order in which the instantiations are first named here is their order in the code object.)
+static hipError_t launch_step(const GemmStep& p, const GemmH2Args& a, hipStream_t s) {
+  if (p.family == GEMM_SKINNY16) {
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.full) hipLaunchKernelGGL((gemm_h2_skinny16_kernel<true>), grid, dim3(256), 0, s, a, p.tiles_n);
+    else hipLaunchKernelGGL((gemm_h2_skinny16_kernel<false>), grid, dim3(256), 0, s, a, p.tiles_n);
   }
-  hipError_t e = tiles(p, s);
-  if (e != hipSuccess) return e;
-  const size_t n = (size_t)a.M * a.N, n4 = (size_t)a.M * (a.N >> 2);
-  if (!fused)
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.part, ks, p.part_stride, a.M, a.N,
-                       a.out[0], a.ldo[0], a.resid, a.ldr);
-  else if (epilogue_vec4(a))
-    hipLaunchKernelGGL(splitk_epilogue4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, a, a.part, ks, p.part_stride);
-  else
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, a.part, ks, p.part_stride);
+  else if (p.family == GEMM_PP) launch_256(p, a, s);
+  else if (p.family == GEMM_WSPLIT && p.bm == 32) launch_wsplit_cfg<1, 1, 4>(p, a, s);
+  else if (p.family == GEMM_DMA && p.bn == 64 && !p.bf16) launch_cfg<64>(p, a, s);
+  else if (p.family == GEMM_DMA && p.bn == 64) launch_cfg<64, true>(p, a, s);
+  else if (p.family == GEMM_DMA && p.bf16) launch_cfg<128, true>(p, a, s);
+  else if (p.family == GEMM_DMA) launch_cfg<128>(p, a, s);
+  else if (p.bn == 32) launch_wsplit_cfg<2, 1, 3>(p, a, s);
+  else launch_wsplit_cfg<2, 2, 2>(p, a, s);
   return hipGetLastError();
 }
 
-// Partial tiles per split-K launch that the 128 x 64 routes aim for.
-constexpr int SPLITK_TARGET = 640;
+// Split-K over blockIdx.y: the tile launch writes the fp32 partial sums of the ks K ranges to the caller's scratch a.part, then
+// one launch combines them in split order (bitwise reproducible). REDUCE_SUM: splitk_reduce_kernel adds them to the fp32
+// residual (a plain sum into out[0]); REDUCE_FUSED{,4}: splitk_epilogue{,4}_kernel applies a's whole epilogue to the sum, so
+// the tile launch runs with every epilogue field cleared.
+static GemmH2Args splitk_tile_args(const GemmH2Args& a, const GemmStep& st) {
+  GemmH2Args p = a;
+  p.ksplit = st.ksplit; p.part_stride = (size_t)a.M * a.N;
+  p.out[0] = p.out[1] = p.out[2] = a.part; p.ldo[0] = p.ldo[1] = p.ldo[2] = a.N; p.split_n = a.N; p.resid = nullptr;
+  if (st.reduce != REDUCE_SUM) {
+    p.out_h = nullptr; p.resid_h = nullptr; p.relu = 0; p.row_ssq = nullptr; p.ssq_out = nullptr;
+    p.rm_B = 0; p.acc_scale = 1.0f; p.dyn_a = p.dyn_b = nullptr;
+  }
+  return p;
+}
 
-// Split-K through the 256x256 ping-pong kernel (weight gradients of the training step: dW[N, K] = dY^T X reduces over the
-// 8192 rows of the batch into 9 .. 36 output tiles): blockIdx.y = K range, partial tiles to the caller's scratch,
-// splitk_reduce_kernel adds them in split order (bitwise reproducible). Returns hipErrorNotSupported when the shape does
-// not qualify (the caller falls back to the 128x64 split-K route).
-static hipError_t launch_256_splitk(const GemmH2Args& a, hipStream_t s) {
-  const int kstep = a.bf16 ? 2 * HBK : HBK;
-  if (!a.part || (a.M & 255) || (a.N & 255) || (a.K % kstep) || a.relu || a.out_h || a.row_ssq || a.ssq_out || a.resid_h ||
-      a.m_dev || a.rm_B || a.split_n < a.N || (a.ldo[0] & 3) || (a.resid && (a.ldr & 3)))
-    return hipErrorNotSupported;
-  const long tiles = (long)(a.M / 256) * (a.N / 256);
-  const int cus = a.cus > 0 ? a.cus : 256, nkt = a.K / kstep;
-  long ks = cus / tiles;                                        // one round of (tile, K range) blocks on the chip
-  ks = std::min<long>(ks, nkt / 4);                             // at least 4 K-tiles per block
-  ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-  ks = trim_ks(ks, nkt);
-  if (tiles > 64 || ks < 2) return hipErrorNotSupported;
-  return launch_splitk(a, (int)ks, false, launch_256, s);
+static hipError_t launch_splitk_reduce(const GemmH2Args& a, const GemmStep& st, hipStream_t s) {
+  const size_t n = (size_t)a.M * a.N, n4 = (size_t)a.M * (a.N >> 2);
+  if (st.reduce == REDUCE_SUM)
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.part, st.ksplit, n, a.M, a.N,
+                       a.out[0], a.ldo[0], a.resid, a.ldr);
+  else if (st.reduce == REDUCE_FUSED4)
+    hipLaunchKernelGGL(splitk_epilogue4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, a, a.part, st.ksplit, n);
+  else
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, a.part, st.ksplit, n);
+  return hipGetLastError();
 }
 
 hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
   GemmH2Args a = a_in;
   if (a.acc_scale == 0.f) a.acc_scale = 1.f;      // zero-initialised args mean "no scaling"
   if (a.plane_scale == 0.f) a.plane_scale = 1.f;
-  a_in.kernel_cls = RPR_K_GEMM_SMALL;
-  if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (a.K % HBK != 0 || a.K <= 0 || (a.lda & 7) || (a.ldw & 7)) return hipErrorInvalidValue;
-  constexpr int skinny = 352;   // max rows (measured per search: 320 rows skinny 66.0 vs split-K route 68.5 ms, 400 rows 95.5 vs 71.8)
-  auto launch_skinny = [&](const GemmH2Args& k) {
-    if (k.M <= 32 && (k.N & 15) == 0) {   // one query in flight: 16 x 16 tiles, all of K = 768 in flight
-      const int tiles_n = k.N / 16;
-      const dim3 grid(tiles_n, (k.M + 15) / 16);
-      if (!k.m_dev) hipLaunchKernelGGL((gemm_h2_skinny16_kernel<true>), grid, dim3(256), 0, s, k, tiles_n);
-      else hipLaunchKernelGGL((gemm_h2_skinny16_kernel<false>), grid, dim3(256), 0, s, k, tiles_n);
-      return hipGetLastError();
+  const GemmTuning& tune = gemm_tuning();
+  const GemmPlan plan = plan_gemm_h2(route_inputs(a), tune);
+  a_in.kernel_cls = plan.cls;
+  if (plan.invalid) return hipErrorInvalidValue;
+  for (int i = 0; i < plan.n; ++i) {
+    const GemmStep& st = plan.step[i];
+    GemmH2Args p = a;   // this step's rows of the product, its live window and tile order
+    p.M = st.rows; p.live_lo = st.live_lo; p.live_hi = st.live_hi; p.tile_cw = st.tile_cw; p.tile_rb = st.tile_rb;
+    if (st.m_base > 0) {   // the rows behind a row split
+      const int r0 = st.m_base;
+      if (tune.row_split_log) fprintf(stderr, "[rowsplit] M=%d N=%d K=%d: %d rows on 256x256 tiles, %d on 128x128\n", a.M, a.N, a.K, r0, st.rows);
+      p.m_base = a.m_base + r0;
+      p.A = a.A + (size_t)r0 * a.lda;
+      for (int o = 0; o < 3; ++o) if (a.out[o]) p.out[o] = a.out[o] + (size_t)r0 * a.ldo[o];
+      if (a.out_h) p.out_h = a.out_h + (size_t)r0 * a.ldoh;
+      if (a.resid) p.resid = a.resid + (size_t)r0 * a.ldr;
+      if (a.resid_h) p.resid_h = a.resid_h + (size_t)r0 * a.ldrh;
+      if (a.row_ssq) p.row_ssq = a.row_ssq + r0;
+      if (a.ssq_out) p.ssq_out = a.ssq_out + r0;
     }
-    return launch_wsplit_cfg<1, 1, 4>(k, s);   // 32 x 32 wave-split tiles
-  };
-  if (a.m_dev && a.small_live > 0 && a.M > a.small_live && !a.bf16) {
-    // a compacted stage: capacity M rows, usually a handful alive. The large-tile kernel would walk all of K with the
-    // one or two blocks that hold live rows (60-250 us per launch). The launch is enqueued as a group of three, each
-    // gated on the device-side live count (two of them exit at once): the large-tile kernel for more than small_live
-    // rows, a 128x64 launch sized for small_live rows, and the skinny tiles for at most `skinny` rows (a few leftover
-    // queries: 10 us instead of 17-20 for the 128x64 tile walking K alone).
-    GemmH2Args big = a, mid = a, sk = a;
-    const int sk_rows = std::min(skinny, a.small_live);
-    big.small_live = 0; big.live_lo = a.small_live; big.live_hi = 0x7fffffff;
-    mid.small_live = 0; mid.live_lo = sk_rows; mid.live_hi = a.small_live; mid.M = a.small_live;
-    sk.small_live = 0; sk.live_lo = -1; sk.live_hi = sk_rows; sk.M = (sk_rows + 31) / 32 * 32;
-    hipError_t e = launch_gemm_h2(big, s);
+    hipError_t e = launch_step(st, st.reduce == REDUCE_NONE ? p : splitk_tile_args(p, st), s);
+    if (e == hipSuccess && st.reduce != REDUCE_NONE) e = launch_splitk_reduce(p, st, s);
     if (e != hipSuccess) return e;
-    a_in.kernel_cls = big.kernel_cls;
-    if (sk_rows < a.small_live) { e = launch_cfg<128, 64>(mid, s); if (e != hipSuccess) return e; }
-    return launch_skinny(sk);
   }
-  if (a.bf16) {
-    // one bf16 plane per operand (training GEMMs, RPR_PREC_BF16): fp32 output, optional residual / ReLU, split-K for the
-    // long reductions into few tiles (weight gradients); K-tiles of 64 columns
-    if (a.out_h || a.row_ssq || a.ssq_out || a.resid_h || a.m_dev || a.rm_B || (a.K & 63) || (a.N & 3) || (a.ldo[0] & 3) ||
-        (a.resid && (a.ldr & 3)) || a.split_n < a.N)
-      return hipErrorInvalidValue;                       // (the bf16 kernels' epilogues store 16-byte pieces of ONE fp32 output)
-    if (a.out_b || a.out_bt) {
-      // bf16 operands for the consumers straight from the epilogue (GemmH2Args::out_b): the 256 x 256 kernel's FULL instantiation only
-      if ((a.M & 255) || (a.N & 255) || a.resid || a.ksplit > 1 || (a.out_b && (a.ldob & 7)) || (a.out_bt && ((a.ldobt & 7) || a.ldobt < a.M)) ||
-          (a.mask_src && (a.ldmask & 3)))
-        return hipErrorInvalidValue;
-      a_in.kernel_cls = RPR_K_GEMM;
-      return launch_256(a, s);
-    }
-    const long t128b = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    // (A kernel with 128x128 wave tiles — 256x256 block, four waves, one per SIMD, 512 registers: two thirds of the LDS reads
-    // per MFMA — was built and measured: 31-34 us per 256x256x768 tile against 23 us for this shape on the 128-row kernel
-    // and 60-65 us against 54-58 on the ping-pong kernel. With ONE wave per SIMD the 16 LDS-DMA pieces and 32 fragment reads
-    // of a K-tile are issued by the wave that also issues the 64 MFMAs, in series: ~2.2 us per K-tile again. Source kept
-    // as tools/gemm_bf16_w128.hip.txt; HISTORY.md.)
-    if (a.K >= 2048) {
-      const hipError_t e = launch_256_splitk(a, s);
-      if (e != hipErrorNotSupported) { if (e == hipSuccess) a_in.kernel_cls = RPR_K_GEMM; return e; }
-    }
-    if (a.part && a.K >= 2048 && t128b * 2 < SPLITK_TARGET && !a.relu && a.split_n >= a.N && (a.N & 3) == 0 && (a.ldo[0] & 3) == 0 &&
-        (!a.resid || (a.ldr & 3) == 0)) {
-      const long t = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-      long ks = std::min<long>((SPLITK_TARGET + t - 1) / t, a.K / 1024);
-      ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-      ks = trim_ks(ks, a.K / (2 * HBK));
-      if (ks > 1) return launch_splitk(a, (int)ks, false, launch_cfg<128, 64, 2, 2, true>, s);
-    }
-    const long t256b = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    constexpr int bf_pp = 200;   // min tiles of 256^2
-    if (t256b >= bf_pp) return launch_256(a, s);     // ping-pong 256x256 tiles when they fill the chip
-    return t128b < 256 ? launch_cfg<128, 64, 2, 2, true>(a, s) : launch_cfg<128, 128, 2, 2, true>(a, s);
-  }
-  static const int force = [] { const char* e = dev_getenv("RPR_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-  // 256-tile rounds on the 256 CUs: a launch just over a whole number of rounds (e.g. 288 tiles) leaves most of the
-  // chip idle in its last round; the 128-tile kernels quantise finer (measured M = 8192, N = 2304: 135 vs 151 us)
-  const int cus = a.cus > 0 ? a.cus : 256;         // a lane stream owns part of the chip: thresholds scale with it
-  const double round_eff = (double)t256 / (double)(((t256 + cus - 1) / cus) * cus);
-  if (force == 256 || (force == 0 && t256 >= 112L * cus / 256 && (round_eff >= 0.6 || a.out_h || a.row_ssq))) {
-    a_in.kernel_cls = RPR_K_GEMM;
-    // Row split of a launch just over a whole number of rounds (beam 1000 with one query: 318 tiles of 256^2 for the
-    // N = 768 products = 1.24 rounds, the second one with 62 of 256 CUs busy): the row tiles that fill whole rounds go to
-    // the ping-pong kernel, the rows behind them to the 128 x 128 tile kernel (a quarter of the work per block, 1.22 x the
-    // time per flop), as a second launch on the same stream. Taken when the estimate — whole rounds + 0.43 per round of
-    // 128^2 tiles (measured: 5240 rows x 768 columns = 246 such tiles in 35.7 us against 87.1 us for the 255 tiles of 256^2
-    // in front of them, profiles/archive/r05x_rowsplit_gemm.txt) + ~6 us for the second launch — is under 0.9 of the rounds the
-    // ping-pong kernel alone would need. RPR_GEMM_ROWSPLIT=0: off; =2 (tests): every launch of this route with two or more
-    // row tiles is split in the middle.
-    static const int row_split = [] { const char* e = dev_getenv("RPR_GEMM_ROWSPLIT"); return e ? atoi(e) : 1; }();
-    const bool split_all = row_split == 2 && a.M > 256;
-    if (row_split && (force == 0 || split_all) && !a.rm_B && a.ksplit <= 1 && a.small_live == 0 && (!a.no_row_split || split_all) &&
-        (t256 > cus || split_all)) {
-      const int tiles_n = (a.N + 255) / 256;
-      const long rounds = t256 / cus;
-      const int rows_main = split_all ? ((a.M + 255) / 256 / 2) * 256 : (int)((rounds * cus) / tiles_n) * 256, m_rest = a.M - rows_main;
-      if ((t256 % cus != 0 || split_all) && rows_main > 0 && m_rest > 0) {
-        const long t128r = (long)((m_rest + 127) / 128) * ((a.N + 127) / 128);
-        const double tile_us = 78.0 * a.K / 768.0;
-        const double cost_split = (double)rounds + 0.43 * (double)((t128r + cus - 1) / cus) + 6.0 / tile_us;
-        if (split_all || cost_split < 0.9 * (double)(rounds + 1)) {
-          static const int log_split = [] { const char* e = dev_getenv("RPR_GEMM_ROWSPLIT_LOG"); return e ? atoi(e) : 0; }();
-          if (log_split) fprintf(stderr, "[rowsplit] M=%d N=%d K=%d: %d rows on 256x256 tiles, %d on 128x128\n", a.M, a.N, a.K, rows_main, m_rest);
-          GemmH2Args main_p = a, rest = a;
-          main_p.M = rows_main;
-          rest.M = m_rest; rest.m_base = a.m_base + rows_main;
-          rest.A = a.A + (size_t)rows_main * a.lda;
-          for (int i = 0; i < 3; ++i) if (a.out[i]) rest.out[i] = a.out[i] + (size_t)rows_main * a.ldo[i];
-          if (a.out_h) rest.out_h = a.out_h + (size_t)rows_main * a.ldoh;
-          if (a.resid) rest.resid = a.resid + (size_t)rows_main * a.ldr;
-          if (a.resid_h) rest.resid_h = a.resid_h + (size_t)rows_main * a.ldrh;
-          if (a.row_ssq) rest.row_ssq = a.row_ssq + rows_main;
-          if (a.ssq_out) rest.ssq_out = a.ssq_out + rows_main;
-          hipError_t e = launch_256(main_p, s);
-          if (e != hipSuccess) return e;
-          return launch_cfg<128, 128>(rest, s);
-        }
-      }
-    }
-    return launch_256(a, s);
-  }
-  // a handful of rows (one to a few queries in flight): the launch is a weight stream; a 128-row tile would spend
-  // most of the per-CU LDS-DMA rate (~25 GB/s) on padding rows, and 32-wide column tiles give 4x the blocks
-  // 33 .. ~1500 rows (a handful to ~150 queries in flight, the tail pass of one query, beam 1000 at batch 1): wave-split tiles,
-  // shape and K split from choose_wsplit (RPR_WSPLIT_CFG / RPR_WSPLIT_KS force them; RPR_GEMM_WSPLIT_MAX = 0: the routes below)
-  static const int wsplit_max = [] { const char* e = dev_getenv("RPR_GEMM_WSPLIT_MAX"); return e ? atoi(e) : 1400; }();
-  static const int wsplit_cfg = [] { const char* e = dev_getenv("RPR_WSPLIT_CFG"); return e ? atoi(e) : -1; }();
-  static const int wsplit_ks = [] { const char* e = dev_getenv("RPR_WSPLIT_KS"); return e ? atoi(e) : 0; }();
-  if (force == 0 && a.M > 32 && a.M <= wsplit_max) {
-    const bool can_split = a.part && a.mid_split && !a.m_dev && (a.N & 63) == 0;
-    WsplitChoice ch = choose_wsplit(a.M, a.N, a.K, a.cus > 0 ? a.cus : 256, can_split, a.part_cap);
-    // beyond the 32 x 32 tile's old range the 128 x 64 split-K route is as fast once the best wave-split shape needs a second
-    // round of blocks (measured at 640 rows: N = 2304 / 3072 27.8 / 28.9 us against 28.9 / 30.0): those launches stay where they were
-    const bool take = a.M <= skinny || ch.rounds <= 1 || wsplit_cfg >= 0;
-    if (wsplit_cfg >= 0 && wsplit_cfg <= 2) ch.cfg = wsplit_cfg;
-    if (wsplit_ks > 0 && (wsplit_ks == 1 || (can_split && (size_t)a.M * a.N * wsplit_ks <= a.part_cap && a.K / wsplit_ks >= 64))) ch.ks = wsplit_ks;
-    const TileLaunch go = ch.cfg == 0 ? launch_wsplit_cfg<1, 1, 4> : ch.cfg == 1 ? launch_wsplit_cfg<2, 1, 3> : launch_wsplit_cfg<2, 2, 2>;
-    if (take && ch.ks <= 1) return go(a, s);
-    if (take) return launch_splitk(a, ch.ks, true, go, s);
-  }
-  if (force == 0 && a.M <= skinny) return launch_skinny(a);   // (with m_dev: row tiles past the live rows exit)
-  const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-  // A few hundred to a few thousand rows in flight (beam 1000 with one query, beam 100 with a dozen, beam 10 with
-  // 40-400): the 128x64 launch has fewer blocks than CUs and each walks all of K alone (24-96 K-tiles at ~1 us).
-  // Split K over blockIdx.y into the caller's scratch and run the fused epilogue as its own launch.
-  if (force == 0 && a.part && a.mid_split && !a.m_dev && (a.N & 63) == 0 && a.K >= 512) {
-    const long t = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-    constexpr int ks_cap = 4;
-    long ks = std::min<long>(std::min<long>((3L * cus / 2 + t - 1) / t, ks_cap), a.K / 128);
-    ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-    ks = trim_ks(ks, a.K / HBK);
-    if (ks > 1 && t < cus) return launch_splitk(a, (int)ks, true, launch_cfg<128, 64>, s);
-  }
-  // split-K: the caller lent scratch for partial results and the launch is a long reduction into few tiles
-  if (a.part && a.K >= 2048 && t128 * 2 < SPLITK_TARGET && !a.mid_split) {
-    const hipError_t e = launch_256_splitk(a, s);
-    if (e != hipErrorNotSupported) { if (e == hipSuccess) a_in.kernel_cls = RPR_K_GEMM; return e; }
-  }
-  if (a.part && a.K >= 2048 && t128 * 2 < SPLITK_TARGET && !a.out_h && !a.ssq_out && !a.row_ssq && !a.relu && !a.resid_h &&
-      !a.m_dev && a.split_n >= a.N && (a.N & 3) == 0 && (a.ldo[0] & 3) == 0 && (!a.resid || (a.ldr & 3) == 0)) {
-    const long t = (long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-    long ks = std::min<long>((SPLITK_TARGET + t - 1) / t, a.K / 1024);
-    ks = std::min<long>(ks, (long)(a.part_cap / ((size_t)a.M * a.N)));
-    ks = trim_ks(ks, a.K / HBK);
-    if (ks > 1) return launch_splitk(a, (int)ks, false, launch_cfg<128, 64>, s);
-  }
-  const bool narrow = force ? (force == 64) : (t128 < 256);
-  return narrow ? launch_cfg<128, 64>(a, s) : launch_cfg<128, 128>(a, s);
+  return hipSuccess;
 }
 
 // fp32 [rows, cols] -> two f16 planes [2][rows][cols] (weights at load time, generic activations)
