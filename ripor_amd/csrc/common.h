@@ -257,7 +257,7 @@ hipError_t launch_embed_rows(const float* table, const int32_t* ids, float* out,
 // Packed encoder rows: offs[q] = sum of lens[<q] (offs[Q] = live rows), row_src[offs[q] + j] = q * Lq + j
 hipError_t launch_pack_rows(const int32_t* lens, int32_t* offs, int32_t* row_src, int Q, int Lq, hipStream_t s);
 // x[r] = t==0 ? start : in_embeds[t-1][tokens[r][t-1]]
-// rows_dev (nullable): live row count on the device (a compacted stage of the forced-tail search, api.hip)
+// rows_dev (nullable): live row count on the device (a compacted stage of the forced-tail search, passes.hip)
 hipError_t launch_dec_embed(const float* start, const float* in_embeds, const uint16_t* tokens, int tok_ld,
                             float* out, int R, int d, int V, int t, hipStream_t s, XOut xo = XOut{},
                             const int* rows_dev = nullptr);
@@ -406,7 +406,7 @@ hipError_t launch_zero_u64(unsigned long long* p, size_t n, hipStream_t s);
 hipError_t launch_mask_lengths(const int32_t* mask, int32_t* lens, int Q, int Lq, hipStream_t s,
                                unsigned int* status = nullptr);
 
-// ---- forced-tail evaluation (tail_kernels.hip; orchestration in api.hip) -------------------------------------------
+// ---- forced-tail evaluation (tail_kernels.hip; orchestration in passes.hip) ----------------------------------------
 // Once every beam of a query stands on a trie node under which a single distinct sequence remains, beam search can no
 // longer prune for that query: each beam has exactly one valid child per step, the B valid candidates beat every
 // masked one (-1e9) and the remaining tokens are the rest of the beam's code row. Such a query leaves the sequential
@@ -418,7 +418,7 @@ struct ForkArgs {
   const uint16_t* codes; int Lc;
   int Qcap; const int* nq_dev;   // stage capacity / live queries (nullable = Qcap)
   int B, T, L;
-  double spread_max;         // forced only if max - min of the query's beam scores is below this (see api.hip)
+  double spread_max;         // forced only if max - min of the query's beam scores is below this (see passes.hip: enqueue_fork)
   int32_t* flag;             // out [Qcap]: 1 = forced
 };
 hipError_t launch_fork_classify(const ForkArgs& a, hipStream_t s);

@@ -1,5 +1,5 @@
-// Internal declarations shared by the translation units behind the C ABI (api.hip: search path, train_api.hip: the
-// training step). Not part of the ABI: include/ripor_hip.h is.
+// Internal declarations shared by the translation units behind the C ABI (api.hip: the ABI and the search driver,
+// passes.hip: the forward passes it enqueues, train_api.hip: the training step). Not part of the ABI: include/ripor_hip.h is.
 #pragma once
 #include <map>
 #include <memory>
@@ -50,7 +50,7 @@ struct rpr_model {
   size_t params_total = 0;
   // bound of |logit| for any decoder state: sqrt(d_model) * max row norm of the output codebooks times the final
   // layer-norm weight (Cauchy-Schwarz on the RMS-normalised hidden state), times the scaleup factor; computed at load.
-  // The forced-tail fork uses it to prove that no masked (-1e9) candidate can overtake a valid one (api.hip).
+  // The forced-tail fork uses it to prove that no masked (-1e9) candidate can overtake a valid one (passes.hip: enqueue_fork).
   float logit_bound = INFINITY;
   int inner() const { return d.num_heads * d.d_kv; }
   ~rpr_model() {   // device memory goes with the object, also on the error paths of rpr_load_model
@@ -112,7 +112,7 @@ struct GraphKey {
   }
 };
 
-// Forced-tail search (api.hip::enqueue_search): a compacted batch of queries that goes on step by step after a fork
+// Forced-tail search (passes.hip::enqueue_search): a compacted batch of queries that goes on step by step after a fork
 struct StageBufs {
   DevBuf qmap;              // int32 [cap]: stage query -> query of the call
   DevBuf cnt;               // int32 [4]: live queries, live rows (queries x beams)
@@ -275,5 +275,43 @@ struct Launcher {
     }
   }
 };
+
+// ---- the forward passes (passes.hip) and the linear layer they are made of --------------------------------------------
+// One linear layer C = act(A @ W^T) (+ residual). A and W are given in both representations; the
+// ctx precision picks the exact fp32 MFMA kernel or the f16x2 split kernel.
+struct LinIn {                                                               // activation [M, K]
+  const float* f; const __half* h; size_t ps; int ld; float scale = A_PLANE_SCALE;   //   fp32 / planes (+ their scale)
+  const unsigned long long* ssq = nullptr; float inv_d_fix = 0.f, eps = 0.f;         //   fused RMSNorm: h = planes of x, W folded
+};
+struct LinW {                                                                // weight [N, K] (+ planes)
+  const float* f; const __half* h; int N, K;                                 //   N: fp32 rows = columns the profile accounts
+  size_t ps = 0;                                                             //   plane stride (0 = N * K)
+  int Nh = 0;                                                                //   rows of a plane padded beyond N (0 = N): what the split kernel computes
+  bool no_scratch = false;                                                   //   the ctx's split-K scratch is not lent to this product: the mid-size
+                                                                             //   split-K route (gemm_route.h: part, mid_split) stays closed to it
+  bool row_split_ok = false;                                                 //   the ctx's cur_no_row_split does not reach this product
+};
+struct LinOut {                                                              // destination
+  float* f[3]; int ldo[3]; int split_n;                                      //   fp32 (up to 3 column blocks)
+  __half* h; size_t ps; int ldh;                                             //   or f16 planes (next GEMM's input)
+  const float* resid; int relu;
+  int rm_B; size_t rm_stride, rm_slot, rm_head;                              //   KV-cache element map (common.h)
+  int rm_dshift;                                                             //   log2(d_kv) of the map (0 = 6)
+  float plane_scale;                                                         //   scale of the planes written to h (0 = 1)
+  const __half* resid_h; unsigned long long* ssq_out;                        //   fused RMSNorm producer: residual read from the
+};                                                                           //   planes h (in place), row sums accumulated
+LinOut out_f32(float* p, int ld, int N, const float* resid = nullptr, int relu = 0);
+// m_dev (nullable): device-side live row count (packed encoder); m_acc = rows to account flops/bytes for
+void linear(Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, const int* m_dev = nullptr, int m_acc = -1);
+// forks: depths at which forced queries leave the sequential steps (ascending, each in [1, L-1]; empty = plain search)
+// drop_last: no stage after the last fork (optimistic mode, see choose_forks): its caches are not needed
+int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L, const std::vector<int>& forks = {},
+                    bool drop_last = false, bool log_softmax = false);
+int alloc_train_workspace(rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L);
+void enqueue_encoder(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int Q, int Lq, bool packed);
+void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, int Q, int Lq, int B, int L,
+                    unsigned flags, const rpr_debug_taps* taps, const std::vector<int>& forks, bool drop_last);
+void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L,
+                           const int32_t* codes /*[bz, ndoc, L]*/, float* pos_scores /*[bz, ndoc, L]*/);
 
 }  // namespace rpr

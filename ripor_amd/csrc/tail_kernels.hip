@@ -1,6 +1,6 @@
 // Forced-tail evaluation of the trie-constrained beam search (gfx950, wave64): the fork (which queries can no longer
 // be pruned, compaction of the others into the next stage) and the kernels of the teacher-forced tail pass that are
-// not shared with the sequential steps. Orchestration: api.hip::enqueue_search.
+// not shared with the sequential steps. Orchestration: passes.hip::enqueue_search.
 //
 // Semantics preserved (reference t5_pretrainer/tasks/generation.py): per step, candidate = ((double)logit_f32 +
 // (valid ? 0 : -1e9)) + beam_score in float64 (:453-463); the first B of the sorted candidates become the new beams in
@@ -1443,7 +1443,7 @@ hipError_t launch_tail_gold(const float* x, const float* ln, const float* out_em
 
 // RPR_FLAG_LOG_SOFTMAX: the score of a position is the log-probability of its token (reference generation.py:453-455:
 // log_softmax over the V logits of the position in fp32). One wave per tail row: logits = the row's V exact-fp32 logits
-// (one GEMM per position, api.hip::enqueue_tail), arithmetic as select_kernel's: (x - max) - log(sum exp(x - max)).
+// (one GEMM per position, passes.hip::enqueue_tail), arithmetic as select_kernel's: (x - max) - log(sum exp(x - max)).
 __global__ __launch_bounds__(256) void tail_logprob_kernel(const float* __restrict__ logits, const uint16_t* __restrict__ tokens,
                                                             float* __restrict__ gold, int rows, const int* __restrict__ rows_dev, int T,
                                                             int L, int V) {

@@ -12,7 +12,7 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAP = 16 << 20          # floats of split-K scratch lent by the caller
-SEARCH = dict(part=1, mid_split=1, part_cap=CAP)   # what the search path's projections set (api.hip)
+SEARCH = dict(part=1, mid_split=1, part_cap=CAP)   # what the search path's projections set (passes.hip: linear)
 INT_MAX = 0x7fffffff
 
 

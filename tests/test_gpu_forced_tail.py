@@ -1,5 +1,5 @@
 """-m gpu: the forced-tail evaluation (rpr_search's forks + teacher-forced tail passes, ripor_amd/csrc/api.hip,
-tail_kernels.hip) against the plain step-by-step loop and against the CPU oracle.
+passes.hip, tail_kernels.hip) against the plain step-by-step loop and against the CPU oracle.
 
 The step-by-step loop is what the reference does (tasks/generation.py:423-540, one model call + mask + top-k per
 position) and is itself pinned to the reference's golden vectors (test_gpu_parity.py, which also runs every golden with
