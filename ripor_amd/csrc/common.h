@@ -112,7 +112,7 @@ struct GemmArgs {
 };
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 
-// ---- residual quantization (gemm_f32.hip; rpr_rq_train / rpr_rq_encode in train_api.hip) ----------------------------
+// ---- residual quantization (gemm_f32.hip; rpr_rq_train / rpr_rq_encode in rq_api.hip) -------------------------------
 // Greedy residual k-means (DESIGN.md "Residual quantization"). Row tile of the assign kernel: 128 rows; d % 32 == 0,
 // K % 64 == 0, K <= 1024.
 constexpr int RQ_BM = 128, RQ_SORT_ROWS = 256, RQ_MAX_K = 1024;

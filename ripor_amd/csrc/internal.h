@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units behind the C ABI (api.hip: the ABI and the search driver,
-// passes.hip: the forward passes it enqueues, train_api.hip: the training step). Not part of the ABI: include/ripor_hip.h is.
+// passes.hip: the forward passes it enqueues, train_api.hip: the training step, rq_api.hip: docid creation). Not part of the ABI: include/ripor_hip.h is.
 #pragma once
 #include <map>
 #include <memory>
@@ -152,7 +152,7 @@ struct Workspace {
   TailBufs tail[MAX_FORKS];
   DevBuf t_x, t_h, t_qkv, t_q, t_attn, t_ff, t_x_h, t_attn_h, t_ff_h, t_ssq;
   DevBuf t_logits;        // log-softmax mode: the V logits of every tail row (fp32)
-  // residual quantization (rpr_rq_train / rpr_rq_encode, train_api.hip): residuals [n, d], codes, counting-sort
+  // residual quantization (rpr_rq_train / rpr_rq_encode, rq_api.hip): residuals [n, d], codes, counting-sort
   // histogram / row order, codeword norms, per-block fp64 sums of |r|^2, initial centroid rows
   DevBuf rq_r, rq_code, rq_hist, rq_order, rq_cnorm, rq_part, rq_idx;
 };

@@ -1,0 +1,112 @@
+// Docid creation behind the C ABI: rpr_rq_train / rpr_rq_encode (kernels in gemm_f32.hip, buffers in the search workspace).
+#include <vector>
+
+#include "internal.h"
+
+using namespace rpr;
+
+extern "C" {
+
+// ---- residual quantization: docid creation (reference: faiss.IndexResidualQuantizer in tasks/evaluator.py:405-421) ------
+// Greedy residual k-means, DESIGN.md "Residual quantization": Lloyd iterations of the fused assign kernel and the
+// deterministic centroid update (gemm_f32.hip) per level, the residuals of the training rows in the ctx workspace.
+
+static int rq_check(rpr_ctx* c, const float* x, int64_t n, int32_t d, int32_t M, int32_t K, const void* out) {
+  RPR_REQUIRE(c && x && out, "NULL argument");
+  RPR_REQUIRE(n >= 1 && n <= (int64_t)1 << 30, "row count out of range (1 .. 2^30 per call)");
+  RPR_REQUIRE(d >= 32 && d % 32 == 0, "d must be a positive multiple of 32");
+  RPR_REQUIRE(K >= 64 && K % 64 == 0 && K <= RQ_MAX_K, "K must be a multiple of 64 and at most 1024");
+  RPR_REQUIRE(M >= 1 && M <= 4096, "M out of range");
+  return RPR_OK;
+}
+
+static int rq_ws(rpr_ctx* c, int64_t n, int32_t d, int32_t M, int32_t K, bool train) {
+  Workspace& w = c->ws;
+  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM), nb = (size_t)((n + RQ_SORT_ROWS - 1) / RQ_SORT_ROWS);
+  int e = ensure(c, w.rq_r, (size_t)n * d * sizeof(float));
+  if (!e) e = ensure(c, w.rq_cnorm, (size_t)M * K * sizeof(float));
+  if (!e) e = ensure(c, w.rq_part, (size_t)M * nblk * sizeof(double));
+  if (train) {
+    if (!e) e = ensure(c, w.rq_code, (size_t)n * sizeof(uint16_t));
+    if (!e) e = ensure(c, w.rq_hist, ((size_t)K * nb + 1) * sizeof(int));
+    if (!e) e = ensure(c, w.rq_order, (size_t)n * sizeof(int));
+    if (!e) e = ensure(c, w.rq_idx, (size_t)M * K * sizeof(int));
+  }
+  return e;
+}
+
+// sum of the per-block |r|^2 partials of every level, block by block (host, fp64)
+static int rq_level_sums(rpr_ctx* c, int64_t n, int32_t M, double* out, hipStream_t s) {
+  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM);
+  std::vector<double> part((size_t)M * nblk);
+  RPR_HIP(hipMemcpyAsync(part.data(), c->ws.rq_part.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  RPR_HIP(hipStreamSynchronize(s));
+  for (int m = 0; m < M; ++m) {
+    double t = 0.0;
+    for (size_t b = 0; b < nblk; ++b) t += part[(size_t)m * nblk + b];
+    out[m] = t;
+  }
+  return RPR_OK;
+}
+
+int rpr_rq_train(rpr_ctx* c, const float* x, int64_t n, int32_t d, int32_t M, int32_t K, int32_t niter, const int32_t* init_idx,
+                 float* codebooks, double* level_mse, void* stream) {
+  { const int e = rq_check(c, x, n, d, M, K, codebooks); if (e) return e; }
+  RPR_REQUIRE(init_idx, "NULL init_idx");
+  RPR_REQUIRE(n >= K, "fewer training rows than codewords");
+  RPR_REQUIRE(niter >= 0 && niter <= 10000, "niter out of range");
+  for (int64_t i = 0; i < (int64_t)M * K; ++i) RPR_REQUIRE(init_idx[i] >= 0 && init_idx[i] < n, "init_idx entry out of range");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  { const int e = rq_ws(c, n, d, M, K, true); if (e) return e; }
+  Workspace& w = c->ws;
+  float* R = static_cast<float*>(w.rq_r.p);
+  uint16_t* code = static_cast<uint16_t*>(w.rq_code.p);
+  float* cnorm = static_cast<float*>(w.rq_cnorm.p);
+  int* idx = static_cast<int*>(w.rq_idx.p);
+  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM);
+  RPR_HIP(hipMemcpyAsync(R, x, (size_t)n * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+  RPR_HIP(hipMemcpyAsync(idx, init_idx, (size_t)M * K * sizeof(int), hipMemcpyHostToDevice, s));
+  RPR_HIP(hipStreamSynchronize(s));   // init_idx is the caller's
+  for (int m = 0; m < M; ++m) {
+    float* Cm = codebooks + (size_t)m * K * d;
+    RPR_HIP(launch_rq_gather(R, d, idx + (size_t)m * K, K, Cm, s));
+    RPR_HIP(launch_rq_norms(Cm, K, d, cnorm, s));
+    RqAssignArgs a{R, (int)n, d, Cm, cnorm, K, code, 1, nullptr};
+    for (int it = 0; it < niter; ++it) {
+      RPR_HIP(launch_rq_assign(a, s));
+      RPR_HIP(launch_rq_update(R, (int)n, d, code, K, static_cast<int*>(w.rq_hist.p), static_cast<int*>(w.rq_order.p), Cm, cnorm, s));
+    }
+    a.part = static_cast<double*>(w.rq_part.p) + (size_t)m * nblk;   // final assignment, R -= C_m[code]
+    RPR_HIP(launch_rq_assign(a, s));
+  }
+  if (level_mse) {
+    { const int e = rq_level_sums(c, n, M, level_mse, s); if (e) return e; }
+    for (int m = 0; m < M; ++m) level_mse[m] /= (double)n;
+  }
+  return RPR_OK;
+}
+
+int rpr_rq_encode(rpr_ctx* c, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K, uint16_t* codes,
+                  double* level_sse, void* stream) {
+  { const int e = rq_check(c, x, n, d, M, K, codebooks); if (e) return e; }
+  RPR_REQUIRE(codes, "NULL codes");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  { const int e = rq_ws(c, n, d, M, K, false); if (e) return e; }
+  Workspace& w = c->ws;
+  float* R = static_cast<float*>(w.rq_r.p);
+  float* cnorm = static_cast<float*>(w.rq_cnorm.p);
+  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM);
+  RPR_HIP(hipMemcpyAsync(R, x, (size_t)n * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+  RPR_HIP(launch_rq_norms(codebooks, M * K, d, cnorm, s));
+  for (int m = 0; m < M; ++m) {
+    RqAssignArgs a{R, (int)n, d, codebooks + (size_t)m * K * d, cnorm + (size_t)m * K, K, codes + m, M,
+                   static_cast<double*>(w.rq_part.p) + (size_t)m * nblk};
+    RPR_HIP(launch_rq_assign(a, s));
+  }
+  if (level_sse) return rq_level_sums(c, n, M, level_sse, s);
+  return RPR_OK;
+}
+
+}  // extern "C"

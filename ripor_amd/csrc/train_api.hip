@@ -11,6 +11,7 @@
 // before the split; in RPR_PREC_F32 mode the exact-fp32 MFMA kernel (gemm_f32.hip). The reference trains under bf16
 // autocast: both are the more precise side. The backward products reuse the forward kernels on transposed operands
 // (train_kernels.hip); the reductions are deterministic (fixed-order partials, fixed-point integer atomics).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <unordered_map>
@@ -20,44 +21,155 @@
 
 using namespace rpr;
 
+struct TrainWs;
+namespace { int tensure(rpr_ctx* c, DevBuf& b, size_t bytes); }   // allocate or grow a buffer of the training workspace
+
+// The weight-gradient products dW[N, K] = dY^T X run on ONE side stream beside the input-gradient chain. This struct owns that
+// stream and all that lives by its clock; nothing outside it touches them. dW reduces over all rows of the batch into
+// 9 .. 36 tiles of 256 x 256: split-K over the rows and a reduce pass.
+// Measured, t5-base bz 128, against a whole-K route (one K-loop per 256 x 256 tile, products round-robin on 2-4 side
+// streams; removed): bf16 32.4 ms whole-K vs 32.7 split-K; f16x2 56.3 vs 52.3 (a lone 256 x 256 block walks 256 K-tiles
+// of the two-plane operands in 670 us and the side streams fall behind the main chain). And once the search path's two
+// CU-masked lane streams exist in the process, a second side stream lands on the main stream's hardware queue and the
+// step serialises (bf16 50 ms). The split-K route on ONE side stream does not depend on how the runtime maps streams to
+// queues.
+// Per-product route: the transposed-operand scratch rotates over NSIDE sets; a set is reused NSIDE products later, after
+// its product has finished. Grouped route (bf16 mode, where the shapes allow it; measured: DESIGN.md section 9): the dY^T
+// operands of one layer's products live side by side in one of two sets (a set is rewritten two layers later, after its
+// group launch has finished), the products are collected in `grp` while the layer's input-gradient chain is enqueued and
+// go out as ONE launch (gemm_h2_pp_group_kernel; gtab = the device table it reads its argument structs from).
+struct WGradSide {
+  static constexpr int NSIDE = 4, NGRP = 2;
+  // fork: recorded on the main stream, the side stream waits for it; done: recorded behind the side stream's work;
+  // pending: done has been recorded and the main stream has not been made to wait for it yet
+  struct Sync { hipEvent_t fork = nullptr, done = nullptr; bool pending = false; };
+  struct Set { DevBuf tX, tY; Sync sync; };   // X^T and dY^T of one product (fp32, two f16 planes or bf16)
+  enum Fit { FIT_OPEN, FIT_EMPTY, FIT_NONE };
+  // a dY the producing dX product's epilogue left converted: bf16 rows, and the transposed copy in a reserved slot of `gset`
+  struct Pre { const float* dY = nullptr; const void* py = nullptr; __half* pyt = nullptr; int gset = -1; };
+
+  // set_bytes: one transposed operand; dyT_bytes: one layer's dY^T operands (0 = no grouped route: every mode but bf16)
+  int create(rpr_ctx* c, size_t set_bytes, size_t dyT_bytes) {
+    int e = 0;
+    for (Set& t : set) { if (!e) e = tensure(c, t.tX, set_bytes); if (!e) e = tensure(c, t.tY, set_bytes); }
+    static_assert(GemmGroupArgs::MAXP * sizeof(GemmH2Args) <= GemmGroupArgs::TABLE_BYTES, "argument table");
+    for (DevBuf& b : dyT) if (!e && dyT_bytes) e = tensure(c, b, dyT_bytes);
+    if (!e && dyT_bytes) e = tensure(c, gtab, GemmGroupArgs::SCRATCH_BYTES);
+    if (e || side) return e;
+    hipError_t he = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
+    each_sync([&](Sync& y) {
+      for (hipEvent_t* ev : {&y.fork, &y.done}) if (he == hipSuccess) he = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    });
+    RPR_HIP(he);
+    return 0;
+  }
+  void destroy() {   // the buffers go with the workspace's registry (free_train_ws)
+    each_sync([](Sync& y) { for (hipEvent_t ev : {y.fork, y.done}) if (ev) (void)hipEventDestroy(ev); });
+    if (side) (void)hipStreamDestroy(side);
+  }
+  // the next rotating scratch set: the product that last read it (NSIDE products ago) must be over before Ln's stream rewrites it
+  Set& next_set(Launcher& Ln) {
+    Set& t = set[flip++ % NSIDE];
+    wait(Ln, Ln.s, t.sync, true);
+    return t;
+  }
+  // f32 mode runs both products on the main stream and borrows the X^T buffer of set 0 (no product is pending between passes)
+  float* main_stream_scratch() const { return P<float>(set[0].tX); }
+  // body(L2) runs on the side stream after everything Ln's stream holds so far; Ln's stream goes on at once
+  template <class F> void run(Launcher& Ln, Sync& y, F&& body) {
+    if (Ln.err) return;
+    if (hipEventRecord(y.fork, Ln.s) != hipSuccess || hipStreamWaitEvent(side, y.fork, 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
+    Launcher L2{Ln.c, side};
+    body(L2);
+    if (L2.err) { Ln.err = L2.err; return; }
+    if (hipEventRecord(y.done, side) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
+    y.pending = true;
+  }
+  // stream x waits for every per-product launch (the last product of every set: stream order covers the earlier ones) /
+  // every group launch still in flight. clear: x is the main stream, the marks go; a communication stream leaves them
+  void wait_products(Launcher& Ln, hipStream_t x, bool clear) { for (Set& t : set) wait(Ln, x, t.sync, clear); }
+  void wait_groups(Launcher& Ln, hipStream_t x, bool clear) { for (Sync& y : gsync) wait(Ln, x, y, clear); }
+
+  // ---- the group collector. A product is dW[N, K] reduced over `rows` (padded), its dY^T slot [N][ld] bf16 (256-byte aligned)
+  static size_t slot_bytes(int N, int ld) { return (((size_t)N * ld * sizeof(__half)) + 255) & ~(size_t)255; }
+  static int tiles(int N, int K) { return ((N + 255) / 256) * ((K + 255) / 256); }
+  // does the product join the group being collected, only an empty group (flush first), or no group at all?
+  Fit fit(int N, int K, int rows, size_t slot) const {
+    if (tiles(N, K) > GemmGroupArgs::MAX_TILES || slot > dyT[gset].cap) return FIT_NONE;   // (the two sets have one size)
+    const bool open = grp.n > 0 && grp.K == rows && grp.n < GemmGroupArgs::MAXP && grp_tiles + tiles(N, K) <= GemmGroupArgs::MAX_TILES &&
+                      dyT_used + slot <= dyT[gset].cap;
+    return open ? FIT_OPEN : FIT_EMPTY;
+  }
+  __half* reserve(size_t slot) {   // after fit() said FIT_OPEN, or flush() and FIT_EMPTY
+    dyT_used += slot;
+    return reinterpret_cast<__half*>(static_cast<char*>(dyT[gset].p) + dyT_used - slot);
+  }
+  void add(const __half* dyT_slot, const void* xT, float* dW, int N, int K, int rows, int ld) {
+    const int i = grp.n++;
+    grp.A[i] = dyT_slot; grp.W[i] = reinterpret_cast<const __half*>(xT); grp.out[i] = dW;
+    grp.M[i] = N; grp.N[i] = K; grp.ldo[i] = K; grp.K = rows; grp.lda = ld; grp.ldw = ld;
+    grp_tiles += tiles(N, K);
+    grp_flops += 2.0 * N * (double)K * rows;
+    grp_bytes += 2.0 * ((double)N * rows + (double)K * rows) + 4.0 * (double)N * K;
+  }
+  // enqueue the products collected since the last flush on the side stream; the main stream goes on
+  void flush(Launcher& Ln) {
+    if (grp.n == 0 || Ln.err) return;
+    run(Ln, gsync[gset], [&](Launcher& L2) {
+      const GemmGroupArgs g = grp;
+      L2.run(RPR_K_GEMM, grp_flops, grp_bytes, [&] { return launch_gemm_h2_group(g, gtab.p, side); });
+    });
+    if (Ln.err) return;
+    clear_group();
+    gset ^= 1;
+    wait(Ln, Ln.s, gsync[gset], true);   // the next layer writes into the other set: its last group launch must be over
+  }
+  // a backward that aborted on Ln.err leaves collected-but-unflushed products behind: never carry them into the next pass
+  void reset() { clear_group(); pre = Pre{}; }
+  bool pre_is(const float* dY) const { return pre.dY == dY && pre.gset == gset; }
+  void leave_pre(const float* dY, const void* py, __half* pyt) { pre.dY = dY; pre.py = py; pre.pyt = pyt; pre.gset = gset; }
+  Pre take_pre() { const Pre p = pre; pre = Pre{}; return p; }
+  bool pre_left() const { return pre.dY != nullptr; }
+
+ private:
+  hipStream_t side = nullptr;
+  Set set[NSIDE];
+  unsigned flip = 0;
+  DevBuf dyT[NGRP], gtab;
+  Sync gsync[NGRP];
+  GemmGroupArgs grp = {};
+  int gset = 0, grp_tiles = 0;
+  size_t dyT_used = 0;
+  double grp_flops = 0, grp_bytes = 0;
+  Pre pre;
+  template <class F> void each_sync(F&& f) { for (Set& t : set) f(t.sync); for (Sync& y : gsync) f(y); }
+  void clear_group() { grp.n = 0; grp_tiles = 0; grp_flops = grp_bytes = 0; dyT_used = 0; }
+  static void wait(Launcher& Ln, hipStream_t x, Sync& y, bool clear) {
+    if (!y.pending) return;
+    if (hipStreamWaitEvent(x, y.done, 0) != hipSuccess) Ln.err = RPR_ERR_HIP;
+    if (clear) y.pending = false;
+  }
+};
+
 struct TrainWs {
+  std::vector<DevBuf*> bufs;   // every buffer tensure() has allocated, wherever it lives: what free_train_ws frees
   // saved forward activations
-  DevBuf enc_act, dec_act, enc_out, xkv, x_last, scores, margins, dscores, in_idx, out_idx, tok_idx;
+  DevBuf enc_act, dec_act, enc_out, xkv, x_last, scores, margins, dscores, in_idx, out_idx;
   // seq2seq head: the decoder's last hidden state (after the final norm), dlogits of every row, the row losses
   DevBuf hF, dlog, row_loss;
   // scratch
   DevBuf h, dxa, dxb, dbig, dattn, dxkv, denc, tA, wT, w_part, bias_part, fix, gn_part, gn_out, amax, part, part2;
-  // The weight-gradient GEMMs run on a side stream beside the input-gradient chain. dW[N, K] = dY^T X reduces over all
-  // rows of the batch into 9 .. 36 tiles of 256 x 256: split-K over the rows and a reduce pass (Bwd). The transposed-operand
-  // scratch rotates over NSIDE sets: a set is reused NSIDE dxdw calls later, after its product has finished (ev_done).
-  static constexpr int NSIDE = 4;
-  DevBuf tB[NSIDE], tC[NSIDE];
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork[NSIDE] = {}, ev_done[NSIDE] = {};
-  bool done_pending[NSIDE] = {};
-  int flip = 0;
-  std::vector<hipEvent_t> bucket_ev;   // gradient buckets handed to the caller's communication stream (2 events each)
+  WGradSide side;
+  std::vector<hipEvent_t> bucket_ev;   // gradient buckets handed to the caller's communication stream (one event each)
   // bf16 mode: the GEMM weights are converted once per step (plain + transposed copies at the tensors' offsets of the flat
   // parameter layout) instead of once per GEMM call, and the forward pass leaves the transposed bf16 copy of every
   // linear layer's input behind — the X^T operand of its weight-gradient product — so the backward pass neither converts
   // X again nor recomputes the normalised inputs it would only need for that
   DevBuf wc, wcT, wseg, wpref, xT;
-  // bf16 mode, grouped weight gradients: the dY^T operands of one layer's products live side by side in one of two sets
-  // (a set is rewritten two layers later, after its group launch has finished: ev_gdone), the products are collected in
-  // `grp` while the layer's input-gradient chain is enqueued and go out as ONE launch on the side stream (gtab = the
-  // device table the launch reads its argument structs from)
-  DevBuf dyT[2], gtab;
   // bf16 mode, round 6: the feed-forward block's wide intermediate leaves its producing GEMM's epilogue in bf16 (rows here, the
   // transposed copy in the consumer's X^T / dY^T slot) instead of through a conversion launch: relu(h Wi^T) in the forward
   // pass, the masked gradient w.r.t. it in the backward pass (GemmH2Args::out_b / out_bt / mask_src)
   DevBuf bfb;
-  struct Pre { const float* dY = nullptr; const void* py = nullptr; __half* pyt = nullptr; int gset = -1; } pre;   // a dY the producer left converted
-  hipEvent_t ev_gfork[2] = {}, ev_gdone[2] = {};
-  bool gdone_pending[2] = {};
-  GemmGroupArgs grp = {};
-  int gset = 0, grp_tiles = 0;
-  size_t dyT_used = 0;
-  double grp_flops = 0, grp_bytes = 0;
   DevBuf aseg, apref;                  // rpr_adamw_step: one launch over all tensors (table built once per model)
   const rpr_model* aw_model = nullptr;
   int aw_nseg = 0, aw_chunks = 0;
@@ -114,6 +226,8 @@ size_t param_offset(const rpr_model* m, int kind, int layer) {
 
 int tensure(rpr_ctx* c, DevBuf& b, size_t bytes) {   // like ensure(), without touching the search graphs
   if (bytes <= b.cap) return 0;
+  auto& bufs = c->tws->bufs;
+  if (std::find(bufs.begin(), bufs.end(), &b) == bufs.end()) bufs.push_back(&b);
   if (b.p) { RPR_HIP(hipFree(b.p)); c->tws->bytes -= b.cap; b.p = nullptr; b.cap = 0; }
   const size_t want = (bytes + 255) & ~(size_t)255;
   RPR_HIP(hipMalloc(&b.p, want));
@@ -167,8 +281,6 @@ void gemm_planes(Launcher& Ln, const Planes& A, const Planes& B, float* C, int l
          &g.kernel_cls);
 }
 
-// C[M, N] = act(A[M, K] B[N, K]^T) (+ resid): exact fp32 MFMA, or (split-precision mode) f16x2 planes with dynamic scales
-// one bf16 plane per operand, one MFMA per product (RPR_PREC_BF16)
 // bf16 outputs of the epilogue (256 x 256 kernel only; see GemmH2Args::out_b): rows [M][N], transposed [N][ldt], optional mask
 struct BOut { void* rows = nullptr; void* tr = nullptr; int ldt = 0; const float* mask = nullptr; };
 // a product whose result may leave its epilogue as bf16 operands: whole 256 x 256 tiles, and as many of them as send a bf16
@@ -195,6 +307,8 @@ void gemm_bf16(Launcher& Ln, const void* A, int lda, const void* B, int ldb, flo
          &g.kernel_cls);
 }
 
+// C[M, N] = act(A[M, K] B[N, K]^T) (+ resid): exact fp32 MFMA, or (split-precision mode) f16x2 planes with dynamic scales,
+// or one bf16 plane per operand, one MFMA per product (RPR_PREC_BF16)
 // save_xt (bf16 mode): where to leave the transposed copy [K][pad64(M)] (row stride ldT(M)) of A for the weight-gradient product
 // a_ready (bf16 mode): A's bf16 rows — and its transposed copy in save_xt — were written by the epilogue that produced A
 void gemm(Launcher& Ln, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
@@ -206,9 +320,8 @@ void gemm(Launcher& Ln, const float* A, int lda, const float* B, int ldb, float*
     if (lda != K || ldb != K) { Ln.err = RPR_ERR_INVALID; return; }
     hipStream_t s = Ln.s;
     const void* ab = a_ready ? a_ready : w.tA.p;
-    if (a_ready) {}
-    else if (save_xt) Ln.run(RPR_K_OTHER, 0, 8.0 * M * K, [&] { return launch_to_bf16_T(A, M, K, lda, pad64(M), save_xt, w.tA.p, s, nullptr, ldT(M)); });
-    else Ln.run(RPR_K_OTHER, 0, 6.0 * M * K, [&] { return launch_to_bf16(A, M, K, lda, w.tA.p, s); });
+    if (!a_ready && save_xt) Ln.run(RPR_K_OTHER, 0, 8.0 * M * K, [&] { return launch_to_bf16_T(A, M, K, lda, pad64(M), save_xt, w.tA.p, s, nullptr, ldT(M)); });
+    else if (!a_ready) Ln.run(RPR_K_OTHER, 0, 6.0 * M * K, [&] { return launch_to_bf16(A, M, K, lda, w.tA.p, s); });
     const void* wb = w.wT.p;
     auto it = w.wc_off.find(B);
     if (it != w.wc_off.end() && w.wc.p) wb = reinterpret_cast<const __half*>(w.wc.p) + it->second;   // converted once per step
@@ -323,165 +436,120 @@ int refresh_weight_cache(Launcher& Ln, rpr_ctx* c, rpr_model* m) {
 
 struct Bwd {
   Launcher& Ln; rpr_ctx* c; TrainWs& w; const Dims& D;
-  // Weight gradients: one side stream, split-K over the rows + a reduce pass per product.
-  // Measured, t5-base bz 128, against a whole-K route (one K-loop per 256 x 256 tile, products round-robin on 2-4 side
-  // streams; removed): bf16 32.4 ms whole-K vs 32.7 split-K; f16x2 56.3 vs 52.3 (a lone 256 x 256 block walks 256 K-tiles
-  // of the two-plane operands in 670 us and the side streams fall behind the main chain). And once the search path's two
-  // CU-masked lane streams exist in the process, a second side stream lands on the main stream's hardware queue and the
-  // step serialises (bf16 50 ms). The split-K route on ONE side stream does not depend on how the runtime maps streams to
-  // queues.
-  // bf16 mode: the weight gradients of a layer as one grouped launch (gemm_h2_pp_group_kernel) where the shapes allow it,
-  // else the per-product route. Measured, t5-base bz 128: see DESIGN.md section 9.
-  // enqueue the products collected since the last flush on the side stream; the main stream goes on
-  void flush_group() {
-    if (w.grp.n == 0 || Ln.err) return;
-    hipStream_t s = Ln.s, side = w.side;
-    const int gs = w.gset;
-    if (hipEventRecord(w.ev_gfork[gs], s) != hipSuccess || hipStreamWaitEvent(side, w.ev_gfork[gs], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-    Launcher L2{c, side};
-    const GemmGroupArgs grp = w.grp;
-    L2.run(RPR_K_GEMM, w.grp_flops, w.grp_bytes, [&] { return launch_gemm_h2_group(grp, w.gtab.p, side); });
-    if (L2.err) { Ln.err = L2.err; return; }
-    if (hipEventRecord(w.ev_gdone[gs], side) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-    w.gdone_pending[gs] = true;
-    w.grp.n = 0; w.grp_tiles = 0; w.grp_flops = w.grp_bytes = 0; w.dyT_used = 0;
-    w.gset = gs ^ 1;
-    if (w.gdone_pending[w.gset]) {   // the next layer writes into the other set: its last group launch must be over
-      if (hipStreamWaitEvent(s, w.ev_gdone[w.gset], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-      w.gdone_pending[w.gset] = false;
-    }
-  }
-  // dX[M, K] = dY[M, N] W[N, K]  and  dW[N, K] = dY[M, N]^T X[M, K]  (dX may alias X: X is consumed first)
+  // dX[M, K] = dY[M, N] W[N, K]  and  dW[N, K] = dY[M, N]^T X[M, K]  (dX may alias X: X is consumed first); dX on the main
+  // stream, dW on the side stream (w.side) except in f32 mode
   // relu_act (bf16 mode only): dY is the gradient w.r.t. relu(.) and relu_act the stored activation; the mask is applied
   // while dY is converted (the caller skips launch_relu_bwd)
   // fuse_mask (bf16 mode, grouped route): dX is only read by the NEXT dxdw call, as its dY with relu_act = fuse_mask (the
   // feed-forward block: dX = gradient w.r.t. relu(.), [M, K]); when the shapes allow it the dX product's epilogue writes that
-  // dY's bf16 rows and transposed copy itself (masked), no fp32 dX is written, and the next call finds them in w.pre
+  // dY's bf16 rows and transposed copy itself (masked), no fp32 dX is written, and the next call finds them left with w.side
   void dxdw(const float* dY, const float* W, const float* X, float* dX, float* dW, int M, int N, int K, const void* saved_xt = nullptr,
             const float* relu_act = nullptr, const float* fuse_mask = nullptr) {
-    const int Mp = pad32(M);
+    if (Ln.err) return;
+    if (c->precision == RPR_PREC_BF16) dxdw_bf16(dY, W, X, dX, dW, M, N, K, saved_xt, relu_act, fuse_mask);
+    else if (c->precision == RPR_PREC_F16X2) dxdw_f16x2(dY, W, X, dX, dW, M, N, K);
+    else dxdw_f32(dY, W, X, dX, dW, M, N, K);
+  }
+  // bf16 operands (see gemm()): one read of dY gives its plain and its transposed copy. The weight gradients of a layer go out
+  // as one grouped launch where the shapes allow it, else product by product.
+  void dxdw_bf16(const float* dY, const float* W, const float* X, float* dX, float* dW, int M, int N, int K, const void* saved_xt,
+                 const float* relu_act, const float* fuse_mask) {
+    WGradSide& sd = w.side;
     hipStream_t s = Ln.s;
-    if (c->precision == RPR_PREC_BF16) {
-      // bf16 operands (see gemm()): one read of dY gives its plain and its transposed copy; dW on the side stream.
-      // The bf16 kernel walks K in tiles of 64: the reduction length of the dW product (the rows) is padded to 64.
-      const int Mp = (M + 63) & ~63;
-      auto wit_g = w.wc_off.find(W);
-      const int Ml = ldT(M);
-      const size_t need = (((size_t)N * Ml * sizeof(__half)) + 255) & ~(size_t)255;
-      const int ptiles = ((N + 255) / 256) * ((K + 255) / 256);
-      // a dY the previous call's dX product left converted (rows + transposed copy in this group's set): nothing to convert,
-      // and the group has room (checked when the slot was reserved)
-      const bool pre = w.pre.dY == dY && w.pre.gset == w.gset && saved_xt && wit_g != w.wc_off.end() && w.wcT.p;
-      if (w.pre.dY && !pre) { Ln.err = RPR_ERR_INVALID; set_error("dxdw: a pre-converted gradient was not consumed by the next product"); return; }
-      if (!pre && saved_xt && wit_g != w.wc_off.end() && w.wcT.p && w.dyT[w.gset].p && ptiles <= GemmGroupArgs::MAX_TILES &&
-          (w.grp.n == 0 || w.grp.K != Mp || w.grp.n >= GemmGroupArgs::MAXP || w.grp_tiles + ptiles > GemmGroupArgs::MAX_TILES ||
-           w.dyT_used + need > w.dyT[w.gset].cap))
-        flush_group();   // the product does not fit the group being collected: send that one off, start the next
-      if (pre || (saved_xt && wit_g != w.wc_off.end() && w.wcT.p && w.dyT[w.gset].p && w.dyT_used + need <= w.dyT[w.gset].cap &&
-                  ptiles <= GemmGroupArgs::MAX_TILES)) {
-        // grouped route: dY^T into this layer's set, the product into the group, dX on the main stream at once
-        const void* py = w.tA.p;
-        __half* pyt;
-        if (pre) { py = w.pre.py; pyt = w.pre.pyt; w.pre = TrainWs::Pre{}; }
-        else {
-          pyt = reinterpret_cast<__half*>(static_cast<char*>(w.dyT[w.gset].p) + w.dyT_used);
-          w.dyT_used += need;
-          void* pyw = w.tA.p;
-          Ln.run(RPR_K_OTHER, 0, (relu_act ? 12.0 : 8.0) * M * N, [&] { return launch_to_bf16_T(dY, M, N, N, Mp, pyt, pyw, s, relu_act, Ml); });
-        }
-        GemmGroupArgs& gp = w.grp;
-        const int i = gp.n++;
-        gp.A[i] = pyt; gp.W[i] = reinterpret_cast<const __half*>(saved_xt); gp.out[i] = dW;
-        gp.M[i] = N; gp.N[i] = K; gp.ldo[i] = K; gp.K = Mp; gp.lda = Ml; gp.ldw = Ml;
-        w.grp_tiles += ptiles;
-        w.grp_flops += 2.0 * N * (double)K * Mp;
-        w.grp_bytes += 2.0 * ((double)N * Mp + (double)K * Mp) + 4.0 * (double)N * K;
-        const void* pwt = reinterpret_cast<const __half*>(w.wcT.p) + wit_g->second;
-        // the next product (dY = this dX, [M, K]) joins the same group: its dY^T slot is reserved now and this product's
-        // epilogue fills it, with the rows for its dX product beside it
-        const size_t need2 = (((size_t)K * Ml * sizeof(__half)) + 255) & ~(size_t)255;
-        const int ptiles2 = ((K + 255) / 256) * ((N + 255) / 256);    // the next product is dW2[K, N2]; N2 is not known here: bound by this one's N
-        if (fuse_mask && fused_ok(c, M, K) && Mp == M && w.bfb.p && w.bfb.cap >= (size_t)M * K * sizeof(__half) && w.grp.n < GemmGroupArgs::MAXP &&
-            w.grp_tiles + ptiles2 <= GemmGroupArgs::MAX_TILES && w.dyT_used + need2 <= w.dyT[w.gset].cap) {
-          __half* pyt2 = reinterpret_cast<__half*>(static_cast<char*>(w.dyT[w.gset].p) + w.dyT_used);
-          w.dyT_used += need2;
-          const BOut bo{w.bfb.p, pyt2, Ml, fuse_mask};
-          gemm_bf16(Ln, py, N, pwt, N, nullptr, K, M, K, N, nullptr, 0, nullptr, &bo);
-          w.pre.dY = dX; w.pre.py = w.bfb.p; w.pre.pyt = pyt2; w.pre.gset = w.gset;
-          return;
-        }
-        gemm_bf16(Ln, py, N, pwt, N, dX, K, M, K, N, nullptr, 0);
-        return;
-      }
-      flush_group();   // (a product the group cannot take: keep the order of the side stream's work)
-      const int f = w.flip; w.flip = (w.flip + 1) % TrainWs::NSIDE;
-      hipStream_t side = w.side;
-      void *py = w.tA.p, *pyt = w.tC[f].p;
-      const void *pxt = w.tB[f].p, *pwt = w.wT.p;
-      if (w.done_pending[f]) {
-        if (hipStreamWaitEvent(s, w.ev_done[f], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-        w.done_pending[f] = false;
-      }
-      Ln.run(RPR_K_OTHER, 0, (relu_act ? 12.0 : 8.0) * M * N, [&] { return launch_to_bf16_T(dY, M, N, N, Mp, pyt, py, s, relu_act); });
+    // Mk: the reduction length of the dW product (the rows; the bf16 kernel walks K in tiles of 64); Ml: the row stride of the
+    // transposed operands that have a slot of their own (saved X^T, grouped dY^T)
+    const int Mk = pad64(M), Ml = ldT(M);
+    const auto wit = w.wc_off.find(W);
+    const bool cached = wit != w.wc_off.end() && w.wcT.p;   // W^T was converted once per step
+    const void* wT_cached = cached ? reinterpret_cast<const __half*>(w.wcT.p) + wit->second : nullptr;
+    const size_t slot = WGradSide::slot_bytes(N, Ml);
+    // the route, decided once. PRE: the previous call's dX product left this dY converted, rows + transposed copy in the group's
+    // set (the room was checked when the slot was reserved); JOIN: convert into the group being collected; FLUSH_JOIN: send
+    // that group off and start the next with this product; SINGLE: no group can take it (no saved X^T, no cached W^T, more
+    // tiles or a larger dY^T than a group holds)
+    enum { PRE, JOIN, FLUSH_JOIN, SINGLE } route = SINGLE;
+    if (sd.pre_is(dY) && saved_xt && cached) route = PRE;
+    else if (sd.pre_left()) { Ln.err = RPR_ERR_INVALID; set_error("dxdw: a pre-converted gradient was not consumed by the next product"); return; }
+    else if (saved_xt && cached) {
+      const WGradSide::Fit f = sd.fit(N, K, Mk, slot);
+      route = f == WGradSide::FIT_OPEN ? JOIN : f == WGradSide::FIT_EMPTY ? FLUSH_JOIN : SINGLE;
+    }
+    if (route == FLUSH_JOIN || route == SINGLE) sd.flush(Ln);   // (SINGLE: keep the order of the side stream's work)
+    if (Ln.err) return;
+    if (route == SINGLE) {
+      WGradSide::Set& t = sd.next_set(Ln);
+      if (Ln.err) return;
+      void *py = w.tA.p, *pyt = t.tY.p;
+      const void *pxt = t.tX.p, *pwt = w.wT.p;
+      Ln.run(RPR_K_OTHER, 0, (relu_act ? 12.0 : 8.0) * M * N, [&] { return launch_to_bf16_T(dY, M, N, N, Mk, pyt, py, s, relu_act); });
       if (saved_xt) pxt = saved_xt;                       // left behind by the forward pass
-      else Ln.run(RPR_K_OTHER, 0, 6.0 * M * K, [&] { return launch_to_bf16_T(X, M, K, K, Mp, w.tB[f].p, nullptr, s); });
-      auto wit = w.wc_off.find(W);
-      if (wit != w.wc_off.end() && w.wcT.p) pwt = reinterpret_cast<const __half*>(w.wcT.p) + wit->second;   // once per step
+      else Ln.run(RPR_K_OTHER, 0, 6.0 * M * K, [&] { return launch_to_bf16_T(X, M, K, K, Mk, t.tX.p, nullptr, s); });
+      if (cached) pwt = wT_cached;
       else Ln.run(RPR_K_OTHER, 0, 6.0 * N * K, [&] { return launch_to_bf16_T(W, N, K, K, N, w.wT.p, nullptr, s); });
-      if (hipEventRecord(w.ev_fork[f], s) != hipSuccess || hipStreamWaitEvent(side, w.ev_fork[f], 0) != hipSuccess) {
-        Ln.err = RPR_ERR_HIP; return;
-      }
-      {
-        Launcher L2{c, side};
-        gemm_bf16(L2, pyt, Mp, pxt, saved_xt ? Ml : Mp, dW, K, N, K, Mp, nullptr, 0, &w.part2);
-        if (L2.err) { Ln.err = L2.err; return; }
-        if (hipEventRecord(w.ev_done[f], side) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-        w.done_pending[f] = true;
-      }
+      sd.run(Ln, t.sync, [&](Launcher& L2) { gemm_bf16(L2, pyt, Mk, pxt, saved_xt ? Ml : Mk, dW, K, N, K, Mk, nullptr, 0, &w.part2); });
+      if (Ln.err) return;
       gemm_bf16(Ln, py, N, pwt, N, dX, K, M, K, N, nullptr, 0);
       return;
     }
-    if (c->precision == RPR_PREC_F16X2) {
-      // one read of dY gives its plain planes (for dX) and its transposed planes (for dW); W is transposed straight
-      // from the fp32 weight
-      float* am = amax_slots(c, 3);
-      if (!am) { Ln.err = RPR_ERR_INVALID; return; }
-      const int f = w.flip; w.flip = (w.flip + 1) % TrainWs::NSIDE;
-      hipStream_t side = w.side;
-      __half *py = P<__half>(w.tA), *pyt = P<__half>(w.tC[f]), *pxt = P<__half>(w.tB[f]), *pwt = P<__half>(w.wT);
-      if (w.done_pending[f]) {   // the dW product that last read this scratch set (NSIDE calls ago) must be over
-        if (hipStreamWaitEvent(s, w.ev_done[f], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-        w.done_pending[f] = false;
-      }
-      const float *am_x = am + 2, *am_w = am + 1;
-      auto site = w.site_amax.find(W);
-      if (site != w.site_amax.end()) {   // X and W are the forward GEMM's operands: their maxima are known
-        am_x = site->second; am_w = site->second + 1;
-        Ln.run(RPR_K_OTHER, 0, 4.0 * M * N, [&] { return launch_absmax2(dY, (size_t)M * N, nullptr, 0, am, s); });
-      } else {
-        Ln.run(RPR_K_OTHER, 0, 4.0 * M * N + 4.0 * N * K, [&] { return launch_absmax2(dY, (size_t)M * N, W, (size_t)N * K, am, s); });
-        Ln.run(RPR_K_OTHER, 0, 4.0 * M * K, [&] { return launch_absmax2(X, (size_t)M * K, nullptr, 0, am + 2, s); });
-      }
-      Ln.run(RPR_K_OTHER, 0, 12.0 * M * N, [&] { return launch_split_dyn_T(dY, M, N, N, Mp, pyt, py, am, s); });
-      Ln.run(RPR_K_OTHER, 0, 8.0 * M * K, [&] { return launch_split_dyn_T(X, M, K, K, Mp, pxt, nullptr, am_x, s); });
-      Ln.run(RPR_K_OTHER, 0, 8.0 * N * K, [&] { return launch_split_dyn_T(W, N, K, K, N, pwt, nullptr, am_w, s); });
-      // dW on the side stream, dX on the main one
-      if (hipEventRecord(w.ev_fork[f], s) != hipSuccess || hipStreamWaitEvent(side, w.ev_fork[f], 0) != hipSuccess) {
-        Ln.err = RPR_ERR_HIP; return;
-      }
-      {
-        Launcher L2{c, side};
-        gemm_planes(L2, {pyt, (size_t)N * Mp, Mp, am}, {pxt, (size_t)K * Mp, Mp, am_x}, dW, K, N, K, Mp, nullptr, 0, &w.part2);
-        if (L2.err) { Ln.err = L2.err; return; }
-        if (hipEventRecord(w.ev_done[f], side) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-        w.done_pending[f] = true;
-      }
-      gemm_planes(Ln, {py, (size_t)M * N, N, am}, {pwt, (size_t)K * N, N, am_w}, dX, K, M, K, N, nullptr, 0);
+    // grouped route: dY^T into this layer's set, the product into the group, dX on the main stream at once
+    const void* py = w.tA.p;
+    __half* pyt;
+    if (route == PRE) { const WGradSide::Pre p = sd.take_pre(); py = p.py; pyt = p.pyt; }
+    else {
+      pyt = sd.reserve(slot);
+      void* pyw = w.tA.p;
+      Ln.run(RPR_K_OTHER, 0, (relu_act ? 12.0 : 8.0) * M * N, [&] { return launch_to_bf16_T(dY, M, N, N, Mk, pyt, pyw, s, relu_act, Ml); });
+    }
+    sd.add(pyt, saved_xt, dW, N, K, Mk, Ml);
+    // the next product (dY = this dX, [M, K]) joins the same group: its dY^T slot is reserved now and this product's epilogue
+    // fills it, with the rows for its dX product beside it. (The next product is dW2[K, N2]; N2 is not known here: its tiles
+    // are bound by this one's N.)
+    const size_t slot2 = WGradSide::slot_bytes(K, Ml);
+    if (fuse_mask && fused_ok(c, M, K) && Mk == M && w.bfb.p && w.bfb.cap >= (size_t)M * K * sizeof(__half) &&
+        sd.fit(K, N, Mk, slot2) == WGradSide::FIT_OPEN) {
+      __half* pyt2 = sd.reserve(slot2);
+      const BOut bo{w.bfb.p, pyt2, Ml, fuse_mask};
+      gemm_bf16(Ln, py, N, wT_cached, N, nullptr, K, M, K, N, nullptr, 0, nullptr, &bo);
+      sd.leave_pre(dX, w.bfb.p, pyt2);
       return;
     }
+    gemm_bf16(Ln, py, N, wT_cached, N, dX, K, M, K, N, nullptr, 0);
+  }
+  // one read of dY gives its plain planes (for dX) and its transposed planes (for dW); W is transposed straight from the
+  // fp32 weight. Mp: the reduction length of the dW product (the split kernel walks K in tiles of 32)
+  void dxdw_f16x2(const float* dY, const float* W, const float* X, float* dX, float* dW, int M, int N, int K) {
+    hipStream_t s = Ln.s;
+    const int Mp = pad32(M);
+    float* am = amax_slots(c, 3);
+    if (!am) { Ln.err = RPR_ERR_INVALID; return; }
+    WGradSide::Set& t = w.side.next_set(Ln);
+    if (Ln.err) return;
+    __half *py = P<__half>(w.tA), *pyt = P<__half>(t.tY), *pxt = P<__half>(t.tX), *pwt = P<__half>(w.wT);
+    const float *am_x = am + 2, *am_w = am + 1;
+    auto site = w.site_amax.find(W);
+    if (site != w.site_amax.end()) {   // X and W are the forward GEMM's operands: their maxima are known
+      am_x = site->second; am_w = site->second + 1;
+      Ln.run(RPR_K_OTHER, 0, 4.0 * M * N, [&] { return launch_absmax2(dY, (size_t)M * N, nullptr, 0, am, s); });
+    } else {
+      Ln.run(RPR_K_OTHER, 0, 4.0 * M * N + 4.0 * N * K, [&] { return launch_absmax2(dY, (size_t)M * N, W, (size_t)N * K, am, s); });
+      Ln.run(RPR_K_OTHER, 0, 4.0 * M * K, [&] { return launch_absmax2(X, (size_t)M * K, nullptr, 0, am + 2, s); });
+    }
+    Ln.run(RPR_K_OTHER, 0, 12.0 * M * N, [&] { return launch_split_dyn_T(dY, M, N, N, Mp, pyt, py, am, s); });
+    Ln.run(RPR_K_OTHER, 0, 8.0 * M * K, [&] { return launch_split_dyn_T(X, M, K, K, Mp, pxt, nullptr, am_x, s); });
+    Ln.run(RPR_K_OTHER, 0, 8.0 * N * K, [&] { return launch_split_dyn_T(W, N, K, K, N, pwt, nullptr, am_w, s); });
+    w.side.run(Ln, t.sync, [&](Launcher& L2) {
+      gemm_planes(L2, {pyt, (size_t)N * Mp, Mp, am}, {pxt, (size_t)K * Mp, Mp, am_x}, dW, K, N, K, Mp, nullptr, 0, &w.part2);
+    });
+    if (Ln.err) return;
+    gemm_planes(Ln, {py, (size_t)M * N, N, am}, {pwt, (size_t)K * N, N, am_w}, dX, K, M, K, N, nullptr, 0);
+  }
+  void dxdw_f32(const float* dY, const float* W, const float* X, float* dX, float* dW, int M, int N, int K) {   // both on the main stream
+    hipStream_t s = Ln.s;
+    const int Mp = pad32(M);
+    float* xT = w.side.main_stream_scratch();
     Ln.run(RPR_K_OTHER, 0, 8.0 * M * N, [&] { return launch_transpose_pad(dY, P<float>(w.tA), M, N, N, Mp, s); });
-    Ln.run(RPR_K_OTHER, 0, 8.0 * M * K, [&] { return launch_transpose_pad(X, P<float>(w.tB[0]), M, K, K, Mp, s); });
-    gemm(Ln, P<float>(w.tA), Mp, P<float>(w.tB[0]), Mp, dW, K, N, K, Mp);
+    Ln.run(RPR_K_OTHER, 0, 8.0 * M * K, [&] { return launch_transpose_pad(X, xT, M, K, K, Mp, s); });
+    gemm(Ln, P<float>(w.tA), Mp, xT, Mp, dW, K, N, K, Mp);
     Ln.run(RPR_K_OTHER, 0, 8.0 * N * K, [&] { return launch_transpose_pad(W, P<float>(w.wT), N, K, K, N, s); });
     gemm(Ln, dY, N, P<float>(w.wT), N, dX, K, M, K, N);
   }
@@ -522,40 +590,22 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
   E(w.dec_act, (size_t)D.nd * D.dec_stride * f);
   E(w.enc_out, T * dm * f); E(w.xkv, T * (size_t)D.xld * f); E(w.x_last, R * dm * f);
   E(w.scores, R * f); E(w.margins, 8 * (size_t)D.bz * f); E(w.dscores, R * f);
-  E(w.in_idx, R * 4); E(w.out_idx, R * 4); E(w.tok_idx, T * 4);
+  E(w.in_idx, R * 4); E(w.out_idx, R * 4);
   if (D.docs == 1) { E(w.hF, R * dm * f); E(w.dlog, R * (size_t)D.V * f); E(w.row_loss, R * f); }   // the seq2seq head
   E(w.h, rows * dm * f); E(w.dxa, rows * dm * f); E(w.dxb, rows * dm * f); E(w.dbig, rows * wide * f);
   E(w.dattn, rows * inner * f); E(w.dxkv, T * (size_t)D.xld * f); E(w.denc, T * dm * f);
   E(w.tA, wide * rp * f);
-  // the transposed operands of a weight-gradient product (fp32, two f16 planes or bf16), one set per side stream
-  for (int i = 0; i < TrainWs::NSIDE; ++i) { E(w.tB[i], wide * rp * f); E(w.tC[i], wide * rp * f); }
-  if (c->precision == RPR_PREC_BF16) {
-    E(w.xT, XtLayout(D).total * sizeof(__half));
-    // grouped weight gradients: dY^T of one layer's products, [N_out][pad64(rows)] bf16 each, 256-byte aligned
-    const size_t Rp = ldT(D.R), Tp = ldT(D.T);
-    const size_t dec = (3 * dm + dff + 4 * inner) * Rp, enc = (2 * dm + dff + 3 * inner) * Tp, xkv = (size_t)D.xld * Tp;
-    const size_t need = std::max(std::max(dec, enc), xkv) * sizeof(__half) + 8 * 256;
-    E(w.dyT[0], need); E(w.dyT[1], need);
-    E(w.bfb, rp * dff * sizeof(__half));
-    static_assert(GemmGroupArgs::MAXP * sizeof(GemmH2Args) <= GemmGroupArgs::TABLE_BYTES, "argument table");
-    E(w.gtab, GemmGroupArgs::SCRATCH_BYTES);
-  }
+  // grouped weight gradients (bf16 mode): dY^T of one layer's products, [N_out][pad64(rows)] bf16 each, 256-byte aligned
+  const size_t Rp = ldT(D.R), Tp = ldT(D.T);
+  const size_t dec = (3 * dm + dff + 4 * inner) * Rp, enc = (2 * dm + dff + 3 * inner) * Tp, xkv = (size_t)D.xld * Tp;
+  const bool bf16 = c->precision == RPR_PREC_BF16;
+  if (!e) e = w.side.create(c, wide * rp * f, bf16 ? std::max(std::max(dec, enc), xkv) * sizeof(__half) + 8 * 256 : 0);
+  if (bf16) { E(w.xT, XtLayout(D).total * sizeof(__half)); E(w.bfb, rp * dff * sizeof(__half)); }
   E(w.wT, std::max<size_t>(std::max<size_t>(dff * dm, 3 * inner * dm), (size_t)D.xld * dm) * f);
   E(w.w_part, ColsumSites::MAXS * ((rows + 3) / 4) * dm * f);   // the partials of up to four norm sites (Bwd::norm_bwd)
   E(w.bias_part, std::max<size_t>((size_t)D.S, (size_t)D.bz) * D.H * D.buckets * f);
   E(w.fix, std::max<size_t>((size_t)m->d.vocab_size, (size_t)m->d.L * D.V) * dm * 8);
   E(w.gn_part, 1024 * 8); E(w.gn_out, 16); E(w.amax, AMAX_SLOTS * f); E(w.part, (size_t)16 << 20 << 2); E(w.part2, (size_t)16 << 20 << 2);   // split-K partials: 16 M floats per stream
-  if (!e && !w.side) {
-    RPR_HIP(hipStreamCreateWithFlags(&w.side, hipStreamNonBlocking));
-    for (int i = 0; i < TrainWs::NSIDE; ++i) {
-      RPR_HIP(hipEventCreateWithFlags(&w.ev_fork[i], hipEventDisableTiming));
-      RPR_HIP(hipEventCreateWithFlags(&w.ev_done[i], hipEventDisableTiming));
-    }
-    for (int i = 0; i < 2; ++i) {
-      RPR_HIP(hipEventCreateWithFlags(&w.ev_gfork[i], hipEventDisableTiming));
-      RPR_HIP(hipEventCreateWithFlags(&w.ev_gdone[i], hipEventDisableTiming));
-    }
-  }
   return e;
 }
 
@@ -689,20 +739,17 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
   hipStream_t s = Ln.s;
   auto bucket = [&](size_t off, size_t numel) {
     if (!hook || !hook->cb || Ln.err) return;
-    while ((int)w.bucket_ev.size() < 2 * (hook->next + 1)) {
+    while ((int)w.bucket_ev.size() <= hook->next) {
       hipEvent_t e = nullptr;
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
       w.bucket_ev.push_back(e);
     }
-    hipEvent_t e0 = w.bucket_ev[(size_t)2 * hook->next], e1 = w.bucket_ev[(size_t)2 * hook->next + 1];
-    ++hook->next;
-    (void)e1;
+    hipEvent_t e0 = w.bucket_ev[(size_t)hook->next++];
     if (hipEventRecord(e0, s) != hipSuccess || hipStreamWaitEvent(hook->comm, e0, 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-    // ... and for the weight gradients in flight: the last product of every side stream (stream order covers the earlier ones)
-    for (int i = 0; i < TrainWs::NSIDE; ++i)
-      if (w.done_pending[i] && hipStreamWaitEvent(hook->comm, w.ev_done[i], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
-    for (int i = 0; i < 2; ++i)     // grouped weight gradients: the launch of every set still in flight
-      if (w.gdone_pending[i] && hipStreamWaitEvent(hook->comm, w.ev_gdone[i], 0) != hipSuccess) { Ln.err = RPR_ERR_HIP; return; }
+    // ... and for the weight gradients in flight on the side stream; the marks stay for the end-of-pass join
+    w.side.wait_products(Ln, hook->comm, false);
+    w.side.wait_groups(Ln, hook->comm, false);
+    if (Ln.err) return;
     hook->cb(hook->user, (int64_t)off, (int64_t)numel);
   };
   auto layer_numel = [&](int first_kind, int last_kind, int layer) {
@@ -711,9 +758,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
     return std::make_pair(lo, hi - lo);
   };
   const int T = D.T, R = D.R, dm = D.dm, inner = D.inner, dff = D.dff, H = D.H;
-  // a backward that aborted on Ln.err leaves collected-but-unflushed products behind: never carry them into this step's
-  // gradient buffer
-  w.grp.n = 0; w.grp_tiles = 0; w.grp_flops = w.grp_bytes = 0; w.dyT_used = 0; w.pre = TrainWs::Pre{};
+  w.side.reset();
   Bwd B{Ln, c, w, D};
   const XtSlots xt{c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr, XtLayout(D)};
   const bool saved = xt.base != nullptr;   // the normalised inputs are only recomputed for their weight-gradient products
@@ -774,7 +819,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
     B.dxdw(dbig, m->dec_qkv[i], h, h, g(K_DEC_QKV, i), R, 3 * inner, dm, xt.dec(i, XT_QKV));
     B.norm_bwd(a.x0, m->dec_ln0[i], h, dx, dx2, g(K_DEC_LN0, i), R);
     std::swap(dx, dx2);                                            // dx = gradient w.r.t. x0 = the previous layer's output
-    B.flush_group();                                               // the layer's six weight gradients: one launch on the side stream
+    w.side.flush(Ln);                                               // the layer's six weight gradients: one launch on the side stream
     B.flush_norms();                                               // ... and its three layer-norm weight gradients
     { const auto b = layer_numel(K_DEC_LN0, K_DEC_WO, i); bucket(b.first, b.second); }
   }
@@ -785,7 +830,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
   // ---- cross K/V projection and the encoder's final norm
   float* denc = P<float>(w.denc);
   B.dxdw(P<float>(w.dxkv), d.dec_xkv, P<float>(w.enc_out), denc, g(K_XKV), T, D.xld, dm, xt.xkv());
-  B.flush_group();
+  w.side.flush(Ln);
   float* xe_last = P<float>(w.enc_act) + (size_t)D.ne * D.enc_stride;
   B.norm_bwd(xe_last, d.enc_final_ln, denc, nullptr, dxa, g(K_ENC_FLN), T);
   dx = dxa; dx2 = dxb;
@@ -806,7 +851,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
     B.dxdw(dbig, m->enc_qkv[i], h, h, g(K_ENC_QKV, i), T, 3 * inner, dm, xt.enc(i, XT_QKV));
     B.norm_bwd(a.x, m->enc_ln0[i], h, dx, dx2, g(K_ENC_LN0, i), T);
     std::swap(dx, dx2);
-    B.flush_group();
+    w.side.flush(Ln);
     B.flush_norms();
     { const auto b = layer_numel(K_ENC_LN0, K_ENC_WO, i); bucket(b.first, b.second); }
   }
@@ -814,18 +859,10 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dx, ids, fix, T, dm, s); });
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g(K_SHARED), (size_t)d.vocab_size * dm, s); });
   // the weight gradients still in flight on the side stream belong to this pass: join
-  for (int i = 0; i < TrainWs::NSIDE; ++i)
-    if (w.done_pending[i]) {
-      if (hipStreamWaitEvent(s, w.ev_done[i], 0) != hipSuccess) Ln.err = RPR_ERR_HIP;
-      w.done_pending[i] = false;
-    }
-  B.flush_group();
+  w.side.wait_products(Ln, s, true);
+  w.side.flush(Ln);
   B.flush_norms();                                                 // the encoder's final norm (the decoder's went with its last layer)
-  for (int i = 0; i < 2; ++i)
-    if (w.gdone_pending[i]) {
-      if (hipStreamWaitEvent(s, w.ev_gdone[i], 0) != hipSuccess) Ln.err = RPR_ERR_HIP;
-      w.gdone_pending[i] = false;
-    }
+  w.side.wait_groups(Ln, s, true);
   bucket(0, param_offset(m, K_ENC_LN0, 0));   // everything in front of the first layer: final only now
 }
 
@@ -872,23 +909,8 @@ void rpr::train_forget_model(rpr_ctx* c, const rpr_model* m) {
 void rpr::free_train_ws(rpr_ctx* c) {
   if (!c->tws) return;
   TrainWs& w = *c->tws;
-  DevBuf* all[] = {&w.hF, &w.dlog, &w.row_loss, &w.enc_act, &w.dec_act, &w.enc_out, &w.xkv, &w.x_last, &w.scores, &w.margins, &w.dscores, &w.in_idx, &w.out_idx,
-                   &w.tok_idx, &w.h, &w.dxa, &w.dxb, &w.dbig, &w.dattn, &w.dxkv, &w.denc, &w.tA, &w.wT, &w.w_part, &w.bias_part,
-                   &w.fix, &w.gn_part, &w.gn_out, &w.amax, &w.part, &w.part2, &w.wc, &w.wcT, &w.wseg, &w.wpref, &w.xT, &w.aseg, &w.apref, &w.bfb};
-  for (DevBuf* b : all) if (b->p) (void)hipFree(b->p);
-  for (int i = 0; i < 2; ++i) {
-    if (w.dyT[i].p) (void)hipFree(w.dyT[i].p);
-    if (w.ev_gfork[i]) (void)hipEventDestroy(w.ev_gfork[i]);
-    if (w.ev_gdone[i]) (void)hipEventDestroy(w.ev_gdone[i]);
-  }
-  if (w.gtab.p) (void)hipFree(w.gtab.p);
-  for (int i = 0; i < TrainWs::NSIDE; ++i) {
-    if (w.tB[i].p) (void)hipFree(w.tB[i].p);
-    if (w.tC[i].p) (void)hipFree(w.tC[i].p);
-    if (w.ev_fork[i]) (void)hipEventDestroy(w.ev_fork[i]);
-    if (w.ev_done[i]) (void)hipEventDestroy(w.ev_done[i]);
-  }
-  if (w.side) (void)hipStreamDestroy(w.side);
+  for (DevBuf* b : w.bufs) if (b->p) (void)hipFree(b->p);
+  w.side.destroy();
   for (hipEvent_t e : w.bucket_ev) (void)hipEventDestroy(e);
   delete c->tws;
   c->tws = nullptr;
@@ -1040,109 +1062,6 @@ int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp
   // that needs them (ensure_weight_planes) — a training loop never does, and the refresh costs a pass over every weight
   // plus a stream synchronisation per step
   m->planes_dirty = true;
-  return RPR_OK;
-}
-
-
-// ---- residual quantization: docid creation (reference: faiss.IndexResidualQuantizer in tasks/evaluator.py:405-421) ------
-// Greedy residual k-means, DESIGN.md "Residual quantization": Lloyd iterations of the fused assign kernel and the
-// deterministic centroid update (gemm_f32.hip) per level, the residuals of the training rows in the ctx workspace.
-
-static int rq_check(rpr_ctx* c, const float* x, int64_t n, int32_t d, int32_t M, int32_t K, const void* out) {
-  RPR_REQUIRE(c && x && out, "NULL argument");
-  RPR_REQUIRE(n >= 1 && n <= (int64_t)1 << 30, "row count out of range (1 .. 2^30 per call)");
-  RPR_REQUIRE(d >= 32 && d % 32 == 0, "d must be a positive multiple of 32");
-  RPR_REQUIRE(K >= 64 && K % 64 == 0 && K <= RQ_MAX_K, "K must be a multiple of 64 and at most 1024");
-  RPR_REQUIRE(M >= 1 && M <= 4096, "M out of range");
-  return RPR_OK;
-}
-
-static int rq_ws(rpr_ctx* c, int64_t n, int32_t d, int32_t M, int32_t K, bool train) {
-  Workspace& w = c->ws;
-  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM), nb = (size_t)((n + RQ_SORT_ROWS - 1) / RQ_SORT_ROWS);
-  int e = ensure(c, w.rq_r, (size_t)n * d * sizeof(float));
-  if (!e) e = ensure(c, w.rq_cnorm, (size_t)M * K * sizeof(float));
-  if (!e) e = ensure(c, w.rq_part, (size_t)M * nblk * sizeof(double));
-  if (train) {
-    if (!e) e = ensure(c, w.rq_code, (size_t)n * sizeof(uint16_t));
-    if (!e) e = ensure(c, w.rq_hist, ((size_t)K * nb + 1) * sizeof(int));
-    if (!e) e = ensure(c, w.rq_order, (size_t)n * sizeof(int));
-    if (!e) e = ensure(c, w.rq_idx, (size_t)M * K * sizeof(int));
-  }
-  return e;
-}
-
-// sum of the per-block |r|^2 partials of every level, block by block (host, fp64)
-static int rq_level_sums(rpr_ctx* c, int64_t n, int32_t M, double* out, hipStream_t s) {
-  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM);
-  std::vector<double> part((size_t)M * nblk);
-  RPR_HIP(hipMemcpyAsync(part.data(), c->ws.rq_part.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  RPR_HIP(hipStreamSynchronize(s));
-  for (int m = 0; m < M; ++m) {
-    double t = 0.0;
-    for (size_t b = 0; b < nblk; ++b) t += part[(size_t)m * nblk + b];
-    out[m] = t;
-  }
-  return RPR_OK;
-}
-
-int rpr_rq_train(rpr_ctx* c, const float* x, int64_t n, int32_t d, int32_t M, int32_t K, int32_t niter, const int32_t* init_idx,
-                 float* codebooks, double* level_mse, void* stream) {
-  { const int e = rq_check(c, x, n, d, M, K, codebooks); if (e) return e; }
-  RPR_REQUIRE(init_idx, "NULL init_idx");
-  RPR_REQUIRE(n >= K, "fewer training rows than codewords");
-  RPR_REQUIRE(niter >= 0 && niter <= 10000, "niter out of range");
-  for (int64_t i = 0; i < (int64_t)M * K; ++i) RPR_REQUIRE(init_idx[i] >= 0 && init_idx[i] < n, "init_idx entry out of range");
-  RPR_HIP(hipSetDevice(c->device));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  { const int e = rq_ws(c, n, d, M, K, true); if (e) return e; }
-  Workspace& w = c->ws;
-  float* R = static_cast<float*>(w.rq_r.p);
-  uint16_t* code = static_cast<uint16_t*>(w.rq_code.p);
-  float* cnorm = static_cast<float*>(w.rq_cnorm.p);
-  int* idx = static_cast<int*>(w.rq_idx.p);
-  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM);
-  RPR_HIP(hipMemcpyAsync(R, x, (size_t)n * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-  RPR_HIP(hipMemcpyAsync(idx, init_idx, (size_t)M * K * sizeof(int), hipMemcpyHostToDevice, s));
-  RPR_HIP(hipStreamSynchronize(s));   // init_idx is the caller's
-  for (int m = 0; m < M; ++m) {
-    float* Cm = codebooks + (size_t)m * K * d;
-    RPR_HIP(launch_rq_gather(R, d, idx + (size_t)m * K, K, Cm, s));
-    RPR_HIP(launch_rq_norms(Cm, K, d, cnorm, s));
-    RqAssignArgs a{R, (int)n, d, Cm, cnorm, K, code, 1, nullptr};
-    for (int it = 0; it < niter; ++it) {
-      RPR_HIP(launch_rq_assign(a, s));
-      RPR_HIP(launch_rq_update(R, (int)n, d, code, K, static_cast<int*>(w.rq_hist.p), static_cast<int*>(w.rq_order.p), Cm, cnorm, s));
-    }
-    a.part = static_cast<double*>(w.rq_part.p) + (size_t)m * nblk;   // final assignment, R -= C_m[code]
-    RPR_HIP(launch_rq_assign(a, s));
-  }
-  if (level_mse) {
-    { const int e = rq_level_sums(c, n, M, level_mse, s); if (e) return e; }
-    for (int m = 0; m < M; ++m) level_mse[m] /= (double)n;
-  }
-  return RPR_OK;
-}
-
-int rpr_rq_encode(rpr_ctx* c, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K, uint16_t* codes,
-                  double* level_sse, void* stream) {
-  { const int e = rq_check(c, x, n, d, M, K, codebooks); if (e) return e; }
-  RPR_REQUIRE(codes, "NULL codes");
-  RPR_HIP(hipSetDevice(c->device));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  { const int e = rq_ws(c, n, d, M, K, false); if (e) return e; }
-  Workspace& w = c->ws;
-  float* R = static_cast<float*>(w.rq_r.p);
-  float* cnorm = static_cast<float*>(w.rq_cnorm.p);
-  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM);
-  RPR_HIP(hipMemcpyAsync(R, x, (size_t)n * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-  RPR_HIP(launch_rq_norms(codebooks, M * K, d, cnorm, s));
-  for (int m = 0; m < M; ++m) {
-    RqAssignArgs a{R, (int)n, d, codebooks + (size_t)m * K * d, cnorm + (size_t)m * K, K, codes + m, M,
-                   static_cast<double*>(w.rq_part.p) + (size_t)m * nblk};
-    RPR_HIP(launch_rq_assign(a, s));
-  }
-  if (level_sse) return rq_level_sums(c, n, M, level_sse, s);
   return RPR_OK;
 }
 
