@@ -435,6 +435,32 @@ int rpr_rq_train(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, int32_t M, 
 int rpr_rq_encode(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K,
                   uint16_t* codes, double* level_sse, void* stream);
 
+/* ---- searching the residual-quantizer index (reference --task=aq_evaluate: evaluate.py:302-332,
+ * AddictvieQuantizeIndexer.search, tasks/evaluator.py:423-443) ---- */
+/* Dense embedding of a text: encoder, then ONE decoder position fed with the start embedding (decoder_input_ids = [-1]);
+ * out [dev] fp32 [bz, d_model] = decoder_last_hidden_state[:, 0, :] after the final RMSNorm and the scaleup_output_hidden
+ * factor (T5SeqAQEncoder.query_encode / T5AQEncoder.query_encode, modeling/t5_generative_retriever.py:786-792, 891-897).
+ * The pass is rpr_lngknp_forward's with n_docs = 1, L = 1 and follows the context's precision like it. input_ids /
+ * attention_mask: [dev] int32 [bz, Lq]; Lq <= 256; d_kv == 64. */
+int rpr_embed(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+              int32_t Lq, float* out, void* stream);
+/* Top-k inner-product search over the codes rpr_rq_encode wrote (faiss.IndexResidualQuantizer.search with
+ * METRIC_INNER_PRODUCT). Exact semantics (tests/rq_search_ref.py restates them in numpy):
+ *   LUT[q][m][k]  = <queries[q], codebooks[m][k]> from the exact-fp32 MFMA GEMM (one fixed fp32 chain per entry);
+ *   score[q][n]   = ((LUT[q][0][c_n0] + LUT[q][1][c_n1]) + ...) in fp32, levels in ascending order: the inner product
+ *                   with the decoded vector;
+ *   ranking       = score descending, exact ties to the smaller row n; -0.0 equals +0.0 (and is returned as +0.0);
+ *   topk > N      : the tail of a row is idx = -1, score = -inf (faiss's convention).
+ * Inputs must be finite. Codes must be < K; a larger value is clamped to K - 1 (nothing outside the LUT is read).
+ * Deterministic: two runs are bit-identical, no result depends on the order in which atomics land, and the rows of a
+ * query do not depend on how the queries are batched. All pointers are device pointers:
+ *   queries [Q, d] fp32, codebooks [M, K, d] fp32, codes [N, M] uint16, out_idx [Q, topk] int64, out_scores [Q, topk] fp32.
+ * d % 32 == 0, K % 64 == 0, 64 <= K <= 1024, 1 <= M <= 64, 1 <= N <= 2^31 - 1, 1 <= topk <= 2048, Q >= 1 (large Q is
+ * chunked inside); anything else is RPR_ERR_INVALID. Device scratch beyond the caller's buffers stays under 64 MB (the
+ * Q x N scores are never stored: the selection recomputes them pass by pass). */
+int rpr_rq_search(rpr_ctx* ctx, const float* queries, int32_t Q, int32_t d, const float* codebooks, int32_t M, int32_t K,
+                  const uint16_t* codes, int64_t N, int32_t topk, int64_t* out_idx, float* out_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

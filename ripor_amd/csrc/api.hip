@@ -890,6 +890,34 @@ int rpr_encode(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t
   return RPR_OK;
 }
 
+// Dense embedding of a text (reference T5SeqAQEncoder.query_encode / T5AQEncoder.query_encode,
+// modeling/t5_generative_retriever.py:786-792, 891-897): the teacher-forced forward with one document of one position,
+// ended by the normalised hidden row instead of a gold-code score.
+int rpr_embed(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lq,
+              float* out, void* stream) {
+  RPR_REQUIRE(c && m && input_ids && attention_mask && out, "NULL argument");
+  RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
+  RPR_REQUIRE(bz >= 1 && bz < (1 << 24) && Lq >= 1 && Lq <= MAX_LQ, "bz or Lq out of range (Lq <= 256)");
+  RPR_REQUIRE(m->d.d_kv == DKV, "the teacher-forced kernels are written for d_kv == 64 (t5-base / t5-large)");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int e = ensure_weight_planes(c, m, s);
+  if (e) return e;
+  e = alloc_train_workspace(c, m, bz, Lq, 1, 1);
+  if (e) return e;
+  Workspace& w = c->ws;
+  const size_t T = (size_t)bz * Lq;
+  RPR_HIP(hipMemcpyAsync(w.ids.p, input_ids, T * 4, hipMemcpyDeviceToDevice, s));
+  RPR_HIP(hipMemcpyAsync(w.mask.p, attention_mask, T * 4, hipMemcpyDeviceToDevice, s));
+  // position 0 is fed with the start embedding (decoder_input_ids = [-1]): no code is read; the slot stays defined anyway
+  int32_t* codes = reinterpret_cast<int32_t*>(P<float>(w.tr_misc) + bz);
+  RPR_HIP(hipMemsetAsync(codes, 0, (size_t)bz * 4, s));
+  PrecGuard prec_guard(c, m);
+  Launcher Ln{c, s};
+  enqueue_train_forward(Ln, c, m, bz, Lq, 1, 1, codes, P<float>(w.tr_misc), out);
+  return Ln.err ? Ln.err : RPR_OK;
+}
+
 int rpr_op_linear(rpr_ctx* c, const float* A, const float* W, const float* residual, float* C, int32_t M, int32_t N,
                   int32_t K, int32_t relu, void* stream) {
   RPR_REQUIRE(c && A && W && C, "NULL argument");

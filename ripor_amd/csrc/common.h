@@ -133,6 +133,24 @@ hipError_t launch_rq_gather(const float* R, int d, const int* idx, int K, float*
 hipError_t launch_rq_update(const float* R, int n, int d, const uint16_t* code, int K, int* hist, int* order, float* C,
                             float* cnorm, hipStream_t s);
 
+// ---- top-k inner-product search over the codes (rq_search.hip; rpr_rq_search in rq_api.hip) ------------
+constexpr int RQS_BINS = 1024;   // ten bits of the 63-bit (score key, row) value per histogram pass
+constexpr int RQS_CAP = 8192;    // candidates of a query the finish kernel sorts in LDS (>= the largest topk)
+struct RqSelState { unsigned long long prefix; unsigned need, above; int done, pad; };
+struct RqScanArgs {
+  const float* lut;              // [Q, M * K] inner products of the queries with every codeword
+  const uint16_t* codes;         // [N, M]
+  long long N; int M, K, Q;
+  RqSelState* st;                // [Q]
+  unsigned* hist;                // [Q, RQS_BINS], zero between passes
+  unsigned long long* cand;      // [Q, RQS_CAP]
+  unsigned* cand_n;              // [Q]
+  int ngroups;                   // filled by the launcher
+};
+int rq_search_group(int M, int K);   // queries a block serves at once (4, 2 or 1 by the size of a query's table)
+// the whole selection for Q queries whose LUT is ready: idx / scores [Q, topk]; cus = CUs of the device
+hipError_t launch_rq_select(const RqScanArgs& a, int topk, int64_t* out_idx, float* out_scores, int cus, hipStream_t s);
+
 // ---- split-precision GEMM: operands as two f16 planes (hi, lo), 3 f16 MFMAs per product ---------
 struct GemmH2Args {
   const __half* A; size_t a_ps; int lda;   // planes [2][M][lda], plane stride a_ps elements
@@ -500,7 +518,7 @@ hipError_t launch_train_dec_embed(const float* start, const float* in_embeds, co
                                   int L, int d, int V, hipStream_t s, XOut xo = XOut{});
 hipError_t launch_gold_scores(const float* x, const float* ln, const float* out_embeds, const int32_t* codes, float* scores,
                               int S, int L, int d, int V, float eps, float post, hipStream_t s,
-                              const __half* x_h = nullptr, size_t x_ps = 0);
+                              const __half* x_h = nullptr, size_t x_ps = 0, float* hidden = nullptr);
 hipError_t launch_margin_mse(const float* scores, const float* teacher_pos, const float* teacher_neg, const int32_t* prefix_lens,
                              int n_prefix, int bz, int L, float* losses, float* margins, hipStream_t s);
 // ---- backward pass + optimizer of the same step (train_kernels.hip) ------------------------------------------------

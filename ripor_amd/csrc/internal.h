@@ -155,6 +155,8 @@ struct Workspace {
   // residual quantization (rpr_rq_train / rpr_rq_encode, rq_api.hip): residuals [n, d], codes, counting-sort
   // histogram / row order, codeword norms, per-block fp64 sums of |r|^2, initial centroid rows
   DevBuf rq_r, rq_code, rq_hist, rq_order, rq_cnorm, rq_part, rq_idx;
+  // rpr_rq_search: the LUT of a query chunk [Qc, M * K] and the selection scratch (state, histograms, candidate lists)
+  DevBuf rq_lut, rq_sel;
 };
 
 static_assert(sizeof(Workspace) % sizeof(DevBuf) == 0 && std::is_standard_layout<Workspace>::value,
@@ -311,7 +313,8 @@ int alloc_train_workspace(rpr_ctx* c, const rpr_model* m, int bz, int Lq, int nd
 void enqueue_encoder(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int Q, int Lq, bool packed);
 void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, int Q, int Lq, int B, int L,
                     unsigned flags, const rpr_debug_taps* taps, const std::vector<int>& forks, bool drop_last);
+// hidden (nullable): decoder_last_hidden_state of every row [bz * ndoc * L, d_model] instead of the gold-code scores (rpr_embed)
 void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L,
-                           const int32_t* codes /*[bz, ndoc, L]*/, float* pos_scores /*[bz, ndoc, L]*/);
+                           const int32_t* codes /*[bz, ndoc, L]*/, float* pos_scores /*[bz, ndoc, L]*/, float* hidden = nullptr);
 
 }  // namespace rpr

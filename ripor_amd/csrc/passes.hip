@@ -574,7 +574,7 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
 // rows (q, doc, position) = bz * n_docs * L, causal block self-attention per (sequence, head), cross-attention with
 // the n_docs * L rows of a query sharing its encoder K/V. Output: the gold-code score of every position.
 void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L,
-                           const int32_t* codes /*[bz, ndoc, L]*/, float* pos_scores /*[bz, ndoc, L]*/) {
+                           const int32_t* codes /*[bz, ndoc, L]*/, float* pos_scores /*[bz, ndoc, L]*/, float* hidden) {
   const auto& d = m->d;
   Workspace& w = c->ws;
   const int T = bz * Lq, S = bz * ndoc, R = S * L, inner = m->inner(), dm = d.d_model, H = d.num_heads;
@@ -614,10 +614,11 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
     p.attn_out(i, 1, m->dec_xo[i], m->h_dec_xo[i]);
     p.ff_block(i, 2, m->dec_ln2[i], m->dec_wi[i], m->h_dec_wi[i], m->dec_wo[i], m->h_dec_wo[i]);
   }
-  // decoder_last_hidden_state (final RMSNorm, scaleup factor) dotted with the gold codes' OUTPUT codebook rows
+  // decoder_last_hidden_state (final RMSNorm, scaleup factor) dotted with the gold codes' OUTPUT codebook rows — or, for
+  // rpr_embed, written out as it is
   Ln.run(RPR_K_OTHER, 2.0 * R * dm, 4.0 * 2 * R * dm, [&] {
     return launch_gold_scores(p.x, d.dec_final_ln, d.out_embeds, codes, pos_scores, S, L, dm, V, p.xs.eps, p.post, s,
-                              p.x_planes(), p.xs.ps);
+                              p.x_planes(), p.xs.ps, hidden);
   });
 }
 

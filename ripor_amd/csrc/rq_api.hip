@@ -1,4 +1,5 @@
-// Docid creation behind the C ABI: rpr_rq_train / rpr_rq_encode (kernels in gemm_f32.hip, buffers in the search workspace).
+// Docid creation behind the C ABI: rpr_rq_train / rpr_rq_encode (kernels in gemm_f32.hip, buffers in the search workspace),
+// and the search over the codes they produce: rpr_rq_search (kernels in rq_search.hip).
 #include <vector>
 
 #include "internal.h"
@@ -106,6 +107,56 @@ int rpr_rq_encode(rpr_ctx* c, const float* x, int64_t n, int32_t d, const float*
     RPR_HIP(launch_rq_assign(a, s));
   }
   if (level_sse) return rq_level_sums(c, n, M, level_sse, s);
+  return RPR_OK;
+}
+
+// ---- top-k inner-product search over the codes (reference: AddictvieQuantizeIndexer.search, tasks/evaluator.py:423-443) --
+// DESIGN.md §9d. Per chunk of queries: one exact-fp32 GEMM fills the LUT [Qc, M * K], then the radix selection of
+// rq_search.hip recomputes the scores from it pass by pass. Scratch per query: the LUT row, 4 KB of histogram and a 64 KB
+// candidate list; a chunk is sized to stay under 60 MB of it.
+int rpr_rq_search(rpr_ctx* c, const float* queries, int32_t Q, int32_t d, const float* codebooks, int32_t M, int32_t K,
+                  const uint16_t* codes, int64_t N, int32_t topk, int64_t* out_idx, float* out_scores, void* stream) {
+  RPR_REQUIRE(c, "NULL argument");
+  RPR_REQUIRE(Q >= 1, "Q must be at least 1");
+  RPR_REQUIRE(d >= 32 && d % 32 == 0, "d must be a positive multiple of 32");
+  RPR_REQUIRE(K >= 64 && K % 64 == 0 && K <= RQ_MAX_K, "K must be a multiple of 64 and at most 1024");
+  RPR_REQUIRE(M >= 1 && M <= 64, "M out of range (1 .. 64)");
+  RPR_REQUIRE(N >= 1 && N <= (int64_t)0x7fffffff, "N out of range (1 .. 2^31 - 1)");
+  RPR_REQUIRE(topk >= 1 && topk <= 2048, "topk out of range (1 .. 2048)");
+  RPR_REQUIRE(queries && codebooks && codes && out_idx && out_scores, "NULL argument");   // after the limits: an empty tensor has no address
+  static_assert(RQS_CAP >= 2048, "the candidate list holds the largest topk");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int cus = 0;
+  RPR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+  const size_t MK = (size_t)M * K;
+  const size_t per_q = MK * sizeof(float) + RQS_BINS * sizeof(unsigned) + RQS_CAP * sizeof(unsigned long long) + sizeof(RqSelState) +
+                       sizeof(unsigned);
+  const int G = rq_search_group(M, K);
+  int64_t qc = (int64_t)(((size_t)60 << 20) / per_q) / G * G;
+  qc = qc < G ? G : qc;
+  qc = qc > Q ? Q : qc;
+  Workspace& w = c->ws;
+  { const int e = ensure(c, w.rq_lut, (size_t)qc * MK * sizeof(float)); if (e) return e; }
+  { const int e = ensure(c, w.rq_sel, (size_t)qc * (per_q - MK * sizeof(float)) + 64); if (e) return e; }
+  RqScanArgs a{};
+  a.lut = P<float>(w.rq_lut);
+  a.codes = codes; a.N = N; a.M = M; a.K = K;
+  a.cand = P<unsigned long long>(w.rq_sel);                                   // 8-byte items first
+  a.st = reinterpret_cast<RqSelState*>(a.cand + (size_t)qc * RQS_CAP);
+  a.hist = reinterpret_cast<unsigned*>(a.st + qc);
+  a.cand_n = a.hist + (size_t)qc * RQS_BINS;
+  for (int64_t q0 = 0; q0 < Q; q0 += qc) {
+    const int nq = (int)(Q - q0 < qc ? Q - q0 : qc);
+    GemmArgs g{};
+    g.A = queries + (size_t)q0 * d; g.lda = d;
+    g.W = codebooks; g.ldw = d;
+    g.out[0] = P<float>(w.rq_lut); g.ldo[0] = (int)MK; g.split_n = (int)MK;
+    g.M = nq; g.N = (int)MK; g.K = d;
+    RPR_HIP(launch_gemm(g, s));
+    a.Q = nq;
+    RPR_HIP(launch_rq_select(a, topk, out_idx + (size_t)q0 * topk, out_scores + (size_t)q0 * topk, cus, s));
+  }
   return RPR_OK;
 }
 

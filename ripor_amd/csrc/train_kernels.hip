@@ -67,14 +67,16 @@ hipError_t launch_train_dec_embed(const float* start, const float* in_embeds, co
 // d_model^-0.5 under config.scaleup_output_hidden) dotted with the OUTPUT codebook row of the doc's code at that
 // position: (query_embeds * doc_embeds).sum(-1) of the reference (:917-918; decode() :812-826). One wave per row,
 // exact fp32 in the reference's operation order (w * (x * rsqrt(mean(x^2) + eps)), then the product, then the sum).
+// hidden (nullable): the normalised row itself is written to hidden[row] and no score is formed (rpr_embed).
 __global__ __launch_bounds__(256) void gold_score_kernel(const float* __restrict__ x, const float* __restrict__ ln,
                                                           const float* __restrict__ out_embeds, const int32_t* __restrict__ codes,
                                                           float* __restrict__ scores, int S, int L, int d, int V, float eps,
-                                                          float post, const __half* __restrict__ x_h, size_t x_ps) {
+                                                          float post, const __half* __restrict__ x_h, size_t x_ps,
+                                                          float* __restrict__ hidden) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= S * L) return;
   const int s = row / L, i = row - s * L;
-  int tok = codes[(size_t)s * L + i];
+  int tok = hidden ? 0 : codes[(size_t)s * L + i];
   tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
   const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * d);
   const float4* wr = reinterpret_cast<const float4*>(ln);
@@ -99,18 +101,21 @@ __global__ __launch_bounds__(256) void gold_score_kernel(const float* __restrict
     const float4 v = load4(k), g = wr[k], e = er[k];
     float4 h = make_float4(g.x * (v.x * rs), g.y * (v.y * rs), g.z * (v.z * rs), g.w * (v.w * rs));
     if (post != 1.0f) { h.x *= post; h.y *= post; h.z *= post; h.w *= post; }
+    if (hidden) reinterpret_cast<float4*>(hidden + (size_t)row * d)[k] = h;
     acc += (h.x * e.x + h.y * e.y) + (h.z * e.z + h.w * e.w);
   }
+  if (hidden) return;
   acc = wave_sum_f(acc);
   if (lane == 0) scores[row] = acc;
 }
 
 hipError_t launch_gold_scores(const float* x, const float* ln, const float* out_embeds, const int32_t* codes, float* scores,
-                              int S, int L, int d, int V, float eps, float post, hipStream_t s, const __half* x_h, size_t x_ps) {
+                              int S, int L, int d, int V, float eps, float post, hipStream_t s, const __half* x_h, size_t x_ps,
+                              float* hidden) {
   const int rows = S * L;
   if (rows <= 0) return hipSuccess;
   hipLaunchKernelGGL(gold_score_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, ln, out_embeds, codes, scores, S, L, d, V, eps,
-                     post, x_h, x_ps);
+                     post, x_h, x_ps, hidden);
   return hipGetLastError();
 }
 

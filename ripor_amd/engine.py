@@ -1103,3 +1103,55 @@ def rq_encode(ctx: Context, x, codebooks: torch.Tensor, chunk_rows: int = 1 << 2
             if err:
                 raise err[0]
     return codes, sse / max(N, 1)
+
+
+def embed(model: DeviceModel, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+    """Dense embedding of every text: ``decoder_last_hidden_state[:, 0, :]`` of the encoder plus one decoder position fed
+    with the start embedding (reference ``query_encode``, modeling/t5_generative_retriever.py:786-792). -> fp32 [bz, d_model]
+    on the model's device. The pass follows the context's precision."""
+    dev = model.ctx.device
+    ids = input_ids.to(device=dev, dtype=torch.int32).contiguous()
+    mask = attention_mask.to(device=dev, dtype=torch.int32).contiguous()
+    bz, Lq = ids.shape
+    if Lq % 8 and Lq < 256:   # same bucketing as search(): masked padding columns, identical results
+        pad = min(256, (Lq + 7) // 8 * 8) - Lq
+        ids = torch.nn.functional.pad(ids, (0, pad)); mask = torch.nn.functional.pad(mask, (0, pad)); Lq += pad
+    out = torch.empty((bz, model.d_model), dtype=torch.float32, device=dev)
+    check(model.ctx.lib.rpr_embed(model.ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lq, out.data_ptr(),
+                                  _stream_ptr(dev)), "rpr_embed")
+    return out
+
+
+def _codes_on_device(codes, dev) -> torch.Tensor:
+    """uint16 codes [N, M] as an int16 device tensor (torch has no device arithmetic on uint16; the bits are what counts)."""
+    if isinstance(codes, torch.Tensor):
+        if codes.dtype not in (torch.int16, torch.uint16):
+            raise ValueError(f"codes must be 16-bit, got {codes.dtype}")
+        return codes.view(torch.int16).to(dev).contiguous()
+    arr = np.ascontiguousarray(codes)
+    if arr.dtype not in (np.uint16, np.int16):
+        raise ValueError(f"codes must be 16-bit, got {arr.dtype}")
+    return torch.from_numpy(arr.view(np.int16)).to(dev)
+
+
+def rq_search(ctx: Context, queries, codebooks, codes, topk: int):
+    """Top-``topk`` rows of every query by inner product with the decoded codes (``rpr_rq_search``).
+    ``queries`` fp32 [Q, d], ``codebooks`` fp32 [M, K, d], ``codes`` uint16 [N, M] (``rq_encode``'s layout): device tensors,
+    or host arrays that are uploaded. -> (idx int64 [Q, topk], scores fp32 [Q, topk]) on the device; past N rows the tail
+    is idx -1, score -inf."""
+    dev = ctx.device
+    q = torch.as_tensor(queries, dtype=torch.float32).to(dev).contiguous()
+    books = torch.as_tensor(codebooks, dtype=torch.float32).to(dev).contiguous()
+    cd = _codes_on_device(codes, dev)
+    if q.dim() != 2 or books.dim() != 3 or cd.dim() != 2:
+        raise ValueError("queries [Q, d], codebooks [M, K, d] and codes [N, M] expected")
+    Q, d = q.shape
+    M, K, d2 = books.shape
+    if d2 != d or cd.shape[1] != M:
+        raise ValueError(f"queries of width {d} and codes of {cd.shape[1]} levels against codebooks {tuple(books.shape)}")
+    topk = int(topk)
+    idx = torch.empty((Q, max(topk, 0)), dtype=torch.int64, device=dev)
+    scores = torch.empty((Q, max(topk, 0)), dtype=torch.float32, device=dev)
+    check(ctx.lib.rpr_rq_search(ctx.handle, q.data_ptr(), Q, d, books.data_ptr(), M, K, cd.data_ptr(), cd.shape[0], topk,
+                                idx.data_ptr(), scores.data_ptr(), _stream_ptr(dev)), "rpr_rq_search")
+    return idx, scores

@@ -30,6 +30,7 @@ from .utils.metrics import load_and_evaluate
 from .utils.utils import convert_ptsmtids_to_strsmtid, get_dataset_name
 
 QUERY_PREFIX = "query: "  # reference dataset/dataset.py:15
+AQ_EVALUATE_TOPK, AQ_EVALUATE_BATCH = 200, 128   # hard-coded in the reference's aq_evaluate (evaluate.py:302-332)
 
 
 class DocidTable:
@@ -628,6 +629,35 @@ def aq_index(args):
     return train_index(args.mmap_dir, args.index_dir, args.num_subvectors_for_pq, args.codebook_bits)
 
 
+def aq_evaluate(args):
+    """reference evaluate.py:302-332: embeds every query collection, searches the residual-quantizer index for the top 200
+    documents of each query (``rpr_rq_search`` instead of faiss), writes ``out_dir/<dataset>/run.json`` and evaluates."""
+    from transformers import AutoTokenizer
+    from .modeling.t5_generative_retriever import T5AQEncoder
+    from .tasks.rq_indexer import check_index, search_index
+
+    absent = [f for f in ("pretrained_path", "mmap_dir", "index_dir", "out_dir") if not getattr(args, f)]
+    if absent:
+        raise ValueError(f"task: {args.task} is not valid without " + ", ".join("--" + f for f in absent))
+    info = check_index(args.mmap_dir, args.index_dir)   # before the checkpoint is read
+    model = T5AQEncoder.from_pretrained(args.pretrained_path)
+    model.eval()
+    if info["d"] != model.config.d_model:
+        raise ValueError(f"the index in {args.index_dir} holds vectors of width {info['d']}, the model's d_model is "
+                         f"{model.config.d_model}")
+    local_rank = max(0, int(args.local_rank if args.local_rank >= 0 else os.environ.get("LOCAL_RANK", 0)))
+    model.to(_device_index(local_rank))
+    tokenizer = AutoTokenizer.from_pretrained(args.pretrained_path)
+    os.makedirs(args.out_dir, exist_ok=True)
+    for data_dir in _list_flag(args.q_collection_paths):
+        coll = QueryCollection(data_dir)
+        out_dir = os.path.join(args.out_dir, get_dataset_name(data_dir))
+        print("out_dir: ", out_dir)
+        loader = query_batches(coll, tokenizer, list(range(len(coll))), AQ_EVALUATE_BATCH, 256)
+        search_index(model, loader, args.mmap_dir, args.index_dir, out_dir, topk=AQ_EVALUATE_TOPK)
+    return evaluate(args)
+
+
 def get_args(argv=None):
     """EvalArguments fields used by the generative-retrieval branch (reference arguments.py:145-212)."""
     ap = argparse.ArgumentParser()
@@ -676,6 +706,8 @@ def main(argv=None):
         mmap_2(args)
     elif args.task == "aq_index":
         aq_index(args)
+    elif args.task == "aq_evaluate":
+        aq_evaluate(args)
     else:
         raise ValueError(f"task: {args.task} is not valid.")
 

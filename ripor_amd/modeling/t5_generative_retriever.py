@@ -238,6 +238,32 @@ class T5SeqAQEncoder:
     def save_pretrained(self, save_dir):
         self.base_model.save_pretrained(save_dir)
 
+    def query_encode(self, **inputs):
+        """reference :786-792: ``decoder_last_hidden_state[:, 0, :]`` of the encoder plus one decoder position fed with the
+        start embedding (``decoder_input_ids = [-1]``, which is all a query collection carries). -> fp32 [bz, d_model]."""
+        from .. import engine as E
+        dec = inputs.get("decoder_input_ids")
+        if dec is not None and (dec.dim() != 2 or dec.shape[1] != 1 or bool((dec != -1).any())):
+            raise ValueError("query_encode embeds with one decoder position fed by the start embedding: decoder_input_ids must be [-1]")
+        return E.embed(self.base_model.engine_model(), inputs["input_ids"], inputs["attention_mask"])
+
+    def decode(self, text_encodings, summation=False):
+        """reference :811-830: the output-codebook rows of every position's code, [bz, smtid_length, d_model]
+        (or their sum over the positions, [bz, d_model])."""
+        sd = self.base_model.state_dict()
+        name = "list_decoder_embeds" if self.config.shared_output_input_embeds else "list_output_embeds"
+        enc = torch.as_tensor(text_encodings).long().cpu()
+        embeds = torch.stack([sd[f"{name}.{i}.weight"].cpu()[enc[:, i]] for i in range(enc.shape[1])], dim=1)
+        return embeds.sum(dim=1) if summation else embeds
+
+
+class T5AQEncoder(T5SeqAQEncoder):
+    """reference :886-900: the dense view of the same model — ``query_encode`` as above, ``decode`` summed over the levels
+    (the vector a residual-quantizer code stands for)."""
+
+    def decode(self, text_encodings):
+        return super().decode(text_encodings, summation=True)
+
 
 class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
     """reference :902-966 — forward of the prefix-oriented ranking fine-tune step, same

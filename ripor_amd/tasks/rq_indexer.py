@@ -94,3 +94,54 @@ def load_index(index_dir: str):
     books = np.load(os.path.join(index_dir, "rq_codebooks.npy"))
     assert books.shape == (info["M"], info["K"], info["d"]), (books.shape, info)
     return books, info
+
+
+def check_index(mmap_dir: str, index_dir: str, d_model: int = None):
+    """The files ``search_index`` needs, or a ValueError that names what is missing or does not fit."""
+    for path in (os.path.join(index_dir, "rq.json"), os.path.join(index_dir, "rq_codebooks.npy"),
+                 os.path.join(mmap_dir, "text_ids.tsv"), os.path.join(mmap_dir, "doc_embeds.mmap"),
+                 os.path.join(mmap_dir, "meta.pkl")):
+        if not os.path.exists(path):
+            raise ValueError(f"{path} not found: run --task=mmap_2 and --task=aq_index first")
+    with open(os.path.join(index_dir, "rq.json")) as f:
+        info = json.load(f)
+    if d_model is not None and int(info["d"]) != int(d_model):
+        raise ValueError(f"the index in {index_dir} holds vectors of width {info['d']}, the model's d_model is {d_model}")
+    return info
+
+
+def read_text_ids(mmap_dir: str):
+    with open(os.path.join(mmap_dir, "text_ids.tsv")) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def search_index(model, loader, mmap_dir: str, index_dir: str, out_dir: str, topk: int = 200) -> dict:
+    """Searches the residual-quantizer index for every query of ``loader`` (replaces ``AddictvieQuantizeIndexer.search``,
+    reference tasks/evaluator.py:423-443, faiss.IndexResidualQuantizer.search with METRIC_INNER_PRODUCT): the collection is
+    encoded with the trained codebooks (streamed, nothing cached on disk) and the codes stay on the device; every query batch
+    is embedded (``model.query_encode``) and searched (``engine.rq_search``); ``out_dir/run.json`` = {qid: {docid: score}}.
+    ``loader`` yields dicts with ``input_ids``, ``attention_mask`` and ``id``; ``model`` is a T5SeqAQEncoder on a HIP device."""
+    import torch
+    from .. import engine as E
+    em = model.base_model.engine_model()
+    check_index(mmap_dir, index_dir, em.d_model)
+    books, info = load_index(index_dir)
+    X = load_doc_embeds(mmap_dir)
+    text_ids = read_text_ids(mmap_dir)
+    if X.shape[1] != info["d"] or len(text_ids) != X.shape[0]:
+        raise ValueError(f"{mmap_dir}: {X.shape[0]} x {X.shape[1]} embeddings, {len(text_ids)} ids, index width {info['d']}")
+    ctx = em.ctx
+    books_dev = torch.from_numpy(np.ascontiguousarray(books)).to(ctx.device)
+    codes, _ = E.rq_encode(ctx, X, books_dev)
+    codes_dev = torch.from_numpy(codes.view(np.int16)).to(ctx.device)
+    qid_to_rankdata = {}
+    for batch in loader:
+        q = E.embed(em, batch["input_ids"], batch["attention_mask"])
+        idx, scores = E.rq_search(ctx, q, books_dev, codes_dev, topk)
+        idx, scores = idx.cpu().tolist(), scores.cpu().tolist()
+        for qid, rows, scs in zip(batch["id"].tolist(), idx, scores):
+            qid_to_rankdata[str(qid)] = {str(text_ids[r]): float(s) for r, s in zip(rows, scs) if r >= 0}
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "run.json"), "w") as f:
+        json.dump(qid_to_rankdata, f)
+    return qid_to_rankdata

@@ -5,7 +5,14 @@ achieved fp32 rate against the 157.3 TF/s fp32 MFMA peak of the MI355X. One JSON
   python tools/rq_bench.py --n 8841823 --d 768 --M 32 --K 256
 
 The embeddings are generated on the device (anisotropic Gaussian, seeded); the host memmap path of the CLI is not part of
-the timed region."""
+the timed region.
+
+  python tools/rq_bench.py --search --n 8841823 --d 768 --M 32 --K 256 --Q 128 --topk 200
+
+times rpr_rq_search alone over seeded random codes: the first call (cold: scratch allocation, code objects)
+and the best and median of --repeats warm calls by device events, the code bytes per second it streams (one read of the
+code matrix per pass) and the LUT lookups per second it sustains (Q N M per pass), and as the yardstick on the same card
+a plain torch path: the LUT by matmul, per chunk of queries the level sum of LUT columns gathered by the codes, torch.topk."""
 import argparse
 import json
 import os
@@ -20,6 +27,57 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PEAK_F32_TFLOPS = 157.3
 
 
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e-3, out
+
+
+def search_leg(args, E):
+    ctx = E.Context.get(0)
+    N, d, M, K, Q, topk = args.n, args.d, args.M, args.K, args.Q, args.topk
+    g = torch.Generator(device="cuda").manual_seed(0)
+    books = torch.randn((M, K, d), generator=g, device="cuda") * torch.linspace(1.0, 0.05, M, device="cuda")[:, None, None]
+    q = torch.randn((Q, d), generator=g, device="cuda")
+    codes = torch.randint(0, K, (N, M), generator=g, device="cuda", dtype=torch.int16)
+    torch.cuda.synchronize()
+    cold, _ = _timed(lambda: E.rq_search(ctx, q, books, codes, topk))
+    warm = []
+    for _ in range(max(3, args.repeats)):
+        t, (idx, sc) = _timed(lambda: E.rq_search(ctx, q, books, codes, topk))
+        warm.append(t)
+
+    def torch_path():
+        lut = (q @ books.reshape(M * K, d).T).reshape(Q, M, K)
+        out_i, out_s = [], []
+        for q0 in range(0, Q, args.torch_chunk):
+            part = lut[q0:q0 + args.torch_chunk]
+            s = torch.zeros((part.shape[0], N), device="cuda")
+            for m in range(M):
+                s += part[:, m].index_select(1, codes_l[:, m])
+            v, i = torch.topk(s, topk, dim=1)
+            out_i.append(i); out_s.append(v)
+        return torch.cat(out_i), torch.cat(out_s)
+
+    codes_l = codes.long()
+    _timed(torch_path)   # warm-up of every shape
+    t_torch, (ti, ts) = min((_timed(torch_path) for _ in range(2)), key=lambda r: r[0])
+    best, med = min(warm), sorted(warm)[len(warm) // 2]
+    same = float((ti == idx).float().mean())
+    out = dict(metric="rq_search", n=N, d=d, M=M, K=K, Q=Q, topk=topk, cold_s=round(cold, 5), warm_s=round(best, 5),
+               warm_median_s=round(med, 5), warm_s_all=[round(t, 5) for t in warm],
+               queries_per_s=round(Q / best, 1),
+               # per pass over the rows: the code matrix once from HBM (the other query groups hit the caches), Q N M lookups
+               code_gb_per_s_per_pass_time=round(N * M * 2 / best / 1e9, 1),
+               lut_lookups_per_s_per_pass_time=float("%.4g" % (Q * N * M / best)),
+               torch_s=round(t_torch, 5), torch_over_rq_search=round(t_torch / best, 2),
+               idx_equal_to_torch_frac=round(same, 6), max_score_diff_to_torch=float((ts - sc).abs().max()))
+    print(json.dumps(out), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8841823)
@@ -29,8 +87,14 @@ def main(argv=None):
     ap.add_argument("--niter", type=int, default=25)
     ap.add_argument("--chunk_rows", type=int, default=1 << 21)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--search", action="store_true", help="time rpr_rq_search instead of training / encoding")
+    ap.add_argument("--Q", type=int, default=128)
+    ap.add_argument("--topk", type=int, default=200)
+    ap.add_argument("--torch_chunk", type=int, default=8, help="queries per chunk of the torch yardstick")
     args = ap.parse_args(argv)
     from ripor_amd import engine as E
+    if args.search:
+        return search_leg(args, E)
 
     ctx = E.Context.get(0)
     N, d, M, K = args.n, args.d, args.M, args.K
