@@ -434,6 +434,22 @@ int rpr_rq_train(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, int32_t M, 
  * chunking. */
 int rpr_rq_encode(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K,
                   uint16_t* codes, double* level_sse, void* stream);
+/* The same with a beam (faiss's max_beam_size; DESIGN.md 9c, tests/rq_beam_ref.py restates it in numpy). A row keeps up to
+ * `beam` candidate encodings: b_0 = 1 (the row), b_{m+1} = min(beam, b_m K). At level m every candidate (s, k), s < b_m,
+ * k < K, has total(s, k) = |r_s|^2 + (|c_k|^2 - 2 r_s.c_k): the score in fp32 as in rpr_rq_encode, |r_s|^2 a fixed-order
+ * sum over the stored fp32 residual, the two added in fp64. The b_{m+1} smallest totals form the next beam, exact ties to
+ * the smaller parent slot s, then the smaller k, stored in that order (slot 0 is the best; nothing is de-duplicated);
+ * residual = fp32(r_s - c_k). codes[n, M] is the history of slot 0 after the last level, level_sse[m] the sum of slot 0's
+ * |r|^2 after level m. beam = 1 is rpr_rq_encode: the same codes and the same level_sse bits. Deterministic, no float
+ * atomics; a row's codes do not depend on the chunking. Inputs must be finite. The limits of rpr_rq_encode and
+ * 1 <= beam <= 8; anything else is RPR_ERR_INVALID. Workspace in the context, B = beam:
+ *   2 * n * B * d * 4   two residual planes (a parent is read by several children: a level cannot run in place)
+ * + n * B * 8           |r|^2 of the entries, two planes
+ * + n * B * B * 6       a level's candidates: the B best (score fp32, code u16) of every entry
+ * + M * n * B * 3       parent slot (u8) and code (u16) of every entry of every level
+ * + M * K * 4 + M * ceil(n / 128) * 8   codeword norms and per-block fp64 partials, as rpr_rq_encode. */
+int rpr_rq_encode_beam(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K,
+                       int32_t beam, uint16_t* codes, double* level_sse, void* stream);
 
 /* ---- searching the residual-quantizer index (reference --task=aq_evaluate: evaluate.py:302-332,
  * AddictvieQuantizeIndexer.search, tasks/evaluator.py:423-443) ---- */

@@ -143,6 +143,8 @@ SIGNATURES = {
                                C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "rpr_rq_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "rpr_rq_encode_beam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "rpr_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rpr_rq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,7 +1,8 @@
 """CLI-compatible replacement of reference aq_preprocess/create_customized_smtid_file.py:14-80.
 
 Encodes every row of ``model_dir/mmap/doc_embeds.mmap`` with the residual quantizer of ``model_dir/aq_index`` on the
-device (rpr_rq_encode; the reference runs faiss's ``rq.compute_codes`` on the CPU) and writes
+device (rpr_rq_encode, or rpr_rq_encode_beam with ``--max_beam_size`` above 1; the reference runs faiss's
+``rq.compute_codes`` on the CPU, whose beam is 5) and writes
 ``model_dir/aq_smtid/docid_to_smtid.json`` = {docid: [-1, c_1 .. c_M]}, plus the binary trie cache beside it
 (``list_smtid_to_nextids.rprtrie``) so that the first retrieval does not parse the JSON."""
 from __future__ import annotations
@@ -22,6 +23,8 @@ def get_args(argv=None):
     ap.add_argument("--model_dir", default="", type=str)
     ap.add_argument("--M", default=32, type=int)
     ap.add_argument("--bits", default=8, type=int)
+    ap.add_argument("--max_beam_size", default=1, type=int,
+                    help="candidate encodings kept per document through the levels (1: greedy; faiss's default is 5)")
     return ap.parse_args(argv)
 
 
@@ -61,7 +64,7 @@ def main(argv=None):
         raise ValueError(f"the index holds M = {info['M']}, K = {info['K']}; --M {M} --bits {args.bits} asks for K = {K}")
     assert len(docids) == X.shape[0], (len(docids), X.shape)
     ctx = E.Context.get(None)
-    codes, mse = E.rq_encode(ctx, X, torch.from_numpy(books).to(ctx.device))
+    codes, mse = E.rq_encode(ctx, X, torch.from_numpy(books).to(ctx.device), beam=args.max_beam_size)
     for m, v in enumerate(mse):
         print(f"[level {m}] encoding MSE after the level: {v:.6g}")
     print("size of docid_to_smtid = {}".format(len(docids)))

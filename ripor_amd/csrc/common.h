@@ -133,6 +133,30 @@ hipError_t launch_rq_gather(const float* R, int d, const int* idx, int K, float*
 hipError_t launch_rq_update(const float* R, int n, int d, const uint16_t* code, int K, int* hist, int* order, float* C,
                             float* cnorm, hipStream_t s);
 
+// ---- beam encoding (rq_beam.hip; rpr_rq_encode_beam in rq_api.hip) ------------------------------------
+// A row's beam holds b entries (residual rows (row * b + s) of a plane, slot 0 the best); a level makes T children of it.
+constexpr int RQ_MAX_BEAM = 8;
+struct RqTopTArgs {
+  const float* R; long long rows; int d;       // [rows, d] residuals of all beam entries
+  const float* C; const float* cnorm; int K;   // [K, d] codebook and its squared row norms
+  int T;                                       // 1 .. RQ_MAX_BEAM
+  float* cand_v; uint16_t* cand_k;             // [rows, T] out: the T smallest |c_k|^2 - 2 r.c_k of a row in (score, k) order
+};
+hipError_t launch_rq_topt(const RqTopTArgs& a, hipStream_t s);
+struct RqMergeArgs {
+  const float* Rin; const float* rnorm;        // [n * b, d] parents and their |r|^2 [n * b] (nullptr: zeros)
+  long long n; int b, d, T;
+  const float* cand_v; const uint16_t* cand_k; // [n * b, T] from launch_rq_topt
+  const float* C;                              // [K, d]
+  float* Rout; float* rnorm_out;               // [n * T, d] children (another buffer than Rin), [n * T]
+  unsigned char* par; uint16_t* code; int hstride;   // parent slot and code of child t of a row -> [row * hstride + t]
+  double* part;                                // part[block of RQ_BM rows] = sum of slot 0's new |r|^2, fixed order
+};
+hipError_t launch_rq_merge(const RqMergeArgs& a, hipStream_t s);
+// codes[row * M + m] along the parent slots back from slot 0 of the last level; par / code: M planes of [n * hstride]
+hipError_t launch_rq_backtrack(const unsigned char* par, const uint16_t* code, long long n, int M, int hstride, uint16_t* codes,
+                               hipStream_t s);
+
 // ---- top-k inner-product search over the codes (rq_search.hip; rpr_rq_search in rq_api.hip) ------------
 constexpr int RQS_BINS = 1024;   // ten bits of the 63-bit (score key, row) value per histogram pass
 constexpr int RQS_CAP = 8192;    // candidates of a query the finish kernel sorts in LDS (>= the largest topk)

@@ -1,4 +1,5 @@
 // Docid creation behind the C ABI: rpr_rq_train / rpr_rq_encode (kernels in gemm_f32.hip, buffers in the search workspace),
+// rpr_rq_encode_beam (kernels in rq_beam.hip),
 // and the search over the codes they produce: rpr_rq_search (kernels in rq_search.hip).
 #include <vector>
 
@@ -106,6 +107,54 @@ int rpr_rq_encode(rpr_ctx* c, const float* x, int64_t n, int32_t d, const float*
                    static_cast<double*>(w.rq_part.p) + (size_t)m * nblk};
     RPR_HIP(launch_rq_assign(a, s));
   }
+  if (level_sse) return rq_level_sums(c, n, M, level_sse, s);
+  return RPR_OK;
+}
+
+// Beam encoding (kernels in rq_beam.hip). Level m turns the b_m beam entries of every row (b_0 = 1: the row
+// itself, read from x) into T children: T = beam, and 1 at the last level, where only slot 0 is asked for. The planes
+// alternate: a parent is read by several children, so a level cannot run in place.
+int rpr_rq_encode_beam(rpr_ctx* c, const float* x, int64_t n, int32_t d, const float* codebooks, int32_t M, int32_t K, int32_t beam,
+                       uint16_t* codes, double* level_sse, void* stream) {
+  { const int e = rq_check(c, x, n, d, M, K, codebooks); if (e) return e; }
+  RPR_REQUIRE(codes, "NULL codes");
+  RPR_REQUIRE(beam >= 1 && beam <= RQ_MAX_BEAM, "beam out of range (1 .. 8)");
+  static_assert(RQ_MAX_BEAM == 8, "the message above names the limit");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Workspace& w = c->ws;
+  const size_t nblk = (size_t)((n + RQ_BM - 1) / RQ_BM), ent = (size_t)n * beam;   // beam entries of a level
+  const size_t par_bytes = ((size_t)M * ent + 255) & ~(size_t)255;
+  int e = ensure(c, w.rq_r, ent * d * sizeof(float));
+  if (!e) e = ensure(c, w.rq_r2, ent * d * sizeof(float));
+  if (!e) e = ensure(c, w.rq_bnorm, 2 * ent * sizeof(float));
+  if (!e) e = ensure(c, w.rq_cand, ent * beam * (sizeof(float) + sizeof(uint16_t)));
+  if (!e) e = ensure(c, w.rq_bhist, par_bytes + (size_t)M * ent * sizeof(uint16_t));
+  if (!e) e = ensure(c, w.rq_cnorm, (size_t)M * K * sizeof(float));
+  if (!e) e = ensure(c, w.rq_part, (size_t)M * nblk * sizeof(double));
+  if (e) return e;
+  float* plane[2] = {P<float>(w.rq_r), P<float>(w.rq_r2)};
+  float* rnorm[2] = {P<float>(w.rq_bnorm), P<float>(w.rq_bnorm) + ent};
+  float* cand_v = P<float>(w.rq_cand);
+  uint16_t* cand_k = reinterpret_cast<uint16_t*>(cand_v + ent * beam);
+  unsigned char* par = P<unsigned char>(w.rq_bhist);
+  uint16_t* code = reinterpret_cast<uint16_t*>(par + par_bytes);
+  float* cnorm = P<float>(w.rq_cnorm);
+  RPR_HIP(launch_rq_norms(codebooks, M * K, d, cnorm, s));
+  const float* Rin = x;
+  const float* rn_in = nullptr;   // one parent: its |r|^2 orders nothing
+  int b = 1;
+  for (int m = 0; m < M; ++m) {
+    const float* Cm = codebooks + (size_t)m * K * d;
+    const int T = m == M - 1 ? 1 : beam;
+    RqTopTArgs t{Rin, (long long)n * b, d, Cm, cnorm + (size_t)m * K, K, T, cand_v, cand_k};
+    RPR_HIP(launch_rq_topt(t, s));
+    RqMergeArgs g{Rin, rn_in, (long long)n, b, d, T, cand_v, cand_k, Cm, plane[m & 1], rnorm[m & 1],
+                  par + (size_t)m * ent, code + (size_t)m * ent, beam, P<double>(w.rq_part) + (size_t)m * nblk};
+    RPR_HIP(launch_rq_merge(g, s));
+    Rin = plane[m & 1]; rn_in = rnorm[m & 1]; b = T;
+  }
+  RPR_HIP(launch_rq_backtrack(par, code, (long long)n, M, beam, codes, s));
   if (level_sse) return rq_level_sums(c, n, M, level_sse, s);
   return RPR_OK;
 }

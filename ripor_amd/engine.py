@@ -1027,8 +1027,14 @@ def rq_train(ctx: Context, x_train: torch.Tensor, M: int, K: int, init_idx: np.n
     return books, np.asarray(list(mse), dtype=np.float64)
 
 
-def rq_encode(ctx: Context, x, codebooks: torch.Tensor, chunk_rows: int = 1 << 20):
-    """Greedy residual encoding of every row of ``x`` with trained codebooks (fp32 [M, K, d] on the device).
+RQ_MAX_BEAM, RQ_BEAM_PLANE_BYTES = 8, 8 << 30
+
+
+def rq_encode(ctx: Context, x, codebooks: torch.Tensor, chunk_rows: int = 1 << 20, beam: int = 1):
+    """Residual encoding of every row of ``x`` with trained codebooks (fp32 [M, K, d] on the device): the greedy chain
+    (``beam`` = 1, ``rpr_rq_encode``), or ``beam`` candidate encodings kept per row through the levels and the best one
+    returned (``rpr_rq_encode_beam``, faiss's ``max_beam_size``). A beam lowers ``chunk_rows`` so that the
+    two residual planes of a chunk (2 * rows * beam * d * 4 bytes) stay under 8 GB.
     ``x``: a device tensor (encoded chunk by chunk in place), or a host array / np.memmap [N, d] streamed through two pinned
     buffers (the copy of chunk i + 1 runs while chunk i is encoded). -> (codes: uint16 [N, M] host array,
     level_mse: float64 [M], the mean |r|^2 of all rows after each level). The codes do not depend on chunk_rows."""
@@ -1043,13 +1049,22 @@ def rq_encode(ctx: Context, x, codebooks: torch.Tensor, chunk_rows: int = 1 << 2
     sse = np.zeros(M, dtype=np.float64)
     part = (C.c_double * M)()
     stream = torch.cuda.current_stream(dev)
+    beam = int(beam)
+    if beam != 1:
+        if not 1 <= beam <= RQ_MAX_BEAM:
+            raise ValueError(f"beam must be 1 .. {RQ_MAX_BEAM}, got {beam}")
+        chunk_rows = min(int(chunk_rows), RQ_BEAM_PLANE_BYTES // (2 * beam * d * 4))
     chunk_rows = max(1, min(int(chunk_rows), max(N, 1)))
     codes_dev = torch.empty((chunk_rows, M), dtype=torch.int16, device=dev)
 
     def run(xc: torch.Tensor, lo: int):
         n = xc.shape[0]
-        check(ctx.lib.rpr_rq_encode(ctx.handle, xc.data_ptr(), n, d, books.data_ptr(), M, K, codes_dev.data_ptr(), part,
-                                    C.c_void_p(stream.cuda_stream)), "rpr_rq_encode")   # synchronises the stream (level sums)
+        if beam == 1:
+            check(ctx.lib.rpr_rq_encode(ctx.handle, xc.data_ptr(), n, d, books.data_ptr(), M, K, codes_dev.data_ptr(), part,
+                                        C.c_void_p(stream.cuda_stream)), "rpr_rq_encode")   # synchronises the stream (level sums)
+        else:
+            check(ctx.lib.rpr_rq_encode_beam(ctx.handle, xc.data_ptr(), n, d, books.data_ptr(), M, K, beam, codes_dev.data_ptr(),
+                                             part, C.c_void_p(stream.cuda_stream)), "rpr_rq_encode_beam")   # synchronises too
         sse[:] += np.asarray(list(part))
         with torch.cuda.stream(stream):
             codes[lo:lo + n] = codes_dev[:n].cpu().numpy().view(np.uint16)

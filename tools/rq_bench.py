@@ -2,7 +2,10 @@
 embeddings and encodes all N rows on the device (rpr_rq_train / rpr_rq_encode), each timed on its own, and reports the
 achieved fp32 rate against the 157.3 TF/s fp32 MFMA peak of the MI355X. One JSON line on stdout.
 
-  python tools/rq_bench.py --n 8841823 --d 768 --M 32 --K 256
+  python tools/rq_bench.py --n 8841823 --d 768 --M 32 --K 256 [--beam 5]
+
+--beam N encodes with a beam of N candidate encodings per row (rpr_rq_encode_beam; the training stays greedy); the encode
+rate then counts the distance work of the beam, (1 + (M - 1) N) / M times the greedy one.
 
 The embeddings are generated on the device (anisotropic Gaussian, seeded); the host memmap path of the CLI is not part of
 the timed region.
@@ -87,6 +90,7 @@ def main(argv=None):
     ap.add_argument("--niter", type=int, default=25)
     ap.add_argument("--chunk_rows", type=int, default=1 << 21)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--beam", type=int, default=1, help="beam of the encode leg (1: greedy rpr_rq_encode; else rpr_rq_encode_beam)")
     ap.add_argument("--search", action="store_true", help="time rpr_rq_search instead of training / encoding")
     ap.add_argument("--Q", type=int, default=128)
     ap.add_argument("--topk", type=int, default=200)
@@ -109,7 +113,8 @@ def main(argv=None):
 
     # warm-up of every shape the timed region uses
     E.rq_train(ctx, Xs, M, K, init, niter=1)
-    E.rq_encode(ctx, X[:min(N, args.chunk_rows)], torch.zeros((M, K, d), device="cuda"), chunk_rows=args.chunk_rows)
+    E.rq_encode(ctx, X[:min(N, args.chunk_rows)], torch.zeros((M, K, d), device="cuda"), chunk_rows=args.chunk_rows,
+                beam=args.beam)
     torch.cuda.synchronize()
 
     train_s, enc_s = [], []
@@ -119,13 +124,13 @@ def main(argv=None):
         torch.cuda.synchronize()
         train_s.append(time.perf_counter() - t0)
         t0 = time.perf_counter()
-        codes, enc_mse = E.rq_encode(ctx, X, books, chunk_rows=args.chunk_rows)
+        codes, enc_mse = E.rq_encode(ctx, X, books, chunk_rows=args.chunk_rows, beam=args.beam)
         torch.cuda.synchronize()
         enc_s.append(time.perf_counter() - t0)
     train_flop = 2.0 * n_train * K * d * M * (args.niter + 1)
-    enc_flop = 2.0 * N * K * d * M
+    enc_flop = 2.0 * N * K * d * (1 + (M - 1) * args.beam)   # level 0 scores the row, every later level its beam entries
     tr, en = min(train_s), min(enc_s)
-    out = dict(metric="rq_docid_creation", n=N, d=d, M=M, K=K, niter=args.niter, n_train=n_train,
+    out = dict(metric="rq_docid_creation", n=N, d=d, M=M, K=K, niter=args.niter, n_train=n_train, beam=args.beam,
                train_s=round(tr, 4), encode_s=round(en, 4), train_s_all=[round(t, 4) for t in train_s],
                encode_s_all=[round(t, 4) for t in enc_s],
                train_tflops=round(train_flop / tr / 1e12, 2), encode_tflops=round(enc_flop / en / 1e12, 2),
