@@ -257,6 +257,16 @@ int32_t rpr_forced_tail(const rpr_ctx* ctx);
 int rpr_set_fork_depths(rpr_ctx* ctx, int32_t n, const int32_t* depths);
 int rpr_fork_depths(rpr_ctx* ctx, rpr_model* model, rpr_trie* trie, int32_t Q, int32_t B, int32_t L, uint32_t flags,
                     int32_t* out_depths);
+/* Layer-0 Q/K/V table. The decoder's input row at layer 0 depends on (position, token) alone, so its self-attention
+ * projection does too: in RPR_PREC_F16X2 the first rpr_search of a model makes the L * V + 1 rows of q | k | v once (on
+ * the device, by the projection kernel itself), and the searches read rows of it where they would launch that projection
+ * through the 256 x 256 tile kernel; results are the same bits. rpr_adamw_step and rpr_set_precision drop the table (the
+ * next search makes it again); a model whose table would exceed 160 MiB (t5-3b at 32 x 256) keeps the projection.
+ *   rpr_set_l0_table(ctx, mode)      0 = never, 1 = as above (default), 2 = for every such launch of a search, whatever
+ *                                    kernel it would have taken (tests: scores then differ by that kernel's rounding);
+ *   rpr_l0_table_bytes(ctx, model)   size of the model's table if the next search on this ctx may read it, else 0. */
+int rpr_set_l0_table(rpr_ctx* ctx, int32_t mode);
+int64_t rpr_l0_table_bytes(const rpr_ctx* ctx, const rpr_model* model);
 /* HOST ONLY (no ctx, no GPU): the statistic the automatic fork depths come from. codes: [host] [N, Lc] in any order;
  * out_frac: [host] L + 1 doubles, out_frac[t] = share of the trie nodes at depth t (distinct t-prefixes) under which
  * exactly one distinct L-token sequence remains. A query whose B beams stand on random depth-t nodes is forced with

@@ -124,6 +124,8 @@ SIGNATURES = {
     "rpr_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "rpr_set_lane_split": (C.c_int, [C.c_void_p, C.c_int32]),
     "rpr_lane_split": (C.c_int32, [C.c_void_p]),
+    "rpr_set_l0_table": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rpr_l0_table_bytes": (C.c_int64, [C.c_void_p, C.c_void_p]),
     "rpr_set_forced_tail": (C.c_int, [C.c_void_p, C.c_int32]),
     "rpr_forced_tail": (C.c_int32, [C.c_void_p]),
     "rpr_set_fork_depths": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),

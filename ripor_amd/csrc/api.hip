@@ -72,6 +72,7 @@ int refresh_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s) {
   RPR_HIP(hipMemcpyAsync(&sat, probe, 4, hipMemcpyDeviceToHost, s));
   RPR_HIP(hipStreamSynchronize(s));
   m->f32_only = sat != 0;
+  m->l0_valid = false;   // the layer-0 Q/K/V table is made from in_embeds and these planes: the next search makes it again
   // the weights changed (optimizer step, or a caller writing through rpr_param_info's pointers): the logit bound of the
   // forced-tail proof follows them, and so do the graphs that hold the spread limit derived from it by value
   float lb = m->logit_bound;
@@ -214,6 +215,7 @@ int rpr_set_precision(rpr_ctx* c, int precision) {
   RPR_REQUIRE(c, "NULL ctx");
   RPR_REQUIRE(precision == RPR_PREC_F32 || precision == RPR_PREC_F16X2 || precision == RPR_PREC_BF16, "unknown precision");
   c->precision = precision;
+  ++c->l0_epoch;   // a precision switch drops every model's layer-0 Q/K/V table: the next split-precision search makes it again
   return RPR_OK;
 }
 int rpr_get_precision(const rpr_ctx* c) { return c ? c->precision : -1; }
@@ -684,7 +686,8 @@ int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
     // the per-call debug switches of the selection / ranking kernels are part of the key (tests flip them between calls)
     auto env_int = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     const unsigned dbg = (env_int("RPR_TAIL_RANK_REPLAY", 0) ? 1u : 0u) | ((unsigned)(env_int("RPR_SELECT_RADIX", -1) + 1) << 1);
-    GraphKey key{m, tr, Q, Lq, B, L, flags | ((unsigned)c->precision << 16) | (dbg << 20), lane, pack_forks(forks, drop_last)};
+    const unsigned l0 = m->l0_ready(c) ? (unsigned)c->l0_mode : 0u;   // whether the capture reads the layer-0 Q/K/V table
+    GraphKey key{m, tr, Q, Lq, B, L, flags | ((unsigned)c->precision << 16) | (dbg << 20) | (l0 << 24), lane, pack_forks(forks, drop_last)};
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
       hipGraph_t graph = nullptr;
@@ -732,6 +735,7 @@ int rpr_search(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
   RPR_HIP(hipSetDevice(c->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   { const int pe = ensure_weight_planes(c, m, s); if (pe) return pe; }   // after an optimizer step
+  { const int te = ensure_l0_table(c, m, s); if (te) return te; }        // first search of the model, or after the above
   c->last_ws_mask = 0;
   // Large batches: two halves on the two CU-masked lanes, side by side (see Lane). Results are those of one call: every
   // query is processed on its own rows. The caller's stream waits for both lanes.
@@ -785,6 +789,13 @@ int32_t rpr_lane_split(rpr_ctx* c) {
   (void)hipSetDevice(c->device);
   return ensure_lanes(c) ? c->lane_min_rows : 0;
 }
+
+int rpr_set_l0_table(rpr_ctx* c, int32_t mode) {
+  RPR_REQUIRE(c && mode >= 0 && mode <= 2, "mode must be 0 (never), 1 (where the ping-pong GEMM would run) or 2 (always)");
+  c->l0_mode = mode;
+  return RPR_OK;
+}
+int64_t rpr_l0_table_bytes(const rpr_ctx* c, const rpr_model* m) { return c && m && m->l0_ready(c) ? (int64_t)m->l0_bytes() : 0; }
 
 int rpr_set_forced_tail(rpr_ctx* c, int32_t mode) {
   RPR_REQUIRE(c && mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (exact) or 2 (optimistic)");

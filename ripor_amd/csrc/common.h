@@ -218,6 +218,7 @@ struct GemmH2Args {
   int bf16;                                // 1: A and W are single bf16 planes (training GEMMs, RPR_PREC_BF16); fp32 output only
   int no_row_split;                        // 1: never split the rows of this launch over two kernels (packed encoder: M is a capacity far above
                                            // the live row count, which only the device knows)
+  int force_pp;                            // 1: the 256x256 ping-pong kernel whatever the shape, rows never split (the layer-0 Q/K/V table)
   int kernel_cls;                          // out (host side): profile class of the kernel chosen (RPR_K_GEMM = 256x256 ping-pong, RPR_K_GEMM_SMALL = the others)
   // bf16 launches on the 256x256 kernel only (training step, round 6): the result leaves the epilogue in the operand formats
   // of the products that consume it, instead of one conversion launch per consumer reading the fp32 result back —
@@ -256,6 +257,8 @@ __device__ __forceinline__ size_t out_off(const G& g, int oi, int m, int ldo, in
   return (size_t)m * ldo + on;
 }
 hipError_t launch_gemm_h2(GemmH2Args& a, hipStream_t s);
+// true when launch_gemm_h2 would run every row of this product on the ping-pong kernel alone (gemm_route.h: plan_is_pp_only)
+bool gemm_h2_pp_only(const GemmH2Args& a);
 // several bf16 products C_i[M_i, N_i] = A_i[M_i, K] W_i[N_i, K]^T (fp32 output, no fused extras) in one launch of the 256x256
 // ping-pong kernel, one block and one K-loop per tile (gemm_h2_pp_group_kernel): the weight gradients of one transformer
 // layer. At most MAX_TILES tiles in total (the greedy assignment then stays within 64 per XCD); otherwise hipErrorInvalidValue.
@@ -303,6 +306,14 @@ hipError_t launch_pack_rows(const int32_t* lens, int32_t* offs, int32_t* row_src
 hipError_t launch_dec_embed(const float* start, const float* in_embeds, const uint16_t* tokens, int tok_ld,
                             float* out, int R, int d, int V, int t, hipStream_t s, XOut xo = XOut{},
                             const int* rows_dev = nullptr);
+
+// Layer-0 Q/K/V table of the decoder (passes.hip: ensure_l0_table): rows (p - 1) * V + tok, then the start token's row.
+// x planes and row sums of the table's input rows (rows = L * V + 1; xo.x_h must be set)
+hipError_t launch_l0_table_embed(const float* start, const float* in_embeds, int rows, int d, hipStream_t s, XOut xo);
+// step t of R rows: q -> qb[row], k / v -> the KV-cache element map of GemmArgs (rm_*); rows_dev as launch_dec_embed
+hipError_t launch_dec_l0_qkv(const float* table, const uint16_t* tokens, int tok_ld, int R, int V, int start_row, int t, int inner,
+                             float* qb, float* kc, float* vc, int rm_B, size_t rm_stride, size_t rm_slot, size_t rm_head, int rm_dshift,
+                             const int* rows_dev, hipStream_t s);
 
 struct EncAttnArgs {
   const float* qkv;        // [Q*Lq, 3*inner]  (q | k | v)
@@ -496,6 +507,9 @@ hipError_t launch_tail_tokens(const BeamState& st, const uint16_t* codes, int Lc
 // decoder input embedding of the tail rows (sequence-major: row = seq * (L-T) + (p - T)): in_embeds[p-1][token p-1]
 hipError_t launch_tail_embed(const float* in_embeds, const uint16_t* tokens, float* out, int rows, const int* rows_dev, int T, int L,
                              int d, int V, hipStream_t s, XOut xo = XOut{});
+// q | k | v of the tail rows (n3 = 3 * inner floats each) from the layer-0 table; tokens / rows_dev as launch_tail_embed
+hipError_t launch_tail_l0_qkv(const float* table, const uint16_t* tokens, float* qkv, int rows, const int* rows_dev, int T, int L,
+                              int V, int n3, hipStream_t s);
 struct TailSelfAttnArgs {
   const float* qkv;          // [rows, 3*inner] of the tail rows (q | k | v)
   const float* kcache;       // the fork stage's cache of this layer (positions < T)

@@ -1149,6 +1149,7 @@ static GemmRouteIn route_inputs(const GemmH2Args& a) {
   r.split_n = a.split_n; r.rm_B = a.rm_B; r.ksplit = a.ksplit; r.small_live = a.small_live; r.live_lo = a.live_lo; r.live_hi = a.live_hi;
   r.part_cap = a.part_cap;
   r.part = a.part; r.mid_split = a.mid_split; r.m_dev = a.m_dev; r.bf16 = a.bf16; r.no_row_split = a.no_row_split;
+  r.force_pp = a.force_pp;
   r.out_h = a.out_h; r.row_ssq = a.row_ssq; r.ssq_out = a.ssq_out; r.resid = a.resid; r.resid_h = a.resid_h; r.relu = a.relu;
   r.out_b = a.out_b; r.out_bt = a.out_bt;
   r.ab_al8 = !(a.lda & 7) && !(a.ldw & 7);
@@ -1203,6 +1204,8 @@ static hipError_t launch_splitk_reduce(const GemmH2Args& a, const GemmStep& st, 
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, a.part, st.ksplit, n);
   return hipGetLastError();
 }
+
+bool gemm_h2_pp_only(const GemmH2Args& a) { return plan_is_pp_only(plan_gemm_h2(route_inputs(a), gemm_tuning())); }
 
 hipError_t launch_gemm_h2(GemmH2Args& a_in, hipStream_t s) {
   GemmH2Args a = a_in;

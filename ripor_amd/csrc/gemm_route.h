@@ -20,6 +20,7 @@ struct GemmRouteIn {
   int split_n = 0, rm_B = 0, ksplit = 0, small_live = 0, live_lo = 0, live_hi = 0;
   size_t part_cap = 0;
   bool part = false, mid_split = false, m_dev = false, bf16 = false, no_row_split = false;
+  bool force_pp = false;  // the caller pins this launch to the 256x256 ping-pong kernel, unsplit (GemmH2Args::force_pp)
   bool out_h = false, row_ssq = false, ssq_out = false, resid = false, resid_h = false, relu = false, out_b = false, out_bt = false;
   bool ab_al8 = true;     // lda and ldw multiples of 8
   bool ldo0_al4 = true;   // ldo[0] a multiple of 4
@@ -230,13 +231,13 @@ inline void route_bf16(const GemmRouteIn& a, const GemmTuning& t, GemmPlan& pl) 
 // Everything but the compacted triple: the steps of one product whose live window, if any, is a's.
 inline void route_one(const GemmRouteIn& a, const GemmTuning& t, GemmPlan& pl) {
   if (a.bf16) return route_bf16(a, t, pl);
-  const int force = t.force_tile;
+  const int force = a.force_pp ? 256 : t.force_tile;
   const long t256 = ceil_tiles(a.M, a.N, 256, 256);
   const int cus = a.cus > 0 ? a.cus : 256;         // a lane stream owns part of the chip: thresholds scale with it
   const double round_eff = (double)t256 / (double)(((t256 + cus - 1) / cus) * cus);
   if (force == 256 || (force == 0 && t256 >= (long)t.pp_min_tiles * cus / 256 && (round_eff >= t.pp_round_eff || a.out_h || a.row_ssq))) {
     pl.cls = RPR_K_GEMM;
-    const bool split_all = t.row_split == 2 && a.M > 256;
+    const bool split_all = t.row_split == 2 && a.M > 256 && !a.force_pp;
     if (t.row_split && (force == 0 || split_all) && !a.rm_B && a.ksplit <= 1 && a.small_live == 0 && (!a.no_row_split || split_all) &&
         (t256 > cus || split_all)) {
       const int tiles_n = (a.N + 255) / 256;
@@ -292,6 +293,23 @@ inline void route_one(const GemmRouteIn& a, const GemmTuning& t, GemmPlan& pl) {
   const bool narrow = force ? (force == 64) : (t128 < 256);
   pl.add(dma_step(a, t, narrow ? 64 : 128));
 }
+
+// Every row of the product is computed by the ping-pong kernel walking all of K in one block: the launches whose rows a
+// table made by that kernel (passes.hip: the layer-0 Q/K/V table) reproduces bit for bit.
+inline bool plan_is_pp_only(const GemmPlan& pl) {
+  if (pl.invalid || pl.n < 1) return false;
+  for (int i = 0; i < pl.n; ++i)
+    if (pl.step[i].family != GEMM_PP || pl.step[i].ksplit != 1) return false;
+  return true;
+}
+
+// Size policy of that table (internal.h: rpr_model::l0_table): L * V + 1 rows of q | k | v = 3 * inner fp32 values. A model
+// whose table would exceed the cap keeps its GEMM: the cap admits t5-base at 32 x 256 (75 MB) and at 16 x 1024 (151 MB) and
+// t5-large at 32 x 256 (101 MB); t5-3b at 32 x 256 (403 MB) is over it.
+constexpr size_t L0_TABLE_CAP = (size_t)160 << 20;
+inline size_t l0_table_rows(int L, int V) { return (size_t)L * (size_t)V + 1; }
+inline size_t l0_table_bytes(int L, int V, int inner) { return l0_table_rows(L, V) * 3 * (size_t)inner * sizeof(float); }
+inline bool l0_table_fits(int L, int V, int inner) { return l0_table_bytes(L, V, inner) <= L0_TABLE_CAP; }
 
 inline GemmPlan plan_gemm_h2(const GemmRouteIn& a, const GemmTuning& t = GemmTuning()) {
   GemmPlan pl;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_route.h"
 #include "trie.h"
 
 namespace rpr {
@@ -40,6 +41,18 @@ struct rpr_model {
   // the fp32 weights of the caller stay untouched and serve the exact-fp32 mode.
   bool f32_only = false;           // a weight does not fit the f16 planes: every search of this model runs exact fp32
   bool planes_dirty = false;       // the fp32 weights changed (rpr_adamw_step) since the planes were split
+  // Layer-0 Q/K/V table of the decoder (passes.hip: ensure_l0_table): q | k | v of every (position, token)
+  // input row and of the start token's, [L * V + 1][3 * inner] fp32, as the layer-0 projection writes them in split
+  // precision. Made on first use by a search, in place again after anything replaced the weights it is made from
+  // (l0_valid: rpr_adamw_step, refresh_weight_planes) or switched the ctx's precision (l0_epoch against rpr_ctx::l0_epoch);
+  // the allocation stays (captured graphs hold its address). l0_state -1: not for this model (over L0_TABLE_CAP, or no memory).
+  float* l0_table = nullptr;
+  bool l0_valid = false;
+  unsigned l0_epoch = 0;
+  int l0_state = 0;
+  size_t l0_rows() const { return rpr::l0_table_rows(d.L, d.V); }
+  size_t l0_bytes() const { return rpr::l0_table_bytes(d.L, d.V, inner()); }
+  bool l0_ready(const rpr_ctx* c) const;   // made, and current for this ctx state (defined below rpr_ctx)
   std::vector<void*> owned;
   // how every plane buffer was produced (replayed by refresh_weight_planes after an optimizer step changed the weights)
   struct PlaneJob { const float* w; size_t n; __half* dst; const float* ln; float pre; size_t plane_stride; };   // plane_stride 0 = n
@@ -197,6 +210,9 @@ struct rpr_ctx {
   int last_ws_mask = 0;         //   -> rpr_last_fork_stats
   size_t ws_bytes = 0;
   int enc_rows_accounted = 0;   // live encoder rows of the last enqueue (profile accounting)
+  unsigned l0_epoch = 0;        // bumped by rpr_set_precision: a model's layer-0 Q/K/V table of another epoch is made again
+  int l0_mode = 1;              // rpr_set_l0_table: 0 = the table is never made nor read, 1 = it replaces the launches the route planner
+                                //   sends to the ping-pong kernel, 2 = every layer-0 Q/K/V launch of a search (tests)
   hipStream_t cap_stream = nullptr;
   std::map<GraphKey, hipGraphExec_t> graphs;
   // profiling
@@ -211,6 +227,8 @@ struct rpr_ctx {
   rpr_kernel_stats done[RPR_K_COUNT];
 };
 
+inline bool rpr_model::l0_ready(const rpr_ctx* c) const { return c->l0_mode > 0 && l0_table && l0_valid && l0_epoch == c->l0_epoch; }
+
 namespace rpr {
 
 // re-split every GEMM weight into its f16 planes (api.hip); sets model->f32_only if a weight no longer fits
@@ -221,6 +239,8 @@ inline int ensure_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s) {
   if (!e) m->planes_dirty = false;
   return e;
 }
+// the table is there and current for the search about to be enqueued on stream s (split precision only); passes.hip
+int ensure_l0_table(rpr_ctx* c, rpr_model* m, hipStream_t s);
 void free_train_ws(rpr_ctx* c);   // train_api.hip
 void train_forget_model(rpr_ctx* c, const rpr_model* m);   // train_api.hip: drop the per-model weight cache table
 
@@ -295,6 +315,7 @@ struct LinW {                                                                // 
   bool no_scratch = false;                                                   //   the ctx's split-K scratch is not lent to this product: the mid-size
                                                                              //   split-K route (gemm_route.h: part, mid_split) stays closed to it
   bool row_split_ok = false;                                                 //   the ctx's cur_no_row_split does not reach this product
+  bool force_pp = false;                                                     //   the 256x256 ping-pong kernel whatever the shape (GemmH2Args::force_pp)
 };
 struct LinOut {                                                              // destination
   float* f[3]; int ldo[3]; int split_n;                                      //   fp32 (up to 3 column blocks)

@@ -16,28 +16,40 @@ LinOut out_f32(float* p, int ld, int N, const float* resid, int relu) {
   return o;
 }
 
+namespace {
+
+// The split-precision launch of one linear layer: what linear() hands to launch_gemm_h2 (and the layer-0 table's gate to
+// the route planner).
+GemmH2Args h2_args(const rpr_ctx* c, const LinIn& A, const LinW& W, int M, const LinOut& O, const int* m_dev) {
+  const int Nh = W.Nh ? W.Nh : W.N;
+  GemmH2Args g{};
+  g.A = A.h; g.a_ps = A.ps; g.lda = A.ld; g.W = W.h; g.w_ps = W.ps ? W.ps : (size_t)W.N * W.K; g.ldw = W.K;
+  g.resid = O.resid; g.ldr = O.ldo[0];
+  for (int i = 0; i < 3; ++i) { g.out[i] = O.f[i]; g.ldo[i] = O.ldo[i]; }
+  g.split_n = O.split_n; g.out_h = O.h; g.o_ps = O.ps; g.ldoh = O.ldh;
+  g.M = M; g.N = Nh; g.K = W.K; g.relu = O.relu;
+  g.rm_B = O.rm_B; g.rm_stride = O.rm_stride; g.rm_slot = O.rm_slot; g.rm_head = O.rm_head; g.rm_dshift = O.rm_dshift;
+  g.m_dev = m_dev; g.acc_scale = 1.0f / (W_PLANE_SCALE * A.scale); g.plane_scale = O.plane_scale;
+  g.row_ssq = A.ssq; g.inv_d_fix = A.inv_d_fix; g.eps = A.eps;
+  g.resid_h = O.resid_h; g.r_ps = O.ps; g.ldrh = O.ldh; g.ssq_out = O.ssq_out;
+  g.sat = c->status;
+  g.cus = c->cur_cus;
+  g.small_live = m_dev ? c->cur_small_live : 0;
+  g.no_row_split = W.row_split_ok ? 0 : c->cur_no_row_split;
+  g.force_pp = W.force_pp ? 1 : 0;
+  if (!W.no_scratch) { g.part = P<float>(c->ws.part); g.part_cap = c->ws.part.cap / sizeof(float); g.mid_split = 1; }
+  return g;
+}
+
+}  // namespace
+
 void linear(Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, const int* m_dev, int m_acc) {
   const double Ma = m_acc >= 0 ? m_acc : M;
   const double fl = 2.0 * Ma * (double)W.N * W.K;
   const double by = 4.0 * (Ma * W.K + (double)W.N * W.K + Ma * W.N * ((O.resid || O.resid_h) ? 2 : 1));
   hipStream_t s = L.s;
   if (L.c->precision == RPR_PREC_F16X2) {
-    const int Nh = W.Nh ? W.Nh : W.N;
-    GemmH2Args g{};
-    g.A = A.h; g.a_ps = A.ps; g.lda = A.ld; g.W = W.h; g.w_ps = W.ps ? W.ps : (size_t)W.N * W.K; g.ldw = W.K;
-    g.resid = O.resid; g.ldr = O.ldo[0];
-    for (int i = 0; i < 3; ++i) { g.out[i] = O.f[i]; g.ldo[i] = O.ldo[i]; }
-    g.split_n = O.split_n; g.out_h = O.h; g.o_ps = O.ps; g.ldoh = O.ldh;
-    g.M = M; g.N = Nh; g.K = W.K; g.relu = O.relu;
-    g.rm_B = O.rm_B; g.rm_stride = O.rm_stride; g.rm_slot = O.rm_slot; g.rm_head = O.rm_head; g.rm_dshift = O.rm_dshift;
-    g.m_dev = m_dev; g.acc_scale = 1.0f / (W_PLANE_SCALE * A.scale); g.plane_scale = O.plane_scale;
-    g.row_ssq = A.ssq; g.inv_d_fix = A.inv_d_fix; g.eps = A.eps;
-    g.resid_h = O.resid_h; g.r_ps = O.ps; g.ldrh = O.ldh; g.ssq_out = O.ssq_out;
-    g.sat = L.c->status;
-    g.cus = L.c->cur_cus;
-    g.small_live = m_dev ? L.c->cur_small_live : 0;
-    g.no_row_split = W.row_split_ok ? 0 : L.c->cur_no_row_split;
-    if (!W.no_scratch) { g.part = P<float>(L.c->ws.part); g.part_cap = L.c->ws.part.cap / sizeof(float); g.mid_split = 1; }
+    GemmH2Args g = h2_args(L.c, A, W, M, O, m_dev);
     L.run(RPR_K_GEMM, fl, by, [&] { return launch_gemm_h2(g, s); }, &g.kernel_cls);
   } else {
     GemmArgs g{};
@@ -179,6 +191,14 @@ struct Pass {
   // x += projection: destination of the residual projection behind norm k
   LinOut residual(int layer, int k) const { return h2 ? xs.out(site(layer, k) + 1) : out_f32(x, dm, dm, x); }
   void project(const LinIn& A, const LinW& W, const LinOut& O) { linear(Ln, A, W, M, O, m_dev, m_acc); }
+  // The model's layer-0 Q/K/V table stands in for this pass's layer-0 self-attention projection into O: split precision, the
+  // table current, and the launch one the route planner sends whole to the ping-pong kernel — the kernel the table was made
+  // by, whose K order does not depend on where a row sits, so the rows are the same bits (l0_mode 2: whatever the route).
+  bool l0_replaces(const rpr_model* m, const LinOut& O) const {
+    if (!h2 || !m->l0_ready(Ln.c)) return false;
+    if (Ln.c->l0_mode >= 2) return true;
+    return gemm_h2_pp_only(h2_args(Ln.c, xs.in(0), {m->dec_qkv[0], m->h_dec_qkv[0], 3 * inner, dm}, M, O, m_dev));
+  }
   void attn_out(int layer, int k, const float* W, const __half* Wh) {   // o / xo: the attention output back into the stream
     project(LinIn{attn, attn_h, ps_i, inner}, {W, Wh, dm, inner}, residual(layer, k));
   }
@@ -191,6 +211,45 @@ struct Pass {
 };
 
 }  // namespace
+
+// The layer-0 Q/K/V table of m (internal.h), made by the path it stands in for: the embedding copy of every table row into
+// x planes with the site-0 row sums, then the layer-0 projection of those rows as ONE launch pinned to the ping-pong kernel.
+// Saturation raises the ctx's sticky word like the launches it replaces. Scratch (x planes, row sums: 25 MB at the
+// headline) lives for the call only. Not profiled: it is not part of a search.
+int ensure_l0_table(rpr_ctx* c, rpr_model* m, hipStream_t s) {
+  const int prec = m->f32_only ? RPR_PREC_F32 : (c->precision == RPR_PREC_BF16 ? RPR_PREC_F16X2 : c->precision);   // PrecGuard's
+  if (c->l0_mode <= 0 || prec != RPR_PREC_F16X2 || m->l0_state < 0 || m->l0_ready(c)) return RPR_OK;
+  const auto& d = m->d;
+  const size_t rows = m->l0_rows(), dm = d.d_model;
+  if (!l0_table_fits(d.L, d.V, m->inner()) || rows >= ((size_t)1 << 30)) { m->l0_state = -1; return RPR_OK; }
+  DevTmp x_h, ssq;
+  if (!m->l0_table) {
+    void* p = nullptr;
+    if (hipMalloc(&p, m->l0_bytes()) != hipSuccess) { (void)hipGetLastError(); m->l0_state = -1; return RPR_OK; }
+    m->owned.push_back(p);
+    m->l0_table = reinterpret_cast<float*>(p);
+  }
+  if (x_h.alloc(rows * dm * 2 * sizeof(__half)) != hipSuccess || ssq.alloc(rows * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    return RPR_OK;   // no scratch right now: this search keeps its GEMM, the next one tries again
+  }
+  struct Restore {
+    rpr_ctx* c; int prec; bool prof;
+    ~Restore() { c->precision = prec; c->profiling = prof; }
+  } restore{c, c->precision, c->profiling};
+  c->precision = RPR_PREC_F16X2; c->profiling = false;
+  const DevBuf none{}, xb{x_h.p, rows * dm * 2 * sizeof(__half)}, sb{ssq.p, rows * 8};
+  Launcher Ln{c, s};
+  Pass p(Ln, m, {none, none, none, none, xb, none, none, sb}, 3, 1, (int)rows, nullptr, (int)rows);
+  Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_l0_table_embed(d.start_embed, d.in_embeds, (int)rows, (int)dm, s, p.embed_out()); });
+  LinW w{m->dec_qkv[0], m->h_dec_qkv[0], 3 * m->inner(), (int)dm};
+  w.no_scratch = true; w.row_split_ok = true; w.force_pp = true;
+  p.project(p.normed(0, 0, m->dec_ln0[0]), w, out_f32(m->l0_table, 3 * m->inner(), 3 * m->inner()));
+  if (Ln.err) return Ln.err;
+  RPR_HIP(hipStreamSynchronize(s));   // the scratch goes with this scope
+  m->l0_valid = true; m->l0_epoch = c->l0_epoch; m->l0_state = 1;
+  return RPR_OK;
+}
 
 // Encoder forward into ws.enc_out (reference generation.py:132-137 -> model.encoder(...)).
 // packed = false: rows are [Q, Lq] padded (taps / rpr_encode return that layout).
@@ -305,7 +364,13 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
         o.f[0] = qb; o.f[1] = kc + (size_t)t * kv_pos; o.f[2] = vc + (size_t)t * kv_pos;
         o.ldo[0] = o.ldo[1] = o.ldo[2] = inner; o.split_n = inner;
         o.rm_B = Bt; o.rm_stride = kv_q; o.rm_slot = kv_slot; o.rm_head = kv_h; o.rm_dshift = sv.dkv == 128 ? 7 : 6;
-        p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, o);
+        if (i == 0 && p.l0_replaces(m, o))   // the row's q | k | v from the model's table, landing where the epilogue puts them
+          Ln.run(RPR_K_OTHER, 0, 2.0 * Ma * 3 * inner * 4, [&] {
+            return launch_dec_l0_qkv(m->l0_table, cur.tokens, L, Rt, V, d.L * V, t, inner, o.f[0], o.f[1], o.f[2], o.rm_B, o.rm_stride,
+                                     o.rm_slot, o.rm_head, o.rm_dshift, sv.nrows_dev, s);
+          });
+        else
+          p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, o);
       }
       {
         DecSelfAttnArgs a{qb, kc, vc, kv_q, kv_h, kv_pos, kv_slot, cur.anc, L, d.dec_rel_bias, m->dec_bucket, p.attn, Q, Bt, H, t,
@@ -438,7 +503,13 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const SearchDims
   });
   const size_t kv_pos = (size_t)B * sv.dkv;
   for (int i = 0; i < nd; ++i) {
-    p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, out_f32(qkv, 3 * inner, 3 * inner));
+    const LinOut o_qkv = out_f32(qkv, 3 * inner, 3 * inner);
+    if (i == 0 && p.l0_replaces(m, o_qkv))   // layer 0: the rows of the model's (position, token) table instead of the projection
+      Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * 3 * inner * 4, [&] {
+        return launch_tail_l0_qkv(m->l0_table, P<uint16_t>(tb.tokens), qkv, R, nrows_dev, T, L, V, 3 * inner, s);
+      });
+    else
+      p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, o_qkv);
     {
       const size_t ls = sv.kv_layer(B, inner);
       TailSelfAttnArgs a{qkv, sv.kcache + i * ls, sv.vcache + i * ls, sv.kv_q(B, inner), sv.kv_h(B), kv_pos, (size_t)sv.dkv,

@@ -146,6 +146,59 @@ hipError_t launch_dec_embed(const float* start, const float* in_embeds, const ui
   return hipGetLastError();
 }
 
+// ---- layer-0 Q/K/V table of the decoder (passes.hip: ensure_l0_table) ------------------------------------------------
+// The decoder's layer-0 input row depends on (position, token) alone, and so does its Q/K/V projection: row (p - 1) * V + tok
+// of the table holds q | k | v of in_embeds[p - 1][tok], row L * V those of the start token.
+// Input rows of the table's one GEMM, in table order: in_embeds is [L][V][d], the start row follows it.
+__global__ __launch_bounds__(256) void l0_table_embed_kernel(const float* __restrict__ start, const float* __restrict__ in_embeds,
+                                                              int rows, int d, XOut xo) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* src = row == rows - 1 ? start : in_embeds + (size_t)row * d;
+  copy_row_x(reinterpret_cast<const float4*>(src), nullptr, row, d, lane, xo);
+}
+
+hipError_t launch_l0_table_embed(const float* start, const float* in_embeds, int rows, int d, hipStream_t s, XOut xo) {
+  if (rows <= 0 || !xo.x_h) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(l0_table_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, start, in_embeds, rows, d, xo);
+  return hipGetLastError();
+}
+
+// A sequential step's layer-0 Q/K/V from the table, landing where the projection's epilogue puts them: q in row `row` of
+// qb, k and v at out_off's KV-cache element of (row, column) (common.h: GemmArgs::rm_B). One wave per row, 16-byte pieces
+// (a piece stays inside one head: the head dim is a multiple of 4).
+__global__ __launch_bounds__(256) void dec_l0_qkv_kernel(const float* __restrict__ table, const uint16_t* __restrict__ tokens,
+                                                          int tok_ld, int R, int V, int start_row, int t, int inner,
+                                                          float* __restrict__ qb, float* __restrict__ kc, float* __restrict__ vc,
+                                                          int rm_B, size_t rm_stride, size_t rm_slot, size_t rm_head, int dshift,
+                                                          const int* __restrict__ rows_dev) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= R || (rows_dev && row >= *rows_dev)) return;
+  const size_t trow = t > 0 ? (size_t)(t - 1) * V + tokens[(size_t)row * tok_ld + (t - 1)] : (size_t)start_row;
+  const float4* src = reinterpret_cast<const float4*>(table + trow * 3 * (size_t)inner);
+  const int n4 = inner >> 2, qi = row / rm_B;
+  const size_t base = (size_t)qi * rm_stride + (size_t)(row - qi * rm_B) * rm_slot;
+  for (int i = lane; i < n4; i += 64) {
+    const int on = 4 * i;
+    const size_t off = base + (size_t)(on >> dshift) * rm_head + (on & ((1 << dshift) - 1));
+    const float4 q = src[i], k = src[n4 + i], v = src[2 * n4 + i];
+    *reinterpret_cast<float4*>(qb + (size_t)row * inner + on) = q;
+    *reinterpret_cast<float4*>(kc + off) = k;
+    *reinterpret_cast<float4*>(vc + off) = v;
+  }
+}
+
+hipError_t launch_dec_l0_qkv(const float* table, const uint16_t* tokens, int tok_ld, int R, int V, int start_row, int t, int inner,
+                             float* qb, float* kc, float* vc, int rm_B, size_t rm_stride, size_t rm_slot, size_t rm_head, int rm_dshift,
+                             const int* rows_dev, hipStream_t s) {
+  if (R <= 0) return hipSuccess;
+  const int dshift = rm_dshift ? rm_dshift : 6;
+  if (rm_B < 1 || (inner & 3) || ((rm_stride | rm_slot | rm_head) & 3)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dec_l0_qkv_kernel, dim3((R + 3) / 4), dim3(256), 0, s, table, tokens, tok_ld, R, V, start_row, t, inner, qb, kc,
+                     vc, rm_B, rm_stride, rm_slot, rm_head, dshift, rows_dev);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------ encoder self-attention
 // One block per (query, head). K and V of the head are staged once in LDS ([Lq][65] padded), every
 // wave then handles query rows i = wave, wave+4, ...: lane j scores keys j, j+64, ...; the q row is

@@ -200,6 +200,29 @@ hipError_t launch_tail_embed(const float* in_embeds, const uint16_t* tokens, flo
   return hipGetLastError();
 }
 
+// Layer-0 Q/K/V of the tail rows from the model's table (t5_kernels.hip: l0_table_embed_kernel) instead of the projection:
+// row r copies table row (p - 1) * V + token(p - 1) into qkv[r], 16 bytes per lane and piece; rows past the live count exit
+// like tail_embed_kernel's. One wave per row.
+__global__ __launch_bounds__(256) void tail_l0_qkv_kernel(const float* __restrict__ table, const uint16_t* __restrict__ tokens,
+                                                           float* __restrict__ qkv, int rows, const int* __restrict__ rows_dev,
+                                                           int T, int L, int V, int n4) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows || row >= *rows_dev) return;
+  const int Lt = L - T, seq = row / Lt, p = T + (row - seq * Lt);
+  const int tok = tokens[(size_t)seq * L + (p - 1)];
+  const float4* src = reinterpret_cast<const float4*>(table) + ((size_t)(p - 1) * V + tok) * n4;
+  float4* dst = reinterpret_cast<float4*>(qkv) + (size_t)row * n4;
+#pragma unroll 4
+  for (int i = lane; i < n4; i += 64) dst[i] = src[i];
+}
+
+hipError_t launch_tail_l0_qkv(const float* table, const uint16_t* tokens, float* qkv, int rows, const int* rows_dev, int T, int L,
+                              int V, int n3, hipStream_t s) {
+  if (rows <= 0 || T < 1 || (n3 & 3)) return rows <= 0 ? hipSuccess : hipErrorInvalidValue;
+  hipLaunchKernelGGL(tail_l0_qkv_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, table, tokens, qkv, rows, rows_dev, T, L, V, n3 >> 2);
+  return hipGetLastError();
+}
+
 // Causal self-attention of the tail positions of one beam: one block per (sequence, head). K and V of all L positions
 // are staged once in LDS — positions < T from the fork stage's KV cache through the beam's ancestry (written by the
 // sequential steps, never moved), positions >= T from this pass's own q|k|v rows — then every wave handles query

@@ -1062,6 +1062,7 @@ int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp
   // that needs them (ensure_weight_planes) — a training loop never does, and the refresh costs a pass over every weight
   // plus a stream synchronisation per step
   m->planes_dirty = true;
+  m->l0_valid = false;   // and so is the layer-0 Q/K/V table made from them (in_embeds, dec_ln0[0], dec_qkv[0])
   return RPR_OK;
 }
 

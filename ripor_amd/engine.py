@@ -72,6 +72,15 @@ class Context:
         """The threshold in force; 0 when splitting is off or masked streams are unavailable."""
         return int(self.lib.rpr_lane_split(self.handle))
 
+    def set_l0_table(self, mode: int):
+        """The decoder's layer-0 Q/K/V table (``rpr_set_l0_table``): 0 = never, 1 = where the search would launch the
+        projection on the 256 x 256 tile kernel (library default, same bits), 2 = always (tests)."""
+        check(self.lib.rpr_set_l0_table(self.handle, int(mode)), "rpr_set_l0_table")
+
+    def l0_table_bytes(self, model: "DeviceModel") -> int:
+        """Size of the model's layer-0 Q/K/V table if the next search may read it, else 0."""
+        return int(self.lib.rpr_l0_table_bytes(self.handle, model.handle))
+
     def set_forced_tail(self, mode):
         """Forced-tail evaluation (``rpr_set_forced_tail``): queries whose beams can no longer be pruned leave the
         step-by-step loop at a fork and get their remaining positions scored in one teacher-forced pass.
