@@ -136,7 +136,8 @@ enum { RPR_K_GEMM = 0, RPR_K_DEC_SELF_ATTN = 1, RPR_K_DEC_CROSS_ATTN = 2, RPR_K_
 int rpr_init(int device, rpr_ctx** out_ctx);
 void rpr_free_ctx(rpr_ctx* ctx);
 const char* rpr_last_error(void);
-/* Library/ABI version; bumped when a signature changes or a symbol is added (4: the seq2seq step). */
+/* Library/ABI version; bumped when a signature changes or a symbol is added (4: the seq2seq step). Version 4 has since gained
+ * rpr_search_margins without a bump: a binding that needs it probes for the symbol (dlsym) rather than for a version. */
 int rpr_abi_version(void);
 /* Select the GEMM arithmetic (RPR_PREC_*); default RPR_PREC_F16X2, or RPR_PRECISION=f32|f16x2 in the
  * environment at rpr_init. Takes effect on the next rpr_search/rpr_encode/rpr_op_linear. */
@@ -218,6 +219,27 @@ int rpr_search(rpr_ctx* ctx, rpr_model* model, rpr_trie* trie, const int32_t* in
                const int32_t* attention_mask, int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags,
                int32_t* out_tokens, float* out_scores, int64_t* out_row_lo, int64_t* out_row_hi,
                const rpr_debug_taps* taps, void* stream);
+
+/* The same search plus its per-query PRUNING MARGIN. Every argument, every result and the work enqueued for them are those
+ * of rpr_search (same bits); out_margin: [dev] float64 [Q] is written in addition (every entry, by every call).
+ * Definition. At decode step t let s_t[0] >= s_t[1] >= ... be the step's candidates of one query in float64, the keys of
+ * the selection: ((double)logit + (token is a trie child of the beam ? 0 : -1e9)) + beam score, the logit being the fp32
+ * log-softmax value under RPR_FLAG_LOG_SOFTMAX; the padding of a logits row beyond the model's V is no candidate. The step
+ * keeps ranks 0 .. B-1. gap_t = s_t[B-1] - s_t[B] if s_t[B] > -1e8 (a LIVE candidate was dropped: masked tokens and dead
+ * beams carry -1e9), else +inf; an exact tie across the boundary gives 0. out_margin[q] = min over the steps of gap_t:
+ * +inf = nothing live was ever dropped (the result set is the whole live candidate set), small = the choice of WHICH
+ * sequences survive depended on a difference of that size at some step. The split-precision GEMMs move a cumulative score
+ * by up to ~1e-4, the reference's own float32 arithmetic likewise: a query whose margin is below ~1e-3 (the test-suite's
+ * PRUNE_TOL) may legitimately return a different SET of smtids than the reference; above it the set is decided.
+ * Steps behind a forced-tail fork contribute nothing for the queries that left at it (all B beams live and single-sequence:
+ * exactly B live candidates per later step, rank B is masked), so nothing is launched in a tail pass. The margin is
+ * computed from the device's own scores: it differs from the reference's by the score error of the precision in force.
+ * In the optimistic forced-tail mode the margins of a call that raised RPR_STATUS_TAIL_LEFTOVER are unspecified, like its
+ * other outputs. Cost: one more kernel per selection step (one block per live query over its B * V candidates). */
+int rpr_search_margins(rpr_ctx* ctx, rpr_model* model, rpr_trie* trie, const int32_t* input_ids,
+                       const int32_t* attention_mask, int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags,
+                       int32_t* out_tokens, float* out_scores, int64_t* out_row_lo, int64_t* out_row_hi,
+                       double* out_margin, const rpr_debug_taps* taps, void* stream);
 
 /* Lane split of large batches. A call of rpr_search with at least `min_rows` decoder rows (queries x beams; default
  * 10240; 0 = never; env RPR_LANE_MIN_ROWS) runs as two halves on two internal HIP streams, each confined to half of the CUs

@@ -659,7 +659,7 @@ int pack_forks(const std::vector<int>& forks, bool drop_last) {
 // one search on stream s; lane >= 0: in that lane's workspace (swapped into c->ws for the duration of the call)
 int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask, int32_t Q,
                int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores, int64_t* out_row_lo,
-               int64_t* out_row_hi, const rpr_debug_taps* taps, hipStream_t s, int lane) {
+               int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, hipStream_t s, int lane) {
   struct WsGuard {
     rpr_ctx* c; int lane;
     WsGuard(rpr_ctx* c_, int l) : c(c_), lane(l) { if (lane >= 0) { std::swap(c->ws, c->lanes[lane].ws); c->cur_cus = c->lane_cus; c->cur_lane = lane; } }
@@ -687,7 +687,9 @@ int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
     auto env_int = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     const unsigned dbg = (env_int("RPR_TAIL_RANK_REPLAY", 0) ? 1u : 0u) | ((unsigned)(env_int("RPR_SELECT_RADIX", -1) + 1) << 1);
     const unsigned l0 = m->l0_ready(c) ? (unsigned)c->l0_mode : 0u;   // whether the capture reads the layer-0 Q/K/V table
-    GraphKey key{m, tr, Q, Lq, B, L, flags | ((unsigned)c->precision << 16) | (dbg << 20) | (l0 << 24), lane, pack_forks(forks, drop_last)};
+    const unsigned mg = c->cur_margins ? 1u : 0u;                     // whether every selection is followed by the margin kernel
+    GraphKey key{m, tr, Q, Lq, B, L, flags | ((unsigned)c->precision << 16) | (dbg << 20) | (l0 << 24) | (mg << 28), lane,
+                 pack_forks(forks, drop_last)};
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
       hipGraph_t graph = nullptr;
@@ -709,17 +711,18 @@ int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
   RPR_HIP(hipMemcpyAsync(out_scores, w.o_scores.p, R * 4, hipMemcpyDeviceToDevice, s));
   if (out_row_lo) RPR_HIP(hipMemcpyAsync(out_row_lo, w.o_lo.p, R * 8, hipMemcpyDeviceToDevice, s));
   if (out_row_hi) RPR_HIP(hipMemcpyAsync(out_row_hi, w.o_hi.p, R * 8, hipMemcpyDeviceToDevice, s));
+  if (out_margin) RPR_HIP(hipMemcpyAsync(out_margin, w.o_margin.p, (size_t)Q * 8, hipMemcpyDeviceToDevice, s));
   return RPR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rpr_search(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
-               int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
-               int64_t* out_row_lo, int64_t* out_row_hi, const rpr_debug_taps* taps, void* stream) {
+// rpr_search (out_margin == nullptr) and rpr_search_margins: argument checks, weight planes, the lane split
+int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
+                 int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
+                 int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, void* stream) {
   RPR_REQUIRE(c && m && tr && input_ids && attention_mask && out_tokens && out_scores, "NULL argument");
+  // margin mode for everything this call sizes and enqueues (alloc_workspace, enqueue_search, the graph key), both lanes included
+  struct MarginMode { rpr_ctx* c; MarginMode(rpr_ctx* c_, bool on) : c(c_) { c->cur_margins = on ? 1 : 0; } ~MarginMode() { c->cur_margins = 0; } }
+      margin_mode(c, out_margin != nullptr);
   RPR_REQUIRE(m->ctx == c && tr->ctx == c, "model/trie belong to another ctx");
   RPR_REQUIRE(Q >= 1 && B >= 1 && B <= 65535, "Q or B out of range");
   RPR_REQUIRE(Lq >= 1 && Lq <= MAX_LQ, "Lq out of range (1..256)");
@@ -764,7 +767,7 @@ int rpr_search(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
       const size_t r0 = (size_t)q0 * B;
       int e = search_one(c, m, tr, input_ids + (size_t)q0 * Lq, attention_mask + (size_t)q0 * Lq, Qh[i], Lq, B, L, flags,
                          out_tokens + r0 * L, out_scores + r0, out_row_lo ? out_row_lo + r0 : nullptr,
-                         out_row_hi ? out_row_hi + r0 : nullptr, nullptr, ln.stream, i);
+                         out_row_hi ? out_row_hi + r0 : nullptr, out_margin ? out_margin + q0 : nullptr, nullptr, ln.stream, i);
       if (e) {   // the other half may already be writing the caller's buffers: let it finish before reporting the error
         for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(c->lanes[k].stream);
         return e;
@@ -775,8 +778,27 @@ int rpr_search(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
     for (int i = 0; i < 2; ++i) RPR_HIP(hipStreamWaitEvent(s, c->lanes[i].done, 0));
     return RPR_OK;
   }
-  return search_one(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi, taps,
-                    s, -1);
+  return search_one(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi, out_margin,
+                    taps, s, -1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rpr_search(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
+               int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
+               int64_t* out_row_lo, int64_t* out_row_hi, const rpr_debug_taps* taps, void* stream) {
+  return search_entry(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi,
+                      nullptr, taps, stream);
+}
+
+int rpr_search_margins(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
+                       int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
+                       int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, void* stream) {
+  RPR_REQUIRE(out_margin != nullptr, "out_margin is NULL");
+  return search_entry(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi,
+                      out_margin, taps, stream);
 }
 
 int rpr_set_lane_split(rpr_ctx* c, int32_t min_rows) {

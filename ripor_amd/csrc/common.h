@@ -439,6 +439,24 @@ hipError_t launch_select_radix_reset(const RadixWs& w, int Q, hipStream_t s);
 hipError_t launch_select_radix(const SelectArgs& a, hipStream_t s);
 bool select_fits(int B, int V);   // the beam's candidate bitmaps and state fit the 160 KB of LDS
 
+// Pruning margin of one selection step (prune_margin.hip; rpr_search_margins): launched behind launch_select on the same
+// logits, the pre-step beam scores, the child bitmap the selection exported (SelectArgs::tap_valid) and the new slots' scores
+struct MarginArgs {
+  const float* logits;               // as SelectArgs::logits ([Q, V] when shared0)
+  const double* cur_score;           // [Q, B] beam scores before the step
+  const double* nxt_score;           // [Q, B] scores of the new slots
+  const unsigned long long* valid;   // [Q, B * V / 64] child bitmap of the step (bit = beam * V + token); unused when shared0
+  const uint16_t* codes; int Lc, t;  // shared0: the sorted code matrix and the step, for the children of the root range
+  const int32_t* cur_lo; const int32_t* cur_hi;   //   [Q, B] row ranges of the beams before the step
+  int Q, B, V, Vreal, log_softmax, shared0;
+  const int* nq_dev;                 // nullable: live queries of a compacted stage
+  const int32_t* qmap;               // nullable: stage query -> query of the call
+  double* out;                       // [queries of the call] running minimum of the step gaps (+inf before step 0)
+};
+constexpr int MARGIN_MAX_V = 65536;  // widest token axis (rpr_load_model's limit)
+hipError_t launch_margin_init(double* out, int Q, hipStream_t s);
+hipError_t launch_prune_margin(const MarginArgs& a, hipStream_t s);
+
 struct FinalizeArgs {
   BeamState st;
   int Q, B, L;

@@ -154,6 +154,9 @@ struct Workspace {
   DevBuf score[2], lo[2], hi[2], tokens[2], anc[2];
   // staged outputs
   DevBuf o_tokens, o_scores, o_lo, o_hi;
+  // rpr_search_margins only: the child bitmap of the current step [Q, B * Vp / 64] (the selection's tap_valid export) and
+  // the per-query pruning margins [Q] float64 (prune_margin.hip)
+  DevBuf mg_valid, o_margin;
   // f16 hi/lo planes of the GEMM inputs (split-precision mode): attention outputs, FF intermediates, the final
   // encoder states, and the UN-normalised residual streams (fused RMSNorm) with their row sums of squares
   DevBuf eattn_h, eff_h, enc_out_h, attn_h, ff_h, ex_h, x_h, ssq_e, ssq_d;
@@ -203,6 +206,8 @@ struct rpr_ctx {
   int cur_lane = -1;            // lane of the current enqueue (-1 = the ctx stream)
   int cur_no_row_split = 0;     // 1 while the packed encoder (and the cross-K/V product on its rows) is enqueued: GemmH2Args.no_row_split
   int cur_small_live = 0;       // > 0 while a leftover stage is enqueued: its GEMMs are paired (GemmH2Args.small_live)
+  int cur_margins = 0;          // 1 while rpr_search_margins sizes and enqueues its search: every selection step is followed by
+                                //   the pruning-margin kernel (part of the graph key)
   int forced_tail = 1;          // 0 = every query runs all L steps sequentially, 1 = exact forced tail, 2 = optimistic (see choose_forks)
   int fork_override[MAX_FORKS] = {0, 0};   // explicit fork depths (rpr_set_fork_depths / RPR_FORK_DEPTHS); 0 = from the trie statistics
   int n_fork_override = -1;     // -1 = automatic

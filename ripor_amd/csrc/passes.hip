@@ -83,6 +83,7 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
     E(w.tokens[i], R * (size_t)L * 2); E(w.anc[i], R * (size_t)L * 2);
   }
   E(w.o_tokens, R * (size_t)L * 4); E(w.o_scores, R * 4); E(w.o_lo, R * 8); E(w.o_hi, R * 8);
+  if (c->cur_margins) { E(w.mg_valid, R * (size_t)m->Vp() / 8); E(w.o_margin, (size_t)Q * 8); }
   const size_t hb = sizeof(__half) * 2;  // two planes
   E(w.eattn_h, T * inner * hb); E(w.eff_h, T * dff * hb); E(w.enc_out_h, T * dm * hb);
   E(w.attn_h, R * inner * hb); E(w.ff_h, R * dff * hb);
@@ -423,7 +424,15 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
       sa.tap_parent = taps->step_parent ? taps->step_parent + (size_t)t * R : nullptr;
       sa.tap_valid = taps->step_valid ? reinterpret_cast<unsigned long long*>(taps->step_valid) + (size_t)t * ((size_t)R * V / 64) : nullptr;
     }
+    // the bitmap of this step, for the margin kernel (the shared step 0 needs none: every beam stands on the root)
+    if (c->cur_margins && !sa.tap_valid && !sa.shared0) sa.tap_valid = P<unsigned long long>(w.mg_valid);
     Ln.run(RPR_K_SELECT, 0, (double)Ma * V * 4 + (double)Ma * 40, [&] { return launch_select(sa, s); });
+    if (c->cur_margins) {
+      // pruning margin of the step (rpr_search_margins): one more pass over the step's candidates, behind the selection
+      MarginArgs ma{lg, cur.score, nxt.score, sa.tap_valid, tr->codes, tr->L, t, cur.lo, cur.hi, Q, B, Vp, V, sa.log_softmax,
+                    sa.shared0, sv.nq_dev, sv.io.qmap, P<double>(w.o_margin)};
+      Ln.run(RPR_K_SELECT, 0, (double)Ma * V * 4, [&] { return launch_prune_margin(ma, s); });
+    }
   }
   Ln.account_live(nullptr, 0);   // the live counter of this stage scales THIS stage's records only (fork, tail, finalize follow)
 }
@@ -599,6 +608,7 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
   sv.kcache = P<float>(w.kcache); sv.vcache = P<float>(w.vcache); sv.depth = forks.empty() ? L : forks[0]; sv.dkv = d.d_kv;
   for (int i = 0; i < 2; ++i) sv.st[i] = beam_state(w.score, w.lo, w.hi, w.tokens, w.anc, i, L);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_init_beams(sv.st[0], Q, B, tr->N, s); });
+  if (c->cur_margins) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_margin_init(P<double>(w.o_margin), Q, s); });
   if (w.sel_rs.p && select_radix_wanted(B, m->Vp()) && w.sel_rs.cap >= select_radix_ws_bytes(Q, B, m->Vp())) {
     RadixWs rs;   // the radix selection's histograms and counters start at zero (every step leaves them so)
     select_radix_carve(rs, w.sel_rs.p, nullptr, Q, B, m->Vp());

@@ -498,13 +498,45 @@ class SearchResult:
     row_lo: torch.Tensor      # int64 [Q, B]
     row_hi: torch.Tensor      # int64 [Q, B]
     taps: Optional[dict] = None
+    # search(..., margins=True): float64 [Q] pruning margin of every query (include/ripor_hip.h: rpr_search_margins)
+    margins: Optional[torch.Tensor] = None
+    # search_guarded(..., margin_guard=eps): bool [Q] which queries were searched again in exact fp32 (their rows above are
+    # those of the fp32 run), and float64 [rerun.sum()] the fp32 margins of those queries in ascending query order — one
+    # still below eps is a near-tie of the reference's own arithmetic, nothing more can be done about it
+    rerun: Optional[torch.Tensor] = None
+    margins_f32: Optional[torch.Tensor] = None
+
+
+def splice_rows(full, mask, sub):
+    """Pure host logic of the near-tie guard: ``full`` is a sequence of arrays with one leading row per query, ``mask`` a
+    bool vector over the queries and ``sub`` the same arrays for the masked queries only (ascending query order). Returns the
+    arrays with exactly the masked rows replaced — the inputs themselves when nothing is masked, ``sub`` itself when
+    everything is; numpy arrays or torch tensors."""
+    full, sub = tuple(full), tuple(sub)
+    n, q = int(mask.sum()), int(mask.shape[0])
+    assert len(full) == len(sub) and all(int(f.shape[0]) == q for f in full) and all(int(x.shape[0]) == n for x in sub)
+    if n == 0:
+        return full
+    if n == q:
+        return sub
+    out = []
+    for f, x in zip(full, sub):
+        if isinstance(f, torch.Tensor):
+            o = f.clone()
+            o[torch.as_tensor(np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask), device=f.device)] = x.to(f.device)
+        else:
+            o = np.array(f, copy=True)
+            o[np.asarray(mask, dtype=bool)] = x
+        out.append(o)
+    return tuple(out)
 
 
 def search(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attention_mask: torch.Tensor,
            num_beams: int, max_new_tokens: int, apply_log_softmax_for_scores: bool = False,
-           use_graph: bool = True, taps: bool = False) -> SearchResult:
+           use_graph: bool = True, taps: bool = False, margins: bool = False) -> SearchResult:
     """One call of the hot path: encoder + L fused decode/select steps. Asynchronous on the
-    current torch stream; results are device tensors."""
+    current torch stream; results are device tensors. ``margins``: also the per-query pruning margin
+    (``rpr_search_margins``: one more kernel per selection step; tokens, scores and row ranges are the same bits)."""
     ctx = model.ctx
     dev = ctx.device
     ids = input_ids.to(device=dev, dtype=torch.int32).contiguous()
@@ -537,11 +569,19 @@ def search(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attent
         tap_struct = _lib.DebugTaps(*[tap_out[k].data_ptr() for k in
                                       ("encoder_out", "step_logits", "step_scores", "step_tokens", "step_parent",
                                        "step_valid")])
-    check(ctx.lib.rpr_search(ctx.handle, model.handle, trie.handle, ids.data_ptr(), mask.data_ptr(), Q, Lq, B, L, flags,
-                             tokens.data_ptr(), scores.data_ptr(), lo.data_ptr(), hi.data_ptr(),
-                             C.byref(tap_struct) if tap_struct is not None else None, _stream_ptr(dev)), "rpr_search")
+    tap_arg = C.byref(tap_struct) if tap_struct is not None else None
+    mg = None
+    if margins:
+        mg = torch.empty((Q,), dtype=torch.float64, device=dev)
+        check(ctx.lib.rpr_search_margins(ctx.handle, model.handle, trie.handle, ids.data_ptr(), mask.data_ptr(), Q, Lq, B, L,
+                                         flags, tokens.data_ptr(), scores.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                         mg.data_ptr(), tap_arg, _stream_ptr(dev)), "rpr_search_margins")
+    else:
+        check(ctx.lib.rpr_search(ctx.handle, model.handle, trie.handle, ids.data_ptr(), mask.data_ptr(), Q, Lq, B, L, flags,
+                                 tokens.data_ptr(), scores.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                 tap_arg, _stream_ptr(dev)), "rpr_search")
     # ids/mask must stay alive until the async D2D staging copies have been enqueued (they have).
-    return SearchResult(tokens, scores, lo, hi, tap_out)
+    return SearchResult(tokens, scores, lo, hi, tap_out, margins=mg)
 
 
 class GuardedSearch:
@@ -551,10 +591,18 @@ class GuardedSearch:
     synchronously with the safe settings before returning: ``STATUS_TAIL_LEFTOVER`` (optimistic forced-tail mode: a
     query was still unforced at the last fork) -> exact forced-tail mode; ``STATUS_SATURATED`` (an activation left the
     f16 plane range of the split-precision GEMMs) -> exact fp32 MFMA. ``STATUS_EMPTY_QUERY`` raises ``ValueError``.
-    ``repeated`` tells whether the returned result is a second run (its tensors are then new ones)."""
+    ``repeated`` tells whether the returned result is a second run (its tensors are then new ones).
 
-    def __init__(self, model, trie, ids, mask, B, L, log_softmax, res, ticket, optimistic=False):
+    ``margin_guard`` (a threshold eps, None = off): the search also computes the per-query pruning margins, and queries
+    whose margin is below eps on a ctx that is not already in f32 are searched again as ONE batch in exact fp32; their rows
+    replace the split-precision ones (``splice_rows``), and the result carries ``margins``, ``rerun`` and ``margins_f32``."""
+
+    def __init__(self, model, trie, ids, mask, B, L, log_softmax, res, ticket, optimistic=False, margin_guard=None):
         self._args = (model, trie, ids, mask, B, L, log_softmax)
+        self._margin_guard = margin_guard
+        # whether the search just issued ran in exact fp32 (the ctx setting, or a model pinned to it): nothing to re-run then
+        self._ran_f32 = margin_guard is not None and (
+            model.ctx.get_precision() == "f32" or bool(model.ctx.lib.rpr_model_f32_only(model.handle)))
         self._res, self._ticket = res, ticket
         self._optimistic = bool(optimistic)      # this call ran in the optimistic forced-tail mode on the caller's behalf
         self.repeated = False
@@ -575,6 +623,41 @@ class GuardedSearch:
         return res
 
     def _result(self) -> SearchResult:
+        res = self._status_result()
+        return res if self._margin_guard is None else self._near_tie_result(res)
+
+    def _near_tie_result(self, res: SearchResult) -> SearchResult:
+        model, trie, ids, mask, B, L, log_softmax = self._args
+        ctx = model.ctx
+        eps = float(self._margin_guard)
+        Q = int(res.margins.shape[0])
+        rerun = (res.margins < eps).cpu()                 # synchronises the search
+        # an exact-fp32 result (the ctx setting, a model pinned to f32, or the saturation guard's repeat) has nothing to re-run
+        if self._ran_f32 or not bool(rerun.any()):
+            res.rerun = torch.zeros((Q,), dtype=torch.bool)
+            res.margins_f32 = torch.empty((0,), dtype=torch.float64, device=res.margins.device)
+            self._res = res
+            return res
+        sel = rerun.to(ids.device)
+        saved_mode, saved_prec = ctx.forced_tail(), ctx.get_precision()
+        ctx.set_precision("f32")
+        if saved_mode == 2:   # the re-run is reported as exact: no query may be left behind at the last fork
+            ctx.set_forced_tail(1)
+        try:
+            ctx.status(clear=True)
+            sub = search(model, trie, ids[sel], mask[sel], B, L, apply_log_softmax_for_scores=log_softmax, margins=True)
+            st = ctx.status(clear=True)
+        finally:
+            ctx.set_precision(saved_prec)
+            ctx.set_forced_tail(saved_mode)
+        if st & _lib.STATUS_TAIL_LEFTOVER:   # cannot happen in the exact mode; never splice unspecified rows in
+            raise RuntimeError("near-tie re-run left a query unforced at the last fork")
+        tokens, scores, lo, hi = splice_rows((res.tokens, res.scores, res.row_lo, res.row_hi), rerun,
+                                             (sub.tokens, sub.scores, sub.row_lo, sub.row_hi))
+        self._res = SearchResult(tokens, scores, lo, hi, None, margins=res.margins, rerun=rerun, margins_f32=sub.margins)
+        return self._res
+
+    def _status_result(self) -> SearchResult:
         st = self._ticket.flags()
         if st & _lib.STATUS_EMPTY_QUERY:
             raise ValueError("a query has an all-zero attention_mask (no token to attend to)")
@@ -587,13 +670,15 @@ class GuardedSearch:
                 warnings.warn("activation outside the f16 plane range of the split-precision GEMMs: repeating this batch "
                               "with exact fp32 MFMA (RPR_PRECISION=f32 avoids the retry)")
                 ctx.set_precision("f32")
+                self._ran_f32 = True
             if saved_mode == 2:
                 ctx.set_forced_tail(1)
             if st & _lib.STATUS_TAIL_LEFTOVER:
                 _note_optimistic_outcome(ctx, leftover=True)
             try:
                 ctx.status(clear=True)
-                self._res = search(model, trie, ids, mask, B, L, apply_log_softmax_for_scores=log_softmax)
+                self._res = search(model, trie, ids, mask, B, L, apply_log_softmax_for_scores=log_softmax,
+                                   margins=self._margin_guard is not None)
                 ctx.status(clear=True)
             finally:
                 ctx.set_precision(saved_prec)
@@ -632,11 +717,13 @@ def _optimistic_allowed(ctx: Context) -> bool:
 
 def search_guarded(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attention_mask: torch.Tensor,
                    num_beams: int, max_new_tokens: int, apply_log_softmax_for_scores: bool = False,
-                   optimistic: Optional[bool] = None) -> GuardedSearch:
+                   optimistic: Optional[bool] = None, margin_guard: Optional[float] = None) -> GuardedSearch:
     """``search`` plus the status guards, checked when ``result()`` is called (see :class:`GuardedSearch`). With
     ``optimistic`` (default: on unless ``RPR_OPTIMISTIC_TAIL=0``) a ctx in the exact forced-tail mode runs this call in
     the optimistic mode — the last, almost always empty, step-by-step stage is not enqueued — and the guard repeats the
-    batch exactly in the rare case a query needed it."""
+    batch exactly in the rare case a query needed it. ``margin_guard`` = eps (None: off, the same calls and the same bits
+    as before): the near-tie guard of :class:`GuardedSearch`; 1e-3, the project's tolerance for cumulative scores at the
+    pruning boundary, is the suggested value."""
     import os
     ctx = model.ctx
     if optimistic is None:
@@ -648,12 +735,12 @@ def search_guarded(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor
         ctx.set_forced_tail(2)
     try:
         res = search(model, trie, input_ids, attention_mask, num_beams, max_new_tokens,
-                     apply_log_softmax_for_scores=apply_log_softmax_for_scores)
+                     apply_log_softmax_for_scores=apply_log_softmax_for_scores, margins=margin_guard is not None)
     finally:
         ctx.set_forced_tail(mode)
     ticket = ctx.status_async(clear=True)
     return GuardedSearch(model, trie, input_ids, attention_mask, int(num_beams), int(max_new_tokens),
-                         bool(apply_log_softmax_for_scores), res, ticket, optimistic=went_optimistic)
+                         bool(apply_log_softmax_for_scores), res, ticket, optimistic=went_optimistic, margin_guard=margin_guard)
 
 
 def lngknp_forward(model: DeviceModel, input_ids: torch.Tensor, attention_mask: torch.Tensor, doc_codes: torch.Tensor,

@@ -88,13 +88,17 @@ class _HostCopier:
 
 
 def constrained_decode_doc(model, dataloader, prefix_constrain_processor, smtid_to_docids, max_new_token, device,
-                           out_dir, local_rank, topk=100, apply_log_softmax_for_scores=False, write=True, gather=False):
+                           out_dir, local_rank, topk=100, apply_log_softmax_for_scores=False, write=True, gather=False,
+                           near_tie_guard=None, near_tie=None):
     """reference evaluate.py:87-132. ``smtid_to_docids``: the reference's dict
     ``{"c1_.._cL": [docids]}`` or a :class:`DocidTable` (range lookup, no strings).
 
     ``gather=True`` (multi-process runs with a DocidTable): instead of one ``run_{rank}.json`` per rank, the ranks'
     row ranges and scores are exchanged with one RCCL all_gather (ripor_amd/dist_gather.py) and rank 0 writes the
-    merged ``run.json`` itself — the ``..._2`` merge step then finds it complete (:func:`merge_runs`)."""
+    merged ``run.json`` itself — the ``..._2`` merge step then finds it complete (:func:`merge_runs`).
+
+    ``near_tie_guard`` (None = off): threshold of the near-tie guard (queries whose pruning margin is below it are
+    searched again in exact fp32); ``near_tie``: a :class:`NearTieLog` the batches are noted in."""
     import torch.distributed as dist
     from .dist_gather import all_gather_results
     qid_to_rankdata: Dict[int, Dict[str, float]] = {}
@@ -139,8 +143,12 @@ def constrained_decode_doc(model, dataloader, prefix_constrain_processor, smtid_
                 attention_mask=inputs["attention_mask"].long(), max_new_tokens=max_new_token, output_scores=True,
                 return_dict=True, return_dict_in_generate=True, num_beams=topk, num_return_sequences=topk,
                 apply_log_softmax_for_scores=apply_log_softmax_for_scores,
-                defer_status=copier is not None)   # the side-stream path checks the guards in finish(), one batch later
+                # the side-stream path checks the guards in finish(), one batch later; the near-tie guard needs the margins now
+                defer_status=copier is not None and near_tie_guard is None,
+                **({} if near_tie_guard is None else {"near_tie_guard": near_tie_guard}))
         batch_qids = batch["id"].cpu().tolist()
+        if near_tie is not None and outputs.near_tie is not None:
+            near_tie.note(batch_qids, *outputs.near_tie)
         tm["enqueue_search_s"] += time.perf_counter() - t0
         tm["batches"] += 1
         tm["queries"] += len(batch_qids)
@@ -237,10 +245,12 @@ def constrained_decode(model, dataloader, prefix_constrain_processor, smtid_to_d
 
 
 def constrained_decode_smtid(model, dataloader, prefix_constrain_processor, smtid_to_docids, max_new_token, device,
-                             out_dir, local_rank, topk=100, apply_log_softmax_for_scores=False, write=True):
+                             out_dir, local_rank, topk=100, apply_log_softmax_for_scores=False, write=True,
+                             near_tie_guard=None, near_tie=None):
     """reference evaluate.py:134-178: nested ``{qid: {smtid: {docid: score}}}`` for the training-data
     generation pass (prefix search: max_new_token in {4, 8, 16, 32}, many docids per smtid) ->
-    ``qid_smtid_rankdata_{rank}.json``. ``smtid_to_docids``: the reference's dict or a DocidTable."""
+    ``qid_smtid_rankdata_{rank}.json``. ``smtid_to_docids``: the reference's dict or a DocidTable.
+    ``near_tie_guard`` / ``near_tie``: as in :func:`constrained_decode_doc`."""
     out: Dict[int, Dict[str, Dict[str, float]]] = {}
     use_ranges = isinstance(smtid_to_docids, DocidTable)
     for batch in dataloader:
@@ -250,8 +260,11 @@ def constrained_decode_smtid(model, dataloader, prefix_constrain_processor, smti
                 model, prefix_constrain_processor, input_ids=inputs["input_ids"].long(),
                 attention_mask=inputs["attention_mask"].long(), max_new_tokens=max_new_token, output_scores=True,
                 return_dict=True, return_dict_in_generate=True, num_beams=topk, num_return_sequences=topk,
-                apply_log_softmax_for_scores=apply_log_softmax_for_scores)
+                apply_log_softmax_for_scores=apply_log_softmax_for_scores,
+                **({} if near_tie_guard is None else {"near_tie_guard": near_tie_guard}))
         batch_qids = batch["id"].cpu().tolist()
+        if near_tie is not None and outputs.near_tie is not None:
+            near_tie.note(batch_qids, *outputs.near_tie)
         str_smtids = convert_ptsmtids_to_strsmtid(outputs.sequences.view(-1, topk, max_new_token + 1), max_new_token)
         relevant_scores = outputs.sequences_scores.view(-1, topk).cpu().tolist()
         lo = outputs.row_lo.view(-1, topk).cpu().tolist()
@@ -272,6 +285,45 @@ def constrained_decode_smtid(model, dataloader, prefix_constrain_processor, smti
         with open(os.path.join(out_dir, f"qid_smtid_rankdata_{local_rank}.json"), "w") as fout:
             json.dump(out, fout)
     return out
+
+
+class NearTieLog:
+    """What ``--near_tie_guard`` reports: per dataset the queries searched, those whose split-precision pruning margin was
+    below the threshold and were searched again in exact fp32, and those still below it there (near-ties of the reference's
+    own arithmetic). ``write`` gathers the ranks' logs (when a process group is up) and rank 0 writes ``near_tie.json``."""
+
+    def __init__(self, threshold: float):
+        self.threshold = float(threshold)
+        self.queries = 0
+        self.rerun_qids: List = []
+        self.still_qids: List = []
+
+    def note(self, qids, margins, rerun, margins_f32):
+        rerun = rerun.cpu().tolist()
+        f32 = margins_f32.cpu().tolist()
+        self.queries += len(qids)
+        picked = [qid for qid, r in zip(qids, rerun) if r]
+        self.rerun_qids += picked
+        self.still_qids += [qid for qid, m in zip(picked, f32) if m < self.threshold]
+
+    def write(self, out_dir: str):
+        import sys
+        import torch.distributed as dist
+        logs = [self]
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            logs = [None] * dist.get_world_size()
+            dist.all_gather_object(logs, self)
+            if dist.get_rank() != 0:
+                return
+        # shards are padded by wrap-around: a query may have been searched by two ranks
+        rerun = sorted(set(q for l in logs for q in l.rerun_qids), key=str)
+        still = sorted(set(q for l in logs for q in l.still_qids), key=str)
+        rec = {"threshold": self.threshold, "queries": sum(l.queries for l in logs), "rerun_fp32": len(rerun),
+               "still_under_threshold_fp32": len(still), "rerun_qids": rerun, "still_under_threshold_qids": still}
+        with open(os.path.join(out_dir, "near_tie.json"), "w") as fout:
+            json.dump(rec, fout)
+        print(f"near-tie guard: {rec['rerun_fp32']} of {rec['queries']} queries searched again in exact fp32, "
+              f"{rec['still_under_threshold_fp32']} still under {self.threshold:g}", file=sys.stderr)
 
 
 def build_smtid_to_docids(docid_to_smtids: Dict[str, Sequence[int]], max_new_token: int) -> Dict[str, List[str]]:
@@ -480,10 +532,14 @@ def t5seq_aq_retrieve_docids(args):
         if rank == 0:
             print(f"queries per search call: {qbs} (--batch_size={args.batch_size})")
         loader = query_batches(coll, tokenizer, shard_indices(len(coll), world, rank), qbs, 256)
+        eps = getattr(args, "near_tie_guard", None)
+        log = NearTieLog(eps) if eps is not None else None
         constrained_decode_doc(model.base_model, loader, processor, table, max_new_token, device=device,
                                out_dir=out_dir, local_rank=local_rank, topk=args.topk,
                                apply_log_softmax_for_scores=args.apply_log_softmax_for_scores,
-                               gather=bool(args.gather_results))
+                               gather=bool(args.gather_results), near_tie_guard=eps, near_tie=log)
+        if log is not None:
+            log.write(out_dir)
 
 
 def merge_runs(out_dir: str, expected_files: Optional[int] = None) -> Dict[str, Dict[str, float]]:
@@ -544,9 +600,13 @@ def t5seq_aq_get_qid_to_smtid_rankdata(args):
     if rank == 0:
         print(f"queries per search call: {qbs} (--batch_size={args.batch_size})")
     loader = query_batches(coll, tokenizer, shard_indices(len(coll), world, rank), qbs, 256)
+    eps = getattr(args, "near_tie_guard", None)
+    log = NearTieLog(eps) if eps is not None else None
     constrained_decode_smtid(model.base_model, loader, processor, table, args.max_new_token, device=local_rank,
                              out_dir=args.out_dir, local_rank=local_rank, topk=args.topk,
-                             apply_log_softmax_for_scores=args.apply_log_softmax_for_scores)
+                             apply_log_softmax_for_scores=args.apply_log_softmax_for_scores, near_tie_guard=eps, near_tie=log)
+    if log is not None:
+        log.write(args.out_dir)
 
 
 def merge_qid_smtid_rankdata(out_dir: str, expected_files: Optional[int] = None):
@@ -687,6 +747,10 @@ def get_args(argv=None):
     ap.add_argument("--codebook_bits", type=int, default=8)
     ap.add_argument("--apply_log_softmax_for_scores", type=lambda s: str(s).lower() in ("1", "true", "yes"),
                     default=False)
+    # absent unless given (the namespace of a run without it is unchanged): threshold of the near-tie guard
+    ap.add_argument("--near_tie_guard", type=float, default=argparse.SUPPRESS,
+                    help="t5seq_aq_retrieve_docids / t5seq_aq_get_qid_to_smtid_rankdata: search queries whose pruning margin is "
+                         "below this (suggested: 1e-3) again in exact fp32 and write near_tie.json")
     return ap.parse_args(argv)
 
 

@@ -37,7 +37,7 @@ class BeamSearchEncoderDecoderOutput:
 
     def __init__(self, sequences=None, sequences_scores=None, scores=None, beam_indices=None, encoder_attentions=None,
                  encoder_hidden_states=None, decoder_attentions=None, cross_attentions=None, decoder_hidden_states=None,
-                 row_lo=None, row_hi=None, guard=None, _step_record=None):
+                 row_lo=None, row_hi=None, guard=None, _step_record=None, near_tie=None):
         self.sequences, self.sequences_scores = sequences, sequences_scores
         self._scores, self._beam_indices = scores, beam_indices
         self.encoder_attentions, self.encoder_hidden_states = encoder_attentions, encoder_hidden_states
@@ -47,6 +47,8 @@ class BeamSearchEncoderDecoderOutput:
         self.row_lo, self.row_hi = row_lo, row_hi
         # with defer_status=True: the E.GuardedSearch whose result() must be consulted before the tensors above are trusted
         self.guard = guard
+        # with near_tie_guard (and without defer_status): (margins [Q] float64, rerun [Q] bool, margins_f32 [rerun.sum()])
+        self.near_tie = near_tie
         self._step_record = _step_record      # callable -> (scores tuple, beam_indices tuple), or None
 
     def _materialise(self):
@@ -242,8 +244,11 @@ def generate_for_constrained_prefix_beam_search(
     # when a query was left unforced at the last fork. The reference call is synchronous (>= 2*B*Q syncs per step) and so
     # is this one by default; with defer_status=True the check happens when the caller asks for `outputs.guard.result()`
     # (ripor_amd/evaluate.py: while the next batch runs).
+    # near_tie_guard = eps (extra of this implementation, default off): queries whose pruning margin is below eps are
+    # searched again in exact fp32 (E.GuardedSearch); the output then carries .near_tie = (margins, rerun, margins_f32)
+    near_tie_guard = model_kwargs.pop("near_tie_guard", None)
     guard = E.search_guarded(em, trie, input_ids, attention_mask, num_beams, L,
-                             apply_log_softmax_for_scores=bool(apply_log_softmax_for_scores))
+                             apply_log_softmax_for_scores=bool(apply_log_softmax_for_scores), margin_guard=near_tie_guard)
     defer = bool(model_kwargs.pop("defer_status", False)) and bool(return_dict_in_generate)
     res = guard._res if defer else guard.result()
     Q, B, K = input_ids.shape[0], num_beams, num_return_sequences
@@ -264,4 +269,5 @@ def generate_for_constrained_prefix_beam_search(
         sequences=seqs,
         sequences_scores=res.scores[:, :K].reshape(Q * K) if output_scores else None,
         row_lo=res.row_lo[:, :K].reshape(Q * K), row_hi=res.row_hi[:, :K].reshape(Q * K), guard=guard if defer else None,
-        _step_record=record)
+        _step_record=record,
+        near_tie=(res.margins, res.rerun, res.margins_f32) if near_tie_guard is not None and not defer else None)
