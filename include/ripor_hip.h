@@ -509,6 +509,27 @@ int rpr_embed(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const in
 int rpr_rq_search(rpr_ctx* ctx, const float* queries, int32_t Q, int32_t d, const float* codebooks, int32_t M, int32_t K,
                   const uint16_t* codes, int64_t N, int32_t topk, int64_t* out_idx, float* out_scores, void* stream);
 
+/* ---- exact dense retrieval (reference --task=retrieve: faiss.IndexFlatIP.search over the collection's embeddings) ---- */
+/* Exact top-k inner-product search over a block of the fp32 embedding matrix. x is rows row_base .. row_base + n - 1 of the
+ * collection, row-major [n, d]. Exact semantics (tests/flat_search_ref.py restates them in numpy):
+ *   score[q][r]   = <queries[q], x[r]> from the exact-fp32 MFMA GEMM: one fixed fp32 chain per entry, whatever
+ *                   rpr_set_precision says, whatever the query batch and however the rows are cut into blocks;
+ *   ranking       = score descending, exact ties to the smaller GLOBAL row; -0.0 equals +0.0 (and is returned as +0.0);
+ *   merge == 0    : io_idx / io_scores [Q, topk] receive the top topk of this block; missing entries are idx = -1,
+ *                   score = -inf;
+ *   merge == 1    : the top topk of the union of this block and the entries already in io_* (a previous result: sorted,
+ *                   the idx < 0 entries last, which are ignored). The caller guarantees that the stored rows are not rows
+ *                   of this block.
+ * Searching [0, N) in one call therefore equals chaining any partition of it through merge, in any order, bit for bit.
+ * Inputs must be finite. Deterministic: no float atomics, two runs are bit-identical. All pointers are device pointers:
+ *   queries [Q, d] fp32, x [n, d] fp32, io_idx [Q, topk] int64, io_scores [Q, topk] fp32.
+ * d % 32 == 0, d >= 32, Q >= 1, n >= 1, row_base >= 0, row_base + n <= 2^31 - 1, 1 <= topk <= 2048, merge 0 or 1; anything
+ * else is RPR_ERR_INVALID. The Q x n scores never exist in full: the rows are walked in sub-blocks so that the score
+ * scratch stays within 256 MB (csrc/common.h FLAT_SCRATCH_BYTES), large Q is chunked as in rpr_rq_search; the scratch
+ * lives in the context's workspace. */
+int rpr_flat_search(rpr_ctx* ctx, const float* queries, int32_t Q, int32_t d, const float* x, int64_t n, int64_t row_base,
+                    int32_t topk, int64_t* io_idx, float* io_scores, int32_t merge, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,8 @@ SIGNATURES = {
     "rpr_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rpr_rq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rpr_flat_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

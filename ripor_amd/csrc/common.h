@@ -175,6 +175,66 @@ int rq_search_group(int M, int K);   // queries a block serves at once (4, 2 or 
 // the whole selection for Q queries whose LUT is ready: idx / scores [Q, topk]; cus = CUs of the device
 hipError_t launch_rq_select(const RqScanArgs& a, int topk, int64_t* out_idx, float* out_scores, int cus, hipStream_t s);
 
+// The selection machinery both searches share (kernels in rq_search.hip). A (score, row) pair is the 63-bit value
+// rqs_key(score) << 31 | (2^31 - 1 - row): descending = score descending, ties to the smaller row, -0.0 = +0.0.
+__device__ __forceinline__ unsigned rqs_key(float s) {
+  const unsigned u = s == 0.f ? 0u : __float_as_uint(s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float rqs_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+__device__ __forceinline__ unsigned long long rqs_value(float s, long long row) {
+  return ((unsigned long long)rqs_key(s) << 31) | (0x7fffffffull - (unsigned long long)row);
+}
+struct RqSelBufs { RqSelState* st; unsigned* hist; unsigned long long* cand; unsigned* cand_n; };
+hipError_t launch_rq_sel_init(RqSelState* st, int Q, unsigned need, int done, hipStream_t s);
+hipError_t launch_rq_locate(RqSelState* st, unsigned* hist, int Q, int shift, hipStream_t s);
+hipError_t launch_rq_finish(const unsigned long long* cand, const unsigned* cand_n, int Q, int topk, int64_t* out_idx,
+                            float* out_scores, hipStream_t s);
+// The pass schedule over N values per query: scan(collect, shift, width) enqueues one pass over the caller's score source
+// (collect == 0: histogram of the digit at `shift` of the values matching the prefix; 1: append every value >= prefix).
+template <class Scan>
+hipError_t rq_select_passes(const RqSelBufs& b, int Q, long long N, int topk, int64_t* out_idx, float* out_scores, hipStream_t s,
+                            Scan scan) {
+  hipError_t e = hipMemsetAsync(b.hist, 0, (size_t)Q * RQS_BINS * sizeof(unsigned), s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(b.cand_n, 0, (size_t)Q * sizeof(unsigned), s);
+  if (e != hipSuccess) return e;
+  const unsigned need = (unsigned)(N < topk ? N : topk);
+  e = launch_rq_sel_init(b.st, Q, need, N <= RQS_CAP ? 1 : 0, s);
+  if (e != hipSuccess) return e;
+  if (N > RQS_CAP) {
+    // 63 bits, ten at a time from the top; a pass whose queries are all done returns at once
+    for (int shift = 53; ; shift = shift >= 10 ? shift - 10 : 0) {
+      const int width = shift == 0 ? 3 : 10;
+      e = scan(0, shift, width);
+      if (e != hipSuccess) return e;
+      e = launch_rq_locate(b.st, b.hist, Q, shift, s);
+      if (e != hipSuccess) return e;
+      if (shift == 0) break;
+    }
+  }
+  e = scan(1, 0, 0);
+  if (e != hipSuccess) return e;
+  return launch_rq_finish(b.cand, b.cand_n, Q, topk, out_idx, out_scores, s);
+}
+
+// ---- exact top-k inner-product search over the embedding matrix (flat_search.hip; rpr_flat_search in rq_api.hip; §9e) --
+constexpr size_t FLAT_SCRATCH_BYTES = (size_t)256 << 20;   // the score matrix of one (query chunk, row sub-block) stays under this
+struct FlatScanArgs {
+  const float* sc; long long ld;   // [Q, ld] scores of a sub-block, ld % 4 == 0
+  long long n, row0;               // live columns; global row of column 0
+  int Q;
+  RqSelBufs b;
+  const int64_t* io_idx; const float* io_scores; int topk;   // the running state [Q, topk]: once a query's list is full its last
+                                                             // value is a lower bound, and the scan leaves out what is below it
+};
+// top `topk` of the sub-block's scores per query -> tmp_idx / tmp_scores [Q, topk] sorted (global rows; -1 / -inf past n)
+hipError_t launch_flat_select(const FlatScanArgs& a, int topk, int64_t* tmp_idx, float* tmp_scores, int cus, hipStream_t s);
+// io <- the top `topk` of (io, tmp) per query, both sorted by value; entries with idx < 0 are ignored
+hipError_t launch_flat_merge(const int64_t* tmp_idx, const float* tmp_scores, int Q, int topk, int64_t* io_idx, float* io_scores,
+                             hipStream_t s);
+hipError_t launch_flat_clear(int64_t* idx, float* scores, long long count, hipStream_t s);   // idx = -1, score = -inf
+
 // ---- split-precision GEMM: operands as two f16 planes (hi, lo), 3 f16 MFMAs per product ---------
 struct GemmH2Args {
   const __half* A; size_t a_ps; int lda;   // planes [2][M][lda], plane stride a_ps elements

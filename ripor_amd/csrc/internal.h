@@ -173,6 +173,8 @@ struct Workspace {
   DevBuf rq_r, rq_code, rq_hist, rq_order, rq_cnorm, rq_part, rq_idx;
   // rpr_rq_search: the LUT of a query chunk [Qc, M * K] and the selection scratch (state, histograms, candidate lists)
   DevBuf rq_lut, rq_sel;
+  // rpr_flat_search: the scores of one (query chunk, row sub-block) [Qc, ld]; its selection scratch is rq_sel
+  DevBuf flat_sc;
   // rpr_rq_encode_beam: the second residual plane (the first is rq_r), |r|^2 of the beam entries (two planes), the
   // candidates of a level (scores, then codes) and the parent slot / code history of every level (slots, then codes)
   DevBuf rq_r2, rq_bnorm, rq_cand, rq_bhist;

@@ -1,6 +1,7 @@
 // Docid creation behind the C ABI: rpr_rq_train / rpr_rq_encode (kernels in gemm_f32.hip, buffers in the search workspace),
 // rpr_rq_encode_beam (kernels in rq_beam.hip),
-// and the search over the codes they produce: rpr_rq_search (kernels in rq_search.hip).
+// the search over the codes they produce: rpr_rq_search (kernels in rq_search.hip),
+// and the exact search over the embeddings themselves: rpr_flat_search (kernels in flat_search.hip).
 #include <vector>
 
 #include "internal.h"
@@ -205,6 +206,67 @@ int rpr_rq_search(rpr_ctx* c, const float* queries, int32_t Q, int32_t d, const 
     RPR_HIP(launch_gemm(g, s));
     a.Q = nq;
     RPR_HIP(launch_rq_select(a, topk, out_idx + (size_t)q0 * topk, out_scores + (size_t)q0 * topk, cus, s));
+  }
+  return RPR_OK;
+}
+
+// ---- exact top-k inner-product search over the embeddings (reference: faiss.IndexFlatIP.search, --task=retrieve) --------
+// DESIGN.md §9e. Per chunk of queries and per sub-block of rows: the exact-fp32 GEMM fills the score scratch [Qc, rows]
+// (at most FLAT_SCRATCH_BYTES), flat_search.hip selects the sub-block's top-k and merges it into io_*. The row in every
+// compared value is the global one, so neither the sub-block size nor the caller's blocks change a bit of the result.
+int rpr_flat_search(rpr_ctx* c, const float* queries, int32_t Q, int32_t d, const float* x, int64_t n, int64_t row_base,
+                    int32_t topk, int64_t* io_idx, float* io_scores, int32_t merge, void* stream) {
+  RPR_REQUIRE(c, "NULL argument");
+  RPR_REQUIRE(Q >= 1, "Q must be at least 1");
+  RPR_REQUIRE(d >= 32 && d % 32 == 0, "d must be a positive multiple of 32");
+  RPR_REQUIRE(n >= 1, "n must be at least 1");
+  RPR_REQUIRE(row_base >= 0, "row_base must be at least 0");
+  RPR_REQUIRE(n <= (int64_t)0x7fffffff && row_base <= (int64_t)0x7fffffff - n, "row_base + n out of range (at most 2^31 - 1)");
+  RPR_REQUIRE(topk >= 1 && topk <= 2048, "topk out of range (1 .. 2048)");
+  RPR_REQUIRE(merge == 0 || merge == 1, "merge must be 0 or 1");
+  RPR_REQUIRE(queries && x && io_idx && io_scores, "NULL argument");   // after the limits: an empty tensor has no address
+  static_assert(RQS_CAP >= 2048, "the candidate list holds the largest topk");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int cus = 0;
+  RPR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+  // queries are chunked as rpr_rq_search chunks them: the per-query selection scratch (plus the sub-block's sorted list) under 60 MB
+  const size_t per_q = RQS_BINS * sizeof(unsigned) + RQS_CAP * sizeof(unsigned long long) + sizeof(RqSelState) + sizeof(unsigned) +
+                       (size_t)topk * (sizeof(int64_t) + sizeof(float));
+  int64_t qc = (int64_t)(((size_t)60 << 20) / per_q);
+  qc = qc > Q ? Q : qc;
+  // rows of a sub-block: whole 128-row GEMM tiles, Qc x rows x 4 bytes within the scratch constant
+  int64_t rows = (int64_t)(FLAT_SCRATCH_BYTES / sizeof(float)) / qc / 128 * 128;
+  rows = rows < 128 ? 128 : rows;
+  const int64_t ld = rows < n ? rows : (n + 3) / 4 * 4;
+  Workspace& w = c->ws;
+  { const int e = ensure(c, w.flat_sc, (size_t)qc * ld * sizeof(float)); if (e) return e; }
+  { const int e = ensure(c, w.rq_sel, (size_t)qc * per_q + 64); if (e) return e; }
+  FlatScanArgs a{};
+  a.sc = P<float>(w.flat_sc); a.ld = ld;
+  a.b.cand = P<unsigned long long>(w.rq_sel);                                 // 8-byte items first
+  int64_t* tmp_idx = reinterpret_cast<int64_t*>(a.b.cand + (size_t)qc * RQS_CAP);
+  a.b.st = reinterpret_cast<RqSelState*>(tmp_idx + (size_t)qc * topk);
+  a.b.hist = reinterpret_cast<unsigned*>(a.b.st + qc);
+  a.b.cand_n = a.b.hist + (size_t)qc * RQS_BINS;
+  float* tmp_scores = reinterpret_cast<float*>(a.b.cand_n + qc);
+  if (!merge) RPR_HIP(launch_flat_clear(io_idx, io_scores, (long long)Q * topk, s));
+  for (int64_t q0 = 0; q0 < Q; q0 += qc) {
+    const int nq = (int)(Q - q0 < qc ? Q - q0 : qc);
+    a.Q = nq;
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t nr = n - r0 < rows ? n - r0 : rows;
+      GemmArgs g{};
+      g.A = queries + (size_t)q0 * d; g.lda = d;
+      g.W = x + (size_t)r0 * d; g.ldw = d;
+      g.out[0] = P<float>(w.flat_sc); g.ldo[0] = (int)ld; g.split_n = (int)nr;
+      g.M = nq; g.N = (int)nr; g.K = d;
+      RPR_HIP(launch_gemm(g, s));
+      a.n = nr; a.row0 = row_base + r0;
+      a.io_idx = io_idx + (size_t)q0 * topk; a.io_scores = io_scores + (size_t)q0 * topk; a.topk = topk;
+      RPR_HIP(launch_flat_select(a, topk, tmp_idx, tmp_scores, cus, s));
+      RPR_HIP(launch_flat_merge(tmp_idx, tmp_scores, nq, topk, io_idx + (size_t)q0 * topk, io_scores + (size_t)q0 * topk, s));
+    }
   }
   return RPR_OK;
 }

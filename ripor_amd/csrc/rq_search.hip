@@ -20,6 +20,9 @@
 // a finish kernel sorts the list by c and writes topk rows. Equal scores in excess of the list (all scores equal, N >>
 // topk) simply take more digits: the later ones are bits of the row index. Every count is an integer and every candidate
 // value is unique, so the result does not depend on the order in which atomics land.
+//
+// The key helpers, the selection state, the pass schedule (rq_select_passes) and the init / locate / finish launchers are
+// declared in common.h: flat_search.hip runs the same selection over a score matrix with a scan kernel of its own.
 #include "common.h"
 
 namespace rpr {
@@ -28,12 +31,6 @@ namespace {
 
 constexpr int RQS_THREADS = 256, RQS_ROWS = 4, RQS_CHUNK = RQS_THREADS * RQS_ROWS;
 constexpr size_t RQS_LDS = 160 * 1024;
-
-__device__ __forceinline__ unsigned rqs_key(float s) {
-  const unsigned u = s == 0.f ? 0u : __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float rqs_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
 template <int G>
 __device__ __forceinline__ void rqs_add(float (&acc)[G], const float* e) {
@@ -177,6 +174,14 @@ __global__ __launch_bounds__(RQS_BINS) void rq_locate_kernel(RqSelState* st, uns
     __syncthreads();
   }
   const unsigned incl = sc[t], excl = incl - h;
+  if (t == RQS_BINS - 1 && incl < cur.need) {
+    // fewer values were counted than asked for: a scan that leaves out values under a lower bound (flat_search.hip; never
+    // rpr_rq_search, whose first pass counts all N >= need). They all fit the candidate list: collect them, take them all
+    RqSelState nx = cur;
+    nx.need = incl;
+    nx.done = 1;
+    st[q] = nx;
+  }
   if (excl < cur.need && cur.need <= incl) {
     RqSelState nx = cur;
     nx.prefix = cur.prefix | ((unsigned long long)bin << shift);
@@ -262,35 +267,34 @@ hipError_t launch_rq_scan(RqScanArgs a, int collect, int shift, int width, int c
 #undef RPR_RQS
 }
 
-hipError_t launch_rq_select(const RqScanArgs& a, int topk, int64_t* out_idx, float* out_scores, int cus, hipStream_t s) {
-  hipError_t e = hipMemsetAsync(a.hist, 0, (size_t)a.Q * RQS_BINS * sizeof(unsigned), s);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(a.cand_n, 0, (size_t)a.Q * sizeof(unsigned), s);
-  if (e != hipSuccess) return e;
-  const unsigned need = (unsigned)(a.N < topk ? a.N : topk);
-  hipLaunchKernelGGL(rq_sel_init_kernel, dim3((a.Q + 255) / 256), dim3(256), 0, s, a.st, a.Q, need, a.N <= RQS_CAP ? 1 : 0);
-  if (a.N > RQS_CAP) {
-    // 63 bits, ten at a time from the top; a pass whose queries are all done returns at once
-    for (int shift = 53; ; shift = shift >= 10 ? shift - 10 : 0) {
-      const int width = shift == 0 ? 3 : 10;
-      e = launch_rq_scan(a, 0, shift, width, cus, s);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(rq_locate_kernel, dim3(a.Q), dim3(RQS_BINS), 0, s, a.st, a.hist, shift);
-      if (shift == 0) break;
-    }
-  }
-  e = launch_rq_scan(a, 1, 0, 0, cus, s);
-  if (e != hipSuccess) return e;
+hipError_t launch_rq_sel_init(RqSelState* st, int Q, unsigned need, int done, hipStream_t s) {
+  hipLaunchKernelGGL(rq_sel_init_kernel, dim3((Q + 255) / 256), dim3(256), 0, s, st, Q, need, done);
+  return hipGetLastError();
+}
+
+hipError_t launch_rq_locate(RqSelState* st, unsigned* hist, int Q, int shift, hipStream_t s) {
+  hipLaunchKernelGGL(rq_locate_kernel, dim3(Q), dim3(RQS_BINS), 0, s, st, hist, shift);
+  return hipGetLastError();
+}
+
+hipError_t launch_rq_finish(const unsigned long long* cand, const unsigned* cand_n, int Q, int topk, int64_t* out_idx,
+                            float* out_scores, hipStream_t s) {
   static bool attr_done = false;
   if (!attr_done) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(rq_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            RQS_CAP * (int)sizeof(unsigned long long));
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rq_finish_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, RQS_CAP * (int)sizeof(unsigned long long));
     if (e != hipSuccess) return e;
     attr_done = true;
   }
-  hipLaunchKernelGGL(rq_finish_kernel, dim3(a.Q), dim3(1024), RQS_CAP * sizeof(unsigned long long), s, a.cand, a.cand_n, topk,
-                     out_idx, out_scores);
+  hipLaunchKernelGGL(rq_finish_kernel, dim3(Q), dim3(1024), RQS_CAP * sizeof(unsigned long long), s, cand, cand_n, topk, out_idx,
+                     out_scores);
   return hipGetLastError();
+}
+
+hipError_t launch_rq_select(const RqScanArgs& a, int topk, int64_t* out_idx, float* out_scores, int cus, hipStream_t s) {
+  const RqSelBufs b{a.st, a.hist, a.cand, a.cand_n};
+  return rq_select_passes(b, a.Q, a.N, topk, out_idx, out_scores, s,
+                          [&](int collect, int shift, int width) { return launch_rq_scan(a, collect, shift, width, cus, s); });
 }
 
 }  // namespace rpr

@@ -1266,3 +1266,38 @@ def rq_search(ctx: Context, queries, codebooks, codes, topk: int):
     check(ctx.lib.rpr_rq_search(ctx.handle, q.data_ptr(), Q, d, books.data_ptr(), M, K, cd.data_ptr(), cd.shape[0], topk,
                                 idx.data_ptr(), scores.data_ptr(), _stream_ptr(dev)), "rpr_rq_search")
     return idx, scores
+
+
+FLAT_SCRATCH_BYTES = 256 << 20   # csrc/common.h FLAT_SCRATCH_BYTES: the score scratch of one (query chunk, row sub-block)
+
+
+def flat_search(ctx: Context, queries, x, topk: int, row_base: int = 0, state=None):
+    """Exact top-``topk`` rows of every query by inner product with the rows of ``x`` (``rpr_flat_search``).
+    ``queries`` fp32 [Q, d] (device tensor or host array), ``x`` fp32 [n, d] device tensor holding the rows ``row_base`` ..
+    ``row_base + n - 1`` of the collection. ``state``: the (idx, scores) a previous call returned for other rows of the same
+    collection; the result is then the top of the union (the tensors of ``state`` are left as they are).
+    -> (idx int64 [Q, topk] of global rows, scores fp32 [Q, topk]) on the device; the tail of a short result is idx -1,
+    score -inf. Ties go to the smaller global row, so any partition of the collection chained through ``state`` gives the
+    bits of a single call."""
+    dev = ctx.device
+    q = torch.as_tensor(queries, dtype=torch.float32).to(dev).contiguous()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise ValueError("x must be an fp32 device tensor [n, d]")
+    x = x.contiguous()
+    if q.dim() != 2 or x.dim() != 2:
+        raise ValueError("queries [Q, d] and x [n, d] expected")
+    Q, d = q.shape
+    if x.shape[1] != d:
+        raise ValueError(f"queries of width {d} against rows of width {x.shape[1]}")
+    topk = int(topk)
+    if state is None:
+        idx = torch.empty((Q, max(topk, 0)), dtype=torch.int64, device=dev)
+        scores = torch.empty((Q, max(topk, 0)), dtype=torch.float32, device=dev)
+    else:
+        idx = torch.as_tensor(state[0], dtype=torch.int64).to(dev).clone().contiguous()
+        scores = torch.as_tensor(state[1], dtype=torch.float32).to(dev).clone().contiguous()
+        if idx.shape != (Q, topk) or scores.shape != (Q, topk):
+            raise ValueError(f"state of shape {tuple(idx.shape)} / {tuple(scores.shape)} against Q {Q}, topk {topk}")
+    check(ctx.lib.rpr_flat_search(ctx.handle, q.data_ptr(), Q, d, x.data_ptr(), x.shape[0], int(row_base), topk, idx.data_ptr(),
+                                  scores.data_ptr(), 0 if state is None else 1, _stream_ptr(dev)), "rpr_flat_search")
+    return idx, scores

@@ -31,6 +31,7 @@ from .utils.utils import convert_ptsmtids_to_strsmtid, get_dataset_name
 
 QUERY_PREFIX = "query: "  # reference dataset/dataset.py:15
 AQ_EVALUATE_TOPK, AQ_EVALUATE_BATCH = 200, 128   # hard-coded in the reference's aq_evaluate (evaluate.py:302-332)
+RETRIEVE_BATCH = 128                             # hard-coded in the reference's retrieve (evaluate.py:240)
 
 
 class DocidTable:
@@ -718,6 +719,118 @@ def aq_evaluate(args):
     return evaluate(args)
 
 
+DENSE_DEFAULTS = dict(collection_path=None, max_length=256, index_retrieve_batch_size=256, encoder_type=None)
+
+
+def _dense_flag(args, name):
+    return getattr(args, name, DENSE_DEFAULTS[name])
+
+
+def _require(args, *flags):
+    """The refusal every task gives for a missing flag, before anything touches a device or a file."""
+    absent = [f for f in flags if not getattr(args, f, None)]
+    if absent:
+        raise ValueError(f"task: {args.task} is not valid without " + ", ".join("--" + f for f in absent))
+
+
+def _pretrain_encoder(args):
+    from .modeling.t5_generative_retriever import T5SeqPretrainEncoder
+    encoder_type = _dense_flag(args, "encoder_type")
+    if encoder_type not in (None, "t5seq_pretrain_encoder"):
+        raise ValueError(f"{encoder_type} is not valid.")
+    model = T5SeqPretrainEncoder.from_pretrained(args.pretrained_path)
+    model.eval()
+    return model
+
+
+def mmap(args):
+    """reference evaluate.py:669-671, 184-224 (``index`` with an index_dir that holds "mmap"): every rank embeds its share
+    of ``--collection_path`` into ``index_dir/embs_{rank}_{chunk}.npy`` + ``ids_{rank}_{chunk}.npy``, rank 0 writes
+    ``plan.json``; ``--task=mmap_2`` gathers them."""
+    _require(args, "pretrained_path", "collection_path", "index_dir")
+    import torch.distributed as dist
+    from transformers import AutoTokenizer
+    from .tasks.dense_indexer import embed_collection
+
+    if "mmap" not in args.index_dir:
+        raise ValueError(f'--index_dir {args.index_dir} must contain "mmap" for --task=mmap')
+    ddp_setup()
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    local_rank = max(0, int(args.local_rank if args.local_rank >= 0 else os.environ.get("LOCAL_RANK", 0)))
+    model = _pretrain_encoder(args)
+    model.to(_device_index(local_rank))
+    tokenizer = AutoTokenizer.from_pretrained(args.pretrained_path)
+    return embed_collection(model.base_model.engine_model(), tokenizer, args.collection_path, args.index_dir, rank, world,
+                            batch_size=_dense_flag(args, "index_retrieve_batch_size"), max_length=_dense_flag(args, "max_length"))
+
+
+def retrieve(args):
+    """reference evaluate.py:229-266: embeds every query collection and searches the gathered embeddings exactly
+    (``rpr_flat_search`` instead of faiss.IndexFlatIP), writes ``out_dir/<dataset>/run.json`` and evaluates."""
+    _require(args, "pretrained_path", "out_dir")
+    if not (args.mmap_dir or args.index_dir):
+        raise ValueError(f"task: {args.task} is not valid without --mmap_dir (or --index_dir)")
+    from transformers import AutoTokenizer
+    from .tasks.dense_indexer import FlatIndex, check_mmap, flat_search_index
+
+    mmap_dir = args.mmap_dir or args.index_dir
+    check_mmap(mmap_dir)   # before the checkpoint is read
+    model = _pretrain_encoder(args)
+    local_rank = max(0, int(args.local_rank if args.local_rank >= 0 else os.environ.get("LOCAL_RANK", 0)))
+    model.to(_device_index(local_rank))
+    tokenizer = AutoTokenizer.from_pretrained(args.pretrained_path)
+    index = FlatIndex(mmap_dir, model.base_model.engine_model().ctx.device)
+    os.makedirs(args.out_dir, exist_ok=True)
+    for data_dir in _list_flag(args.q_collection_paths):
+        coll = QueryCollection(data_dir)
+        out_dir = os.path.join(args.out_dir, get_dataset_name(data_dir))
+        print("out_dir: ", out_dir)
+        loader = query_batches(coll, tokenizer, list(range(len(coll))), RETRIEVE_BATCH, _dense_flag(args, "max_length"))
+        flat_search_index(model, loader, index, out_dir, args.topk)
+    return evaluate(args)
+
+
+def aq_to_flat_index_search_evaluate(args):
+    """reference evaluate.py:334-: the sanity check of a quantizer. Every docid's codes are decoded to the vector they stand
+    for (``T5AQEncoder.decode``: the sum of the levels' codewords in ascending order), the decoded matrix is searched exactly
+    for the top 200 of every query, ``run.json`` is written and evaluated."""
+    _require(args, "pretrained_path", "docid_to_smtid_path", "out_dir")
+    from transformers import AutoTokenizer
+    from . import engine as E
+    from .modeling.t5_generative_retriever import T5AQEncoder
+    from .tasks.dense_indexer import add_to_run
+
+    model = T5AQEncoder.from_pretrained(args.pretrained_path)
+    model.eval()
+    local_rank = max(0, int(args.local_rank if args.local_rank >= 0 else os.environ.get("LOCAL_RANK", 0)))
+    model.to(_device_index(local_rank))
+    em = model.base_model.engine_model()
+    with open(args.docid_to_smtid_path) as f:
+        docid_to_smtid = json.load(f)
+    docids = list(docid_to_smtid)
+    codes = torch.tensor([docid_to_smtid[i][1:] for i in docids], dtype=torch.long, device=em.ctx.device)   # [N, M]: the leading -1 dropped
+    sd = model.base_model.state_dict()
+    name = "list_decoder_embeds" if model.config.shared_output_input_embeds else "list_output_embeds"
+    X = None   # T5AQEncoder.decode on the device: the levels' codewords added in ascending order
+    for m in range(codes.shape[1]):
+        rows = sd[f"{name}.{m}.weight"].to(device=em.ctx.device, dtype=torch.float32)[codes[:, m]]
+        X = rows if X is None else X + rows
+    tokenizer = AutoTokenizer.from_pretrained(args.pretrained_path)
+    for data_dir in _list_flag(args.q_collection_paths):
+        coll = QueryCollection(data_dir)
+        out_dir = os.path.join(args.out_dir, get_dataset_name(data_dir))
+        run: Dict[str, Dict[str, float]] = {}
+        for batch in query_batches(coll, tokenizer, list(range(len(coll))), AQ_EVALUATE_BATCH, _dense_flag(args, "max_length")):
+            q = E.embed(em, batch["input_ids"], batch["attention_mask"])
+            idx, scores = E.flat_search(em.ctx, q, X, AQ_EVALUATE_TOPK)
+            add_to_run(run, batch["id"].tolist(), idx, scores, docids)
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "run.json"), "w") as f:
+            json.dump(run, f)
+    return evaluate(args)
+
+
 def get_args(argv=None):
     """EvalArguments fields used by the generative-retrieval branch (reference arguments.py:145-212)."""
     ap = argparse.ArgumentParser()
@@ -743,6 +856,12 @@ def get_args(argv=None):
     ap.add_argument("--train_query_dir", default=None)
     ap.add_argument("--mmap_dir", default=None)
     ap.add_argument("--index_dir", default=None)
+    # the dense tasks' flags (mmap / retrieve / aq_to_flat_index_search_evaluate; reference arguments.py): absent unless given, like
+    # --near_tie_guard, so the namespace of every other run is unchanged; DENSE_DEFAULTS holds the reference's defaults
+    ap.add_argument("--collection_path", default=argparse.SUPPRESS)
+    ap.add_argument("--max_length", type=int, default=argparse.SUPPRESS)
+    ap.add_argument("--index_retrieve_batch_size", type=int, default=argparse.SUPPRESS)
+    ap.add_argument("--encoder_type", default=argparse.SUPPRESS)
     ap.add_argument("--num_subvectors_for_pq", type=int, default=32)
     ap.add_argument("--codebook_bits", type=int, default=8)
     ap.add_argument("--apply_log_softmax_for_scores", type=lambda s: str(s).lower() in ("1", "true", "yes"),
@@ -772,6 +891,12 @@ def main(argv=None):
         aq_index(args)
     elif args.task == "aq_evaluate":
         aq_evaluate(args)
+    elif args.task == "mmap":
+        mmap(args)
+    elif args.task == "retrieve":
+        retrieve(args)
+    elif args.task == "aq_to_flat_index_search_evaluate":
+        aq_to_flat_index_search_evaluate(args)
     else:
         raise ValueError(f"task: {args.task} is not valid.")
 

@@ -265,6 +265,14 @@ class T5AQEncoder(T5SeqAQEncoder):
         return super().decode(text_encodings, summation=True)
 
 
+class T5SeqPretrainEncoder(T5SeqAQEncoder):
+    """reference :558-: the dense first-stage model (inference surface only). ``doc_encode`` and ``query_encode`` are the
+    same pass: the encoder plus one decoder position fed with the start embedding."""
+
+    def doc_encode(self, **inputs):
+        return self.query_encode(**inputs)
+
+
 class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
     """reference :902-966 — forward of the prefix-oriented ranking fine-tune step, same
     ``forward(**inputs)`` dict interface and return keys (``rank``, ``rank_4``, ``rank_8``, ``rank_16``). The whole

@@ -15,7 +15,15 @@ the timed region.
 times rpr_rq_search alone over seeded random codes: the first call (cold: scratch allocation, code objects)
 and the best and median of --repeats warm calls by device events, the code bytes per second it streams (one read of the
 code matrix per pass) and the LUT lookups per second it sustains (Q N M per pass), and as the yardstick on the same card
-a plain torch path: the LUT by matmul, per chunk of queries the level sum of LUT columns gathered by the codes, torch.topk."""
+a plain torch path: the LUT by matmul, per chunk of queries the level sum of LUT columns gathered by the codes, torch.topk.
+
+  python tools/rq_bench.py --flat --n 8841823 --d 768 --M 32 --K 256 --Q 128 --topks 200 1000
+
+times the exact search (FlatIndex.search -> rpr_flat_search) over the same synthetic embeddings held on the
+device in blocks of at most 4 GB: cold and warm by device events per topk, the fp32 rate of its 2 Q N d flops against the
+peak, and as the yardstick on the same card a plain torch path (torch.matmul per block, torch.topk, merge by a second
+topk). Then it trains greedy codebooks on the same embeddings, encodes them, and reports recall@10 / 100 / 200 of
+rpr_rq_search against the exact result."""
 import argparse
 import json
 import os
@@ -81,6 +89,71 @@ def search_leg(args, E):
     print(json.dumps(out), flush=True)
 
 
+def flat_leg(args, E):
+    from ripor_amd.tasks.dense_indexer import FLAT_BLOCK_BYTES, FlatIndex
+    ctx = E.Context.get(0)
+    N, d, M, K, Q = args.n, args.d, args.M, args.K, args.Q
+    g = torch.Generator(device="cuda").manual_seed(0)
+    scale = torch.linspace(0.25, 2.0, d, device="cuda")
+    rows = max(1, FLAT_BLOCK_BYTES // (d * 4))
+    blocks = []
+    for lo in range(0, N, rows):
+        xb = torch.empty((min(rows, N - lo), d), dtype=torch.float32, device="cuda")
+        for p in range(0, xb.shape[0], 1 << 20):
+            xb[p:p + (1 << 20)] = torch.randn((min(1 << 20, xb.shape[0] - p), d), generator=g, device="cuda") * scale
+        blocks.append((lo, xb))
+    q = torch.randn((Q, d), generator=g, device="cuda") * scale
+    index = FlatIndex.from_blocks(ctx, blocks)
+    torch.cuda.synchronize()
+    out = dict(metric="flat_search", n=N, d=d, Q=Q, blocks=len(blocks), scratch_bytes=E.FLAT_SCRATCH_BYTES)
+    exact = None
+    for topk in args.topks:
+        cold, _ = _timed(lambda: index.search(q, topk))
+        warm = []
+        for _ in range(max(3, args.repeats)):
+            t, (idx, sc) = _timed(lambda: index.search(q, topk))
+            warm.append(t)
+
+        def torch_path():
+            state = None
+            for lo, xb in blocks:
+                v, i = torch.topk(torch.matmul(q, xb.T), min(topk, xb.shape[0]), dim=1)
+                i = i + lo
+                if state is not None:
+                    v, i = torch.cat([state[0], v], dim=1), torch.cat([state[1], i], dim=1)
+                    v, o = torch.topk(v, min(topk, v.shape[1]), dim=1)
+                    i = i.gather(1, o)
+                state = (v, i)
+            return state
+
+        _timed(torch_path)   # warm-up of every shape
+        t_torch, (tv, ti) = min((_timed(torch_path) for _ in range(2)), key=lambda r: r[0])
+        best = min(warm)
+        tf = 2.0 * Q * N * d / best / 1e12
+        out[f"top{topk}"] = dict(cold_s=round(cold, 5), warm_s=round(best, 5), warm_median_s=round(sorted(warm)[len(warm) // 2], 5),
+                                 warm_s_all=[round(t, 5) for t in warm], queries_per_s=round(Q / best, 1), tflops=round(tf, 2),
+                                 frac_of_f32_peak=round(tf / PEAK_F32_TFLOPS, 3), torch_s=round(t_torch, 5),
+                                 torch_over_flat_search=round(t_torch / best, 3),
+                                 idx_equal_to_torch_frac=round(float((ti == idx).float().mean()), 6),
+                                 max_score_diff_to_torch=float((tv - sc).abs().max()))
+        if exact is None:
+            exact = idx
+    if args.recall:
+        S, init = E.rq_training_plan(N, M, K)
+        St = torch.from_numpy(S).cuda()
+        Xs = torch.cat([xb[St[(St >= lo) & (St < lo + xb.shape[0])] - lo] for lo, xb in blocks])
+        books, _ = E.rq_train(ctx, Xs, M, K, init, niter=args.niter)
+        del Xs
+        codes = np.concatenate([E.rq_encode(ctx, xb, books, chunk_rows=args.chunk_rows)[0] for _, xb in blocks])
+        ri, _ = E.rq_search(ctx, q, books, codes, max(200, args.topks[0]))
+        ri, ex = ri.cpu().numpy(), exact.cpu().numpy()
+        out["rq_search_recall_vs_exact"] = {f"recall@{k}": round(float(np.mean([len(set(ri[i, :k]) & set(ex[i, :k])) / k
+                                                                                  for i in range(Q)])), 4)
+                                             for k in (10, 100, 200) if k <= ex.shape[1]}
+        out["rq"] = dict(M=M, K=K, niter=args.niter, n_train=int(len(S)))
+    print(json.dumps(out), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8841823)
@@ -92,6 +165,9 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--beam", type=int, default=1, help="beam of the encode leg (1: greedy rpr_rq_encode; else rpr_rq_encode_beam)")
     ap.add_argument("--search", action="store_true", help="time rpr_rq_search instead of training / encoding")
+    ap.add_argument("--flat", action="store_true", help="time the exact search (rpr_flat_search) and the recall of rpr_rq_search against it")
+    ap.add_argument("--topks", type=int, nargs="+", default=[200, 1000], help="--flat: the topk values timed (recall uses the first)")
+    ap.add_argument("--recall", type=int, default=1, help="--flat: 0 skips the quantizer training and the recall figures")
     ap.add_argument("--Q", type=int, default=128)
     ap.add_argument("--topk", type=int, default=200)
     ap.add_argument("--torch_chunk", type=int, default=8, help="queries per chunk of the torch yardstick")
@@ -99,6 +175,8 @@ def main(argv=None):
     from ripor_amd import engine as E
     if args.search:
         return search_leg(args, E)
+    if args.flat:
+        return flat_leg(args, E)
 
     ctx = E.Context.get(0)
     N, d, M, K = args.n, args.d, args.M, args.K
