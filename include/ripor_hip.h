@@ -295,6 +295,24 @@ int64_t rpr_l0_table_bytes(const rpr_ctx* ctx, const rpr_model* model);
  * probability ~ out_frac[t]^B: the first fork is the first depth where that reaches 1/2, the second the first later
  * depth where fewer than 0.05 queries of the call are expected to stay unforced. */
 int rpr_trie_single_frac(const uint16_t* codes, int64_t N, int32_t Lc, int32_t L, double* out_frac);
+/* HOST ONLY: from the same pass, out_mean[t] (L + 1 doubles) = the mean over the depth-t nodes of (distinct L-token
+ * sequences under the node - 1): what a fork that takes queries with a few extra sequences along (rpr_set_tail_extras)
+ * has to carry per beam. Duplicated smtids count once. */
+int rpr_trie_extra_mean(const uint16_t* codes, int64_t N, int32_t Lc, int32_t L, double* out_mean);
+/* HOST ONLY: the fork depths the library derives from those two statistics (L + 1 doubles each) for a search of Q
+ * queries, B beams, L tokens under rpr_set_forced_tail mode `forced_tail` and rpr_set_tail_extras mode `tail_extras`;
+ * out_depths: 2 entries; *out_drop_last = 1 when no stage follows the last fork (optimistic mode). Returns the number of
+ * forks. Explicit depths (rpr_set_fork_depths) and the model's logit bound are not part of it. */
+int rpr_plan_forks(const double* single_frac, const double* extra_mean, int32_t Q, int32_t B, int32_t L, int32_t forced_tail,
+                   int32_t tail_extras, int32_t* out_depths, int32_t* out_drop_last);
+/* Forced with extras: at a fork, a query whose beams hold a few distinct sequences more than one each (at most n over all
+ * its beams) is forced as well — the extra sequences ride through the same tail pass in a spare entry and the remaining
+ * selection steps of the query are replayed on its B + extras candidates, pruning included. Results are those of the
+ * step-by-step loop. mode: -1 = automatic (default: searches with more than 4096 decoder rows and fewer than 32 beams,
+ * n = 4), 0 = off, 1..31 = always, with budget n (never with 32 beams or more, nor in rpr_search_margins). Part of the
+ * key of the captured graphs. */
+int rpr_set_tail_extras(rpr_ctx* ctx, int32_t mode);
+int32_t rpr_tail_extras(const rpr_ctx* ctx);
 /* Diagnostic (synchronises the device): for every fork of the last rpr_search its depth, the number of queries that
  * were forced there and the number that walked on; [host] arrays of 2 entries each; returns the number of forks. */
 int rpr_last_fork_stats(rpr_ctx* ctx, int32_t* out_depths, int32_t* out_forced, int32_t* out_left);

@@ -135,6 +135,11 @@ SIGNATURES = {
     "rpr_fork_depths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                                   C.POINTER(C.c_int32)]),
     "rpr_trie_single_frac": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "rpr_trie_extra_mean": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "rpr_plan_forks": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rpr_set_tail_extras": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rpr_tail_extras": (C.c_int32, [C.c_void_p]),
     "rpr_last_fork_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rpr_op_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int32, C.c_void_p]),

@@ -89,6 +89,79 @@ int refresh_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s) {
 
 }  // namespace rpr
 
+namespace rpr {
+
+namespace {
+// P(X > k) and E[max(0, X - k)] of X ~ Poisson(lam), summed term by term (the terms of interest are far below 1 - sum)
+double poisson_pmf(double lam, int i) { return lam > 0 ? std::exp(-lam + i * std::log(lam) - std::lgamma((double)i + 1.0)) : (i == 0 ? 1.0 : 0.0); }
+double poisson_tail(double lam, int k) {
+  if (lam <= 0) return 0.0;
+  if (lam > 4.0 * k + 50.0) return 1.0;
+  double s = 0;
+  const int n = k + 60 + (int)(lam + 12.0 * std::sqrt(lam));
+  for (int i = k + 1; i <= n; ++i) s += poisson_pmf(lam, i);
+  return s < 1.0 ? s : 1.0;
+}
+double poisson_excess(double lam, int k) {
+  if (lam <= 0) return 0.0;
+  if (lam > 4.0 * k + 50.0) return lam;            // (an upper bound: E[(X - k)+] <= E[X])
+  double s = 0;
+  const int n = k + 60 + (int)(lam + 12.0 * std::sqrt(lam));
+  for (int i = k + 1; i <= n; ++i) s += (double)(i - k) * poisson_pmf(lam, i);
+  return s;
+}
+}  // namespace
+
+// Fork depths from the trie statistics. f[t] = the share of the depth-t nodes under which one distinct sequence remains
+// (trie_single_frac): a query whose B beams sit on random depth-t nodes is forced with probability ~ f[t]^B. First fork:
+// the first depth where that reaches one half. Second fork: the first depth after it where fewer than 0.05 queries of the
+// call are expected to stay unforced, so that the last stage is almost always empty (a stage with a handful of live rows
+// still pays ~100 launches per step).
+// Expected number of queries a fork at depth t leaves behind, left(t):
+//   E = 0 (no extras):  Q * (1 - f[t]^B).
+//   E > 0 (the fork also takes queries with up to E extra sequences, each in one of `pool` spare tail entries): with
+//   mu[t] = the mean of (distinct sequences - 1) over the depth-t nodes (trie_single_frac's extra_mean), the extras of a
+//   query are taken as Poisson with mean lam = B * mu[t]; a query stays behind when it has more than E of them, or when it
+//   has some and the pool is empty — the queries that want a spare entry are Poisson with mean Q * (1 - exp(-lam)):
+//     left(t) = Q * P[Poisson(lam) > E] + E[max(0, Poisson(Q * (1 - exp(-lam))) - pool)].
+//   (1 - f <= mu, so the share without extras, exp(-lam), is never above f^B: the estimate of the queries that need a spare
+//   entry is on the high side. Nodes with very many sequences make the true tail heavier than Poisson's; the optimistic
+//   mode's leftover flag and the caller's back-off cover that.)
+std::vector<int> plan_forks(const double* f, const double* mu, int Q, int B, int L, int forced_tail, int E, int pool, bool* drop_last) {
+  std::vector<int> forks;
+  *drop_last = false;
+  auto p_forced = [&](int t) { return std::pow(f[t], (double)B); };
+  auto left = [&](int t) {
+    if (E <= 0) return (double)Q * (1.0 - p_forced(t));
+    const double lam = (double)B * mu[t];
+    return (double)Q * poisson_tail(lam, E) + poisson_excess((double)Q * (1.0 - std::exp(-lam)), pool);
+  };
+  int t0 = 0;
+  for (int t = 1; t <= L - 2 && !t0; ++t) if (p_forced(t) >= 0.5) t0 = t;
+  // a tail pass costs what its positions cost step by step minus the K/V gathering, plus a fork (~100 launches, two
+  // partly filled launches for the leftovers): with thousands of decoder rows in flight — steps bound by the matrix
+  // pipes — the plain loop is as fast below 8 remaining positions (measured at beam 100, len 8, 214 queries: 1890
+  // queries/s without forks, 1510 with). A few hundred rows (the reference's rank-data flags: beam 100, batch 4, len 8)
+  // are bound by the launch chain instead: a step of 12 layers costs 1.6 ms whatever it computes, the four remaining
+  // positions as ONE pass of 1600 rows cost as much as one and a half steps (round 6: 306 -> 378 queries/s)
+  const int min_tail = (int64_t)Q * B <= 4096 ? 2 : 8;
+  if (!t0 || L - t0 < min_tail) return forks;
+  forks.push_back(t0);
+  // Optimistic mode (rpr_set_forced_tail(ctx, 2)): when the statistics promise an (almost always) empty last stage, that
+  // stage is not enqueued at all — ~100 launches per step for nobody — and a query that is still unforced at the last
+  // fork raises RPR_STATUS_TAIL_LEFTOVER instead; the caller then repeats the batch in the exact mode (1).
+  // A handful of queries in flight, or a fork that takes the few queries with extras along: the first fork already leaves
+  // fewer than 0.05 queries behind in expectation, so the second fork (a compacted stage, its steps and a second tail pass:
+  // ~300 launches that almost always work on nothing, 2 of the 9.8 ms of a single-query search) is not enqueued either.
+  if (forced_tail == 2 && left(t0) <= 0.05) { *drop_last = true; return forks; }
+  for (int t = t0 + 1; t <= L - 2 && t <= t0 + 12; ++t)
+    if (left(t) <= 0.05) { forks.push_back(t); break; }
+  *drop_last = forced_tail == 2 && forks.size() == 2;
+  return forks;
+}
+
+}  // namespace rpr
+
 using namespace rpr;
 
 namespace {
@@ -444,6 +517,34 @@ int rpr_trie_single_frac(const uint16_t* codes, int64_t N, int32_t Lc, int32_t L
   return RPR_OK;
 }
 
+int rpr_trie_extra_mean(const uint16_t* codes, int64_t N, int32_t Lc, int32_t L, double* out_mean) {
+  RPR_REQUIRE(codes && out_mean, "NULL argument");
+  RPR_REQUIRE(N > 0 && N < ((int64_t)1 << 31) - 1 && Lc >= 1 && Lc <= 4096 && L >= 1 && L <= Lc, "N, Lc or L out of range");
+  try {
+    std::vector<uint16_t> sorted;
+    std::vector<int64_t> perm;
+    sort_codes(codes, N, Lc, sorted, perm);
+    std::vector<double> f, mu;
+    trie_single_frac(sorted.data(), N, Lc, L, f, &mu);
+    for (int t = 0; t <= L; ++t) out_mean[t] = mu[(size_t)t];
+  } catch (const std::exception& ex) {
+    set_error(std::string("rpr_trie_extra_mean: ") + ex.what());
+    return RPR_ERR_OOM;
+  }
+  return RPR_OK;
+}
+
+int rpr_plan_forks(const double* single_frac, const double* extra_mean, int32_t Q, int32_t B, int32_t L, int32_t forced_tail,
+                   int32_t tail_extras, int32_t* out_depths, int32_t* out_drop_last) {
+  RPR_REQUIRE(single_frac && extra_mean && out_depths && out_drop_last, "NULL argument");
+  RPR_REQUIRE(Q >= 1 && B >= 1 && L >= 1 && L < 256 && forced_tail >= 0 && forced_tail <= 2 && tail_extras >= -1, "argument out of range");
+  bool drop_last = false;
+  const std::vector<int> f = plan_forks(single_frac, extra_mean, Q, B, L, forced_tail, tail_extras_budget(tail_extras, Q, B, false), tail_extras_pool(Q), &drop_last);
+  for (size_t i = 0; i < f.size(); ++i) out_depths[i] = f[i];
+  *out_drop_last = drop_last ? 1 : 0;
+  return (int)f.size();
+}
+
 int rpr_trie_file_info(const char* path, int64_t* N, int32_t* L, int32_t* V, int64_t* key_bytes, int64_t* src_size,
                        int64_t* src_mtime_ns) {
   RPR_REQUIRE(path, "NULL argument");
@@ -597,11 +698,7 @@ bool ensure_lanes(rpr_ctx* c) {
 }
 
 // Fork depths of a search (ascending, at most MAX_FORKS; empty = every query walks all L steps). Explicit depths
-// (rpr_set_fork_depths / RPR_FORK_DEPTHS) win; otherwise they come from the trie: with f_t = the share of depth-t nodes
-// under which one distinct sequence remains (trie_single_frac), a query whose B beams sit on random depth-t nodes is
-// forced with probability ~ f_t^B. First fork: the first depth where that reaches one half; second fork: the first
-// depth after it where fewer than 0.05 queries of the call are expected to stay unforced, so that the last stage is
-// almost always empty (a stage with a handful of live rows still pays ~100 launches per step).
+// (rpr_set_fork_depths / RPR_FORK_DEPTHS) win; otherwise they come from the trie (plan_forks below).
 std::vector<int> choose_forks(rpr_ctx* c, const rpr_model* m, rpr_trie* tr, int Q, int B, int L, unsigned flags, bool taps,
                               bool* drop_last) {
   std::vector<int> forks;
@@ -620,34 +717,13 @@ std::vector<int> choose_forks(rpr_ctx* c, const rpr_model* m, rpr_trie* tr, int 
   }
   auto it = tr->single_frac.find(L);
   if (it == tr->single_frac.end()) {
-    std::vector<double> f;
-    trie_single_frac(tr->host_sorted.data(), tr->N, tr->L, L, f);
+    std::vector<double> f, mu;
+    trie_single_frac(tr->host_sorted.data(), tr->N, tr->L, L, f, &mu);
     it = tr->single_frac.emplace(L, std::move(f)).first;
+    tr->extra_mean[L] = std::move(mu);
   }
-  const std::vector<double>& f = it->second;
-  auto p_forced = [&](int t) { return std::pow(f[(size_t)t], (double)B); };
-  int t0 = 0;
-  for (int t = 1; t <= L - 2 && !t0; ++t) if (p_forced(t) >= 0.5) t0 = t;
-  // a tail pass costs what its positions cost step by step minus the K/V gathering, plus a fork (~100 launches, two
-  // partly filled launches for the leftovers): with thousands of decoder rows in flight — steps bound by the matrix
-  // pipes — the plain loop is as fast below 8 remaining positions (measured at beam 100, len 8, 214 queries: 1890
-  // queries/s without forks, 1510 with). A few hundred rows (the reference's rank-data flags: beam 100, batch 4, len 8)
-  // are bound by the launch chain instead: a step of 12 layers costs 1.6 ms whatever it computes, the four remaining
-  // positions as ONE pass of 1600 rows cost as much as one and a half steps (round 6: 306 -> 378 queries/s)
-  const int min_tail = (int64_t)Q * B <= 4096 ? 2 : 8;
-  if (!t0 || L - t0 < min_tail) return forks;
-  forks.push_back(t0);
-  // Optimistic mode (rpr_set_forced_tail(ctx, 2)): when the statistics promise an (almost always) empty last stage, that
-  // stage is not enqueued at all — ~100 launches per step for nobody — and a query that is still unforced at the last
-  // fork raises RPR_STATUS_TAIL_LEFTOVER instead; the caller then repeats the batch in the exact mode (1).
-  // A handful of queries in flight: the first fork already leaves fewer than 0.05 queries behind in expectation, so the
-  // second fork (a compacted stage, its steps and a second tail pass: ~300 launches that almost always work on nothing,
-  // 2 of the 9.8 ms of a single-query search) is not enqueued either.
-  if (c->forced_tail == 2 && (double)Q * (1.0 - p_forced(t0)) <= 0.05) { *drop_last = true; return forks; }
-  for (int t = t0 + 1; t <= L - 2 && t <= t0 + 12; ++t)
-    if ((double)Q * (1.0 - p_forced(t)) <= 0.05) { forks.push_back(t); break; }
-  *drop_last = c->forced_tail == 2 && forks.size() == 2;
-  return forks;
+  const int E = tail_extras_budget(c->tail_extras, Q, B, c->cur_margins != 0);
+  return plan_forks(it->second.data(), tr->extra_mean[L].data(), Q, B, L, c->forced_tail, E, E > 0 ? tail_extras_pool(Q) : 0, drop_last);
 }
 
 int pack_forks(const std::vector<int>& forks, bool drop_last) {
@@ -688,8 +764,9 @@ int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
     const unsigned dbg = (env_int("RPR_TAIL_RANK_REPLAY", 0) ? 1u : 0u) | ((unsigned)(env_int("RPR_SELECT_RADIX", -1) + 1) << 1);
     const unsigned l0 = m->l0_ready(c) ? (unsigned)c->l0_mode : 0u;   // whether the capture reads the layer-0 Q/K/V table
     const unsigned mg = c->cur_margins ? 1u : 0u;                     // whether every selection is followed by the margin kernel
+    const int ex = tail_extras_budget(c->tail_extras, Q, B, c->cur_margins != 0);   // extra sequences a forced query may carry (< 32)
     GraphKey key{m, tr, Q, Lq, B, L, flags | ((unsigned)c->precision << 16) | (dbg << 20) | (l0 << 24) | (mg << 28), lane,
-                 pack_forks(forks, drop_last)};
+                 pack_forks(forks, drop_last) | (ex << 24)};
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
       hipGraph_t graph = nullptr;
@@ -819,6 +896,13 @@ int rpr_set_l0_table(rpr_ctx* c, int32_t mode) {
 }
 int64_t rpr_l0_table_bytes(const rpr_ctx* c, const rpr_model* m) { return c && m && m->l0_ready(c) ? (int64_t)m->l0_bytes() : 0; }
 
+int rpr_set_tail_extras(rpr_ctx* c, int32_t mode) {
+  RPR_REQUIRE(c && mode >= -1 && mode <= 31, "mode must be -1 (automatic), 0 (off) or a budget of 1..31 extra sequences per query");
+  c->tail_extras = mode;
+  return RPR_OK;
+}
+int32_t rpr_tail_extras(const rpr_ctx* c) { return c ? c->tail_extras : -1; }
+
 int rpr_set_forced_tail(rpr_ctx* c, int32_t mode) {
   RPR_REQUIRE(c && mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (exact) or 2 (optimistic)");
   c->forced_tail = mode;
@@ -856,7 +940,7 @@ int rpr_last_fork_stats(rpr_ctx* c, int32_t* out_depths, int32_t* out_forced, in
     for (int i = 0; i < 3; ++i) {
       if (!(c->last_ws_mask & (1 << i)) || !wss[i]->tail[k].cnt.p || !wss[i]->stage[k].cnt.p) continue;
       int32_t a = 0, b = 0;
-      RPR_HIP(hipMemcpy(&a, wss[i]->tail[k].cnt.p, 4, hipMemcpyDeviceToHost));
+      RPR_HIP(hipMemcpy(&a, static_cast<const char*>(wss[i]->tail[k].cnt.p) + 12, 4, hipMemcpyDeviceToHost));   // forced queries (cnt[0] counts their spare entries too)
       RPR_HIP(hipMemcpy(&b, wss[i]->stage[k].cnt.p, 4, hipMemcpyDeviceToHost));
       out_forced[k] += a; out_left[k] += b;
     }

@@ -550,13 +550,31 @@ struct ForkArgs {
   int Qcap; const int* nq_dev;   // stage capacity / live queries (nullable = Qcap)
   int B, T, L;
   double spread_max;         // forced only if max - min of the query's beam scores is below this (see passes.hip: enqueue_fork)
-  int32_t* flag;             // out [Qcap]: 1 = forced
+  int32_t* flag;             // out [Qcap]: 0 = not forced, 1 + extras = forced (extras <= E)
+  int E = 0;                 // forced with extras: over its beams a query may hold up to E distinct sequences more than one each
 };
 hipError_t launch_fork_classify(const ForkArgs& a, hipStream_t s);
-// exclusive scans of the flags: forced queries -> flist / tail_cnt {queries, sequences = x B, rows = x B x (L-T), 0},
-// the others -> src (source stage query of every query of the next stage) / next_cnt {queries, rows = x B, 0, 0}
-hipError_t launch_fork_scan(const int32_t* flag, int Qcap, const int* nq_dev, int B, int Lt, int32_t* flist, int32_t* tail_cnt,
-                            int32_t* src, int32_t* next_cnt, hipStream_t s);
+// Forced with extras. A query whose beams hold n_b >= 1 distinct sequences over the columns T..L-1 with extras = sum(n_b - 1)
+// in 1..E leaves at the fork too: its own tail entry carries the first sequence of every beam, as always, and one SPARE
+// entry (from a pool of `pool` per stage, handed out in query order; none left = not forced) carries the extra sequences
+// in its slots 0..extras-1, each with its parent beam's tokens, ancestry and score. The spare entry is the virtual stage
+// query Qcap + k behind the stage's beam state (the buffers hold Qcap + pool queries); it reads its owner's caches, mask
+// and encoder rows (kvq). tail_rank_kernel replays the remaining selection steps of such a query on its B + extras
+// candidates, pruning included.
+// spare: [Qcap] own entry -> spare entry k or -1 | [1] spare entries in use | [pool] owner (stage query) of spare k |
+//        [pool * B] parent beam of slot s of spare k (-1 = filler slot, results ignored)
+struct ForkScanArgs {
+  const int32_t* flag; int Qcap; const int* nq_dev; int B, Lt;
+  int32_t* flist;            // [Qcap + pool] tail entry -> stage query (own entries in query order, then the spare entries in use)
+  int32_t* tail_cnt;         // {entries, sequences = x B, rows = x B x (L-T), forced queries = own entries}
+  int32_t* src; int32_t* next_cnt;   // the others -> src (source stage query of every query of the next stage) / {queries, rows = x B, 0, 0}
+  int32_t* kvq;              // [Qcap + pool] tail entry -> the stage query whose caches / inputs it reads
+  int32_t* spare; int pool;
+};
+hipError_t launch_fork_scan(const ForkScanArgs& a, hipStream_t s);
+// the virtual queries of the spare entries in use: beam state rows (Qcap + k) * B + s and spare's parent table
+struct ForkExtrasArgs { BeamState st; const uint16_t* codes; int Lc; int Qcap, B, T, L, pool; int32_t* spare; };
+hipError_t launch_fork_extras(const ForkExtrasArgs& a, hipStream_t s);
 struct StageIO {             // per-query inputs of a stage (all indexed by the stage's query index)
   const int32_t* qmap;       // nullable = identity: query of the call
   const int32_t* offs;       // nullable = q * Lq: first encoder row
@@ -600,6 +618,7 @@ struct TailSelfAttnArgs {
   float* out; __half* out_h; size_t o_ps; unsigned int* sat;
   int nseq_cap, B, H, T, L;
   int dkv = 0;               // head dim (0 = 64); 128 (t5-3b) takes the VALU kernel tail_self_attn_kernel<128>
+  const int32_t* kvq = nullptr;   // tail query -> the stage query whose cache it reads (null = flist: no spare entries)
 };
 hipError_t launch_tail_self_attn(const TailSelfAttnArgs& a, hipStream_t s);
 // cross-attention of the tail rows (a.B = rows per query): fp32-MFMA tiles for Lq <= 64, else the block kernel
@@ -621,6 +640,10 @@ struct TailRankArgs {
   int Qcap, B, T, L;
   int32_t* out_tokens; float* out_scores; int64_t* out_lo; int64_t* out_hi;
   int replay = 0;            // 1: always replay the L - T steps (RPR_TAIL_RANK_REPLAY=1; the tie path, for tests)
+  // forced with extras (pool > 0): nf_dev counts the own entries, spare entry k is tail entry *nf_dev + k and the virtual
+  // stage query Qcap + k; the code matrix, for the row range of a surviving sequence
+  const int32_t* spare = nullptr; int pool = 0;
+  const uint16_t* codes = nullptr; int Lc = 0;
 };
 hipError_t launch_tail_rank(const TailRankArgs& a, hipStream_t s);
 // max over the rows of |E[r] (*) w|_2 (w nullable): bound of the logits after the final RMSNorm (model load)

@@ -107,6 +107,7 @@ struct rpr_trie {
   std::vector<uint16_t> host_sorted;
   std::string keys;           // docid strings in original row order, '\n'-joined (only when loaded from a file that has them)
   std::map<int, std::vector<double>> single_frac;   // per search length L: trie_single_frac (lazily, first search of that length)
+  std::map<int, std::vector<double>> extra_mean;    //   and its extra_mean, from the same pass
   ~rpr_trie() { if (codes) (void)hipFree(codes); free_levels(); }
 };
 
@@ -135,9 +136,13 @@ struct StageBufs {
   DevBuf score[2], lo[2], hi[2], tokens[2], anc[2];
 };
 // ... and the queries that leave at that fork: their remaining positions are scored in one teacher-forced pass
+// cap = the stage's queries + the spare entries of the queries forced with extras (tail_extras_pool; 0 when the search has none)
 struct TailBufs {
-  DevBuf flag, flist;       // int32 [cap]: forced?, tail query -> stage query
-  DevBuf cnt;               // int32 [4]: forced queries, sequences (x B), rows (x B x (L - T))
+  DevBuf flag, flist;       // int32 [cap]: forced? (1 + extras), tail entry -> stage query (a spare entry: the virtual query cap_q + k)
+  DevBuf cnt;               // int32 [4]: entries, sequences (x B), rows (x B x (L - T)), forced queries (= entries - spare entries in use)
+  DevBuf kvq;               // int32 [cap]: tail entry -> the stage query whose caches, mask and encoder rows it reads (a spare entry: its owner)
+  DevBuf spare;             // int32 [cap_q + 1 + pool + pool * B]: own entry -> spare entry index or -1 | spare entries in use |
+                            //   owner of spare k | parent beam of slot s of spare k (-1 = filler)
   DevBuf qmap, offs, last, mask;
   DevBuf tokens;            // uint16 [cap * B][L]
   DevBuf gold;              // float [cap * B][L - T]
@@ -213,6 +218,7 @@ struct rpr_ctx {
   int forced_tail = 1;          // 0 = every query runs all L steps sequentially, 1 = exact forced tail, 2 = optimistic (see choose_forks)
   int fork_override[MAX_FORKS] = {0, 0};   // explicit fork depths (rpr_set_fork_depths / RPR_FORK_DEPTHS); 0 = from the trie statistics
   int n_fork_override = -1;     // -1 = automatic
+  int tail_extras = -1;         // rpr_set_tail_extras: -1 = automatic (tail_extras_budget), 0 = off, n > 0 = always, up to n extra sequences per query
   std::vector<int> last_forks;  // fork depths of the last rpr_search and the workspaces it ran in (bit 0: ctx, 1 / 2: lanes)
   int last_ws_mask = 0;         //   -> rpr_last_fork_stats
   size_t ws_bytes = 0;
@@ -237,6 +243,22 @@ struct rpr_ctx {
 inline bool rpr_model::l0_ready(const rpr_ctx* c) const { return c->l0_mode > 0 && l0_table && l0_valid && l0_epoch == c->l0_epoch; }
 
 namespace rpr {
+
+// Forced with extras (common.h: ForkArgs::E): how many extra sequences a forced query may carry into the tail pass, and how
+// many spare tail entries a stage keeps for such queries. Automatic mode: stages with more than 4096 decoder rows (the
+// threshold of choose_forks for "steps bound by the matrix pipes": there a leftover stage costs two partly filled launches
+// per GEMM) and fewer than 32 beams (the one-block selection; with more beams extras are the rule and a spare entry of B
+// slots per query is the wrong layout). Never with the pruning margins: a query with extras is still pruned inside the tail.
+constexpr int TAIL_EXTRAS_AUTO = 4;
+inline int tail_extras_budget(int mode, int Q, int B, bool margins) {
+  if (mode == 0 || B >= 32 || margins) return 0;
+  if (mode > 0) return mode < B ? mode : B;
+  return (int64_t)Q * B > 4096 ? (TAIL_EXTRAS_AUTO < B ? TAIL_EXTRAS_AUTO : B) : 0;
+}
+inline int tail_extras_pool(int Q) { return Q / 32 < 4 ? 4 : (Q / 32 > 64 ? 64 : Q / 32); }
+// fork depths from the trie statistics (api.hip; rpr_plan_forks exposes it to the host tests)
+std::vector<int> plan_forks(const double* single_frac, const double* extra_mean, int Q, int B, int L, int forced_tail, int E, int pool,
+                            bool* drop_last);
 
 // re-split every GEMM weight into its f16 planes (api.hip); sets model->f32_only if a weight no longer fits
 int refresh_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s);

@@ -67,6 +67,9 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
   const size_t T = (size_t)Q * Lq, R = (size_t)Q * B, inner = m->inner(), dm = d.d_model, dff = d.d_ff;
   const size_t nd = d.num_decoder_layers, ne = d.num_layers, f = sizeof(float);
   Workspace& w = c->ws;
+  // forced with extras: `pool` spare tail entries per fork = virtual queries behind the beam state of the stage (internal.h)
+  const size_t pool = !forks.empty() && tail_extras_budget(c->tail_extras, Q, B, c->cur_margins != 0) > 0 ? (size_t)tail_extras_pool(Q) : 0;
+  const size_t Qt = (size_t)Q + pool, Rv = Qt * B;
   int e = 0;
   auto E = [&](DevBuf& b, size_t bytes) { if (!e) e = ensure(c, b, bytes); };
   E(w.ids, T * 4); E(w.mask, T * 4); E(w.last, (size_t)Q * 4); E(w.offs, ((size_t)Q + 1) * 4); E(w.row_src, T * 4);
@@ -79,8 +82,8 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
   E(w.lb, R * (size_t)m->Vp() * 4 * 2);   // start and end of every child's row range
   if (select_radix_wanted(B, m->Vp())) E(w.sel_rs, select_radix_ws_bytes(Q, B, m->Vp()));
   for (int i = 0; i < 2; ++i) {
-    E(w.score[i], R * 8); E(w.lo[i], R * 4); E(w.hi[i], R * 4);
-    E(w.tokens[i], R * (size_t)L * 2); E(w.anc[i], R * (size_t)L * 2);
+    E(w.score[i], Rv * 8); E(w.lo[i], Rv * 4); E(w.hi[i], Rv * 4);
+    E(w.tokens[i], Rv * (size_t)L * 2); E(w.anc[i], Rv * (size_t)L * 2);
   }
   E(w.o_tokens, R * (size_t)L * 4); E(w.o_scores, R * 4); E(w.o_lo, R * 8); E(w.o_hi, R * 8);
   if (c->cur_margins) { E(w.mg_valid, R * (size_t)m->Vp() / 8); E(w.o_margin, (size_t)Q * 8); }
@@ -99,17 +102,18 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
       E(sb.qmap, (size_t)Q * 4); E(sb.offs, (size_t)Q * 4); E(sb.last, (size_t)Q * 4); E(sb.mask, T * 4);
       E(sb.kcache, nd * depth * R * inner * f); E(sb.vcache, nd * depth * R * inner * f);
       for (int i = 0; i < 2; ++i) {
-        E(sb.score[i], R * 8); E(sb.lo[i], R * 4); E(sb.hi[i], R * 4);
-        E(sb.tokens[i], R * (size_t)L * 2); E(sb.anc[i], R * (size_t)L * 2);
+        E(sb.score[i], Rv * 8); E(sb.lo[i], Rv * 4); E(sb.hi[i], Rv * 4);
+        E(sb.tokens[i], Rv * (size_t)L * 2); E(sb.anc[i], Rv * (size_t)L * 2);
       }
     }
     TailBufs& tb = w.tail[k];
-    E(tb.flag, (size_t)Q * 4); E(tb.flist, (size_t)Q * 4); E(tb.cnt, 16);
-    E(tb.qmap, (size_t)Q * 4); E(tb.offs, (size_t)Q * 4); E(tb.last, (size_t)Q * 4); E(tb.mask, T * 4);
-    E(tb.tokens, R * (size_t)L * 2); E(tb.gold, R * Lt * f);
+    E(tb.flag, (size_t)Q * 4); E(tb.flist, Qt * 4); E(tb.cnt, 16);
+    E(tb.kvq, Qt * 4); E(tb.spare, ((size_t)Q + 1 + pool + pool * B) * 4);
+    E(tb.qmap, Qt * 4); E(tb.offs, Qt * 4); E(tb.last, Qt * 4); E(tb.mask, Qt * Lq * 4);
+    E(tb.tokens, Rv * (size_t)L * 2); E(tb.gold, Rv * Lt * f);
   }
   if (!forks.empty()) {
-    const size_t Rt = R * (size_t)(L - forks[0]);
+    const size_t Rt = Rv * (size_t)(L - forks[0]);
     E(w.t_qkv, Rt * 3 * inner * f); E(w.t_q, Rt * inner * f);
     if (c->precision == RPR_PREC_F16X2 && !m->f32_only) {
       E(w.t_x_h, Rt * dm * hb); E(w.t_attn_h, Rt * inner * hb); E(w.t_ff_h, Rt * dff * hb); E(w.t_ssq, (3 * nd + 1) * Rt * 8);
@@ -453,19 +457,24 @@ StageView enqueue_fork(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_t
   // Log-softmax scores: a step adds a log-probability in [-(2*bound + ln V), 0] instead of a logit in [-bound, bound].
   const double per_step = (sd.flags & RPR_FLAG_LOG_SOFTMAX) ? 2.0 * (double)m->logit_bound + log((double)d.V) : 2.0 * (double)m->logit_bound;
   const double spread_max = 1e8 - (double)(L - T) * per_step;
-  ForkArgs fa{st, tr->codes, tr->L, Q, sv.nq_dev, B, T, L, spread_max, P<int32_t>(tb.flag)};
+  // forced with extras (common.h: ForkScanArgs): the budget per query and the stage's spare tail entries
+  const int extras = tail_extras_budget(c->tail_extras, sd.Q, B, c->cur_margins != 0), pool = extras > 0 ? tail_extras_pool(sd.Q) : 0;
+  ForkArgs fa{st, tr->codes, tr->L, Q, sv.nq_dev, B, T, L, spread_max, P<int32_t>(tb.flag), extras};
   Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_fork_classify(fa, s); });
-  Ln.run(RPR_K_FORK, 0, 0, [&] {
-    return launch_fork_scan(P<int32_t>(tb.flag), Q, sv.nq_dev, B, L - T, P<int32_t>(tb.flist), P<int32_t>(tb.cnt), P<int32_t>(nb.src),
-                            P<int32_t>(nb.cnt), s);
-  });
-  // tail job: per-query inputs and the full token rows of the forced beams
+  const ForkScanArgs fs{P<int32_t>(tb.flag), Q, sv.nq_dev, B, L - T, P<int32_t>(tb.flist), P<int32_t>(tb.cnt), P<int32_t>(nb.src),
+                        P<int32_t>(nb.cnt), P<int32_t>(tb.kvq), P<int32_t>(tb.spare), pool};
+  Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_fork_scan(fs, s); });
+  if (pool > 0) {
+    const ForkExtrasArgs fe{st, tr->codes, tr->L, Q, B, T, L, pool, P<int32_t>(tb.spare)};
+    Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_fork_extras(fe, s); });
+  }
+  // tail job: per-entry inputs (a spare entry: its owner's) and the full token rows of the forced beams
   Ln.run(RPR_K_FORK, 0, 0, [&] {
     return launch_gather_stage_io(sv.io, StageOut{P<int32_t>(tb.qmap), P<int32_t>(tb.offs), P<int32_t>(tb.last), P<int32_t>(tb.mask)},
-                                  P<int32_t>(tb.flist), P<int>(tb.cnt), Q, Lq, s);
+                                  P<int32_t>(tb.kvq), P<int>(tb.cnt), Q + pool, Lq, s);
   });
   Ln.run(RPR_K_FORK, 0, 0, [&] {
-    return launch_tail_tokens(st, tr->codes, tr->L, P<int32_t>(tb.flist), P<int>(tb.cnt), Q, B, T, L, P<uint16_t>(tb.tokens), s);
+    return launch_tail_tokens(st, tr->codes, tr->L, P<int32_t>(tb.flist), P<int>(tb.cnt), Q + pool, B, T, L, P<uint16_t>(tb.tokens), s);
   });
   // next stage
   StageView nv{};
@@ -494,10 +503,13 @@ StageView enqueue_fork(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_t
 // through the beams' ancestry and the positions >= T from this pass's own K/V rows; the B*(L-T) rows of a query share
 // its encoder K/V in cross-attention; instead of V logits per row only the logit of the row's (only valid) token is
 // computed, in exact fp32 (tail_gold_kernel).
-void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const SearchDims& sd, const StageView& sv, int T, TailBufs& tb) {
+void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchDims& sd, const StageView& sv, int T,
+                  TailBufs& tb) {
   const auto& d = m->d;
   Workspace& w = c->ws;
-  const int Q = sv.Qcap, B = sd.B, L = sd.L, Lq = sd.Lq, Lt = L - T, S = Q * B, R = S * Lt;
+  const int pool = tail_extras_budget(c->tail_extras, sd.Q, sd.B, c->cur_margins != 0) > 0 ? tail_extras_pool(sd.Q) : 0;
+  const int Q = sv.Qcap + pool;   // tail entries: the stage's queries and the spare entries of those forced with extras
+  const int B = sd.B, L = sd.L, Lq = sd.Lq, Lt = L - T, S = Q * B, R = S * Lt;
   const int inner = m->inner(), dm = d.d_model, H = d.num_heads, nd = d.num_decoder_layers, V = d.V, xld = sd.xld;
   hipStream_t s = Ln.s;
   const int* nf_dev = P<int>(tb.cnt);
@@ -525,6 +537,7 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const SearchDims
                          sv.st[T & 1].anc, L, P<int32_t>(tb.flist), nseq_dev, d.dec_rel_bias, m->dec_bucket, p.attn,
                          p.attn_planes(), p.ps_i, c->status, S, B, H, T, L};
       a.dkv = d.d_kv;
+      a.kvq = P<int32_t>(tb.kvq);
       Ln.run(RPR_K_TAIL_SELF_ATTN, 2.0 * Ra * H * (double)(L + T + 1) * sv.dkv, 4.0 * ((double)Ra * 4 * inner + 2.0 * (Ra / Lt) * (double)T * inner),
              [&] { return launch_tail_self_attn(a, s); });
     }
@@ -567,8 +580,9 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const SearchDims
                               p.post, s, p.x_planes(), p.xs.ps);
     });
   }
-  TailRankArgs ra{sv.st[T & 1], P<int32_t>(tb.flist), P<int32_t>(tb.qmap), nf_dev, P<uint16_t>(tb.tokens), P<float>(tb.gold), Q, B, T, L,
+  TailRankArgs ra{sv.st[T & 1], P<int32_t>(tb.flist), P<int32_t>(tb.qmap), nf_dev + 3, P<uint16_t>(tb.tokens), P<float>(tb.gold), sv.Qcap, B, T, L,
                   P<int32_t>(w.o_tokens), P<float>(w.o_scores), P<int64_t>(w.o_lo), P<int64_t>(w.o_hi)};
+  ra.spare = P<int32_t>(tb.spare); ra.pool = pool; ra.codes = tr->codes; ra.Lc = tr->L;
   Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_tail_rank(ra, s); });
   Ln.account_live(nullptr, 0);
 }
@@ -637,7 +651,7 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
       const int next_depth = k + 1 < forks.size() ? forks[k + 1] : L;
       const bool last_dropped = drop_last && k + 1 == forks.size();
       const StageView nv = enqueue_fork(Ln, c, m, tr, sd, sv, t1, next_depth, w.tail[k], w.stage[k], !last_dropped);
-      enqueue_tail(Ln, c, m, sd, sv, t1, w.tail[k]);
+      enqueue_tail(Ln, c, m, tr, sd, sv, t1, w.tail[k]);
       if (last_dropped) return;   // every query was finished by a tail pass (or flagged)
       sv = nv;
     }

@@ -20,11 +20,30 @@ namespace rpr {
 // One wave per stage query. forced <=> every beam is live (non-empty trie range), its range holds one distinct
 // sequence over the columns T..L-1 (first row == last row there: the rows are sorted), and the spread of the beam
 // scores is small enough that B valid continuations stay above every masked candidate for all remaining steps.
+// Rows [r, hi) are sorted and share the columns [0, T): the first row behind r that differs from row r in the columns
+// [T, L), or hi — the end of the run of r's sequence (duplicated smtids: many rows, one sequence).
+__device__ inline int seq_run_end(const uint16_t* __restrict__ codes, int Lc, int r, int hi, int T, int L) {
+  const uint16_t* a = codes + (size_t)r * Lc;
+  int lo = r + 1;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    const uint16_t* m = codes + (size_t)mid * Lc;
+    bool same = true;
+    for (int p = T; p < L; ++p)
+      if (a[p] != m[p]) { same = false; break; }
+    if (same) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// a.E > 0: a beam whose range holds several sequences does not fail the query by itself; the sequences beyond the first are
+// counted (one binary search per sequence, given up beyond E + 1) and the query is forced with 1..E of them over all beams.
 __global__ __launch_bounds__(256) void fork_classify_kernel(ForkArgs a) {
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (q >= a.Qcap || (a.nq_dev && q >= *a.nq_dev)) return;
   const int r0 = q * a.B;
   bool ok = true;
+  int extras = 0;
   double smin = INFINITY, smax = -INFINITY;
   for (int b = lane; b < a.B; b += 64) {
     const int lo = a.st.lo[r0 + b], hi = a.st.hi[r0 + b];
@@ -34,8 +53,15 @@ __global__ __launch_bounds__(256) void fork_classify_kernel(ForkArgs a) {
     if (hi - lo > 1) {
       const uint16_t* first = a.codes + (size_t)lo * a.Lc;
       const uint16_t* last = a.codes + (size_t)(hi - 1) * a.Lc;
+      bool one = true;
       for (int p = a.T; p < a.L; ++p)
-        if (first[p] != last[p]) { ok = false; break; }
+        if (first[p] != last[p]) { one = false; break; }
+      if (!one) {
+        if (a.E <= 0) { ok = false; continue; }
+        int n = 0;
+        for (int r = lo; r < hi && n <= a.E + 1; ++n) r = seq_run_end(a.codes, a.Lc, r, hi, a.T, a.L);
+        extras += n - 1;
+      }
     }
   }
 #pragma unroll
@@ -43,8 +69,12 @@ __global__ __launch_bounds__(256) void fork_classify_kernel(ForkArgs a) {
     smin = fmin(smin, __shfl_xor(smin, o, 64));
     smax = fmax(smax, __shfl_xor(smax, o, 64));
   }
-  const bool all_ok = __all(ok);
-  if (lane == 0) a.flag[q] = (all_ok && (smax - smin) < a.spread_max) ? 1 : 0;   // NaN scores compare false: not forced
+  if (a.E > 0) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) extras += __shfl_xor(extras, o, 64);
+  }
+  const bool all_ok = __all(ok) && extras <= a.E;
+  if (lane == 0) a.flag[q] = (all_ok && (smax - smin) < a.spread_max) ? 1 + extras : 0;   // NaN scores compare false: not forced
 }
 
 hipError_t launch_fork_classify(const ForkArgs& a, hipStream_t s) {
@@ -53,45 +83,115 @@ hipError_t launch_fork_classify(const ForkArgs& a, hipStream_t s) {
 }
 
 // One block: the two lists in query order (forced -> flist, the others -> src) and the live counts of the tail pass
-// and of the next stage.
-__global__ __launch_bounds__(1024) void fork_scan_kernel(const int32_t* __restrict__ flag, int Qcap, const int* __restrict__ nq_dev,
-                                                          int B, int Lt, int32_t* __restrict__ flist, int32_t* __restrict__ tail_cnt,
-                                                          int32_t* __restrict__ src, int32_t* __restrict__ next_cnt) {
+// and of the next stage. pool > 0: the queries flagged with extras take the spare entries in query order first (a query
+// that finds the pool empty is not forced), and the spare entries in use follow the own entries in flist.
+__device__ inline void block_scan_1024(int* part, int tid) {   // Hillis-Steele inclusive scan of part[0..1023]
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int add = tid >= o ? part[tid - o] : 0;
+    __syncthreads();
+    part[tid] += add;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(1024) void fork_scan_kernel(ForkScanArgs a) {
   __shared__ int part[1024];
-  __shared__ int carry;
-  const int tid = threadIdx.x;
-  const int n = nq_dev ? min(*nq_dev, Qcap) : Qcap;
-  if (tid == 0) carry = 0;
+  __shared__ int carry, carry_x;
+  const int tid = threadIdx.x, Qcap = a.Qcap;
+  const int n = a.nq_dev ? min(*a.nq_dev, Qcap) : Qcap;
+  int32_t* sp_of = a.spare;
+  int32_t* owner = a.spare + Qcap + 1;
+  if (tid == 0) { carry = 0; carry_x = 0; }
   __syncthreads();
   for (int q0 = 0; q0 < n; q0 += 1024) {
     const int q = q0 + tid;
-    const int v = (q < n && flag[q] != 0) ? 1 : 0;
-    part[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {          // Hillis-Steele inclusive scan
-      const int add = tid >= o ? part[tid - o] : 0;
+    const int fl = q < n ? a.flag[q] : 0;
+    int k = -1;                                      // spare entry of q
+    if (a.pool > 0) {                                // (block-uniform)
+      const int x = fl > 1 ? 1 : 0;
+      part[tid] = x;
+      block_scan_1024(part, tid);
+      const int kx = carry_x + part[tid] - x;
+      if (x && kx < a.pool) k = kx;
       __syncthreads();
-      part[tid] += add;
+      if (tid == 1023) carry_x += part[1023];
       __syncthreads();
     }
+    const int v = (fl == 1 || k >= 0) ? 1 : 0;
+    part[tid] = v;
+    block_scan_1024(part, tid);
     if (q < n) {
       const int nf_before = carry + part[tid] - v;   // forced queries before q
-      if (v) flist[nf_before] = q; else src[q - nf_before] = q;
+      if (v) {
+        a.flist[nf_before] = q; a.kvq[nf_before] = q; sp_of[nf_before] = k;
+        if (k >= 0) owner[k] = q;
+      } else {
+        a.src[q - nf_before] = q;
+      }
     }
     __syncthreads();
     if (tid == 1023) carry += part[1023];
     __syncthreads();
   }
+  const int nf = carry, used = min(carry_x, a.pool);
+  for (int k = tid; k < used; k += 1024) { a.flist[nf + k] = Qcap + k; a.kvq[nf + k] = owner[k]; }
   if (tid == 0) {
-    const int nf = carry, nu = n - carry;
-    tail_cnt[0] = nf; tail_cnt[1] = nf * B; tail_cnt[2] = nf * B * Lt; tail_cnt[3] = 0;
-    next_cnt[0] = nu; next_cnt[1] = nu * B; next_cnt[2] = 0; next_cnt[3] = 0;
+    const int ne = nf + used, nu = n - nf;
+    a.tail_cnt[0] = ne; a.tail_cnt[1] = ne * a.B; a.tail_cnt[2] = ne * a.B * a.Lt; a.tail_cnt[3] = nf;
+    a.next_cnt[0] = nu; a.next_cnt[1] = nu * a.B; a.next_cnt[2] = 0; a.next_cnt[3] = 0;
+    a.spare[Qcap] = used;
   }
 }
 
-hipError_t launch_fork_scan(const int32_t* flag, int Qcap, const int* nq_dev, int B, int Lt, int32_t* flist, int32_t* tail_cnt,
-                            int32_t* src, int32_t* next_cnt, hipStream_t s) {
-  hipLaunchKernelGGL(fork_scan_kernel, dim3(1), dim3(1024), 0, s, flag, Qcap, nq_dev, B, Lt, flist, tail_cnt, src, next_cnt);
+hipError_t launch_fork_scan(const ForkScanArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(fork_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
+// One block per spare entry in use: the extra sequences of its owner in (beam, row) order become the slots of the virtual
+// query Qcap + k — parent beam's score, tokens and ancestry of the positions < T, the sequence's own row range; the
+// remaining slots are copies of the owner's beam 0 (computed like any sequence, ignored by the ranking).
+__global__ __launch_bounds__(64) void fork_extras_kernel(ForkExtrasArgs a) {
+  const int k = blockIdx.x, tid = threadIdx.x, B = a.B, T = a.T;
+  if (k >= a.spare[a.Qcap]) return;
+  __shared__ int pb[32], plo[32], phi[32];
+  const int q = a.spare[a.Qcap + 1 + k];
+  const size_t r0 = (size_t)q * B, v0 = (size_t)(a.Qcap + k) * B;
+  int32_t* parent = a.spare + a.Qcap + 1 + a.pool + (size_t)k * B;
+  if (tid == 0) {
+    int s = 0;
+    for (int b = 0; b < B && s < B; ++b) {
+      const int lo = a.st.lo[r0 + b], hi = a.st.hi[r0 + b];
+      if (lo >= hi) continue;
+      for (int r = seq_run_end(a.codes, a.Lc, lo, hi, T, a.L); r < hi && s < B; ++s) {
+        const int e = seq_run_end(a.codes, a.Lc, r, hi, T, a.L);
+        pb[s] = b; plo[s] = r; phi[s] = e;
+        r = e;
+      }
+    }
+    for (; s < B; ++s) { pb[s] = -1; plo[s] = a.st.lo[r0]; phi[s] = a.st.hi[r0]; }
+  }
+  __syncthreads();
+  for (int s = tid; s < B; s += 64) {
+    const size_t src = r0 + (pb[s] > 0 ? pb[s] : 0);
+    a.st.score[v0 + s] = a.st.score[src];
+    a.st.lo[v0 + s] = plo[s];
+    a.st.hi[v0 + s] = phi[s];
+    parent[s] = pb[s];
+  }
+  for (int i = tid; i < B * T; i += 64) {
+    const int s = i / T, p = i - s * T;
+    const size_t src = r0 + (pb[s] > 0 ? pb[s] : 0);
+    a.st.tokens[(v0 + s) * a.st.ld + p] = a.st.tokens[src * a.st.ld + p];
+    a.st.anc[(v0 + s) * a.st.ld + p] = a.st.anc[src * a.st.ld + p];
+  }
+}
+
+hipError_t launch_fork_extras(const ForkExtrasArgs& a, hipStream_t s) {
+  if (a.pool <= 0) return hipSuccess;
+  if (a.B > 32) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fork_extras_kernel, dim3(a.pool), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -245,7 +345,7 @@ __global__ __launch_bounds__(256) void tail_self_attn_kernel(TailSelfAttnArgs a)
   const int fi = seq / a.B, b = seq - fi * a.B;
   const int qi = a.flist[fi];
   const uint16_t* ancr = a.anc + ((size_t)qi * a.B + b) * a.anc_ld;
-  const size_t cbase = (size_t)qi * a.q_stride + (size_t)h * a.h_stride;
+  const size_t cbase = (size_t)(a.kvq ? a.kvq[fi] : qi) * a.q_stride + (size_t)h * a.h_stride;
   const float* tbase = a.qkv + (size_t)seq * Lt * ld + h * D;
   for (int i = tid; i < L * (D / 4); i += 256) {
     const int j = i / (D / 4), c = (i - j * (D / 4)) * 4;
@@ -437,7 +537,7 @@ __global__ __launch_bounds__(256, OCC) void tail_self_attn_mfma_kernel(TailSelfA
   const int fi = seq / a.B, b = seq - fi * a.B;
   const int qi = a.flist[fi];
   const uint16_t* ancr = a.anc + ((size_t)qi * a.B + b) * a.anc_ld;
-  const size_t cbase = (size_t)qi * a.q_stride + (size_t)h * a.h_stride;
+  const size_t cbase = (size_t)(a.kvq ? a.kvq[fi] : qi) * a.q_stride + (size_t)h * a.h_stride;
   const float* tbase = a.qkv + (size_t)seq * Lt * ld + h * DKV;
   {  // V rows -> LDS, four coalesced 256-B rows per instruction; rows past L are zero (0 * garbage must stay 0)
     const int g = lane >> 4, li = lane & 15;
@@ -715,8 +815,9 @@ __global__ __launch_bounds__(256, OCC) void tail_self_attn_mfma_v2_kernel(TailSe
   const int fi = udiv_magic((unsigned)seq, a.B, b_magic), b = seq - fi * a.B;
   const int qi = a.flist[fi];
   const uint16_t* ancr = a.anc + ((size_t)qi * a.B + b) * a.anc_ld;
-  const float* kc = a.kcache + (size_t)qi * a.q_stride + (size_t)h * a.h_stride;
-  const float* vc = a.vcache + (size_t)qi * a.q_stride + (size_t)h * a.h_stride;
+  const int qc = a.kvq ? a.kvq[fi] : qi;
+  const float* kc = a.kcache + (size_t)qc * a.q_stride + (size_t)h * a.h_stride;
+  const float* vc = a.vcache + (size_t)qc * a.q_stride + (size_t)h * a.h_stride;
   const float* tbase = a.qkv + (size_t)seq * Lt * ld + h * DKV;
   const int kk_end = L > 24 ? 16 : L > 16 ? 12 : L > 8 ? 8 : 4;   // key slots kk >= kk_end hold keys >= L in both halves
   float4 kreg[8], qreg[8];
@@ -1492,6 +1593,97 @@ hipError_t launch_tail_logprob(const float* logits, const uint16_t* tokens, floa
   return hipGetLastError();
 }
 
+// A query forced with extras (own entry i, spare entry k): the reference's loop (generation.py:453-503, :532-540) on its
+// B + extras enumerated candidates. Candidate c < B = the first sequence of beam c (tail sequence i * B + c), candidate
+// B + s = slot s of the spare entry (parent beam parent[s]). At step t every current slot expands into the distinct next
+// tokens of its surviving members; a group of members with the same token is one candidate of the step, scored with its
+// lowest-index member's logit (members that share a prefix share its logits): ((double)gold + 0.0) + slot score. The
+// candidates are ranked by (score desc, slot * V + token asc), the first B become the new slots in that order and the
+// members of the others are dropped. Every slot keeps at least one member, so at least B candidates exist at every step.
+// Then finalize's rule on the B survivors. One block; a thread per candidate (at most 2 B <= 62).
+__device__ void tail_rank_extras(const TailRankArgs& a, int i, int k) {
+  constexpr int CM = 64;
+  __shared__ double S[2][32], sc[CM];
+  __shared__ int slot[CM], lead[CM], flat[CM], nslot[CM], cseq[CM], alive[CM], orank[CM];
+  const int tid = threadIdx.x, nt = blockDim.x, B = a.B, T = a.T, L = a.L, Lt = L - T, C = 2 * B;
+  const int q = a.flist[i], es = *a.nf_dev + k;
+  const size_t r0 = (size_t)q * B, v0 = (size_t)(a.Qcap + k) * B;
+  const int32_t* parent = a.spare + a.Qcap + 1 + a.pool + (size_t)k * B;
+  if (tid < C) {
+    const int pb = tid < B ? tid : parent[tid - B];
+    alive[tid] = pb >= 0;
+    slot[tid] = pb >= 0 ? pb : 0;
+    cseq[tid] = tid < B ? i * B + tid : es * B + (tid - B);
+    orank[tid] = -1;
+  }
+  if (tid < B) S[0][tid] = a.st.score[r0 + tid];
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < Lt; ++t) {
+    const int p = T + t;
+    if (tid < C && alive[tid]) {
+      const int tok = a.tokens[(size_t)cseq[tid] * L + p], j = slot[tid];
+      int ld = tid;
+      for (int c = 0; c < tid; ++c)
+        if (alive[c] && slot[c] == j && a.tokens[(size_t)cseq[c] * L + p] == tok) { ld = c; break; }
+      lead[tid] = ld;
+      if (ld == tid) {
+        sc[tid] = ((double)a.gold[(size_t)cseq[tid] * Lt + t] + 0.0) + S[cur][j];
+        flat[tid] = j * 65536 + tok;                       // (tokens are 16 bits: the order of slot * V + token)
+      }
+    }
+    __syncthreads();
+    if (tid < C && alive[tid] && lead[tid] == tid) {
+      const double s = sc[tid];
+      const int fl = flat[tid];
+      int rk = 0;
+      for (int c = 0; c < C; ++c) rk += (alive[c] && lead[c] == c) && (sc[c] > s || (sc[c] == s && flat[c] < fl));
+      nslot[tid] = rk < B ? rk : -1;
+      if (rk < B) S[cur ^ 1][rk] = s;
+    }
+    __syncthreads();
+    if (tid < C && alive[tid]) {
+      const int ns = nslot[lead[tid]];
+      if (ns < 0) alive[tid] = 0; else slot[tid] = ns;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (tid < C && alive[tid]) {
+    bool first = true;                                     // (distinct sequences never share a slot at the end)
+    for (int c = 0; c < tid; ++c) first = first && !(alive[c] && slot[c] == slot[tid]);
+    if (first) {
+      const int pb = slot[tid];
+      const double s = S[cur][pb] / (double)(L + 1);
+      int rk = 0;
+      for (int c = 0; c < C; ++c) {
+        if (!alive[c] || c == tid) continue;
+        const double o = S[cur][slot[c]] / (double)(L + 1);
+        rk += (o > s) || (o == s && slot[c] > pb);
+      }
+      if (rk < B) {
+        const size_t o = (size_t)a.qmap[i] * B + rk;
+        orank[tid] = rk;
+        a.out_scores[o] = (float)s;
+        if (tid < B) {
+          const int lo = a.st.lo[r0 + tid];
+          a.out_lo[o] = lo;
+          a.out_hi[o] = seq_run_end(a.codes, a.Lc, lo, a.st.hi[r0 + tid], T, L);
+        } else {
+          a.out_lo[o] = a.st.lo[v0 + tid - B];
+          a.out_hi[o] = a.st.hi[v0 + tid - B];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const size_t o0 = (size_t)a.qmap[i] * B;
+  for (int x = tid; x < C * L; x += nt) {
+    const int c = x / L, p = x - c * L;
+    if (orank[c] >= 0) a.out_tokens[(o0 + orank[c]) * L + p] = (int32_t)a.tokens[(size_t)cseq[c] * L + p];
+  }
+}
+
 // One block per forced query: replay of the remaining L - T selection steps and the finalize step on the B forced
 // candidates. Per step the B winners are the beams' single valid children; new slot order = (cumulative score desc,
 // parent slot asc) — the sort order of the sequential select_kernel restricted to those candidates. Then
@@ -1503,6 +1695,7 @@ __global__ __launch_bounds__(1024) void tail_rank_kernel(TailRankArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int i = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   if (i >= *a.nf_dev) return;
+  if (a.pool > 0 && a.spare[i] >= 0) { tail_rank_extras(a, i, a.spare[i]); return; }   // block-uniform
   const int B = a.B, T = a.T, L = a.L, Lt = L - T;
   double* S = reinterpret_cast<double*>(smem_raw);       // [B] cumulative score of the beam that started in slot b
   int* pos = reinterpret_cast<int*>(S + B);              // [B] its current slot
@@ -1573,6 +1766,7 @@ hipError_t launch_tail_rank(const TailRankArgs& a_in, hipStream_t s) {
   const int replay = rp ? atoi(rp) : 0;
   TailRankArgs a = a_in;
   if (replay) a.replay = 1;
+  if (a.pool > 0 && (a.B >= 32 || !a.spare || !a.codes)) return hipErrorInvalidValue;
   const size_t smem = (size_t)a.B * (sizeof(double) + 2 * sizeof(int)) + 16;
   hipLaunchKernelGGL(tail_rank_kernel, dim3(a.Qcap), dim3(a.B > 256 ? 1024 : 256), smem, s, a);
   return hipGetLastError();

@@ -102,7 +102,10 @@ int sort_codes(const uint16_t* codes, int64_t N, int L, std::vector<uint16_t>& s
 // c_i = min(lcp(row i-1, row i), L); the rows between two boundaries with c < L are one distinct sequence ("run");
 // with a / b the c of its left / right boundary (-1 at the ends of the matrix) the run opens a new node at every
 // depth t > a and is alone in its node at every depth t > max(a, b).
-void trie_single_frac(const uint16_t* sorted, int64_t N, int Lc, int L, std::vector<double>& frac) {
+// extra_mean (nullable): extra_mean[t] = the mean over the depth-t nodes of (distinct L-token sequences under the node - 1)
+// = (runs - nodes at depth t) / nodes at depth t — what a fork at depth t that also accepts beams with a few sequences
+// left (tail_kernels.hip: forced with extras) has to carry per beam on average.
+void trie_single_frac(const uint16_t* sorted, int64_t N, int Lc, int L, std::vector<double>& frac, std::vector<double>* extra_mean) {
   std::vector<int64_t> nodes((size_t)L + 2, 0), single((size_t)L + 2, 0);   // histograms over a + 1 and max(a, b) + 1
   int a = -1;
   for (int64_t i = 1; i <= N; ++i) {
@@ -119,11 +122,15 @@ void trie_single_frac(const uint16_t* sorted, int64_t N, int Lc, int L, std::vec
     a = c;
   }
   frac.assign((size_t)L + 1, 0.0);
+  if (extra_mean) extra_mean->assign((size_t)L + 1, 0.0);
+  int64_t runs = 0;
+  for (int t = 0; t <= L + 1; ++t) runs += nodes[(size_t)t];
   int64_t n = 0, s = 0;
   for (int t = 0; t <= L; ++t) {                 // nodes at depth t: runs with a < t; single: runs with max(a, b) < t
     n += nodes[(size_t)t];
     s += single[(size_t)t];
     frac[(size_t)t] = n ? (double)s / (double)n : 0.0;
+    if (extra_mean) (*extra_mean)[(size_t)t] = n ? (double)(runs - n) / (double)n : 0.0;
   }
 }
 

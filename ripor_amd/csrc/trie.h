@@ -10,7 +10,8 @@ int save_trie_file(const char* path, const std::vector<uint16_t>& sorted, const 
 int load_trie_file(const char* path, std::vector<uint16_t>& sorted, std::vector<int64_t>& perm, int64_t& N, int& L,
                    int& V, std::string& keys, std::string& err);
 // forced-tail statistics: frac[t] = share of the depth-t trie nodes that hold a single distinct L-token sequence
-void trie_single_frac(const uint16_t* sorted, int64_t N, int Lc, int L, std::vector<double>& frac);
+void trie_single_frac(const uint16_t* sorted, int64_t N, int Lc, int L, std::vector<double>& frac,
+                      std::vector<double>* extra_mean = nullptr);
 // Child arrays of the trie (the selection kernels read a node's children from them instead of probing the code matrix):
 //   lvl0[c]            first sorted row whose code 0 is >= c            (V + 1 entries, lvl0[V] = N)
 //   lvl1[c0 * V + c1]  first row >= (c0, c1)                            (V * V + 1 entries; only for V <= 1024, L >= 2)

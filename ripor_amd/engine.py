@@ -81,6 +81,14 @@ class Context:
         """Size of the model's layer-0 Q/K/V table if the next search may read it, else 0."""
         return int(self.lib.rpr_l0_table_bytes(self.handle, model.handle))
 
+    def set_tail_extras(self, mode: int):
+        """Forced with extras (``rpr_set_tail_extras``): -1 = automatic (library default: more than 4096 decoder rows and
+        fewer than 32 beams), 0 = off, n > 0 = always, with a budget of n extra sequences per query."""
+        check(self.lib.rpr_set_tail_extras(self.handle, int(mode)), "rpr_set_tail_extras")
+
+    def tail_extras(self) -> int:
+        return int(self.lib.rpr_tail_extras(self.handle))
+
     def set_forced_tail(self, mode):
         """Forced-tail evaluation (``rpr_set_forced_tail``): queries whose beams can no longer be pruned leave the
         step-by-step loop at a fork and get their remaining positions scored in one teacher-forced pass.
@@ -266,6 +274,32 @@ def trie_single_frac(codes: np.ndarray, L: Optional[int] = None) -> np.ndarray:
     out = (C.c_double * (L + 1))()
     check(lib.rpr_trie_single_frac(codes.ctypes.data_as(C.c_void_p), N, Lc, L, out), "rpr_trie_single_frac")
     return np.asarray(list(out), dtype=np.float64)
+
+
+def trie_extra_mean(codes: np.ndarray, L: Optional[int] = None) -> np.ndarray:
+    """``out[t]`` = mean over the depth-t trie nodes of (distinct L-token sequences under the node - 1), host only
+    (``rpr_trie_extra_mean``) — the statistic behind the fork depths of a search that forces queries with extras."""
+    lib = _lib.load()
+    codes = np.ascontiguousarray(codes, dtype=np.uint16)
+    N, Lc = codes.shape
+    L = Lc if L is None else int(L)
+    out = (C.c_double * (L + 1))()
+    check(lib.rpr_trie_extra_mean(codes.ctypes.data_as(C.c_void_p), N, Lc, L, out), "rpr_trie_extra_mean")
+    return np.array(out[:], dtype=np.float64)
+
+
+def plan_forks(single_frac: np.ndarray, extra_mean: np.ndarray, Q: int, B: int, L: int, forced_tail: int = 1,
+               tail_extras: int = -1):
+    """The fork depths the library derives from the two trie statistics, host only (``rpr_plan_forks``): ``(depths,
+    drop_last)``."""
+    lib = _lib.load()
+    f = (C.c_double * (L + 1))(*[float(x) for x in single_frac[:L + 1]])
+    mu = (C.c_double * (L + 1))(*[float(x) for x in extra_mean[:L + 1]])
+    depths, drop = (C.c_int32 * 2)(), C.c_int32(0)
+    n = int(lib.rpr_plan_forks(f, mu, int(Q), int(B), int(L), int(forced_tail), int(tail_extras), depths, C.byref(drop)))
+    if n < 0:
+        check(n, "rpr_plan_forks")
+    return [int(depths[i]) for i in range(n)], bool(drop.value)
 
 
 def trie_file_info(path: str) -> dict:
