@@ -1,5 +1,5 @@
 // C-ABI of libripor_hip.so (see include/ripor_hip.h): context, model binding, trie, test hooks, profiling, and the
-// driver of one constrained beam search: fork depths, workspace, the two lanes of a large batch, and the capture of
+// driver of one constrained beam search: its plan (search_plan.h), workspace, the two lanes of a large batch, and the capture of
 // what passes.hip enqueues (T5 encoder once + L KV-cached decoder steps, each fused with the trie mask / top-B / beam
 // expand) on one HIP stream, replayed as a hipGraph (no host synchronisation inside the search; the reference syncs
 // >= 1 + 2*B*Q times per step).
@@ -80,84 +80,9 @@ int refresh_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s) {
   if (e) return e;
   if (lb != m->logit_bound) {
     m->logit_bound = lb;
-    for (auto it = c->graphs.begin(); it != c->graphs.end();) {
-      if (it->first.m == m) { (void)hipGraphExecDestroy(it->second); it = c->graphs.erase(it); } else ++it;
-    }
+    drop_graphs(c, [m](const GraphKey& k) { return k.m == m; });
   }
   return RPR_OK;
-}
-
-}  // namespace rpr
-
-namespace rpr {
-
-namespace {
-// P(X > k) and E[max(0, X - k)] of X ~ Poisson(lam), summed term by term (the terms of interest are far below 1 - sum)
-double poisson_pmf(double lam, int i) { return lam > 0 ? std::exp(-lam + i * std::log(lam) - std::lgamma((double)i + 1.0)) : (i == 0 ? 1.0 : 0.0); }
-double poisson_tail(double lam, int k) {
-  if (lam <= 0) return 0.0;
-  if (lam > 4.0 * k + 50.0) return 1.0;
-  double s = 0;
-  const int n = k + 60 + (int)(lam + 12.0 * std::sqrt(lam));
-  for (int i = k + 1; i <= n; ++i) s += poisson_pmf(lam, i);
-  return s < 1.0 ? s : 1.0;
-}
-double poisson_excess(double lam, int k) {
-  if (lam <= 0) return 0.0;
-  if (lam > 4.0 * k + 50.0) return lam;            // (an upper bound: E[(X - k)+] <= E[X])
-  double s = 0;
-  const int n = k + 60 + (int)(lam + 12.0 * std::sqrt(lam));
-  for (int i = k + 1; i <= n; ++i) s += (double)(i - k) * poisson_pmf(lam, i);
-  return s;
-}
-}  // namespace
-
-// Fork depths from the trie statistics. f[t] = the share of the depth-t nodes under which one distinct sequence remains
-// (trie_single_frac): a query whose B beams sit on random depth-t nodes is forced with probability ~ f[t]^B. First fork:
-// the first depth where that reaches one half. Second fork: the first depth after it where fewer than 0.05 queries of the
-// call are expected to stay unforced, so that the last stage is almost always empty (a stage with a handful of live rows
-// still pays ~100 launches per step).
-// Expected number of queries a fork at depth t leaves behind, left(t):
-//   E = 0 (no extras):  Q * (1 - f[t]^B).
-//   E > 0 (the fork also takes queries with up to E extra sequences, each in one of `pool` spare tail entries): with
-//   mu[t] = the mean of (distinct sequences - 1) over the depth-t nodes (trie_single_frac's extra_mean), the extras of a
-//   query are taken as Poisson with mean lam = B * mu[t]; a query stays behind when it has more than E of them, or when it
-//   has some and the pool is empty — the queries that want a spare entry are Poisson with mean Q * (1 - exp(-lam)):
-//     left(t) = Q * P[Poisson(lam) > E] + E[max(0, Poisson(Q * (1 - exp(-lam))) - pool)].
-//   (1 - f <= mu, so the share without extras, exp(-lam), is never above f^B: the estimate of the queries that need a spare
-//   entry is on the high side. Nodes with very many sequences make the true tail heavier than Poisson's; the optimistic
-//   mode's leftover flag and the caller's back-off cover that.)
-std::vector<int> plan_forks(const double* f, const double* mu, int Q, int B, int L, int forced_tail, int E, int pool, bool* drop_last) {
-  std::vector<int> forks;
-  *drop_last = false;
-  auto p_forced = [&](int t) { return std::pow(f[t], (double)B); };
-  auto left = [&](int t) {
-    if (E <= 0) return (double)Q * (1.0 - p_forced(t));
-    const double lam = (double)B * mu[t];
-    return (double)Q * poisson_tail(lam, E) + poisson_excess((double)Q * (1.0 - std::exp(-lam)), pool);
-  };
-  int t0 = 0;
-  for (int t = 1; t <= L - 2 && !t0; ++t) if (p_forced(t) >= 0.5) t0 = t;
-  // a tail pass costs what its positions cost step by step minus the K/V gathering, plus a fork (~100 launches, two
-  // partly filled launches for the leftovers): with thousands of decoder rows in flight — steps bound by the matrix
-  // pipes — the plain loop is as fast below 8 remaining positions (measured at beam 100, len 8, 214 queries: 1890
-  // queries/s without forks, 1510 with). A few hundred rows (the reference's rank-data flags: beam 100, batch 4, len 8)
-  // are bound by the launch chain instead: a step of 12 layers costs 1.6 ms whatever it computes, the four remaining
-  // positions as ONE pass of 1600 rows cost as much as one and a half steps (round 6: 306 -> 378 queries/s)
-  const int min_tail = (int64_t)Q * B <= 4096 ? 2 : 8;
-  if (!t0 || L - t0 < min_tail) return forks;
-  forks.push_back(t0);
-  // Optimistic mode (rpr_set_forced_tail(ctx, 2)): when the statistics promise an (almost always) empty last stage, that
-  // stage is not enqueued at all — ~100 launches per step for nobody — and a query that is still unforced at the last
-  // fork raises RPR_STATUS_TAIL_LEFTOVER instead; the caller then repeats the batch in the exact mode (1).
-  // A handful of queries in flight, or a fork that takes the few queries with extras along: the first fork already leaves
-  // fewer than 0.05 queries behind in expectation, so the second fork (a compacted stage, its steps and a second tail pass:
-  // ~300 launches that almost always work on nothing, 2 of the 9.8 ms of a single-query search) is not enqueued either.
-  if (forced_tail == 2 && left(t0) <= 0.05) { *drop_last = true; return forks; }
-  for (int t = t0 + 1; t <= L - 2 && t <= t0 + 12; ++t)
-    if (left(t) <= 0.05) { forks.push_back(t); break; }
-  *drop_last = forced_tail == 2 && forks.size() == 2;
-  return forks;
 }
 
 }  // namespace rpr
@@ -166,15 +91,11 @@ using namespace rpr;
 
 namespace {
 
-// Precision of what one call enqueues, restored on every return path: bf16 is a training-GEMM mode (scores need
-// fp32-equivalent arithmetic), and a model whose weights do not fit the f16 planes runs on the exact-fp32 kernels
-// whatever the ctx setting
+// Precision of what one call enqueues (effective_precision, or the plan's), restored on every return path
 struct PrecGuard {
   rpr_ctx* c; int saved;
-  PrecGuard(rpr_ctx* c_, const rpr_model* m) : c(c_), saved(c_->precision) {
-    if (c->precision == RPR_PREC_BF16) c->precision = RPR_PREC_F16X2;
-    if (m && m->f32_only) c->precision = RPR_PREC_F32;
-  }
+  PrecGuard(rpr_ctx* c_, int prec) : c(c_), saved(c_->precision) { c->precision = prec; }
+  PrecGuard(rpr_ctx* c_, const rpr_model* m) : PrecGuard(c_, effective_precision(c_->precision, m && m->f32_only)) {}
   ~PrecGuard() { c->precision = saved; }
 };
 
@@ -261,7 +182,7 @@ void rpr_free_ctx(rpr_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.second);
+  drop_graphs(c, [](const GraphKey&) { return true; });
   auto free_ws = [](Workspace& w) {   // a Workspace is nothing but DevBufs (static_assert in internal.h)
     DevBuf* all = reinterpret_cast<DevBuf*>(&w);
     for (size_t i = 0; i < sizeof(Workspace) / sizeof(DevBuf); ++i) if (all[i].p) (void)hipFree(all[i].p);
@@ -398,10 +319,7 @@ void rpr_free_model(rpr_model* m) {
   if (!m) return;
   (void)hipSetDevice(m->ctx->device);
   (void)hipDeviceSynchronize();
-  // graphs that reference this model's tables are dropped
-  for (auto it = m->ctx->graphs.begin(); it != m->ctx->graphs.end();) {
-    if (it->first.m == m) { (void)hipGraphExecDestroy(it->second); it = m->ctx->graphs.erase(it); } else ++it;
-  }
+  drop_graphs(m->ctx, [m](const GraphKey& k) { return k.m == m; });   // graphs that reference this model's tables
   train_forget_model(m->ctx, m);
   delete m;
 }
@@ -459,9 +377,7 @@ void rpr_free_trie(rpr_trie* t) {
   if (!t) return;
   (void)hipSetDevice(t->ctx->device);
   (void)hipDeviceSynchronize();
-  for (auto it = t->ctx->graphs.begin(); it != t->ctx->graphs.end();) {
-    if (it->first.t == t) { (void)hipGraphExecDestroy(it->second); it = t->ctx->graphs.erase(it); } else ++it;
-  }
+  drop_graphs(t->ctx, [t](const GraphKey& k) { return k.t == t; });
   delete t;
 }
 
@@ -539,10 +455,11 @@ int rpr_plan_forks(const double* single_frac, const double* extra_mean, int32_t 
   RPR_REQUIRE(single_frac && extra_mean && out_depths && out_drop_last, "NULL argument");
   RPR_REQUIRE(Q >= 1 && B >= 1 && L >= 1 && L < 256 && forced_tail >= 0 && forced_tail <= 2 && tail_extras >= -1, "argument out of range");
   bool drop_last = false;
-  const std::vector<int> f = plan_forks(single_frac, extra_mean, Q, B, L, forced_tail, tail_extras_budget(tail_extras, Q, B, false), tail_extras_pool(Q), &drop_last);
-  for (size_t i = 0; i < f.size(); ++i) out_depths[i] = f[i];
+  int forks[MAX_FORKS];
+  const int n = plan_forks(single_frac, extra_mean, Q, B, L, forced_tail, tail_extras_budget(tail_extras, Q, B, false), tail_extras_pool(Q), forks, &drop_last);
+  for (int i = 0; i < n; ++i) out_depths[i] = forks[i];
   *out_drop_last = drop_last ? 1 : 0;
-  return (int)f.size();
+  return n;
 }
 
 int rpr_trie_file_info(const char* path, int64_t* N, int32_t* L, int32_t* V, int64_t* key_bytes, int64_t* src_size,
@@ -622,9 +539,7 @@ int rpr_trie_set_vocab(rpr_trie* t, int32_t V) {
   // tables are dropped with them)
   RPR_HIP(hipSetDevice(t->ctx->device));
   RPR_HIP(hipDeviceSynchronize());
-  for (auto it = t->ctx->graphs.begin(); it != t->ctx->graphs.end();) {
-    if (it->first.t == t) { (void)hipGraphExecDestroy(it->second); it = t->ctx->graphs.erase(it); } else ++it;
-  }
+  drop_graphs(t->ctx, [t](const GraphKey& k) { return k.t == t; });
   return upload_levels(t);
 }
 
@@ -697,82 +612,62 @@ bool ensure_lanes(rpr_ctx* c) {
   return true;
 }
 
-// Fork depths of a search (ascending, at most MAX_FORKS; empty = every query walks all L steps). Explicit depths
-// (rpr_set_fork_depths / RPR_FORK_DEPTHS) win; otherwise they come from the trie (plan_forks below).
-std::vector<int> choose_forks(rpr_ctx* c, const rpr_model* m, rpr_trie* tr, int Q, int B, int L, unsigned flags, bool taps,
-                              bool* drop_last) {
-  std::vector<int> forks;
-  *drop_last = false;
-  if (!c->forced_tail || taps || L < 3 || !std::isfinite(m->logit_bound)) return forks;
-  const double per_step = 2.0 * (double)m->logit_bound + ((flags & RPR_FLAG_LOG_SOFTMAX) ? log((double)m->d.V) : 0.0);
-  if (1e8 - L * per_step <= 1e7) return forks;   // logits too large for the masked-candidate proof
-  if (c->n_fork_override >= 0) {
-    int prev = 0;
-    for (int i = 0; i < c->n_fork_override; ++i) {
-      const int t = c->fork_override[i];
-      if (t > prev && t <= L - 1) { forks.push_back(t); prev = t; }
+// The plan of one search on one workspace (lane -1: the ctx's): the ctx's settings (its base), the model's facts and the call handed to
+// plan_search, which asks for the trie's statistics when the automatic fork planner needs them (one pass over the sorted
+// codes, on the first such search of that length)
+SearchPlan make_plan(rpr_ctx* c, const rpr_model* m, rpr_trie* tr, int Q, int Lq, int B, int L, unsigned flags, bool taps, bool margins,
+                     int lane) {
+  SearchModel f;
+  f.logit_bound = m->logit_bound; f.V = m->d.V; f.f32_only = m->f32_only; f.l0_current = m->l0_ready(c);
+  // the per-call debug switches of the selection / ranking kernels are part of the plan (tests flip them between calls)
+  auto env_int = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
+  const SearchCall a{Q, Lq, B, L, flags, taps, margins, lane, env_int("RPR_TAIL_RANK_REPLAY", 0), env_int("RPR_SELECT_RADIX", -1)};
+  return plan_search(*c, f, a, [&] {
+    auto it = tr->single_frac.find(L);
+    if (it == tr->single_frac.end()) {
+      std::vector<double> sf, mu;
+      trie_single_frac(tr->host_sorted.data(), tr->N, tr->L, L, sf, &mu);
+      it = tr->single_frac.emplace(L, std::move(sf)).first;
+      tr->extra_mean[L] = std::move(mu);
     }
-    *drop_last = c->forced_tail == 2 && !forks.empty();
-    return forks;
-  }
-  auto it = tr->single_frac.find(L);
-  if (it == tr->single_frac.end()) {
-    std::vector<double> f, mu;
-    trie_single_frac(tr->host_sorted.data(), tr->N, tr->L, L, f, &mu);
-    it = tr->single_frac.emplace(L, std::move(f)).first;
-    tr->extra_mean[L] = std::move(mu);
-  }
-  const int E = tail_extras_budget(c->tail_extras, Q, B, c->cur_margins != 0);
-  return plan_forks(it->second.data(), tr->extra_mean[L].data(), Q, B, L, c->forced_tail, E, E > 0 ? tail_extras_pool(Q) : 0, drop_last);
+    return TrieStats{it->second.data(), tr->extra_mean[L].data()};
+  });
 }
 
-int pack_forks(const std::vector<int>& forks, bool drop_last) {
-  int v = drop_last ? (1 << 30) : 0;
-  for (size_t i = 0; i < forks.size(); ++i) v |= forks[i] << (8 * i);
-  return v;
-}
+// a lane's workspace stands in c->ws for the scope (lane -1: the ctx's own stays)
+struct WsGuard {
+  rpr_ctx* c; int lane;
+  WsGuard(rpr_ctx* c_, int l) : c(c_), lane(l) { if (lane >= 0) std::swap(c->ws, c->lanes[lane].ws); }
+  ~WsGuard() { if (lane >= 0) std::swap(c->ws, c->lanes[lane].ws); }
+};
 
-// one search on stream s; lane >= 0: in that lane's workspace (swapped into c->ws for the duration of the call)
-int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask, int32_t Q,
-               int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores, int64_t* out_row_lo,
-               int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, hipStream_t s, int lane) {
-  struct WsGuard {
-    rpr_ctx* c; int lane;
-    WsGuard(rpr_ctx* c_, int l) : c(c_), lane(l) { if (lane >= 0) { std::swap(c->ws, c->lanes[lane].ws); c->cur_cus = c->lane_cus; c->cur_lane = lane; } }
-    ~WsGuard() { if (lane >= 0) { std::swap(c->ws, c->lanes[lane].ws); c->cur_cus = 0; c->cur_lane = -1; } }
-  } ws_guard(c, lane);
-  PrecGuard prec_guard(c, m);
-  bool drop_last = false;
-  const std::vector<int> forks = choose_forks(c, m, tr, Q, B, L, flags, taps != nullptr, &drop_last);
-  int e = alloc_workspace(c, m, Q, Lq, B, L, forks, drop_last, (flags & RPR_FLAG_LOG_SOFTMAX) != 0);
-  if (e) return e;
-  c->last_forks = forks;
-  c->last_ws_mask |= lane >= 0 ? (2 << lane) : 1;
+// one planned search on stream s, in the workspace of its plan, which search_entry has sized
+int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const SearchPlan& plan, const int32_t* input_ids, const int32_t* attention_mask,
+               int32_t* out_tokens, float* out_scores, int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin,
+               const rpr_debug_taps* taps, hipStream_t s) {
+  WsGuard ws_guard(c, plan.lane);
+  PrecGuard prec_guard(c, plan.prec);
+  const int Q = plan.Q, L = plan.L;
+  c->last_forks.assign(plan.forks, plan.forks + plan.n_forks);
+  c->last_ws_mask |= plan.lane >= 0 ? (2 << plan.lane) : 1;
   Workspace& w = c->ws;
-  const size_t T = (size_t)Q * Lq, R = (size_t)Q * B;
+  const size_t T = (size_t)Q * plan.Lq, R = (size_t)Q * plan.B;
   RPR_HIP(hipMemcpyAsync(w.ids.p, input_ids, T * 4, hipMemcpyDeviceToDevice, s));
   RPR_HIP(hipMemcpyAsync(w.mask.p, attention_mask, T * 4, hipMemcpyDeviceToDevice, s));
 
-  const bool eager = (flags & RPR_FLAG_NO_GRAPH) || taps || c->profiling;
+  const bool eager = (plan.flags & RPR_FLAG_NO_GRAPH) || taps || c->profiling;
   if (eager) {
     Launcher Ln{c, s};
-    enqueue_search(Ln, c, m, tr, Q, Lq, B, L, flags, taps, forks, drop_last);
+    enqueue_search(Ln, c, m, tr, plan, taps);
     if (Ln.err) return Ln.err;
   } else {
-    // the per-call debug switches of the selection / ranking kernels are part of the key (tests flip them between calls)
-    auto env_int = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
-    const unsigned dbg = (env_int("RPR_TAIL_RANK_REPLAY", 0) ? 1u : 0u) | ((unsigned)(env_int("RPR_SELECT_RADIX", -1) + 1) << 1);
-    const unsigned l0 = m->l0_ready(c) ? (unsigned)c->l0_mode : 0u;   // whether the capture reads the layer-0 Q/K/V table
-    const unsigned mg = c->cur_margins ? 1u : 0u;                     // whether every selection is followed by the margin kernel
-    const int ex = tail_extras_budget(c->tail_extras, Q, B, c->cur_margins != 0);   // extra sequences a forced query may carry (< 32)
-    GraphKey key{m, tr, Q, Lq, B, L, flags | ((unsigned)c->precision << 16) | (dbg << 20) | (l0 << 24) | (mg << 28), lane,
-                 pack_forks(forks, drop_last) | (ex << 24)};
+    const GraphKey key{m, tr, plan};
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
       hipGraph_t graph = nullptr;
       RPR_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
       Launcher Ln{c, c->cap_stream};
-      enqueue_search(Ln, c, m, tr, Q, Lq, B, L, flags, nullptr, forks, drop_last);
+      enqueue_search(Ln, c, m, tr, plan, nullptr);
       hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
       if (Ln.err) { if (graph) (void)hipGraphDestroy(graph); return Ln.err; }
       if (ce != hipSuccess) return hip_fail(ce, "hipStreamEndCapture", __FILE__, __LINE__);
@@ -792,14 +687,11 @@ int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids,
   return RPR_OK;
 }
 
-// rpr_search (out_margin == nullptr) and rpr_search_margins: argument checks, weight planes, the lane split
+// rpr_search (out_margin == nullptr) and rpr_search_margins: argument checks, weight planes, the plans, the lane split
 int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
                  int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
                  int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, void* stream) {
   RPR_REQUIRE(c && m && tr && input_ids && attention_mask && out_tokens && out_scores, "NULL argument");
-  // margin mode for everything this call sizes and enqueues (alloc_workspace, enqueue_search, the graph key), both lanes included
-  struct MarginMode { rpr_ctx* c; MarginMode(rpr_ctx* c_, bool on) : c(c_) { c->cur_margins = on ? 1 : 0; } ~MarginMode() { c->cur_margins = 0; } }
-      margin_mode(c, out_margin != nullptr);
   RPR_REQUIRE(m->ctx == c && tr->ctx == c, "model/trie belong to another ctx");
   RPR_REQUIRE(Q >= 1 && B >= 1 && B <= 65535, "Q or B out of range");
   RPR_REQUIRE(Lq >= 1 && Lq <= MAX_LQ, "Lq out of range (1..256)");
@@ -819,32 +711,28 @@ int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_id
   c->last_ws_mask = 0;
   // Large batches: two halves on the two CU-masked lanes, side by side (see Lane). Results are those of one call: every
   // query is processed on its own rows. The caller's stream waits for both lanes.
-  if (c->lane_min_rows > 0 && (int64_t)Q * B >= c->lane_min_rows && Q >= 2 && !taps && ensure_lanes(c)) {
-    const int32_t Qh[2] = {(Q + 1) / 2, Q / 2};
-    // both lane workspaces are sized BEFORE either half is enqueued: growing a buffer drops every cached graph of the
-    // ctx (ensure()), which must not happen while the other lane's graph is in flight — and an allocation failure then
-    // leaves nothing running
-    for (int i = 0; i < 2; ++i) {
-      std::swap(c->ws, c->lanes[i].ws);
-      int e;
-      {
-        PrecGuard prec_guard(c, m);
-        bool drop_last = false;
-        const std::vector<int> forks = choose_forks(c, m, tr, Qh[i], B, L, flags, false, &drop_last);
-        e = alloc_workspace(c, m, Qh[i], Lq, B, L, forks, drop_last, (flags & RPR_FLAG_LOG_SOFTMAX) != 0);
-      }
-      std::swap(c->ws, c->lanes[i].ws);
-      if (e) return e;
-    }
+  const bool split = c->lane_min_rows > 0 && (int64_t)Q * B >= c->lane_min_rows && Q >= 2 && !taps && ensure_lanes(c);
+  // Every workspace of the call is planned once and sized BEFORE anything is enqueued: growing a buffer drops every cached
+  // graph of the ctx (ensure()), which must not happen while the other lane's graph is in flight — and an allocation failure
+  // then leaves nothing running
+  const int32_t Qh[2] = {split ? (Q + 1) / 2 : Q, Q / 2};
+  SearchPlan plans[2];
+  for (int i = 0; i < (split ? 2 : 1); ++i) {
+    plans[i] = make_plan(c, m, tr, Qh[i], Lq, B, L, flags, taps != nullptr, out_margin != nullptr, split ? i : -1);
+    WsGuard ws_guard(c, plans[i].lane);
+    const int e = alloc_workspace(c, m, plans[i]);
+    if (e) return e;
+  }
+  if (split) {
     RPR_HIP(hipEventRecord(c->fork_ev, s));
     int32_t q0 = 0;
     for (int i = 0; i < 2; ++i) {
       Lane& ln = c->lanes[i];
       RPR_HIP(hipStreamWaitEvent(ln.stream, c->fork_ev, 0));
       const size_t r0 = (size_t)q0 * B;
-      int e = search_one(c, m, tr, input_ids + (size_t)q0 * Lq, attention_mask + (size_t)q0 * Lq, Qh[i], Lq, B, L, flags,
-                         out_tokens + r0 * L, out_scores + r0, out_row_lo ? out_row_lo + r0 : nullptr,
-                         out_row_hi ? out_row_hi + r0 : nullptr, out_margin ? out_margin + q0 : nullptr, nullptr, ln.stream, i);
+      int e = search_one(c, m, tr, plans[i], input_ids + (size_t)q0 * Lq, attention_mask + (size_t)q0 * Lq, out_tokens + r0 * L,
+                         out_scores + r0, out_row_lo ? out_row_lo + r0 : nullptr, out_row_hi ? out_row_hi + r0 : nullptr,
+                         out_margin ? out_margin + q0 : nullptr, nullptr, ln.stream);
       if (e) {   // the other half may already be writing the caller's buffers: let it finish before reporting the error
         for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(c->lanes[k].stream);
         return e;
@@ -855,8 +743,7 @@ int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_id
     for (int i = 0; i < 2; ++i) RPR_HIP(hipStreamWaitEvent(s, c->lanes[i].done, 0));
     return RPR_OK;
   }
-  return search_one(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi, out_margin,
-                    taps, s, -1);
+  return search_one(c, m, tr, plans[0], input_ids, attention_mask, out_tokens, out_scores, out_row_lo, out_row_hi, out_margin, taps, s);
 }
 
 }  // namespace
@@ -923,10 +810,9 @@ int rpr_set_fork_depths(rpr_ctx* c, int32_t n, const int32_t* depths) {
 int rpr_fork_depths(rpr_ctx* c, rpr_model* m, rpr_trie* tr, int32_t Q, int32_t B, int32_t L, uint32_t flags, int32_t* out_depths) {
   RPR_REQUIRE(c && m && tr && out_depths, "NULL argument");
   RPR_REQUIRE(Q >= 1 && B >= 1 && L >= 1 && L <= tr->L, "Q, B or L out of range");
-  bool drop_last = false;
-  const std::vector<int> f = choose_forks(c, m, tr, Q, B, L, flags, false, &drop_last);
-  for (size_t i = 0; i < f.size(); ++i) out_depths[i] = f[i];
-  return (int)f.size();
+  const SearchPlan p = make_plan(c, m, tr, Q, 0, B, L, flags, false, false, -1);   // the plan of rpr_search (no margins) on one workspace
+  for (int i = 0; i < p.n_forks; ++i) out_depths[i] = p.forks[i];
+  return p.n_forks;
 }
 
 int rpr_last_fork_stats(rpr_ctx* c, int32_t* out_depths, int32_t* out_forced, int32_t* out_left) {
@@ -993,7 +879,7 @@ int rpr_encode(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int e = ensure_weight_planes(c, m, s);
   if (e) return e;
-  e = alloc_workspace(c, m, Q, Lq, 1, 1);
+  e = alloc_workspace(c, m, plain_plan(Q, Lq, 1, 1));
   if (e) return e;
   Workspace& w = c->ws;
   const size_t T = (size_t)Q * Lq;

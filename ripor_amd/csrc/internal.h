@@ -1,5 +1,7 @@
 // Internal declarations shared by the translation units behind the C ABI (api.hip: the ABI and the search driver,
-// passes.hip: the forward passes it enqueues, train_api.hip: the training step, rq_api.hip: docid creation). Not part of the ABI: include/ripor_hip.h is.
+// passes.hip: the forward passes it enqueues, train_api.hip: the training step, rq_api.hip: docid creation). What the driver
+// decides about one search is search_plan.h (host arithmetic only); here are the objects it decides about. Not part of the
+// ABI: include/ripor_hip.h is.
 #pragma once
 #include <map>
 #include <memory>
@@ -10,6 +12,7 @@
 
 #include "common.h"
 #include "gemm_route.h"
+#include "search_plan.h"
 #include "trie.h"
 
 namespace rpr {
@@ -119,11 +122,8 @@ struct rpr_d2s {
 };
 
 struct GraphKey {
-  const rpr_model* m; const rpr_trie* t; int Q, Lq, B, L; unsigned flags; int lane;   // lane: -1 = the ctx workspace
-  int forks;                                                                           // fork depths, 8 bits each (0 = none)
-  bool operator<(const GraphKey& o) const {
-    return std::tie(m, t, Q, Lq, B, L, flags, lane, forks) < std::tie(o.m, o.t, o.Q, o.Lq, o.B, o.L, o.flags, o.lane, o.forks);
-  }
+  const rpr_model* m; const rpr_trie* t; rpr::SearchPlan plan;
+  bool operator<(const GraphKey& o) const { return std::tie(m, t, plan) < std::tie(o.m, o.t, o.plan); }
 };
 
 // Forced-tail search (passes.hip::enqueue_search): a compacted batch of queries that goes on step by step after a fork
@@ -136,7 +136,7 @@ struct StageBufs {
   DevBuf score[2], lo[2], hi[2], tokens[2], anc[2];
 };
 // ... and the queries that leave at that fork: their remaining positions are scored in one teacher-forced pass
-// cap = the stage's queries + the spare entries of the queries forced with extras (tail_extras_pool; 0 when the search has none)
+// cap = the stage's queries + the spare entries of the queries forced with extras (SearchPlan::pool)
 struct TailBufs {
   DevBuf flag, flist;       // int32 [cap]: forced? (1 + extras), tail entry -> stage query (a spare entry: the virtual query cap_q + k)
   DevBuf cnt;               // int32 [4]: entries, sequences (x B), rows (x B x (L - T)), forced queries (= entries - spare entries in use)
@@ -147,7 +147,7 @@ struct TailBufs {
   DevBuf tokens;            // uint16 [cap * B][L]
   DevBuf gold;              // float [cap * B][L - T]
 };
-constexpr int MAX_FORKS = 2;
+using rpr::MAX_FORKS;
 
 struct Workspace {
   // encoder
@@ -197,9 +197,8 @@ struct Lane {
   hipEvent_t done = nullptr;
 };
 
-struct rpr_ctx {
+struct rpr_ctx : rpr::SearchSettings {   // (what a search is planned from: precision, forced tail, fork depths, extras, layer-0 table mode, lane CUs)
   int device;
-  int precision = RPR_PREC_F16X2;
   unsigned int* status = nullptr;       // [dev, 64 words] [8] weight-range probe; sticky words: [0] a value left the f16 plane range, [1] a query attends to nothing, [2] a query was left unforced by the last fork of an optimistic forced-tail search
   unsigned int* status_host = nullptr;  // pinned mirror filled by rpr_get_status
   struct TrainWs* tws = nullptr;        // activations / scratch of the training step (train_api.hip), freed by free_train_ws
@@ -208,24 +207,11 @@ struct rpr_ctx {
   int lanes_state = 0;          // 0 not tried yet, 1 ready, -1 masked streams unavailable on this device
   int lane_min_rows = 10240;    // batches of at least this many decoder rows (queries x beams) are split over the two lanes (0 = never)
   hipEvent_t fork_ev = nullptr;
-  int cur_cus = 0;              // CUs of the lane the current enqueue runs on (0 = the whole chip)
-  int lane_cus = 0;             // CUs per lane
-  int cur_lane = -1;            // lane of the current enqueue (-1 = the ctx stream)
-  int cur_no_row_split = 0;     // 1 while the packed encoder (and the cross-K/V product on its rows) is enqueued: GemmH2Args.no_row_split
-  int cur_small_live = 0;       // > 0 while a leftover stage is enqueued: its GEMMs are paired (GemmH2Args.small_live)
-  int cur_margins = 0;          // 1 while rpr_search_margins sizes and enqueues its search: every selection step is followed by
-                                //   the pruning-margin kernel (part of the graph key)
-  int forced_tail = 1;          // 0 = every query runs all L steps sequentially, 1 = exact forced tail, 2 = optimistic (see choose_forks)
-  int fork_override[MAX_FORKS] = {0, 0};   // explicit fork depths (rpr_set_fork_depths / RPR_FORK_DEPTHS); 0 = from the trie statistics
-  int n_fork_override = -1;     // -1 = automatic
-  int tail_extras = -1;         // rpr_set_tail_extras: -1 = automatic (tail_extras_budget), 0 = off, n > 0 = always, up to n extra sequences per query
   std::vector<int> last_forks;  // fork depths of the last rpr_search and the workspaces it ran in (bit 0: ctx, 1 / 2: lanes)
   int last_ws_mask = 0;         //   -> rpr_last_fork_stats
   size_t ws_bytes = 0;
   int enc_rows_accounted = 0;   // live encoder rows of the last enqueue (profile accounting)
   unsigned l0_epoch = 0;        // bumped by rpr_set_precision: a model's layer-0 Q/K/V table of another epoch is made again
-  int l0_mode = 1;              // rpr_set_l0_table: 0 = the table is never made nor read, 1 = it replaces the launches the route planner
-                                //   sends to the ping-pong kernel, 2 = every layer-0 Q/K/V launch of a search (tests)
   hipStream_t cap_stream = nullptr;
   std::map<GraphKey, hipGraphExec_t> graphs;
   // profiling
@@ -244,22 +230,6 @@ inline bool rpr_model::l0_ready(const rpr_ctx* c) const { return c->l0_mode > 0 
 
 namespace rpr {
 
-// Forced with extras (common.h: ForkArgs::E): how many extra sequences a forced query may carry into the tail pass, and how
-// many spare tail entries a stage keeps for such queries. Automatic mode: stages with more than 4096 decoder rows (the
-// threshold of choose_forks for "steps bound by the matrix pipes": there a leftover stage costs two partly filled launches
-// per GEMM) and fewer than 32 beams (the one-block selection; with more beams extras are the rule and a spare entry of B
-// slots per query is the wrong layout). Never with the pruning margins: a query with extras is still pruned inside the tail.
-constexpr int TAIL_EXTRAS_AUTO = 4;
-inline int tail_extras_budget(int mode, int Q, int B, bool margins) {
-  if (mode == 0 || B >= 32 || margins) return 0;
-  if (mode > 0) return mode < B ? mode : B;
-  return (int64_t)Q * B > 4096 ? (TAIL_EXTRAS_AUTO < B ? TAIL_EXTRAS_AUTO : B) : 0;
-}
-inline int tail_extras_pool(int Q) { return Q / 32 < 4 ? 4 : (Q / 32 > 64 ? 64 : Q / 32); }
-// fork depths from the trie statistics (api.hip; rpr_plan_forks exposes it to the host tests)
-std::vector<int> plan_forks(const double* single_frac, const double* extra_mean, int Q, int B, int L, int forced_tail, int E, int pool,
-                            bool* drop_last);
-
 // re-split every GEMM weight into its f16 planes (api.hip); sets model->f32_only if a weight no longer fits
 int refresh_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s);
 inline int ensure_weight_planes(rpr_ctx* c, rpr_model* m, hipStream_t s) {
@@ -273,15 +243,20 @@ int ensure_l0_table(rpr_ctx* c, rpr_model* m, hipStream_t s);
 void free_train_ws(rpr_ctx* c);   // train_api.hip
 void train_forget_model(rpr_ctx* c, const rpr_model* m);   // train_api.hip: drop the per-model weight cache table
 
+// destroy the captured graphs whose key `stale` names: whatever they reference is about to go or to change
+template <class Pred> void drop_graphs(rpr_ctx* c, Pred&& stale) {
+  for (auto it = c->graphs.begin(); it != c->graphs.end();) {
+    if (stale(it->first)) { (void)hipGraphExecDestroy(it->second); it = c->graphs.erase(it); } else ++it;
+  }
+}
+
 inline int ensure(rpr_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return 0;
   if (b.p) {
     RPR_HIP(hipFree(b.p));
     c->ws_bytes -= b.cap;
     b.p = nullptr; b.cap = 0;
-    // graphs captured against the old pointers are stale
-    for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.second);
-    c->graphs.clear();
+    drop_graphs(c, [](const GraphKey&) { return true; });   // graphs captured against the old pointers are stale
   }
   const size_t want = (bytes + 255) & ~(size_t)255;
   RPR_HIP(hipMalloc(&b.p, want));
@@ -307,6 +282,10 @@ struct Launcher {
   int err = 0;
   const int* live_dev = nullptr;   // profile accounting of the launches that follow (see rpr_ctx::Rec)
   int live_static = 0;
+  // what the split-precision GEMM launches that follow are told (passes.hip: h2_args)
+  int cus = 0;                     // CUs of the stream (0 = the whole chip): GemmH2Args.cus
+  int no_row_split = 0;            // 1 while the packed encoder (and the cross-K/V product on its rows) is enqueued: GemmH2Args.no_row_split
+  int small_live = 0;              // > 0 while a leftover stage is enqueued: its GEMMs are paired (GemmH2Args.small_live)
   void account_live(const int* dev, int rows_static) { live_dev = dev; live_static = rows_static; }
   hipEvent_t get_event() {
     if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
@@ -343,7 +322,7 @@ struct LinW {                                                                // 
   int Nh = 0;                                                                //   rows of a plane padded beyond N (0 = N): what the split kernel computes
   bool no_scratch = false;                                                   //   the ctx's split-K scratch is not lent to this product: the mid-size
                                                                              //   split-K route (gemm_route.h: part, mid_split) stays closed to it
-  bool row_split_ok = false;                                                 //   the ctx's cur_no_row_split does not reach this product
+  bool row_split_ok = false;                                                 //   the launcher's no_row_split does not reach this product
   bool force_pp = false;                                                     //   the 256x256 ping-pong kernel whatever the shape (GemmH2Args::force_pp)
 };
 struct LinOut {                                                              // destination
@@ -358,14 +337,11 @@ struct LinOut {                                                              // 
 LinOut out_f32(float* p, int ld, int N, const float* resid = nullptr, int relu = 0);
 // m_dev (nullable): device-side live row count (packed encoder); m_acc = rows to account flops/bytes for
 void linear(Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, const int* m_dev = nullptr, int m_acc = -1);
-// forks: depths at which forced queries leave the sequential steps (ascending, each in [1, L-1]; empty = plain search)
-// drop_last: no stage after the last fork (optimistic mode, see choose_forks): its caches are not needed
-int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L, const std::vector<int>& forks = {},
-                    bool drop_last = false, bool log_softmax = false);
+// sizes c->ws for the plan (a lane's workspace: swapped in by the caller)
+int alloc_workspace(rpr_ctx* c, const rpr_model* m, const SearchPlan& plan);
 int alloc_train_workspace(rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L);
 void enqueue_encoder(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int Q, int Lq, bool packed);
-void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, int Q, int Lq, int B, int L,
-                    unsigned flags, const rpr_debug_taps* taps, const std::vector<int>& forks, bool drop_last);
+void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchPlan& plan, const rpr_debug_taps* taps);
 // hidden (nullable): decoder_last_hidden_state of every row [bz * ndoc * L, d_model] instead of the gold-code scores (rpr_embed)
 void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L,
                            const int32_t* codes /*[bz, ndoc, L]*/, float* pos_scores /*[bz, ndoc, L]*/, float* hidden = nullptr);

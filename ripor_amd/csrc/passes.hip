@@ -20,7 +20,8 @@ namespace {
 
 // The split-precision launch of one linear layer: what linear() hands to launch_gemm_h2 (and the layer-0 table's gate to
 // the route planner).
-GemmH2Args h2_args(const rpr_ctx* c, const LinIn& A, const LinW& W, int M, const LinOut& O, const int* m_dev) {
+GemmH2Args h2_args(const Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, const int* m_dev) {
+  const rpr_ctx* c = L.c;
   const int Nh = W.Nh ? W.Nh : W.N;
   GemmH2Args g{};
   g.A = A.h; g.a_ps = A.ps; g.lda = A.ld; g.W = W.h; g.w_ps = W.ps ? W.ps : (size_t)W.N * W.K; g.ldw = W.K;
@@ -33,9 +34,9 @@ GemmH2Args h2_args(const rpr_ctx* c, const LinIn& A, const LinW& W, int M, const
   g.row_ssq = A.ssq; g.inv_d_fix = A.inv_d_fix; g.eps = A.eps;
   g.resid_h = O.resid_h; g.r_ps = O.ps; g.ldrh = O.ldh; g.ssq_out = O.ssq_out;
   g.sat = c->status;
-  g.cus = c->cur_cus;
-  g.small_live = m_dev ? c->cur_small_live : 0;
-  g.no_row_split = W.row_split_ok ? 0 : c->cur_no_row_split;
+  g.cus = L.cus;
+  g.small_live = m_dev ? L.small_live : 0;
+  g.no_row_split = W.row_split_ok ? 0 : L.no_row_split;
   g.force_pp = W.force_pp ? 1 : 0;
   if (!W.no_scratch) { g.part = P<float>(c->ws.part); g.part_cap = c->ws.part.cap / sizeof(float); g.mid_split = 1; }
   return g;
@@ -49,7 +50,7 @@ void linear(Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, 
   const double by = 4.0 * (Ma * W.K + (double)W.N * W.K + Ma * W.N * ((O.resid || O.resid_h) ? 2 : 1));
   hipStream_t s = L.s;
   if (L.c->precision == RPR_PREC_F16X2) {
-    GemmH2Args g = h2_args(L.c, A, W, M, O, m_dev);
+    GemmH2Args g = h2_args(L, A, W, M, O, m_dev);
     L.run(RPR_K_GEMM, fl, by, [&] { return launch_gemm_h2(g, s); }, &g.kernel_cls);
   } else {
     GemmArgs g{};
@@ -62,14 +63,15 @@ void linear(Launcher& L, const LinIn& A, const LinW& W, int M, const LinOut& O, 
   }
 }
 
-int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L, const std::vector<int>& forks, bool drop_last, bool log_softmax) {
+int alloc_workspace(rpr_ctx* c, const rpr_model* m, const SearchPlan& plan) {
   const auto& d = m->d;
+  const int Q = plan.Q, Lq = plan.Lq, B = plan.B, L = plan.L, nf = plan.n_forks;
+  const int* forks = plan.forks;
   const size_t T = (size_t)Q * Lq, R = (size_t)Q * B, inner = m->inner(), dm = d.d_model, dff = d.d_ff;
   const size_t nd = d.num_decoder_layers, ne = d.num_layers, f = sizeof(float);
   Workspace& w = c->ws;
-  // forced with extras: `pool` spare tail entries per fork = virtual queries behind the beam state of the stage (internal.h)
-  const size_t pool = !forks.empty() && tail_extras_budget(c->tail_extras, Q, B, c->cur_margins != 0) > 0 ? (size_t)tail_extras_pool(Q) : 0;
-  const size_t Qt = (size_t)Q + pool, Rv = Qt * B;
+  // forced with extras: `pool` spare tail entries per fork = virtual queries behind the beam state of the stage (0 without forks)
+  const size_t pool = (size_t)plan.pool, Qt = (size_t)Q + pool, Rv = Qt * B;
   int e = 0;
   auto E = [&](DevBuf& b, size_t bytes) { if (!e) e = ensure(c, b, bytes); };
   E(w.ids, T * 4); E(w.mask, T * 4); E(w.last, (size_t)Q * 4); E(w.offs, ((size_t)Q + 1) * 4); E(w.row_src, T * 4);
@@ -77,7 +79,7 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
   E(w.eff, T * dff * f); E(w.enc_out, T * dm * f); E(w.xkv, T * nd * 2 * inner * f);
   E(w.x, R * dm * f); E(w.h, R * dm * f); E(w.q, R * inner * f); E(w.attn, R * inner * f);
   E(w.ff, R * dff * f); E(w.logits, R * (size_t)m->Vp() * f);
-  const size_t depth0 = forks.empty() ? (size_t)L : (size_t)forks[0];   // stage 0 stops at the first fork
+  const size_t depth0 = nf ? (size_t)forks[0] : (size_t)L;   // stage 0 stops at the first fork
   E(w.kcache, nd * depth0 * R * inner * f); E(w.vcache, nd * depth0 * R * inner * f);
   E(w.lb, R * (size_t)m->Vp() * 4 * 2);   // start and end of every child's row range
   if (select_radix_wanted(B, m->Vp())) E(w.sel_rs, select_radix_ws_bytes(Q, B, m->Vp()));
@@ -86,7 +88,7 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
     E(w.tokens[i], Rv * (size_t)L * 2); E(w.anc[i], Rv * (size_t)L * 2);
   }
   E(w.o_tokens, R * (size_t)L * 4); E(w.o_scores, R * 4); E(w.o_lo, R * 8); E(w.o_hi, R * 8);
-  if (c->cur_margins) { E(w.mg_valid, R * (size_t)m->Vp() / 8); E(w.o_margin, (size_t)Q * 8); }
+  if (plan.margins) { E(w.mg_valid, R * (size_t)m->Vp() / 8); E(w.o_margin, (size_t)Q * 8); }
   const size_t hb = sizeof(__half) * 2;  // two planes
   E(w.eattn_h, T * inner * hb); E(w.eff_h, T * dff * hb); E(w.enc_out_h, T * dm * hb);
   E(w.attn_h, R * inner * hb); E(w.ff_h, R * dff * hb);
@@ -94,11 +96,11 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
   E(w.ssq_e, (2 * ne + 1) * T * 8); E(w.ssq_d, (3 * nd + 1) * R * 8);
   E(w.part, (size_t)9 << 20 << 2);   // split-K partials of the mid-size GEMM route: < 256 tiles of 128 x 64, up to 4 splits
   // forced-tail search: one compacted stage and one tail job per fork, tail activations for the longest tail
-  for (size_t k = 0; k < forks.size(); ++k) {
-    const size_t depth = k + 1 < forks.size() ? (size_t)forks[k + 1] : (size_t)L, Lt = (size_t)(L - forks[k]);
+  for (int k = 0; k < nf; ++k) {
+    const size_t depth = k + 1 < nf ? (size_t)forks[k + 1] : (size_t)L, Lt = (size_t)(L - forks[k]);
     StageBufs& sb = w.stage[k];
     E(sb.cnt, 16); E(sb.src, (size_t)Q * 4);
-    if (!(drop_last && k + 1 == forks.size())) {
+    if (!(plan.drop_last && k + 1 == nf)) {
       E(sb.qmap, (size_t)Q * 4); E(sb.offs, (size_t)Q * 4); E(sb.last, (size_t)Q * 4); E(sb.mask, T * 4);
       E(sb.kcache, nd * depth * R * inner * f); E(sb.vcache, nd * depth * R * inner * f);
       for (int i = 0; i < 2; ++i) {
@@ -112,15 +114,15 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, int Q, int Lq, int B, int L,
     E(tb.qmap, Qt * 4); E(tb.offs, Qt * 4); E(tb.last, Qt * 4); E(tb.mask, Qt * Lq * 4);
     E(tb.tokens, Rv * (size_t)L * 2); E(tb.gold, Rv * Lt * f);
   }
-  if (!forks.empty()) {
+  if (nf) {
     const size_t Rt = Rv * (size_t)(L - forks[0]);
     E(w.t_qkv, Rt * 3 * inner * f); E(w.t_q, Rt * inner * f);
-    if (c->precision == RPR_PREC_F16X2 && !m->f32_only) {
+    if (plan.prec == RPR_PREC_F16X2) {
       E(w.t_x_h, Rt * dm * hb); E(w.t_attn_h, Rt * inner * hb); E(w.t_ff_h, Rt * dff * hb); E(w.t_ssq, (3 * nd + 1) * Rt * 8);
     } else {
       E(w.t_x, Rt * dm * f); E(w.t_h, Rt * dm * f); E(w.t_attn, Rt * inner * f); E(w.t_ff, Rt * dff * f);
     }
-    if (log_softmax) { E(w.t_h, Rt * dm * f); E(w.t_logits, Rt * (size_t)d.V * f); }   // normalised rows, V logits per row
+    if (plan.log_softmax()) { E(w.t_h, Rt * dm * f); E(w.t_logits, Rt * (size_t)d.V * f); }   // normalised rows, V logits per row
   }
   return e;
 }
@@ -197,12 +199,12 @@ struct Pass {
   LinOut residual(int layer, int k) const { return h2 ? xs.out(site(layer, k) + 1) : out_f32(x, dm, dm, x); }
   void project(const LinIn& A, const LinW& W, const LinOut& O) { linear(Ln, A, W, M, O, m_dev, m_acc); }
   // The model's layer-0 Q/K/V table stands in for this pass's layer-0 self-attention projection into O: split precision, the
-  // table current, and the launch one the route planner sends whole to the ping-pong kernel — the kernel the table was made
+  // table current (SearchPlan::l0), and the launch one the route planner sends whole to the ping-pong kernel — the kernel the table was made
   // by, whose K order does not depend on where a row sits, so the rows are the same bits (l0_mode 2: whatever the route).
-  bool l0_replaces(const rpr_model* m, const LinOut& O) const {
-    if (!h2 || !m->l0_ready(Ln.c)) return false;
-    if (Ln.c->l0_mode >= 2) return true;
-    return gemm_h2_pp_only(h2_args(Ln.c, xs.in(0), {m->dec_qkv[0], m->h_dec_qkv[0], 3 * inner, dm}, M, O, m_dev));
+  bool l0_replaces(const rpr_model* m, const SearchPlan& plan, const LinOut& O) const {
+    if (!h2 || !plan.l0) return false;
+    if (plan.l0 >= 2) return true;
+    return gemm_h2_pp_only(h2_args(Ln, xs.in(0), {m->dec_qkv[0], m->h_dec_qkv[0], 3 * inner, dm}, M, O, m_dev));
   }
   void attn_out(int layer, int k, const float* W, const __half* Wh) {   // o / xo: the attention output back into the stream
     project(LinIn{attn, attn_h, ps_i, inner}, {W, Wh, dm, inner}, residual(layer, k));
@@ -222,8 +224,7 @@ struct Pass {
 // Saturation raises the ctx's sticky word like the launches it replaces. Scratch (x planes, row sums: 25 MB at the
 // headline) lives for the call only. Not profiled: it is not part of a search.
 int ensure_l0_table(rpr_ctx* c, rpr_model* m, hipStream_t s) {
-  const int prec = m->f32_only ? RPR_PREC_F32 : (c->precision == RPR_PREC_BF16 ? RPR_PREC_F16X2 : c->precision);   // PrecGuard's
-  if (c->l0_mode <= 0 || prec != RPR_PREC_F16X2 || m->l0_state < 0 || m->l0_ready(c)) return RPR_OK;
+  if (c->l0_mode <= 0 || effective_precision(c->precision, m->f32_only) != RPR_PREC_F16X2 || m->l0_state < 0 || m->l0_ready(c)) return RPR_OK;
   const auto& d = m->d;
   const size_t rows = m->l0_rows(), dm = d.d_model;
   if (!l0_table_fits(d.L, d.V, m->inner()) || rows >= ((size_t)1 << 30)) { m->l0_state = -1; return RPR_OK; }
@@ -333,16 +334,16 @@ int live_count(Launcher& Ln, const int* dev, int rows) {
   return rows;
 }
 
-struct SearchDims { int Q, Lq, B, L, xld; bool packed; unsigned flags; };
+int xkv_ld(const rpr_model* m) { return m->d.num_decoder_layers * 2 * m->inner(); }   // row of ws.xkv: K | V of every decoder layer
 
 // Decoder steps [t0, t1) of one stage: embed, nd x {self-attention over the beam's ancestry, cross-attention, FF},
 // logits of position t, fused trie mask / top-B / beam expand (reference generation.py:423-526, one iteration per step).
-void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchDims& sd, const StageView& sv,
+void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchPlan& plan, const StageView& sv,
                    int t0, int t1, bool shared0, const rpr_debug_taps* taps) {
   const auto& d = m->d;
   Workspace& w = c->ws;
-  const int Q = sv.Qcap, B = sd.B, L = sd.L, Lq = sd.Lq, R = Q * B, inner = m->inner(), dm = d.d_model, H = d.num_heads;
-  const int nd = d.num_decoder_layers, V = d.V, Vp = m->Vp(), xld = sd.xld;   // Vp: logits row / selection width (V padded to 64)
+  const int Q = sv.Qcap, B = plan.B, L = plan.L, Lq = plan.Lq, R = Q * B, inner = m->inner(), dm = d.d_model, H = d.num_heads;
+  const int nd = d.num_decoder_layers, V = d.V, Vp = m->Vp(), xld = xkv_ld(m);   // Vp: logits row / selection width (V padded to 64)
   hipStream_t s = Ln.s;
   float *qb = P<float>(w.q), *logits = P<float>(w.logits);
   const size_t layer_stride = sv.kv_layer(B, inner), kv_q = sv.kv_q(B, inner), kv_h = sv.kv_h(B), kv_pos = (size_t)B * sv.dkv, kv_slot = sv.dkv;
@@ -369,7 +370,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
         o.f[0] = qb; o.f[1] = kc + (size_t)t * kv_pos; o.f[2] = vc + (size_t)t * kv_pos;
         o.ldo[0] = o.ldo[1] = o.ldo[2] = inner; o.split_n = inner;
         o.rm_B = Bt; o.rm_stride = kv_q; o.rm_slot = kv_slot; o.rm_head = kv_h; o.rm_dshift = sv.dkv == 128 ? 7 : 6;
-        if (i == 0 && p.l0_replaces(m, o))   // the row's q | k | v from the model's table, landing where the epilogue puts them
+        if (i == 0 && p.l0_replaces(m, plan, o))   // the row's q | k | v from the model's table, landing where the epilogue puts them
           Ln.run(RPR_K_OTHER, 0, 2.0 * Ma * 3 * inner * 4, [&] {
             return launch_dec_l0_qkv(m->l0_table, cur.tokens, L, Rt, V, d.L * V, t, inner, o.f[0], o.f[1], o.f[2], o.rm_B, o.rm_stride,
                                      o.rm_slot, o.rm_head, o.rm_dshift, sv.nrows_dev, s);
@@ -402,7 +403,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
     {
       // codebook t: V fp32 rows; its planes (times the final layer-norm weight and the scaleup factor) are Vp rows inside
       // the stacked [2][L*Vp][d] buffer. The split kernel writes whole rows of Vp logits, the exact-fp32 kernel the V real
-      // columns (the pad stays 0). The split-K scratch is not lent and the ctx's no-row-split state does not apply:
+      // columns (the pad stays 0). The split-K scratch is not lent and the launcher's no-row-split state does not apply:
       // this product has never taken the mid-size split-K route nor set no_row_split, whoever calls enqueue_steps.
       // Its profile record is stated on V columns.
       LinW wt{d.out_embeds + (size_t)t * V * dm, m->h_out_embeds + (size_t)t * Vp * dm, V, dm};
@@ -419,7 +420,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
     }
     if (w.sel_rs.p && select_radix_wanted(B, Vp) && w.sel_rs.cap >= select_radix_ws_bytes(Q, B, Vp))
       select_radix_carve(sa.rs, w.sel_rs.p, P<int32_t>(w.lb) + (size_t)R * Vp, Q, B, Vp);
-    sa.log_softmax = (sd.flags & RPR_FLAG_LOG_SOFTMAX) ? 1 : 0;
+    sa.log_softmax = plan.log_softmax() ? 1 : 0;
     sa.shared0 = (Bt != B) ? 1 : 0;
     sa.nq_dev = sv.nq_dev;
     if (taps) {
@@ -429,9 +430,9 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
       sa.tap_valid = taps->step_valid ? reinterpret_cast<unsigned long long*>(taps->step_valid) + (size_t)t * ((size_t)R * V / 64) : nullptr;
     }
     // the bitmap of this step, for the margin kernel (the shared step 0 needs none: every beam stands on the root)
-    if (c->cur_margins && !sa.tap_valid && !sa.shared0) sa.tap_valid = P<unsigned long long>(w.mg_valid);
+    if (plan.margins && !sa.tap_valid && !sa.shared0) sa.tap_valid = P<unsigned long long>(w.mg_valid);
     Ln.run(RPR_K_SELECT, 0, (double)Ma * V * 4 + (double)Ma * 40, [&] { return launch_select(sa, s); });
-    if (c->cur_margins) {
+    if (plan.margins) {
       // pruning margin of the step (rpr_search_margins): one more pass over the step's candidates, behind the selection
       MarginArgs ma{lg, cur.score, nxt.score, sa.tap_valid, tr->codes, tr->L, t, cur.lo, cur.hi, Q, B, Vp, V, sa.log_softmax,
                     sa.shared0, sv.nq_dev, sv.io.qmap, P<double>(w.o_margin)};
@@ -445,20 +446,19 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
 // the next stage (`nb` / returned view): beam state, the K/V of the T positions walked so far, the cross-attention inputs.
 // compact = false (optimistic mode, last fork): nobody walks on — a query that is not forced here only raises the ctx's
 // sticky RPR_STATUS_TAIL_LEFTOVER word and the caller repeats the batch in the exact mode.
-StageView enqueue_fork(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchDims& sd, const StageView& sv,
+StageView enqueue_fork(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchPlan& plan, const StageView& sv,
                        int T, int next_depth, TailBufs& tb, StageBufs& nb, bool compact) {
   const auto& d = m->d;
-  const int Q = sv.Qcap, B = sd.B, L = sd.L, Lq = sd.Lq, inner = m->inner(), nd = d.num_decoder_layers, H = d.num_heads;
+  const int Q = sv.Qcap, B = plan.B, L = plan.L, Lq = plan.Lq, inner = m->inner(), nd = d.num_decoder_layers, H = d.num_heads;
   hipStream_t s = Ln.s;
   const BeamState st = sv.st[T & 1];
   // No masked candidate may overtake a valid one during the remaining n = L - T steps. With |logit| <= bound
   // (rpr_model::logit_bound) the valid candidates of a step are >= smin - n*bound and the masked ones
   // <= smax + n*bound - 1e9, so forced requires (smax - smin) + 2*n*bound < 1e9; a tenth of that is demanded.
   // Log-softmax scores: a step adds a log-probability in [-(2*bound + ln V), 0] instead of a logit in [-bound, bound].
-  const double per_step = (sd.flags & RPR_FLAG_LOG_SOFTMAX) ? 2.0 * (double)m->logit_bound + log((double)d.V) : 2.0 * (double)m->logit_bound;
+  const double per_step = plan.log_softmax() ? 2.0 * (double)m->logit_bound + log((double)d.V) : 2.0 * (double)m->logit_bound;
   const double spread_max = 1e8 - (double)(L - T) * per_step;
-  // forced with extras (common.h: ForkScanArgs): the budget per query and the stage's spare tail entries
-  const int extras = tail_extras_budget(c->tail_extras, sd.Q, B, c->cur_margins != 0), pool = extras > 0 ? tail_extras_pool(sd.Q) : 0;
+  const int extras = plan.extras, pool = plan.pool;   // forced with extras (common.h: ForkScanArgs): the budget per query, the stage's spare tail entries
   ForkArgs fa{st, tr->codes, tr->L, Q, sv.nq_dev, B, T, L, spread_max, P<int32_t>(tb.flag), extras};
   Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_fork_classify(fa, s); });
   const ForkScanArgs fs{P<int32_t>(tb.flag), Q, sv.nq_dev, B, L - T, P<int32_t>(tb.flist), P<int32_t>(tb.cnt), P<int32_t>(nb.src),
@@ -503,14 +503,14 @@ StageView enqueue_fork(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_t
 // through the beams' ancestry and the positions >= T from this pass's own K/V rows; the B*(L-T) rows of a query share
 // its encoder K/V in cross-attention; instead of V logits per row only the logit of the row's (only valid) token is
 // computed, in exact fp32 (tail_gold_kernel).
-void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchDims& sd, const StageView& sv, int T,
+void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchPlan& plan, const StageView& sv, int T,
                   TailBufs& tb) {
   const auto& d = m->d;
   Workspace& w = c->ws;
-  const int pool = tail_extras_budget(c->tail_extras, sd.Q, sd.B, c->cur_margins != 0) > 0 ? tail_extras_pool(sd.Q) : 0;
+  const int pool = plan.pool;
   const int Q = sv.Qcap + pool;   // tail entries: the stage's queries and the spare entries of those forced with extras
-  const int B = sd.B, L = sd.L, Lq = sd.Lq, Lt = L - T, S = Q * B, R = S * Lt;
-  const int inner = m->inner(), dm = d.d_model, H = d.num_heads, nd = d.num_decoder_layers, V = d.V, xld = sd.xld;
+  const int B = plan.B, L = plan.L, Lq = plan.Lq, Lt = L - T, S = Q * B, R = S * Lt;
+  const int inner = m->inner(), dm = d.d_model, H = d.num_heads, nd = d.num_decoder_layers, V = d.V, xld = xkv_ld(m);
   hipStream_t s = Ln.s;
   const int* nf_dev = P<int>(tb.cnt);
   const int* nseq_dev = nf_dev + 1;
@@ -525,7 +525,7 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
   const size_t kv_pos = (size_t)B * sv.dkv;
   for (int i = 0; i < nd; ++i) {
     const LinOut o_qkv = out_f32(qkv, 3 * inner, 3 * inner);
-    if (i == 0 && p.l0_replaces(m, o_qkv))   // layer 0: the rows of the model's (position, token) table instead of the projection
+    if (i == 0 && p.l0_replaces(m, plan, o_qkv))   // layer 0: the rows of the model's (position, token) table instead of the projection
       Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * 3 * inner * 4, [&] {
         return launch_tail_l0_qkv(m->l0_table, P<uint16_t>(tb.tokens), qkv, R, nrows_dev, T, L, V, 3 * inner, s);
       });
@@ -554,7 +554,7 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
     p.attn_out(i, 1, m->dec_xo[i], m->h_dec_xo[i]);
     p.ff_block(i, 2, m->dec_ln2[i], m->dec_wi[i], m->h_dec_wi[i], m->dec_wo[i], m->h_dec_wo[i]);
   }
-  if (sd.flags & RPR_FLAG_LOG_SOFTMAX) {
+  if (plan.log_softmax()) {
     // the score of a position is the log-probability of its token: final RMSNorm of every row, the V logits of the rows
     // of one position per launch of the exact-fp32 GEMM (rows of a position are Lt apart; its codebook is out_embeds[pos]),
     // then log_softmax at the token (tail_logprob_kernel)
@@ -590,17 +590,18 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
 }  // namespace
 
 // Everything between the staged inputs (ws.ids/ws.mask) and the staged outputs (ws.o_*).
-void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, int Q, int Lq, int B, int L,
-                    unsigned flags, const rpr_debug_taps* taps, const std::vector<int>& forks, bool drop_last) {
+void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* tr, const SearchPlan& plan, const rpr_debug_taps* taps) {
   const auto& d = m->d;
   Workspace& w = c->ws;
-  const int T = Q * Lq, inner = m->inner(), dm = d.d_model;
-  const int nd = d.num_decoder_layers;
+  const int Q = plan.Q, Lq = plan.Lq, B = plan.B, L = plan.L, nf = plan.n_forks;
+  const int* forks = plan.forks;
+  const int T = Q * Lq, dm = d.d_model, xld = xkv_ld(m);
   hipStream_t s = Ln.s;
+  Ln.cus = plan.cus;
   // index of the last attended key + 1 per query: row packing of the encoder and the cross-attention loop bound
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_mask_lengths(P<int32_t>(w.mask), P<int32_t>(w.last), Q, Lq, s, c->status + 1); });
   const bool packed = !taps;   // taps return the padded [Q, Lq, d] encoder output
-  c->cur_no_row_split = packed ? 1 : 0;   // the packed rows' capacity says nothing about the live rows (reset below, after the cross-K/V product)
+  Ln.no_row_split = packed ? 1 : 0;   // the packed rows' capacity says nothing about the live rows (reset below, after the cross-K/V product)
   enqueue_encoder(Ln, c, m, Q, Lq, packed);
   if (taps && taps->encoder_out && !Ln.err) {
     hipError_t e = hipMemcpyAsync(taps->encoder_out, w.enc_out.p, (size_t)T * dm * 4, hipMemcpyDeviceToDevice, s);
@@ -608,21 +609,19 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
   }
   // cross-attention K/V of every decoder layer in one GEMM (shared by the B beams of a query;
   // the reference recomputes them for every beam at every step)
-  const int xld = nd * 2 * inner;
   Ln.account_live(packed ? P<int>(w.offs) + Q : nullptr, T);
   linear(Ln, {P<float>(w.enc_out), P<__half>(w.enc_out_h), (size_t)T * dm, dm}, {d.dec_xkv, m->h_dec_xkv, xld, dm}, T,
          out_f32(P<float>(w.xkv), xld, xld), packed ? P<int>(w.offs) + Q : nullptr, c->enc_rows_accounted);
   Ln.account_live(nullptr, 0);
-  c->cur_no_row_split = 0;
+  Ln.no_row_split = 0;
 
-  const SearchDims sd{Q, Lq, B, L, xld, packed, flags};
   StageView sv{};
   sv.Qcap = Q;
   sv.io = StageIO{nullptr, packed ? P<int32_t>(w.offs) : nullptr, P<int32_t>(w.last), P<int32_t>(w.mask)};
-  sv.kcache = P<float>(w.kcache); sv.vcache = P<float>(w.vcache); sv.depth = forks.empty() ? L : forks[0]; sv.dkv = d.d_kv;
+  sv.kcache = P<float>(w.kcache); sv.vcache = P<float>(w.vcache); sv.depth = nf ? forks[0] : L; sv.dkv = d.d_kv;
   for (int i = 0; i < 2; ++i) sv.st[i] = beam_state(w.score, w.lo, w.hi, w.tokens, w.anc, i, L);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_init_beams(sv.st[0], Q, B, tr->N, s); });
-  if (c->cur_margins) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_margin_init(P<double>(w.o_margin), Q, s); });
+  if (plan.margins) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_margin_init(P<double>(w.o_margin), Q, s); });
   if (w.sel_rs.p && select_radix_wanted(B, m->Vp()) && w.sel_rs.cap >= select_radix_ws_bytes(Q, B, m->Vp())) {
     RadixWs rs;   // the radix selection's histograms and counters start at zero (every step leaves them so)
     select_radix_carve(rs, w.sel_rs.p, nullptr, Q, B, m->Vp());
@@ -640,18 +639,17 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
   // still stepping at L. Without forks this is the plain loop of the reference.
   // Everything after the first fork works on what that fork left over — usually a handful of queries in buffers sized for
   // all of them: those GEMMs are enqueued as large-tile / small-tile pairs gated on the live count (GemmH2Args.small_live)
-  struct SmallLive { rpr_ctx* c; ~SmallLive() { c->cur_small_live = 0; } } small_guard{c};
   constexpr int small_live_rows = 1024;
   int t0 = 0;
-  for (size_t k = 0; k <= forks.size(); ++k) {
-    const int t1 = k < forks.size() ? forks[k] : L;
-    c->cur_small_live = k >= 1 ? small_live_rows : 0;
-    enqueue_steps(Ln, c, m, tr, sd, sv, t0, t1, shared0, taps);
-    if (k < forks.size()) {
-      const int next_depth = k + 1 < forks.size() ? forks[k + 1] : L;
-      const bool last_dropped = drop_last && k + 1 == forks.size();
-      const StageView nv = enqueue_fork(Ln, c, m, tr, sd, sv, t1, next_depth, w.tail[k], w.stage[k], !last_dropped);
-      enqueue_tail(Ln, c, m, tr, sd, sv, t1, w.tail[k]);
+  for (int k = 0; k <= nf; ++k) {
+    const int t1 = k < nf ? forks[k] : L;
+    Ln.small_live = k >= 1 ? small_live_rows : 0;
+    enqueue_steps(Ln, c, m, tr, plan, sv, t0, t1, shared0, taps);
+    if (k < nf) {
+      const int next_depth = k + 1 < nf ? forks[k + 1] : L;
+      const bool last_dropped = plan.drop_last && k + 1 == nf;
+      const StageView nv = enqueue_fork(Ln, c, m, tr, plan, sv, t1, next_depth, w.tail[k], w.stage[k], !last_dropped);
+      enqueue_tail(Ln, c, m, tr, plan, sv, t1, w.tail[k]);
       if (last_dropped) return;   // every query was finished by a tail pass (or flagged)
       sv = nv;
     }
@@ -676,13 +674,13 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
   const int nd = d.num_decoder_layers, V = d.V;
   hipStream_t s = Ln.s;
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_mask_lengths(P<int32_t>(w.mask), P<int32_t>(w.last), bz, Lq, s, c->status + 1); });
-  c->cur_no_row_split = 1;
+  Ln.no_row_split = 1;
   enqueue_encoder(Ln, c, m, bz, Lq, true);
-  const int xld = nd * 2 * inner;
+  const int xld = xkv_ld(m);
   linear(Ln, {P<float>(w.enc_out), P<__half>(w.enc_out_h), (size_t)T * dm, dm}, {d.dec_xkv, m->h_dec_xkv, xld, dm}, T,
          out_f32(P<float>(w.xkv), xld, xld), P<int>(w.offs) + bz, c->enc_rows_accounted);
   Ln.account_live(nullptr, 0);
-  c->cur_no_row_split = 0;
+  Ln.no_row_split = 0;
 
   float *qkv = P<float>(w.tr_x), *qb = P<float>(w.q);
   Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, 3, nd, R, nullptr, R);   // every row is live
@@ -719,7 +717,7 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
 
 int alloc_train_workspace(rpr_ctx* c, const rpr_model* m, int bz, int Lq, int ndoc, int L) {
   // the search workspace for bz queries with ndoc * L "beams" of one position covers every shared buffer
-  int e = alloc_workspace(c, m, bz, Lq, ndoc * L, 1);
+  int e = alloc_workspace(c, m, plain_plan(bz, Lq, ndoc * L, 1));
   if (e) return e;
   const size_t R = (size_t)bz * ndoc * L;
   e = ensure(c, c->ws.tr_x, R * 3 * m->inner() * sizeof(float));

@@ -98,7 +98,7 @@ int sort_codes(const uint16_t* codes, int64_t N, int L, std::vector<uint16_t>& s
 // For a search of length L over the sorted matrix: frac[t] (t = 0..L) = the fraction of the trie nodes at depth t
 // (distinct t-prefixes) under which exactly ONE distinct L-token sequence remains. A beam standing on such a node has
 // a single valid child at every remaining step, so its tokens are known and only its scores are missing; a query
-// whose beams all stand on such nodes is "forced" (api.hip: choose_forks; passes.hip: the forks and their tail passes). One pass over adjacent rows:
+// whose beams all stand on such nodes is "forced" (search_plan.h: plan_forks; passes.hip: the forks and their tail passes). One pass over adjacent rows:
 // c_i = min(lcp(row i-1, row i), L); the rows between two boundaries with c < L are one distinct sequence ("run");
 // with a / b the c of its left / right boundary (-1 at the ends of the matrix) the run opens a new node at every
 // depth t > a and is alone in its node at every depth t > max(a, b).

@@ -15,7 +15,7 @@ from conftest import ORDER_TOL, SCORE_TOL
 
 pytestmark = pytest.mark.gpu
 
-POOL = 4          # spare tail entries of a stage of fewer than 160 queries (csrc/internal.h: tail_extras_pool)
+POOL = 4          # spare tail entries of a stage of fewer than 160 queries (csrc/search_plan.h: tail_extras_pool)
 
 
 @pytest.fixture(scope="module")
