@@ -548,6 +548,41 @@ int rpr_rq_search(rpr_ctx* ctx, const float* queries, int32_t Q, int32_t d, cons
 int rpr_flat_search(rpr_ctx* ctx, const float* queries, int32_t Q, int32_t d, const float* x, int64_t n, int64_t row_base,
                     int32_t topk, int64_t* io_idx, float* io_scores, int32_t merge, void* stream);
 
+/* ---- cross-encoder teacher (reference modeling/cross_encoder.py: HF BertForSequenceClassification, one logit) ---- */
+/* A post-LayerNorm BERT encoder with absolute positions, erf GELU, the tanh pooler and a [1, hidden] classifier, run over a
+ * PACKED batch: only attended tokens exist as rows. Everything is fp32: the products are the exact-fp32
+ * MFMA GEMM whatever rpr_set_precision says. All weight pointers are device pointers owned by the caller, which keeps
+ * them alive while the handle lives; nn.Linear layout [out, in]. The per-layer tensors are stacked: layer l of qkv_w is
+ * qkv_w + l * 3 * hidden * hidden (rows: query, then key, then value), of ff1_w is ff1_w + l * d_ff * hidden, and so on. */
+typedef struct rpr_xenc_desc {
+  int32_t vocab_size, hidden, layers, heads, d_ff, max_pos, type_vocab;
+  float ln_eps;
+  const float *word_emb, *pos_emb, *type_emb, *emb_ln_w, *emb_ln_b;
+  const float *qkv_w, *qkv_b, *ao_w, *ao_b, *ln1_w, *ln1_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b, *ln2_w, *ln2_b;
+  const float *pool_w, *pool_b, *cls_w, *cls_b;
+} rpr_xenc_desc;
+typedef struct rpr_xenc rpr_xenc;
+
+/* Binds the weights (nothing is copied). RPR_ERR_INVALID: a NULL pointer, a dimension below 1, hidden % heads != 0. */
+int rpr_xenc_load(rpr_ctx* ctx, const rpr_xenc_desc* desc, rpr_xenc** out);
+void rpr_xenc_free(rpr_xenc* model);
+/* One logit per sequence. T = seq_off[bz] rows:
+ *   input_ids, token_type_ids, position_ids: [dev] int32 [T], the attended tokens of sequence 0, then of sequence 1, ...;
+ *       position_ids are the tokens' ORIGINAL positions (they differ from 0, 1, 2, ... where the mask had a hole). The
+ *       caller guarantees ids inside their tables (the kernel clamps them: memory safety, not semantics);
+ *   seq_off: [HOST] int32 [bz + 1], seq_off[0] = 0, non-decreasing: sequence b owns rows seq_off[b] .. seq_off[b + 1] - 1.
+ *       Read before the call returns;
+ *   out_scores: [dev] fp32 [bz]: classifier(tanh(pooler(first row of the sequence))).
+ * Asynchronous on `stream`; no host synchronisation once the workspaces are warm. They live in the context and grow on
+ * demand: a call with more rows than any before frees and reallocates them (hipFree synchronises the device) and drops
+ * the context's captured search graphs, like every other entry point that sizes a workspace. Deterministic: no atomics,
+ * the same call twice gives the same bits (another batch composition may pick another GEMM tile: last-bit differences).
+ * RPR_ERR_INVALID, before anything is enqueued: a head size other than 32 or 64, hidden % 32 or d_ff % 32 nonzero,
+ * hidden > 4096, bz < 1 or bz > 2^20, seq_off[0] != 0, an empty sequence, a sequence longer than min(max_pos, 512).
+ * RPR_ERR_OOM: no host memory for the tile list. */
+int rpr_xenc_score(rpr_ctx* ctx, rpr_xenc* model, const int32_t* input_ids, const int32_t* token_type_ids,
+                   const int32_t* position_ids, const int32_t* seq_off, int32_t bz, float* out_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,16 @@ class KernelStats(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("launches", C.c_int64), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class XencDesc(C.Structure):
+    """``rpr_xenc_desc``: the cross-encoder's dimensions and device weight pointers (stacked per layer)."""
+    _fields_ = ([(n, C.c_int32) for n in ("vocab_size", "hidden", "layers", "heads", "d_ff", "max_pos", "type_vocab")] +
+                [("ln_eps", C.c_float)] +
+                [(n, C.c_void_p) for n in ("word_emb", "pos_emb", "type_emb", "emb_ln_w", "emb_ln_b",
+                                           "qkv_w", "qkv_b", "ao_w", "ao_b", "ln1_w", "ln1_b",
+                                           "ff1_w", "ff1_b", "ff2_w", "ff2_b", "ln2_w", "ln2_b",
+                                           "pool_w", "pool_b", "cls_w", "cls_b")])
+
+
 # every symbol include/ripor_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "rpr_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -160,6 +170,10 @@ SIGNATURES = {
                                 C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rpr_flat_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rpr_xenc_load": (C.c_int, [C.c_void_p, C.POINTER(XencDesc), C.POINTER(C.c_void_p)]),
+    "rpr_xenc_free": (None, [C.c_void_p]),
+    "rpr_xenc_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                 C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -112,6 +112,34 @@ struct GemmArgs {
 };
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 
+// ---- BERT cross-encoder over a packed batch (xenc_kernels.hip; rpr_xenc_score in xenc_api.hip) ----------
+// T rows = the attended tokens of every sequence, sequence b owns rows seq_off[b] .. seq_off[b + 1] - 1. All fp32.
+struct XencEmbedArgs {
+  const int32_t *ids, *types, *pos; int T, H;          // per row: token, token type, original position
+  int vocab, type_vocab, max_pos;                      // table heights (ids are clamped into them)
+  const float *word, *typew, *posw, *ln_w, *ln_b; float eps;
+  float* out;                                          // [T, H]
+};
+struct XencAttnArgs {
+  const float* qkv;          // [T, 3 H]: q | k | v of every row, WITHOUT their biases
+  const float* bias;         // [3 H]: added while loading
+  const int32_t* seq_off;    // [dev, bz + 1]
+  const int2* tiles;         // [dev, ntiles]: (sequence, first query row inside it) of every 64-query tile
+  int ntiles, H, heads;
+  float* out;                // [T, H]
+};
+struct XencMetaChunk { static constexpr int N = 512; int32_t v[N]; };
+// dst[0 .. n) = host[0 .. n), carried by kernel arguments (async, the host array is free on return)
+hipError_t launch_xenc_meta(const int32_t* host, int n, int32_t* dst, hipStream_t s);
+hipError_t launch_xenc_embed_ln(const XencEmbedArgs& a, hipStream_t s);
+hipError_t launch_xenc_attn(const XencAttnArgs& a, int dh, hipStream_t s);   // dh = 32 or 64, sequences of 1 .. any length
+// out = LayerNorm(y + bias + resid) (biased variance); out may be resid
+hipError_t launch_xenc_bias_resid_ln(const float* y, const float* bias, const float* resid, const float* ln_w, const float* ln_b,
+                                     float eps, int T, int H, float* out, hipStream_t s);
+hipError_t launch_xenc_bias_gelu(float* x, const float* bias, int rows, int N, hipStream_t s);   // erf GELU, in place
+hipError_t launch_xenc_head(const float* x, const int32_t* seq_off, int bz, int H, const float* pool_w, const float* pool_b,
+                            const float* cls_w, const float* cls_b, float* out, hipStream_t s);
+
 // ---- residual quantization (gemm_f32.hip; rpr_rq_train / rpr_rq_encode in rq_api.hip) -------------------------------
 // Greedy residual k-means (DESIGN.md "Residual quantization"). Row tile of the assign kernel: 128 rows; d % 32 == 0,
 // K % 64 == 0, K <= 1024.

@@ -183,6 +183,9 @@ struct Workspace {
   // rpr_rq_encode_beam: the second residual plane (the first is rq_r), |r|^2 of the beam entries (two planes), the
   // candidates of a level (scores, then codes) and the parent slot / code history of every level (slots, then codes)
   DevBuf rq_r2, rq_bnorm, rq_cand, rq_bhist;
+  // rpr_xenc_score (xenc_api.hip): hidden states [T, H], q | k | v [T, 3 H], attention output [T, H], a product's raw
+  // result [T, H], the feed-forward intermediate [T, d_ff], and the tile list + sequence offsets
+  DevBuf xe_x, xe_qkv, xe_ctx, xe_tmp, xe_ff, xe_meta;
 };
 
 static_assert(sizeof(Workspace) % sizeof(DevBuf) == 0 && std::is_standard_layout<Workspace>::value,

@@ -1335,3 +1335,132 @@ def flat_search(ctx: Context, queries, x, topk: int, row_base: int = 0, state=No
     check(ctx.lib.rpr_flat_search(ctx.handle, q.data_ptr(), Q, d, x.data_ptr(), x.shape[0], int(row_base), topk, idx.data_ptr(),
                                   scores.data_ptr(), 0 if state is None else 1, _stream_ptr(dev)), "rpr_flat_search")
     return idx, scores
+
+
+# ---- cross-encoder teacher (rpr_xenc_*) ----------------------------------------------------------------
+XENC_MAX_LEN = 512   # attended tokens per sequence the attention kernel takes
+
+
+@dataclass
+class XencConfig:
+    vocab_size: int
+    hidden: int
+    layers: int
+    heads: int
+    d_ff: int
+    max_pos: int
+    type_vocab: int
+    ln_eps: float = 1e-12
+
+
+# the stacked per-layer tensors of rpr_xenc_desc and the global ones, with their shapes as functions of the config
+def xenc_weight_shapes(cfg: XencConfig) -> Dict[str, tuple]:
+    H, F, n = cfg.hidden, cfg.d_ff, cfg.layers
+    return {
+        "word_emb": (cfg.vocab_size, H), "pos_emb": (cfg.max_pos, H), "type_emb": (cfg.type_vocab, H), "emb_ln_w": (H,), "emb_ln_b": (H,),
+        "qkv_w": (n, 3 * H, H), "qkv_b": (n, 3 * H), "ao_w": (n, H, H), "ao_b": (n, H), "ln1_w": (n, H), "ln1_b": (n, H),
+        "ff1_w": (n, F, H), "ff1_b": (n, F), "ff2_w": (n, H, F), "ff2_b": (n, H), "ln2_w": (n, H), "ln2_b": (n, H),
+        "pool_w": (H, H), "pool_b": (H,), "cls_w": (H,), "cls_b": (1,),
+    }
+
+
+class XencModel:
+    """The BERT cross-encoder's weights bound to an ``rpr_xenc`` handle. ``weights``: name -> fp32 tensor in the layout of
+    ``xenc_weight_shapes`` (q, k, v rows stacked in that order; per-layer tensors stacked over the layers)."""
+
+    def __init__(self, ctx: Context, weights: Dict[str, torch.Tensor], cfg: XencConfig):
+        self.ctx, self.cfg = ctx, cfg
+        self.handle = None
+        self.w: Dict[str, torch.Tensor] = {}
+        for name, shape in xenc_weight_shapes(cfg).items():
+            if name not in weights:
+                raise KeyError(f"cross-encoder weight {name} is missing")
+            t = torch.as_tensor(weights[name], dtype=torch.float32)
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"cross-encoder weight {name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+            self.w[name] = t.to(ctx.device).contiguous()
+        d = _lib.XencDesc(vocab_size=cfg.vocab_size, hidden=cfg.hidden, layers=cfg.layers, heads=cfg.heads, d_ff=cfg.d_ff,
+                          max_pos=cfg.max_pos, type_vocab=cfg.type_vocab, ln_eps=float(cfg.ln_eps))
+        for name, t in self.w.items():
+            setattr(d, name, t.data_ptr())
+        h = C.c_void_p()
+        check(ctx.lib.rpr_xenc_load(ctx.handle, C.byref(d), C.byref(h)), "rpr_xenc_load")
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if self.handle is not None:
+                self.ctx.lib.rpr_xenc_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def xenc_pack(input_ids, token_type_ids, attention_mask):
+    """Padded [bz, L] batch -> the packed form ``rpr_xenc_score`` takes: (ids [T], types [T], positions [T], seq_off
+    int32 numpy [bz + 1]). Only attended tokens are kept, in row-major order; a token's position id is its original column,
+    so a hole in a mask does not shift the positions after it. The mask is read on the host (a device mask: one ``.cpu()``);
+    ids and types are gathered where they live. ``token_type_ids`` None = zeros. A row whose column 0 is masked raises
+    ``ValueError``: the pooled token is column 0."""
+    mask = torch.as_tensor(attention_mask)
+    ids = torch.as_tensor(input_ids)
+    if mask.dim() != 2 or ids.shape != mask.shape:
+        raise ValueError(f"input_ids {tuple(ids.shape)} and attention_mask {tuple(mask.shape)}: two equal [bz, L] shapes expected")
+    keep = mask.cpu() != 0
+    if keep.shape[0] and not bool(keep[:, 0].all()):
+        bad = (~keep[:, 0]).nonzero().flatten().tolist()
+        raise ValueError(f"attention_mask masks column 0 of rows {bad[:8]}: the pooled token of a cross-encoder pair is column 0")
+    lens = keep.sum(dim=1)
+    seq_off = np.zeros(keep.shape[0] + 1, dtype=np.int32)
+    np.cumsum(lens.numpy(), out=seq_off[1:])
+    rows, cols = keep.nonzero(as_tuple=True)   # row-major: sequence by sequence, columns ascending
+    r, c = rows.to(ids.device), cols.to(ids.device)
+    pk_ids = ids[r, c].to(torch.int32)
+    if token_type_ids is None:
+        pk_types = torch.zeros_like(pk_ids)
+    else:
+        tt = torch.as_tensor(token_type_ids)
+        if tt.shape != ids.shape:
+            raise ValueError(f"token_type_ids {tuple(tt.shape)} against input_ids {tuple(ids.shape)}")
+        pk_types = tt[rows.to(tt.device), cols.to(tt.device)].to(torch.int32)
+    return pk_ids, pk_types, cols.to(torch.int32), seq_off
+
+
+def xenc_score_packed(model: XencModel, pk_ids, pk_types, pk_pos, seq_off) -> torch.Tensor:
+    """``rpr_xenc_score`` on a packed batch (``xenc_pack``) -> fp32 [bz] logits on the model's device. Asynchronous."""
+    dev = model.ctx.device
+    ids = torch.as_tensor(pk_ids).to(device=dev, dtype=torch.int32).contiguous()
+    types = torch.as_tensor(pk_types).to(device=dev, dtype=torch.int32).contiguous()
+    pos = torch.as_tensor(pk_pos).to(device=dev, dtype=torch.int32).contiguous()
+    off = np.ascontiguousarray(seq_off, dtype=np.int32)
+    bz = off.shape[0] - 1
+    if bz < 1 or ids.dim() != 1 or ids.shape != types.shape or ids.shape != pos.shape or int(off[-1]) != ids.shape[0]:
+        raise ValueError("packed batch: ids, types and positions [T] with T = seq_off[-1], and at least one sequence, expected")
+    out = torch.empty((bz,), dtype=torch.float32, device=dev)
+    check(model.ctx.lib.rpr_xenc_score(model.ctx.handle, model.handle, ids.data_ptr(), types.data_ptr(), pos.data_ptr(),
+                                       off.ctypes.data_as(C.POINTER(C.c_int32)), bz, out.data_ptr(), _stream_ptr(dev)),
+          "rpr_xenc_score")
+    return out
+
+
+def xenc_score(model: XencModel, input_ids, token_type_ids, attention_mask) -> torch.Tensor:
+    """One logit per (query, passage) row of a padded tokenizer batch -> fp32 [bz] on the model's device. Packs on the way
+    (``xenc_pack``), so padding costs nothing. Token, type and position ids outside the model's tables raise ``ValueError``.
+    With device tensors the call synchronises twice (the mask's ``.cpu()`` and the range check of ids and types); with the
+    host tensors of a tokenizer not at all."""
+    cfg = model.cfg
+    ids = torch.as_tensor(input_ids)
+    if ids.dim() != 2 or ids.shape[0] < 1:
+        raise ValueError("input_ids [bz, L] with bz >= 1 expected")
+    if ids.shape[1] > cfg.max_pos:
+        raise ValueError(f"batch padded to {ids.shape[1]} columns, the model has {cfg.max_pos} positions")
+    pk_ids, pk_types, pk_pos, seq_off = xenc_pack(ids, token_type_ids, attention_mask)
+    if pk_ids.numel():
+        # one small transfer: free for the host tensors a tokenizer hands over (rerank.py), one synchronisation for device tensors
+        lo, hi, tlo, thi = torch.stack([pk_ids.min(), pk_ids.max(), pk_types.min().to(pk_ids.device),
+                                        pk_types.max().to(pk_ids.device)]).tolist()
+        if lo < 0 or hi >= cfg.vocab_size:
+            raise ValueError(f"input_ids in [{lo}, {hi}] leave the vocabulary of {cfg.vocab_size}")
+        if tlo < 0 or thi >= cfg.type_vocab:
+            raise ValueError(f"token_type_ids in [{tlo}, {thi}] leave the {cfg.type_vocab} token types")
+    return xenc_score_packed(model, pk_ids, pk_types, pk_pos, seq_off)
