@@ -550,8 +550,9 @@ int rpr_flat_search(rpr_ctx* ctx, const float* queries, int32_t Q, int32_t d, co
 
 /* ---- cross-encoder teacher (reference modeling/cross_encoder.py: HF BertForSequenceClassification, one logit) ---- */
 /* A post-LayerNorm BERT encoder with absolute positions, erf GELU, the tanh pooler and a [1, hidden] classifier, run over a
- * PACKED batch: only attended tokens exist as rows. Everything is fp32: the products are the exact-fp32
- * MFMA GEMM whatever rpr_set_precision says. All weight pointers are device pointers owned by the caller, which keeps
+ * PACKED batch: only attended tokens exist as rows. By default everything is fp32: the products are the
+ * exact-fp32 MFMA GEMM whatever rpr_set_precision says (rpr_xenc_set_precision below switches one model to f16 operands).
+ * All weight pointers are device pointers owned by the caller, which keeps
  * them alive while the handle lives; nn.Linear layout [out, in]. The per-layer tensors are stacked: layer l of qkv_w is
  * qkv_w + l * 3 * hidden * hidden (rows: query, then key, then value), of ff1_w is ff1_w + l * d_ff * hidden, and so on. */
 typedef struct rpr_xenc_desc {
@@ -582,6 +583,21 @@ void rpr_xenc_free(rpr_xenc* model);
  * RPR_ERR_OOM: no host memory for the tile list. */
 int rpr_xenc_score(rpr_ctx* ctx, rpr_xenc* model, const int32_t* input_ids, const int32_t* token_type_ids,
                    const int32_t* position_ids, const int32_t* seq_off, int32_t bz, float* out_scores, void* stream);
+/* Precision of one model's rpr_xenc_score calls (a new model is RPR_XENC_F32).
+ *   RPR_XENC_F32: fp32 throughout, as described above.
+ *   RPR_XENC_F16: the arithmetic of torch's fp16 autocast, how the reference runs its teacher: the four products of a layer
+ *       and both attention products take f16 operands (round to nearest even) and accumulate in fp32 on the f16 matrix
+ *       cores; q | k | v, the attention probabilities, the attention output and the GELU output are stored as f16; the
+ *       residual stream, LayerNorm, softmax, biases, embeddings, pooler and classifier stay fp32. A stored value beyond
+ *       +-65504 becomes +-inf and the pair's score non-finite, as under autocast: check the scores with isfinite.
+ *       Same limits, determinism and workspace rules as the fp32 mode.
+ * The first switch to RPR_XENC_F16 makes f16 copies of qkv_w, ao_w, ff1_w and ff2_w on `stream` (owned by the model, freed
+ * by rpr_xenc_free; the fp32 weights must not change afterwards). Switching back keeps the copies and restores the fp32
+ * bits. Any other value: RPR_ERR_INVALID, nothing changes. RPR_ERR_OOM: no device memory for the copies. */
+#define RPR_XENC_F32 0
+#define RPR_XENC_F16 1
+int rpr_xenc_set_precision(rpr_ctx* ctx, rpr_xenc* model, int precision, void* stream);
+int rpr_xenc_get_precision(const rpr_xenc* model);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,8 @@ SIGNATURES = {
     "rpr_xenc_free": (None, [C.c_void_p]),
     "rpr_xenc_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
                                  C.c_void_p, C.c_void_p]),
+    "rpr_xenc_set_precision": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rpr_xenc_get_precision": (C.c_int, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -139,6 +139,21 @@ hipError_t launch_xenc_bias_resid_ln(const float* y, const float* bias, const fl
 hipError_t launch_xenc_bias_gelu(float* x, const float* bias, int rows, int N, hipStream_t s);   // erf GELU, in place
 hipError_t launch_xenc_head(const float* x, const int32_t* seq_off, int bz, int H, const float* pool_w, const float* pool_b,
                             const float* cls_w, const float* cls_b, float* out, hipStream_t s);
+// The f16 mode (xenc_half.hip): f16 matrix operands, fp32 accumulation, fp32 residual stream / LayerNorm / softmax.
+hipError_t launch_xenc_f32_to_f16(const float* src, __half* dst, size_t n, hipStream_t s);   // round to nearest even
+hipError_t launch_xenc_embed_ln_h(const XencEmbedArgs& a, __half* outh, hipStream_t s);       // a.out fp32 and its f16 copy
+// out = LayerNorm(y) (y = product + bias + residual, epilogue XENC_EPI_RESID) and its f16 copy; out may be y
+hipError_t launch_xenc_ln_h(const float* y, const float* ln_w, const float* ln_b, float eps, int T, int H, float* out, __half* outh,
+                            hipStream_t s);
+// C[M, N] = A[M, K] . W[N, K]^T, f16 operands, fp32 accumulators; M >= 1, N % 32 == 0, K % 32 == 0
+constexpr int XENC_EPI_BIAS = 0;        // + bias -> outh (f16)
+constexpr int XENC_EPI_BIAS_GELU = 1;   // + bias, erf GELU in fp32 -> outh (f16)
+constexpr int XENC_EPI_RESID = 2;       // + bias + resid (fp32) -> outf (fp32)
+hipError_t launch_xenc_gemm_h(int epilogue, const __half* A, const __half* W, const float* bias, const float* resid, __half* outh,
+                              float* outf, int M, int N, int K, hipStream_t s);
+// qkv [T, 3 H] f16 with the biases in it -> out [T, H] f16; dh = 32 or 64
+hipError_t launch_xenc_attn_h(const __half* qkv, const int32_t* seq_off, const int2* tiles, int ntiles, int H, int heads, int dh,
+                              __half* out, hipStream_t s);
 
 // ---- residual quantization (gemm_f32.hip; rpr_rq_train / rpr_rq_encode in rq_api.hip) -------------------------------
 // Greedy residual k-means (DESIGN.md "Residual quantization"). Row tile of the assign kernel: 128 rows; d % 32 == 0,

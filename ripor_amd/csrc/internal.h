@@ -186,6 +186,9 @@ struct Workspace {
   // rpr_xenc_score (xenc_api.hip): hidden states [T, H], q | k | v [T, 3 H], attention output [T, H], a product's raw
   // result [T, H], the feed-forward intermediate [T, d_ff], and the tile list + sequence offsets
   DevBuf xe_x, xe_qkv, xe_ctx, xe_tmp, xe_ff, xe_meta;
+  // its f16 mode (rpr_xenc_set_precision): f16 copy of the hidden states, q | k | v with their biases, attention output
+  // and GELU output; xe_x (fp32 residual stream), xe_tmp and xe_meta are shared with the fp32 mode
+  DevBuf xe_xh, xe_qkvh, xe_ctxh, xe_ffh;
 };
 
 static_assert(sizeof(Workspace) % sizeof(DevBuf) == 0 && std::is_standard_layout<Workspace>::value,

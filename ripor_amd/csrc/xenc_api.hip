@@ -1,5 +1,6 @@
 // C ABI of the cross-encoder teacher: rpr_xenc_load / rpr_xenc_free / rpr_xenc_score (kernels in xenc_kernels.hip, the
-// products through the exact-fp32 GEMM of gemm_f32.hip).
+// products through the exact-fp32 GEMM of gemm_f32.hip) and its opt-in f16 mode, rpr_xenc_set_precision (kernels in
+// xenc_half.hip); DESIGN.md §9f.
 #include <new>
 #include <vector>
 
@@ -10,7 +11,69 @@ using namespace rpr;
 struct rpr_xenc {
   rpr_ctx* ctx;
   rpr_xenc_desc d;
+  int device;                    // of ctx, kept here: the model may outlive a look at its ctx
+  int precision = RPR_XENC_F32;
+  __half* wh = nullptr;          // f16 copies of qkv_w | ao_w | ff1_w | ff2_w (one allocation, made by the first switch to f16)
+  const __half *qkv_h = nullptr, *ao_h = nullptr, *ff1_h = nullptr, *ff2_h = nullptr;
 };
+
+namespace {
+
+// the f16 mode of rpr_xenc_score: the same layer walk with f16 operands. X stays fp32; Xh, QKV, CTX and FF are f16.
+int score_f16(rpr_ctx* c, rpr_xenc* x, const int32_t* input_ids, const int32_t* token_type_ids, const int32_t* position_ids,
+              const int32_t* seq_off, int32_t bz, const std::vector<int32_t>& meta, int ntiles, float* out_scores, hipStream_t s) {
+  const rpr_xenc_desc& d = x->d;
+  const int H = d.hidden, F = d.d_ff, dh = H / d.heads, T = seq_off[bz];
+  Workspace& w = c->ws;
+  int e = ensure(c, w.xe_x, (size_t)T * H * sizeof(float));
+  if (!e) e = ensure(c, w.xe_tmp, (size_t)T * H * sizeof(float));
+  if (!e) e = ensure(c, w.xe_meta, meta.size() * sizeof(int32_t));
+  if (!e) e = ensure(c, w.xe_xh, (size_t)T * H * sizeof(__half));
+  if (!e) e = ensure(c, w.xe_qkvh, (size_t)T * 3 * H * sizeof(__half));
+  if (!e) e = ensure(c, w.xe_ctxh, (size_t)T * H * sizeof(__half));
+  if (!e) e = ensure(c, w.xe_ffh, (size_t)T * F * sizeof(__half));
+  if (e) return e;
+  float *X = P<float>(w.xe_x), *TMP = P<float>(w.xe_tmp);
+  __half *Xh = P<__half>(w.xe_xh), *QKVh = P<__half>(w.xe_qkvh), *CTXh = P<__half>(w.xe_ctxh), *FFh = P<__half>(w.xe_ffh);
+  const int2* tiles = P<int2>(w.xe_meta);
+  const int32_t* off_dev = P<int32_t>(w.xe_meta) + (size_t)2 * ntiles;
+
+  Launcher Ln{c, s};
+  const double Td = (double)T;
+  Ln.run(RPR_K_OTHER, 0, 4.0 * meta.size(), [&] { return launch_xenc_meta(meta.data(), (int)meta.size(), P<int32_t>(w.xe_meta), s); });
+  XencEmbedArgs ea{input_ids, token_type_ids, position_ids, T, H, d.vocab_size, d.type_vocab, d.max_pos,
+                   d.word_emb, d.type_emb, d.pos_emb, d.emb_ln_w, d.emb_ln_b, d.ln_eps, X};
+  Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 4 + 2.0) * Td * H, [&] { return launch_xenc_embed_ln_h(ea, Xh, s); });
+  // bytes: f16 operands; out_b = bytes per output element written (+ read, for the residual)
+  auto gemm = [&](int epi, const __half* A, const __half* W, const float* bias, int N, int K, __half* outh, float* outf) {
+    const double out_b = epi == XENC_EPI_RESID ? 8.0 : 2.0;
+    Ln.run(RPR_K_GEMM, 2.0 * Td * N * K, 2.0 * (Td * K + (double)N * K) + out_b * Td * N,
+           [&] { return launch_xenc_gemm_h(epi, A, W, bias, epi == XENC_EPI_RESID ? X : nullptr, outh, outf, T, N, K, s); });
+  };
+  double qk_pairs = 0.0;
+  for (int b = 0; b < bz; ++b) { const double len = seq_off[b + 1] - seq_off[b]; qk_pairs += len * len; }
+  for (int l = 0; l < d.layers; ++l) {
+    const size_t HH = (size_t)H * H, FH = (size_t)F * H;
+    gemm(XENC_EPI_BIAS, Xh, x->qkv_h + l * 3 * HH, d.qkv_b + (size_t)l * 3 * H, 3 * H, H, QKVh, nullptr);
+    Ln.run(RPR_K_ENC_ATTN, 4.0 * qk_pairs * H, 2.0 * 4 * Td * H,
+           [&] { return launch_xenc_attn_h(QKVh, off_dev, tiles, ntiles, H, d.heads, dh, CTXh, s); });
+    gemm(XENC_EPI_RESID, CTXh, x->ao_h + l * HH, d.ao_b + (size_t)l * H, H, H, nullptr, TMP);
+    Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 2 + 2.0) * Td * H, [&] {
+      return launch_xenc_ln_h(TMP, d.ln1_w + (size_t)l * H, d.ln1_b + (size_t)l * H, d.ln_eps, T, H, X, Xh, s);
+    });
+    gemm(XENC_EPI_BIAS_GELU, Xh, x->ff1_h + l * FH, d.ff1_b + (size_t)l * F, F, H, FFh, nullptr);
+    gemm(XENC_EPI_RESID, FFh, x->ff2_h + l * FH, d.ff2_b + (size_t)l * H, H, F, nullptr, TMP);
+    Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 2 + 2.0) * Td * H, [&] {
+      return launch_xenc_ln_h(TMP, d.ln2_w + (size_t)l * H, d.ln2_b + (size_t)l * H, d.ln_eps, T, H, X, Xh, s);
+    });
+  }
+  Ln.run(RPR_K_OTHER, 2.0 * bz * ((double)H * H + H), 4.0 * ((double)H * H + 2.0 * bz * H), [&] {
+    return launch_xenc_head(X, off_dev, bz, H, d.pool_w, d.pool_b, d.cls_w, d.cls_b, out_scores, s);
+  });
+  return Ln.err;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -23,11 +86,51 @@ int rpr_xenc_load(rpr_ctx* c, const rpr_xenc_desc* d, rpr_xenc** out) {
   RPR_REQUIRE(d->word_emb && d->pos_emb && d->type_emb && d->emb_ln_w && d->emb_ln_b && d->qkv_w && d->qkv_b && d->ao_w && d->ao_b &&
               d->ln1_w && d->ln1_b && d->ff1_w && d->ff1_b && d->ff2_w && d->ff2_b && d->ln2_w && d->ln2_b && d->pool_w && d->pool_b &&
               d->cls_w && d->cls_b, "NULL weight pointer");
-  *out = new rpr_xenc{c, *d};
+  rpr_xenc* x = new rpr_xenc{};
+  x->ctx = c; x->d = *d; x->device = c->device;
+  *out = x;
   return RPR_OK;
 }
 
-void rpr_xenc_free(rpr_xenc* x) { delete x; }
+void rpr_xenc_free(rpr_xenc* x) {
+  if (!x) return;
+  if (x->wh) {
+    (void)hipSetDevice(x->device);
+    (void)hipFree(x->wh);
+  }
+  delete x;
+}
+
+int rpr_xenc_get_precision(const rpr_xenc* x) { return x ? x->precision : RPR_ERR_INVALID; }
+
+int rpr_xenc_set_precision(rpr_ctx* c, rpr_xenc* x, int precision, void* stream) {
+  RPR_REQUIRE(c && x, "NULL argument");
+  RPR_REQUIRE(x->ctx == c, "the cross-encoder belongs to another ctx");
+  RPR_REQUIRE(precision == RPR_XENC_F32 || precision == RPR_XENC_F16, "precision is neither 0 (fp32) nor 1 (f16 operands)");
+  if (precision == RPR_XENC_F16 && !x->wh) {
+    const rpr_xenc_desc& d = x->d;
+    const size_t HH = (size_t)d.hidden * d.hidden, FH = (size_t)d.d_ff * d.hidden, L = (size_t)d.layers;
+    const size_t n_qkv = L * 3 * HH, n_ao = L * HH, n_ff = L * FH;   // (each a multiple of 8 halves when hidden % 32 == 0)
+    RPR_HIP(hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    __half* wh = nullptr;
+    RPR_HIP(hipMalloc(&wh, (n_qkv + n_ao + 2 * n_ff) * sizeof(__half)));
+    const float* src[4] = {d.qkv_w, d.ao_w, d.ff1_w, d.ff2_w};
+    const size_t n[4] = {n_qkv, n_ao, n_ff, n_ff};
+    Launcher Ln{c, s};
+    size_t at = 0;
+    for (int i = 0; i < 4; ++i) {
+      __half* dst = wh + at;
+      Ln.run(RPR_K_OTHER, 0, 6.0 * n[i], [&] { return launch_xenc_f32_to_f16(src[i], dst, n[i], s); });
+      at += n[i];
+    }
+    if (Ln.err) { (void)hipFree(wh); return Ln.err; }
+    x->wh = wh;
+    x->qkv_h = wh; x->ao_h = wh + n_qkv; x->ff1_h = wh + n_qkv + n_ao; x->ff2_h = wh + n_qkv + n_ao + n_ff;
+  }
+  x->precision = precision;
+  return RPR_OK;
+}
 
 int rpr_xenc_score(rpr_ctx* c, rpr_xenc* x, const int32_t* input_ids, const int32_t* token_type_ids, const int32_t* position_ids,
                    const int32_t* seq_off, int32_t bz, float* out_scores, void* stream) {
@@ -62,6 +165,8 @@ int rpr_xenc_score(rpr_ctx* c, rpr_xenc* x, const int32_t* input_ids, const int3
 
   RPR_HIP(hipSetDevice(c->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (x->precision == RPR_XENC_F16)
+    return score_f16(c, x, input_ids, token_type_ids, position_ids, seq_off, bz, meta, ntiles, out_scores, s);
   Workspace& w = c->ws;
   int e = ensure(c, w.xe_x, (size_t)T * H * sizeof(float));
   if (!e) e = ensure(c, w.xe_qkv, (size_t)T * 3 * H * sizeof(float));

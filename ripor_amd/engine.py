@@ -1339,6 +1339,8 @@ def flat_search(ctx: Context, queries, x, topk: int, row_base: int = 0, state=No
 
 # ---- cross-encoder teacher (rpr_xenc_*) ----------------------------------------------------------------
 XENC_MAX_LEN = 512   # attended tokens per sequence the attention kernel takes
+# rpr_xenc_set_precision: exact fp32 (default) | f16 matrix operands, fp32 accumulation (the reference's fp16 autocast)
+XENC_PRECISIONS = {"f32": 0, "f16": 1}
 
 
 @dataclass
@@ -1386,6 +1388,19 @@ class XencModel:
         h = C.c_void_p()
         check(ctx.lib.rpr_xenc_load(ctx.handle, C.byref(d), C.byref(h)), "rpr_xenc_load")
         self.handle = h
+
+    def set_precision(self, precision: str) -> None:
+        """``"f32"`` (default) or ``"f16"``: what ``xenc_score`` of this model computes in from now on. The first switch to
+        f16 makes f16 copies of the four per-layer weight stacks on the current stream; the library owns them."""
+        if precision not in XENC_PRECISIONS:
+            raise ValueError(f"cross-encoder precision {precision!r}; one of {sorted(XENC_PRECISIONS)} expected")
+        check(self.ctx.lib.rpr_xenc_set_precision(self.ctx.handle, self.handle, XENC_PRECISIONS[precision], _stream_ptr(self.ctx.device)),
+              "rpr_xenc_set_precision")
+
+    @property
+    def precision(self) -> str:
+        code = self.ctx.lib.rpr_xenc_get_precision(self.handle)
+        return {v: k for k, v in XENC_PRECISIONS.items()}[code]
 
     def __del__(self):
         try:

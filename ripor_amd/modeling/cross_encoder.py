@@ -1,7 +1,8 @@
 """The cross-encoder teacher (reference modeling/cross_encoder.py:7-34): ``CrossEncoder(model_name_or_path)`` scores
 (query, passage) pairs with a BERT ``AutoModelForSequenceClassification`` checkpoint such as
-``cross-encoder/ms-marco-MiniLM-L-6-v2`` — here on the HIP path (``engine.xenc_score``), in exact fp32, over
-a packed batch in which padding does not exist.
+``cross-encoder/ms-marco-MiniLM-L-6-v2`` — here on the HIP path (``engine.xenc_score``), in exact fp32 or,
+with ``precision="f16"``, with f16 matrix operands and fp32 accumulation (the reference's fp16 autocast), over a packed
+batch in which padding does not exist.
 
 Same surface as the reference class for inference: ``from_pretrained``, ``.to(device)``, ``.eval()``,
 ``forward(**{"qd_kwargs": ...})`` -> logits [bz], ``rerank_forward(qd_kwargs)`` -> ``{"scores": ...}``. Training the teacher
@@ -70,8 +71,11 @@ def weights_from_state_dict(sd: Dict[str, torch.Tensor], cfg: E.XencConfig) -> D
 
 
 class CrossEncoder:
-    def __init__(self, model_name_or_path: str):
+    def __init__(self, model_name_or_path: str, precision: str = "f32"):
         from .t5_generative_retriever import _load_checkpoint
+        if precision not in E.XENC_PRECISIONS:
+            raise ValueError(f"CrossEncoder: precision {precision!r}; one of {sorted(E.XENC_PRECISIONS)} expected")
+        self.precision = precision
         self.name_or_path = model_name_or_path
         self.cfg = read_config(model_name_or_path)
         self._weights = weights_from_state_dict(_load_checkpoint(model_name_or_path), self.cfg)
@@ -82,14 +86,24 @@ class CrossEncoder:
         self.model_args = None   # (reference: incompatible with previous models)
 
     @classmethod
-    def from_pretrained(cls, model_name_or_path: str) -> "CrossEncoder":
-        return cls(model_name_or_path)
+    def from_pretrained(cls, model_name_or_path: str, precision: str = "f32") -> "CrossEncoder":
+        return cls(model_name_or_path, precision=precision)
+
+    def set_precision(self, precision: str) -> "CrossEncoder":
+        """``"f32"`` or ``"f16"`` (``engine.XencModel.set_precision``); before ``.to(device)`` it is applied there."""
+        if precision not in E.XENC_PRECISIONS:
+            raise ValueError(f"CrossEncoder: precision {precision!r}; one of {sorted(E.XENC_PRECISIONS)} expected")
+        self.precision = precision
+        if self._model is not None:
+            self._model.set_precision(precision)
+        return self
 
     def to(self, device) -> "CrossEncoder":
         """Binds the weights on a HIP device (an int is a device index, like the reference's ``model.to(local_rank)``)."""
         ctx = E.Context.get(device)
         if self._model is None or self._model.ctx is not ctx:
             self._model = E.XencModel(ctx, self._weights, self.cfg)
+        self._model.set_precision(self.precision)
         return self
 
     def eval(self) -> "CrossEncoder":

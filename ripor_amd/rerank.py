@@ -13,8 +13,10 @@ Differences by design:
 * The shard file is ``<dir>/<basename without ".train.json">_teacher_score_<rank>.train.json``. The reference takes
   ``path.split(".")[0]`` as the prefix, which cuts a path such as ``./out/x.train.json`` at its first dot (to an empty
   string); for the paths the reference scripts pass (no dot before the extension) both give the same file.
-* Scores are exact fp32 (the reference runs the teacher under fp16 autocast), and a batch is packed: its padding is never
-  computed.
+* Scores are exact fp32 by default (the reference runs the teacher under fp16 autocast), and a batch is packed: its
+  padding is never computed. ``--teacher_precision=fp16`` (not a reference flag) takes the reference's arithmetic instead:
+  f16 matrix operands with fp32 accumulation (``rpr_xenc_set_precision``). A score that left the f16 range
+  on the way is non-finite, as under autocast; the task then stops and points to fp32.
 * The merge does not assert that the number of shards equals ``torch.cuda.device_count()``: it may run on any machine.
 * The process group and the device follow ``evaluate.py``: ``ddp_setup`` (``RPR_DIST_BACKEND``), ``RPR_EVAL_DEVICE``.
 """
@@ -33,6 +35,9 @@ UNBUILT_TASKS = ("rerank_for_eval", "rerank_for_create_trainset", "rerank_for_cr
                  "query_to_docid_rerank_for_qid_smtids_2", "teacher_rerank_for_qid_smtids", "teacher_rerank_for_qid_smtids_2",
                  "cross_encoder_rerank_for_same_prefix_docid", "cross_encoder_rerank_for_same_prefix_docid_2",
                  "cross_encoder_rerank_for_same_reldocid_hard_docids", "cross_encoder_rerank_for_same_reldocid_hard_docids_2")
+
+# --teacher_precision -> CrossEncoder precision
+TEACHER_PRECISIONS = {"fp32": "f32", "fp16": "f16"}
 
 Triple = Tuple[str, str, str]   # (qid, docid, smtid)
 
@@ -75,9 +80,12 @@ def teacher_score_path(qid_smtid_docids_path: str, rank: int) -> str:
 
 
 def score_triples(triples: Sequence[Triple], qid_to_query: Dict[str, str], docid_to_doc: Dict[str, str], tokenizer,
-                  score_fn: Callable, batch_size: int, max_length: int) -> List[float]:
+                  score_fn: Callable, batch_size: int, max_length: int,
+                  require_finite: bool = False) -> List[float]:
     """The loader and the loop of reference dataloader.py:142-152 / tasks/reranker.py:61-76: batches of ``batch_size``
-    triples in order, the reference's tokenizer call, ``score_fn(qd_kwargs)`` -> [bz] scores."""
+    triples in order, the reference's tokenizer call, ``score_fn(qd_kwargs)`` -> [bz] scores. ``require_finite`` (the f16
+    teacher): a non-finite score of a batch, which is on the host by then, raises."""
+    import math
     scores: List[float] = []
     for b0 in range(0, len(triples), batch_size):
         chunk = triples[b0:b0 + batch_size]
@@ -85,7 +93,12 @@ def score_triples(triples: Sequence[Triple], qid_to_query: Dict[str, str], docid
         docs = [docid_to_doc[docid] for _, docid, _ in chunk]
         qd_kwargs = tokenizer(queries, docs, padding=True, truncation='longest_first', return_attention_mask=True,
                               return_tensors="pt", max_length=max_length)
-        scores.extend(score_fn(qd_kwargs).cpu().tolist())
+        got = score_fn(qd_kwargs).cpu().tolist()
+        if require_finite and not all(math.isfinite(v) for v in got):
+            bad = [chunk[i] for i, v in enumerate(got) if not math.isfinite(v)]
+            raise FloatingPointError(f"the fp16 teacher gave a non-finite score for {len(bad)} pairs (first: qid, docid, smtid = "
+                                     f"{bad[0]}): an activation left the f16 range; run with --teacher_precision=fp32")
+        scores.extend(got)
     return scores
 
 
@@ -99,7 +112,10 @@ def cross_encoder_rerank_for_qid_smtid_docids(args):
     world = dist.get_world_size() if dist.is_initialized() else 1
     local_rank = max(0, int(args.local_rank if args.local_rank >= 0 else os.environ.get("LOCAL_RANK", 0)))
     print("model_name_or_path for cross_encoder: ", args.model_name_or_path)
-    model = CrossEncoder(args.model_name_or_path)
+    precision = TEACHER_PRECISIONS[args.teacher_precision]
+    if rank == 0:
+        print("teacher precision: ", args.teacher_precision)
+    model = CrossEncoder(args.model_name_or_path, precision=precision)
     model.to(_device_index(local_rank))
     model.eval()
     with open(args.qid_smtid_docids_path) as fin:
@@ -110,7 +126,8 @@ def cross_encoder_rerank_for_qid_smtid_docids(args):
     triples = build_triples(sampled)
     tokenizer = AutoTokenizer.from_pretrained(args.model_name_or_path)
     scores = score_triples(triples, read_tsv(args.train_queries_path), read_tsv(os.path.join(args.collection_path, "raw.tsv")),
-                           tokenizer, lambda kw: model.rerank_forward(kw)["scores"], args.batch_size, args.max_length)
+                           tokenizer, lambda kw: model.rerank_forward(kw)["scores"], args.batch_size, args.max_length,
+                           require_finite=precision == "f16")
     out_path = teacher_score_path(args.qid_smtid_docids_path, rank)
     with open(out_path, "w") as fout:
         json.dump(triple_ids_to_json_output(scores, triples), fout)
@@ -176,6 +193,8 @@ def get_args(argv=None):
     ap.add_argument("--qid_to_reldocid_hard_docids_path", default=None)
     ap.add_argument("--eval_qrel_path", default=None)
     ap.add_argument("--eval_metrics", default=None)
+    # not a reference flag: fp32 = exact fp32 (default), fp16 = f16 operands with fp32 accumulation (the reference's autocast)
+    ap.add_argument("--teacher_precision", choices=sorted(TEACHER_PRECISIONS), default="fp32")
     return ap.parse_args(argv)
 
 

@@ -6,11 +6,11 @@ weights on --pairs (query, passage) pairs, for two seeded inputs:
   mix   a length mix as MS MARCO pairs give it: lengths 20 .. --max_len, mean about 90, padded to the longest.
 
 Per input: pairs/s (best and median of --repeats warm calls by device events, the packing and the upload included), then
-one profiled call (per-kernel-class device events) for the fp32 rate of the GEMMs against the 157.3 TF/s fp32 MFMA peak
-and the share of device time in attention. As the yardstick on the same card and inputs, HF BertForSequenceClassification
+one profiled call (per-kernel-class device events) for the rate of the GEMMs against the peak of the mode (--precision f32:
+the 157.3 TF/s fp32 MFMA peak; f16: the 2516.6 TF/s dense f16 MFMA peak) and the share of device time in attention. As the yardstick on the same card and inputs, HF BertForSequenceClassification
 in torch on the padded batch, in fp32 and under fp16 autocast (how the reference runs its teacher). One JSON line on stdout.
 
-  python tools/xenc_bench.py --pairs 256 --max_len 256"""
+  python tools/xenc_bench.py --pairs 256 --max_len 256 [--precision f16]"""
 import argparse
 import json
 import os
@@ -22,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PEAK_F32_TFLOPS = 157.3
+PEAK_F16_TFLOPS = 2516.6   # dense f16 MFMA
 DIMS = dict(vocab_size=30522, hidden=384, layers=6, heads=12, d_ff=1536, max_pos=512, type_vocab=2)
 
 
@@ -78,6 +79,7 @@ def main():
     ap.add_argument("--max_len", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--no_torch", action="store_true", help="skip the HF yardstick")
+    ap.add_argument("--precision", choices=("f32", "f16"), default="f32", help="engine.XencModel.set_precision")
     args = ap.parse_args()
     from ripor_amd import engine as E
     ctx = E.Context.get(0)
@@ -89,8 +91,11 @@ def main():
         weights[name] = (1.0 + 0.2 * n) if name.endswith("ln_w") or name in ("ln1_w", "ln2_w") else \
             (0.1 * n) if name.endswith("_b") else n if name.endswith("_emb") else n / cfg.hidden ** 0.5
     model = E.XencModel(ctx, weights, cfg)
+    model.set_precision(args.precision)
+    peak = PEAK_F16_TFLOPS if args.precision == "f16" else PEAK_F32_TFLOPS
     hf = None if args.no_torch else hf_model(weights, cfg).cuda()
-    out = dict(dims=DIMS, pairs=args.pairs, max_len=args.max_len, peak_f32_tflops=PEAK_F32_TFLOPS, inputs={})
+    out = dict(dims=DIMS, pairs=args.pairs, max_len=args.max_len, precision=model.precision, peak_f32_tflops=PEAK_F32_TFLOPS,
+               peak_f16_tflops=PEAK_F16_TFLOPS, inputs={})
     for kind in ("full", "mix"):
         ids, types, mask, lens = make_inputs(kind, args.pairs, args.max_len, seed=11)
         run = lambda: E.xenc_score(model, ids, types, mask)  # noqa: E731
@@ -107,7 +112,10 @@ def main():
                  kernel_ms=dev_ms, gemm_ms=gemm["total_ms"], gemm_tflops=gemm["flops"] / (gemm["total_ms"] * 1e-3) / 1e12,
                  attn_ms=prof["enc_attn"]["total_ms"], attn_share=prof["enc_attn"]["total_ms"] / dev_ms,
                  other_ms=prof["other"]["total_ms"])
-        r["gemm_frac_of_peak"] = r["gemm_tflops"] / PEAK_F32_TFLOPS
+        r["gemm_frac_of_peak"] = r["gemm_tflops"] / peak
+        r["gemm_gbytes_per_s"] = gemm["bytes"] / (gemm["total_ms"] * 1e-3) / 1e9   # operands and results once: a lower bound
+        r["finite"] = bool(torch.isfinite(ours).all())
+        r["score_sha256"] = __import__("hashlib").sha256(ours.cpu().numpy().tobytes()).hexdigest()
         if hf is not None:
             kw = {"input_ids": ids.cuda(), "token_type_ids": types.cuda(), "attention_mask": mask.cuda()}
             for label, amp in (("torch_fp32", False), ("torch_fp16_autocast", True)):
