@@ -113,7 +113,8 @@ struct GemmArgs {
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 
 // ---- BERT cross-encoder over a packed batch (xenc_kernels.hip; rpr_xenc_score in xenc_api.hip) ----------
-// T rows = the attended tokens of every sequence, sequence b owns rows seq_off[b] .. seq_off[b + 1] - 1. All fp32.
+// T rows = the attended tokens of every sequence, sequence b owns rows seq_off[b] .. seq_off[b + 1] - 1. The residual
+// stream, LayerNorm and the softmax are fp32 in both modes; the f16 mode also keeps the hidden states in f16 (outh below).
 struct XencEmbedArgs {
   const int32_t *ids, *types, *pos; int T, H;          // per row: token, token type, original position
   int vocab, type_vocab, max_pos;                      // table heights (ids are clamped into them)
@@ -131,20 +132,17 @@ struct XencAttnArgs {
 struct XencMetaChunk { static constexpr int N = 512; int32_t v[N]; };
 // dst[0 .. n) = host[0 .. n), carried by kernel arguments (async, the host array is free on return)
 hipError_t launch_xenc_meta(const int32_t* host, int n, int32_t* dst, hipStream_t s);
-hipError_t launch_xenc_embed_ln(const XencEmbedArgs& a, hipStream_t s);
-hipError_t launch_xenc_attn(const XencAttnArgs& a, int dh, hipStream_t s);   // dh = 32 or 64, sequences of 1 .. any length
-// out = LayerNorm(y + bias + resid) (biased variance); out may be resid
-hipError_t launch_xenc_bias_resid_ln(const float* y, const float* bias, const float* resid, const float* ln_w, const float* ln_b,
-                                     float eps, int T, int H, float* out, hipStream_t s);
+hipError_t launch_xenc_embed_ln(const XencEmbedArgs& a, __half* outh, hipStream_t s);   // outh: nullable f16 copy of a.out
+hipError_t launch_xenc_attn(const XencAttnArgs& a, int dh, hipStream_t s);   // fp32; dh = 32 or 64, sequences of 1 .. any length
+// out = LayerNorm(y + bias + resid) (biased variance) with outh == nullptr; out = LayerNorm(y) and its f16 copy outh with
+// bias == resid == nullptr (y = product + bias + residual, epilogue XENC_EPI_RESID). out may be resid or y
+hipError_t launch_xenc_add_ln(const float* y, const float* bias, const float* resid, const float* ln_w, const float* ln_b, float eps,
+                              int T, int H, float* out, __half* outh, hipStream_t s);
 hipError_t launch_xenc_bias_gelu(float* x, const float* bias, int rows, int N, hipStream_t s);   // erf GELU, in place
 hipError_t launch_xenc_head(const float* x, const int32_t* seq_off, int bz, int H, const float* pool_w, const float* pool_b,
                             const float* cls_w, const float* cls_b, float* out, hipStream_t s);
-// The f16 mode (xenc_half.hip): f16 matrix operands, fp32 accumulation, fp32 residual stream / LayerNorm / softmax.
+// The f16 mode (xenc_half.hip): f16 matrix operands, fp32 accumulation.
 hipError_t launch_xenc_f32_to_f16(const float* src, __half* dst, size_t n, hipStream_t s);   // round to nearest even
-hipError_t launch_xenc_embed_ln_h(const XencEmbedArgs& a, __half* outh, hipStream_t s);       // a.out fp32 and its f16 copy
-// out = LayerNorm(y) (y = product + bias + residual, epilogue XENC_EPI_RESID) and its f16 copy; out may be y
-hipError_t launch_xenc_ln_h(const float* y, const float* ln_w, const float* ln_b, float eps, int T, int H, float* out, __half* outh,
-                            hipStream_t s);
 // C[M, N] = A[M, K] . W[N, K]^T, f16 operands, fp32 accumulators; M >= 1, N % 32 == 0, K % 32 == 0
 constexpr int XENC_EPI_BIAS = 0;        // + bias -> outh (f16)
 constexpr int XENC_EPI_BIAS_GELU = 1;   // + bias, erf GELU in fp32 -> outh (f16)

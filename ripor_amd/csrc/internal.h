@@ -183,12 +183,10 @@ struct Workspace {
   // rpr_rq_encode_beam: the second residual plane (the first is rq_r), |r|^2 of the beam entries (two planes), the
   // candidates of a level (scores, then codes) and the parent slot / code history of every level (slots, then codes)
   DevBuf rq_r2, rq_bnorm, rq_cand, rq_bhist;
-  // rpr_xenc_score (xenc_api.hip): hidden states [T, H], q | k | v [T, 3 H], attention output [T, H], a product's raw
-  // result [T, H], the feed-forward intermediate [T, d_ff], and the tile list + sequence offsets
-  DevBuf xe_x, xe_qkv, xe_ctx, xe_tmp, xe_ff, xe_meta;
-  // its f16 mode (rpr_xenc_set_precision): f16 copy of the hidden states, q | k | v with their biases, attention output
-  // and GELU output; xe_x (fp32 residual stream), xe_tmp and xe_meta are shared with the fp32 mode
-  DevBuf xe_xh, xe_qkvh, xe_ctxh, xe_ffh;
+  // rpr_xenc_score (xenc_api.hip): hidden states [T, H] fp32, q | k | v [T, 3 H], attention output [T, H], a product's raw
+  // result [T, H] fp32, the feed-forward intermediate [T, d_ff], the tile list + sequence offsets, and the f16 mode's f16
+  // copy of the hidden states. xe_qkv, xe_ctx and xe_ff hold the elements of the call's mode (fp32 or f16)
+  DevBuf xe_x, xe_qkv, xe_ctx, xe_tmp, xe_ff, xe_meta, xe_xh;
 };
 
 static_assert(sizeof(Workspace) % sizeof(DevBuf) == 0 && std::is_standard_layout<Workspace>::value,

@@ -1,6 +1,6 @@
-// C ABI of the cross-encoder teacher: rpr_xenc_load / rpr_xenc_free / rpr_xenc_score (kernels in xenc_kernels.hip, the
-// products through the exact-fp32 GEMM of gemm_f32.hip) and its opt-in f16 mode, rpr_xenc_set_precision (kernels in
-// xenc_half.hip); DESIGN.md §9f.
+// C ABI of the cross-encoder teacher: rpr_xenc_load / rpr_xenc_free / rpr_xenc_score and the opt-in f16 mode,
+// rpr_xenc_set_precision. One layer walk (xenc_forward) over two modes: fp32 (kernels in xenc_kernels.hip, the products
+// through the exact-fp32 GEMM of gemm_f32.hip) and f16 operands (xenc_half.hip); DESIGN.md §9f.
 #include <new>
 #include <vector>
 
@@ -19,56 +19,119 @@ struct rpr_xenc {
 
 namespace {
 
-// the f16 mode of rpr_xenc_score: the same layer walk with f16 operands. X stays fp32; Xh, QKV, CTX and FF are f16.
-int score_f16(rpr_ctx* c, rpr_xenc* x, const int32_t* input_ids, const int32_t* token_type_ids, const int32_t* position_ids,
-              const int32_t* seq_off, int32_t bz, const std::vector<int32_t>& meta, int ntiles, float* out_scores, hipStream_t s) {
-  const rpr_xenc_desc& d = x->d;
-  const int H = d.hidden, F = d.d_ff, dh = H / d.heads, T = seq_off[bz];
-  Workspace& w = c->ws;
-  int e = ensure(c, w.xe_x, (size_t)T * H * sizeof(float));
-  if (!e) e = ensure(c, w.xe_tmp, (size_t)T * H * sizeof(float));
-  if (!e) e = ensure(c, w.xe_meta, meta.size() * sizeof(int32_t));
-  if (!e) e = ensure(c, w.xe_xh, (size_t)T * H * sizeof(__half));
-  if (!e) e = ensure(c, w.xe_qkvh, (size_t)T * 3 * H * sizeof(__half));
-  if (!e) e = ensure(c, w.xe_ctxh, (size_t)T * H * sizeof(__half));
-  if (!e) e = ensure(c, w.xe_ffh, (size_t)T * F * sizeof(__half));
-  if (e) return e;
-  float *X = P<float>(w.xe_x), *TMP = P<float>(w.xe_tmp);
-  __half *Xh = P<__half>(w.xe_xh), *QKVh = P<__half>(w.xe_qkvh), *CTXh = P<__half>(w.xe_ctxh), *FFh = P<__half>(w.xe_ffh);
-  const int2* tiles = P<int2>(w.xe_meta);
-  const int32_t* off_dev = P<int32_t>(w.xe_meta) + (size_t)2 * ntiles;
+// What the steps of one rpr_xenc_score call share. A mode (below) adds its weights and says how a step is launched and
+// what it costs; the walk (xenc_forward) owns the order, the buffers and the weight offsets.
+template <class E>
+struct XencCall {
+  using Elem = E;                  // of QKV, CTX and FF
+  Launcher Ln;
+  const rpr_xenc_desc& d;
+  int T, H, F, dh, ntiles;
+  double Td, qk_pairs;             // rows; pairs of keys a query tile meets: 64 x len per tile (an upper bound on a sequence's last)
+  float *X, *TMP;                  // hidden states (the residual stream), a product's raw result
+  Elem *QKV, *CTX, *FF;            // q | k | v, attention output, feed-forward intermediate
+  __half* Xh;                      // f16 mode: the hidden states once more
+  const int2* tiles;
+  const int32_t* off_dev;
+};
 
-  Launcher Ln{c, s};
-  const double Td = (double)T;
-  Ln.run(RPR_K_OTHER, 0, 4.0 * meta.size(), [&] { return launch_xenc_meta(meta.data(), (int)meta.size(), P<int32_t>(w.xe_meta), s); });
-  XencEmbedArgs ea{input_ids, token_type_ids, position_ids, T, H, d.vocab_size, d.type_vocab, d.max_pos,
-                   d.word_emb, d.type_emb, d.pos_emb, d.emb_ln_w, d.emb_ln_b, d.ln_eps, X};
-  Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 4 + 2.0) * Td * H, [&] { return launch_xenc_embed_ln_h(ea, Xh, s); });
+// fp32: the exact GEMM has no epilogue, so the biases are added by attention, bias_gelu and add_ln
+struct XencF32 : XencCall<float> {
+  using Call = XencCall<float>;
+  static constexpr bool HALF_X = false;
+  const float *qkv_w, *ao_w, *ff1_w, *ff2_w;
+  XencF32(const Call& k, const rpr_xenc* x) : Call(k), qkv_w(x->d.qkv_w), ao_w(x->d.ao_w), ff1_w(x->d.ff1_w), ff2_w(x->d.ff2_w) {}
+
+  void gemm(const float* A, const float* W, int N, int K, float* out) {
+    GemmArgs g{};
+    g.A = A; g.lda = K; g.W = W; g.ldw = K;
+    g.out[0] = out; g.ldo[0] = N; g.split_n = N;
+    g.M = T; g.N = N; g.K = K;
+    Ln.run(RPR_K_GEMM, 2.0 * Td * N * K, 4.0 * (Td * (N + K) + (double)N * K), [&] { return launch_gemm(g, Ln.s); });
+  }
+  void embed(const XencEmbedArgs& ea) {
+    Ln.run(RPR_K_OTHER, 10.0 * Td * H, 4.0 * 4 * Td * H, [&] { return launch_xenc_embed_ln(ea, nullptr, Ln.s); });
+  }
+  void project_qkv(const float* W, const float*) { gemm(X, W, 3 * H, H, QKV); }
+  void attend(const float* bias) {
+    XencAttnArgs aa{QKV, bias, off_dev, tiles, ntiles, H, d.heads, CTX};
+    Ln.run(RPR_K_ENC_ATTN, 4.0 * qk_pairs * H, 4.0 * 4 * Td * H, [&] { return launch_xenc_attn(aa, dh, Ln.s); });
+  }
+  void project_add_ln(const float* A, const float* W, const float* bias, int K, const float* ln_w, const float* ln_b) {
+    gemm(A, W, H, K, TMP);
+    Ln.run(RPR_K_OTHER, 10.0 * Td * H, 4.0 * 3 * Td * H,
+           [&] { return launch_xenc_add_ln(TMP, bias, X, ln_w, ln_b, d.ln_eps, T, H, X, nullptr, Ln.s); });
+  }
+  void project_gelu(const float* W, const float* bias) {
+    gemm(X, W, F, H, FF);
+    Ln.run(RPR_K_OTHER, 10.0 * Td * F, 4.0 * 2 * Td * F, [&] { return launch_xenc_bias_gelu(FF, bias, T, F, Ln.s); });
+  }
+};
+
+// f16 operands: bias, GELU and the residual sit in the GEMM epilogues; X stays fp32, Xh feeds the products
+struct XencF16 : XencCall<__half> {
+  using Call = XencCall<__half>;
+  static constexpr bool HALF_X = true;
+  const __half *qkv_w, *ao_w, *ff1_w, *ff2_w;
+  XencF16(const Call& k, const rpr_xenc* x) : Call(k), qkv_w(x->qkv_h), ao_w(x->ao_h), ff1_w(x->ff1_h), ff2_w(x->ff2_h) {}
+
   // bytes: f16 operands; out_b = bytes per output element written (+ read, for the residual)
-  auto gemm = [&](int epi, const __half* A, const __half* W, const float* bias, int N, int K, __half* outh, float* outf) {
+  void gemm(int epi, const __half* A, const __half* W, const float* bias, int N, int K, __half* outh, float* outf) {
     const double out_b = epi == XENC_EPI_RESID ? 8.0 : 2.0;
     Ln.run(RPR_K_GEMM, 2.0 * Td * N * K, 2.0 * (Td * K + (double)N * K) + out_b * Td * N,
-           [&] { return launch_xenc_gemm_h(epi, A, W, bias, epi == XENC_EPI_RESID ? X : nullptr, outh, outf, T, N, K, s); });
-  };
+           [&] { return launch_xenc_gemm_h(epi, A, W, bias, epi == XENC_EPI_RESID ? X : nullptr, outh, outf, T, N, K, Ln.s); });
+  }
+  void embed(const XencEmbedArgs& ea) {
+    Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 4 + 2.0) * Td * H, [&] { return launch_xenc_embed_ln(ea, Xh, Ln.s); });
+  }
+  void project_qkv(const __half* W, const float* bias) { gemm(XENC_EPI_BIAS, Xh, W, bias, 3 * H, H, QKV, nullptr); }
+  void attend(const float*) {
+    Ln.run(RPR_K_ENC_ATTN, 4.0 * qk_pairs * H, 2.0 * 4 * Td * H,
+           [&] { return launch_xenc_attn_h(QKV, off_dev, tiles, ntiles, H, d.heads, dh, CTX, Ln.s); });
+  }
+  void project_add_ln(const __half* A, const __half* W, const float* bias, int K, const float* ln_w, const float* ln_b) {
+    gemm(XENC_EPI_RESID, A, W, bias, H, K, nullptr, TMP);
+    Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 2 + 2.0) * Td * H,
+           [&] { return launch_xenc_add_ln(TMP, nullptr, nullptr, ln_w, ln_b, d.ln_eps, T, H, X, Xh, Ln.s); });
+  }
+  void project_gelu(const __half* W, const float* bias) { gemm(XENC_EPI_BIAS_GELU, Xh, W, bias, F, H, FF, nullptr); }
+};
+
+// the forward over a packed batch, once for both modes: meta = the attention kernel's tile list, then the sequence offsets
+template <class Mode>
+int xenc_forward(rpr_ctx* c, const rpr_xenc* x, const int32_t* input_ids, const int32_t* token_type_ids, const int32_t* position_ids,
+                 const int32_t* seq_off, int32_t bz, const std::vector<int32_t>& meta, int ntiles, float* out_scores, hipStream_t s) {
+  const rpr_xenc_desc& d = x->d;
+  const int H = d.hidden, F = d.d_ff, T = seq_off[bz];
+  Workspace& w = c->ws;
+  using Elem = typename Mode::Elem;
+  const size_t TH = (size_t)T * H, el = sizeof(Elem);
+  const struct { DevBuf& buf; size_t n, size; } need[] = {
+      {w.xe_x, TH, sizeof(float)}, {w.xe_qkv, 3 * TH, el}, {w.xe_ctx, TH, el}, {w.xe_tmp, TH, sizeof(float)}, {w.xe_ff, (size_t)T * F, el},
+      {w.xe_meta, meta.size(), sizeof(int32_t)}, {w.xe_xh, Mode::HALF_X ? TH : 0, sizeof(__half)}};
+  for (const auto& r : need)
+    if (const int e = ensure(c, r.buf, r.n * r.size)) return e;
+
   double qk_pairs = 0.0;
   for (int b = 0; b < bz; ++b) { const double len = seq_off[b + 1] - seq_off[b]; qk_pairs += len * len; }
+  Mode m(typename Mode::Call{Launcher{c, s}, d, T, H, F, H / d.heads, ntiles, (double)T, qk_pairs, P<float>(w.xe_x), P<float>(w.xe_tmp),
+                             P<Elem>(w.xe_qkv), P<Elem>(w.xe_ctx), P<Elem>(w.xe_ff), P<__half>(w.xe_xh), P<int2>(w.xe_meta),
+                             P<int32_t>(w.xe_meta) + (size_t)2 * ntiles},
+         x);
+  Launcher& Ln = m.Ln;
+  Ln.run(RPR_K_OTHER, 0, 4.0 * meta.size(), [&] { return launch_xenc_meta(meta.data(), (int)meta.size(), P<int32_t>(w.xe_meta), s); });
+  m.embed(XencEmbedArgs{input_ids, token_type_ids, position_ids, T, H, d.vocab_size, d.type_vocab, d.max_pos,
+                        d.word_emb, d.type_emb, d.pos_emb, d.emb_ln_w, d.emb_ln_b, d.ln_eps, m.X});
   for (int l = 0; l < d.layers; ++l) {
-    const size_t HH = (size_t)H * H, FH = (size_t)F * H;
-    gemm(XENC_EPI_BIAS, Xh, x->qkv_h + l * 3 * HH, d.qkv_b + (size_t)l * 3 * H, 3 * H, H, QKVh, nullptr);
-    Ln.run(RPR_K_ENC_ATTN, 4.0 * qk_pairs * H, 2.0 * 4 * Td * H,
-           [&] { return launch_xenc_attn_h(QKVh, off_dev, tiles, ntiles, H, d.heads, dh, CTXh, s); });
-    gemm(XENC_EPI_RESID, CTXh, x->ao_h + l * HH, d.ao_b + (size_t)l * H, H, H, nullptr, TMP);
-    Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 2 + 2.0) * Td * H, [&] {
-      return launch_xenc_ln_h(TMP, d.ln1_w + (size_t)l * H, d.ln1_b + (size_t)l * H, d.ln_eps, T, H, X, Xh, s);
-    });
-    gemm(XENC_EPI_BIAS_GELU, Xh, x->ff1_h + l * FH, d.ff1_b + (size_t)l * F, F, H, FFh, nullptr);
-    gemm(XENC_EPI_RESID, FFh, x->ff2_h + l * FH, d.ff2_b + (size_t)l * H, H, F, nullptr, TMP);
-    Ln.run(RPR_K_OTHER, 10.0 * Td * H, (4.0 * 2 + 2.0) * Td * H, [&] {
-      return launch_xenc_ln_h(TMP, d.ln2_w + (size_t)l * H, d.ln2_b + (size_t)l * H, d.ln_eps, T, H, X, Xh, s);
-    });
+    const size_t HH = (size_t)H * H, FH = (size_t)F * H, lH = (size_t)l * H;
+    m.project_qkv(m.qkv_w + l * 3 * HH, d.qkv_b + 3 * lH);
+    m.attend(d.qkv_b + 3 * lH);
+    m.project_add_ln(m.CTX, m.ao_w + l * HH, d.ao_b + lH, H, d.ln1_w + lH, d.ln1_b + lH);
+    m.project_gelu(m.ff1_w + l * FH, d.ff1_b + (size_t)l * F);
+    m.project_add_ln(m.FF, m.ff2_w + l * FH, d.ff2_b + lH, F, d.ln2_w + lH, d.ln2_b + lH);
   }
   Ln.run(RPR_K_OTHER, 2.0 * bz * ((double)H * H + H), 4.0 * ((double)H * H + 2.0 * bz * H), [&] {
-    return launch_xenc_head(X, off_dev, bz, H, d.pool_w, d.pool_b, d.cls_w, d.cls_b, out_scores, s);
+    return launch_xenc_head(m.X, m.off_dev, bz, H, d.pool_w, d.pool_b, d.cls_w, d.cls_b, out_scores, s);
   });
   return Ln.err;
 }
@@ -161,60 +224,12 @@ int rpr_xenc_score(rpr_ctx* c, rpr_xenc* x, const int32_t* input_ids, const int3
     set_error("out of host memory for the tile list");
     return RPR_ERR_OOM;
   }
-  const int T = seq_off[bz];
 
   RPR_HIP(hipSetDevice(c->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (x->precision == RPR_XENC_F16)
-    return score_f16(c, x, input_ids, token_type_ids, position_ids, seq_off, bz, meta, ntiles, out_scores, s);
-  Workspace& w = c->ws;
-  int e = ensure(c, w.xe_x, (size_t)T * H * sizeof(float));
-  if (!e) e = ensure(c, w.xe_qkv, (size_t)T * 3 * H * sizeof(float));
-  if (!e) e = ensure(c, w.xe_ctx, (size_t)T * H * sizeof(float));
-  if (!e) e = ensure(c, w.xe_tmp, (size_t)T * H * sizeof(float));
-  if (!e) e = ensure(c, w.xe_ff, (size_t)T * F * sizeof(float));
-  if (!e) e = ensure(c, w.xe_meta, meta.size() * sizeof(int32_t));
-  if (e) return e;
-  float *X = P<float>(w.xe_x), *QKV = P<float>(w.xe_qkv), *CTX = P<float>(w.xe_ctx), *TMP = P<float>(w.xe_tmp), *FF = P<float>(w.xe_ff);
-  const int2* tiles = P<int2>(w.xe_meta);
-  const int32_t* off_dev = P<int32_t>(w.xe_meta) + (size_t)2 * ntiles;
-
-  Launcher Ln{c, s};
-  const double Td = (double)T;
-  Ln.run(RPR_K_OTHER, 0, 4.0 * meta.size(), [&] { return launch_xenc_meta(meta.data(), (int)meta.size(), P<int32_t>(w.xe_meta), s); });
-  XencEmbedArgs ea{input_ids, token_type_ids, position_ids, T, H, d.vocab_size, d.type_vocab, d.max_pos,
-                   d.word_emb, d.type_emb, d.pos_emb, d.emb_ln_w, d.emb_ln_b, d.ln_eps, X};
-  Ln.run(RPR_K_OTHER, 10.0 * Td * H, 4.0 * 4 * Td * H, [&] { return launch_xenc_embed_ln(ea, s); });
-  auto gemm = [&](const float* A, const float* W, int N, int K, float* out) {
-    GemmArgs g{};
-    g.A = A; g.lda = K; g.W = W; g.ldw = K;
-    g.out[0] = out; g.ldo[0] = N; g.split_n = N;
-    g.M = T; g.N = N; g.K = K;
-    Ln.run(RPR_K_GEMM, 2.0 * Td * N * K, 4.0 * (Td * (N + K) + (double)N * K), [&] { return launch_gemm(g, s); });
-  };
-  // pairs of keys a query tile meets: 64 x len per tile (an upper bound on the last tile of a sequence)
-  double qk_pairs = 0.0;
-  for (int b = 0; b < bz; ++b) { const double len = seq_off[b + 1] - seq_off[b]; qk_pairs += len * len; }
-  for (int l = 0; l < d.layers; ++l) {
-    const size_t HH = (size_t)H * H, FH = (size_t)F * H;
-    gemm(X, d.qkv_w + l * 3 * HH, 3 * H, H, QKV);
-    XencAttnArgs aa{QKV, d.qkv_b + (size_t)l * 3 * H, off_dev, tiles, ntiles, H, d.heads, CTX};
-    Ln.run(RPR_K_ENC_ATTN, 4.0 * qk_pairs * H, 4.0 * 4 * Td * H, [&] { return launch_xenc_attn(aa, dh, s); });
-    gemm(CTX, d.ao_w + l * HH, H, H, TMP);
-    Ln.run(RPR_K_OTHER, 10.0 * Td * H, 4.0 * 3 * Td * H, [&] {
-      return launch_xenc_bias_resid_ln(TMP, d.ao_b + (size_t)l * H, X, d.ln1_w + (size_t)l * H, d.ln1_b + (size_t)l * H, d.ln_eps, T, H, X, s);
-    });
-    gemm(X, d.ff1_w + l * FH, F, H, FF);
-    Ln.run(RPR_K_OTHER, 10.0 * Td * F, 4.0 * 2 * Td * F, [&] { return launch_xenc_bias_gelu(FF, d.ff1_b + (size_t)l * F, T, F, s); });
-    gemm(FF, d.ff2_w + l * FH, H, F, TMP);
-    Ln.run(RPR_K_OTHER, 10.0 * Td * H, 4.0 * 3 * Td * H, [&] {
-      return launch_xenc_bias_resid_ln(TMP, d.ff2_b + (size_t)l * H, X, d.ln2_w + (size_t)l * H, d.ln2_b + (size_t)l * H, d.ln_eps, T, H, X, s);
-    });
-  }
-  Ln.run(RPR_K_OTHER, 2.0 * bz * ((double)H * H + H), 4.0 * ((double)H * H + 2.0 * bz * H), [&] {
-    return launch_xenc_head(X, off_dev, bz, H, d.pool_w, d.pool_b, d.cls_w, d.cls_b, out_scores, s);
-  });
-  return Ln.err;
+  return x->precision == RPR_XENC_F16
+             ? xenc_forward<XencF16>(c, x, input_ids, token_type_ids, position_ids, seq_off, bz, meta, ntiles, out_scores, s)
+             : xenc_forward<XencF32>(c, x, input_ids, token_type_ids, position_ids, seq_off, bz, meta, ntiles, out_scores, s);
 }
 
 }  // extern "C"

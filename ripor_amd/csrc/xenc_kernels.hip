@@ -3,33 +3,28 @@
 //
 // Packed: only attended tokens exist. Row t of every [T, .] matrix is one token, sequence b owns the rows
 // seq_off[b] .. seq_off[b + 1] - 1, and a row carries its original position id. Attention runs per (sequence, head) over
-// that sequence's rows, so there is no key mask and padding costs nothing. Everything is fp32; the matrix products are the
-// exact-fp32 GEMM of gemm_f32.hip (no bias, no activation: those live here).
+// that sequence's rows, so there is no key mask and padding costs nothing. The fp32 mode runs on these kernels and the
+// exact-fp32 GEMM of gemm_f32.hip (no bias, no activation: those live here); the f16 mode (xenc_half.hip) shares the row
+// kernels, which then also write an f16 copy of the hidden states, and the head.
 //
-//   xenc_embed_ln       LayerNorm(word[id] + type[tt] + pos[p])
-//   xenc_attn<DH>       softmax((q + b_q)(k + b_k)^T / sqrt(DH)) (v + b_v), DH = 32 or 64, v_mfma_f32_16x16x4_f32 for both products
-//   xenc_bias_resid_ln  LayerNorm(y + bias + residual)
-//   xenc_bias_gelu      bias + exact (erf) GELU, in place
-//   xenc_head           tanh(pool_w x_first + pool_b) . cls_w + cls_b of every sequence's first row
+//   xenc_embed_ln<HALF_COPY>     LayerNorm(word[id] + type[tt] + pos[p])
+//   xenc_attn<DH, XencAttnF32>   softmax((q + b_q)(k + b_k)^T / sqrt(DH)) (v + b_v), DH = 32 or 64 (skeleton: xenc_device.h)
+//   xenc_add_ln<ADD, HALF_COPY>  LayerNorm(y + bias + residual), or LayerNorm(y) after a GEMM that has added both
+//   xenc_bias_gelu               bias + exact (erf) GELU, in place
+//   xenc_head                    tanh(pool_w x_first + pool_b) . cls_w + cls_b of every sequence's first row
 //
 // Every reduction has a fixed order (shuffles inside a wave, no atomics): a call repeated gives the same bits.
-#include "common.h"
+#include "xenc_device.h"
 
 namespace rpr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // LayerNorm of one row held as out[0 .. H) (already written by this wave: lane l owns the float4 pieces l, l + 64, ...),
-// biased variance, two passes over the row
-__device__ __forceinline__ void row_layernorm(float* out, int H, float sum, const float* w, const float* b, float eps, int lane) {
+// biased variance, two passes over the row; HALF_COPY: the result goes to outh[0 .. H) in f16 as well
+template <bool HALF_COPY>
+__device__ __forceinline__ void row_layernorm(float* out, __half* outh, int H, float sum, const float* w, const float* b, float eps,
+                                              int lane) {
   const float mean = wave_sum(sum) / (float)H;
   float ss = 0.f;
   for (int i = lane * 4; i < H; i += 256) {
@@ -44,12 +39,19 @@ __device__ __forceinline__ void row_layernorm(float* out, int H, float sum, cons
     v.x = (v.x - mean) * rstd * g.x + bb.x; v.y = (v.y - mean) * rstd * g.y + bb.y;
     v.z = (v.z - mean) * rstd * g.z + bb.z; v.w = (v.w - mean) * rstd * g.w + bb.w;
     *reinterpret_cast<float4*>(out + i) = v;
+    if constexpr (HALF_COPY) {
+      __half2 lo = __floats2half2_rn(v.x, v.y), hi = __floats2half2_rn(v.z, v.w);
+      uint2 pk;
+      pk.x = *reinterpret_cast<const unsigned*>(&lo); pk.y = *reinterpret_cast<const unsigned*>(&hi);
+      *reinterpret_cast<uint2*>(outh + i) = pk;
+    }
   }
 }
 
 // one wave per row, 4 rows per block; H % 4 == 0. Ids outside their tables are clamped (memory safety only: the Python
 // boundary refuses them before the call).
-__global__ __launch_bounds__(256) void xenc_embed_ln_kernel(XencEmbedArgs a) {
+template <bool HALF_COPY>
+__global__ __launch_bounds__(256) void xenc_embed_ln_kernel(XencEmbedArgs a, __half* outh) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.T) return;
   const int id = min(max(a.ids[row], 0), a.vocab - 1), tt = min(max(a.types[row], 0), a.type_vocab - 1),
@@ -67,12 +69,14 @@ __global__ __launch_bounds__(256) void xenc_embed_ln_kernel(XencEmbedArgs a) {
     *reinterpret_cast<float4*>(out + i) = v;
     sum += (v.x + v.y) + (v.z + v.w);
   }
-  row_layernorm(out, a.H, sum, a.ln_w, a.ln_b, a.eps, lane);
+  row_layernorm<HALF_COPY>(out, outh + (size_t)row * a.H, a.H, sum, a.ln_w, a.ln_b, a.eps, lane);
 }
 
-// out may be resid (in place): a lane reads its pieces of the residual before it writes them
-__global__ __launch_bounds__(256) void xenc_bias_resid_ln_kernel(const float* y, const float* bias, const float* resid, const float* w,
-                                                                 const float* b, float eps, int T, int H, float* outp) {
+// LayerNorm(y + bias + resid) when ADD, LayerNorm(y) otherwise (the f16 GEMM's epilogue has added both). out may be resid
+// or y (in place): a lane reads its pieces before it writes them
+template <bool ADD, bool HALF_COPY>
+__global__ __launch_bounds__(256) void xenc_add_ln_kernel(const float* y, const float* bias, const float* resid, const float* w,
+                                                          const float* b, float eps, int T, int H, float* outp, __half* outh) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= T) return;
   const float* yr = y + (size_t)row * H;
@@ -80,17 +84,16 @@ __global__ __launch_bounds__(256) void xenc_bias_resid_ln_kernel(const float* y,
   float* out = outp + (size_t)row * H;
   float sum = 0.f;
   for (int i = lane * 4; i < H; i += 256) {
-    const float4 x = *reinterpret_cast<const float4*>(yr + i), bb = *reinterpret_cast<const float4*>(bias + i),
-                 r = *reinterpret_cast<const float4*>(rr + i);
-    float4 v;
-    v.x = (x.x + bb.x) + r.x; v.y = (x.y + bb.y) + r.y; v.z = (x.z + bb.z) + r.z; v.w = (x.w + bb.w) + r.w;
+    float4 v = *reinterpret_cast<const float4*>(yr + i);
+    if constexpr (ADD) {
+      const float4 bb = *reinterpret_cast<const float4*>(bias + i), r = *reinterpret_cast<const float4*>(rr + i);
+      v.x = (v.x + bb.x) + r.x; v.y = (v.y + bb.y) + r.y; v.z = (v.z + bb.z) + r.z; v.w = (v.w + bb.w) + r.w;
+    }
     *reinterpret_cast<float4*>(out + i) = v;
     sum += (v.x + v.y) + (v.z + v.w);
   }
-  row_layernorm(out, H, sum, w, b, eps, lane);
+  row_layernorm<HALF_COPY>(out, outh + (size_t)row * H, H, sum, w, b, eps, lane);
 }
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // x [rows, N] in place; N % 4 == 0, n4 = rows * N / 4
 __global__ __launch_bounds__(256) void xenc_bias_gelu_kernel(float* x, const float* bias, long long n4, int N) {
@@ -102,49 +105,27 @@ __global__ __launch_bounds__(256) void xenc_bias_gelu_kernel(float* x, const flo
   reinterpret_cast<float4*>(x)[i] = v;
 }
 
-// Attention of one (64-query tile of a sequence, head). 4 waves, 16 query rows each; keys and values walk through LDS in
-// tiles of 64 rows with an online softmax. MFMA 16x16x4 f32 operand maps (lane l, c = l & 15, g = l >> 4):
-//   A[i = c][k = g], B[k = g][j = c], C/D[row = 4 g + reg][col = c].
-// S = Q K^T: A = Q[row c][d = 4 kk + g] (registers, loaded once), B = K[key 16 j + c][d = 4 kk + g]: four independent
-//   accumulators (j) per wave. LDS row stride DH + 4 floats: the 64 lanes of a B read hit 64 different banks.
-// O += P V:  P leaves the S accumulators in the C map and is needed in the A map: through a private LDS strip per wave
-//   (row stride 64 + 4). B = V[key 4 kk + g][d = 16 n + c], row stride DH + 16: again 64 different banks.
-// The C map of S and of O share the row (4 g + reg), so the running maximum / sum of a row and the rescaling of O stay in
-// the lane's own registers; a row's 64 scores sit in 16 lanes x 4 accumulators: reduced with 4 xor-shuffles.
-// A tile always holds at least one key of the sequence (k0 < len), so the running maximum is finite after the first
-// tile; keys past the end get -inf and weigh exactly 0. Query rows past the end compute on q = 0 and are not stored.
+// The fp32 operands of xenc_attn_kernel (xenc_device.h): v_mfma_f32_16x16x4_f32, A[i = c][k = g], B[k = g][j = c]; the
+// q | k | v biases are added while loading.
+//   S: A = Q[row c][d = 4 kk + g], B = K[key 16 j + c][d = 4 kk + g]; K rows of DH + 4 floats: the 64 lanes of a B read hit
+//      64 different banks.
+//   O: A = P[row c][key 4 kk + g] (strip rows of 64 + 4), B = V[key 4 kk + g][d = 16 n + c], V rows of DH + 16: again 64
+//      different banks.
 template <int DH>
-__global__ __launch_bounds__(256) void xenc_attn_kernel(XencAttnArgs a) {
-  constexpr int LDK = DH + 4, LDV = DH + 16, LDP = 64 + 4, KS = DH / 4, NB = DH / 16, C4 = DH / 4;
-  __shared__ __attribute__((aligned(16))) float k_s[64 * LDK];
-  __shared__ __attribute__((aligned(16))) float v_s[64 * LDV];
-  __shared__ float p_s[4 * 16 * LDP];
-  const int2 t = a.tiles[blockIdx.x];   // (sequence, first query row of the tile inside it)
-  const int head = blockIdx.y;
-  const int s0 = a.seq_off[t.x], len = a.seq_off[t.x + 1] - s0;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
-  const size_t ld = (size_t)3 * a.H;
-  const float* qb = a.qkv + (size_t)s0 * ld + (size_t)head * DH;
-  const float* bq = a.bias + head * DH;
-  const float scale = 1.0f / sqrtf((float)DH);
-  const bool wave_live = t.y + wave * 16 < len;
+struct XencAttnF32 {
+  using Elem = float;
+  using Args = XencAttnArgs;
+  using QFrag = float;
+  using PFrag = float;
+  static constexpr int LDK = DH + 4, LDV = DH + 16, V_ELEMS = 64 * LDV, LDP = 64 + 4, KS = DH / 4, PS = 16, PU = 4, NB = DH / 16, C4 = DH / 4;
 
-  float qf[KS];
-  {
-    const int qrow = t.y + wave * 16 + c;
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) qf[kk] = qrow < len ? qb[(size_t)qrow * ld + 4 * kk + g] + bq[4 * kk + g] : 0.f;
+  static __device__ __forceinline__ float load_q(const Args& a, const float* qb, size_t ld, int head, int qrow, int len, int g, int kk) {
+    const float* bq = a.bias + head * DH;
+    return qrow < len ? qb[(size_t)qrow * ld + 4 * kk + g] + bq[4 * kk + g] : 0.f;
   }
-  f32x4 o[NB];
-#pragma unroll
-  for (int n = 0; n < NB; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m_run[4], l_run[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m_run[r] = -INFINITY; l_run[r] = 0.f; }
-  float* pw = p_s + wave * 16 * LDP;
-
-  for (int k0 = 0; k0 < len; k0 += 64) {
-    __syncthreads();   // the previous tile's K, V and P have been read
+  static __device__ __forceinline__ void stage(float* k_s, float* v_s, const Args& a, const float* qb, size_t ld, int head, int k0,
+                                               int len, int tid) {
+    const float* bq = a.bias + head * DH;
     for (int idx = tid; idx < 64 * C4; idx += 256) {
       const int r = idx / C4, c4 = (idx - r * C4) * 4;
       float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
@@ -159,66 +140,16 @@ __global__ __launch_bounds__(256) void xenc_attn_kernel(XencAttnArgs a) {
       *reinterpret_cast<float4*>(&k_s[r * LDK + c4]) = kv;
       *reinterpret_cast<float4*>(&v_s[r * LDV + c4]) = vv;
     }
-    __syncthreads();
-    if (wave_live) {
-      f32x4 s[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          s[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[kk], k_s[(16 * j + c) * LDK + 4 * kk + g], s[j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = k0 + 16 * j + c < len;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[j][r] = ok ? s[j][r] * scale : -INFINITY;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float mx = fmaxf(fmaxf(s[0][r], s[1][r]), fmaxf(s[2][r], s[3][r]));
-#pragma unroll
-        for (int sh = 1; sh < 16; sh <<= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-        const float m_new = fmaxf(m_run[r], mx);        // finite: the tile holds a key of the sequence
-        const float alpha = expf(m_run[r] - m_new);     // first tile: exp(-inf) = 0
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float p = expf(s[j][r] - m_new);
-          sum += p;
-          pw[(4 * g + r) * LDP + 16 * j + c] = p;
-        }
-#pragma unroll
-        for (int sh = 1; sh < 16; sh <<= 1) sum += __shfl_xor(sum, sh, 64);
-        l_run[r] = l_run[r] * alpha + sum;
-        m_run[r] = m_new;
-#pragma unroll
-        for (int n = 0; n < NB; ++n) o[n][r] *= alpha;
-      }
-    }
-    __syncthreads();   // P is in the wave's strip
-    if (wave_live) {
-#pragma unroll 4
-      for (int kk = 0; kk < 16; ++kk) {
-        const float pa = pw[c * LDP + 4 * kk + g];
-#pragma unroll
-        for (int n = 0; n < NB; ++n)
-          o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa, v_s[(4 * kk + g) * LDV + 16 * n + c], o[n], 0, 0, 0);
-      }
-    }
   }
-  if (!wave_live) return;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int qrow = t.y + wave * 16 + 4 * g + r;
-    if (qrow >= len) continue;
-    const float inv = 1.0f / l_run[r];
-    float* dst = a.out + (size_t)(s0 + qrow) * a.H + (size_t)head * DH + c;
-#pragma unroll
-    for (int n = 0; n < NB; ++n) dst[16 * n] = o[n][r] * inv;
+  static __device__ __forceinline__ f32x4 qk(float q, const float* k_s, int j, int kk, int c, int g, f32x4 acc) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(q, k_s[(16 * j + c) * LDK + 4 * kk + g], acc, 0, 0, 0);
   }
-}
+  static __device__ __forceinline__ float load_p(const float* pw, int c, int g, int kk) { return pw[c * LDP + 4 * kk + g]; }
+  static __device__ __forceinline__ f32x4 pv(float p, const float* v_s, int n, int kk, int c, int g, f32x4 acc) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(p, v_s[(4 * kk + g) * LDV + 16 * n + c], acc, 0, 0, 0);
+  }
+  static __device__ __forceinline__ float cvt(float v) { return v; }
+};
 
 // one block per sequence: x = its first row; pooled[j] = tanh(pool_w[j] . x + pool_b[j]) (a wave per j, fixed order), then
 // the classifier row. Dynamic LDS: 2 H floats.
@@ -269,24 +200,26 @@ hipError_t launch_xenc_meta(const int32_t* host, int n, int32_t* dst, hipStream_
   return hipSuccess;
 }
 
-hipError_t launch_xenc_embed_ln(const XencEmbedArgs& a, hipStream_t s) {
+hipError_t launch_xenc_embed_ln(const XencEmbedArgs& a, __half* outh, hipStream_t s) {
   if (a.T <= 0 || a.H <= 0 || (a.H & 3)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(xenc_embed_ln_kernel, dim3((a.T + 3) / 4), dim3(256), 0, s, a);
+  if (outh) hipLaunchKernelGGL(xenc_embed_ln_kernel<true>, dim3((a.T + 3) / 4), dim3(256), 0, s, a, outh);
+  else hipLaunchKernelGGL(xenc_embed_ln_kernel<false>, dim3((a.T + 3) / 4), dim3(256), 0, s, a, outh);
   return hipGetLastError();
 }
 
-hipError_t launch_xenc_attn(const XencAttnArgs& a, int dh, hipStream_t s) {
-  if (a.ntiles <= 0 || a.heads <= 0 || a.H != a.heads * dh) return hipErrorInvalidValue;
-  if (dh == 32) hipLaunchKernelGGL(xenc_attn_kernel<32>, dim3(a.ntiles, a.heads), dim3(256), 0, s, a);
-  else if (dh == 64) hipLaunchKernelGGL(xenc_attn_kernel<64>, dim3(a.ntiles, a.heads), dim3(256), 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
+hipError_t launch_xenc_attn(const XencAttnArgs& a, int dh, hipStream_t s) { return launch_xenc_attn_as<XencAttnF32>(a, dh, s); }
 
-hipError_t launch_xenc_bias_resid_ln(const float* y, const float* bias, const float* resid, const float* ln_w, const float* ln_b,
-                                     float eps, int T, int H, float* out, hipStream_t s) {
+hipError_t launch_xenc_add_ln(const float* y, const float* bias, const float* resid, const float* ln_w, const float* ln_b, float eps,
+                              int T, int H, float* out, __half* outh, hipStream_t s) {
   if (T <= 0 || H <= 0 || (H & 3)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(xenc_bias_resid_ln_kernel, dim3((T + 3) / 4), dim3(256), 0, s, y, bias, resid, ln_w, ln_b, eps, T, H, out);
+  const dim3 grid((T + 3) / 4);
+  // the two forms the walk has: fp32 adds while loading, f16 has added in the GEMM and wants the f16 copy
+  if (bias && resid && !outh)
+    hipLaunchKernelGGL((xenc_add_ln_kernel<true, false>), grid, dim3(256), 0, s, y, bias, resid, ln_w, ln_b, eps, T, H, out, outh);
+  else if (!bias && !resid && outh)
+    hipLaunchKernelGGL((xenc_add_ln_kernel<false, true>), grid, dim3(256), 0, s, y, bias, resid, ln_w, ln_b, eps, T, H, out, outh);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

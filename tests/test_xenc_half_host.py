@@ -102,13 +102,12 @@ def test_cross_encoder_refuses_an_unknown_precision(tmp_path):
         ce.set_precision("half")
 
 
-def test_f16_kernels_use_no_scratch():
-    """Every f16 GEMM and attention instantiation of xenc_half.hip compiles without scratch (cross-compile for gfx950, no
-    GPU needed; the pattern of test_abi.py::test_hot_gemm_kernels_use_no_scratch)."""
+def _scratch_by_kernel(source):
+    """{mangled kernel name: scratch bytes per lane} of a cross-compile of ripor_amd/csrc/<source> for gfx950."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(REPO, "ripor_amd", "csrc", "xenc_half.hip")
+    src = os.path.join(REPO, "ripor_amd", "csrc", source)
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
                         "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, src], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -120,7 +119,19 @@ def test_f16_kernels_use_no_scratch():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and name:
             seen[name] = int(m.group(1))
+    return seen
+
+
+def test_f16_kernels_use_no_scratch():
+    """Every f16 GEMM and attention instantiation of xenc_half.hip compiles without scratch (cross-compile for gfx950, no
+    GPU needed; the pattern of test_abi.py::test_hot_gemm_kernels_use_no_scratch), and so do the two fp32 instantiations of
+    the shared attention kernel and the row kernels in xenc_kernels.hip."""
+    seen = _scratch_by_kernel("xenc_half.hip")
     gemm = {k: v for k, v in seen.items() if "xenc_gemm_h_kernel" in k}
-    attn = {k: v for k, v in seen.items() if "xenc_attn_h_kernel" in k}
+    attn = {k: v for k, v in seen.items() if "xenc_attn_kernel" in k and "XencAttnF16" in k}
     assert len(gemm) == 3 and len(attn) == 2, sorted(seen)   # three epilogues; heads of 32 and 64
+    assert all(v == 0 for v in seen.values()), {k: v for k, v in seen.items() if v}
+    seen = _scratch_by_kernel("xenc_kernels.hip")   # (the row kernels with the f16 copy live there too)
+    full = {k: v for k, v in seen.items() if "xenc_attn_kernel" in k and "XencAttnF32" in k}
+    assert len(full) == 2, sorted(seen)
     assert all(v == 0 for v in seen.values()), {k: v for k, v in seen.items() if v}
