@@ -148,6 +148,7 @@ int rpr_init(int device, rpr_ctx** out_ctx) {
   RPR_HIP(init_beam_kernel_attributes());
   RPR_HIP(init_train_kernel_attributes());
   RPR_HIP(init_tail_kernel_attributes());
+  RPR_HIP(init_attn_mfma_attributes());
   auto* c = new rpr_ctx();
   c->device = device;
   if (const char* e = getenv("RPR_PRECISION"))

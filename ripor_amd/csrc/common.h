@@ -7,14 +7,11 @@
 #include <string>
 
 #include "../../include/ripor_hip.h"
+#include "attn_route.h"
 
 namespace rpr {
 
-constexpr int WAVE = 64;
-constexpr int MAX_LQ = 256;          // encoder tokens per query supported by the attention kernels
-constexpr int MAX_DEC_LEN = 64;      // decoder positions supported (reference uses 32 or 16)
-constexpr int DKV = 64;              // head dim the fast attention kernels are written for (t5-base/large); d_kv = 128 (t5-3b) runs
-                                     // on the generic kernels enc_attn_kernel<128> / dec_attn_kernel<., 128> without the forced tail
+constexpr int WAVE = 64;   // (MAX_LQ, MAX_DEC_LEN, DKV and the other constants the attention routes depend on: attn_route.h)
 
 // Environment switches. The product library reads a handful (README: precision, forced tail, fork depths, lane split, trie
 // threads, and the three selectors the test-suite compares bit for bit against the default: RPR_SELECT_RADIX,
@@ -434,14 +431,13 @@ struct EncAttnArgs {
   int dkv = 0;             // head dim (0 = 64); 128 (t5-3b) takes enc_attn_kernel<128>
 };
 hipError_t launch_enc_attn(const EncAttnArgs& a, hipStream_t s);
-// tail_kernels.hip: the search encoder's attention (<= 32 positions) on the fp32-MFMA tile; false = shape not taken
-bool launch_enc_attn_mfma_v2(const EncAttnArgs& a, hipStream_t s, hipError_t* err);
-// training forward, Lq <= 32, padded layout, fp32 output: one wave per (sequence, head) on fp32 MFMA tiles (tail_kernels.hip)
-hipError_t launch_train_self_attn_mfma(const EncAttnArgs& a, hipStream_t s);
-// its backward (Ls <= 32): dqkv and the per-(sequence, head) bias-gradient parts, as self_attn_bwd_kernel writes them
-hipError_t launch_train_self_attn_bwd_mfma(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias,
-                                           const int32_t* bucket, float* dqkv, float* dbias_part, int S, int Ls, int H, int buckets,
-                                           int causal, hipStream_t s);
+// attn_mfma.hip: runs the plans of launch_enc_attn whose kernels live there (ENC_V2, TRAIN_SELF_MFMA) ...
+hipError_t run_enc_attn_mfma(const AttnLaunch& p, const EncAttnArgs& a, hipStream_t s);
+// ... and the MFMA plan of launch_self_attn_bwd: dqkv and the per-(sequence, head) bias-gradient parts, as self_attn_bwd_kernel writes them
+hipError_t run_self_attn_bwd_mfma(const AttnLaunch& p, const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias,
+                                  const int32_t* bucket, float* dqkv, float* dbias_part, int S, int Ls, int H, int buckets, int causal,
+                                  hipStream_t s);
+extern AttnTuning g_attn_tuning;   // attn_mfma.hip: the development switches of the attention routes
 
 struct DecSelfAttnArgs {
   const float* q;          // [R, inner]
@@ -479,6 +475,8 @@ struct DecCrossAttnArgs {
   int dkv = 0;             // head dim (0 = 64); 128 (t5-3b) takes the generic kernel dec_attn_kernel<false, 128>
 };
 hipError_t launch_dec_cross_attn(const DecCrossAttnArgs& a, hipStream_t s);
+// t5_kernels.hip: runs a block cross-attention plan (CROSS_BLOCK64 / 128, CROSS_WAVE128), also for the tail and step launchers
+hipError_t run_cross_block(const AttnLaunch& p, const DecCrossAttnArgs& a, hipStream_t s);
 
 // ---- beam state + trie-constrained selection ------------------------------------------------------
 struct BeamState {           // one of two ping-pong buffers
@@ -578,7 +576,7 @@ hipError_t launch_zero_u64(unsigned long long* p, size_t n, hipStream_t s);
 hipError_t launch_mask_lengths(const int32_t* mask, int32_t* lens, int Q, int Lq, hipStream_t s,
                                unsigned int* status = nullptr);
 
-// ---- forced-tail evaluation (tail_kernels.hip; orchestration in passes.hip) ----------------------------------------
+// ---- forced-tail evaluation (tail_kernels.hip, its attention in attn_mfma.hip; orchestration in passes.hip) ---------
 // Once every beam of a query stands on a trie node under which a single distinct sequence remains, beam search can no
 // longer prune for that query: each beam has exactly one valid child per step, the B valid candidates beat every
 // masked one (-1e9) and the remaining tokens are the rest of the beam's code row. Such a query leaves the sequential
@@ -692,6 +690,7 @@ hipError_t launch_tail_rank(const TailRankArgs& a, hipStream_t s);
 hipError_t launch_flag_nonzero(const int* cnt, unsigned int* flag, hipStream_t s);
 hipError_t launch_max_row_norm(const float* E, const float* w, int rows, int d, float* out /*zeroed*/, hipStream_t s);
 hipError_t init_tail_kernel_attributes();
+hipError_t init_attn_mfma_attributes();
 
 // ---- teacher-forced forward of the ranking fine-tune step (train_kernels.hip) -------------------
 hipError_t launch_train_dec_embed(const float* start, const float* in_embeds, const int32_t* codes, float* out, int S,
@@ -734,7 +733,6 @@ struct ColsumSites {
 };
 int rmsnorm_bwd_parts(int rows);
 hipError_t launch_colsum_multi(const ColsumSites& p, int d, hipStream_t s);
-size_t self_attn_bwd_smem(int Ls, int buckets);
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
                                 hipStream_t s);

@@ -1,4 +1,4 @@
-// Device helpers shared by the kernel translation units (t5_kernels.hip, tail_kernels.hip).
+// Device helpers shared by the kernel translation units (t5_kernels.hip, tail_kernels.hip, attn_mfma.hip).
 #pragma once
 #include <hip/hip_fp16.h>
 

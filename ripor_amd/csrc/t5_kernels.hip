@@ -349,25 +349,19 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(EncAttnArgs a) {
   }
 }
 
-static size_t enc_attn_smem(int Lq, int D, bool stage_v = true) {
-  return ((size_t)Lq * (D + 1) + (stage_v ? (size_t)Lq * D : 0) + 4 * (size_t)Lq + 2 * (size_t)Lq + 4 * 8 * (size_t)D + (size_t)Lq) * sizeof(float);
-}
 hipError_t launch_enc_attn(const EncAttnArgs& a, hipStream_t s) {
-  if (a.Lq > MAX_LQ || a.buckets > 64) return hipErrorInvalidValue;
-  if (a.dkv == 128) {   // t5-3b heads: the generic kernel only
-    const size_t smem = enc_attn_smem(a.Lq, 128);
-    if (smem <= 160 * 1024) {                               // Lq <= ~150: K and V of a head in LDS
-      hipLaunchKernelGGL(enc_attn_kernel<128>, dim3(a.Q * a.H), dim3(256), smem, s, a);
-      return hipGetLastError();
-    }
-    const size_t smem_k = enc_attn_smem(a.Lq, 128, false);  // up to MAX_LQ = 256 tokens: K in LDS (155 KB), V from global memory
-    if (smem_k > 160 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((enc_attn_kernel<128, true>), dim3(a.Q * a.H), dim3(256), smem_k, s, a);
-    return hipGetLastError();
+  EncAttnIn in;
+  in.Q = a.Q; in.Lq = a.Lq; in.H = a.H; in.buckets = a.buckets; in.dkv = a.dkv;
+  in.causal = a.causal != 0; in.mask = a.mask != nullptr; in.offs = a.offs != nullptr; in.out_h = a.out_h != nullptr; in.mfma = a.mfma != 0;
+  const AttnLaunch p = plan_enc_attn(in, g_attn_tuning);
+  const dim3 grid(p.grid_x), blk(p.block);
+  switch (p.kernel) {
+    case ATTN_ENC_VALU64: hipLaunchKernelGGL(enc_attn_kernel<64>, grid, blk, p.smem, s, a); break;
+    case ATTN_ENC_VALU128: hipLaunchKernelGGL(enc_attn_kernel<128>, grid, blk, p.smem, s, a); break;
+    case ATTN_ENC_VALU128_VG: hipLaunchKernelGGL((enc_attn_kernel<128, true>), grid, blk, p.smem, s, a); break;
+    case ATTN_ENC_V2: case ATTN_TRAIN_SELF_MFMA: return run_enc_attn_mfma(p, a, s);   // attn_mfma.hip
+    default: return hipErrorInvalidValue;
   }
-  if (a.mfma && a.Lq <= 32 && !a.offs && !a.out_h) return launch_train_self_attn_mfma(a, s);
-  if (!a.mfma) { hipError_t e; if (launch_enc_attn_mfma_v2(a, s, &e)) return e; }
-  hipLaunchKernelGGL(enc_attn_kernel<64>, dim3(a.Q * a.H), dim3(256), enc_attn_smem(a.Lq, 64), s, a);
   return hipGetLastError();
 }
 
@@ -494,8 +488,6 @@ __device__ __forceinline__ float4 ld_stream(const float* p) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-constexpr int SELF_MAXIT_MAX = 9;  // 36 keys: covers L <= 35 (the reference uses L = 32 or 16)
-
 // SELF_MAXIT = row groups of 4 keys held in registers. Early steps use the small instantiations: fewer
 // VGPRs -> 8 waves per SIMD instead of 4, which is what hides the anc -> K/V dependent-load chain when a
 // wave only has a few hundred bytes to fetch.
@@ -607,33 +599,30 @@ __global__ __launch_bounds__(256) void dec_self_attn_fast_kernel(DecSelfAttnArgs
 hipError_t launch_dec_self_attn(const DecSelfAttnArgs& a_in, hipStream_t s) {
   DecSelfAttnArgs a = a_in;
   a.b_magic = div_magic(a.B); a.h_magic = div_magic(a.H);
-  const int items = a.Q * a.B * a.H;
-  if ((long)items >= (1l << 32) / std::max(a.B, a.H)) return hipErrorInvalidValue;   // udiv_magic's exact range
-  const dim3 grid((items + 3) / 4), blk(256);
-  if (a.dkv == 128) {   // t5-3b heads: two keys per register group; beyond 36 keys the generic one-wave-per-(beam, head) kernel
-    const int nk = a.t + 1;
-    if (nk <= 8) { hipLaunchKernelGGL((dec_self_attn_fast_kernel<4, 128>), grid, blk, 0, s, a); return hipGetLastError(); }
-    if (nk <= 16) { hipLaunchKernelGGL((dec_self_attn_fast_kernel<8, 128>), grid, blk, 0, s, a); return hipGetLastError(); }
-    if (nk <= 24) { hipLaunchKernelGGL((dec_self_attn_fast_kernel<12, 128>), grid, blk, 0, s, a); return hipGetLastError(); }
-    if (nk <= 36) { hipLaunchKernelGGL((dec_self_attn_fast_kernel<18, 128>), grid, blk, 0, s, a); return hipGetLastError(); }
-    if (a.t + 1 > MAX_LQ) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((dec_attn_kernel<true, 128>), grid, blk, 0, s, a.q, a.kcache, a.vcache, a.anc, a.anc_ld, a.rel_bias, a.bucket,
-                       (const int32_t*)nullptr, a.out, a.Q, a.B, a.H, a.t, 0, 0, a.out_h, a.o_ps, a.q_stride, a.h_stride, a.pos_stride,
-                       a.slot_stride, a.sat, a.nq_dev, (const int32_t*)nullptr);
-    return hipGetLastError();
+  const AttnLaunch p = plan_dec_self_attn(DecSelfAttnIn{a.Q, a.B, a.H, a.t, a.dkv});
+  const dim3 grid(p.grid_x), blk(p.block);
+  switch (p.kernel) {
+    case ATTN_SELF_FAST2: hipLaunchKernelGGL(dec_self_attn_fast_kernel<2>, grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST4: hipLaunchKernelGGL(dec_self_attn_fast_kernel<4>, grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST6: hipLaunchKernelGGL(dec_self_attn_fast_kernel<6>, grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST8: hipLaunchKernelGGL(dec_self_attn_fast_kernel<8>, grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST9: hipLaunchKernelGGL(dec_self_attn_fast_kernel<SELF_MAXIT_MAX>, grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST4_D128: hipLaunchKernelGGL((dec_self_attn_fast_kernel<4, 128>), grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST8_D128: hipLaunchKernelGGL((dec_self_attn_fast_kernel<8, 128>), grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST12_D128: hipLaunchKernelGGL((dec_self_attn_fast_kernel<12, 128>), grid, blk, 0, s, a); break;
+    case ATTN_SELF_FAST18_D128: hipLaunchKernelGGL((dec_self_attn_fast_kernel<18, 128>), grid, blk, 0, s, a); break;
+    case ATTN_SELF_GENERIC:
+      hipLaunchKernelGGL(dec_attn_kernel<true>, grid, blk, 0, s, a.q, a.kcache, a.vcache, a.anc, a.anc_ld, a.rel_bias, a.bucket,
+                         (const int32_t*)nullptr, a.out, a.Q, a.B, a.H, a.t, 0, 0, a.out_h, a.o_ps, a.q_stride, a.h_stride, a.pos_stride,
+                         a.slot_stride, a.sat, a.nq_dev);
+      break;
+    case ATTN_SELF_GENERIC_D128:
+      hipLaunchKernelGGL((dec_attn_kernel<true, 128>), grid, blk, 0, s, a.q, a.kcache, a.vcache, a.anc, a.anc_ld, a.rel_bias, a.bucket,
+                         (const int32_t*)nullptr, a.out, a.Q, a.B, a.H, a.t, 0, 0, a.out_h, a.o_ps, a.q_stride, a.h_stride, a.pos_stride,
+                         a.slot_stride, a.sat, a.nq_dev, (const int32_t*)nullptr);
+      break;
+    default: return hipErrorInvalidValue;
   }
-  const int nk = a.t + 1;
-  if (nk <= 8) { hipLaunchKernelGGL(dec_self_attn_fast_kernel<2>, grid, blk, 0, s, a); return hipGetLastError(); }
-  if (nk <= 16) { hipLaunchKernelGGL(dec_self_attn_fast_kernel<4>, grid, blk, 0, s, a); return hipGetLastError(); }
-  if (nk <= 24) { hipLaunchKernelGGL(dec_self_attn_fast_kernel<6>, grid, blk, 0, s, a); return hipGetLastError(); }
-  if (nk <= 32) { hipLaunchKernelGGL(dec_self_attn_fast_kernel<8>, grid, blk, 0, s, a); return hipGetLastError(); }
-  if (nk <= 4 * SELF_MAXIT_MAX) {
-    hipLaunchKernelGGL(dec_self_attn_fast_kernel<SELF_MAXIT_MAX>, grid, blk, 0, s, a);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(dec_attn_kernel<true>, dim3((items + 3) / 4), dim3(256), 0, s, a.q, a.kcache, a.vcache, a.anc,
-                     a.anc_ld, a.rel_bias, a.bucket, (const int32_t*)nullptr, a.out, a.Q, a.B, a.H, a.t, 0, 0, a.out_h, a.o_ps,
-                     a.q_stride, a.h_stride, a.pos_stride, a.slot_stride, a.sat, a.nq_dev);
   return hipGetLastError();
 }
 
@@ -641,7 +630,6 @@ hipError_t launch_dec_self_attn(const DecSelfAttnArgs& a_in, hipStream_t s) {
 // the query's B beams are staged once in LDS (the per-beam version re-read K/V B times through L2);
 // then three block-wide phases: scores — one thread per (beam, key) pair, float4 LDS reads with rows
 // padded to 68 floats (conflict-free); softmax — one wave per beam; P.V — one thread per (beam, 4 dims).
-constexpr int XK_LD = DKV + 4, QS_LD = DKV + 4;
 
 template <int D>   // head dim: 64, or 128 (t5-3b); rows padded by 4 floats either way (stride = 4 mod 32 banks)
 __global__ __launch_bounds__(256) void dec_cross_attn_block_kernel(DecCrossAttnArgs a) {
@@ -773,56 +761,36 @@ __global__ __launch_bounds__(256) void dec_cross_attn_block_kernel(DecCrossAttnA
 }
 
 hipError_t init_t5_kernel_attributes() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<64>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(dec_cross_attn_block_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(dec_cross_attn_block_kernel<64>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  const void* big[] = {reinterpret_cast<const void*>(enc_attn_kernel<64>), reinterpret_cast<const void*>(enc_attn_kernel<128>),
+                       reinterpret_cast<const void*>(enc_attn_kernel<128, true>), reinterpret_cast<const void*>(dec_cross_attn_block_kernel<128>),
+                       reinterpret_cast<const void*>(dec_cross_attn_block_kernel<64>)};
+  for (const void* f : big) {
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
-hipError_t launch_dec_cross_attn(const DecCrossAttnArgs& a_in, hipStream_t s) {
+// runs a plan of plan_cross_block (attn_route.h); the tail and step launchers of attn_mfma.hip hand theirs over too
+hipError_t run_cross_block(const AttnLaunch& p, const DecCrossAttnArgs& a_in, hipStream_t s) {
   DecCrossAttnArgs a = a_in;
-  if (a.Lq > MAX_LQ) return hipErrorInvalidValue;
-  if (a.dkv == 128) {   // t5-3b heads
-    // the block kernel (K / V of the (query, head) staged once for all beams) when everything fits one block's LDS ...
-    auto smem128 = [&](int nb) { return ((size_t)a.Lq * (132 + 128) + (size_t)nb * (132 + 2 * (a.Lq + 1)) + 4) * sizeof(float); };
-    a.bchunk = 0;
-    int chunks128 = 1;
-    if (smem128(a.B) > 96 * 1024) {   // many rows per query (the tail pass: beams x remaining positions): chunks of the rows over blockIdx.y
-      a.bchunk = 64;
-      while (a.bchunk > 1 && smem128(a.bchunk) > 96 * 1024) a.bchunk >>= 1;
-      chunks128 = (a.B + a.bchunk - 1) / a.bchunk;
-    }
-    if (smem128(a.bchunk ? a.bchunk : a.B) <= 160 * 1024) {
-      hipLaunchKernelGGL(dec_cross_attn_block_kernel<128>, dim3(a.Q * a.H, chunks128), dim3(256), smem128(a.bchunk ? a.bchunk : a.B), s, a);
-      return hipGetLastError();
-    }
-    a.bchunk = 0;
-    // ... else one wave per (beam, head) over the query's encoder K / V rows (unattended keys masked)
-    const long items = (long)a.Q * a.B * a.H;
-    hipLaunchKernelGGL((dec_attn_kernel<false, 128>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, a.q, a.xk, a.xv,
-                       (const uint16_t*)nullptr, 0, (const float*)nullptr, (const int32_t*)nullptr, a.mask, a.out, a.Q, a.B, a.H, 0, a.Lq,
-                       a.xld, a.out_h, a.o_ps, (size_t)0, (size_t)0, (size_t)0, (size_t)0, a.sat, a.nq_dev, a.offs);
-    return hipGetLastError();
+  a.bchunk = p.bchunk;
+  const dim3 grid(p.grid_x, p.grid_y), blk(p.block);
+  switch (p.kernel) {
+    case ATTN_CROSS_BLOCK64: hipLaunchKernelGGL(dec_cross_attn_block_kernel<64>, grid, blk, p.smem, s, a); break;
+    case ATTN_CROSS_BLOCK128: hipLaunchKernelGGL(dec_cross_attn_block_kernel<128>, grid, blk, p.smem, s, a); break;
+    case ATTN_CROSS_WAVE128:   // one wave per (row, head) over the query's encoder K / V rows (unattended keys masked)
+      hipLaunchKernelGGL((dec_attn_kernel<false, 128>), grid, blk, 0, s, a.q, a.xk, a.xv, (const uint16_t*)nullptr, 0, (const float*)nullptr,
+                         (const int32_t*)nullptr, a.mask, a.out, a.Q, a.B, a.H, 0, a.Lq, a.xld, a.out_h, a.o_ps, (size_t)0, (size_t)0, (size_t)0,
+                         (size_t)0, a.sat, a.nq_dev, a.offs);
+      break;
+    default: return hipErrorInvalidValue;
   }
-  auto smem_for = [&](int nb) { return ((size_t)a.Lq * (XK_LD + DKV) + (size_t)nb * (QS_LD + 2 * (a.Lq + 1)) + 4) * sizeof(float); };
-  a.bchunk = 0;
-  int chunks = 1;
-  if (smem_for(a.B) > 64 * 1024) {   // large beams: split the query's beams over blockIdx.y (K/V re-staged per chunk)
-    a.bchunk = 64;
-    while (a.bchunk > 1 && smem_for(a.bchunk) > 64 * 1024) a.bchunk >>= 1;
-    chunks = (a.B + a.bchunk - 1) / a.bchunk;
-  }
-  const size_t smem = smem_for(a.bchunk ? a.bchunk : a.B);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(dec_cross_attn_block_kernel<64>, dim3(a.Q * a.H, chunks), dim3(256), smem, s, a);
   return hipGetLastError();
+}
+
+hipError_t launch_dec_cross_attn(const DecCrossAttnArgs& a, hipStream_t s) {
+  return run_cross_block(plan_cross_block(CrossAttnIn{a.Q, a.B, a.H, a.Lq, a.dkv}), a, s);
 }
 
 // zeroes the per-site row sums of a pass (a kernel node rather than a memset node: memset nodes captured into the

@@ -563,22 +563,22 @@ __global__ __launch_bounds__(512) void bias_reduce_kernel(const float* __restric
   }
 }
 
-size_t self_attn_bwd_smem(int Ls, int buckets) {
-  (void)buckets;   // <= 64, fixed slot
-  return ((size_t)4 * Ls * AST + 2 * (size_t)Ls * (Ls + 1) + 64 + 5 * (size_t)Ls) * sizeof(float);
-}
-
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
                                 hipStream_t s) {
-  const size_t smem = self_attn_bwd_smem(Ls, buckets);
-  if (smem > 160 * 1024 || buckets > 64) return hipErrorInvalidValue;
-  if (Ls <= 32) {   // one wave per (sequence, head) on the fp32 matrix cores (tail_kernels.hip)
-    const hipError_t e = launch_train_self_attn_bwd_mfma(qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, s);
-    if (e != hipSuccess) return e;
-  } else
-  hipLaunchKernelGGL(self_attn_bwd_kernel, dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S, Ls,
-                     H, buckets, causal);
+  const AttnLaunch p = plan_self_attn_bwd(SelfAttnBwdIn{S, Ls, H, buckets});
+  switch (p.kernel) {
+    case ATTN_TRAIN_BWD_MFMA: {   // attn_mfma.hip
+      const hipError_t e = run_self_attn_bwd_mfma(p, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, s);
+      if (e != hipSuccess) return e;
+      break;
+    }
+    case ATTN_TRAIN_BWD_VALU:
+      hipLaunchKernelGGL(self_attn_bwd_kernel, dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S,
+                         Ls, H, buckets, causal);
+      break;
+    default: return hipErrorInvalidValue;
+  }
   hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 """The second-generation fp32-MFMA attention kernels (tail self / cross attention, search encoder attention;
-ripor_amd/csrc/tail_kernels.hip) against the kernels they replace, through the product path: the same searches in
+ripor_amd/csrc/attn_mfma.hip; routes: attn_route.h) against the kernels they replace, through the product path: the same searches in
 subprocesses that load the development build of the library (RPR_DEV_LIB=1) and differ only in RPR_TAIL_ATTN_GEN /
 RPR_ENC_ATTN_MFMA / RPR_STEP_CROSS_MFMA (read once, when the library loads). The tail kernels issue the same MFMAs in the same order and must give the same bits; the encoder and the step
 cross-attention move from VALU sums to MFMA sums (fp32 rounding order changes): same ranked smtids, scores within 1e-5.

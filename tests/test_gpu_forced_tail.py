@@ -1,5 +1,5 @@
 """-m gpu: the forced-tail evaluation (rpr_search's forks + teacher-forced tail passes, ripor_amd/csrc/api.hip,
-passes.hip, tail_kernels.hip) against the plain step-by-step loop and against the CPU oracle.
+passes.hip, tail_kernels.hip, attn_mfma.hip) against the plain step-by-step loop and against the CPU oracle.
 
 The step-by-step loop is what the reference does (tasks/generation.py:423-540, one model call + mask + top-k per
 position) and is itself pinned to the reference's golden vectors (test_gpu_parity.py, which also runs every golden with
@@ -483,7 +483,7 @@ def test_optimistic_mode_backs_off_after_repeated_leftovers(E):
 @pytest.mark.parametrize("lens", [(20, 60), (70, 150)])
 def test_tail_pass_with_long_queries(E, lens):
     """Cross-attention of the tail pass over long queries: 33-64 encoder keys take the two-key-tile MFMA kernel, more than 64
-    the block kernel of the sequential steps (tail_kernels.hip::launch_tail_cross_attn). Forced tail vs the plain loop, and
+    the block kernel of the sequential steps (attn_route.h::plan_tail_cross_attn). Forced tail vs the plain loop, and
     the CPU oracle on two queries."""
     from oracle import beam_ref, t5_ref
     from ripor_amd.utils import synth
@@ -503,6 +503,42 @@ def test_tail_pass_with_long_queries(E, lens):
     finally:
         ctx.set_fork_depths(None)
     assert stats and stats[0]["forced"] + stats[1]["forced"] > 0, stats
+    pm = beam_ref.PrefixMaskRef(beam_ref.build_list_smtid_to_nextids(synth.codes_to_docid_to_smtid(codes)), V)
+    seqs, sc = beam_ref.beam_search_ref(t5_ref.T5RefCached(sd, dims), pm, ids[:2], mask[:2], B, L, use_kv_cache=True)
+    ref_tok, ref_sc = seqs.numpy().reshape(2, B, L + 1)[:, :, 1:], sc.numpy().reshape(2, B)
+    got_tok, got_sc = res.tokens[:2].cpu().numpy(), res.scores[:2].cpu().numpy()
+    near = np.zeros((2, B), dtype=bool)
+    near[:, 1:] |= (ref_sc[:, :-1] - ref_sc[:, 1:]) <= ORDER_TOL
+    near[:, :-1] |= (ref_sc[:, :-1] - ref_sc[:, 1:]) <= ORDER_TOL
+    assert ((got_tok == ref_tok).all(axis=2) | near).all()
+    np.testing.assert_allclose(got_sc, ref_sc, atol=SCORE_TOL, rtol=0)
+
+
+@pytest.mark.parametrize("L,forks", [(40, [4, 12]), (16, [9])])
+def test_first_generation_tail_self_attention_by_default(E, L, forks):
+    """The two shapes that take the first-generation tail self-attention tiles with every switch at its default
+    (attn_route.h: plan_tail_self_attn). L = 40, forks [4, 12]: more than 32 keys, so two key tiles; the fork at 4 leaves
+    36 tail rows per sequence = two row tiles and the separate output strip, the fork at 12 is deeper than 8. L = 16, fork [9]:
+    one key tile, but a fork deeper than the second generation's eight cache rows. Q = 4, B = 4.
+    The trie of the first case: 20 000 uniform documents, of which every document of the first half whose second token is
+    2 mod 4 has a sibling in the second half with the same first eight tokens — a beam on such a prefix holds two sequences
+    at depth 4 and one at depth 12, so some queries leave at the first fork and the others at the second. Forced tail vs the
+    plain loop, and the CPU oracle on two queries."""
+    from oracle import beam_ref, t5_ref
+    from ripor_amd.utils import synth
+    V, B, N, Q = 256, 4, 20_000, 4
+    codes = synth.make_codes(N, L, V, seed=77)
+    if len(forks) > 1:
+        half = N // 2
+        fam = codes[:half, 1] % 4 == 2
+        codes[half:][fam, :8] = codes[:half][fam, :8]
+    ctx, model, trie, sd, dims, ids, mask = _setup(E, codes, L, V, Q=Q)
+    ctx.set_fork_depths(forks)
+    try:
+        res, plain, stats = _same_as_plain(ctx, E, model, trie, ids, mask, B, L, f"first-generation self-attention, L = {L}, forks {forks}")
+    finally:
+        ctx.set_fork_depths(None)
+    assert [f["depth"] for f in stats] == forks and all(f["forced"] > 0 for f in stats), stats
     pm = beam_ref.PrefixMaskRef(beam_ref.build_list_smtid_to_nextids(synth.codes_to_docid_to_smtid(codes)), V)
     seqs, sc = beam_ref.beam_search_ref(t5_ref.T5RefCached(sd, dims), pm, ids[:2], mask[:2], B, L, use_kv_cache=True)
     ref_tok, ref_sc = seqs.numpy().reshape(2, B, L + 1)[:, :, 1:], sc.numpy().reshape(2, B)

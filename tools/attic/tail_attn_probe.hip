@@ -1,8 +1,8 @@
-// A/B of the two generations of the fp32-MFMA tail attention kernels (tail_kernels.hip) at the bench's shape, outside
+// A/B of the two generations of the fp32-MFMA tail attention kernels (attn_mfma.hip) at the bench's shape, outside
 // the search: same synthetic inputs, outputs compared bit for bit, launches timed with hipEvents on an idle chip.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ripor_amd/csrc -I include tools/tail_attn_probe.hip \
-//         -L ripor_amd -lripor_hip -Wl,-rpath,'$ORIGIN/../ripor_amd' -o tools/tail_attn_probe
-//   tools/tail_attn_probe [queries = 2150] [half]
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ripor_amd/csrc -I include tools/attic/tail_attn_probe.hip \
+//         -L ripor_amd -lripor_hip -Wl,-rpath,'$ORIGIN/../ripor_amd' -o tools/attic/tail_attn_probe
+//   tools/attic/tail_attn_probe [queries = 2150] [half]
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -14,7 +14,7 @@
 #include "common.h"
 
 namespace rpr {
-extern int g_tail_attn_gen, g_tail_attn_opt, g_tail_cross_tpw;
+extern int g_tail_attn_opt, g_tail_cross_tpw;
 }
 using namespace rpr;
 
@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
     const double gb = ((double)rows * 4 * inner * 4 + 2.0 * nseq * T * inner * 4) / 1e9;
     printf("self-attention: %.2f GB algorithmic per launch\n", gb);
     auto run = [&](int gen, int opt, __half* out, const char* name) {
-      g_tail_attn_gen = gen; g_tail_attn_opt = opt; a.out_h = out;
+      g_attn_tuning.gen = gen; g_tail_attn_opt = opt; a.out_h = out;
       CK(hipMemset(out, 0xff, 2 * rows * inner * sizeof(__half)));
       const double us = time_us([&] { return launch_tail_self_attn(a, g_stream); });
       printf("  %-44s %8.1f us  %6.2f TB/s\n", name, us, gb / us * 1e3);
@@ -138,7 +138,7 @@ int main(int argc, char** argv) {
     printf("cross-attention: %.2f GB algorithmic per launch (%zu encoder rows, mean %.1f per query)\n", gb, tp, (double)tp / Q);
     g_tail_attn_opt = 0;
     auto run = [&](int gen, int tpw, __half* out, const char* name) {
-      g_tail_attn_gen = gen; g_tail_cross_tpw = tpw; a.out_h = out;
+      g_attn_tuning.gen = gen; g_tail_cross_tpw = tpw; a.out_h = out;
       CK(hipMemset(out, 0xff, 2 * rows * inner * sizeof(__half)));
       const double us = time_us([&] { return launch_tail_cross_attn(a, g_stream); });
       printf("  %-44s %8.1f us  %6.2f TB/s\n", name, us, gb / us * 1e3);
