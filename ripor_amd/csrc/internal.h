@@ -13,6 +13,7 @@
 #include "common.h"
 #include "gemm_route.h"
 #include "search_plan.h"
+#include "train_layout.h"
 #include "trie.h"
 
 namespace rpr {
@@ -61,9 +62,7 @@ struct rpr_model {
   struct PlaneJob { const float* w; size_t n; __half* dst; const float* ln; float pre; size_t plane_stride; };   // plane_stride 0 = n
   std::vector<PlaneJob> plane_jobs;
   // trainable tensors in the order of the flat gradient / optimizer-state buffers (train_api.hip)
-  struct ParamRef { int kind; int layer; float* ptr; size_t numel; size_t offset; };
-  std::vector<ParamRef> params;
-  size_t params_total = 0;
+  rpr::ParamOrder params;
   // bound of |logit| for any decoder state: sqrt(d_model) * max row norm of the output codebooks times the final
   // layer-norm weight (Cauchy-Schwarz on the RMS-normalised hidden state), times the scaleup factor; computed at load.
   // The forced-tail fork uses it to prove that no masked (-1e9) candidate can overtake a valid one (passes.hip: enqueue_fork).

@@ -185,43 +185,19 @@ struct TrainWs {
 
 namespace {
 
-enum { K_SHARED, K_ENC_REL, K_DEC_REL, K_ENC_FLN, K_DEC_FLN, K_START, K_IN_EMB, K_OUT_EMB, K_XKV, K_ENC_LN0, K_ENC_QKV, K_ENC_O,
-       K_ENC_LN1, K_ENC_WI, K_ENC_WO, K_DEC_LN0, K_DEC_QKV, K_DEC_O, K_DEC_LN1, K_DEC_XQ, K_DEC_XO, K_DEC_LN2, K_DEC_WI, K_DEC_WO };
-
+// The flat parameter order is train_layout.h's (ParamOrder); here every slot gets its tensor. The model names the layer
+// tensors stack by stack: this is the one place that maps (sub-block, role) to those names.
 void build_params(rpr_model* m) {
-  if (!m->params.empty()) return;
+  if (!m->params.slots.empty()) return;
   const auto& d = m->d;
-  const size_t dm = d.d_model, inner = m->inner(), dff = d.d_ff, nd = d.num_decoder_layers;
-  size_t off = 0;
-  auto add = [&](int kind, int layer, const float* p, size_t n) {
-    m->params.push_back({kind, layer, const_cast<float*>(p), n, off});
-    off += n;
-  };
-  add(K_SHARED, -1, d.shared, (size_t)d.vocab_size * dm);
-  add(K_ENC_REL, -1, d.enc_rel_bias, (size_t)d.rel_buckets * d.num_heads);
-  add(K_DEC_REL, -1, d.dec_rel_bias, (size_t)d.rel_buckets * d.num_heads);
-  add(K_ENC_FLN, -1, d.enc_final_ln, dm);
-  add(K_DEC_FLN, -1, d.dec_final_ln, dm);
-  add(K_START, -1, d.start_embed, dm);
-  add(K_IN_EMB, -1, d.in_embeds, (size_t)d.L * d.V * dm);
-  if (d.out_embeds != d.in_embeds) add(K_OUT_EMB, -1, d.out_embeds, (size_t)d.L * d.V * dm);
-  add(K_XKV, -1, d.dec_xkv, nd * 2 * inner * dm);
-  for (int i = 0; i < d.num_layers; ++i) {
-    add(K_ENC_LN0, i, m->enc_ln0[i], dm); add(K_ENC_QKV, i, m->enc_qkv[i], 3 * inner * dm); add(K_ENC_O, i, m->enc_o[i], dm * inner);
-    add(K_ENC_LN1, i, m->enc_ln1[i], dm); add(K_ENC_WI, i, m->enc_wi[i], dff * dm); add(K_ENC_WO, i, m->enc_wo[i], dm * dff);
-  }
-  for (int i = 0; i < (int)nd; ++i) {
-    add(K_DEC_LN0, i, m->dec_ln0[i], dm); add(K_DEC_QKV, i, m->dec_qkv[i], 3 * inner * dm); add(K_DEC_O, i, m->dec_o[i], dm * inner);
-    add(K_DEC_LN1, i, m->dec_ln1[i], dm); add(K_DEC_XQ, i, m->dec_xq[i], inner * dm); add(K_DEC_XO, i, m->dec_xo[i], dm * inner);
-    add(K_DEC_LN2, i, m->dec_ln2[i], dm); add(K_DEC_WI, i, m->dec_wi[i], dff * dm); add(K_DEC_WO, i, m->dec_wo[i], dm * dff);
-  }
-  m->params_total = off;
-}
-
-size_t param_offset(const rpr_model* m, int kind, int layer) {
-  for (const auto& p : m->params)
-    if (p.kind == kind && p.layer == layer) return p.offset;
-  return (size_t)-1;
+  m->params = ParamOrder(d);
+  const std::vector<const float*>* layer[K_END - K_ENC_LAYER] = {
+      &m->enc_ln0, &m->enc_qkv, &m->enc_o, &m->enc_ln1, &m->enc_wi, &m->enc_wo,
+      &m->dec_ln0, &m->dec_qkv, &m->dec_o, &m->dec_ln1, &m->dec_xq, &m->dec_xo, &m->dec_ln2, &m->dec_wi, &m->dec_wo};
+  const float* global[K_ENC_LAYER] = {d.shared, d.enc_rel_bias, d.dec_rel_bias, d.enc_final_ln, d.dec_final_ln, d.start_embed,
+                                      d.in_embeds, d.out_embeds, d.dec_xkv};
+  for (ParamSlot& p : m->params.slots)
+    p.ptr = const_cast<float*>(p.kind < K_ENC_LAYER ? global[p.kind] : (*layer[p.kind - K_ENC_LAYER])[(size_t)p.layer]);
 }
 
 int tensure(rpr_ctx* c, DevBuf& b, size_t bytes) {   // like ensure(), without touching the search graphs
@@ -235,19 +211,6 @@ int tensure(rpr_ctx* c, DevBuf& b, size_t bytes) {   // like ensure(), without t
   c->tws->bytes += want;
   return 0;
 }
-
-inline int pad32(int n) { return (n + 31) & ~31; }
-inline int pad64(int n) { return (n + 63) & ~63; }
-// row stride (elements) of the transposed bf16 operands [cols][pad64(rows)] of the weight-gradient products. (Padding it off
-// the power of two — 8192 rows = 16 KB looked like a memory-channel hazard for K-tiles that are 128-byte pieces of 256 rows —
-// measured no different: 27.4 ms per step unpadded, 27.6 with 64 elements, 28.3 with 32; HISTORY.md.)
-inline int ldT(int rows) { return pad64(rows); }
-
-struct Dims {
-  int bz, Lq, L, docs, S, R, T, dm, inner, dff, H, ne, nd, V, xld, buckets;   // docs: decoder sequences per query (S = bz docs)
-  float eps, post;
-  size_t enc_stride, dec_stride;   // floats per saved layer
-};
 
 // Split-precision training GEMM: both operands are fp32 tensors of unknown magnitude (activations, gradients, weights
 // that change every step), so each gets a per-tensor power-of-two scale from its absolute maximum, found on the device
@@ -349,46 +312,38 @@ void gemm(Launcher& Ln, const float* A, int lda, const float* B, int ldb, float*
   Ln.run(RPR_K_GEMM, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), [&] { return launch_gemm(g, Ln.s); });
 }
 
-// Saved X^T operands (bf16 mode): encoder layer i holds [qkv | o | wi | wo], then the cross K/V projection, then decoder
-// layer i [qkv | o | xq | xo | wi | wo]; a slot is [K][pad64(rows)] bf16 with row stride ldT(rows).
-enum XtSite { XT_QKV, XT_O, XT_XQ, XT_XO, XT_WI, XT_WO };
-struct XtLayout {
-  size_t Tp, Rp, enc_layer, dec_layer, xkv_off, dec_off, total;
-  int dm, inner, dff;
-  explicit XtLayout(const Dims& D) : Tp(ldT(D.T)), Rp(ldT(D.R)), dm(D.dm), inner(D.inner), dff(D.dff) {   // Tp, Rp: row strides
-    enc_layer = Tp * (size_t)(2 * dm + inner + dff);
-    dec_layer = Rp * (size_t)(3 * dm + 2 * inner + dff);
-    xkv_off = enc_layer * D.ne;
-    dec_off = xkv_off + Tp * (size_t)dm;
-    total = dec_off + dec_layer * D.nd;
+// One stack on the device: its table (train_layout.h) with the buffers the table's offsets index, and what its self-attention
+// takes. Sub-block j of layer i reads the stream x(i, j) and writes x(i, j + 1); the last one writes the next layer's input,
+// the last layer's x_end.
+struct Stack {
+  const StackLayout& lay;
+  const ParamOrder& po;
+  float *act, *x_end;           // saved activations; the stream behind the last layer
+  __half* xT;                   // saved X^T operands (bf16 mode); null: nothing is saved (every other mode)
+  const int32_t* mask;          // self-attention: key mask (encoder) or none, bias table and buckets, sequences x length, causal?
+  const float* rel_bias; const int32_t* bucket;
+  int nseq, len, causal;
+  float* x(int i, int j) const {
+    if (j == lay.nsub) { ++i; j = 0; }
+    return i == lay.layers ? x_end : act + lay.act(i, lay.at[j].x);
   }
-  size_t enc(int layer, XtSite st) const {
-    const size_t o = enc_layer * layer;
-    switch (st) {
-      case XT_QKV: return o;
-      case XT_O: return o + Tp * dm;
-      case XT_WI: return o + Tp * (size_t)(dm + inner);
-      default: return o + Tp * (size_t)(2 * dm + inner);   // XT_WO
-    }
-  }
-  size_t dec(int layer, XtSite st) const {
-    const size_t o = dec_off + dec_layer * layer;
-    switch (st) {
-      case XT_QKV: return o;
-      case XT_O: return o + Rp * dm;
-      case XT_XQ: return o + Rp * (size_t)(dm + inner);
-      case XT_XO: return o + Rp * (size_t)(2 * dm + inner);
-      case XT_WI: return o + Rp * (size_t)(2 * dm + 2 * inner);
-      default: return o + Rp * (size_t)(3 * dm + 2 * inner);   // XT_WO
-    }
-  }
+  float* in(int i, int j) const { return act + lay.act(i, lay.at[j].in); }
+  float* mid(int i, int j) const { return act + lay.act(i, lay.at[j].mid); }
+  void* xt_in(int i, int j) const { return xT ? xT + lay.xt(i, lay.at[j].xt_in) : nullptr; }
+  void* xt_out(int i, int j) const { return xT ? xT + lay.xt(i, lay.at[j].xt_out) : nullptr; }
+  const ParamSlot* params(int i, int j) const { return po.sub(lay, i, j); }   // ln, W_in, W_out
 };
-struct XtSlots {     // null base: nothing is saved (every mode but bf16)
-  __half* base; XtLayout lay;
-  void* enc(int l, XtSite st) const { return base ? base + lay.enc(l, st) : nullptr; }
-  void* dec(int l, XtSite st) const { return base ? base + lay.dec(l, st) : nullptr; }
-  void* xkv() const { return base ? base + lay.xkv_off : nullptr; }
-};
+Stack enc_stack(const rpr_ctx* c, const rpr_model* m, const TrainDims& D, const TrainLayout& Y, const int32_t* mask) {
+  TrainWs& w = *c->tws;
+  float* act = P<float>(w.enc_act);
+  return {Y.enc, m->params, act, act + Y.enc.act(D.ne, 0), c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr,
+          mask, m->d.enc_rel_bias, m->enc_bucket, D.bz, D.Lq, 0};
+}
+Stack dec_stack(const rpr_ctx* c, const rpr_model* m, const TrainDims& D, const TrainLayout& Y) {
+  TrainWs& w = *c->tws;
+  return {Y.dec, m->params, P<float>(w.dec_act), P<float>(w.x_last), c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr,
+          nullptr, m->d.dec_rel_bias, m->dec_bucket, D.S, D.L, 1};
+}
 
 // bf16 copies of every GEMM weight, refreshed at the start of each pass (the weights change between passes: AdamW, or the
 // caller writing through rpr_param_info's pointers). The table of tensors is built once per model.
@@ -399,43 +354,42 @@ int refresh_weight_cache(Launcher& Ln, rpr_ctx* c, rpr_model* m) {
     std::vector<int> pref;
     w.wc_off.clear();
     int tiles = 0;
-    const auto& d = m->d;
-    const int dm = d.d_model, inner = m->inner(), dff = d.d_ff, nd = d.num_decoder_layers;
-    auto add = [&](const float* p, int R, int C) {
-      size_t off = (size_t)-1;
-      for (const auto& pr : m->params) if (pr.ptr == p) off = pr.offset;
-      if (off == (size_t)-1 || (R & 1) || (C & 3)) return;
-      segs.push_back(WSeg{p, R, C, (unsigned long long)off});
+    auto add = [&](const ParamSlot& p, int R, int C) {
+      if ((R & 1) || (C & 3)) return;
+      segs.push_back(WSeg{p.ptr, R, C, (unsigned long long)p.offset});
       pref.push_back(tiles);
       tiles += ((R + 63) / 64) * ((C + 63) / 64);
-      w.wc_off[p] = off;
+      w.wc_off[p.ptr] = p.offset;
     };
-    for (int i = 0; i < d.num_layers; ++i) {
-      add(m->enc_qkv[i], 3 * inner, dm); add(m->enc_o[i], dm, inner); add(m->enc_wi[i], dff, dm); add(m->enc_wo[i], dm, dff);
-    }
-    add(d.dec_xkv, nd * 2 * inner, dm);
-    for (int i = 0; i < nd; ++i) {
-      add(m->dec_qkv[i], 3 * inner, dm); add(m->dec_o[i], dm, inner); add(m->dec_xq[i], inner, dm); add(m->dec_xo[i], dm, inner);
-      add(m->dec_wi[i], dff, dm); add(m->dec_wo[i], dm, dff);
-    }
+    const auto& d = m->d;
+    auto add_stack = [&](const StackLayout& st) {   // W_in [n_in][d_model] and W_out [d_model][k_out] of every sub-block
+      for (int i = 0; i < st.layers; ++i)
+        for (int j = 0; j < st.nsub; ++j) {
+          const ParamSlot* p = m->params.sub(st, i, j);
+          add(p[P_WIN], st.sub[j].n_in, st.dm); add(p[P_WOUT], st.dm, st.sub[j].k_out);
+        }
+    };
+    add_stack(StackLayout(false, 0, d.num_layers, d.d_model, m->inner(), d.d_ff));
+    add(m->params.at(K_XKV), d.num_decoder_layers * 2 * m->inner(), d.d_model);
+    add_stack(StackLayout(true, 0, d.num_decoder_layers, d.d_model, m->inner(), d.d_ff));
     int e = tensure(c, w.wseg, segs.size() * sizeof(WSeg));
     if (!e) e = tensure(c, w.wpref, pref.size() * sizeof(int));
-    if (!e) e = tensure(c, w.wc, m->params_total * sizeof(__half));
-    if (!e) e = tensure(c, w.wcT, m->params_total * sizeof(__half));
+    if (!e) e = tensure(c, w.wc, m->params.total * sizeof(__half));
+    if (!e) e = tensure(c, w.wcT, m->params.total * sizeof(__half));
     if (e) { w.wc_off.clear(); return e; }
     RPR_HIP(hipMemcpyAsync(w.wseg.p, segs.data(), segs.size() * sizeof(WSeg), hipMemcpyHostToDevice, Ln.s));
     RPR_HIP(hipMemcpyAsync(w.wpref.p, pref.data(), pref.size() * sizeof(int), hipMemcpyHostToDevice, Ln.s));
     RPR_HIP(hipStreamSynchronize(Ln.s));              // the host vectors go out of scope
     w.wc_model = m; w.wc_nseg = (int)segs.size(); w.wc_tiles = tiles;
   }
-  Ln.run(RPR_K_OTHER, 0, 8.0 * (double)m->params_total, [&] {
+  Ln.run(RPR_K_OTHER, 0, 8.0 * (double)m->params.total, [&] {
     return launch_weights_bf16(P<WSeg>(w.wseg), P<int>(w.wpref), w.wc_nseg, w.wc_tiles, w.wc.p, w.wcT.p, Ln.s);
   });
   return Ln.err;
 }
 
 struct Bwd {
-  Launcher& Ln; rpr_ctx* c; TrainWs& w; const Dims& D;
+  Launcher& Ln; rpr_ctx* c; TrainWs& w; const TrainDims& D;
   // dX[M, K] = dY[M, N] W[N, K]  and  dW[N, K] = dY[M, N]^T X[M, K]  (dX may alias X: X is consumed first); dX on the main
   // stream, dW on the side stream (w.side) except in f32 mode
   // relu_act (bf16 mode only): dY is the gradient w.r.t. relu(.) and relu_act the stored activation; the mask is applied
@@ -578,7 +532,7 @@ struct Bwd {
   }
 };
 
-int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
+int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
   if (!c->tws) c->tws = new TrainWs();
   TrainWs& w = *c->tws;
   const size_t f = sizeof(float), R = D.R, T = D.T, dm = D.dm, inner = D.inner, dff = D.dff;
@@ -586,8 +540,9 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
   const size_t wide = std::max<size_t>(std::max<size_t>(dff, 3 * inner), (size_t)D.xld);
   int e = 0;
   auto E = [&](DevBuf& b, size_t bytes) { if (!e) e = tensure(c, b, bytes); };
-  E(w.enc_act, (size_t)D.ne * D.enc_stride * f + T * dm * f);     // + the encoder's last stream
-  E(w.dec_act, (size_t)D.nd * D.dec_stride * f);
+  const TrainLayout Y(D);
+  E(w.enc_act, (size_t)D.ne * Y.enc.act_stride * f + T * dm * f);     // + the encoder's last stream
+  E(w.dec_act, (size_t)D.nd * Y.dec.act_stride * f);
   E(w.enc_out, T * dm * f); E(w.xkv, T * (size_t)D.xld * f); E(w.x_last, R * dm * f);
   E(w.scores, R * f); E(w.margins, 8 * (size_t)D.bz * f); E(w.dscores, R * f);
   E(w.in_idx, R * 4); E(w.out_idx, R * 4);
@@ -596,11 +551,9 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
   E(w.dattn, rows * inner * f); E(w.dxkv, T * (size_t)D.xld * f); E(w.denc, T * dm * f);
   E(w.tA, wide * rp * f);
   // grouped weight gradients (bf16 mode): dY^T of one layer's products, [N_out][pad64(rows)] bf16 each, 256-byte aligned
-  const size_t Rp = ldT(D.R), Tp = ldT(D.T);
-  const size_t dec = (3 * dm + dff + 4 * inner) * Rp, enc = (2 * dm + dff + 3 * inner) * Tp, xkv = (size_t)D.xld * Tp;
   const bool bf16 = c->precision == RPR_PREC_BF16;
-  if (!e) e = w.side.create(c, wide * rp * f, bf16 ? std::max(std::max(dec, enc), xkv) * sizeof(__half) + 8 * 256 : 0);
-  if (bf16) { E(w.xT, XtLayout(D).total * sizeof(__half)); E(w.bfb, rp * dff * sizeof(__half)); }
+  if (!e) e = w.side.create(c, wide * rp * f, bf16 ? Y.dyT_max() * sizeof(__half) + 8 * 256 : 0);
+  if (bf16) { E(w.xT, Y.xt_total * sizeof(__half)); E(w.bfb, rp * dff * sizeof(__half)); }
   E(w.wT, std::max<size_t>(std::max<size_t>(dff * dm, 3 * inner * dm), (size_t)D.xld * dm) * f);
   E(w.w_part, ColsumSites::MAXS * ((rows + 3) / 4) * dm * f);   // the partials of up to four norm sites (Bwd::norm_bwd)
   E(w.bias_part, std::max<size_t>((size_t)D.S, (size_t)D.bz) * D.H * D.buckets * f);
@@ -609,36 +562,18 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const Dims& D) {
   return e;
 }
 
-// saved activations of one layer (floats, row-major)
-struct EncAct { float *x, *qkv, *attn, *xm, *ff; };
-struct DecAct { float *x0, *qkv, *a0, *x1, *qx, *a1, *x2, *ff; };
-EncAct enc_act(const TrainWs& w, const Dims& D, int i) {
-  float* b = P<float>(w.enc_act) + (size_t)i * D.enc_stride;
-  const size_t T = D.T;
-  EncAct a; a.x = b; a.qkv = a.x + T * D.dm; a.attn = a.qkv + T * 3 * D.inner; a.xm = a.attn + T * D.inner; a.ff = a.xm + T * D.dm;
-  return a;
-}
-DecAct dec_act(const TrainWs& w, const Dims& D, int i) {
-  float* b = P<float>(w.dec_act) + (size_t)i * D.dec_stride;
-  const size_t R = D.R;
-  DecAct a; a.x0 = b; a.qkv = a.x0 + R * D.dm; a.a0 = a.qkv + R * 3 * D.inner; a.x1 = a.a0 + R * D.inner; a.qx = a.x1 + R * D.dm;
-  a.a1 = a.qx + R * D.inner; a.x2 = a.a1 + R * D.inner; a.ff = a.x2 + R * D.dm;
-  return a;
-}
-
 // gold: end with the gold-code scores of the ranking step (w.scores); else the decoder stream is left in w.x_last for the
 // seq2seq head
-void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const int32_t* ids, const int32_t* mask,
+void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, const int32_t* ids, const int32_t* mask,
              const int32_t* codes, int32_t* last, bool gold = true) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
-  const int T = D.T, R = D.R, dm = D.dm, inner = D.inner, dff = D.dff;
+  const int T = D.T, R = D.R, dm = D.dm, inner = D.inner;
   float* h = P<float>(w.h);
   auto norm = [&](const float* x, const float* ln, float* out, int rows, float post = 1.0f) {
     Ln.run(RPR_K_RMSNORM, 0, 8.0 * rows * dm, [&] { return launch_rmsnorm(x, ln, out, rows, dm, D.eps, s, post); });
   };
-  const XtSlots xt{c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr, XtLayout(D)};
   // out = act(norm(x) W^T): in bf16 mode the norm writes the product's bf16 operand and its transposed copy itself
   // (rmsnorm_bf16_T_kernel); otherwise norm into h, then gemm() converts.
   // next_xt: where the NEXT product (the one that reads C) wants C's transposed bf16 copy; when the shapes allow it (fused_ok)
@@ -660,43 +595,50 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const 
     gemm(Ln, h, dm, W, dm, C, N, rows, N, dm, nullptr, relu, save_xt);
     return nullptr;
   };
+  // y = x + mid(norm(x, ln) W_in^T) W_out^T, everything the backward needs kept. Only the middle op differs by kind; the FF
+  // block hands its inner product's bf16 operands to the outer one (next_xt / a_ready)
+  auto sub_fwd = [&](const Stack& k, int i, int j) {
+    const SubBlock& b = k.lay.sub[j];
+    const ParamSlot* p = k.params(i, j);
+    const int rows = k.lay.rows;
+    const bool ff = b.kind == SUB_FF;
+    float *x = k.x(i, j), *in = k.in(i, j), *mid = k.mid(i, j);
+    const void* ready = norm_gemm(x, p[P_LN].ptr, p[P_WIN].ptr, in, rows, b.n_in, ff, k.xt_in(i, j), ff ? k.xt_out(i, j) : nullptr);
+    switch (b.kind) {
+      case SUB_SELF: {
+        EncAttnArgs sa{in, k.mask, k.rel_bias, k.bucket, mid, k.nseq, k.len, D.H, d.rel_buckets, nullptr, 0, nullptr, nullptr, nullptr,
+                       k.causal, 1};
+        Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] { return launch_enc_attn(sa, s); });
+        break;
+      }
+      case SUB_CROSS: {
+        const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
+        DecCrossAttnArgs ca{in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr};
+        // (the query's docs L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64)
+        Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] { return launch_tail_cross_attn(ca, s); });
+        break;
+      }
+      case SUB_FF: break;   // the ReLU ran in the inner product's epilogue
+    }
+    gemm(Ln, mid, b.k_out, p[P_WOUT].ptr, b.k_out, k.x(i, j + 1), dm, rows, dm, b.k_out, x, 0, k.xt_out(i, j), ready);
+  };
+  auto stack_fwd = [&](const Stack& k) {
+    for (int i = 0; i < k.lay.layers; ++i)
+      for (int j = 0; j < k.lay.nsub; ++j) sub_fwd(k, i, j);
+  };
+  const TrainLayout Y(D);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_mask_lengths(mask, last, D.bz, D.Lq, s, c->status + 1); });
   // ---- encoder over the padded [bz, Lq] layout (padded positions get no gradient: nothing downstream reads them)
-  float* xe_last = P<float>(w.enc_act) + (size_t)D.ne * D.enc_stride;
-  Ln.run(RPR_K_OTHER, 0, 8.0 * T * dm, [&] { return launch_embed_rows(d.shared, ids, enc_act(w, D, 0).x, T, dm, d.vocab_size, s); });
-  for (int i = 0; i < D.ne; ++i) {
-    EncAct a = enc_act(w, D, i);
-    float* xnext = i + 1 < D.ne ? enc_act(w, D, i + 1).x : xe_last;
-    norm_gemm(a.x, m->enc_ln0[i], m->enc_qkv[i], a.qkv, T, 3 * inner, 0, xt.enc(i, XT_QKV));
-    EncAttnArgs ea{a.qkv, mask, d.enc_rel_bias, m->enc_bucket, a.attn, D.bz, D.Lq, D.H, d.rel_buckets, nullptr, 0, nullptr, nullptr,
-                   nullptr, 0, 1};
-    Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] { return launch_enc_attn(ea, s); });
-    gemm(Ln, a.attn, inner, m->enc_o[i], inner, a.xm, dm, T, dm, inner, a.x, 0, xt.enc(i, XT_O));
-    const void* ffb = norm_gemm(a.xm, m->enc_ln1[i], m->enc_wi[i], a.ff, T, dff, 1, xt.enc(i, XT_WI), xt.enc(i, XT_WO));
-    gemm(Ln, a.ff, dff, m->enc_wo[i], dff, xnext, dm, T, dm, dff, a.xm, 0, xt.enc(i, XT_WO), ffb);
-  }
-  norm(xe_last, d.enc_final_ln, P<float>(w.enc_out), T);
-  gemm(Ln, P<float>(w.enc_out), dm, d.dec_xkv, dm, P<float>(w.xkv), D.xld, T, D.xld, dm, nullptr, 0, xt.xkv());
+  const Stack enc = enc_stack(c, m, D, Y, mask);
+  Ln.run(RPR_K_OTHER, 0, 8.0 * T * dm, [&] { return launch_embed_rows(d.shared, ids, enc.x(0, 0), T, dm, d.vocab_size, s); });
+  stack_fwd(enc);
+  norm(enc.x_end, d.enc_final_ln, P<float>(w.enc_out), T);
+  gemm(Ln, P<float>(w.enc_out), dm, d.dec_xkv, dm, P<float>(w.xkv), D.xld, T, D.xld, dm, nullptr, 0, enc.xT ? enc.xT + Y.xt_xkv : nullptr);
   // ---- teacher-forced decoder over all positions of every smtid (ranking step: the positive and the negative)
+  const Stack dec = dec_stack(c, m, D, Y);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_train_indices(codes, P<int32_t>(w.in_idx), P<int32_t>(w.out_idx), D.S, D.L, D.V, s); });
-  Ln.run(RPR_K_OTHER, 0, 8.0 * R * dm, [&] { return launch_train_dec_embed(d.start_embed, d.in_embeds, codes, dec_act(w, D, 0).x0, D.S, D.L, dm, D.V, s); });
-  for (int i = 0; i < D.nd; ++i) {
-    DecAct a = dec_act(w, D, i);
-    float* xnext = i + 1 < D.nd ? dec_act(w, D, i + 1).x0 : P<float>(w.x_last);
-    norm_gemm(a.x0, m->dec_ln0[i], m->dec_qkv[i], a.qkv, R, 3 * inner, 0, xt.dec(i, XT_QKV));
-    EncAttnArgs sa{a.qkv, nullptr, d.dec_rel_bias, m->dec_bucket, a.a0, D.S, D.L, D.H, d.rel_buckets, nullptr, 0, nullptr, nullptr,
-                   nullptr, 1, 1};
-    Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] { return launch_enc_attn(sa, s); });
-    gemm(Ln, a.a0, inner, m->dec_o[i], inner, a.x1, dm, R, dm, inner, a.x0, 0, xt.dec(i, XT_O));
-    norm_gemm(a.x1, m->dec_ln1[i], m->dec_xq[i], a.qx, R, inner, 0, xt.dec(i, XT_XQ));
-    const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
-    DecCrossAttnArgs ca{a.qx, xk, xk + inner, D.xld, mask, a.a1, D.bz, D.docs * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr};
-    // (the query's docs L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64)
-    Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] { return launch_tail_cross_attn(ca, s); });
-    gemm(Ln, a.a1, inner, m->dec_xo[i], inner, a.x2, dm, R, dm, inner, a.x1, 0, xt.dec(i, XT_XO));
-    const void* ffb = norm_gemm(a.x2, m->dec_ln2[i], m->dec_wi[i], a.ff, R, dff, 1, xt.dec(i, XT_WI), xt.dec(i, XT_WO));
-    gemm(Ln, a.ff, dff, m->dec_wo[i], dff, xnext, dm, R, dm, dff, a.x2, 0, xt.dec(i, XT_WO), ffb);
-  }
+  Ln.run(RPR_K_OTHER, 0, 8.0 * R * dm, [&] { return launch_train_dec_embed(d.start_embed, d.in_embeds, codes, dec.x(0, 0), D.S, D.L, dm, D.V, s); });
+  stack_fwd(dec);
   if (!gold) return;
   Ln.run(RPR_K_OTHER, 0, 0, [&] {
     return launch_gold_scores(P<float>(w.x_last), d.dec_final_ln, d.out_embeds, codes, P<float>(w.scores), D.S, D.L, dm, D.V, D.eps,
@@ -706,7 +648,7 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const 
 
 // The seq2seq head after forward(gold = false): hF = the final RMSNorm of the decoder stream (times d^-0.5 under
 // scaleup_output_hidden), then logits, log-softmax, cross-entropy and dlogits (train_kernels.hip, exact fp32 in every mode)
-void s2s_head_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const Dims& D, const int32_t* labels, float* out_loss,
+void s2s_head_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, const int32_t* labels, float* out_loss,
                       float* out_label_lp) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
@@ -732,7 +674,7 @@ struct BucketHook {
 };
 
 // ce_head: the seq2seq cross-entropy head (s2s_head_forward ran) instead of the ranking step's gold scores
-void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32_t* ids, const int32_t* mask, float* G,
+void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const int32_t* ids, const int32_t* mask, float* G,
               BucketHook* hook = nullptr, bool ce_head = false) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
@@ -752,18 +694,14 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
     if (Ln.err) return;
     hook->cb(hook->user, (int64_t)off, (int64_t)numel);
   };
-  auto layer_numel = [&](int first_kind, int last_kind, int layer) {
-    size_t lo = param_offset(m, first_kind, layer), hi = param_offset(m, last_kind, layer);
-    for (const auto& p : m->params) if (p.kind == last_kind && p.layer == layer) hi += p.numel;
-    return std::make_pair(lo, hi - lo);
-  };
-  const int T = D.T, R = D.R, dm = D.dm, inner = D.inner, dff = D.dff, H = D.H;
+  const int T = D.T, R = D.R, dm = D.dm, inner = D.inner, H = D.H;
   w.side.reset();
   Bwd B{Ln, c, w, D};
-  const XtSlots xt{c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr, XtLayout(D)};
-  const bool saved = xt.base != nullptr;   // the normalised inputs are only recomputed for their weight-gradient products
+  const TrainLayout Y(D);
+  const Stack enc = enc_stack(c, m, D, Y, mask), dec = dec_stack(c, m, D, Y);
   const bool bf16 = c->precision == RPR_PREC_BF16;   // ReLU backward folded into the conversion of its result (dxdw)
-  auto g = [&](int kind, int layer = -1) { return G + param_offset(m, kind, layer); };
+  const bool saved = bf16;   // X^T kept by the forward: the normalised inputs are only recomputed for their weight-gradient products
+  auto g = [&](int kind, int layer = -1) { return G + m->params.at(kind, layer).offset; };
   float *dxa = P<float>(w.dxa), *dxb = P<float>(w.dxb), *dbig = P<float>(w.dbig), *dattn = P<float>(w.dattn), *h = P<float>(w.h);
   unsigned long long* fix = P<unsigned long long>(w.fix);
 
@@ -784,77 +722,65 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g_out, (size_t)d.L * D.V * dm, s); });
   }
   B.norm_bwd(P<float>(w.x_last), d.dec_final_ln, dxa, nullptr, dxb, g(K_DEC_FLN), R, D.post);
-  float *dx = dxb, *dx2 = dxa;   // dx = gradient w.r.t. the current layer's output stream
-  // ---- decoder layers, last to first
-  Ln.run(RPR_K_OTHER, 0, 0, [&] { return hipMemsetAsync(w.dxkv.p, 0, (size_t)T * D.xld * sizeof(float), s); });
-  for (int i = D.nd - 1; i >= 0; --i) {
-    DecAct a = dec_act(w, D, i);
-    // feed-forward: x3 = x2 + relu(norm(x2) Wi^T) Wo^T
-    B.dxdw(dx, m->dec_wo[i], a.ff, dbig, g(K_DEC_WO, i), R, dm, dff, xt.dec(i, XT_WO), nullptr, bf16 ? a.ff : nullptr);
-    if (!bf16) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_relu_bwd(dbig, a.ff, (size_t)R * dff, s); });
-    if (!saved) B.norm(a.x2, m->dec_ln2[i], R);
-    B.dxdw(dbig, m->dec_wi[i], h, h, g(K_DEC_WI, i), R, dff, dm, xt.dec(i, XT_WI), bf16 ? a.ff : nullptr);     // dh into the (now free) h buffer
-    B.norm_bwd(a.x2, m->dec_ln2[i], h, dx, dx2, g(K_DEC_LN2, i), R);
-    std::swap(dx, dx2);                                            // dx = gradient w.r.t. x2
-    // cross-attention: x2 = x1 + CrossAttn(norm(x1) Wq^T, Kx, Vx) Wo^T
-    B.dxdw(dx, m->dec_xo[i], a.a1, dattn, g(K_DEC_XO, i), R, dm, inner, xt.dec(i, XT_XO));
-    {
-      const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
-      float* dxk = P<float>(w.dxkv) + (size_t)i * 2 * inner;
-      Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {   // dq into dbig (as [R, inner])
-        return launch_cross_attn_bwd(a.qx, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, D.docs * D.L, D.Lq, H, s);
-      });
+  float *dx = dxb, *dx2 = dxa;   // dx = gradient w.r.t. the current sub-block's output stream, dx2 the buffer its input's goes to
+  // y = x + mid(norm(x, ln) W_in^T) W_out^T backwards: dxdw of W_out -> the middle op's backward, into dbig -> (the norm again
+  // when nothing was saved) -> dxdw of W_in into h (free by now) -> norm_bwd adds the residual path: dx2 = gradient w.r.t. x
+  auto sub_bwd = [&](const Stack& k, int i, int j) {
+    const SubBlock& b = k.lay.sub[j];
+    const ParamSlot* p = k.params(i, j);
+    const int rows = k.lay.rows;
+    float *x = k.x(i, j), *in = k.in(i, j);
+    const float* relu = b.kind == SUB_FF && bf16 ? in : nullptr;   // FF: in = relu(norm(x) Wi^T), the mask of its own gradient
+    float* dmid = b.kind == SUB_FF ? dbig : dattn;
+    B.dxdw(dx, p[P_WOUT].ptr, k.mid(i, j), dmid, G + p[P_WOUT].offset, rows, dm, b.k_out, k.xt_out(i, j), nullptr, relu);
+    switch (b.kind) {
+      case SUB_FF:
+        if (!bf16) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_relu_bwd(dbig, in, (size_t)rows * b.n_in, s); });
+        break;
+      case SUB_CROSS: {
+        const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
+        float* dxk = P<float>(w.dxkv) + (size_t)i * 2 * inner;
+        Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {   // dq into dbig (as [R, inner])
+          return launch_cross_attn_bwd(in, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, D.docs * D.L, D.Lq, H, s);
+        });
+        break;
+      }
+      case SUB_SELF:
+        Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
+          return launch_self_attn_bwd(in, dattn, k.mask, k.rel_bias, k.bucket, dbig, P<float>(w.bias_part),
+                                      g(k.lay.dec ? K_DEC_REL : K_ENC_REL), k.nseq, k.len, H, d.rel_buckets, k.causal, s);
+        });
+        break;
     }
-    if (!saved) B.norm(a.x1, m->dec_ln1[i], R);
-    B.dxdw(dbig, m->dec_xq[i], h, h, g(K_DEC_XQ, i), R, inner, dm, xt.dec(i, XT_XQ));
-    B.norm_bwd(a.x1, m->dec_ln1[i], h, dx, dx2, g(K_DEC_LN1, i), R);
-    std::swap(dx, dx2);                                            // dx = gradient w.r.t. x1
-    // self-attention: x1 = x0 + SelfAttn(norm(x0) Wqkv^T) Wo^T
-    B.dxdw(dx, m->dec_o[i], a.a0, dattn, g(K_DEC_O, i), R, dm, inner, xt.dec(i, XT_O));
-    Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
-      return launch_self_attn_bwd(a.qkv, dattn, nullptr, d.dec_rel_bias, m->dec_bucket, dbig, P<float>(w.bias_part), g(K_DEC_REL), D.S,
-                                  D.L, H, d.rel_buckets, 1, s);
-    });
-    if (!saved) B.norm(a.x0, m->dec_ln0[i], R);
-    B.dxdw(dbig, m->dec_qkv[i], h, h, g(K_DEC_QKV, i), R, 3 * inner, dm, xt.dec(i, XT_QKV));
-    B.norm_bwd(a.x0, m->dec_ln0[i], h, dx, dx2, g(K_DEC_LN0, i), R);
-    std::swap(dx, dx2);                                            // dx = gradient w.r.t. x0 = the previous layer's output
-    w.side.flush(Ln);                                               // the layer's six weight gradients: one launch on the side stream
-    B.flush_norms();                                               // ... and its three layer-norm weight gradients
-    { const auto b = layer_numel(K_DEC_LN0, K_DEC_WO, i); bucket(b.first, b.second); }
-  }
+    if (!saved) B.norm(x, p[P_LN].ptr, rows);
+    B.dxdw(dbig, p[P_WIN].ptr, h, h, G + p[P_WIN].offset, rows, b.n_in, dm, k.xt_in(i, j), relu);
+    B.norm_bwd(x, p[P_LN].ptr, h, dx, dx2, G + p[P_LN].offset, rows);
+    std::swap(dx, dx2);
+  };
+  auto stack_bwd = [&](const Stack& k) {   // layers last to first
+    for (int i = k.lay.layers - 1; i >= 0; --i) {
+      for (int j = k.lay.nsub - 1; j >= 0; --j) sub_bwd(k, i, j);
+      w.side.flush(Ln);                                               // the layer's weight gradients: one launch on the side stream
+      B.flush_norms();                                               // ... and its layer-norm weight gradients
+      size_t off, numel;
+      m->params.bucket(k.lay, i, &off, &numel);
+      bucket(off, numel);
+    }
+  };
+  // ---- decoder
+  Ln.run(RPR_K_OTHER, 0, 0, [&] { return hipMemsetAsync(w.dxkv.p, 0, (size_t)T * D.xld * sizeof(float), s); });
+  stack_bwd(dec);
   // decoder input embeddings: codebook rows and the start embedding
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dx, P<int32_t>(w.in_idx), fix, R, dm, s); });
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g(K_IN_EMB), (size_t)d.L * D.V * dm, s); });
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_sum_selected_rows(dx, P<int32_t>(w.in_idx), g(K_START), R, dm, s); });
   // ---- cross K/V projection and the encoder's final norm
   float* denc = P<float>(w.denc);
-  B.dxdw(P<float>(w.dxkv), d.dec_xkv, P<float>(w.enc_out), denc, g(K_XKV), T, D.xld, dm, xt.xkv());
+  B.dxdw(P<float>(w.dxkv), d.dec_xkv, P<float>(w.enc_out), denc, g(K_XKV), T, D.xld, dm, enc.xT ? enc.xT + Y.xt_xkv : nullptr);
   w.side.flush(Ln);
-  float* xe_last = P<float>(w.enc_act) + (size_t)D.ne * D.enc_stride;
-  B.norm_bwd(xe_last, d.enc_final_ln, denc, nullptr, dxa, g(K_ENC_FLN), T);
-  dx = dxa; dx2 = dxb;
-  for (int i = D.ne - 1; i >= 0; --i) {
-    EncAct a = enc_act(w, D, i);
-    B.dxdw(dx, m->enc_wo[i], a.ff, dbig, g(K_ENC_WO, i), T, dm, dff, xt.enc(i, XT_WO), nullptr, bf16 ? a.ff : nullptr);
-    if (!bf16) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_relu_bwd(dbig, a.ff, (size_t)T * dff, s); });
-    if (!saved) B.norm(a.xm, m->enc_ln1[i], T);
-    B.dxdw(dbig, m->enc_wi[i], h, h, g(K_ENC_WI, i), T, dff, dm, xt.enc(i, XT_WI), bf16 ? a.ff : nullptr);
-    B.norm_bwd(a.xm, m->enc_ln1[i], h, dx, dx2, g(K_ENC_LN1, i), T);
-    std::swap(dx, dx2);
-    B.dxdw(dx, m->enc_o[i], a.attn, dattn, g(K_ENC_O, i), T, dm, inner, xt.enc(i, XT_O));
-    Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
-      return launch_self_attn_bwd(a.qkv, dattn, mask, d.enc_rel_bias, m->enc_bucket, dbig, P<float>(w.bias_part), g(K_ENC_REL), D.bz,
-                                  D.Lq, H, d.rel_buckets, 0, s);
-    });
-    if (!saved) B.norm(a.x, m->enc_ln0[i], T);
-    B.dxdw(dbig, m->enc_qkv[i], h, h, g(K_ENC_QKV, i), T, 3 * inner, dm, xt.enc(i, XT_QKV));
-    B.norm_bwd(a.x, m->enc_ln0[i], h, dx, dx2, g(K_ENC_LN0, i), T);
-    std::swap(dx, dx2);
-    w.side.flush(Ln);
-    B.flush_norms();
-    { const auto b = layer_numel(K_ENC_LN0, K_ENC_WO, i); bucket(b.first, b.second); }
-  }
+  B.norm_bwd(enc.x_end, d.enc_final_ln, denc, nullptr, dxa, g(K_ENC_FLN), T);
+  dx = dxa; dx2 = dxb;   // the ping-pong starts again
+  stack_bwd(enc);
   // token embeddings (the encoder's table is the shared one)
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dx, ids, fix, T, dm, s); });
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g(K_SHARED), (size_t)d.vocab_size * dm, s); });
@@ -863,11 +789,11 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const Dims& D, const int32
   w.side.flush(Ln);
   B.flush_norms();                                                 // the encoder's final norm (the decoder's went with its last layer)
   w.side.wait_groups(Ln, s, true);
-  bucket(0, param_offset(m, K_ENC_LN0, 0));   // everything in front of the first layer: final only now
+  bucket(0, m->params.at(K_ENC_LAYER, 0).offset);   // everything in front of the first layer: final only now
 }
 
 // Checks and workspaces shared by the training passes: docs decoder sequences of L positions per query
-int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, Dims& D) {
+int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, TrainDims& D) {
   RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
   RPR_REQUIRE(bz >= 1 && Lq >= 1 && Lq <= 128, "bz or Lq out of range (the training kernels hold Lq <= 128 keys in LDS)");
   RPR_REQUIRE(m->d.d_kv == DKV, "the training kernels are written for d_kv == 64 (t5-base / t5-large)");
@@ -875,12 +801,7 @@ int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int
   RPR_HIP(hipSetDevice(c->device));
   build_params(m);
   const auto& d = m->d;
-  D.bz = bz; D.Lq = Lq; D.L = L; D.docs = docs; D.S = bz * docs; D.R = D.S * L; D.T = bz * Lq; D.dm = d.d_model; D.inner = m->inner();
-  D.dff = d.d_ff; D.H = d.num_heads; D.ne = d.num_layers; D.nd = d.num_decoder_layers; D.V = d.V; D.xld = D.nd * 2 * D.inner;
-  D.buckets = d.rel_buckets;
-  D.eps = d.layer_norm_eps; D.post = d.scaleup_output_hidden ? (float)pow((double)D.dm, -0.5) : 1.0f;
-  D.enc_stride = (size_t)D.T * (2 * D.dm + 4 * D.inner + D.dff);
-  D.dec_stride = (size_t)D.R * (3 * D.dm + 6 * D.inner + D.dff);
+  D = train_dims(d, bz, Lq, L, docs);
   RPR_REQUIRE(self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024,
               "sequence lengths too large for the LDS-resident attention backward");
   int e = alloc_train(c, m, D);
@@ -918,13 +839,13 @@ void rpr::free_train_ws(rpr_ctx* c) {
 
 extern "C" {
 
-int64_t rpr_param_count(rpr_model* m) { if (!m) return 0; build_params(m); return (int64_t)m->params.size(); }
-int64_t rpr_param_total(rpr_model* m) { if (!m) return 0; build_params(m); return (int64_t)m->params_total; }
+int64_t rpr_param_count(rpr_model* m) { if (!m) return 0; build_params(m); return (int64_t)m->params.slots.size(); }
+int64_t rpr_param_total(rpr_model* m) { if (!m) return 0; build_params(m); return (int64_t)m->params.total; }
 int rpr_param_info(rpr_model* m, int64_t index, const float** ptr, int64_t* numel, int64_t* offset) {
   RPR_REQUIRE(m, "NULL model");
   build_params(m);
-  RPR_REQUIRE(index >= 0 && index < (int64_t)m->params.size(), "parameter index out of range");
-  const auto& p = m->params[(size_t)index];
+  RPR_REQUIRE(index >= 0 && index < (int64_t)m->params.slots.size(), "parameter index out of range");
+  const auto& p = m->params.slots[(size_t)index];
   if (ptr) *ptr = p.ptr;
   if (numel) *numel = (int64_t)p.numel;
   if (offset) *offset = (int64_t)p.offset;
@@ -945,12 +866,12 @@ int rpr_lngknp_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_i
   RPR_REQUIRE(c && m && input_ids && attention_mask && doc_codes && teacher_pos && teacher_neg && prefix_lens && out_losses &&
                   flat_grads, "NULL argument");
   RPR_REQUIRE(n_prefix >= 1 && n_prefix <= 8, "n_prefix out of range (1..8)");
-  Dims D{};
+  TrainDims D{};
   int e = train_setup(c, m, bz, Lq, L, 2, D);
   if (e) return e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   TrainWs& w = *c->tws;
-  RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params_total * sizeof(float), s));
+  RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params.total * sizeof(float), s));
   Launcher Ln{c, s};
   e = train_begin(Ln, c, m);
   if (e) return e;
@@ -973,7 +894,7 @@ static int seq2seq_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const
   RPR_REQUIRE(c && m && input_ids && attention_mask && labels && out_loss, "NULL argument");
   RPR_REQUIRE(s2s_head_smem_ok(m->d.V) && m->d.d_model % 32 == 0,
               "the cross-entropy head needs a codebook size V with V % 64 == 0 and V <= 1024, and d_model % 32 == 0");
-  Dims D{};
+  TrainDims D{};
   int e = train_setup(c, m, bz, Lq, L, 1, D);
   if (e) return e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -983,7 +904,7 @@ static int seq2seq_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const
     RPR_HIP(hipStreamSynchronize(s));
     for (int32_t v : h) RPR_REQUIRE(v >= 0 && v < m->d.V, "a label is outside [0, V) of the codebooks");
   }
-  if (flat_grads) RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params_total * sizeof(float), s));
+  if (flat_grads) RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params.total * sizeof(float), s));
   Launcher Ln{c, s};
   e = train_begin(Ln, c, m);
   if (e) return e;
@@ -1028,7 +949,7 @@ int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp
   int e = tensure(c, w.gn_part, 1024 * 8);
   if (!e) e = tensure(c, w.gn_out, 16);
   if (e) return e;
-  RPR_HIP(launch_grad_norm(flat_grads, m->params_total, P<double>(w.gn_part), 1024, max_grad_norm, P<float>(w.gn_out), s));
+  RPR_HIP(launch_grad_norm(flat_grads, m->params.total, P<double>(w.gn_part), 1024, max_grad_norm, P<float>(w.gn_out), s));
   const float bc1 = 1.0f - (float)pow((double)beta1, (double)step);
   const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   // Weight decay follows HF 4.17's Trainer.create_optimizer (what the reference trains with, tasks/trainer.py:477):
@@ -1040,7 +961,7 @@ int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp
     std::vector<AdamSeg> segs;
     std::vector<int> pref;
     int chunks = 0;
-    for (const auto& p : m->params) {
+    for (const auto& p : m->params.slots) {
       if (!p.numel) continue;
       segs.push_back(AdamSeg{p.ptr, (unsigned long long)p.offset, (unsigned long long)p.numel,
                              (p.kind == K_ENC_REL || p.kind == K_DEC_REL) ? 0 : 1});

@@ -80,11 +80,11 @@ class Job:
 
     def step(self):
         losses = E.train_step(self.model, self.state, self.ids, self.mask, self.codes, self.tp, self.tn, self.prefix, lr=1e-4)
-        params = {}
+        params = {}   # every packed tensor once, in the order the model lists them (not by address: that moves from run to run)
         for _, t, _ in self.model.named_device_params():
-            params[t.data_ptr()] = t
+            params.setdefault(t.data_ptr(), t)
         return dict(losses=losses, grads=self.state.grads, exp_avg=self.state.exp_avg, exp_avg_sq=self.state.exp_avg_sq,
-                    grad_norm=self.state.grad_norm, params=torch.cat([params[k].reshape(-1).float() for k in sorted(params)]))
+                    grad_norm=self.state.grad_norm, params=torch.cat([t.reshape(-1).float() for t in params.values()]))
 
     @staticmethod
     def _done(outs, ex):
