@@ -226,27 +226,10 @@ int rpr_load_model(rpr_ctx* c, const rpr_model_desc* d, rpr_model** out) {
   RPR_REQUIRE(d->shared && d->enc_rel_bias && d->dec_rel_bias && d->enc_final_ln && d->dec_final_ln &&
                   d->start_embed && d->in_embeds && d->out_embeds && d->dec_xkv, "NULL weight pointer");
   RPR_HIP(hipSetDevice(c->device));
-  auto m = std::make_unique<rpr_model>();
-  m->ctx = c;
-  m->d = *d;
-  auto copyv = [](std::vector<const float*>& v, const float* const* src, int n) -> bool {
-    if (!src) return false;
-    v.assign(src, src + n);
-    for (auto p : v) if (!p) return false;
-    return true;
-  };
-  bool ok = copyv(m->enc_ln0, d->enc_ln0, d->num_layers) && copyv(m->enc_qkv, d->enc_qkv, d->num_layers) &&
-            copyv(m->enc_o, d->enc_o, d->num_layers) && copyv(m->enc_ln1, d->enc_ln1, d->num_layers) &&
-            copyv(m->enc_wi, d->enc_wi, d->num_layers) && copyv(m->enc_wo, d->enc_wo, d->num_layers);
-  const int nd = d->num_decoder_layers;
-  ok = ok && copyv(m->dec_ln0, d->dec_ln0, nd) && copyv(m->dec_qkv, d->dec_qkv, nd) && copyv(m->dec_o, d->dec_o, nd) &&
-       copyv(m->dec_ln1, d->dec_ln1, nd) && copyv(m->dec_xq, d->dec_xq, nd) && copyv(m->dec_xo, d->dec_xo, nd) &&
-       copyv(m->dec_ln2, d->dec_ln2, nd) && copyv(m->dec_wi, d->dec_wi, nd) && copyv(m->dec_wo, d->dec_wo, nd);
-  RPR_REQUIRE(ok, "NULL per-layer weight pointer");
+  auto m = std::make_unique<rpr_model>(c, *d);
+  RPR_REQUIRE(m->params.fill(*d), "NULL per-layer weight pointer");
   // the desc's host arrays need not outlive this call
-  m->d.enc_ln0 = m->d.enc_qkv = m->d.enc_o = m->d.enc_ln1 = m->d.enc_wi = m->d.enc_wo = nullptr;
-  m->d.dec_ln0 = m->d.dec_qkv = m->d.dec_o = m->d.dec_ln1 = m->d.dec_xq = m->d.dec_xo = nullptr;
-  m->d.dec_ln2 = m->d.dec_wi = m->d.dec_wo = nullptr;
+  for (int kind = K_ENC_LAYER; kind < K_END; ++kind) m->d.*layer_field(kind) = nullptr;
   std::vector<int32_t> eb(2 * MAX_LQ - 1), db(MAX_DEC_LEN);
   for (int rel = -(MAX_LQ - 1); rel <= MAX_LQ - 1; ++rel)
     eb[rel + MAX_LQ - 1] = rel_bucket(rel, 1, d->rel_buckets, d->rel_max_distance);
@@ -257,7 +240,7 @@ int rpr_load_model(rpr_ctx* c, const rpr_model_desc* d, rpr_model** out) {
   RPR_HIP(hipMemcpy(m->dec_bucket, db.data(), db.size() * 4, hipMemcpyHostToDevice));
   // hi/lo f16 planes of every GEMM weight for the split-precision kernels
   {
-    const size_t inner = (size_t)m->inner(), dm = d->d_model, dff = d->d_ff;
+    const size_t dm = d->d_model;
     int err = 0;
     unsigned int* probe = c->status + 8;   // weight-range probe word, apart from the sticky flags (refresh_weight_planes)
     RPR_HIP(hipMemset(probe, 0, 4));
@@ -275,17 +258,16 @@ int rpr_load_model(rpr_ctx* c, const rpr_model_desc* d, rpr_model** out) {
       if (e != hipSuccess) { err = hip_fail(e, "weight split", __FILE__, __LINE__); return; }
       *outp = (__half*)p;
     };
-    auto mkv = [&](const std::vector<const float*>& src, size_t n, std::vector<__half*>& dst,
-                   const std::vector<const float*>* ln = nullptr) {
-      dst.assign(src.size(), nullptr);
-      for (size_t i = 0; i < src.size(); ++i) mk(src[i], n, &dst[i], ln ? (*ln)[i] : nullptr);
-    };
-    mkv(m->enc_qkv, 3 * inner * dm, m->h_enc_qkv, &m->enc_ln0); mkv(m->enc_o, dm * inner, m->h_enc_o);
-    mkv(m->enc_wi, dff * dm, m->h_enc_wi, &m->enc_ln1); mkv(m->enc_wo, dm * dff, m->h_enc_wo);
-    mkv(m->dec_qkv, 3 * inner * dm, m->h_dec_qkv, &m->dec_ln0); mkv(m->dec_o, dm * inner, m->h_dec_o);
-    mkv(m->dec_xq, inner * dm, m->h_dec_xq, &m->dec_ln1); mkv(m->dec_xo, dm * inner, m->h_dec_xo);
-    mkv(m->dec_wi, dff * dm, m->h_dec_wi, &m->dec_ln2); mkv(m->dec_wo, dm * dff, m->h_dec_wo);
-    mk(d->dec_xkv, (size_t)nd * 2 * inner * dm, &m->h_dec_xkv);
+    // W_in and W_out of every sub-block of every layer: W_in carries the ln of its own sub-block (ParamOrder::weight)
+    const auto& slots = m->params.slots;
+    for (int dec = 0; dec < 2; ++dec)
+      for (int i = 0; i < m->params.stack[dec].layers; ++i)
+        for (int j = 0; j < m->params.stack[dec].nsub; ++j)
+          for (int role = P_WIN; role <= P_WOUT; ++role) {
+            const WeightRef r = m->params.weight(dec, i, j, role);
+            mk(slots[r.slot].ptr, slots[r.slot].numel, &m->planes[r.slot], r.fold < 0 ? nullptr : slots[r.fold].ptr);
+          }
+    mk(d->dec_xkv, m->params.at(K_XKV).numel, &m->h_dec_xkv);
     if (!err) {   // the output codebooks, each padded to Vp rows (zero rows: their logits are 0 and never selectable)
       const size_t Vp = (size_t)m->Vp(), ps = (size_t)d->L * Vp * dm, n = (size_t)d->V * dm;
       const float pre = d->scaleup_output_hidden ? (float)pow((double)dm, -0.5) : 1.0f;

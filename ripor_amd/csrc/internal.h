@@ -22,6 +22,21 @@ struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
 };
+// The operands of one linear layer C = act(A @ W^T) (+ residual) (linear(), below), each in both representations: the ctx
+// precision picks the exact fp32 MFMA kernel or the f16x2 split kernel. (Up here: a model hands out its weights as LinW.)
+struct LinIn {                                                               // activation [M, K]
+  const float* f; const __half* h; size_t ps; int ld; float scale = A_PLANE_SCALE;   //   fp32 / planes (+ their scale)
+  const unsigned long long* ssq = nullptr; float inv_d_fix = 0.f, eps = 0.f;         //   fused RMSNorm: h = planes of x, W folded
+};
+struct LinW {                                                                // weight [N, K] (+ planes)
+  const float* f; const __half* h; int N, K;                                 //   N: fp32 rows = columns the profile accounts
+  size_t ps = 0;                                                             //   plane stride (0 = N * K)
+  int Nh = 0;                                                                //   rows of a plane padded beyond N (0 = N): what the split kernel computes
+  bool no_scratch = false;                                                   //   the ctx's split-K scratch is not lent to this product: the mid-size
+                                                                             //   split-K route (gemm_route.h: part, mid_split) stays closed to it
+  bool row_split_ok = false;                                                 //   the launcher's no_row_split does not reach this product
+  bool force_pp = false;                                                     //   the 256x256 ping-pong kernel whatever the shape (GemmH2Args::force_pp)
+};
 
 }  // namespace rpr
 
@@ -29,19 +44,34 @@ using rpr::DevBuf;
 
 struct rpr_model {
   rpr_ctx* ctx;
-  rpr_model_desc d;
-  std::vector<const float*> enc_ln0, enc_qkv, enc_o, enc_ln1, enc_wi, enc_wo;
-  std::vector<const float*> dec_ln0, dec_qkv, dec_o, dec_ln1, dec_xq, dec_xo, dec_ln2, dec_wi, dec_wo;
+  rpr_model_desc d;   // (its per-layer host arrays are null: the tensors of a layer are reached through params)
+  // Every trainable tensor, in the order of the flat gradient / optimizer-state buffers, filled at load (train_layout.h), and,
+  // indexed like params.slots, the f16 hi/lo planes of every per-layer GEMM weight (split once at load; [2][N][K], plane
+  // stride N*K; null for a norm weight and for the tensors in front of the layers)
+  rpr::ParamOrder params;
+  std::vector<__half*> planes;
+  // The weights of sub-block j of layer i of a stack as the passes use them: the norm weight, W_in [n_in, d_model] and
+  // W_out [d_model, k_out] with their planes; the cross-K/V weight of all decoder layers; the output codebook of position t
+  const float* ln(bool dec, int i, int j) const { return params.sub(params.stack[dec], i, j)->ptr; }
+  rpr::LinW weight(bool dec, int i, int j, int role) const {   // role: rpr::P_WIN, P_WOUT
+    const rpr::WeightRef r = params.weight(dec, i, j, role);
+    return {params.slots[r.slot].ptr, planes[r.slot], r.N, r.K};
+  }
+  rpr::LinW w_xkv() const { return {d.dec_xkv, h_dec_xkv, d.num_decoder_layers * 2 * inner(), d.d_model}; }
+  // codebook t: V fp32 rows; its planes (times the final layer-norm weight and the scaleup factor) are Vp rows inside the
+  // stacked [2][L*Vp][d] buffer
+  rpr::LinW w_codebook(int t) const {
+    rpr::LinW w{d.out_embeds + (size_t)t * d.V * d.d_model, h_out_embeds + (size_t)t * Vp() * d.d_model, d.V, d.d_model};
+    w.ps = (size_t)d.L * Vp() * d.d_model; w.Nh = Vp();
+    return w;
+  }
   int32_t* enc_bucket = nullptr;  // [2*MAX_LQ-1]
   int32_t* dec_bucket = nullptr;  // [MAX_DEC_LEN]
-  // f16 hi/lo planes of every GEMM weight (split once at load; [2][N][K], plane stride N*K)
-  std::vector<__half*> h_enc_qkv, h_enc_o, h_enc_wi, h_enc_wo;
-  std::vector<__half*> h_dec_qkv, h_dec_o, h_dec_xq, h_dec_xo, h_dec_wi, h_dec_wo;
   __half* h_dec_xkv = nullptr;
   __half* h_out_embeds = nullptr;  // [2][L*Vp][d]: every codebook padded to Vp = V rounded up to 64 rows (zero rows)
   int Vp() const { return (d.V + 63) & ~63; }   // width of the selection kernel's token axis and of a logits row
   // Fused RMSNorm: the planes of every projection that consumes a normalised input hold W * diag(ln_weight)
-  // (enc_qkv: ln0, enc_wi: ln1, dec_qkv: ln0, dec_xq: ln1, dec_wi: ln2, out_embeds: final ln * scaleup factor);
+  // (W_in of a sub-block: the sub-block's ln, ParamOrder::weight; out_embeds: final ln * scaleup factor);
   // the fp32 weights of the caller stay untouched and serve the exact-fp32 mode.
   bool f32_only = false;           // a weight does not fit the f16 planes: every search of this model runs exact fp32
   bool planes_dirty = false;       // the fp32 weights changed (rpr_adamw_step) since the planes were split
@@ -61,13 +91,12 @@ struct rpr_model {
   // how every plane buffer was produced (replayed by refresh_weight_planes after an optimizer step changed the weights)
   struct PlaneJob { const float* w; size_t n; __half* dst; const float* ln; float pre; size_t plane_stride; };   // plane_stride 0 = n
   std::vector<PlaneJob> plane_jobs;
-  // trainable tensors in the order of the flat gradient / optimizer-state buffers (train_api.hip)
-  rpr::ParamOrder params;
   // bound of |logit| for any decoder state: sqrt(d_model) * max row norm of the output codebooks times the final
   // layer-norm weight (Cauchy-Schwarz on the RMS-normalised hidden state), times the scaleup factor; computed at load.
   // The forced-tail fork uses it to prove that no masked (-1e9) candidate can overtake a valid one (passes.hip: enqueue_fork).
   float logit_bound = INFINITY;
   int inner() const { return d.num_heads * d.d_kv; }
+  rpr_model(rpr_ctx* c, const rpr_model_desc& desc) : ctx(c), d(desc), params(desc), planes(params.slots.size(), nullptr) {}
   ~rpr_model() {   // device memory goes with the object, also on the error paths of rpr_load_model
     if (enc_bucket) (void)hipFree(enc_bucket);
     if (dec_bucket) (void)hipFree(dec_bucket);
@@ -313,21 +342,7 @@ struct Launcher {
 };
 
 // ---- the forward passes (passes.hip) and the linear layer they are made of --------------------------------------------
-// One linear layer C = act(A @ W^T) (+ residual). A and W are given in both representations; the
-// ctx precision picks the exact fp32 MFMA kernel or the f16x2 split kernel.
-struct LinIn {                                                               // activation [M, K]
-  const float* f; const __half* h; size_t ps; int ld; float scale = A_PLANE_SCALE;   //   fp32 / planes (+ their scale)
-  const unsigned long long* ssq = nullptr; float inv_d_fix = 0.f, eps = 0.f;         //   fused RMSNorm: h = planes of x, W folded
-};
-struct LinW {                                                                // weight [N, K] (+ planes)
-  const float* f; const __half* h; int N, K;                                 //   N: fp32 rows = columns the profile accounts
-  size_t ps = 0;                                                             //   plane stride (0 = N * K)
-  int Nh = 0;                                                                //   rows of a plane padded beyond N (0 = N): what the split kernel computes
-  bool no_scratch = false;                                                   //   the ctx's split-K scratch is not lent to this product: the mid-size
-                                                                             //   split-K route (gemm_route.h: part, mid_split) stays closed to it
-  bool row_split_ok = false;                                                 //   the launcher's no_row_split does not reach this product
-  bool force_pp = false;                                                     //   the 256x256 ping-pong kernel whatever the shape (GemmH2Args::force_pp)
-};
+// (LinIn and LinW: at the top)
 struct LinOut {                                                              // destination
   float* f[3]; int ldo[3]; int split_n;                                      //   fp32 (up to 3 column blocks)
   __half* h; size_t ps; int ldh;                                             //   or f16 planes (next GEMM's input)

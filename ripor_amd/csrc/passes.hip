@@ -161,7 +161,8 @@ struct PassBufs { const DevBuf &x, &h, &attn, &ff, &x_h, &attn_h, &ff_h, &ssq; }
 // buffers and keeps what is its own: the embedding, the Q/K/V destination, the attention launches, the head.
 struct Pass {
   Launcher& Ln;
-  const bool h2;                                 // split-precision mode (fused norms); false: exact fp32
+  const rpr_model* const m; const bool dec;      // the model and the stack whose sub-blocks' weights the layers read (internal.h)
+  const bool h2;                                // split-precision mode (fused norms); false: exact fp32
   const int spl, layers, dm, inner, dff;
   int M; const int* const m_dev; int m_acc;      // rows of the launches that follow (rows()), their device-side live count (nullable),
                                                  //   the rows their profile records account
@@ -172,9 +173,9 @@ struct Pass {
   const XStream xs;
   const float post;                              // scaleup_output_hidden: factor on the final norm of the decoder
 
-  Pass(Launcher& Ln_, const rpr_model* m, const PassBufs& b, int spl_, int layers_, int rows_cap, const int* m_dev_, int m_acc_)
-      : Ln(Ln_), h2(Ln_.c->precision == RPR_PREC_F16X2), spl(spl_), layers(layers_), dm(m->d.d_model), inner(m->inner()),
-        dff(m->d.d_ff), M(rows_cap), m_dev(m_dev_), m_acc(m_acc_), norm_acc(m_acc_), x(P<float>(b.x)), h(P<float>(b.h)),
+  Pass(Launcher& Ln_, const rpr_model* m_, const PassBufs& b, bool dec_, int layers_, int rows_cap, const int* m_dev_, int m_acc_)
+      : Ln(Ln_), m(m_), dec(dec_), h2(Ln_.c->precision == RPR_PREC_F16X2), spl(dec_ ? 3 : 2), layers(layers_), dm(m->d.d_model),
+        inner(m->inner()), dff(m->d.d_ff), M(rows_cap), m_dev(m_dev_), m_acc(m_acc_), norm_acc(m_acc_), x(P<float>(b.x)), h(P<float>(b.h)),
         attn(P<float>(b.attn)), ff(P<float>(b.ff)), attn_h(P<__half>(b.attn_h)), ff_h(P<__half>(b.ff_h)),
         ps_i((size_t)rows_cap * inner), ps_f((size_t)rows_cap * dff),
         xs{P<__half>(b.x_h), (size_t)rows_cap * dm, P<unsigned long long>(b.ssq), (size_t)rows_cap, dm, m->d.layer_norm_eps},
@@ -190,7 +191,8 @@ struct Pass {
   __half* attn_planes() const { return h2 ? attn_h : nullptr; }
   // input of the projection behind norm k of a layer: the x planes with the site's row sums (the norm weight is folded
   // into the projection's planes), or, exact fp32, the RMSNorm kernel's output
-  LinIn normed(int layer, int k, const float* ln, float post_scale = 1.0f) {
+  LinIn normed(int layer, int k) { return normed(layer, k, m->ln(dec, layer, k)); }
+  LinIn normed(int layer, int k, const float* ln, float post_scale = 1.0f) {   // (ln given: the final norm, layer = layers)
     if (h2) return xs.in(site(layer, k));
     Ln.run(RPR_K_RMSNORM, 0, 2.0 * norm_acc * dm * 4, [&] { return launch_rmsnorm(x, ln, h, M, dm, xs.eps, Ln.s, post_scale, nullptr, 0, m_dev); });
     return LinIn{h, nullptr, 0, dm};
@@ -198,22 +200,24 @@ struct Pass {
   // x += projection: destination of the residual projection behind norm k
   LinOut residual(int layer, int k) const { return h2 ? xs.out(site(layer, k) + 1) : out_f32(x, dm, dm, x); }
   void project(const LinIn& A, const LinW& W, const LinOut& O) { linear(Ln, A, W, M, O, m_dev, m_acc); }
+  // the inner projection of sub-block k: norm, then W_in (Q/K/V, the cross-attention query)
+  void project_in(int layer, int k, const LinOut& O) { project(normed(layer, k), m->weight(dec, layer, k, P_WIN), O); }
   // The model's layer-0 Q/K/V table stands in for this pass's layer-0 self-attention projection into O: split precision, the
   // table current (SearchPlan::l0), and the launch one the route planner sends whole to the ping-pong kernel — the kernel the table was made
   // by, whose K order does not depend on where a row sits, so the rows are the same bits (l0_mode 2: whatever the route).
-  bool l0_replaces(const rpr_model* m, const SearchPlan& plan, const LinOut& O) const {
+  bool l0_replaces(const SearchPlan& plan, const LinOut& O) const {
     if (!h2 || !plan.l0) return false;
     if (plan.l0 >= 2) return true;
-    return gemm_h2_pp_only(h2_args(Ln, xs.in(0), {m->dec_qkv[0], m->h_dec_qkv[0], 3 * inner, dm}, M, O, m_dev));
+    return gemm_h2_pp_only(h2_args(Ln, xs.in(0), m->weight(true, 0, 0, P_WIN), M, O, m_dev));
   }
-  void attn_out(int layer, int k, const float* W, const __half* Wh) {   // o / xo: the attention output back into the stream
-    project(LinIn{attn, attn_h, ps_i, inner}, {W, Wh, dm, inner}, residual(layer, k));
+  void attn_out(int layer, int k) {   // o / xo: the attention output back into the stream
+    project(LinIn{attn, attn_h, ps_i, inner}, m->weight(dec, layer, k, P_WOUT), residual(layer, k));
   }
-  void ff_block(int layer, int k, const float* ln, const float* wi, const __half* wi_h, const float* wo, const __half* wo_h) {
+  void ff_block(int layer, int k) {
     LinOut o = out_f32(ff, dff, dff, nullptr, 1);
     if (h2) { o.h = ff_h; o.ps = ps_f; o.ldh = dff; o.plane_scale = FF_PLANE_SCALE; }
-    project(normed(layer, k, ln), {wi, wi_h, dff, dm}, o);
-    project(LinIn{ff, ff_h, ps_f, dff, FF_PLANE_SCALE}, {wo, wo_h, dm, dff}, residual(layer, k));
+    project_in(layer, k, o);
+    project(LinIn{ff, ff_h, ps_f, dff, FF_PLANE_SCALE}, m->weight(dec, layer, k, P_WOUT), residual(layer, k));
   }
 };
 
@@ -246,11 +250,11 @@ int ensure_l0_table(rpr_ctx* c, rpr_model* m, hipStream_t s) {
   c->precision = RPR_PREC_F16X2; c->profiling = false;
   const DevBuf none{}, xb{x_h.p, rows * dm * 2 * sizeof(__half)}, sb{ssq.p, rows * 8};
   Launcher Ln{c, s};
-  Pass p(Ln, m, {none, none, none, none, xb, none, none, sb}, 3, 1, (int)rows, nullptr, (int)rows);
+  Pass p(Ln, m, {none, none, none, none, xb, none, none, sb}, true, 1, (int)rows, nullptr, (int)rows);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_l0_table_embed(d.start_embed, d.in_embeds, (int)rows, (int)dm, s, p.embed_out()); });
-  LinW w{m->dec_qkv[0], m->h_dec_qkv[0], 3 * m->inner(), (int)dm};
+  LinW w = m->weight(true, 0, 0, P_WIN);
   w.no_scratch = true; w.row_split_ok = true; w.force_pp = true;
-  p.project(p.normed(0, 0, m->dec_ln0[0]), w, out_f32(m->l0_table, 3 * m->inner(), 3 * m->inner()));
+  p.project(p.normed(0, 0), w, out_f32(m->l0_table, 3 * m->inner(), 3 * m->inner()));
   if (Ln.err) return Ln.err;
   RPR_HIP(hipStreamSynchronize(s));   // the scratch goes with this scope
   m->l0_valid = true; m->l0_epoch = c->l0_epoch; m->l0_state = 1;
@@ -276,21 +280,21 @@ void enqueue_encoder(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int Q, int Lq
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_pack_rows(P<int32_t>(w.last), P<int32_t>(w.offs), P<int32_t>(w.row_src), Q, Lq, s); });
   }
   Ln.account_live(live, T);   // profile pass: flops / bytes below are stated for T rows and scaled by the live count at flush
-  Pass p(Ln, m, {w.ex, w.eh, w.eattn, w.eff, w.ex_h, w.eattn_h, w.eff_h, w.ssq_e}, 2, d.num_layers, T, live, Ta);
+  Pass p(Ln, m, {w.ex, w.eh, w.eattn, w.eff, w.ex_h, w.eattn_h, w.eff_h, w.ssq_e}, false, d.num_layers, T, live, Ta);
   p.zero_ssq();
   Ln.run(RPR_K_OTHER, 0, 2.0 * Ta * dm * 4, [&] {
     return launch_embed_rows(d.shared, P<int32_t>(w.ids), p.x, T, dm, d.vocab_size, s,
                              packed ? P<int32_t>(w.row_src) : nullptr, live, p.embed_out());
   });
   for (int i = 0; i < d.num_layers; ++i) {
-    p.project(p.normed(i, 0, m->enc_ln0[i]), {m->enc_qkv[i], m->h_enc_qkv[i], 3 * inner, dm}, out_f32(qkv, 3 * inner, 3 * inner));
+    p.project_in(i, 0, out_f32(qkv, 3 * inner, 3 * inner));
     EncAttnArgs a{qkv, P<int32_t>(w.mask), d.enc_rel_bias, m->enc_bucket, p.attn, Q, Lq, d.num_heads, d.rel_buckets,
                   p.attn_planes(), p.ps_i, offs, P<int32_t>(w.last), c->status, 0};
     a.dkv = d.d_kv;
     Ln.run(RPR_K_ENC_ATTN, 4.0 * Q * d.num_heads * (double)Lq * Lq * d.d_kv * ((double)Ta / T) * ((double)Ta / T), 4.0 * Ta * 4 * inner,
            [&] { return launch_enc_attn(a, s); });
-    p.attn_out(i, 0, m->enc_o[i], m->h_enc_o[i]);
-    p.ff_block(i, 1, m->enc_ln1[i], m->enc_wi[i], m->h_enc_wi[i], m->enc_wo[i], m->h_enc_wo[i]);
+    p.attn_out(i, 0);
+    p.ff_block(i, 1);
   }
   // final norm: fp32 copy always (taps / rpr_encode), planes for the cross-K/V GEMM in split mode
   Ln.run(RPR_K_RMSNORM, 0, 2.0 * Ta * dm * 4, [&] {
@@ -349,7 +353,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
   const size_t layer_stride = sv.kv_layer(B, inner), kv_q = sv.kv_q(B, inner), kv_h = sv.kv_h(B), kv_pos = (size_t)B * sv.dkv, kv_slot = sv.dkv;
   int Rt = R, Bt = B;   // rows / beams per query of the current step's decoder pass
   const int Racc = live_count(Ln, sv.nrows_dev, R);   // rows the profile accounts for
-  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, 3, nd, R, sv.nrows_dev, Racc);
+  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, true, nd, R, sv.nrows_dev, Racc);
   if (Vp != V && !p.h2)   // exact-fp32 logits GEMM writes the V real columns of a row only: the padding must read as finite
     // (a kernel node: memset nodes captured into the search graph did not re-execute reliably on replay, see launch_zero_u64)
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_zero_u64(reinterpret_cast<unsigned long long*>(logits), (size_t)R * Vp / 2, s); });
@@ -370,13 +374,13 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
         o.f[0] = qb; o.f[1] = kc + (size_t)t * kv_pos; o.f[2] = vc + (size_t)t * kv_pos;
         o.ldo[0] = o.ldo[1] = o.ldo[2] = inner; o.split_n = inner;
         o.rm_B = Bt; o.rm_stride = kv_q; o.rm_slot = kv_slot; o.rm_head = kv_h; o.rm_dshift = sv.dkv == 128 ? 7 : 6;
-        if (i == 0 && p.l0_replaces(m, plan, o))   // the row's q | k | v from the model's table, landing where the epilogue puts them
+        if (i == 0 && p.l0_replaces(plan, o))   // the row's q | k | v from the model's table, landing where the epilogue puts them
           Ln.run(RPR_K_OTHER, 0, 2.0 * Ma * 3 * inner * 4, [&] {
             return launch_dec_l0_qkv(m->l0_table, cur.tokens, L, Rt, V, d.L * V, t, inner, o.f[0], o.f[1], o.f[2], o.rm_B, o.rm_stride,
                                      o.rm_slot, o.rm_head, o.rm_dshift, sv.nrows_dev, s);
           });
         else
-          p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, o);
+          p.project_in(i, 0, o);
       }
       {
         DecSelfAttnArgs a{qb, kc, vc, kv_q, kv_h, kv_pos, kv_slot, cur.anc, L, d.dec_rel_bias, m->dec_bucket, p.attn, Q, Bt, H, t,
@@ -385,8 +389,8 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
         Ln.run(RPR_K_DEC_SELF_ATTN, 4.0 * Ma * H * (double)(t + 1) * d.d_kv,
                4.0 * ((double)Ma * inner * 2 + 2.0 * Ma * (double)(t + 1) * inner), [&] { return launch_dec_self_attn(a, s); });
       }
-      p.attn_out(i, 0, m->dec_o[i], m->h_dec_o[i]);
-      p.project(p.normed(i, 1, m->dec_ln1[i]), {m->dec_xq[i], m->h_dec_xq[i], inner, dm}, out_f32(qb, inner, inner));
+      p.attn_out(i, 0);
+      p.project_in(i, 1, out_f32(qb, inner, inner));
       {
         const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
         DecCrossAttnArgs a{qb, xk, xk + inner, xld, sv.io.mask, p.attn, Q, Bt, H, Lq, p.attn_planes(), p.ps_i,
@@ -395,19 +399,18 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
         Ln.run(RPR_K_DEC_CROSS_ATTN, 4.0 * Ma * H * (double)Lq * d.d_kv,
                4.0 * ((double)Ma * inner * 2 + 2.0 * (Ma / Bt) * (double)Lq * inner), [&] { return launch_step_cross_attn(a, s); });
       }
-      p.attn_out(i, 1, m->dec_xo[i], m->h_dec_xo[i]);
-      p.ff_block(i, 2, m->dec_ln2[i], m->dec_wi[i], m->h_dec_wi[i], m->dec_wo[i], m->h_dec_wo[i]);
+      p.attn_out(i, 1);
+      p.ff_block(i, 2);
     }
     // logits of position t only (the reference computes every position and keeps [-1])
     float* lg = (taps && taps->step_logits) ? taps->step_logits + (size_t)t * R * V : logits;   // taps: V == Vp (rpr_search)
     {
-      // codebook t: V fp32 rows; its planes (times the final layer-norm weight and the scaleup factor) are Vp rows inside
-      // the stacked [2][L*Vp][d] buffer. The split kernel writes whole rows of Vp logits, the exact-fp32 kernel the V real
-      // columns (the pad stays 0). The split-K scratch is not lent and the launcher's no-row-split state does not apply:
+      // codebook t (rpr_model::w_codebook: V fp32 rows, planes of Vp rows). The split kernel writes whole rows of Vp logits,
+      // the exact-fp32 kernel the V real columns (the pad stays 0). The split-K scratch is not lent and the launcher's no-row-split state does not apply:
       // this product has never taken the mid-size split-K route nor set no_row_split, whoever calls enqueue_steps.
       // Its profile record is stated on V columns.
-      LinW wt{d.out_embeds + (size_t)t * V * dm, m->h_out_embeds + (size_t)t * Vp * dm, V, dm};
-      wt.ps = (size_t)d.L * Vp * dm; wt.Nh = Vp; wt.no_scratch = true; wt.row_split_ok = true;
+      LinW wt = m->w_codebook(t);
+      wt.no_scratch = true; wt.row_split_ok = true;
       p.project(p.normed(nd, 0, d.dec_final_ln, p.post), wt, out_f32(lg, Vp, p.h2 ? Vp : V));
     }
     SelectArgs sa{};
@@ -517,7 +520,7 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
   const int* nrows_dev = nf_dev + 2;
   const int Ra = live_count(Ln, nrows_dev, R);
   float *qkv = P<float>(w.t_qkv), *qb = P<float>(w.t_q);
-  Pass p(Ln, m, {w.t_x, w.t_h, w.t_attn, w.t_ff, w.t_x_h, w.t_attn_h, w.t_ff_h, w.t_ssq}, 3, nd, R, nrows_dev, Ra);
+  Pass p(Ln, m, {w.t_x, w.t_h, w.t_attn, w.t_ff, w.t_x_h, w.t_attn_h, w.t_ff_h, w.t_ssq}, true, nd, R, nrows_dev, Ra);
   p.zero_ssq();
   Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * dm * 4, [&] {
     return launch_tail_embed(d.in_embeds, P<uint16_t>(tb.tokens), p.x, R, nrows_dev, T, L, dm, V, s, p.embed_out());
@@ -525,12 +528,12 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
   const size_t kv_pos = (size_t)B * sv.dkv;
   for (int i = 0; i < nd; ++i) {
     const LinOut o_qkv = out_f32(qkv, 3 * inner, 3 * inner);
-    if (i == 0 && p.l0_replaces(m, plan, o_qkv))   // layer 0: the rows of the model's (position, token) table instead of the projection
+    if (i == 0 && p.l0_replaces(plan, o_qkv))   // layer 0: the rows of the model's (position, token) table instead of the projection
       Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * 3 * inner * 4, [&] {
         return launch_tail_l0_qkv(m->l0_table, P<uint16_t>(tb.tokens), qkv, R, nrows_dev, T, L, V, 3 * inner, s);
       });
     else
-      p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, o_qkv);
+      p.project_in(i, 0, o_qkv);
     {
       const size_t ls = sv.kv_layer(B, inner);
       TailSelfAttnArgs a{qkv, sv.kcache + i * ls, sv.vcache + i * ls, sv.kv_q(B, inner), sv.kv_h(B), kv_pos, (size_t)sv.dkv,
@@ -541,8 +544,8 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
       Ln.run(RPR_K_TAIL_SELF_ATTN, 2.0 * Ra * H * (double)(L + T + 1) * sv.dkv, 4.0 * ((double)Ra * 4 * inner + 2.0 * (Ra / Lt) * (double)T * inner),
              [&] { return launch_tail_self_attn(a, s); });
     }
-    p.attn_out(i, 0, m->dec_o[i], m->h_dec_o[i]);
-    p.project(p.normed(i, 1, m->dec_ln1[i]), {m->dec_xq[i], m->h_dec_xq[i], inner, dm}, out_f32(qb, inner, inner));
+    p.attn_out(i, 0);
+    p.project_in(i, 1, out_f32(qb, inner, inner));
     {
       const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
       DecCrossAttnArgs a{qb, xk, xk + inner, xld, P<int32_t>(tb.mask), p.attn, Q, B * Lt, H, Lq, p.attn_planes(), p.ps_i,
@@ -551,8 +554,8 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
       Ln.run(RPR_K_DEC_CROSS_ATTN, 4.0 * Ra * H * (double)Lq * sv.dkv, 4.0 * ((double)Ra * inner * 2 + 2.0 * (Ra / (B * Lt)) * (double)Lq * inner),
              [&] { return launch_tail_cross_attn(a, s); });
     }
-    p.attn_out(i, 1, m->dec_xo[i], m->h_dec_xo[i]);
-    p.ff_block(i, 2, m->dec_ln2[i], m->dec_wi[i], m->h_dec_wi[i], m->dec_wo[i], m->h_dec_wo[i]);
+    p.attn_out(i, 1);
+    p.ff_block(i, 2);
   }
   if (plan.log_softmax()) {
     // the score of a position is the log-probability of its token: final RMSNorm of every row, the V logits of the rows
@@ -610,7 +613,7 @@ void enqueue_search(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie
   // cross-attention K/V of every decoder layer in one GEMM (shared by the B beams of a query;
   // the reference recomputes them for every beam at every step)
   Ln.account_live(packed ? P<int>(w.offs) + Q : nullptr, T);
-  linear(Ln, {P<float>(w.enc_out), P<__half>(w.enc_out_h), (size_t)T * dm, dm}, {d.dec_xkv, m->h_dec_xkv, xld, dm}, T,
+  linear(Ln, {P<float>(w.enc_out), P<__half>(w.enc_out_h), (size_t)T * dm, dm}, m->w_xkv(), T,
          out_f32(P<float>(w.xkv), xld, xld), packed ? P<int>(w.offs) + Q : nullptr, c->enc_rows_accounted);
   Ln.account_live(nullptr, 0);
   Ln.no_row_split = 0;
@@ -677,26 +680,26 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
   Ln.no_row_split = 1;
   enqueue_encoder(Ln, c, m, bz, Lq, true);
   const int xld = xkv_ld(m);
-  linear(Ln, {P<float>(w.enc_out), P<__half>(w.enc_out_h), (size_t)T * dm, dm}, {d.dec_xkv, m->h_dec_xkv, xld, dm}, T,
+  linear(Ln, {P<float>(w.enc_out), P<__half>(w.enc_out_h), (size_t)T * dm, dm}, m->w_xkv(), T,
          out_f32(P<float>(w.xkv), xld, xld), P<int>(w.offs) + bz, c->enc_rows_accounted);
   Ln.account_live(nullptr, 0);
   Ln.no_row_split = 0;
 
   float *qkv = P<float>(w.tr_x), *qb = P<float>(w.q);
-  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, 3, nd, R, nullptr, R);   // every row is live
+  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, true, nd, R, nullptr, R);   // every row is live
   p.zero_ssq();
   Ln.run(RPR_K_OTHER, 0, 2.0 * R * dm * 4, [&] {
     return launch_train_dec_embed(d.start_embed, d.in_embeds, codes, p.x, S, L, dm, V, s, p.embed_out());
   });
   for (int i = 0; i < nd; ++i) {
-    p.project(p.normed(i, 0, m->dec_ln0[i]), {m->dec_qkv[i], m->h_dec_qkv[i], 3 * inner, dm}, out_f32(qkv, 3 * inner, 3 * inner));
+    p.project_in(i, 0, out_f32(qkv, 3 * inner, 3 * inner));
     {  // causal self-attention of every sequence over its own L positions (decoder relative-position table)
       EncAttnArgs a{qkv, nullptr, d.dec_rel_bias, m->dec_bucket, p.attn, S, L, H, d.rel_buckets,
                     p.attn_planes(), p.ps_i, nullptr, nullptr, c->status, 1};
       Ln.run(RPR_K_ENC_ATTN, 2.0 * S * H * (double)L * L * DKV, 4.0 * R * 4 * inner, [&] { return launch_enc_attn(a, s); });
     }
-    p.attn_out(i, 0, m->dec_o[i], m->h_dec_o[i]);
-    p.project(p.normed(i, 1, m->dec_ln1[i]), {m->dec_xq[i], m->h_dec_xq[i], inner, dm}, out_f32(qb, inner, inner));
+    p.attn_out(i, 0);
+    p.project_in(i, 1, out_f32(qb, inner, inner));
     {
       const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
       DecCrossAttnArgs a{qb, xk, xk + inner, xld, P<int32_t>(w.mask), p.attn, bz, ndoc * L, H, Lq, p.attn_planes(), p.ps_i,
@@ -704,8 +707,8 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
       Ln.run(RPR_K_DEC_CROSS_ATTN, 4.0 * R * H * (double)Lq * DKV, 4.0 * ((double)R * inner * 2 + 2.0 * bz * (double)Lq * inner),
              [&] { return launch_dec_cross_attn(a, s); });
     }
-    p.attn_out(i, 1, m->dec_xo[i], m->h_dec_xo[i]);
-    p.ff_block(i, 2, m->dec_ln2[i], m->dec_wi[i], m->h_dec_wi[i], m->dec_wo[i], m->h_dec_wo[i]);
+    p.attn_out(i, 1);
+    p.ff_block(i, 2);
   }
   // decoder_last_hidden_state (final RMSNorm, scaleup factor) dotted with the gold codes' OUTPUT codebook rows — or, for
   // rpr_embed, written out as it is

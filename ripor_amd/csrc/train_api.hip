@@ -185,21 +185,6 @@ struct TrainWs {
 
 namespace {
 
-// The flat parameter order is train_layout.h's (ParamOrder); here every slot gets its tensor. The model names the layer
-// tensors stack by stack: this is the one place that maps (sub-block, role) to those names.
-void build_params(rpr_model* m) {
-  if (!m->params.slots.empty()) return;
-  const auto& d = m->d;
-  m->params = ParamOrder(d);
-  const std::vector<const float*>* layer[K_END - K_ENC_LAYER] = {
-      &m->enc_ln0, &m->enc_qkv, &m->enc_o, &m->enc_ln1, &m->enc_wi, &m->enc_wo,
-      &m->dec_ln0, &m->dec_qkv, &m->dec_o, &m->dec_ln1, &m->dec_xq, &m->dec_xo, &m->dec_ln2, &m->dec_wi, &m->dec_wo};
-  const float* global[K_ENC_LAYER] = {d.shared, d.enc_rel_bias, d.dec_rel_bias, d.enc_final_ln, d.dec_final_ln, d.start_embed,
-                                      d.in_embeds, d.out_embeds, d.dec_xkv};
-  for (ParamSlot& p : m->params.slots)
-    p.ptr = const_cast<float*>(p.kind < K_ENC_LAYER ? global[p.kind] : (*layer[p.kind - K_ENC_LAYER])[(size_t)p.layer]);
-}
-
 int tensure(rpr_ctx* c, DevBuf& b, size_t bytes) {   // like ensure(), without touching the search graphs
   if (bytes <= b.cap) return 0;
   auto& bufs = c->tws->bufs;
@@ -799,7 +784,6 @@ int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int
   RPR_REQUIRE(m->d.d_kv == DKV, "the training kernels are written for d_kv == 64 (t5-base / t5-large)");
   RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_DEC_LEN, "smtid length exceeds the model's decoder length");
   RPR_HIP(hipSetDevice(c->device));
-  build_params(m);
   const auto& d = m->d;
   D = train_dims(d, bz, Lq, L, docs);
   RPR_REQUIRE(self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024,
@@ -839,11 +823,10 @@ void rpr::free_train_ws(rpr_ctx* c) {
 
 extern "C" {
 
-int64_t rpr_param_count(rpr_model* m) { if (!m) return 0; build_params(m); return (int64_t)m->params.slots.size(); }
-int64_t rpr_param_total(rpr_model* m) { if (!m) return 0; build_params(m); return (int64_t)m->params.total; }
+int64_t rpr_param_count(rpr_model* m) { return m ? (int64_t)m->params.slots.size() : 0; }
+int64_t rpr_param_total(rpr_model* m) { return m ? (int64_t)m->params.total : 0; }
 int rpr_param_info(rpr_model* m, int64_t index, const float** ptr, int64_t* numel, int64_t* offset) {
   RPR_REQUIRE(m, "NULL model");
-  build_params(m);
   RPR_REQUIRE(index >= 0 && index < (int64_t)m->params.slots.size(), "parameter index out of range");
   const auto& p = m->params.slots[(size_t)index];
   if (ptr) *ptr = p.ptr;
@@ -943,7 +926,6 @@ int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp
   RPR_REQUIRE(m->ctx == c && step >= 1, "bad model or step (1-based)");
   RPR_HIP(hipSetDevice(c->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  build_params(m);
   if (!c->tws) c->tws = new TrainWs();
   TrainWs& w = *c->tws;
   int e = tensure(c, w.gn_part, 1024 * 8);

@@ -2,7 +2,9 @@
 // A layer is two residual sub-blocks in the encoder and three in the decoder, each y = x + mid(norm(x, ln) W_in^T) W_out^T
 // with mid = self-attention, cross-attention or ReLU. That is written ONCE here, as the table of a stack (StackLayout); the
 // saved activations, the saved X^T slots, the dY^T room of a layer's weight-gradient group, the flat parameter order and a
-// layer's gradient bucket are derived from the table, so the encoder's and the decoder's answers are the same code. Plain
+// layer's gradient bucket are derived from the table, so the encoder's and the decoder's answers are the same code. The
+// same order names a model's weights for the loader and the forward passes (api.hip, passes.hip): which field of the ABI's
+// desc a slot comes from, the shape of a sub-block's GEMM weights and the norm weight folded into their f16 planes. Plain
 // host arithmetic — no HIP types: tests/test_train_layout.py compiles it with the host compiler and checks it without a GPU.
 #pragma once
 #include <algorithm>
@@ -101,17 +103,36 @@ struct TrainLayout {
   size_t dyT_max() const { return std::max(std::max(dec.dyT_elems, enc.dyT_elems), dyT_xkv); }
 };
 
+// ---- the ABI's names of the layer tensors -----------------------------------------------------------------------------------
+// rpr_model_desc names a layer's tensors field by field, one host array of device pointers per kind. The ONE table that maps
+// a layer ParamKind to its field: (ln, W_in, W_out) of the encoder's self-attention and FF sub-blocks, then of the decoder's
+// self-attention, cross-attention and FF.
+typedef const float* const* rpr_model_desc::*LayerField;
+inline LayerField layer_field(int kind) {
+  static const LayerField fields[K_END - K_ENC_LAYER] = {
+      &rpr_model_desc::enc_ln0, &rpr_model_desc::enc_qkv, &rpr_model_desc::enc_o, &rpr_model_desc::enc_ln1, &rpr_model_desc::enc_wi,
+      &rpr_model_desc::enc_wo, &rpr_model_desc::dec_ln0, &rpr_model_desc::dec_qkv, &rpr_model_desc::dec_o, &rpr_model_desc::dec_ln1,
+      &rpr_model_desc::dec_xq, &rpr_model_desc::dec_xo, &rpr_model_desc::dec_ln2, &rpr_model_desc::dec_wi, &rpr_model_desc::dec_wo};
+  return fields[kind - K_ENC_LAYER];
+}
+
 // ---- the flat parameter order -----------------------------------------------------------------------------------------------
-// (observable: rpr_param_info and the checkpoints follow it). ptr: the tensor on the device, filled in by the owner of a model
+// (observable: rpr_param_info and the checkpoints follow it). ptr: the tensor on the device (fill)
 struct ParamSlot { int kind, layer; float* ptr; size_t numel, offset; };
+// One GEMM weight of a sub-block as the loader and the forward passes see it: its slot, its shape [N][K] (the product is
+// x W^T: N output columns, K the reduction) and the slot of the norm weight folded into its f16 planes (-1: none)
+struct WeightRef { int slot, N, K, fold; };
 struct ParamOrder {
   std::vector<ParamSlot> slots;
   size_t total = 0;
-  bool own_out = false;   // the output codebooks are tensors of their own (K_OUT_EMB present)
-  int ne = 0;
+  bool own_out;   // the output codebooks are tensors of their own (K_OUT_EMB present)
+  int ne;
+  StackLayout stack[2];   // encoder, decoder: the tables of sub-blocks only (no rows)
 
-  ParamOrder() = default;
-  explicit ParamOrder(const rpr_model_desc& d) : own_out(d.out_embeds != d.in_embeds), ne(d.num_layers) {
+  explicit ParamOrder(const rpr_model_desc& d)
+      : own_out(d.out_embeds != d.in_embeds), ne(d.num_layers),
+        stack{StackLayout(false, 0, d.num_layers, d.d_model, d.num_heads * d.d_kv, d.d_ff),
+              StackLayout(true, 0, d.num_decoder_layers, d.d_model, d.num_heads * d.d_kv, d.d_ff)} {
     const size_t dm = d.d_model, inner = (size_t)d.num_heads * d.d_kv, nd = d.num_decoder_layers;
     auto add = [&](int kind, int layer, size_t n) { slots.push_back({kind, layer, nullptr, n, total}); total += n; };
     add(K_SHARED, -1, (size_t)d.vocab_size * dm);
@@ -123,12 +144,23 @@ struct ParamOrder {
     add(K_IN_EMB, -1, (size_t)d.L * d.V * dm);
     if (own_out) add(K_OUT_EMB, -1, (size_t)d.L * d.V * dm);
     add(K_XKV, -1, nd * 2 * inner * dm);
-    for (int dec = 0; dec < 2; ++dec) {
-      const StackLayout st(dec, 0, dec ? (int)nd : ne, (int)dm, (int)inner, d.d_ff);
+    for (const StackLayout& st : stack)
       for (int i = 0; i < st.layers; ++i)
         for (int j = 0; j < st.nsub; ++j)
           for (int role = P_LN; role <= P_WOUT; ++role) add(st.kind(j, role), i, st.numel(j, role));
+  }
+  // Every slot gets its tensor from the desc. False if a tensor, a per-layer array or one of its entries is null.
+  bool fill(const rpr_model_desc& d) {
+    const float* global[K_ENC_LAYER] = {d.shared, d.enc_rel_bias, d.dec_rel_bias, d.enc_final_ln, d.dec_final_ln, d.start_embed,
+                                        d.in_embeds, d.out_embeds, d.dec_xkv};
+    bool ok = true;
+    for (ParamSlot& p : slots) {
+      const float* const* per_layer = p.kind < K_ENC_LAYER ? nullptr : d.*layer_field(p.kind);
+      const float* t = p.kind < K_ENC_LAYER ? global[p.kind] : per_layer ? per_layer[p.layer] : nullptr;
+      p.ptr = const_cast<float*>(t);
+      ok = ok && t;
     }
+    return ok;
   }
   // position of a tensor in the order (K_OUT_EMB only where own_out); a layer holds 3 nsub tensors: 6 in the encoder, 9 in the decoder
   int index(int kind, int layer = -1) const {
@@ -139,6 +171,12 @@ struct ParamOrder {
   const ParamSlot& at(int kind, int layer = -1) const { return slots[(size_t)index(kind, layer)]; }
   // (ln, W_in, W_out) of sub-block j of a layer
   const ParamSlot* sub(const StackLayout& st, int layer, int j) const { return &at(st.kind(j, P_LN), layer); }
+  // W_in [n_in][d_model], folded with the ln of its own sub-block, or W_out [d_model][k_out], folded with nothing
+  WeightRef weight(bool dec, int layer, int j, int role) const {
+    const StackLayout& st = stack[dec];
+    const int ln = index(st.kind(j, P_LN), layer);
+    return role == P_WIN ? WeightRef{ln + P_WIN, st.sub[j].n_in, st.dm, ln} : WeightRef{ln + P_WOUT, st.dm, st.sub[j].k_out, -1};
+  }
   // the gradient bucket of a layer as (offset, numel): its tensors are contiguous, ln of sub-block 0 up to the end of the last W_out
   void bucket(const StackLayout& st, int layer, size_t* offset, size_t* numel) const {
     const ParamSlot &lo = at(st.kind0, layer), &hi = at(st.kind(st.nsub - 1, P_WOUT), layer);

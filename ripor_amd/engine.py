@@ -814,11 +814,6 @@ def lngknp_forward(model: DeviceModel, input_ids: torch.Tensor, attention_mask: 
 
 
 # ---- training step of the ranking fine-tune: flat gradient / optimizer buffers -----------------------
-_PARAM_KINDS = ["shared", "enc_rel", "dec_rel", "enc_fln", "dec_fln", "start", "in_emb", "out_emb", "xkv",
-                "enc_ln0", "enc_qkv", "enc_o", "enc_ln1", "enc_wi", "enc_wo",
-                "dec_ln0", "dec_qkv", "dec_o", "dec_ln1", "dec_xq", "dec_xo", "dec_ln2", "dec_wi", "dec_wo"]
-
-
 class TrainState:
     """Flat fp32 buffers of one model replica: gradients and the two AdamW moments, laid out as ``rpr_param_info``
     says (the tensors of ``DeviceModel`` in a fixed order). ``grads`` is what data-parallel ranks all-reduce."""

@@ -4,7 +4,8 @@ tests/train_layout_driver.cpp includes the header and is compiled here with the 
 was worked out by hand from the formulas train_api.hip held before the layout was derived from one table of sub-blocks
 (``Dims::enc_stride`` / ``dec_stride``, ``enc_act`` / ``dec_act``, the two switches of ``XtLayout``, the dY^T sizes of
 ``alloc_train``, the ``K_*`` lists of ``build_params`` and ``layer_numel``); the arithmetic is in the docstrings — none comes
-from running the header. inner = heads x d_kv = 12 x 64 = 768 throughout."""
+from running the header. inner = heads x d_kv = 12 x 64 = 768 throughout, except where the last section says otherwise: the same
+table names a model's weights for rpr_load_model and the forward passes (shapes, folded norms, the ABI's field of every slot)."""
 import json
 import os
 import shutil
@@ -174,3 +175,61 @@ def test_one_doc_per_query(driver):
     assert (dec["dyT_elems"], enc["dyT_elems"], y["dyT_xkv"]) == (540672, 884736, 2359296)
     assert enc["layer"][11]["at"] == enc_expect(100, 128, 768, 768, 3072, 11, 688128, 768000)
     assert dec["layer"][11]["at"] == dec_expect(40, 64, 768, 768, 3072, 11, 8355840, 442368, 399360)
+
+
+# ---- the model's weights as the loader and the forward passes get them (ParamOrder::weight, ParamOrder::fill) ---------------
+WIDE = dict(vocab=512, buckets=32, H=32, dkv=128, dm=1024, dff=16384, ne=2, nd=3, Lm=8, V=256)
+# per stack and sub-block: W_in [N, K], its elements, the folded norm (position of the sub-block's ln in the layer), W_out [N, K],
+# its elements. t5-base: inner = 12 * 64 = 768 = d_model, 3 inner = 2304; 2304 * 768 = 1769472, 768 * 768 = 589824, 3072 * 768 = 2359296.
+BASE_WEIGHTS = dict(enc=[((2304, 768), 1769472, 0, (768, 768), 589824), ((3072, 768), 2359296, 3, (768, 3072), 2359296)],
+                    dec=[((2304, 768), 1769472, 0, (768, 768), 589824), ((768, 768), 589824, 3, (768, 768), 589824),
+                         ((3072, 768), 2359296, 6, (768, 3072), 2359296)])
+# inner = 32 * 128 = 4096 != d_model = 1024, 3 inner = 12288: 12288 * 1024 = 12582912, 4096 * 1024 = 4194304, 16384 * 1024 = 16777216
+WIDE_WEIGHTS = dict(enc=[((12288, 1024), 12582912, 0, (1024, 4096), 4194304), ((16384, 1024), 16777216, 3, (1024, 16384), 16777216)],
+                    dec=[((12288, 1024), 12582912, 0, (1024, 4096), 4194304), ((4096, 1024), 4194304, 3, (1024, 4096), 4194304),
+                         ((16384, 1024), 16777216, 6, (1024, 16384), 16777216)])
+
+
+@pytest.mark.parametrize("model,want", ((BASE, BASE_WEIGHTS), (WIDE, WIDE_WEIGHTS)), ids=("t5_base", "inner_4096_dm_1024"))
+def test_weights_of_every_sub_block(driver, model, want):
+    """W_in [n_in, d_model] carries the ln of its own sub-block, W_out [d_model, k_out] nothing: enc_qkv: ln0, enc_wi: ln1,
+    dec_qkv: ln0, dec_xq: ln1, dec_wi: ln2. With codebooks of their own 9 tensors stand in front of the layers; encoder layer i
+    starts at slot 9 + 6 i, decoder layer i at 9 + 6 ne + 9 i; sub-block j holds (ln, W_in, W_out) at 3 j, 3 j + 1, 3 j + 2."""
+    y = layout(driver, bz=1, Lq=1, L=1, docs=1, **model)
+    for stack, first, per_layer, layers in (("enc", 9, 6, model["ne"]), ("dec", 9 + 6 * model["ne"], 9, model["nd"])):
+        assert len(y["weights"][stack]) == layers
+        for i, layer in enumerate(y["weights"][stack]):
+            base = first + per_layer * i
+            assert len(layer) == len(want[stack])
+            for j, (got, (nk_in, numel_in, ln_at, nk_out, numel_out)) in enumerate(zip(layer, want[stack])):
+                assert ln_at == 3 * j
+                assert got == dict(ln=base + ln_at, w_in=[base + 3 * j + 1, numel_in, *nk_in, base + ln_at],
+                                   w_out=[base + 3 * j + 2, numel_out, *nk_out, -1]), (stack, i, j)
+                assert y["params"][got["w_in"][0]][2] == numel_in and y["params"][got["w_out"][0]][2] == numel_out
+
+
+# the per-layer fields of rpr_model_desc in the order of include/ripor_hip.h, which is the order of the layer kinds
+FIELDS = ["enc_ln0", "enc_qkv", "enc_o", "enc_ln1", "enc_wi", "enc_wo",
+          "dec_ln0", "dec_qkv", "dec_o", "dec_ln1", "dec_xq", "dec_xo", "dec_ln2", "dec_wi", "dec_wo"]
+FIELD_KIND = dict(zip(FIELDS, (K_ENC_LN0, K_ENC_QKV, K_ENC_O, K_ENC_LN1, K_ENC_WI, K_ENC_WO, K_DEC_LN0, K_DEC_QKV, K_DEC_O, K_DEC_LN1,
+                               K_DEC_XQ, K_DEC_XO, K_DEC_LN2, K_DEC_WI, K_DEC_WO)))
+
+
+def test_every_layer_slot_points_into_its_field(driver):
+    """Two encoder and three decoder layers: slot (kind, layer) holds element `layer` of the field of that kind, 6 * 2 + 9 * 3 = 39
+    slots in the order of the layers."""
+    f = layout(driver, **MINI)["fields"]
+    assert f["fill_ok"] == 1 and f["globals_ok"] == 1
+    want = [[FIELD_KIND[name], i, FIELDS.index(name), i] for i in range(2) for name in FIELDS[:6]]
+    want += [[FIELD_KIND[name], i, FIELDS.index(name), i] for i in range(3) for name in FIELDS[6:]]
+    assert len(want) == 39 and f["slots"] == want
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_a_null_entry_is_reported(driver, field):
+    """The last element of every field in turn (encoder: layer 1, decoder: layer 2), and the field's whole array."""
+    k = FIELDS.index(field)
+    for elem in (1 if k < 6 else 2, 0, -1):
+        f = layout(driver, null_field=k, null_elem=elem, **MINI)["fields"]
+        assert f["fill_ok"] == 0, (field, elem)
+        assert len(f["slots"]) == (38 if elem >= 0 else 39 - (2 if k < 6 else 3))
