@@ -411,6 +411,16 @@ int rpr_seq2seq_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* 
 int rpr_adamw_step(rpr_ctx* ctx, rpr_model* model, const float* flat_grads, float* exp_avg, float* exp_avg_sq, int64_t step,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
                    float* out_grad_norm, void* stream);
+/* Dropout of the two training steps (the reference trains in model.train(): every dropout of HF T5Stack is live at the
+ * checkpoint's dropout_rate — stack input, attention probabilities, sub-block outputs, the feed-forward's inner activation,
+ * stack output; both stacks). Applies to the rpr_lngknp_backward[_buckets] and rpr_seq2seq_backward[_buckets] calls that follow,
+ * until set again; rpr_lngknp_forward, rpr_seq2seq_forward, rpr_search*, rpr_encode and rpr_embed stay in evaluation mode.
+ * 0 <= rate < 1, else RPR_ERR_INVALID; the default, rate 0, is off: a training call then enqueues exactly what it enqueues
+ * without this call. The mask of an element is a stateless function of (seed, step, site, logical coordinates) — Philox4x32-10,
+ * csrc/dropout.h, DESIGN.md "Dropout in the training step" — so the same (seed, step) gives the same bits in every precision
+ * mode and launch shape, and nothing but (seed, step) has to be kept to resume a run. The encoder runs once per query: the
+ * positive and the negative pass share its masks (the reference runs it twice, with independent masks). */
+int rpr_set_train_dropout(rpr_ctx* ctx, float rate, uint64_t seed, uint64_t step);
 
 /* ---- sticky status of a ctx ------------------------------------------------------------------------
  * RPR_STATUS_SATURATED: in RPR_PREC_F16X2 mode an activation left the range of the f16 planes (|x| > 65504 after
@@ -461,6 +471,11 @@ int rpr_op_linear_bf16(rpr_ctx* ctx, const float* A, const float* W, const float
 /* out[rows,d] = w * x * rsqrt(mean(x^2) + eps) */
 int rpr_op_rmsnorm(rpr_ctx* ctx, const float* x, const float* w, float* out, int32_t rows, int32_t d,
                    float eps, void* stream);
+/* The activation dropout mask of the training step over x [n_seq, n_pos, n_feat] (out may be x): out = 0 where the element's
+ * draw is below round(rate * 2^32), x * fp32(1 / (1 - rate)) elsewhere. n_pos <= 65536, 0 <= site < 65536. The parity hook of
+ * the device mask against its numpy restatement (tests/dropout_mask.py). */
+int rpr_op_dropout(rpr_ctx* ctx, const float* x, float* out, int64_t n_seq, int32_t n_pos, int32_t n_feat, float rate,
+                   uint64_t seed, uint64_t step, int32_t site, void* stream);
 /* Encoder forward only (reference generation.py:132-137): out [Q, Lq, d_model]. */
 int rpr_encode(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
                int32_t Q, int32_t Lq, float* out, void* stream);

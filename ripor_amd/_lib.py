@@ -128,6 +128,9 @@ SIGNATURES = {
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rpr_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "rpr_set_train_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64]),
+    "rpr_op_dropout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
+                                 C.c_uint64, C.c_int32, C.c_void_p]),
     "rpr_get_status": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
     "rpr_status_words_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "rpr_model_f32_only": (C.c_int, [C.c_void_p]),

@@ -8,6 +8,7 @@
 
 #include "../../include/ripor_hip.h"
 #include "attn_route.h"
+#include "dropout.h"
 
 namespace rpr {
 
@@ -735,10 +736,23 @@ int rmsnorm_bwd_parts(int rows);
 hipError_t launch_colsum_multi(const ColsumSites& p, int d, hipStream_t s);
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
-                                hipStream_t s);
+                                hipStream_t s, const DropAttn* drop = nullptr);
 size_t cross_attn_bwd_smem(int n, int Lq);
 hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, const float* dO,
-                                 float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s);
+                                 float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s,
+                                 const DropAttn* drop = nullptr);
+// dropout of the training step (dropout.h): the attention forward with dropped-out probabilities (the two backward launches
+// above draw the same mask when handed the same DropAttn), the mask over an activation's rows r = sequence * n_pos + position
+// (out = resid + mask(x); resid nullable, x may be out), and the gold-code scores from an already normalised, dropped-out
+// hidden state (dscores null: scores; else dh and de)
+hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, const float* rel_bias, const int32_t* bucket, float* out,
+                                     int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s);
+hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
+                                      int n, int Lq, int H, const DropAttn& drop, hipStream_t s);
+hipError_t launch_dropout_rows(const float* x, const float* resid, float* out, size_t n_seq, int n_pos, int n_feat, const DropKey& key,
+                               int site, hipStream_t s);
+hipError_t launch_gold_rowdot(const float* hd, const float* out_embeds, const int32_t* out_idx, float* scores, const float* dscores,
+                              float* dh, float* de, int rows, int d, hipStream_t s);
 hipError_t launch_scatter_rows_fix(const float* src, const int32_t* idx, unsigned long long* acc, int rows, int d, hipStream_t s);
 hipError_t launch_fix_flush(unsigned long long* acc, float* dst, size_t n, hipStream_t s);
 hipError_t launch_train_indices(const int32_t* codes, int32_t* in_idx, int32_t* out_idx, int S, int L, int V, hipStream_t s);

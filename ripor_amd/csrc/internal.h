@@ -234,6 +234,7 @@ struct rpr_ctx : rpr::SearchSettings {   // (what a search is planned from: prec
   unsigned int* status = nullptr;       // [dev, 64 words] [8] weight-range probe; sticky words: [0] a value left the f16 plane range, [1] a query attends to nothing, [2] a query was left unforced by the last fork of an optimistic forced-tail search
   unsigned int* status_host = nullptr;  // pinned mirror filled by rpr_get_status
   struct TrainWs* tws = nullptr;        // activations / scratch of the training step (train_api.hip), freed by free_train_ws
+  struct { float rate = 0.f; uint64_t seed = 0, step = 0; } train_drop;   // rpr_set_train_dropout: what the backward entry points apply (rate 0 = off)
   Workspace ws;
   Lane lanes[2];
   int lanes_state = 0;          // 0 not tried yet, 1 ready, -1 masked streams unavailable on this device

@@ -170,7 +170,8 @@ struct TrainWs {
   // transposed copy in the consumer's X^T / dY^T slot) instead of through a conversion launch: relu(h Wi^T) in the forward
   // pass, the masked gradient w.r.t. it in the backward pass (GemmH2Args::out_b / out_bt / mask_src)
   DevBuf bfb;
-  DevBuf aseg, apref;                  // rpr_adamw_step: one launch over all tensors (table built once per model)
+  DevBuf drop_dy;                      // dropout: the masked gradient w.r.t. a sub-block's output, the dY of its W_out products
+  DevBuf aseg, apref;                 // rpr_adamw_step: one launch over all tensors (table built once per model)
   const rpr_model* aw_model = nullptr;
   int aw_nseg = 0, aw_chunks = 0;
   const rpr_model* wc_model = nullptr;
@@ -329,6 +330,32 @@ Stack dec_stack(const rpr_ctx* c, const rpr_model* m, const TrainDims& D, const 
   return {Y.dec, m->params, P<float>(w.dec_act), P<float>(w.x_last), c->precision == RPR_PREC_BF16 ? P<__half>(w.xT) : nullptr,
           nullptr, m->d.dec_rel_bias, m->dec_bucket, D.S, D.L, 1};
 }
+
+// The dropout of one pass (rpr_set_train_dropout; the mask function and its sites: dropout.h). Off — rate 0, or an entry point
+// that stays in evaluation mode — nothing here launches anything and the pass enqueues what it always did. On, every site is
+// a small pass of its own over the activation (rows) or a training-only attention kernel (attn); the backward walks the same
+// sites and draws the same masks again. The feed-forward block then takes the unfused route (fused_ok hands bf16 operands
+// from the inner product's epilogue to the outer product: the mask would have to go into the hot GEMM's epilogue).
+struct Drop {
+  DropKey key{};
+  bool on = false;
+  Drop() = default;
+  Drop(float rate, uint64_t seed, uint64_t step) : on(rate > 0.f) {   // 0 <= rate < 1 (checked by the entry points)
+    key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(step >> 32); key.step_lo = (uint32_t)step;
+    key.thr = (uint32_t)llrint((double)rate * 4294967296.0);
+    key.scale = 1.0f / (1.0f - rate);
+  }
+  explicit Drop(const rpr_ctx* c) : Drop(c->train_drop.rate, c->train_drop.seed, c->train_drop.step) {}
+  // out = (resid +) mask(x) over the rows [nseq * len][nfeat] of nseq sequences of len positions
+  void rows(Launcher& Ln, int nseq, int len, const float* x, const float* resid, float* out, int nfeat, int site) const {
+    Ln.run(RPR_K_OTHER, 0, (resid ? 12.0 : 8.0) * nseq * len * nfeat,
+           [&] { return launch_dropout_rows(x, resid, out, (size_t)nseq, len, nfeat, key, site, Ln.s); });
+  }
+  void rows(Launcher& Ln, const Stack& k, const float* x, const float* resid, float* out, int nfeat, int site) const {
+    rows(Ln, k.nseq, k.len, x, resid, out, nfeat, site);
+  }
+  DropAttn attn(int site, int L) const { return DropAttn{key, site, L}; }
+};
 
 // bf16 copies of every GEMM weight, refreshed at the start of each pass (the weights change between passes: AdamW, or the
 // caller writing through rpr_param_info's pointers). The table of tensors is built once per model.
@@ -532,6 +559,7 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
   E(w.scores, R * f); E(w.margins, 8 * (size_t)D.bz * f); E(w.dscores, R * f);
   E(w.in_idx, R * 4); E(w.out_idx, R * 4);
   if (D.docs == 1) { E(w.hF, R * dm * f); E(w.dlog, R * (size_t)D.V * f); E(w.row_loss, R * f); }   // the seq2seq head
+  if (c->train_drop.rate > 0.f) { E(w.hF, R * dm * f); E(w.drop_dy, rows * dm * f); }   // dropout: the ranking step keeps hF too
   E(w.h, rows * dm * f); E(w.dxa, rows * dm * f); E(w.dxb, rows * dm * f); E(w.dbig, rows * wide * f);
   E(w.dattn, rows * inner * f); E(w.dxkv, T * (size_t)D.xld * f); E(w.denc, T * dm * f);
   E(w.tA, wide * rp * f);
@@ -550,7 +578,7 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
 // gold: end with the gold-code scores of the ranking step (w.scores); else the decoder stream is left in w.x_last for the
 // seq2seq head
 void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, const int32_t* ids, const int32_t* mask,
-             const int32_t* codes, int32_t* last, bool gold = true) {
+             const int32_t* codes, int32_t* last, const Drop& drop, bool gold = true) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
@@ -588,9 +616,17 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
     const int rows = k.lay.rows;
     const bool ff = b.kind == SUB_FF;
     float *x = k.x(i, j), *in = k.in(i, j), *mid = k.mid(i, j);
-    const void* ready = norm_gemm(x, p[P_LN].ptr, p[P_WIN].ptr, in, rows, b.n_in, ff, k.xt_in(i, j), ff ? k.xt_out(i, j) : nullptr);
+    const void* ready = norm_gemm(x, p[P_LN].ptr, p[P_WIN].ptr, in, rows, b.n_in, ff, k.xt_in(i, j), ff && !drop.on ? k.xt_out(i, j) : nullptr);
+    const int site_mid = drop_site_mid(k.lay.dec, i, j);
     switch (b.kind) {
       case SUB_SELF: {
+        if (drop.on) {
+          Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
+            return launch_self_attn_drop_fwd(in, k.mask, k.rel_bias, k.bucket, mid, k.nseq, k.len, D.H, d.rel_buckets, k.causal,
+                                             drop.attn(site_mid, k.len), s);
+          });
+          break;
+        }
         EncAttnArgs sa{in, k.mask, k.rel_bias, k.bucket, mid, k.nseq, k.len, D.H, d.rel_buckets, nullptr, 0, nullptr, nullptr, nullptr,
                        k.causal, 1};
         Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] { return launch_enc_attn(sa, s); });
@@ -598,15 +634,26 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
       }
       case SUB_CROSS: {
         const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
+        if (drop.on) {
+          Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {
+            return launch_cross_attn_drop_fwd(in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.Lq, D.H, drop.attn(site_mid, D.L), s);
+          });
+          break;
+        }
         DecCrossAttnArgs ca{in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr};
         // (the query's docs L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64)
         Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] { return launch_tail_cross_attn(ca, s); });
         break;
       }
-      case SUB_FF: break;   // the ReLU ran in the inner product's epilogue
+      case SUB_FF:   // the ReLU ran in the inner product's epilogue
+        if (drop.on) drop.rows(Ln, k, in, nullptr, in, b.n_in, site_mid);
+        break;
     }
-    gemm(Ln, mid, b.k_out, p[P_WOUT].ptr, b.k_out, k.x(i, j + 1), dm, rows, dm, b.k_out, x, 0, k.xt_out(i, j), ready);
+    float* y = k.x(i, j + 1);
+    gemm(Ln, mid, b.k_out, p[P_WOUT].ptr, b.k_out, y, dm, rows, dm, b.k_out, drop.on ? nullptr : x, 0, k.xt_out(i, j), ready);
+    if (drop.on) drop.rows(Ln, k, y, x, y, dm, drop_site_sub_out(k.lay.dec, i, j));   // y = x + dropout(mid W_out^T)
   };
+  auto stack_in = [&](const Stack& k) { if (drop.on) drop.rows(Ln, k, k.x(0, 0), nullptr, k.x(0, 0), dm, drop_site_input(k.lay.dec)); };
   auto stack_fwd = [&](const Stack& k) {
     for (int i = 0; i < k.lay.layers; ++i)
       for (int j = 0; j < k.lay.nsub; ++j) sub_fwd(k, i, j);
@@ -616,15 +663,26 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
   // ---- encoder over the padded [bz, Lq] layout (padded positions get no gradient: nothing downstream reads them)
   const Stack enc = enc_stack(c, m, D, Y, mask);
   Ln.run(RPR_K_OTHER, 0, 8.0 * T * dm, [&] { return launch_embed_rows(d.shared, ids, enc.x(0, 0), T, dm, d.vocab_size, s); });
+  stack_in(enc);
   stack_fwd(enc);
   norm(enc.x_end, d.enc_final_ln, P<float>(w.enc_out), T);
+  if (drop.on) drop.rows(Ln, enc, P<float>(w.enc_out), nullptr, P<float>(w.enc_out), dm, drop_site_output(0));
   gemm(Ln, P<float>(w.enc_out), dm, d.dec_xkv, dm, P<float>(w.xkv), D.xld, T, D.xld, dm, nullptr, 0, enc.xT ? enc.xT + Y.xt_xkv : nullptr);
   // ---- teacher-forced decoder over all positions of every smtid (ranking step: the positive and the negative)
   const Stack dec = dec_stack(c, m, D, Y);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_train_indices(codes, P<int32_t>(w.in_idx), P<int32_t>(w.out_idx), D.S, D.L, D.V, s); });
   Ln.run(RPR_K_OTHER, 0, 8.0 * R * dm, [&] { return launch_train_dec_embed(d.start_embed, d.in_embeds, codes, dec.x(0, 0), D.S, D.L, dm, D.V, s); });
+  stack_in(dec);
   stack_fwd(dec);
   if (!gold) return;
+  if (drop.on) {   // hF = dropout(final norm) by its own launches, then the scores from it (gold_score_kernel fuses norm and score)
+    norm(P<float>(w.x_last), d.dec_final_ln, P<float>(w.hF), R, D.post);
+    drop.rows(Ln, dec, P<float>(w.hF), nullptr, P<float>(w.hF), dm, drop_site_output(1));
+    Ln.run(RPR_K_OTHER, 0, 0, [&] {
+      return launch_gold_rowdot(P<float>(w.hF), d.out_embeds, P<int32_t>(w.out_idx), P<float>(w.scores), nullptr, nullptr, nullptr, R, dm, s);
+    });
+    return;
+  }
   Ln.run(RPR_K_OTHER, 0, 0, [&] {
     return launch_gold_scores(P<float>(w.x_last), d.dec_final_ln, d.out_embeds, codes, P<float>(w.scores), D.S, D.L, dm, D.V, D.eps,
                               D.post, s);
@@ -634,13 +692,14 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
 // The seq2seq head after forward(gold = false): hF = the final RMSNorm of the decoder stream (times d^-0.5 under
 // scaleup_output_hidden), then logits, log-softmax, cross-entropy and dlogits (train_kernels.hip, exact fp32 in every mode)
 void s2s_head_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, const int32_t* labels, float* out_loss,
-                      float* out_label_lp) {
+                      float* out_label_lp, const Drop& drop) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
   Ln.run(RPR_K_RMSNORM, 0, 8.0 * D.R * D.dm, [&] {
     return launch_rmsnorm(P<float>(w.x_last), d.dec_final_ln, P<float>(w.hF), D.R, D.dm, D.eps, s, D.post);
   });
+  if (drop.on) drop.rows(Ln, D.S, D.L, P<float>(w.hF), nullptr, P<float>(w.hF), D.dm, drop_site_output(1));
   Ln.run(RPR_K_OTHER, 2.0 * D.R * (double)D.V * D.dm, 4.0 * ((double)D.R * D.dm + (double)D.L * D.V * D.dm + (double)D.R * D.V), [&] {
     return launch_s2s_head_fwd(P<float>(w.hF), d.out_embeds, labels, P<float>(w.dlog), P<float>(w.row_loss), out_label_lp, out_loss,
                                D.bz, D.L, D.dm, D.V, s);
@@ -660,7 +719,7 @@ struct BucketHook {
 
 // ce_head: the seq2seq cross-entropy head (s2s_head_forward ran) instead of the ranking step's gold scores
 void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const int32_t* ids, const int32_t* mask, float* G,
-              BucketHook* hook = nullptr, bool ce_head = false) {
+              const Drop& drop, BucketHook* hook = nullptr, bool ce_head = false) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
@@ -700,12 +759,15 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
   } else {
     // ---- gold scores: dscore -> (dE rows, dhF) -> final RMSNorm backward
     Ln.run(RPR_K_OTHER, 0, 0, [&] {   // dE rows go to dxb, dhF to dxa
+      if (drop.on)   // from the dropped-out hF the forward kept
+        return launch_gold_rowdot(P<float>(w.hF), d.out_embeds, P<int32_t>(w.out_idx), nullptr, P<float>(w.dscores), dxa, dxb, R, dm, s);
       return launch_gold_score_bwd(P<float>(w.x_last), d.dec_final_ln, d.out_embeds, P<int32_t>(w.out_idx), P<float>(w.dscores), dxa, dxb,
                                    R, dm, D.eps, D.post, s);
     });
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dxb, P<int32_t>(w.out_idx), fix, R, dm, s); });
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g_out, (size_t)d.L * D.V * dm, s); });
   }
+  if (drop.on) drop.rows(Ln, dec, dxa, nullptr, dxa, dm, drop_site_output(1));
   B.norm_bwd(P<float>(w.x_last), d.dec_final_ln, dxa, nullptr, dxb, g(K_DEC_FLN), R, D.post);
   float *dx = dxb, *dx2 = dxa;   // dx = gradient w.r.t. the current sub-block's output stream, dx2 the buffer its input's goes to
   // y = x + mid(norm(x, ln) W_in^T) W_out^T backwards: dxdw of W_out -> the middle op's backward, into dbig -> (the norm again
@@ -717,23 +779,32 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
     float *x = k.x(i, j), *in = k.in(i, j);
     const float* relu = b.kind == SUB_FF && bf16 ? in : nullptr;   // FF: in = relu(norm(x) Wi^T), the mask of its own gradient
     float* dmid = b.kind == SUB_FF ? dbig : dattn;
-    B.dxdw(dx, p[P_WOUT].ptr, k.mid(i, j), dmid, G + p[P_WOUT].offset, rows, dm, b.k_out, k.xt_out(i, j), nullptr, relu);
+    // dropout: the W_out products see the masked dx, the residual path (norm_bwd below) the whole of it; the dropped-out `in` of
+    // the FF block is positive exactly where its ReLU passed AND the element was kept, so it still gates its own gradient
+    const int site_mid = drop_site_mid(k.lay.dec, i, j);
+    const DropAttn da = drop.attn(site_mid, k.lay.dec && b.kind == SUB_CROSS ? D.L : k.len);
+    const float* dy = dx;
+    if (drop.on) { dy = P<float>(w.drop_dy); drop.rows(Ln, k, dx, nullptr, P<float>(w.drop_dy), dm, drop_site_sub_out(k.lay.dec, i, j)); }
+    B.dxdw(dy, p[P_WOUT].ptr, k.mid(i, j), dmid, G + p[P_WOUT].offset, rows, dm, b.k_out, k.xt_out(i, j), nullptr, drop.on ? nullptr : relu);
     switch (b.kind) {
       case SUB_FF:
+        if (drop.on) drop.rows(Ln, k, dbig, nullptr, dbig, b.n_in, site_mid);
         if (!bf16) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_relu_bwd(dbig, in, (size_t)rows * b.n_in, s); });
         break;
       case SUB_CROSS: {
         const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
         float* dxk = P<float>(w.dxkv) + (size_t)i * 2 * inner;
         Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {   // dq into dbig (as [R, inner])
-          return launch_cross_attn_bwd(in, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, D.docs * D.L, D.Lq, H, s);
+          return launch_cross_attn_bwd(in, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, D.docs * D.L, D.Lq, H, s,
+                                       drop.on ? &da : nullptr);
         });
         break;
       }
       case SUB_SELF:
         Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
           return launch_self_attn_bwd(in, dattn, k.mask, k.rel_bias, k.bucket, dbig, P<float>(w.bias_part),
-                                      g(k.lay.dec ? K_DEC_REL : K_ENC_REL), k.nseq, k.len, H, d.rel_buckets, k.causal, s);
+                                      g(k.lay.dec ? K_DEC_REL : K_ENC_REL), k.nseq, k.len, H, d.rel_buckets, k.causal, s,
+                                      drop.on ? &da : nullptr);
         });
         break;
     }
@@ -755,6 +826,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
   // ---- decoder
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return hipMemsetAsync(w.dxkv.p, 0, (size_t)T * D.xld * sizeof(float), s); });
   stack_bwd(dec);
+  if (drop.on) drop.rows(Ln, dec, dx, nullptr, dx, dm, drop_site_input(1));
   // decoder input embeddings: codebook rows and the start embedding
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dx, P<int32_t>(w.in_idx), fix, R, dm, s); });
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g(K_IN_EMB), (size_t)d.L * D.V * dm, s); });
@@ -763,9 +835,11 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
   float* denc = P<float>(w.denc);
   B.dxdw(P<float>(w.dxkv), d.dec_xkv, P<float>(w.enc_out), denc, g(K_XKV), T, D.xld, dm, enc.xT ? enc.xT + Y.xt_xkv : nullptr);
   w.side.flush(Ln);
+  if (drop.on) drop.rows(Ln, enc, denc, nullptr, denc, dm, drop_site_output(0));
   B.norm_bwd(enc.x_end, d.enc_final_ln, denc, nullptr, dxa, g(K_ENC_FLN), T);
   dx = dxa; dx2 = dxb;   // the ping-pong starts again
   stack_bwd(enc);
+  if (drop.on) drop.rows(Ln, enc, dx, nullptr, dx, dm, drop_site_input(0));
   // token embeddings (the encoder's table is the shared one)
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_scatter_rows_fix(dx, ids, fix, T, dm, s); });
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_fix_flush(fix, g(K_SHARED), (size_t)d.vocab_size * dm, s); });
@@ -858,13 +932,14 @@ int rpr_lngknp_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_i
   Launcher Ln{c, s};
   e = train_begin(Ln, c, m);
   if (e) return e;
-  forward(Ln, c, m, D, input_ids, attention_mask, doc_codes, P<int32_t>(c->ws.last));
+  const Drop drop(c);
+  forward(Ln, c, m, D, input_ids, attention_mask, doc_codes, P<int32_t>(c->ws.last), drop);
   if (Ln.err) return Ln.err;
   RPR_HIP(launch_margin_mse(P<float>(w.scores), teacher_pos, teacher_neg, prefix_lens, n_prefix, bz, L, out_losses, P<float>(w.margins), s));
   // total loss = sum of the task losses with weight 1 (reference arguments.py:109-119, trainer.py:228-240)
   RPR_HIP(launch_margin_mse_bwd(P<float>(w.margins), teacher_pos, teacher_neg, prefix_lens, n_prefix, bz, L, P<float>(w.dscores), s));
   BucketHook hook{on_bucket, user, reinterpret_cast<hipStream_t>(comm_stream)};
-  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, on_bucket ? &hook : nullptr);
+  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, drop, on_bucket ? &hook : nullptr);
   return Ln.err;
 }
 
@@ -891,11 +966,12 @@ static int seq2seq_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const
   Launcher Ln{c, s};
   e = train_begin(Ln, c, m);
   if (e) return e;
-  forward(Ln, c, m, D, input_ids, attention_mask, labels, P<int32_t>(c->ws.last), false);
-  s2s_head_forward(Ln, c, m, D, labels, out_loss, out_label_lp);
+  const Drop drop = flat_grads ? Drop(c) : Drop();   // rpr_seq2seq_forward stays in evaluation mode
+  forward(Ln, c, m, D, input_ids, attention_mask, labels, P<int32_t>(c->ws.last), drop, false);
+  s2s_head_forward(Ln, c, m, D, labels, out_loss, out_label_lp, drop);
   if (Ln.err || !flat_grads) return Ln.err;
   BucketHook hook{on_bucket, user, reinterpret_cast<hipStream_t>(comm_stream)};
-  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, on_bucket ? &hook : nullptr, true);
+  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, drop, on_bucket ? &hook : nullptr, true);
   return Ln.err;
 }
 
@@ -917,6 +993,26 @@ int rpr_seq2seq_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_
   RPR_REQUIRE(flat_grads, "NULL argument");
   return seq2seq_run(c, m, input_ids, attention_mask, bz, Lq, labels, L, out_loss, nullptr, flat_grads, stream, comm_stream, on_bucket,
                      user);
+}
+
+int rpr_set_train_dropout(rpr_ctx* c, float rate, uint64_t seed, uint64_t step) {
+  RPR_REQUIRE(c, "NULL ctx");
+  RPR_REQUIRE(rate >= 0.f && rate < 1.f, "dropout rate outside [0, 1)");   // (a NaN fails both comparisons)
+  c->train_drop.rate = rate; c->train_drop.seed = seed; c->train_drop.step = step;
+  return RPR_OK;
+}
+
+// test hook: the activation mask of dropout.h over x [n_seq][n_pos][n_feat] (tests/test_gpu_dropout.py compares it bit for bit
+// with the numpy restatement)
+int rpr_op_dropout(rpr_ctx* c, const float* x, float* out, int64_t n_seq, int32_t n_pos, int32_t n_feat, float rate, uint64_t seed,
+                   uint64_t step, int32_t site, void* stream) {
+  RPR_REQUIRE(c && x && out, "NULL argument");
+  RPR_REQUIRE(rate >= 0.f && rate < 1.f, "dropout rate outside [0, 1)");
+  RPR_REQUIRE(n_seq >= 0 && n_pos >= 1 && n_pos <= 65536 && n_feat >= 1 && site >= 0 && site <= 0xffff, "shape or site out of range");
+  RPR_HIP(hipSetDevice(c->device));
+  const Drop d(rate, seed, step);
+  RPR_HIP(launch_dropout_rows(x, nullptr, out, (size_t)n_seq, n_pos, n_feat, d.key, site, reinterpret_cast<hipStream_t>(stream)));
+  return RPR_OK;
 }
 
 int rpr_adamw_step(rpr_ctx* c, rpr_model* m, const float* flat_grads, float* exp_avg, float* exp_avg_sq, int64_t step, float lr,

@@ -432,8 +432,13 @@ __device__ __forceinline__ void attn_scores_dp(const float* Qs, const float* Ds,
   }
 }
 
-// row softmax of Ps in place, then Gs = dS = P * (dP - sum_j dP P); eight lanes per row
-__device__ __forceinline__ void attn_softmax_ds(float* Ps, float* Gs, int nq, int nk, int PL) {
+// row softmax of Ps in place, then Gs = dS = P * (dP - sum_j dP P); eight lanes per row.
+// DROP: the forward multiplied P by mul (0 where dropped, scale = 1 / (1 - rate) where kept; dropout.h) before the product with
+// V, so Gs comes in as the gradient w.r.t. that product: dP = mul * Gs, and Ps leaves as mul * P, what dV is made from.
+// keep4(i, g) = the keep bits of keys 4 g .. 4 g + 3 of row i: a lane owns whole groups of four keys (one Philox block each)
+// and carries their bits from the first loop to the second in a register — at most 32 keys per lane: nk <= 256.
+template <bool DROP = false, class KEEP4 = int>
+__device__ __forceinline__ void attn_softmax_ds(float* Ps, float* Gs, int nq, int nk, int PL, KEEP4 keep4 = 0, float scale = 1.0f) {
   const int sub = threadIdx.x & 7;
   for (int i = threadIdx.x >> 3; i < nq; i += 32) {
     float* pr = Ps + i * PL; float* gr = Gs + i * PL;
@@ -445,9 +450,32 @@ __device__ __forceinline__ void attn_softmax_ds(float* Ps, float* Gs, int nq, in
     for (int m = 1; m < 8; m <<= 1) sum += __shfl_xor(sum, m, 8);
     const float inv = sum > 0.f ? 1.0f / sum : 0.f;
     float c = 0.f;
-    for (int j = sub; j < nk; j += 8) { const float pj = pr[j] * inv; pr[j] = pj; c = fmaf(gr[j], pj, c); }
-    for (int m = 1; m < 8; m <<= 1) c += __shfl_xor(c, m, 8);
-    for (int j = sub; j < nk; j += 8) gr[j] = pr[j] * (gr[j] - c);
+    if constexpr (DROP) {
+      uint32_t kept = 0;
+      int gi = 0;
+      for (int g = sub; 4 * g < nk; g += 8, ++gi) {
+        const uint32_t k4 = keep4(i, g);
+        kept |= k4 << (4 * gi);
+        for (int k = 0, j = 4 * g; k < 4 && j < nk; ++k, ++j) {
+          const float pj = pr[j] * inv, gm = ((k4 >> k) & 1u) ? gr[j] * scale : 0.f;
+          pr[j] = pj; gr[j] = gm;
+          c = fmaf(gm, pj, c);
+        }
+      }
+      for (int m = 1; m < 8; m <<= 1) c += __shfl_xor(c, m, 8);
+      gi = 0;
+      for (int g = sub; 4 * g < nk; g += 8, ++gi) {
+        const uint32_t k4 = kept >> (4 * gi);
+        for (int k = 0, j = 4 * g; k < 4 && j < nk; ++k, ++j) {
+          gr[j] = pr[j] * (gr[j] - c);
+          pr[j] = ((k4 >> k) & 1u) ? pr[j] * scale : 0.f;
+        }
+      }
+    } else {
+      for (int j = sub; j < nk; j += 8) { const float pj = pr[j] * inv; pr[j] = pj; c = fmaf(gr[j], pj, c); }
+      for (int m = 1; m < 8; m <<= 1) c += __shfl_xor(c, m, 8);
+      for (int j = sub; j < nk; j += 8) gr[j] = pr[j] * (gr[j] - c);
+    }
   }
 }
 
@@ -477,11 +505,13 @@ __device__ __forceinline__ void attn_store16(float* dst, int l16, const float (&
 }
 
 // One block per (sequence, head). Everything of the head lives in LDS: Q, K, V, dO [Ls][65], P and dS [Ls][Ls + 1].
+// DROP: the probabilities were dropped out in the forward (self_attn_drop_fwd_kernel); the same mask is drawn again here
+template <bool DROP>
 __global__ __launch_bounds__(256) void self_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dO,
                                                              const int32_t* __restrict__ mask, const float* __restrict__ rel_bias,
                                                              const int32_t* __restrict__ bucket, float* __restrict__ dqkv,
                                                              float* __restrict__ dbias_part, int S, int Ls, int H, int buckets,
-                                                             int causal) {
+                                                             int causal, DropAttn da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int s = blockIdx.x / H, h = blockIdx.x - s * H, inner = H * DKV, ld = 3 * inner, tid = threadIdx.x;
   const int PL = Ls + 1, nd = causal ? Ls : 2 * Ls - 1;
@@ -511,7 +541,9 @@ __global__ __launch_bounds__(256) void self_attn_bwd_kernel(const float* __restr
                  [&](int i, int j) { return causal ? (j <= i) : (mk[j] != 0); },
                  [&](int i, int j) { return Bs[bk[causal ? i - j : j - i + Ls - 1]]; });
   __syncthreads();
-  attn_softmax_ds(Ps, Gs, Ls, Ls, PL);
+  if constexpr (DROP)
+    attn_softmax_ds<true>(Ps, Gs, Ls, Ls, PL, [&](int i, int g) { return drop_keep4_attn(da.key, da.site, (uint32_t)s, h, i, g); }, da.key.scale);
+  else attn_softmax_ds(Ps, Gs, Ls, Ls, PL);
   __syncthreads();
   {  // dQ_i = sum_j dS_ij K_j ; dK_j = sum_i dS_ij Q_i ; dV_j = sum_i P_ij dO_i — two rows per thread
     const int hr = (Ls + 1) >> 1, l16 = tid & 15;
@@ -565,8 +597,16 @@ __global__ __launch_bounds__(512) void bias_reduce_kernel(const float* __restric
 
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
-                                hipStream_t s) {
+                                hipStream_t s, const DropAttn* drop) {
   const AttnLaunch p = plan_self_attn_bwd(SelfAttnBwdIn{S, Ls, H, buckets});
+  if (drop) {   // dropped-out probabilities: the VALU kernel at every length (the MFMA plan knows no mask)
+    const size_t smem = self_attn_bwd_smem(Ls, buckets);
+    if (p.invalid || smem > 160 * 1024 || Ls > 256) return hipErrorInvalidValue;   // (a lane carries the keep bits of <= 32 keys)
+    hipLaunchKernelGGL(self_attn_bwd_kernel<true>, dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S,
+                       Ls, H, buckets, causal, *drop);
+    hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
+    return hipGetLastError();
+  }
   switch (p.kernel) {
     case ATTN_TRAIN_BWD_MFMA: {   // attn_mfma.hip
       const hipError_t e = run_self_attn_bwd_mfma(p, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, s);
@@ -574,8 +614,8 @@ hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t
       break;
     }
     case ATTN_TRAIN_BWD_VALU:
-      hipLaunchKernelGGL(self_attn_bwd_kernel, dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S,
-                         Ls, H, buckets, causal);
+      hipLaunchKernelGGL(self_attn_bwd_kernel<false>, dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket, dqkv,
+                         dbias_part, S, Ls, H, buckets, causal, DropAttn{});
       break;
     default: return hipErrorInvalidValue;
   }
@@ -587,10 +627,13 @@ hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t
 // keys. q: [bz*n, inner]; K/V of this layer: rows (query, j) at xk/xv + (query*Lq + j) * xld; dO: [bz*n, inner].
 // Outputs dq [bz*n, inner] and dK/dV into dxk/dxv (same layout as xk/xv): every (query, head) block owns its rows
 // and columns, so there is no accumulation across blocks.
+// DROP: as in self_attn_bwd_kernel; row r of the query is position r % da.L of decoder sequence query * (n / da.L) + r / da.L
+template <bool DROP>
 __global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ xk,
                                                               const float* __restrict__ xv, int xld, const int32_t* __restrict__ mask,
                                                               const float* __restrict__ dO, float* __restrict__ dq,
-                                                              float* __restrict__ dxk, float* __restrict__ dxv, int n, int Lq, int H) {
+                                                              float* __restrict__ dxk, float* __restrict__ dxv, int n, int Lq, int H,
+                                                              DropAttn da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int qi = blockIdx.x / H, h = blockIdx.x - qi * H, inner = H * DKV, tid = threadIdx.x;
   const int PL = Lq + 1;
@@ -615,7 +658,15 @@ __global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __rest
   __syncthreads();
   attn_scores_dp(Qs, Ds, Ks, Vs, n, Lq, Ps, Gs, PL, [&](int, int j) { return mk[j] != 0; }, [](int, int) { return 0.f; });
   __syncthreads();
-  attn_softmax_ds(Ps, Gs, n, Lq, PL);
+  if constexpr (DROP) {
+    const int docs = n / da.L;
+    attn_softmax_ds<true>(Ps, Gs, n, Lq, PL, [&](int r, int g) {
+      const int doc = r / da.L;
+      return drop_keep4_attn(da.key, da.site, (uint32_t)(qi * docs + doc), h, r - doc * da.L, g);
+    }, da.key.scale);
+  } else {
+    attn_softmax_ds(Ps, Gs, n, Lq, PL);
+  }
   __syncthreads();
   const int l16 = tid & 15;
   {  // dq_i = sum_j dS_ij K_j
@@ -647,12 +698,217 @@ size_t cross_attn_bwd_smem(int n, int Lq) {
 }
 
 hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, const float* dO,
-                                 float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s) {
+                                 float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s, const DropAttn* drop) {
   const size_t smem = cross_attn_bwd_smem(n, Lq);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
   // (an fp32-MFMA version — one wave per (query, head), dK / dV accumulated over the row tiles in the matrix cores — measured
   // 91 us against this kernel's 88: one wave per SIMD by its 33 KB of strips; removed)
-  hipLaunchKernelGGL(cross_attn_bwd_kernel, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H);
+  if (drop) {
+    if (drop->L < 1 || n % drop->L || Lq > 256) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cross_attn_bwd_kernel<true>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H, *drop);
+  } else {
+    hipLaunchKernelGGL(cross_attn_bwd_kernel<false>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H,
+                       DropAttn{});
+  }
+  return hipGetLastError();
+}
+
+// ---- dropout (rpr_set_train_dropout; dropout.h) ---------------------------------------------------------------------------
+// Training-only attention forward with dropped-out probabilities, in the arithmetic and the LDS layout of the two backward
+// kernels above (which draw the same mask again): exact fp32 scores, row softmax, P * mul, then O = P V. The inference
+// attention kernels the training forward launches at rate 0 are not touched by any of this.
+// Ps[i][j] = softmax_j(score_ij) * (kept ? scale : 0); keep4(i, g) = the keep bits of keys 4 g .. 4 g + 3 (one Philox block)
+template <class OK, class BIAS, class KEEP4>
+__device__ __forceinline__ void attn_probs_drop(const float* Qs, const float* Ks, int nq, int nk, float* Ps, int PL, OK ok, BIAS bias,
+                                                KEEP4 keep4, float scale) {
+  for (int p = threadIdx.x; p < nq * nk; p += 256) {
+    const int i = p / nk, j = p - i * nk;
+    const float *qr = Qs + i * AST, *kr = Ks + j * AST;
+    float sc = 0.f;
+#pragma unroll 8
+    for (int d = 0; d < DKV; ++d) sc = fmaf(qr[d], kr[d], sc);
+    Ps[i * PL + j] = ok(i, j) ? sc + bias(i, j) : -INFINITY;
+  }
+  __syncthreads();
+  const int sub = threadIdx.x & 7;
+  for (int i = threadIdx.x >> 3; i < nq; i += 32) {
+    float* pr = Ps + i * PL;
+    float mx = -INFINITY;
+    for (int j = sub; j < nk; j += 8) mx = fmaxf(mx, pr[j]);
+    for (int m = 1; m < 8; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 8));
+    float sum = 0.f;
+    for (int j = sub; j < nk; j += 8) { const float e = (pr[j] == -INFINITY) ? 0.f : expf(pr[j] - mx); pr[j] = e; sum += e; }
+    for (int m = 1; m < 8; m <<= 1) sum += __shfl_xor(sum, m, 8);
+    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+    for (int g = sub; 4 * g < nk; g += 8) {
+      const uint32_t k4 = keep4(i, g);
+      for (int k = 0, j = 4 * g; k < 4 && j < nk; ++k, ++j) pr[j] = ((k4 >> k) & 1u) ? pr[j] * inv * scale : 0.f;
+    }
+  }
+  __syncthreads();
+}
+
+// block per (sequence, head); qkv [S * Ls][3 inner], out [S * Ls][inner]; LDS carved like self_attn_bwd_kernel's
+__global__ __launch_bounds__(256) void self_attn_drop_fwd_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ mask,
+                                                                  const float* __restrict__ rel_bias, const int32_t* __restrict__ bucket,
+                                                                  float* __restrict__ out, int Ls, int H, int buckets, int causal,
+                                                                  DropAttn da) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int s = blockIdx.x / H, h = blockIdx.x - s * H, inner = H * DKV, ld = 3 * inner, tid = threadIdx.x;
+  const int PL = Ls + 1, nd = causal ? Ls : 2 * Ls - 1;
+  float* Qs = sm;
+  float* Ks = Qs + Ls * AST;
+  float* Vs = Ks + Ls * AST;
+  float* Ps = Vs + Ls * AST;            // [Ls][PL]
+  float* Bs = Ps + Ls * PL;             // [64]
+  int* bk = reinterpret_cast<int*>(Bs + 64);   // [nd]
+  int* mk = bk + 2 * Ls;                // [Ls]
+  const size_t row0 = (size_t)s * Ls;
+  for (int i = tid; i < Ls * 16; i += 256) {
+    const int r = i >> 4, c = (i & 15) * 4;
+    const float* base = qkv + (row0 + r) * ld + h * DKV + c;
+    stage_row4(Qs + r * AST + c, base); stage_row4(Ks + r * AST + c, base + inner); stage_row4(Vs + r * AST + c, base + 2 * inner);
+  }
+  if (tid < buckets) Bs[tid] = rel_bias[tid * H + h];
+  for (int t = tid; t < nd; t += 256) bk[t] = causal ? bucket[t] : bucket[t - (Ls - 1) + (MAX_LQ - 1)];
+  for (int j = tid; j < Ls; j += 256) mk[j] = (causal || mask[row0 + j] != 0) ? 1 : 0;
+  __syncthreads();
+  attn_probs_drop(Qs, Ks, Ls, Ls, Ps, PL, [&](int i, int j) { return causal ? (j <= i) : (mk[j] != 0); },
+                  [&](int i, int j) { return Bs[bk[causal ? i - j : j - i + Ls - 1]]; },
+                  [&](int i, int g) { return drop_keep4_attn(da.key, da.site, (uint32_t)s, h, i, g); }, da.key.scale);
+  const int hr = (Ls + 1) >> 1, l16 = tid & 15;
+  for (int t = tid >> 4; t < hr; t += 16) {
+    const int r0 = t, r1 = (t + hr < Ls) ? t + hr : t;
+    float o0[4] = {}, o1[4] = {};
+    attn_rows_times(Ps, PL, r0, r1, Vs, Ls, l16, o0, o1);
+    attn_store16(out + (row0 + r0) * inner + h * DKV, l16, o0);
+    if (r1 != r0) attn_store16(out + (row0 + r1) * inner + h * DKV, l16, o1);
+  }
+}
+
+// block per (query, head): the n = docs * L decoder rows of the query against its Lq encoder keys (layouts: cross_attn_bwd_kernel)
+__global__ __launch_bounds__(256) void cross_attn_drop_fwd_kernel(const float* __restrict__ q, const float* __restrict__ xk,
+                                                                   const float* __restrict__ xv, int xld, const int32_t* __restrict__ mask,
+                                                                   float* __restrict__ out, int n, int Lq, int H, DropAttn da) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int qi = blockIdx.x / H, h = blockIdx.x - qi * H, inner = H * DKV, tid = threadIdx.x;
+  const int PL = Lq + 1, docs = n / da.L;
+  float* Qs = sm;                     // [n][AST]
+  float* Ks = Qs + n * AST;           // [Lq][AST]
+  float* Vs = Ks + Lq * AST;
+  float* Ps = Vs + Lq * AST;          // [n][PL]
+  int* mk = reinterpret_cast<int*>(Ps + n * PL);   // [Lq]
+  for (int i = tid; i < n * 16; i += 256) {
+    const int r = i >> 4, c = (i & 15) * 4;
+    stage_row4(Qs + r * AST + c, q + ((size_t)qi * n + r) * inner + h * DKV + c);
+  }
+  for (int i = tid; i < Lq * 16; i += 256) {
+    const int j = i >> 4, c = (i & 15) * 4;
+    const size_t o = ((size_t)qi * Lq + j) * xld + h * DKV + c;
+    stage_row4(Ks + j * AST + c, xk + o); stage_row4(Vs + j * AST + c, xv + o);
+  }
+  for (int j = tid; j < Lq; j += 256) mk[j] = mask[(size_t)qi * Lq + j];
+  __syncthreads();
+  attn_probs_drop(Qs, Ks, n, Lq, Ps, PL, [&](int, int j) { return mk[j] != 0; }, [](int, int) { return 0.f; }, [&](int r, int g) {
+    const int doc = r / da.L;
+    return drop_keep4_attn(da.key, da.site, (uint32_t)(qi * docs + doc), h, r - doc * da.L, g);
+  }, da.key.scale);
+  const int hr = (n + 1) >> 1, l16 = tid & 15;
+  for (int t = tid >> 4; t < hr; t += 16) {
+    const int r0 = t, r1 = (t + hr < n) ? t + hr : t;
+    float o0[4] = {}, o1[4] = {};
+    attn_rows_times(Ps, PL, r0, r1, Vs, Lq, l16, o0, o1);
+    attn_store16(out + ((size_t)qi * n + r0) * inner + h * DKV, l16, o0);
+    if (r1 != r0) attn_store16(out + ((size_t)qi * n + r1) * inner + h * DKV, l16, o1);
+  }
+}
+
+hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, const float* rel_bias, const int32_t* bucket, float* out,
+                                     int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s) {
+  const size_t smem = self_attn_bwd_smem(Ls, buckets);   // (the backward's carve holds this kernel's: the step was admitted by it)
+  if (smem > 160 * 1024 || buckets > 64 || Ls < 1 || Ls > MAX_LQ || (!causal && !mask)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(self_attn_drop_fwd_kernel, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets, causal,
+                     drop);
+  return hipGetLastError();
+}
+hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
+                                      int n, int Lq, int H, const DropAttn& drop, hipStream_t s) {
+  const size_t smem = cross_attn_bwd_smem(n, Lq);
+  if (smem > 160 * 1024 || drop.L < 1 || n % drop.L) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cross_attn_drop_fwd_kernel, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
+  return hipGetLastError();
+}
+
+// out[r][f] = (resid ? resid[r][f] : 0) + x[r][f] * mul(sequence, position, f) for the rows r = sequence * n_pos + position of an
+// activation; x may be out (in place). One thread per four features: one Philox block. VEC: n_feat % 4 == 0 and 16-byte
+// aligned pointers (the launch decides)
+template <bool VEC>
+__global__ __launch_bounds__(256) void dropout_rows_kernel(const float* x, const float* resid, float* out, size_t rows, int n_pos,
+                                                            int n_feat, DropKey key, int site) {
+  const int nq = (n_feat + 3) >> 2;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * (size_t)nq) return;
+  const size_t r = idx / (size_t)nq, seq = r / (size_t)n_pos;
+  const int qd = (int)(idx - r * (size_t)nq), pos = (int)(r - seq * (size_t)n_pos);
+  const Draw4 d = drop_draws_act(key, site, (uint32_t)seq, pos, qd);
+  const size_t o = r * (size_t)n_feat + 4 * (size_t)qd;
+  if constexpr (VEC) {
+    const float4 v = *reinterpret_cast<const float4*>(x + o);
+    float4 y = make_float4(d.w[0] < key.thr ? 0.f : v.x * key.scale, d.w[1] < key.thr ? 0.f : v.y * key.scale,
+                           d.w[2] < key.thr ? 0.f : v.z * key.scale, d.w[3] < key.thr ? 0.f : v.w * key.scale);
+    if (resid) { const float4 b = *reinterpret_cast<const float4*>(resid + o); y.x += b.x; y.y += b.y; y.z += b.z; y.w += b.w; }
+    *reinterpret_cast<float4*>(out + o) = y;
+  } else {
+    const int nf = min(4, n_feat - 4 * qd);
+    for (int k = 0; k < nf; ++k) {
+      const float y = d.w[k] < key.thr ? 0.f : x[o + k] * key.scale;
+      out[o + k] = resid ? resid[o + k] + y : y;
+    }
+  }
+}
+hipError_t launch_dropout_rows(const float* x, const float* resid, float* out, size_t n_seq, int n_pos, int n_feat, const DropKey& key,
+                               int site, hipStream_t s) {
+  if (n_seq == 0 || n_pos <= 0 || n_feat <= 0) return hipSuccess;
+  if (n_pos > 65536 || n_seq > 0xffffffffull || site < 0 || site > 0xffff) return hipErrorInvalidValue;
+  const size_t rows = n_seq * (size_t)n_pos, blocks = (rows * (size_t)((n_feat + 3) >> 2) + 255) / 256;
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  const bool vec = (n_feat & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(resid)) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(dropout_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, resid, out, rows, n_pos, n_feat, key, site);
+  else hipLaunchKernelGGL(dropout_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, x, resid, out, rows, n_pos, n_feat, key, site);
+  return hipGetLastError();
+}
+
+// The gold-code scores when the decoder's output is dropped out: h = dropout(final norm) was written by its own launches, so
+// score_r = <h_r, E_r> (E_r = out_embeds row out_idx[r]) and backwards dh_r = dscore_r E_r, de_r = dscore_r h_r (dscores null:
+// the forward). One wave per row.
+__global__ __launch_bounds__(256) void gold_rowdot_kernel(const float* __restrict__ hd, const float* __restrict__ out_embeds,
+                                                           const int32_t* __restrict__ out_idx, float* __restrict__ scores,
+                                                           const float* __restrict__ dscores, float* __restrict__ dh,
+                                                           float* __restrict__ de, int rows, int d) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float4* hr = reinterpret_cast<const float4*>(hd + (size_t)row * d);
+  const float4* er = reinterpret_cast<const float4*>(out_embeds + (size_t)out_idx[row] * d);
+  const int n4 = d >> 2;
+  if (!dscores) {
+    float acc = 0.f;
+    for (int k = lane; k < n4; k += 64) { const float4 v = hr[k], e = er[k]; acc += (v.x * e.x + v.y * e.y) + (v.z * e.z + v.w * e.w); }
+    acc = wave_sum_f(acc);
+    if (lane == 0) scores[row] = acc;
+    return;
+  }
+  const float g = dscores[row];
+  for (int k = lane; k < n4; k += 64) {
+    const float4 v = hr[k], e = er[k];
+    reinterpret_cast<float4*>(de + (size_t)row * d)[k] = make_float4(g * v.x, g * v.y, g * v.z, g * v.w);
+    reinterpret_cast<float4*>(dh + (size_t)row * d)[k] = make_float4(g * e.x, g * e.y, g * e.z, g * e.w);
+  }
+}
+hipError_t launch_gold_rowdot(const float* hd, const float* out_embeds, const int32_t* out_idx, float* scores, const float* dscores,
+                              float* dh, float* de, int rows, int d, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (d & 3) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gold_rowdot_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, hd, out_embeds, out_idx, scores, dscores, dh, de, rows, d);
   return hipGetLastError();
 }
 
@@ -1366,13 +1622,18 @@ hipError_t launch_s2s_head_bwd(const float* hF, const float* E, const float* dlo
 }
 
 hipError_t init_train_kernel_attributes() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
+  for (const void* k : {reinterpret_cast<const void*>(self_attn_bwd_kernel<true>), reinterpret_cast<const void*>(cross_attn_bwd_kernel<true>),
+                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel)}) {
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+  }
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(rmsnorm_bf16_T_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(s2s_head_fwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 }  // namespace rpr

@@ -816,10 +816,16 @@ def lngknp_forward(model: DeviceModel, input_ids: torch.Tensor, attention_mask: 
 # ---- training step of the ranking fine-tune: flat gradient / optimizer buffers -----------------------
 class TrainState:
     """Flat fp32 buffers of one model replica: gradients and the two AdamW moments, laid out as ``rpr_param_info``
-    says (the tensors of ``DeviceModel`` in a fixed order). ``grads`` is what data-parallel ranks all-reduce."""
+    says (the tensors of ``DeviceModel`` in a fixed order). ``grads`` is what data-parallel ranks all-reduce.
 
-    def __init__(self, model: DeviceModel):
+    ``dropout_rate`` / ``dropout_seed``: the dropout the backward entry points apply (``rpr_set_train_dropout``; 0 = off, the
+    default). The mask is a stateless function of (seed, global step, site, coordinates): the global step is ``step`` — the
+    optimizer steps taken so far, restored with a checkpoint — unless a call names another, so a resumed run draws the masks
+    it would have drawn and no RNG state is kept anywhere."""
+
+    def __init__(self, model: DeviceModel, dropout_rate: float = 0.0, dropout_seed: int = 0):
         self.model = model
+        self.set_dropout(dropout_rate, dropout_seed)
         lib, h = model.ctx.lib, model.handle
         self.total = int(lib.rpr_param_total(h))
         n = int(lib.rpr_param_count(h))
@@ -834,6 +840,18 @@ class TrainState:
         self.exp_avg_sq = torch.zeros(self.total, dtype=torch.float32, device=dev)
         self.step = 0
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def set_dropout(self, rate: float, seed: int = 0):
+        if not 0.0 <= float(rate) < 1.0:
+            raise ValueError(f"dropout rate {rate!r} outside [0, 1)")
+        self.dropout_rate, self.dropout_seed = float(rate), int(seed) & (2 ** 64 - 1)
+
+    def apply_dropout(self, global_step: Optional[int] = None):
+        """Tell the context what the next backward call applies: always called by the backward wrappers, so a state at rate 0
+        also switches off what another state of the same context had set."""
+        ctx = self.model.ctx
+        step = self.step if global_step is None else int(global_step)
+        check(ctx.lib.rpr_set_train_dropout(ctx.handle, self.dropout_rate, self.dropout_seed, step), "rpr_set_train_dropout")
 
     def named_grads(self) -> Dict[str, torch.Tensor]:
         """Gradients under the reference checkpoint's tensor names (q/k/v, the cross k/v and the codebooks un-stacked)."""
@@ -969,12 +987,15 @@ class GradExchange:
 
 
 def lngknp_backward(model: DeviceModel, state: TrainState, input_ids, attention_mask, doc_codes, teacher_pos, teacher_neg,
-                    prefix_lens: Sequence[int], exchange: Optional[GradExchange] = None) -> torch.Tensor:
+                    prefix_lens: Sequence[int], exchange: Optional[GradExchange] = None,
+                    global_step: Optional[int] = None) -> torch.Tensor:
     """Forward + backward of the sum of the margin-MSE losses (``rpr_lngknp_backward``): fills ``state.grads`` and
     returns the losses ``[n_prefix]`` (device tensor). Asynchronous on the current stream. With ``exchange`` the
     gradient all-reduce of every bucket is enqueued while the backward is still running (``GradExchange``); the caller
-    then calls ``exchange.finish()`` before the optimizer step."""
+    then calls ``exchange.finish()`` before the optimizer step. Dropout: what ``state`` says (``TrainState.set_dropout``) at
+    ``global_step`` (default: ``state.step``)."""
     ctx = model.ctx
+    state.apply_dropout(global_step)
     dev = ctx.device
     ids = input_ids.to(device=dev, dtype=torch.int32).contiguous()
     mask = attention_mask.to(device=dev, dtype=torch.int32).contiguous()
@@ -1030,10 +1051,12 @@ def seq2seq_forward(model: DeviceModel, input_ids: torch.Tensor, attention_mask:
 
 
 def seq2seq_backward(model: DeviceModel, state: TrainState, input_ids, attention_mask, labels,
-                     exchange: Optional[GradExchange] = None) -> torch.Tensor:
+                     exchange: Optional[GradExchange] = None, global_step: Optional[int] = None) -> torch.Tensor:
     """Forward + backward of the seq2seq cross-entropy (``rpr_seq2seq_backward``): fills ``state.grads`` and returns the loss
-    ``[1]`` (device tensor). With ``exchange`` the gradient buckets are handed over as in :func:`lngknp_backward`."""
+    ``[1]`` (device tensor). With ``exchange`` the gradient buckets are handed over, and dropout is applied, as in
+    :func:`lngknp_backward`."""
     ctx = model.ctx
+    state.apply_dropout(global_step)
     ids, mask, lab, bz, Lq, L = _s2s_args(model, input_ids, attention_mask, labels)
     loss = torch.empty((1,), dtype=torch.float32, device=ctx.device)
     if exchange is not None and exchange.active:
@@ -1049,18 +1072,22 @@ def seq2seq_backward(model: DeviceModel, state: TrainState, input_ids, attention
 
 
 def seq2seq_train_step(model: DeviceModel, state: TrainState, input_ids, attention_mask, labels, lr: float, betas=(0.9, 0.999),
-                       eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 1.0) -> torch.Tensor:
+                       eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 1.0,
+                       dropout_rate: Optional[float] = None, dropout_seed: Optional[int] = None,
+                       global_step: Optional[int] = None) -> torch.Tensor:
     """:func:`train_step` for the seq2seq cross-entropy: backward with the gradient exchange (bucketed and overlapped unless
     ``RPR_GRAD_OVERLAP=0``), clip_grad_norm_, AdamW. Returns the loss ``[1]`` before the update."""
     import os
+    if dropout_rate is not None:
+        state.set_dropout(dropout_rate, state.dropout_seed if dropout_seed is None else dropout_seed)
     if os.environ.get("RPR_GRAD_OVERLAP", "1") == "0":
-        loss = seq2seq_backward(model, state, input_ids, attention_mask, labels)
+        loss = seq2seq_backward(model, state, input_ids, attention_mask, labels, global_step=global_step)
         allreduce_grads(state)
     else:
         ex = getattr(state, "_exchange", None)
         if ex is None or ex.grads is not state.grads:
             ex = state._exchange = GradExchange(state.grads)
-        loss = seq2seq_backward(model, state, input_ids, attention_mask, labels, exchange=ex)
+        loss = seq2seq_backward(model, state, input_ids, attention_mask, labels, exchange=ex, global_step=global_step)
         ex.finish()
     adamw_step(model, state, lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     return loss
@@ -1091,20 +1118,26 @@ def allreduce_mode() -> str:
 
 def train_step(model: DeviceModel, state: TrainState, input_ids, attention_mask, doc_codes, teacher_pos, teacher_neg,
                prefix_lens: Sequence[int], lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-               max_grad_norm: float = 1.0) -> torch.Tensor:
+               max_grad_norm: float = 1.0, dropout_rate: Optional[float] = None, dropout_seed: Optional[int] = None,
+               global_step: Optional[int] = None) -> torch.Tensor:
     """One optimisation step as the reference's trainer performs it (tasks/trainer.py:203-275 + HF Trainer defaults):
     forward + backward, gradient all-reduce across the data-parallel ranks — bucketed and overlapped with the backward
-    (``RPR_GRAD_OVERLAP=0``: one serial pass afterwards) —, clip_grad_norm_, AdamW. Returns the losses before the update."""
+    (``RPR_GRAD_OVERLAP=0``: one serial pass afterwards) —, clip_grad_norm_, AdamW. Returns the losses before the update.
+    ``dropout_rate`` / ``dropout_seed`` (default: what ``state`` holds, off unless set) and ``global_step`` (default:
+    ``state.step``, the optimizer steps taken so far) select the dropout masks of this step (``rpr_set_train_dropout``)."""
     import os
+    if dropout_rate is not None:
+        state.set_dropout(dropout_rate, state.dropout_seed if dropout_seed is None else dropout_seed)
     if os.environ.get("RPR_GRAD_OVERLAP", "1") == "0":
-        losses = lngknp_backward(model, state, input_ids, attention_mask, doc_codes, teacher_pos, teacher_neg, prefix_lens)
+        losses = lngknp_backward(model, state, input_ids, attention_mask, doc_codes, teacher_pos, teacher_neg, prefix_lens,
+                                 global_step=global_step)
         allreduce_grads(state)
     else:
         ex = getattr(state, "_exchange", None)
         if ex is None or ex.grads is not state.grads:
             ex = state._exchange = GradExchange(state.grads)
         losses = lngknp_backward(model, state, input_ids, attention_mask, doc_codes, teacher_pos, teacher_neg, prefix_lens,
-                                 exchange=ex)
+                                 exchange=ex, global_step=global_step)
         ex.finish()
     adamw_step(model, state, lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     return losses

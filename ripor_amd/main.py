@@ -46,9 +46,27 @@ def get_args(argv=None):
     ap.add_argument("--task_names", default=None, help='JSON list, e.g. ["rank","rank_4"]')
     ap.add_argument("--ln_to_weight", default=None, help="JSON dict of task weights (only 1.0 is built)")
     ap.add_argument("--use_fp16", action="store_true", help="bf16 GEMM operands, like the reference (main.py:152 bf16=args.use_fp16)")
+    ap.add_argument("--dropout", default="off",
+                    help="off | config | <rate in [0, 1)>: dropout of the training step. off (default): evaluation arithmetic; config: "
+                         "the checkpoint's dropout_rate, what the reference trains with (model.train()). Deviation from the reference: "
+                         "the encoder runs once per query, so the positive and the negative pass share ONE encoder mask (the "
+                         "reference draws two); decoder-side masks are independent per document")
     ap.add_argument("--wandb_project_name", default=None, help="accepted and ignored (no network)")
     ap.add_argument("--local_rank", type=int, default=-1)
     return ap.parse_args(argv)
+
+
+def resolve_dropout(flag: str, config_rate: float, log=print) -> float:
+    """--dropout=off|config|<float> against the checkpoint's dropout_rate -> the rate the trainer applies."""
+    if flag == "off":
+        if config_rate:
+            log(f"--dropout=off: the checkpoint's dropout_rate {config_rate} is NOT applied (the reference trains with it; "
+                f"--dropout=config applies it)")
+        return 0.0
+    rate = float(config_rate) if flag == "config" else float(flag)
+    if not 0.0 <= rate < 1.0:
+        raise SystemExit(f"--dropout {flag}: the rate must be in [0, 1)")
+    return rate
 
 
 def main(argv=None):
@@ -86,18 +104,21 @@ def main(argv=None):
         collator = LngKnpMarginMSEforT5SeqAQCollator(args.model_name_or_path, max_length=args.max_length)
         model = T5SeqAQEncoderForLngKnpMarginMSE.from_pretrained(args.resume_from_checkpoint or args.pretrained_path)
     model.to(local_rank)
+    dropout_rate = resolve_dropout(args.dropout, float(getattr(model.config, "dropout_rate", 0.0)),
+                                   log=print if local_rank == 0 else (lambda s: None))
     targs = LngKnpTrainingArgs(output_dir=args.output_dir, learning_rate=args.learning_rate, warmup_ratio=args.warmup_ratio,
                                per_device_train_batch_size=args.per_device_train_batch_size, num_train_epochs=args.epochs,
                                max_steps=args.max_steps, logging_steps=args.logging_steps, save_steps=args.save_steps,
                                bf16=args.use_fp16, task_names=json.loads(args.task_names) if args.task_names else None,
-                               ln_to_weight=json.loads(args.ln_to_weight) if args.ln_to_weight else {})
+                               ln_to_weight=json.loads(args.ln_to_weight) if args.ln_to_weight else {},
+                               dropout_rate=dropout_rate)
     os.makedirs(args.output_dir, exist_ok=True)
     trainer = LngKnpTrainer(model, dataset, collator, targs)
     if trainer.rank == 0:
         what = "seq2seq docid step" if seq2seq else "lng_knp fine-tune"
         print(f"{args.loss_type} ({what}): {len(dataset)} examples, {trainer.world} rank(s) x {targs.per_device_train_batch_size}, "
               f"{trainer.max_steps} steps ({trainer.warmup_steps} warm-up), lr {targs.learning_rate}, "
-              f"{'bf16' if targs.bf16 else 'fp32-equivalent'} GEMMs")
+              f"{'bf16' if targs.bf16 else 'fp32-equivalent'} GEMMs, dropout {targs.dropout_rate or 'off'}")
     trainer.train(resume_from_checkpoint=args.resume_from_checkpoint or None)
     trainer.save_torch_model_and_tokenizer(collator.tokenizer)
     if dist.is_initialized():

@@ -30,7 +30,7 @@ class T5forDocIDConfig:
                  d_kv: int = 64, d_ff: int = 3072, num_layers: int = 12, num_decoder_layers: Optional[int] = None,
                  num_heads: int = 12, relative_attention_num_buckets: int = 32,
                  relative_attention_max_distance: int = 128, layer_norm_epsilon: float = 1e-6,
-                 feed_forward_proj: str = "relu", **kwargs):
+                 feed_forward_proj: str = "relu", dropout_rate: float = 0.1, **kwargs):
         self.decoder_vocab_sizes = list(decoder_vocab_sizes) if decoder_vocab_sizes is not None else [256] * 32
         self.decoding = decoding
         self.decoder_start_token_path = decoder_start_token_path
@@ -45,6 +45,9 @@ class T5forDocIDConfig:
         self.relative_attention_max_distance = relative_attention_max_distance
         self.layer_norm_epsilon = layer_norm_epsilon
         self.feed_forward_proj = feed_forward_proj
+        # T5Config.dropout_rate (HF default 0.1): what the reference trains with (model.train()); unused by inference, applied by
+        # the training steps only on request (main.py --dropout=config)
+        self.dropout_rate = float(dropout_rate)
         self.tie_word_embeddings = False
         self.max_decoder_length = len(self.decoder_vocab_sizes)
         self.extra = dict(kwargs)
@@ -354,15 +357,18 @@ class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
                                    pos_q["attention_mask"], codes, tp, tn, prefix_lens)
         return {n: losses[i] for i, n in enumerate(names)}
 
-    def training_step(self, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **inputs):
+    def training_step(self, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, dropout_rate=None,
+                      dropout_seed=None, global_step=None, **inputs):
         """One optimisation step as the reference's trainer performs it: backward with the gradient all-reduce across the
         data-parallel ranks overlapped (RCCL when torch.distributed is initialised; engine.GradExchange), clip_grad_norm_,
-        AdamW — weights updated in place on the device. Returns the task losses of the batch (before the update)."""
+        AdamW — weights updated in place on the device. Returns the task losses of the batch (before the update).
+        ``dropout_rate`` / ``dropout_seed`` / ``global_step``: the dropout of this step (engine.train_step; off by default)."""
         from .. import engine as E
         pos_q, codes, tp, tn, prefix_lens, names = self._batch(inputs)
         losses = E.train_step(self.base_model.engine_model(), self.train_state(), pos_q["input_ids"], pos_q["attention_mask"],
                               codes, tp, tn, prefix_lens, lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                              max_grad_norm=max_grad_norm)
+                              max_grad_norm=max_grad_norm, dropout_rate=dropout_rate, dropout_seed=dropout_seed,
+                              global_step=global_step)
         losses = {n: losses[i] for i, n in enumerate(names)}
         return losses
 
@@ -415,12 +421,14 @@ class T5SeqAQEncoderForSeq2Seq(T5SeqAQEncoder):
         loss = E.seq2seq_backward(self.base_model.engine_model(), self.train_state(), ids, mask, labels)
         return {"rank": loss[0]}
 
-    def training_step(self, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **inputs):
+    def training_step(self, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, dropout_rate=None,
+                      dropout_seed=None, global_step=None, **inputs):
         """One optimisation step (same contract as ``T5SeqAQEncoderForLngKnpMarginMSE.training_step``): backward with the
         data-parallel gradient exchange overlapped, clip_grad_norm_, AdamW in place on the device. Returns ``{"rank": loss}``
         of the batch before the update."""
         from .. import engine as E
         ids, mask, labels = self._batch(inputs)
         loss = E.seq2seq_train_step(self.base_model.engine_model(), self.train_state(), ids, mask, labels, lr, betas=betas, eps=eps,
-                                    weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+                                    weight_decay=weight_decay, max_grad_norm=max_grad_norm, dropout_rate=dropout_rate,
+                                    dropout_seed=dropout_seed, global_step=global_step)
         return {"rank": loss[0]}

@@ -34,6 +34,15 @@ def get_warmup_steps(max_steps: int, warmup_ratio: float, warmup_steps: int = 0)
     return warmup_steps if warmup_steps > 0 else math.ceil(max_steps * warmup_ratio)
 
 
+def dropout_key(seed: int, rank: int) -> int:
+    """The 64-bit dropout key of a rank: every rank of a data-parallel run draws its own masks (as every rank of the reference
+    has its own RNG stream), all from the run's ``seed``. splitmix64 of seed * 2^32 + rank."""
+    z = ((int(seed) & 0xFFFFFFFF) << 32 | (int(rank) & 0xFFFFFFFF)) + 0x9E3779B97F4A7C15 & (2 ** 64 - 1)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2 ** 64 - 1)
+    return z ^ (z >> 31)
+
+
 def linear_schedule_with_warmup(step: int, num_warmup_steps: int, num_training_steps: int) -> float:
     """Multiplier of the base learning rate at optimizer step ``step`` (0-based): HF ``get_linear_schedule_with_warmup``."""
     if step < num_warmup_steps:
@@ -61,6 +70,10 @@ class LngKnpTrainingArgs:
     adam_epsilon: float = 1e-8
     bf16: bool = False              # --use_fp16 in the reference's scripts means bf16 autocast (main.py:152); off unless asked, like
                                     # TrainingArguments.bf16 and main.py's flag
+    # dropout of the device step (rpr_set_train_dropout): 0 = off (evaluation arithmetic, the default); the reference trains
+    # with the checkpoint's dropout_rate (model.train(), tasks/trainer.py:221). The masks are a function of (dropout key,
+    # global optimizer step): nothing about them goes into a checkpoint
+    dropout_rate: float = 0.0
     task_names: Optional[List[str]] = None
     ln_to_weight: Dict[str, float] = field(default_factory=dict)
 
@@ -114,8 +127,12 @@ class LngKnpTrainer:
                     if self.global_step >= self.max_steps:
                         break
                     lr = self.lr_at(self.global_step)
+                    # dropout (off at rate 0: the call is today's): masks of (this rank's key, the global optimizer step), so a
+                    # resumed run goes on with the masks it would have drawn
+                    drop = dict(dropout_rate=a.dropout_rate, dropout_seed=dropout_key(a.seed, self.rank),
+                                global_step=self.global_step) if a.dropout_rate > 0 else {}
                     losses = self.model.training_step(lr=lr, max_grad_norm=a.max_grad_norm, betas=(a.adam_beta1, a.adam_beta2),
-                                                      eps=a.adam_epsilon, weight_decay=a.weight_decay, **batch)
+                                                      eps=a.adam_epsilon, weight_decay=a.weight_decay, **drop, **batch)
                     self.global_step += 1
                     window.append(losses)
                     if self.global_step % a.logging_steps == 0 or self.global_step == self.max_steps:
