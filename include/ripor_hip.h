@@ -289,6 +289,17 @@ int rpr_fork_depths(rpr_ctx* ctx, rpr_model* model, rpr_trie* trie, int32_t Q, i
  *   rpr_l0_table_bytes(ctx, model)   size of the model's table if the next search on this ctx may read it, else 0. */
 int rpr_set_l0_table(rpr_ctx* ctx, int32_t mode);
 int64_t rpr_l0_table_bytes(const rpr_ctx* ctx, const rpr_model* model);
+/* MFMA shape of the 256 x 256 split-precision GEMM kernel (RPR_PREC_F16X2): 0 = v_mfma_f32_32x32x16_f16 everywhere,
+ * 1 (default) = v_mfma_f32_16x16x32_f16 in the forced-tail passes of rpr_search / rpr_search_margins, which hold most of
+ * a large search's GEMM time. Same tiles, same three products per element; a K-tile's 32 columns are summed in another
+ * order, so the scores of forced sequences move in their last bits (<= 3e-5). The encoder, the sequential steps, the
+ * layer-0 table and the projection it replaces keep the 32x32x16 arithmetic and its bits, and with them every pruning
+ * decision of the steps; so do the training step, rpr_encode, the cross-encoder and the bf16 GEMMs. One pruning decision
+ * does see the tail pass's rounding on either shape: a query forced with extras (rpr_set_tail_extras) keeps the best
+ * num_beams of its num_beams + extras sequences by their tail scores, so a tie closer than that rounding may fall
+ * differently at 0 and at 1. */
+int rpr_set_gemm_mfma16(rpr_ctx* ctx, int32_t mode);
+int32_t rpr_gemm_mfma16(const rpr_ctx* ctx);
 /* HOST ONLY (no ctx, no GPU): the statistic the automatic fork depths come from. codes: [host] [N, Lc] in any order;
  * out_frac: [host] L + 1 doubles, out_frac[t] = share of the trie nodes at depth t (distinct t-prefixes) under which
  * exactly one distinct L-token sequence remains. A query whose B beams stand on random depth-t nodes is forced with
@@ -466,6 +477,27 @@ int rpr_op_linear(rpr_ctx* ctx, const float* A, const float* W, const float* res
  * n_products = 1..8: the grouped launch of the weight-gradient products (gemm_h2_pp_group_kernel, one K-loop per tile):
  * product i = rows [0, M - 256 i) of A against W, written to C + i * M * N (row stride N); residual and relu must be 0.
  * K % 64 == 0. Reference arithmetic: torch bf16 autocast matmul with fp32 accumulation (tasks/trainer.py:229). */
+/* Test hook: one RPR_PREC_F16X2 launch C = A[M,K] W[N,K]^T with one of the epilogues a search gives its projections, on the
+ * MFMA shape asked for (mfma16: 0 = 32x32x16, 1 = 16x16x32 where the launch takes the 256 x 256 kernel). All pointers [dev].
+ *   RPR_LIN_F32         out0 [M,N] = relu?(C) + resid (resid nullable)
+ *   RPR_LIN_X_PLANES    residual stream: resid [M,N] is split into out_planes ([2][M][N] f16, scale 1/16) first, then
+ *                       out_planes = planes(resid + C) in place and ssq_out[m] += 65536 * sum_n x[m,n]^2 (fixed point; the caller
+ *                       zeroes it)
+ *   RPR_LIN_FF_PLANES   out_planes = planes(relu(C)), scale 1/16
+ *   RPR_LIN_KV_SCATTER  columns [0, split_n) -> out0 [M, split_n]; the next two blocks of split_n columns -> out1 / out2 in
+ *                       the K/V-cache layout: element (m, n) at (m / rm_B) * (split_n / 64) * rm_B * 64 + (n / 64) * rm_B * 64 +
+ *                       (m % rm_B) * 64 + n % 64
+ *   RPR_LIN_FUSED_NORM  A = the un-normalised stream: out0[m, :] = C[m, :] * rsqrt(row_ssq[m] / (65536 K) + eps)
+ *   RPR_LIN_LIVE_ROWS   out0 rows [0, *m_dev) = C; rows from *m_dev on are not written */
+#define RPR_LIN_F32 0
+#define RPR_LIN_X_PLANES 1
+#define RPR_LIN_FF_PLANES 2
+#define RPR_LIN_KV_SCATTER 3
+#define RPR_LIN_FUSED_NORM 4
+#define RPR_LIN_LIVE_ROWS 5
+int rpr_op_linear_h2(rpr_ctx* ctx, const float* A, const float* W, int32_t M, int32_t N, int32_t K, int32_t mode, int32_t mfma16,
+                     int32_t relu, const float* resid, const uint64_t* row_ssq, float eps, const int32_t* m_dev, int32_t rm_B,
+                     int32_t split_n, float* out0, float* out1, float* out2, void* out_planes, uint64_t* ssq_out, void* stream);
 int rpr_op_linear_bf16(rpr_ctx* ctx, const float* A, const float* W, const float* residual, float* C,
                        int32_t M, int32_t N, int32_t K, int32_t relu, int32_t n_products, void* stream);
 /* out[rows,d] = w * x * rsqrt(mean(x^2) + eps) */

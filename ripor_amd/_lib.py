@@ -142,6 +142,8 @@ SIGNATURES = {
     "rpr_lane_split": (C.c_int32, [C.c_void_p]),
     "rpr_set_l0_table": (C.c_int, [C.c_void_p, C.c_int32]),
     "rpr_l0_table_bytes": (C.c_int64, [C.c_void_p, C.c_void_p]),
+    "rpr_set_gemm_mfma16": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rpr_gemm_mfma16": (C.c_int32, [C.c_void_p]),
     "rpr_set_forced_tail": (C.c_int, [C.c_void_p, C.c_int32]),
     "rpr_forced_tail": (C.c_int32, [C.c_void_p]),
     "rpr_set_fork_depths": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
@@ -156,6 +158,9 @@ SIGNATURES = {
     "rpr_last_fork_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rpr_op_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int32, C.c_void_p]),
+    "rpr_op_linear_h2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rpr_op_linear_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rpr_op_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,

@@ -766,6 +766,13 @@ int rpr_set_l0_table(rpr_ctx* c, int32_t mode) {
 }
 int64_t rpr_l0_table_bytes(const rpr_ctx* c, const rpr_model* m) { return c && m && m->l0_ready(c) ? (int64_t)m->l0_bytes() : 0; }
 
+int rpr_set_gemm_mfma16(rpr_ctx* c, int32_t mode) {
+  RPR_REQUIRE(c && (mode == 0 || mode == 1), "mode must be 0 (32x32x16 everywhere) or 1 (16x16x32 in the tail passes of a search)");
+  c->gemm_mfma16 = mode;
+  return RPR_OK;
+}
+int32_t rpr_gemm_mfma16(const rpr_ctx* c) { return c ? c->gemm_mfma16 : -1; }
+
 int rpr_set_tail_extras(rpr_ctx* c, int32_t mode) {
   RPR_REQUIRE(c && mode >= -1 && mode <= 31, "mode must be -1 (automatic), 0 (off) or a budget of 1..31 extra sequences per query");
   c->tail_extras = mode;
@@ -922,6 +929,54 @@ int rpr_op_linear(rpr_ctx* c, const float* A, const float* W, const float* resid
   }
   linear(Ln, {A, At.as<__half>(), (size_t)M * K, K, 1.0f}, {W, Wt.as<__half>(), N, K}, M, out_f32(C, N, N, residual, relu));
   if (At.p) RPR_HIP(hipStreamSynchronize(s));   // the temporaries are freed when this scope ends
+  return Ln.err;
+}
+
+// Test hook: ONE split-precision launch with the epilogues a search gives it (passes.hip), on either MFMA shape of the 256x256 kernel.
+int rpr_op_linear_h2(rpr_ctx* c, const float* A, const float* W, int32_t M, int32_t N, int32_t K, int32_t mode, int32_t mfma16, int32_t relu,
+                     const float* resid, const uint64_t* row_ssq, float eps, const int32_t* m_dev, int32_t rm_B, int32_t split_n,
+                     float* out0, float* out1, float* out2, void* out_planes, uint64_t* ssq_out, void* stream) {
+  RPR_REQUIRE(c && A && W, "NULL argument");
+  RPR_REQUIRE(M >= 1 && N >= 32 && N % 32 == 0 && K >= 32 && K % 32 == 0, "bad GEMM shape (N and K must be multiples of 32)");
+  RPR_REQUIRE(mode >= RPR_LIN_F32 && mode <= RPR_LIN_LIVE_ROWS && (mfma16 == 0 || mfma16 == 1), "mode or mfma16 out of range");
+  RPR_REQUIRE(c->precision == RPR_PREC_F16X2, "the hook launches the split-precision kernels: the ctx precision must be f16x2");
+  const bool planes = mode == RPR_LIN_X_PLANES || mode == RPR_LIN_FF_PLANES;
+  RPR_REQUIRE(planes ? out_planes != nullptr : out0 != nullptr, "the mode's output buffer is NULL");
+  RPR_REQUIRE(mode != RPR_LIN_X_PLANES || (resid && ssq_out), "x-stream mode needs the residual and the row-sum buffer");
+  RPR_REQUIRE(mode != RPR_LIN_KV_SCATTER || (out1 && out2 && rm_B >= 1 && split_n >= 64 && split_n % 64 == 0 && 3 * split_n >= N),
+              "scatter mode needs out1, out2, rm_B and a split_n that is a multiple of 64 with 3 * split_n >= N");
+  RPR_REQUIRE(mode != RPR_LIN_FUSED_NORM || row_ssq, "fused-norm mode needs row_ssq");
+  RPR_REQUIRE(mode != RPR_LIN_LIVE_ROWS || m_dev, "live-row mode needs m_dev");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Launcher Ln{c, s};
+  Ln.mfma16 = mfma16;
+  DevTmp At, Wt;
+  { const int pe = ensure(c, c->ws.part, (size_t)9 << 20 << 2); if (pe) return pe; }   // split-K scratch, as a search has it
+  const float a_scale = mode == RPR_LIN_FUSED_NORM ? X_PLANE_SCALE : 1.0f;            // (fused norm: A = the planes of the x stream)
+  RPR_HIP(At.alloc((size_t)M * K * 2 * sizeof(__half)));
+  RPR_HIP(Wt.alloc((size_t)N * K * 2 * sizeof(__half)));
+  RPR_HIP(launch_split_planes(A, At.as<__half>(), (size_t)M * K, (size_t)M * K, s, a_scale, nullptr, 0, c->status));
+  RPR_HIP(launch_split_planes(W, Wt.as<__half>(), (size_t)N * K, (size_t)N * K, s, W_PLANE_SCALE, nullptr, 0, c->status));
+  LinIn in{A, At.as<__half>(), (size_t)M * K, K, a_scale};
+  LinOut o = out_f32(out0, N, N, (mode == RPR_LIN_F32) ? resid : nullptr, relu);
+  __half* oh = reinterpret_cast<__half*>(out_planes);
+  if (mode == RPR_LIN_X_PLANES) {          // XStream::out: x += product, in place in the planes, with the site's row sums
+    RPR_HIP(launch_split_planes(resid, oh, (size_t)M * N, (size_t)M * N, s, X_PLANE_SCALE, nullptr, 0, c->status));
+    o = LinOut{};
+    o.split_n = N; o.h = oh; o.ps = (size_t)M * N; o.ldh = N; o.plane_scale = X_PLANE_SCALE; o.resid_h = oh; o.ssq_out = reinterpret_cast<unsigned long long*>(ssq_out);
+  } else if (mode == RPR_LIN_FF_PLANES) {   // Pass::ff_block: relu(h Wi^T) as FF-scaled planes
+    o = out_f32(nullptr, N, N, nullptr, 1);
+    o.h = oh; o.ps = (size_t)M * N; o.ldh = N; o.plane_scale = FF_PLANE_SCALE;
+  } else if (mode == RPR_LIN_KV_SCATTER) {  // q rows | K/V-cache layout [query][head][beam][64] of the steps
+    o = out_f32(out0, split_n, split_n);
+    o.f[1] = out1; o.f[2] = out2;
+    o.rm_B = rm_B; o.rm_slot = 64; o.rm_head = (size_t)rm_B * 64; o.rm_stride = (size_t)(split_n / 64) * rm_B * 64;
+  } else if (mode == RPR_LIN_FUSED_NORM) {  // XStream::in: rows scaled by rsqrt(row_ssq / (K * SSQ_FIX) + eps)
+    in.ssq = reinterpret_cast<const unsigned long long*>(row_ssq); in.inv_d_fix = 1.0f / ((float)K * SSQ_FIX); in.eps = eps;
+  }
+  linear(Ln, in, {W, Wt.as<__half>(), N, K}, M, o, mode == RPR_LIN_LIVE_ROWS ? reinterpret_cast<const int*>(m_dev) : nullptr);
+  RPR_HIP(hipStreamSynchronize(s));   // the temporaries are freed when this scope ends
   return Ln.err;
 }
 

@@ -318,6 +318,8 @@ struct GemmH2Args {
   int no_row_split;                        // 1: never split the rows of this launch over two kernels (packed encoder: M is a capacity far above
                                            // the live row count, which only the device knows)
   int force_pp;                            // 1: the 256x256 ping-pong kernel whatever the shape, rows never split (the layer-0 Q/K/V table)
+  int mfma16;                              // 1: a launch of a search's tail pass — the 256x256 ping-pong step of its plan runs on v_mfma_f32_16x16x32_f16
+                                           // (set from the Launcher's Mfma16Scope; never by the encoder, the steps, the training step, the cross-encoder, bf16 or grouped launches)
   int kernel_cls;                          // out (host side): profile class of the kernel chosen (RPR_K_GEMM = 256x256 ping-pong, RPR_K_GEMM_SMALL = the others)
   // bf16 launches on the 256x256 kernel only (training step, round 6): the result leaves the epilogue in the operand formats
   // of the products that consume it, instead of one conversion launch per consumer reading the fp32 result back —

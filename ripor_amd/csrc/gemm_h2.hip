@@ -38,12 +38,18 @@ namespace rpr {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
+// A wave's accumulators as the epilogue takes them: TM x TN tiles of 32 x 32 (v_mfma_f32_32x32x16_*), or, M16, the same
+// outputs as 2 TM x 2 TN tiles of 16 x 16 (v_mfma_f32_16x16x32_f16: the tail passes' 256x256 kernel)
+template <bool M16, int TM, int TN> struct H2Acc { typedef f32x16 type[TM][TN]; };
+template <int TM, int TN> struct H2Acc<true, TM, TN> { typedef f32x4 type[2 * TM][2 * TN]; };
+
 // the LDS-transposed epilogue of the tile kernels (defined behind gemm_h2_dma_kernel)
-template <bool FULL, int TM, int TN, int WM, int WN, int BM, int BN, bool BOUT = false>
-__device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, f32x16 (&acc)[TM][TN], __half* smem, int wave, int lane, int bm,
+template <bool FULL, int TM, int TN, int WM, int WN, int BM, int BN, bool BOUT = false, bool M16 = false>
+__device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, typename H2Acc<M16, TM, TN>::type& acc, __half* smem, int wave, int lane, int bm,
                                                 int bn, int wm, int wn, const float* rs_tile, float acc_scale);
 
 
@@ -295,11 +301,21 @@ void gemm_h2_dma_kernel(GemmH2Args g, int tiles_m, int tiles_n) {
 // One strip (64 rows of a wave's 128 x 64 outputs) of the epilogue below. The strip index is a template parameter: the
 // accumulators are indexed with it, and a strip loop the compiler declines to unroll — it did once the output paths had
 // grown — puts all 128 of them into scratch.
-template <bool FULL, int TM, int TN, int WM, int WN, int strip, int BM = 256, int BN = 256, bool BOUT = false>
-__device__ __forceinline__ void h2_epilogue_strip(const GemmH2Args& g, f32x16 (&acc)[TM][TN], float* stg, int lane, int bm, int bn,
+template <bool FULL, int TM, int TN, int WM, int WN, int strip, int BM = 256, int BN = 256, bool BOUT = false, bool M16 = false>
+__device__ __forceinline__ void h2_epilogue_strip(const GemmH2Args& g, typename H2Acc<M16, TM, TN>::type& acc, float* stg, int lane, int bm, int bn,
                                                   int wm, int wn, const float* rs_tile, float acc_scale, int Mlim) {
   constexpr int SH = 64, SW = TN * 32;
   const int ncol = lane & 31, rsub = 4 * (lane >> 5);
+  if constexpr (M16) {   // the 16 x 16 C/D map: lane = column lane & 15, rows 4 (lane >> 4) + r of its tile
+    const int c16 = lane & 15, r16 = 4 * (lane >> 4);
+#pragma unroll
+    for (int ii = 0; ii < SH / 16; ++ii)
+#pragma unroll
+      for (int j = 0; j < 2 * TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          stg[(ii * 16 + r16 + r) * SW + j * 16 + c16] = acc[strip * (SH / 16) + ii][j][r];
+  } else
 #pragma unroll
     for (int ii = 0; ii < SH / 32; ++ii)
 #pragma unroll
@@ -540,8 +556,8 @@ __device__ __forceinline__ void h2_epilogue_strip(const GemmH2Args& g, f32x16 (&
     __builtin_amdgcn_wave_barrier();                  // stg is rewritten by the next strip
 }
 
-template <bool FULL, int TM, int TN, int WM, int WN, int BM, int BN, bool BOUT>
-__device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, f32x16 (&acc)[TM][TN], __half* smem, int wave,
+template <bool FULL, int TM, int TN, int WM, int WN, int BM, int BN, bool BOUT, bool M16>
+__device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, typename H2Acc<M16, TM, TN>::type& acc, __half* smem, int wave,
                                                 int lane, int bm, int bn, int wm, int wn, const float* rs_tile,
                                                 float acc_scale) {
   constexpr int SH = 64;
@@ -563,8 +579,8 @@ __device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, f32x16 (&ac
   const int ncol = lane & 31, rsub = 4 * (lane >> 5);
   static_assert(NS == 1 || NS == 2, "one or two strips of 64 rows per wave");
   (void)ncol; (void)rsub;
-  h2_epilogue_strip<FULL, TM, TN, WM, WN, 0, BM, BN, BOUT>(g, acc, stg, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
-  if (NS == 2) h2_epilogue_strip<FULL, TM, TN, WM, WN, NS - 1, BM, BN, BOUT>(g, acc, stg, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
+  h2_epilogue_strip<FULL, TM, TN, WM, WN, 0, BM, BN, BOUT, M16>(g, acc, stg, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
+  if (NS == 2) h2_epilogue_strip<FULL, TM, TN, WM, WN, NS - 1, BM, BN, BOUT, M16>(g, acc, stg, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
 }
 
 // ---- ping-pong 256x256 variant -------------------------------------------------------------------------
@@ -587,8 +603,13 @@ __device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, f32x16 (&ac
 // prefetched under the epilogue — all of them slower or equal on the power-capped headline step.
 // The body is textually shared by two kernels (gemm_h2_pp_body.inc): gemm_h2_pp_kernel (one product, its arguments by value)
 // and gemm_h2_pp_group_kernel (a table of products in device memory, blockIdx.y = product; see there).
-template <bool FULL, bool BF16 = false>
+// M16 = true (the launches of a search's tail passes, GemmH2Args::mfma16; f16x2 only): the same tiles, LDS layout, LDS-DMA feed and barrier
+// schedule with the K-loop on v_mfma_f32_16x16x32_f16 — 48 MFMAs of 16 cycles per phase instead of 24 of 32, a phase per half
+// of the wave's A rows instead of per k-chunk. A product's 32 columns of a K-tile are then summed inside one MFMA, so the
+// results differ from the 32x32x16 body's in the last bits.
+template <bool FULL, bool BF16 = false, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm_h2_pp_kernel(GemmH2Args g, int tiles_m, int tiles_n) {
+  static_assert(!(BF16 && M16), "the 16x16x32 body is the split-precision kernel's");
 #include "gemm_h2_pp_body.inc"
 }
 
@@ -610,7 +631,7 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_pp_kernel(GemmH2Args g, int ti
 // (rocprofv3 FETCH_SIZE; 1.03 GB go through LDS).
 template <bool FULL>
 __global__ __launch_bounds__(512, 2) void gemm_h2_pp_group_kernel(const GemmH2Args* __restrict__ table, const int* __restrict__ assign) {
-  constexpr bool BF16 = true;
+  constexpr bool BF16 = true, M16 = false;
   const int asg = assign[blockIdx.x];
   if (asg < 0) return;
   const GemmH2Args& g = table[asg >> 16];
@@ -1006,6 +1027,8 @@ static void launch_256(const GemmStep& p, const GemmH2Args& a, hipStream_t s) {
   const dim3 gr(p.grid_x, p.grid_y), bl(512);
   if (p.bf16 && p.full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true, true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
   else if (p.bf16) hipLaunchKernelGGL((gemm_h2_pp_kernel<false, true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
+  else if (p.m16 && p.full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true, false, true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
+  else if (p.m16) hipLaunchKernelGGL((gemm_h2_pp_kernel<false, false, true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
   else if (p.full) hipLaunchKernelGGL((gemm_h2_pp_kernel<true>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
   else hipLaunchKernelGGL((gemm_h2_pp_kernel<false>), gr, bl, 0, s, a, p.tiles_m, p.tiles_n);
 }
@@ -1149,7 +1172,7 @@ static GemmRouteIn route_inputs(const GemmH2Args& a) {
   r.split_n = a.split_n; r.rm_B = a.rm_B; r.ksplit = a.ksplit; r.small_live = a.small_live; r.live_lo = a.live_lo; r.live_hi = a.live_hi;
   r.part_cap = a.part_cap;
   r.part = a.part; r.mid_split = a.mid_split; r.m_dev = a.m_dev; r.bf16 = a.bf16; r.no_row_split = a.no_row_split;
-  r.force_pp = a.force_pp;
+  r.force_pp = a.force_pp; r.mfma16 = a.mfma16;
   r.out_h = a.out_h; r.row_ssq = a.row_ssq; r.ssq_out = a.ssq_out; r.resid = a.resid; r.resid_h = a.resid_h; r.relu = a.relu;
   r.out_b = a.out_b; r.out_bt = a.out_bt;
   r.ab_al8 = !(a.lda & 7) && !(a.ldw & 7);

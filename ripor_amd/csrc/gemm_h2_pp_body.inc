@@ -1,7 +1,8 @@
 // Body of the 256x256 ping-pong GEMM kernels (see gemm_h2.hip): textually included by gemm_h2_pp_kernel (one product, its
 // arguments `g` by value) and gemm_h2_pp_group_kernel (`g` = an entry of a table in device memory), so that the single-product
 // kernel of the search path compiles exactly as it did as a self-contained kernel (a shared device function taking the
-// arguments by reference changed its register allocation). Expects: FULL, BF16 (template parameters), g, tiles_m, tiles_n.
+// arguments by reference changed its register allocation). Expects: FULL, BF16, M16 (template parameters; the grouped kernel
+// sets BF16 = true, M16 = false), g, tiles_m, tiles_n. M16: the K-loop of a search's tail passes on v_mfma_f32_16x16x32_f16 (below).
   // per-tensor dynamic plane scales (training): read from the device; g itself must stay untouched — a kernel that writes
   // to its by-value argument struct gets a private copy of all 320 bytes in scratch (measured: +20 % per launch)
   const float acc_scale = g.dyn_a ? 1.0f / (dyn_plane_scale(*g.dyn_a) * dyn_plane_scale(*g.dyn_b)) : g.acc_scale;
@@ -103,6 +104,20 @@
 
   f16x8 ah0, ah1, al0, al1, bh0, bh1, bl0, bl1;
   f16x8 ah2, ah3, al2, al3;   // two-phase schedule: all four 32-row fragments of the wave's A rows per k-chunk
+  // M16 (tail-pass launches, GemmH2Args::mfma16): the wave's 128 x 64 outputs as 8 x 4 tiles of 16 x 16, the same 128 registers.
+  // Lane (c = lane & 15, g = lane >> 4) holds k = 8g .. 8g+7 of row base + c: ONE 16-byte segment of the row, at the
+  // inverse of the DMA's swizzle (PP_SRC_SETUP: seg ^ ((row >> 2) & 3); tile bases are multiples of 16, so the term is the
+  // lane's own) — the 16 lanes of a group read 16 different 16-byte slots of a 256-byte bank line.
+  f32x4 acc16[8][4];
+  f16x8 wh2, wh3, wl2, wl3;   // (with bh0, bh1, bl0, bl1: the four 16-row W fragments, kept over both phases of a K-tile)
+  const int a_row16 = wm * (BM / WM) + (lane & 15), w_row16 = 2 * BM + wn * (BN / WN) + (lane & 15);
+  const int so16 = ((lane >> 4) ^ ((lane >> 2) & 3)) * 8;
+  if constexpr (M16) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 #define PP_LOAD_W(buf, so)                                                                              \
   {                                                                                                     \
     const __half* base_ = smem + (size_t)(buf) * ROWS * HBK;                                            \
@@ -200,6 +215,52 @@
   __builtin_amdgcn_sched_barrier(0)
   constexpr int WAIT_LGKM = 0xc07f, WAIT_ALL = 0x0070;   // lgkmcnt(0) | vmcnt(0) lgkmcnt(0)
   constexpr int WAIT_VM4 = 0x0074;                       // vmcnt(4) lgkmcnt(0)
+// ---- 16x16x32 body: one MFMA spans the K-tile's 32 columns, so the two phases of a K-tile split the wave's A rows (phase p:
+// A tiles 4p .. 4p+3 against the four W tiles = 16 outputs x 3 products = 48 MFMAs of 16 cycles, the 768 matrix-pipe cycles
+// of the 24 x 32 above). Every accumulator takes lo*hi, hi*lo, hi*hi in that order, 16 MFMAs apart; the DMA pieces sit
+// after every 6th MFMA (96 cycles, as after every 3rd above). 8 W + 8 A fragment reads in L_0, 8 A reads in L_1: 24 per K-tile.
+#define PP16_LOAD_W(buf)                                                                                \
+  {                                                                                                     \
+    const __half* base_ = smem + (size_t)(buf) * ROWS * HBK + so16;                                     \
+    bh0 = *reinterpret_cast<const f16x8*>(base_ + (w_row16) * HBK);                                     \
+    bh1 = *reinterpret_cast<const f16x8*>(base_ + (w_row16 + 16) * HBK);                                \
+    wh2 = *reinterpret_cast<const f16x8*>(base_ + (w_row16 + 32) * HBK);                                \
+    wh3 = *reinterpret_cast<const f16x8*>(base_ + (w_row16 + 48) * HBK);                                \
+    bl0 = *reinterpret_cast<const f16x8*>(base_ + (BN + w_row16) * HBK);                                \
+    bl1 = *reinterpret_cast<const f16x8*>(base_ + (BN + w_row16 + 16) * HBK);                           \
+    wl2 = *reinterpret_cast<const f16x8*>(base_ + (BN + w_row16 + 32) * HBK);                           \
+    wl3 = *reinterpret_cast<const f16x8*>(base_ + (BN + w_row16 + 48) * HBK);                           \
+  }
+#define PP16_LOAD_A(buf, ph)                                                                            \
+  {                                                                                                     \
+    const __half* base_ = smem + (size_t)(buf) * ROWS * HBK + so16;                                     \
+    ah0 = *reinterpret_cast<const f16x8*>(base_ + (a_row16 + (ph) * 64) * HBK);                         \
+    ah1 = *reinterpret_cast<const f16x8*>(base_ + (a_row16 + (ph) * 64 + 16) * HBK);                    \
+    ah2 = *reinterpret_cast<const f16x8*>(base_ + (a_row16 + (ph) * 64 + 32) * HBK);                    \
+    ah3 = *reinterpret_cast<const f16x8*>(base_ + (a_row16 + (ph) * 64 + 48) * HBK);                    \
+    al0 = *reinterpret_cast<const f16x8*>(base_ + (BM + a_row16 + (ph) * 64) * HBK);                    \
+    al1 = *reinterpret_cast<const f16x8*>(base_ + (BM + a_row16 + (ph) * 64 + 16) * HBK);               \
+    al2 = *reinterpret_cast<const f16x8*>(base_ + (BM + a_row16 + (ph) * 64 + 32) * HBK);               \
+    al3 = *reinterpret_cast<const f16x8*>(base_ + (BM + a_row16 + (ph) * 64 + 48) * HBK);               \
+  }
+#define PP16_MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
+#define PP16_ROW(A, i, B0, B1, B2, B3)                                                                  \
+    PP16_MFMA(A, B0, acc16[i][0]); PP16_MFMA(A, B1, acc16[i][1]); PP16_MFMA(A, B2, acc16[i][2]); PP16_MFMA(A, B3, acc16[i][3]);
+#define PP16_MMA16(i0, A0, A1, A2, A3, B0, B1, B2, B3, Da, Db, Dc)                                      \
+    PP16_ROW(A0, (i0), B0, B1, B2, B3)                                                                  \
+    PP16_MFMA(A1, B0, acc16[(i0) + 1][0]); PP16_MFMA(A1, B1, acc16[(i0) + 1][1]);                       \
+    PP_SB; Da; PP_SB;                                                                                   \
+    PP16_MFMA(A1, B2, acc16[(i0) + 1][2]); PP16_MFMA(A1, B3, acc16[(i0) + 1][3]);                       \
+    PP16_ROW(A2, (i0) + 2, B0, B1, B2, B3)                                                              \
+    PP_SB; Db; PP_SB;                                                                                   \
+    PP16_ROW(A3, (i0) + 3, B0, B1, B2, B3)                                                              \
+    PP_SB; Dc; PP_SB;
+#define PP16_MMA48(i0, D0, D1, D2, D3, D4, D5, D6, D7)                                                  \
+  {                                                                                                     \
+    PP16_MMA16(i0, al0, al1, al2, al3, bh0, bh1, wh2, wh3, D0, D1, D2)                                  \
+    PP16_MMA16(i0, ah0, ah1, ah2, ah3, bl0, bl1, wl2, wl3, D3, D4, D5)                                  \
+    PP16_MMA16(i0, ah0, ah1, ah2, ah3, bh0, bh1, wh2, wh3, D6, D7, (void)0)                             \
+  }
 
 #pragma unroll
   for (int j = 0; j < PER_WAVE; ++j) PP_PIECE(0, 0, j);
@@ -262,6 +323,22 @@
 #undef PP_DMA1
 #undef PP_DMA2
     }
+  } else if constexpr (M16) {
+    for (int kt = 0; kt < nkt; ++kt) {   // same segments, waits and barriers as the 32x32x16 loop below
+      const int cur = kt & 1, nxt = cur ^ 1;
+      const bool more = kt + 1 < nkt;
+      const int k1 = (kt + 1) * KSTEP;
+      PP16_LOAD_W(cur);
+      PP16_LOAD_A(cur, 0);
+      PP_L_END(WAIT_LGKM, 0);
+      PP16_MMA48(0, PP_DMA_M(0), PP_DMA_M(1), PP_DMA_M(2), PP_DMA_M(3), PP_DMA_M(4), PP_DMA_M(5), PP_DMA_M(6), PP_DMA_M(7));
+      PP_M_END(0);
+      // phase 1: the other 64 A rows (the W fragments stay in registers); tile kt+1 must have landed before anyone's next L_0
+      PP16_LOAD_A(cur, 1);
+      PP_L_END(WAIT_ALL, 1);
+      PP16_MMA48(4, (void)0, (void)0, (void)0, (void)0, (void)0, (void)0, (void)0, (void)0);
+      PP_M_END(1);
+    }
   } else
   for (int kt = 0; kt < nkt; ++kt) {
     const int cur = kt & 1, nxt = cur ^ 1;
@@ -292,6 +369,12 @@
 #undef PP_MMA
 #undef PP_MMA8
 #undef PP_MMA24
+#undef PP16_LOAD_W
+#undef PP16_LOAD_A
+#undef PP16_MFMA
+#undef PP16_ROW
+#undef PP16_MMA16
+#undef PP16_MMA48
 #undef PP_SB
 #undef PP_LOAD_A4
 #undef PP_DMA
@@ -301,6 +384,8 @@
 
   int lane_e = lane;   // laundered like lane_t: the epilogue's per-lane offsets must not live through the K-loop
   asm volatile("" : "+v"(lane_e));
+  if constexpr (M16) h2_epilogue_256<FULL, TM, TN, WM, WN, 256, 256, false, true>(g, acc16, smem, wave, lane_e, bm, bn, wm, wn, g.row_ssq ? rs_tile : nullptr, acc_scale);
+  else
   h2_epilogue_256<FULL, TM, TN, WM, WN, 256, 256, BF16 && FULL>(g, acc, smem, wave, lane_e, bm, bn, wm, wn, g.row_ssq ? rs_tile : nullptr, acc_scale);
   // The staging strips alias the operand buffers the next tile's LDS-DMA writes, and rs_tile is rewritten: every wave's LDS
   // reads must have returned (lgkmcnt(0)) before anyone goes on. NOT __syncthreads(): its fence also waits for vmcnt(0),

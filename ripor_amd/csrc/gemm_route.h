@@ -21,6 +21,7 @@ struct GemmRouteIn {
   size_t part_cap = 0;
   bool part = false, mid_split = false, m_dev = false, bf16 = false, no_row_split = false;
   bool force_pp = false;  // the caller pins this launch to the 256x256 ping-pong kernel, unsplit (GemmH2Args::force_pp)
+  bool mfma16 = false;    // a tail pass's launch: its ping-pong step runs the 16x16x32 body (GemmH2Args::mfma16)
   bool out_h = false, row_ssq = false, ssq_out = false, resid = false, resid_h = false, relu = false, out_b = false, out_bt = false;
   bool ab_al8 = true;     // lda and ldw multiples of 8
   bool ldo0_al4 = true;   // ldo[0] a multiple of 4
@@ -67,6 +68,7 @@ enum GemmReduce { REDUCE_NONE, REDUCE_SUM, REDUCE_FUSED, REDUCE_FUSED4 };
 struct GemmStep {
   int family = GEMM_DMA, bm = 0, bn = 0, stages = 0;   // kernel family, tile shape, LDS ring depth (0: the ping-pong / skinny kernels have one)
   bool full = false, bf16 = false;                     // FULL instantiation (no ragged tiles, no device row count); bf16 operands
+  bool m16 = false;                                    // ping-pong step of a tail-pass launch: the 16x16x32 body (never bf16, never a K split)
   int rows = 0, m_base = 0;                            // covers rows [m_base, m_base + rows) of the product
   int live_lo = 0, live_hi = 0;                        // live-count window (GemmH2Args::live_lo)
   int ksplit = 1, reduce = REDUCE_NONE;
@@ -154,6 +156,7 @@ inline GemmStep pp_step(const GemmRouteIn& a, const GemmTuning& t, int ks = 1, i
   GemmStep s = route_step(a, GEMM_PP, 256, 256, ks, reduce);
   const int cus = a.cus > 0 ? a.cus : 256, nt = s.grid_x, grid = nt > cus ? cus : nt;
   s.block = 512;
+  s.m16 = a.mfma16 && !a.bf16 && s.ksplit == 1;
   if (s.ksplit == 1) s.grid_x = grid;
   if (t.supertile && s.ksplit == 1 && s.tiles_n > 4 && nt > grid) {
     s.tile_cw = t.supertile > 1 ? t.supertile : (s.tiles_n % 4 == 0 ? 4 : (s.tiles_n % 3 == 0 ? 3 : 4));

@@ -319,6 +319,12 @@ struct Launcher {
   int cus = 0;                     // CUs of the stream (0 = the whole chip): GemmH2Args.cus
   int no_row_split = 0;            // 1 while the packed encoder (and the cross-K/V product on its rows) is enqueued: GemmH2Args.no_row_split
   int small_live = 0;              // > 0 while a leftover stage is enqueued: its GEMMs are paired (GemmH2Args.small_live)
+  int mfma16 = 0;                  // 1 while a tail pass is enqueued on a plan with SearchPlan::mfma16 (passes.hip: enqueue_tail): GemmH2Args.mfma16
+  struct Mfma16Scope {             // the MFMA shape of the launches enqueued while the scope lives; the previous one comes back with it
+    Launcher& L; const int old;
+    Mfma16Scope(Launcher& L_, int v) : L(L_), old(L_.mfma16) { L.mfma16 = v; }
+    ~Mfma16Scope() { L.mfma16 = old; }
+  };
   void account_live(const int* dev, int rows_static) { live_dev = dev; live_static = rows_static; }
   hipEvent_t get_event() {
     if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }

@@ -38,6 +38,7 @@ GemmH2Args h2_args(const Launcher& L, const LinIn& A, const LinW& W, int M, cons
   g.small_live = m_dev ? L.small_live : 0;
   g.no_row_split = W.row_split_ok ? 0 : L.no_row_split;
   g.force_pp = W.force_pp ? 1 : 0;
+  g.mfma16 = L.mfma16;
   if (!W.no_scratch) { g.part = P<float>(c->ws.part); g.part_cap = c->ws.part.cap / sizeof(float); g.mid_split = 1; }
   return g;
 }
@@ -522,17 +523,27 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
   float *qkv = P<float>(w.t_qkv), *qb = P<float>(w.t_q);
   Pass p(Ln, m, {w.t_x, w.t_h, w.t_attn, w.t_ff, w.t_x_h, w.t_attn_h, w.t_ff_h, w.t_ssq}, true, nd, R, nrows_dev, Ra);
   p.zero_ssq();
+  // MFMA shape of the pass's 256x256 GEMM launches (SearchPlan::mfma16). A tail pass scores sequences that are already chosen:
+  // its rounding reaches the returned scores, never which sequences survive the steps — those launches (encoder, steps, the
+  // layer-0 table) keep the 32x32x16 arithmetic, and so does the layer-0 projection the table stands in for, below.
+  // One exception: a query forced WITH EXTRAS (plan.extras > 0) brings B + extras sequences, and tail_rank_extras keeps the best
+  // B of them by this pass's scores — that one pruning decision sees the pass's rounding (a few 1e-6 on either shape).
+  Launcher::Mfma16Scope tail_shape(Ln, plan.mfma16);
   Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * dm * 4, [&] {
     return launch_tail_embed(d.in_embeds, P<uint16_t>(tb.tokens), p.x, R, nrows_dev, T, L, dm, V, s, p.embed_out());
   });
   const size_t kv_pos = (size_t)B * sv.dkv;
   for (int i = 0; i < nd; ++i) {
     const LinOut o_qkv = out_f32(qkv, 3 * inner, 3 * inner);
-    if (i == 0 && p.l0_replaces(plan, o_qkv))   // layer 0: the rows of the model's (position, token) table instead of the projection
-      Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * 3 * inner * 4, [&] {
-        return launch_tail_l0_qkv(m->l0_table, P<uint16_t>(tb.tokens), qkv, R, nrows_dev, T, L, V, 3 * inner, s);
-      });
-    else
+    if (i == 0) {   // layer 0 on the table's arithmetic: the gate asks the planner about the launch that would run, flag included
+      Launcher::Mfma16Scope l0_shape(Ln, 0);
+      if (p.l0_replaces(plan, o_qkv))   // the rows of the model's (position, token) table instead of the projection
+        Ln.run(RPR_K_OTHER, 0, 2.0 * Ra * 3 * inner * 4, [&] {
+          return launch_tail_l0_qkv(m->l0_table, P<uint16_t>(tb.tokens), qkv, R, nrows_dev, T, L, V, 3 * inner, s);
+        });
+      else
+        p.project_in(i, 0, o_qkv);
+    } else
       p.project_in(i, 0, o_qkv);
     {
       const size_t ls = sv.kv_layer(B, inner);

@@ -21,6 +21,7 @@ struct SearchPlan {
   int prec = RPR_PREC_F16X2;     // effective_precision of the call
   bool margins = false;          // rpr_search_margins: every selection step is followed by the pruning-margin kernel
   int l0 = 0;                    // the layer-0 Q/K/V table: 0 = not read, 1 / 2 = read in that rpr_set_l0_table mode
+  int mfma16 = 0;                // 1: the 256x256 ping-pong GEMM launches of this search's tail passes run the 16x16x32 body (rpr_set_gemm_mfma16)
   int extras = 0, pool = 0;      // forced with extras: budget per forced query, spare tail entries per fork (both 0 without forks)
   int forks[MAX_FORKS] = {0, 0}; // depths at which forced queries leave the sequential steps (ascending, each in [1, L-1])
   int n_forks = 0;               //   0 = plain search
@@ -28,7 +29,7 @@ struct SearchPlan {
   int tail_rank_replay = 0, select_radix = -1;   // per-call test selectors of the ranking / selection launchers (tests flip them between calls)
   bool log_softmax() const { return (flags & RPR_FLAG_LOG_SOFTMAX) != 0; }
   auto key() const {
-    return std::tie(Q, Lq, B, L, flags, lane, cus, prec, margins, l0, extras, pool, forks[0], forks[1], n_forks, drop_last,
+    return std::tie(Q, Lq, B, L, flags, lane, cus, prec, margins, l0, mfma16, extras, pool, forks[0], forks[1], n_forks, drop_last,
                     tail_rank_replay, select_radix);
   }
   bool operator<(const SearchPlan& o) const { return key() < o.key(); }
@@ -138,6 +139,8 @@ struct SearchSettings {          // the base of rpr_ctx (internal.h)
   int tail_extras = -1;          // rpr_set_tail_extras: -1 = automatic (tail_extras_budget), 0 = off, n > 0 = always, up to n extra sequences per query
   int l0_mode = 1;               // rpr_set_l0_table: 0 = the table is never made nor read, 1 = it replaces the launches the route planner
                                  //   sends to the ping-pong kernel, 2 = every layer-0 Q/K/V launch of a search (tests)
+  int gemm_mfma16 = 1;           // rpr_set_gemm_mfma16: MFMA shape of the 256x256 ping-pong GEMM, 0 = 32x32x16 everywhere,
+                                 //   1 = 16x16x32 in the tail passes of a search (forced sequences: scores only, no pruning decision)
   int lane_cus = 0;              // CUs per lane
 };
 struct SearchModel {             // rpr_model
@@ -165,6 +168,7 @@ SearchPlan plan_search(const SearchSettings& s, const SearchModel& m, const Sear
   p.prec = effective_precision(s.precision, m.f32_only);
   p.margins = a.margins;
   p.l0 = s.l0_mode > 0 && m.l0_current && p.prec == RPR_PREC_F16X2 ? s.l0_mode : 0;
+  p.mfma16 = s.gemm_mfma16 && p.prec == RPR_PREC_F16X2 ? 1 : 0;
   p.tail_rank_replay = a.tail_rank_replay ? 1 : 0; p.select_radix = a.select_radix;
   if (!s.forced_tail || a.taps || a.L < 3 || !std::isfinite(m.logit_bound)) return p;
   const double per_step = 2.0 * (double)m.logit_bound + (p.log_softmax() ? std::log((double)m.V) : 0.0);

@@ -81,6 +81,14 @@ class Context:
         """Size of the model's layer-0 Q/K/V table if the next search may read it, else 0."""
         return int(self.lib.rpr_l0_table_bytes(self.handle, model.handle))
 
+    def set_gemm_mfma16(self, mode: int):
+        """MFMA shape of the 256 x 256 split-precision GEMM (``rpr_set_gemm_mfma16``): 0 = 32x32x16 everywhere,
+        1 = 16x16x32 in the tail passes of a search (library default; scores of forced sequences move in their last bits)."""
+        check(self.lib.rpr_set_gemm_mfma16(self.handle, int(mode)), "rpr_set_gemm_mfma16")
+
+    def gemm_mfma16(self) -> int:
+        return int(self.lib.rpr_gemm_mfma16(self.handle))
+
     def set_tail_extras(self, mode: int):
         """Forced with extras (``rpr_set_tail_extras``): -1 = automatic (library default: more than 4096 decoder rows and
         fewer than 32 beams), 0 = off, n > 0 = always, with a budget of n extra sequences per query."""
@@ -181,6 +189,20 @@ class Context:
         check(self.lib.rpr_op_linear(self.handle, A.data_ptr(), W.data_ptr(), res.data_ptr() if res is not None else None,
                                      out.data_ptr(), M, N, K, 1 if relu else 0, _stream_ptr(A.device)), "rpr_op_linear")
         return out
+
+    def linear_h2(self, A: torch.Tensor, W: torch.Tensor, mode: int = 0, mfma16: int = 0, relu: bool = False,
+                  resid: Optional[torch.Tensor] = None, row_ssq: Optional[torch.Tensor] = None, eps: float = 0.0,
+                  m_dev: Optional[torch.Tensor] = None, rm_B: int = 0, split_n: int = 0, out0: Optional[torch.Tensor] = None,
+                  out1: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None,
+                  out_planes: Optional[torch.Tensor] = None, ssq_out: Optional[torch.Tensor] = None):
+        """Test hook (``rpr_op_linear_h2``, modes RPR_LIN_*): one split-precision launch with a search's epilogue, written
+        into the caller's buffers (fp32 out0 / out1 / out2, float16 out_planes [2, M, N], int64 ssq_out / row_ssq, int32 m_dev)."""
+        assert A.is_cuda and W.is_cuda and A.dtype == torch.float32 and W.dtype == torch.float32 and A.is_contiguous() and W.is_contiguous()
+        M, K = A.shape
+        p = lambda t: t.data_ptr() if t is not None else None
+        check(self.lib.rpr_op_linear_h2(self.handle, A.data_ptr(), W.data_ptr(), M, W.shape[0], K, int(mode), int(mfma16), 1 if relu else 0,
+                                        p(resid), p(row_ssq), float(eps), p(m_dev), int(rm_B), int(split_n), p(out0), p(out1), p(out2),
+                                        p(out_planes), p(ssq_out), _stream_ptr(A.device)), "rpr_op_linear_h2")
 
     def linear_bf16(self, A: torch.Tensor, W: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False,
                     n_products: int = 0):
