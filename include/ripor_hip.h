@@ -47,8 +47,8 @@ typedef struct rpr_trie rpr_trie;
  * the host (rows 0..inner-1 = q, then k, then v). Per-layer pointers are host arrays of device
  * pointers with num_layers / num_decoder_layers entries. */
 typedef struct {
-  int32_t vocab_size, d_model, d_kv, d_ff, num_heads;   /* d_kv: 64 (t5-base / t5-large) or 128 (t5-3b: rpr_search / rpr_encode only,
-                                                         * no training entry points) */
+  int32_t vocab_size, d_model, d_kv, d_ff, num_heads;   /* d_kv: 64 (t5-base / t5-large) or 128 (t5-3b); every entry
+                                                         * point runs both */
   int32_t num_layers, num_decoder_layers;
   int32_t rel_buckets, rel_max_distance;
   int32_t L;                     /* len(config.decoder_vocab_sizes) = max decoder positions      */
@@ -343,7 +343,8 @@ int rpr_last_fork_stats(rpr_ctx* ctx, int32_t* out_depths, int32_t* out_forced, 
  *   out_losses:  [dev] float [n_prefix]        mean_b (student_margin - teacher_margin)^2   (torch.nn.MSELoss)
  *   out_position_scores: [dev] float [bz, n_docs, L], nullable
  * Inference-style forward (split-precision GEMMs, nothing kept for a backward pass); the training step is
- * rpr_lngknp_backward + rpr_adamw_step below. Eager launches on `stream`; asynchronous. */
+ * rpr_lngknp_backward + rpr_adamw_step below. Eager launches on `stream`; asynchronous. Lq <= 256; d_kv 64 or 128 (128-dim
+ * heads run on the attention kernels of the search path: enc_attn_kernel<128>, dec_cross_attn_block_kernel<128>). */
 int rpr_lngknp_forward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
                        int32_t bz, int32_t Lq, const int32_t* doc_codes, int32_t n_docs, int32_t L,
                        const float* teacher_pos, const float* teacher_neg, const int32_t* prefix_lens, int32_t n_prefix,
@@ -368,7 +369,10 @@ int rpr_lngknp_forward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids,
  *   and overwrites flat_grads [dev, rpr_param_total]. fp32 activations and gradients; the matrix products follow the
  *   context's precision (rpr_set_precision): RPR_PREC_F16X2 (default) = split-precision f16 MFMA with per-tensor
  *   dynamic plane scales found on the device, RPR_PREC_F32 = exact-fp32 MFMA. Deterministic reductions in both.
- *   Lq <= 128, L <= the model's decoder length.
+ *   Lq <= 128, L <= the model's decoder length; d_kv 64 or 128. The attention backward holds one (sequence, head) in
+ *   the 160 KB of LDS of a CU, 128-dim heads 64 columns at a time in the same carve, so the lengths admitted do not depend on
+ *   d_kv: self-attention max(L, Lq) <= 91, cross-attention 130 (2 L + Lq) + 4 L (Lq + 1) + Lq <= 40960 floats (L 32 with
+ *   Lq <= 91). A shape beyond is RPR_ERR_INVALID before anything is enqueued.
  * rpr_adamw_step: global L2 norm of flat_grads (-> out_grad_norm [dev, 1], nullable), clip coefficient
  *   min(1, max_grad_norm / (norm + 1e-6)) (max_grad_norm <= 0: no clipping), AdamW update of every tensor with the
  *   bias corrections of `step` (1-based); the f16 weight planes of the search / inference paths are marked stale and
@@ -408,7 +412,8 @@ int rpr_lngknp_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* i
  *                is enqueued: one copy of bz * L labels and a synchronisation of `stream`)
  *   out_loss:    [dev] float [1]
  *   out_label_logprob: [dev] float [bz, L], nullable: log-softmax of each position's logits at its label
- * Limits: d_kv == 64, L <= the model's L, V % 64 == 0 and V <= 1024, d_model % 32 == 0.
+ * Limits: d_kv 64 or 128 and the LDS admission of rpr_lngknp_backward (one document per query), L <= the model's L,
+ * V % 64 == 0 and V <= 1024, d_model % 32 == 0.
  * rpr_seq2seq_forward: the forward and the head only. rpr_seq2seq_backward: forward + backward, overwrites flat_grads
  * [dev, rpr_param_total] (same layout and optimizer step as the ranking step: rpr_adamw_step).
  * rpr_seq2seq_backward_buckets: the same with the gradient buckets of rpr_lngknp_backward_buckets (same order, same layout). */
@@ -554,7 +559,7 @@ int rpr_rq_encode_beam(rpr_ctx* ctx, const float* x, int64_t n, int32_t d, const
  * out [dev] fp32 [bz, d_model] = decoder_last_hidden_state[:, 0, :] after the final RMSNorm and the scaleup_output_hidden
  * factor (T5SeqAQEncoder.query_encode / T5AQEncoder.query_encode, modeling/t5_generative_retriever.py:786-792, 891-897).
  * The pass is rpr_lngknp_forward's with n_docs = 1, L = 1 and follows the context's precision like it. input_ids /
- * attention_mask: [dev] int32 [bz, Lq]; Lq <= 256; d_kv == 64. */
+ * attention_mask: [dev] int32 [bz, Lq]; Lq <= 256; d_kv 64 or 128. */
 int rpr_embed(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
               int32_t Lq, float* out, void* stream);
 /* Top-k inner-product search over the codes rpr_rq_encode wrote (faiss.IndexResidualQuantizer.search with

@@ -833,7 +833,7 @@ int rpr_lngknp_forward(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const
   RPR_REQUIRE(bz >= 1 && Lq >= 1 && Lq <= MAX_LQ, "bz or Lq out of range");
   RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_LQ, "smtid length exceeds the model's decoder length");
   RPR_REQUIRE(n_docs >= 1 && (int64_t)bz * n_docs * L < ((int64_t)1 << 24), "n_docs out of range");
-  RPR_REQUIRE(m->d.d_kv == DKV, "the teacher-forced kernels are written for d_kv == 64 (t5-base / t5-large)");
+  RPR_REQUIRE(m->d.d_kv == DKV || m->d.d_kv == 128, "d_kv must be 64 (t5-base / t5-large) or 128 (t5-3b)");
   RPR_REQUIRE(n_prefix >= 0 && n_prefix <= 8, "n_prefix out of range (0..8)");
   RPR_REQUIRE(n_prefix == 0 || (n_docs == 2 && teacher_pos && teacher_neg && prefix_lens && out_losses),
               "the margin losses need n_docs == 2 (positive, negative), teacher scores, prefix lengths and out_losses");
@@ -891,7 +891,7 @@ int rpr_embed(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t*
   RPR_REQUIRE(c && m && input_ids && attention_mask && out, "NULL argument");
   RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
   RPR_REQUIRE(bz >= 1 && bz < (1 << 24) && Lq >= 1 && Lq <= MAX_LQ, "bz or Lq out of range (Lq <= 256)");
-  RPR_REQUIRE(m->d.d_kv == DKV, "the teacher-forced kernels are written for d_kv == 64 (t5-base / t5-large)");
+  RPR_REQUIRE(m->d.d_kv == DKV || m->d.d_kv == 128, "d_kv must be 64 (t5-base / t5-large) or 128 (t5-3b)");
   RPR_HIP(hipSetDevice(c->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int e = ensure_weight_planes(c, m, s);

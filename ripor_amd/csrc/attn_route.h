@@ -11,7 +11,8 @@ namespace rpr {
 constexpr int MAX_LQ = 256;          // encoder tokens per query supported by the attention kernels
 constexpr int MAX_DEC_LEN = 64;      // decoder positions supported (reference uses 32 or 16)
 constexpr int DKV = 64;              // head dim the fast attention kernels are written for (t5-base/large); d_kv = 128 (t5-3b) runs
-                                     // on the generic kernels enc_attn_kernel<128> / dec_attn_kernel<., 128> without the forced tail
+                                     // on the generic kernels enc_attn_kernel<128> / dec_attn_kernel<., 128> without the forced tail,
+                                     // its training attention on the <., 128> instantiations of train_kernels.hip
 constexpr int SELF_MAXIT_MAX = 9;    // dec_self_attn_fast_kernel: 36 keys, covers L <= 35 (the reference uses L = 32 or 16)
 constexpr int XK_LD = DKV + 4, QS_LD = DKV + 4;   // dec_cross_attn_block_kernel: K / q rows padded by 4 floats (68; 132 for 128-dim heads)
 constexpr size_t LDS_MAX = 160 * 1024;            // LDS of a CU = the most a block may ask for
@@ -47,8 +48,8 @@ struct AttnTuning {
   X(TAIL_CROSS_V2_TPW9) X(TAIL_CROSS_V2_TPW1) X(TAIL_CROSS_G1_NKT1) X(TAIL_CROSS_G1_NKT2)                                \
   /* step cross-attention: step_cross_attn_mfma16_kernel<false> / <true> */                                             \
   X(STEP_CROSS16_ONE) X(STEP_CROSS16_MULTI)                                                                              \
-  /* training self-attention backward */                                                                                \
-  X(TRAIN_BWD_MFMA) X(TRAIN_BWD_VALU)
+  /* training self-attention backward: the fp32-MFMA tile, self_attn_bwd_kernel<., 64>, <., 128> */                     \
+  X(TRAIN_BWD_MFMA) X(TRAIN_BWD_VALU) X(TRAIN_BWD_VALU128)
 
 enum AttnKernel {
 #define X(n) ATTN_##n,
@@ -238,15 +239,18 @@ inline AttnLaunch plan_tail_self_attn(const TailSelfAttnIn& a, const AttnTuning&
 }
 
 // ---- training self-attention backward (launch_self_attn_bwd) ----------------------------------------------------------------
-struct SelfAttnBwdIn { int S = 0, Ls = 0, H = 0, buckets = 0; };
+struct SelfAttnBwdIn { int S = 0, Ls = 0, H = 0, buckets = 0, dkv = DKV; };
 // LDS of the VALU kernel (self_attn_bwd_kernel: rows padded to DKV + 1 floats); the training step is admitted by it whatever
-// the kernel (train_api.hip). buckets <= 64: fixed slot
+// the kernel (train_api.hip). buckets <= 64: fixed slot. 128-dim heads (t5-3b) go through the same carve 64 columns at a time
+// (129-float rows would need 4 * 64 * 129 + 2 * 64 * 65 + 5 * 64 + 64 = 41 728 floats at Ls = 64 against the 40 960 of a CU), so
+// the lengths admitted do not depend on the head dim
 inline size_t self_attn_bwd_smem(int Ls, int /*buckets*/) {
   return ((size_t)4 * Ls * (DKV + 1) + 2 * (size_t)Ls * (Ls + 1) + 64 + 5 * (size_t)Ls) * sizeof(float);
 }
 inline AttnLaunch plan_self_attn_bwd(const SelfAttnBwdIn& a) {
   const size_t smem = self_attn_bwd_smem(a.Ls, a.buckets);
-  if (smem > LDS_MAX || a.buckets > 64 || a.Ls < 1) return attn_invalid();
+  if (smem > LDS_MAX || a.buckets > 64 || a.Ls < 1 || (a.dkv != DKV && a.dkv != 128)) return attn_invalid();
+  if (a.dkv == 128) return attn_launch(ATTN_TRAIN_BWD_VALU128, (long)a.S * a.H, smem);   // the MFMA plan is a 64-dim tile
   if (a.Ls <= 32) {   // one wave per (sequence, head) on the fp32 matrix cores, two waves per block
     AttnLaunch p = attn_launch(ATTN_TRAIN_BWD_MFMA, ((long)a.S * a.H + 1) / 2, 2 * (3 * 32 * 64 + 64 + 96 + 64 + 64) * sizeof(float));
     p.block = 128;

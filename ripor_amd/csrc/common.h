@@ -736,21 +736,22 @@ struct ColsumSites {
 };
 int rmsnorm_bwd_parts(int rows);
 hipError_t launch_colsum_multi(const ColsumSites& p, int d, hipStream_t s);
+// dkv (here and in the four launches below): head dim, 64 or 128; the LDS asked for and so the lengths admitted are the same
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
-                                hipStream_t s, const DropAttn* drop = nullptr);
+                                hipStream_t s, const DropAttn* drop = nullptr, int dkv = DKV);
 size_t cross_attn_bwd_smem(int n, int Lq);
 hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, const float* dO,
                                  float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s,
-                                 const DropAttn* drop = nullptr);
+                                 const DropAttn* drop = nullptr, int dkv = DKV);
 // dropout of the training step (dropout.h): the attention forward with dropped-out probabilities (the two backward launches
 // above draw the same mask when handed the same DropAttn), the mask over an activation's rows r = sequence * n_pos + position
 // (out = resid + mask(x); resid nullable, x may be out), and the gold-code scores from an already normalised, dropped-out
 // hidden state (dscores null: scores; else dh and de)
 hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, const float* rel_bias, const int32_t* bucket, float* out,
-                                     int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s);
+                                     int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s, int dkv = DKV);
 hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
-                                      int n, int Lq, int H, const DropAttn& drop, hipStream_t s);
+                                      int n, int Lq, int H, const DropAttn& drop, hipStream_t s, int dkv = DKV);
 hipError_t launch_dropout_rows(const float* x, const float* resid, float* out, size_t n_seq, int n_pos, int n_feat, const DropKey& key,
                                int site, hipStream_t s);
 hipError_t launch_gold_rowdot(const float* hd, const float* out_embeds, const int32_t* out_idx, float* scores, const float* dscores,

@@ -706,16 +706,16 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
     p.project_in(i, 0, out_f32(qkv, 3 * inner, 3 * inner));
     {  // causal self-attention of every sequence over its own L positions (decoder relative-position table)
       EncAttnArgs a{qkv, nullptr, d.dec_rel_bias, m->dec_bucket, p.attn, S, L, H, d.rel_buckets,
-                    p.attn_planes(), p.ps_i, nullptr, nullptr, c->status, 1};
-      Ln.run(RPR_K_ENC_ATTN, 2.0 * S * H * (double)L * L * DKV, 4.0 * R * 4 * inner, [&] { return launch_enc_attn(a, s); });
+                    p.attn_planes(), p.ps_i, nullptr, nullptr, c->status, 1, 0, d.d_kv};
+      Ln.run(RPR_K_ENC_ATTN, 2.0 * S * H * (double)L * L * d.d_kv, 4.0 * R * 4 * inner, [&] { return launch_enc_attn(a, s); });
     }
     p.attn_out(i, 0);
     p.project_in(i, 1, out_f32(qb, inner, inner));
     {
       const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
       DecCrossAttnArgs a{qb, xk, xk + inner, xld, P<int32_t>(w.mask), p.attn, bz, ndoc * L, H, Lq, p.attn_planes(), p.ps_i,
-                         P<int32_t>(w.last), P<int32_t>(w.offs), 0, c->status};
-      Ln.run(RPR_K_DEC_CROSS_ATTN, 4.0 * R * H * (double)Lq * DKV, 4.0 * ((double)R * inner * 2 + 2.0 * bz * (double)Lq * inner),
+                         P<int32_t>(w.last), P<int32_t>(w.offs), 0, c->status, nullptr, d.d_kv};
+      Ln.run(RPR_K_DEC_CROSS_ATTN, 4.0 * R * H * (double)Lq * d.d_kv, 4.0 * ((double)R * inner * 2 + 2.0 * bz * (double)Lq * inner),
              [&] { return launch_dec_cross_attn(a, s); });
     }
     p.attn_out(i, 1);

@@ -623,12 +623,12 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
         if (drop.on) {
           Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
             return launch_self_attn_drop_fwd(in, k.mask, k.rel_bias, k.bucket, mid, k.nseq, k.len, D.H, d.rel_buckets, k.causal,
-                                             drop.attn(site_mid, k.len), s);
+                                             drop.attn(site_mid, k.len), s, d.d_kv);
           });
           break;
         }
         EncAttnArgs sa{in, k.mask, k.rel_bias, k.bucket, mid, k.nseq, k.len, D.H, d.rel_buckets, nullptr, 0, nullptr, nullptr, nullptr,
-                       k.causal, 1};
+                       k.causal, 1, d.d_kv};
         Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] { return launch_enc_attn(sa, s); });
         break;
       }
@@ -636,12 +636,15 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
         const float* xk = P<float>(w.xkv) + (size_t)i * 2 * inner;
         if (drop.on) {
           Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {
-            return launch_cross_attn_drop_fwd(in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.Lq, D.H, drop.attn(site_mid, D.L), s);
+            return launch_cross_attn_drop_fwd(in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.Lq, D.H, drop.attn(site_mid, D.L), s,
+                                              d.d_kv);
           });
           break;
         }
-        DecCrossAttnArgs ca{in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr};
-        // (the query's docs L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64)
+        DecCrossAttnArgs ca{in, xk, xk + inner, D.xld, mask, mid, D.bz, D.docs * D.L, D.H, D.Lq, nullptr, 0, last, nullptr, 0, nullptr,
+                            nullptr, d.d_kv};
+        // (the query's docs L decoder rows as 32-row tiles on the fp32-MFMA kernel of the search tail when Lq <= 64; 128-dim
+        // heads: the block kernel)
         Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] { return launch_tail_cross_attn(ca, s); });
         break;
       }
@@ -796,7 +799,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
         float* dxk = P<float>(w.dxkv) + (size_t)i * 2 * inner;
         Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] {   // dq into dbig (as [R, inner])
           return launch_cross_attn_bwd(in, xk, xk + inner, D.xld, mask, dattn, dbig, dxk, dxk + inner, D.bz, D.docs * D.L, D.Lq, H, s,
-                                       drop.on ? &da : nullptr);
+                                       drop.on ? &da : nullptr, d.d_kv);
         });
         break;
       }
@@ -804,7 +807,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
         Ln.run(RPR_K_ENC_ATTN, 0, 0, [&] {
           return launch_self_attn_bwd(in, dattn, k.mask, k.rel_bias, k.bucket, dbig, P<float>(w.bias_part),
                                       g(k.lay.dec ? K_DEC_REL : K_ENC_REL), k.nseq, k.len, H, d.rel_buckets, k.causal, s,
-                                      drop.on ? &da : nullptr);
+                                      drop.on ? &da : nullptr, d.d_kv);
         });
         break;
     }
@@ -855,13 +858,14 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
 int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, TrainDims& D) {
   RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
   RPR_REQUIRE(bz >= 1 && Lq >= 1 && Lq <= 128, "bz or Lq out of range (the training kernels hold Lq <= 128 keys in LDS)");
-  RPR_REQUIRE(m->d.d_kv == DKV, "the training kernels are written for d_kv == 64 (t5-base / t5-large)");
+  RPR_REQUIRE(m->d.d_kv == DKV || m->d.d_kv == 128, "d_kv must be 64 (t5-base / t5-large) or 128 (t5-3b)");
   RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_DEC_LEN, "smtid length exceeds the model's decoder length");
   RPR_HIP(hipSetDevice(c->device));
   const auto& d = m->d;
   D = train_dims(d, bz, Lq, L, docs);
   RPR_REQUIRE(self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024,
-              "sequence lengths too large for the LDS-resident attention backward");
+              "sequence lengths beyond the 160 KB of LDS the attention backward holds a head in: self-attention max(L, Lq) <= 91, "
+              "cross-attention 130 (docs L + Lq) + 2 docs L (Lq + 1) + Lq floats <= 40960 (the same for 64- and 128-dim heads)");
   int e = alloc_train(c, m, D);
   if (e) return e;
   // the forward's cross-attention kernel needs the per-query key counts: reuse the search workspace's small buffers

@@ -395,6 +395,11 @@ hipError_t launch_colsum_multi(const ColsumSites& p, int d, hipStream_t s) {
 // ---- attention backward: shared pieces ----------------------------------------------------------------------------------
 // LDS rows of Q / K / V / dO are padded to AST = 65 floats: the score phase reads K[j][d] with j across the lanes, and an
 // unpadded 64-float stride would put all of them on one bank.
+// 128-dim heads (t5-3b) keep these 64-column rows and this carve: a head goes through LDS one half of its head dim at a time
+// (template parameter D = 128 of the kernels below; 129-float rows would not hold the fine-tune shape of the reference, two
+// documents of 32 codes against 64 query tokens, in the 160 KB of a CU). The scores and dP are sums over the whole head dim: the
+// first half leaves its partial sums in Ps / Gs, the second continues the same FMA chains from them; softmax and dS run once;
+// dQ / dK / dV (the forward: O) are products along the rows, made for the 64 columns that are staged.
 constexpr int AST = DKV + 1;
 
 __device__ __forceinline__ void stage_row4(float* dst, const float* src) {
@@ -403,7 +408,9 @@ __device__ __forceinline__ void stage_row4(float* dst, const float* src) {
 }
 
 // Ps[i][j] = score (or -inf where !ok), Gs[i][j] = dP = dO_i . V_j, 2 x 2 outputs per thread (half the LDS reads per FMA)
-template <class OK, class BIAS>
+// FIRST / LAST: the staged columns are the first / the last 64 of the head dim. !LAST leaves the raw partial sums of every pair,
+// !FIRST starts from them (each pair belongs to the same thread in both calls)
+template <bool FIRST = true, bool LAST = true, class OK, class BIAS>
 __device__ __forceinline__ void attn_scores_dp(const float* Qs, const float* Ds, const float* Ks, const float* Vs, int nq, int nk,
                                                float* Ps, float* Gs, int PL, OK ok, BIAS bias) {
   const int hq = (nq + 1) >> 1, hk = (nk + 1) >> 1;
@@ -414,6 +421,12 @@ __device__ __forceinline__ void attn_scores_dp(const float* Qs, const float* Ds,
     const float *q0 = Qs + i0 * AST, *q1 = Qs + (vi1 ? i1 : i0) * AST, *o0 = Ds + i0 * AST, *o1 = Ds + (vi1 ? i1 : i0) * AST;
     const float *k0 = Ks + j0 * AST, *k1 = Ks + (vj1 ? j1 : j0) * AST, *v0 = Vs + j0 * AST, *v1 = Vs + (vj1 ? j1 : j0) * AST;
     float s00 = 0.f, s01 = 0.f, s10 = 0.f, s11 = 0.f, g00 = 0.f, g01 = 0.f, g10 = 0.f, g11 = 0.f;
+    if constexpr (!FIRST) {
+      s00 = Ps[i0 * PL + j0]; g00 = Gs[i0 * PL + j0];
+      if (vj1) { s01 = Ps[i0 * PL + j1]; g01 = Gs[i0 * PL + j1]; }
+      if (vi1) { s10 = Ps[i1 * PL + j0]; g10 = Gs[i1 * PL + j0]; }
+      if (vi1 && vj1) { s11 = Ps[i1 * PL + j1]; g11 = Gs[i1 * PL + j1]; }
+    }
 #pragma unroll 8
     for (int d = 0; d < DKV; ++d) {
       const float a0 = q0[d], a1 = q1[d], b0 = k0[d], b1 = k1[d], c0 = o0[d], c1 = o1[d], e0 = v0[d], e1 = v1[d];
@@ -421,9 +434,14 @@ __device__ __forceinline__ void attn_scores_dp(const float* Qs, const float* Ds,
       g00 = fmaf(c0, e0, g00); g01 = fmaf(c0, e1, g01); g10 = fmaf(c1, e0, g10); g11 = fmaf(c1, e1, g11);
     }
     auto put = [&](int i, int j, float sc, float dp) {
-      const bool k = ok(i, j);
-      Ps[i * PL + j] = k ? sc + bias(i, j) : -INFINITY;
-      Gs[i * PL + j] = k ? dp : 0.f;
+      if constexpr (LAST) {
+        const bool k = ok(i, j);
+        Ps[i * PL + j] = k ? sc + bias(i, j) : -INFINITY;
+        Gs[i * PL + j] = k ? dp : 0.f;
+      } else {
+        Ps[i * PL + j] = sc;
+        Gs[i * PL + j] = dp;
+      }
     };
     put(i0, j0, s00, g00);
     if (vj1) put(i0, j1, s01, g01);
@@ -506,14 +524,16 @@ __device__ __forceinline__ void attn_store16(float* dst, int l16, const float (&
 
 // One block per (sequence, head). Everything of the head lives in LDS: Q, K, V, dO [Ls][65], P and dS [Ls][Ls + 1].
 // DROP: the probabilities were dropped out in the forward (self_attn_drop_fwd_kernel); the same mask is drawn again here
-template <bool DROP>
+// D: head dim, 64 or 128 (two halves through the same carve)
+template <bool DROP, int D = DKV>
 __global__ __launch_bounds__(256) void self_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dO,
                                                              const int32_t* __restrict__ mask, const float* __restrict__ rel_bias,
                                                              const int32_t* __restrict__ bucket, float* __restrict__ dqkv,
                                                              float* __restrict__ dbias_part, int S, int Ls, int H, int buckets,
                                                              int causal, DropAttn da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int s = blockIdx.x / H, h = blockIdx.x - s * H, inner = H * DKV, ld = 3 * inner, tid = threadIdx.x;
+  constexpr int NH = D / DKV;           // halves of the head dim
+  const int s = blockIdx.x / H, h = blockIdx.x - s * H, inner = H * D, ld = 3 * inner, tid = threadIdx.x;
   const int PL = Ls + 1, nd = causal ? Ls : 2 * Ls - 1;
   float* Qs = sm;                       // [Ls][AST]
   float* Ks = Qs + Ls * AST;
@@ -526,26 +546,41 @@ __global__ __launch_bounds__(256) void self_attn_bwd_kernel(const float* __restr
   int* bk = reinterpret_cast<int*>(diag + 2 * Ls);   // [nd] bucket of each diagonal
   int* mk = bk + 2 * Ls;                // [Ls] key mask
   const size_t row0 = (size_t)s * Ls;
-  for (int i = tid; i < Ls * 16; i += 256) {
-    const int r = i >> 4, c = (i & 15) * 4;
-    const float* base = qkv + (row0 + r) * ld + h * DKV + c;
-    stage_row4(Qs + r * AST + c, base); stage_row4(Ks + r * AST + c, base + inner); stage_row4(Vs + r * AST + c, base + 2 * inner);
-    stage_row4(Ds + r * AST + c, dO + (row0 + r) * inner + h * DKV + c);
-  }
+  auto stage = [&](int hf, bool with_v) {   // columns 64 hf .. 64 hf + 63 of the head
+    for (int i = tid; i < Ls * 16; i += 256) {
+      const int r = i >> 4, c = (i & 15) * 4;
+      const float* base = qkv + (row0 + r) * ld + h * D + hf * DKV + c;
+      stage_row4(Qs + r * AST + c, base); stage_row4(Ks + r * AST + c, base + inner);
+      if (with_v) stage_row4(Vs + r * AST + c, base + 2 * inner);
+      stage_row4(Ds + r * AST + c, dO + (row0 + r) * inner + h * D + hf * DKV + c);
+    }
+  };
+  stage(0, true);
   if (tid < buckets) Bs[tid] = rel_bias[tid * H + h];
   // diagonal t: causal i - j = t; bidirectional j - i = t - (Ls - 1)
   for (int t = tid; t < nd; t += 256) bk[t] = causal ? bucket[t] : bucket[t - (Ls - 1) + (MAX_LQ - 1)];
   for (int j = tid; j < Ls; j += 256) mk[j] = (causal || mask[row0 + j] != 0) ? 1 : 0;
   __syncthreads();
-  attn_scores_dp(Qs, Ds, Ks, Vs, Ls, Ls, Ps, Gs, PL,
-                 [&](int i, int j) { return causal ? (j <= i) : (mk[j] != 0); },
-                 [&](int i, int j) { return Bs[bk[causal ? i - j : j - i + Ls - 1]]; });
+  auto ok = [&](int i, int j) { return causal ? (j <= i) : (mk[j] != 0); };
+  auto bias = [&](int i, int j) { return Bs[bk[causal ? i - j : j - i + Ls - 1]]; };
+  if constexpr (NH == 1) {
+    attn_scores_dp(Qs, Ds, Ks, Vs, Ls, Ls, Ps, Gs, PL, ok, bias);
+  } else {
+    attn_scores_dp<true, false>(Qs, Ds, Ks, Vs, Ls, Ls, Ps, Gs, PL, ok, bias);
+    __syncthreads();
+    stage(1, true);
+    __syncthreads();
+    attn_scores_dp<false, true>(Qs, Ds, Ks, Vs, Ls, Ls, Ps, Gs, PL, ok, bias);
+  }
   __syncthreads();
   if constexpr (DROP)
     attn_softmax_ds<true>(Ps, Gs, Ls, Ls, PL, [&](int i, int g) { return drop_keep4_attn(da.key, da.site, (uint32_t)s, h, i, g); }, da.key.scale);
   else attn_softmax_ds(Ps, Gs, Ls, Ls, PL);
   __syncthreads();
-  {  // dQ_i = sum_j dS_ij K_j ; dK_j = sum_i dS_ij Q_i ; dV_j = sum_i P_ij dO_i — two rows per thread
+#pragma unroll
+  for (int hf = NH - 1; hf >= 0; --hf) {   // the last half is the one in LDS; 128-dim heads stage the first again (V is not read)
+    if (hf != NH - 1) { __syncthreads(); stage(hf, false); __syncthreads(); }
+    // dQ_i = sum_j dS_ij K_j ; dK_j = sum_i dS_ij Q_i ; dV_j = sum_i P_ij dO_i — two rows per thread
     const int hr = (Ls + 1) >> 1, l16 = tid & 15;
     for (int t = tid >> 4; t < hr; t += 16) {
       const int r0 = t, r1 = (t + hr < Ls) ? t + hr : t;
@@ -553,10 +588,10 @@ __global__ __launch_bounds__(256) void self_attn_bwd_kernel(const float* __restr
       attn_rows_times(Gs, PL, r0, r1, Ks, Ls, l16, dq0, dq1);
       attn_cols_times(Gs, PL, r0, r1, Qs, Ls, l16, dk0, dk1);
       attn_cols_times(Ps, PL, r0, r1, Ds, Ls, l16, dv0, dv1);
-      float* ob = dqkv + (row0 + r0) * ld + h * DKV;
+      float* ob = dqkv + (row0 + r0) * ld + h * D + hf * DKV;
       attn_store16(ob, l16, dq0); attn_store16(ob + inner, l16, dk0); attn_store16(ob + 2 * inner, l16, dv0);
       if (r1 != r0) {
-        ob = dqkv + (row0 + r1) * ld + h * DKV;
+        ob = dqkv + (row0 + r1) * ld + h * D + hf * DKV;
         attn_store16(ob, l16, dq1); attn_store16(ob + inner, l16, dk1); attn_store16(ob + 2 * inner, l16, dv1);
       }
     }
@@ -597,13 +632,18 @@ __global__ __launch_bounds__(512) void bias_reduce_kernel(const float* __restric
 
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
-                                hipStream_t s, const DropAttn* drop) {
-  const AttnLaunch p = plan_self_attn_bwd(SelfAttnBwdIn{S, Ls, H, buckets});
+                                hipStream_t s, const DropAttn* drop, int dkv) {
+  const AttnLaunch p = plan_self_attn_bwd(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
+  if (p.invalid) return hipErrorInvalidValue;
   if (drop) {   // dropped-out probabilities: the VALU kernel at every length (the MFMA plan knows no mask)
     const size_t smem = self_attn_bwd_smem(Ls, buckets);
-    if (p.invalid || smem > 160 * 1024 || Ls > 256) return hipErrorInvalidValue;   // (a lane carries the keep bits of <= 32 keys)
-    hipLaunchKernelGGL(self_attn_bwd_kernel<true>, dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S,
-                       Ls, H, buckets, causal, *drop);
+    if (smem > 160 * 1024 || Ls > 256) return hipErrorInvalidValue;   // (a lane carries the keep bits of <= 32 keys)
+    if (dkv == 128)
+      hipLaunchKernelGGL((self_attn_bwd_kernel<true, 128>), dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv,
+                         dbias_part, S, Ls, H, buckets, causal, *drop);
+    else
+      hipLaunchKernelGGL(self_attn_bwd_kernel<true>, dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S,
+                         Ls, H, buckets, causal, *drop);
     hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
     return hipGetLastError();
   }
@@ -617,6 +657,10 @@ hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t
       hipLaunchKernelGGL(self_attn_bwd_kernel<false>, dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket, dqkv,
                          dbias_part, S, Ls, H, buckets, causal, DropAttn{});
       break;
+    case ATTN_TRAIN_BWD_VALU128:
+      hipLaunchKernelGGL((self_attn_bwd_kernel<false, 128>), dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket,
+                         dqkv, dbias_part, S, Ls, H, buckets, causal, DropAttn{});
+      break;
     default: return hipErrorInvalidValue;
   }
   hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
@@ -627,15 +671,16 @@ hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t
 // keys. q: [bz*n, inner]; K/V of this layer: rows (query, j) at xk/xv + (query*Lq + j) * xld; dO: [bz*n, inner].
 // Outputs dq [bz*n, inner] and dK/dV into dxk/dxv (same layout as xk/xv): every (query, head) block owns its rows
 // and columns, so there is no accumulation across blocks.
-// DROP: as in self_attn_bwd_kernel; row r of the query is position r % da.L of decoder sequence query * (n / da.L) + r / da.L
-template <bool DROP>
+// DROP, D: as in self_attn_bwd_kernel; row r of the query is position r % da.L of decoder sequence query * (n / da.L) + r / da.L
+template <bool DROP, int D = DKV>
 __global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ xk,
                                                               const float* __restrict__ xv, int xld, const int32_t* __restrict__ mask,
                                                               const float* __restrict__ dO, float* __restrict__ dq,
                                                               float* __restrict__ dxk, float* __restrict__ dxv, int n, int Lq, int H,
                                                               DropAttn da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int qi = blockIdx.x / H, h = blockIdx.x - qi * H, inner = H * DKV, tid = threadIdx.x;
+  constexpr int NH = D / DKV;
+  const int qi = blockIdx.x / H, h = blockIdx.x - qi * H, inner = H * D, tid = threadIdx.x;
   const int PL = Lq + 1;
   float* Qs = sm;                     // [n][AST]
   float* Ds = Qs + n * AST;           // dO [n][AST]
@@ -644,19 +689,33 @@ __global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __rest
   float* Ps = Vs + Lq * AST;          // [n][PL]
   float* Gs = Ps + n * PL;            // [n][PL]
   int* mk = reinterpret_cast<int*>(Gs + n * PL);   // [Lq]
-  for (int i = tid; i < n * 16; i += 256) {
-    const int r = i >> 4, c = (i & 15) * 4;
-    const size_t o = ((size_t)qi * n + r) * inner + h * DKV + c;
-    stage_row4(Qs + r * AST + c, q + o); stage_row4(Ds + r * AST + c, dO + o);
-  }
-  for (int i = tid; i < Lq * 16; i += 256) {
-    const int j = i >> 4, c = (i & 15) * 4;
-    const size_t o = ((size_t)qi * Lq + j) * xld + h * DKV + c;
-    stage_row4(Ks + j * AST + c, xk + o); stage_row4(Vs + j * AST + c, xv + o);
-  }
+  auto stage = [&](int hf, bool with_v) {   // columns 64 hf .. 64 hf + 63 of the head
+    for (int i = tid; i < n * 16; i += 256) {
+      const int r = i >> 4, c = (i & 15) * 4;
+      const size_t o = ((size_t)qi * n + r) * inner + h * D + hf * DKV + c;
+      stage_row4(Qs + r * AST + c, q + o); stage_row4(Ds + r * AST + c, dO + o);
+    }
+    for (int i = tid; i < Lq * 16; i += 256) {
+      const int j = i >> 4, c = (i & 15) * 4;
+      const size_t o = ((size_t)qi * Lq + j) * xld + h * D + hf * DKV + c;
+      stage_row4(Ks + j * AST + c, xk + o);
+      if (with_v) stage_row4(Vs + j * AST + c, xv + o);
+    }
+  };
+  stage(0, true);
   for (int j = tid; j < Lq; j += 256) mk[j] = mask[(size_t)qi * Lq + j];
   __syncthreads();
-  attn_scores_dp(Qs, Ds, Ks, Vs, n, Lq, Ps, Gs, PL, [&](int, int j) { return mk[j] != 0; }, [](int, int) { return 0.f; });
+  auto ok = [&](int, int j) { return mk[j] != 0; };
+  auto bias = [](int, int) { return 0.f; };
+  if constexpr (NH == 1) {
+    attn_scores_dp(Qs, Ds, Ks, Vs, n, Lq, Ps, Gs, PL, ok, bias);
+  } else {
+    attn_scores_dp<true, false>(Qs, Ds, Ks, Vs, n, Lq, Ps, Gs, PL, ok, bias);
+    __syncthreads();
+    stage(1, true);
+    __syncthreads();
+    attn_scores_dp<false, true>(Qs, Ds, Ks, Vs, n, Lq, Ps, Gs, PL, ok, bias);
+  }
   __syncthreads();
   if constexpr (DROP) {
     const int docs = n / da.L;
@@ -669,26 +728,31 @@ __global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __rest
   }
   __syncthreads();
   const int l16 = tid & 15;
-  {  // dq_i = sum_j dS_ij K_j
-    const int hr = (n + 1) >> 1;
-    for (int t = tid >> 4; t < hr; t += 16) {
-      const int r0 = t, r1 = (t + hr < n) ? t + hr : t;
-      float a0[4] = {}, a1[4] = {};
-      attn_rows_times(Gs, PL, r0, r1, Ks, Lq, l16, a0, a1);
-      attn_store16(dq + ((size_t)qi * n + r0) * inner + h * DKV, l16, a0);
-      if (r1 != r0) attn_store16(dq + ((size_t)qi * n + r1) * inner + h * DKV, l16, a1);
+#pragma unroll
+  for (int hf = NH - 1; hf >= 0; --hf) {   // the last half is the one in LDS; 128-dim heads stage the first again (V is not read)
+    if (hf != NH - 1) { __syncthreads(); stage(hf, false); __syncthreads(); }
+    const int hc = h * D + hf * DKV;
+    {  // dq_i = sum_j dS_ij K_j
+      const int hr = (n + 1) >> 1;
+      for (int t = tid >> 4; t < hr; t += 16) {
+        const int r0 = t, r1 = (t + hr < n) ? t + hr : t;
+        float a0[4] = {}, a1[4] = {};
+        attn_rows_times(Gs, PL, r0, r1, Ks, Lq, l16, a0, a1);
+        attn_store16(dq + ((size_t)qi * n + r0) * inner + hc, l16, a0);
+        if (r1 != r0) attn_store16(dq + ((size_t)qi * n + r1) * inner + hc, l16, a1);
+      }
     }
-  }
-  {  // dK_j = sum_i dS_ij q_i ; dV_j = sum_i P_ij dO_i
-    const int hr = (Lq + 1) >> 1;
-    for (int t = tid >> 4; t < hr; t += 16) {
-      const int j0 = t, j1 = (t + hr < Lq) ? t + hr : t;
-      float dk0[4] = {}, dk1[4] = {}, dv0[4] = {}, dv1[4] = {};
-      attn_cols_times(Gs, PL, j0, j1, Qs, n, l16, dk0, dk1);
-      attn_cols_times(Ps, PL, j0, j1, Ds, n, l16, dv0, dv1);
-      size_t o = ((size_t)qi * Lq + j0) * xld + h * DKV;
-      attn_store16(dxk + o, l16, dk0); attn_store16(dxv + o, l16, dv0);
-      if (j1 != j0) { o = ((size_t)qi * Lq + j1) * xld + h * DKV; attn_store16(dxk + o, l16, dk1); attn_store16(dxv + o, l16, dv1); }
+    {  // dK_j = sum_i dS_ij q_i ; dV_j = sum_i P_ij dO_i
+      const int hr = (Lq + 1) >> 1;
+      for (int t = tid >> 4; t < hr; t += 16) {
+        const int j0 = t, j1 = (t + hr < Lq) ? t + hr : t;
+        float dk0[4] = {}, dk1[4] = {}, dv0[4] = {}, dv1[4] = {};
+        attn_cols_times(Gs, PL, j0, j1, Qs, n, l16, dk0, dk1);
+        attn_cols_times(Ps, PL, j0, j1, Ds, n, l16, dv0, dv1);
+        size_t o = ((size_t)qi * Lq + j0) * xld + hc;
+        attn_store16(dxk + o, l16, dk0); attn_store16(dxv + o, l16, dv0);
+        if (j1 != j0) { o = ((size_t)qi * Lq + j1) * xld + hc; attn_store16(dxk + o, l16, dk1); attn_store16(dxv + o, l16, dv1); }
+      }
     }
   }
 }
@@ -698,14 +762,22 @@ size_t cross_attn_bwd_smem(int n, int Lq) {
 }
 
 hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, const float* dO,
-                                 float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s, const DropAttn* drop) {
-  const size_t smem = cross_attn_bwd_smem(n, Lq);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
+                                 float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s, const DropAttn* drop,
+                                 int dkv) {
+  const size_t smem = cross_attn_bwd_smem(n, Lq);   // whatever the head dim: 128-dim heads go through the carve in two halves
+  if (smem > 160 * 1024 || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
   // (an fp32-MFMA version — one wave per (query, head), dK / dV accumulated over the row tiles in the matrix cores — measured
   // 91 us against this kernel's 88: one wave per SIMD by its 33 KB of strips; removed)
   if (drop) {
     if (drop->L < 1 || n % drop->L || Lq > 256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cross_attn_bwd_kernel<true>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H, *drop);
+    if (dkv == 128)
+      hipLaunchKernelGGL((cross_attn_bwd_kernel<true, 128>), dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq,
+                         H, *drop);
+    else
+      hipLaunchKernelGGL(cross_attn_bwd_kernel<true>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H, *drop);
+  } else if (dkv == 128) {
+    hipLaunchKernelGGL((cross_attn_bwd_kernel<false, 128>), dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq,
+                       H, DropAttn{});
   } else {
     hipLaunchKernelGGL(cross_attn_bwd_kernel<false>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H,
                        DropAttn{});
@@ -718,17 +790,21 @@ hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* x
 // kernels above (which draw the same mask again): exact fp32 scores, row softmax, P * mul, then O = P V. The inference
 // attention kernels the training forward launches at rate 0 are not touched by any of this.
 // Ps[i][j] = softmax_j(score_ij) * (kept ? scale : 0); keep4(i, g) = the keep bits of keys 4 g .. 4 g + 3 (one Philox block)
-template <class OK, class BIAS, class KEEP4>
+// FIRST / LAST as in attn_scores_dp: !LAST leaves the raw partial scores and does nothing else
+template <bool FIRST = true, bool LAST = true, class OK, class BIAS, class KEEP4>
 __device__ __forceinline__ void attn_probs_drop(const float* Qs, const float* Ks, int nq, int nk, float* Ps, int PL, OK ok, BIAS bias,
                                                 KEEP4 keep4, float scale) {
   for (int p = threadIdx.x; p < nq * nk; p += 256) {
     const int i = p / nk, j = p - i * nk;
     const float *qr = Qs + i * AST, *kr = Ks + j * AST;
     float sc = 0.f;
+    if constexpr (!FIRST) sc = Ps[i * PL + j];
 #pragma unroll 8
     for (int d = 0; d < DKV; ++d) sc = fmaf(qr[d], kr[d], sc);
-    Ps[i * PL + j] = ok(i, j) ? sc + bias(i, j) : -INFINITY;
+    if constexpr (LAST) Ps[i * PL + j] = ok(i, j) ? sc + bias(i, j) : -INFINITY;
+    else Ps[i * PL + j] = sc;
   }
+  if constexpr (!LAST) return;
   __syncthreads();
   const int sub = threadIdx.x & 7;
   for (int i = threadIdx.x >> 3; i < nq; i += 32) {
@@ -749,12 +825,14 @@ __device__ __forceinline__ void attn_probs_drop(const float* Qs, const float* Ks
 }
 
 // block per (sequence, head); qkv [S * Ls][3 inner], out [S * Ls][inner]; LDS carved like self_attn_bwd_kernel's
+template <int D = DKV>
 __global__ __launch_bounds__(256) void self_attn_drop_fwd_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ mask,
                                                                   const float* __restrict__ rel_bias, const int32_t* __restrict__ bucket,
                                                                   float* __restrict__ out, int Ls, int H, int buckets, int causal,
                                                                   DropAttn da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int s = blockIdx.x / H, h = blockIdx.x - s * H, inner = H * DKV, ld = 3 * inner, tid = threadIdx.x;
+  constexpr int NH = D / DKV;
+  const int s = blockIdx.x / H, h = blockIdx.x - s * H, inner = H * D, ld = 3 * inner, tid = threadIdx.x;
   const int PL = Ls + 1, nd = causal ? Ls : 2 * Ls - 1;
   float* Qs = sm;
   float* Ks = Qs + Ls * AST;
@@ -764,78 +842,122 @@ __global__ __launch_bounds__(256) void self_attn_drop_fwd_kernel(const float* __
   int* bk = reinterpret_cast<int*>(Bs + 64);   // [nd]
   int* mk = bk + 2 * Ls;                // [Ls]
   const size_t row0 = (size_t)s * Ls;
-  for (int i = tid; i < Ls * 16; i += 256) {
-    const int r = i >> 4, c = (i & 15) * 4;
-    const float* base = qkv + (row0 + r) * ld + h * DKV + c;
-    stage_row4(Qs + r * AST + c, base); stage_row4(Ks + r * AST + c, base + inner); stage_row4(Vs + r * AST + c, base + 2 * inner);
-  }
+  auto stage = [&](int hf, bool with_qk, bool with_v) {   // columns 64 hf .. 64 hf + 63 of the head
+    for (int i = tid; i < Ls * 16; i += 256) {
+      const int r = i >> 4, c = (i & 15) * 4;
+      const float* base = qkv + (row0 + r) * ld + h * D + hf * DKV + c;
+      if (with_qk) { stage_row4(Qs + r * AST + c, base); stage_row4(Ks + r * AST + c, base + inner); }
+      if (with_v) stage_row4(Vs + r * AST + c, base + 2 * inner);
+    }
+  };
+  stage(0, true, NH == 1);
   if (tid < buckets) Bs[tid] = rel_bias[tid * H + h];
   for (int t = tid; t < nd; t += 256) bk[t] = causal ? bucket[t] : bucket[t - (Ls - 1) + (MAX_LQ - 1)];
   for (int j = tid; j < Ls; j += 256) mk[j] = (causal || mask[row0 + j] != 0) ? 1 : 0;
   __syncthreads();
-  attn_probs_drop(Qs, Ks, Ls, Ls, Ps, PL, [&](int i, int j) { return causal ? (j <= i) : (mk[j] != 0); },
-                  [&](int i, int j) { return Bs[bk[causal ? i - j : j - i + Ls - 1]]; },
-                  [&](int i, int g) { return drop_keep4_attn(da.key, da.site, (uint32_t)s, h, i, g); }, da.key.scale);
+  auto ok = [&](int i, int j) { return causal ? (j <= i) : (mk[j] != 0); };
+  auto bias = [&](int i, int j) { return Bs[bk[causal ? i - j : j - i + Ls - 1]]; };
+  auto keep4 = [&](int i, int g) { return drop_keep4_attn(da.key, da.site, (uint32_t)s, h, i, g); };
+  if constexpr (NH == 1) {
+    attn_probs_drop(Qs, Ks, Ls, Ls, Ps, PL, ok, bias, keep4, da.key.scale);
+  } else {
+    attn_probs_drop<true, false>(Qs, Ks, Ls, Ls, Ps, PL, ok, bias, keep4, da.key.scale);
+    __syncthreads();
+    stage(1, true, true);
+    __syncthreads();
+    attn_probs_drop<false, true>(Qs, Ks, Ls, Ls, Ps, PL, ok, bias, keep4, da.key.scale);
+  }
   const int hr = (Ls + 1) >> 1, l16 = tid & 15;
-  for (int t = tid >> 4; t < hr; t += 16) {
-    const int r0 = t, r1 = (t + hr < Ls) ? t + hr : t;
-    float o0[4] = {}, o1[4] = {};
-    attn_rows_times(Ps, PL, r0, r1, Vs, Ls, l16, o0, o1);
-    attn_store16(out + (row0 + r0) * inner + h * DKV, l16, o0);
-    if (r1 != r0) attn_store16(out + (row0 + r1) * inner + h * DKV, l16, o1);
+#pragma unroll
+  for (int hf = NH - 1; hf >= 0; --hf) {   // O = P V for the staged 64 columns of V; 128-dim heads stage V's first half last
+    if (hf != NH - 1) { __syncthreads(); stage(hf, false, true); __syncthreads(); }
+    for (int t = tid >> 4; t < hr; t += 16) {
+      const int r0 = t, r1 = (t + hr < Ls) ? t + hr : t;
+      float o0[4] = {}, o1[4] = {};
+      attn_rows_times(Ps, PL, r0, r1, Vs, Ls, l16, o0, o1);
+      attn_store16(out + (row0 + r0) * inner + h * D + hf * DKV, l16, o0);
+      if (r1 != r0) attn_store16(out + (row0 + r1) * inner + h * D + hf * DKV, l16, o1);
+    }
   }
 }
 
 // block per (query, head): the n = docs * L decoder rows of the query against its Lq encoder keys (layouts: cross_attn_bwd_kernel)
+template <int D = DKV>
 __global__ __launch_bounds__(256) void cross_attn_drop_fwd_kernel(const float* __restrict__ q, const float* __restrict__ xk,
                                                                    const float* __restrict__ xv, int xld, const int32_t* __restrict__ mask,
                                                                    float* __restrict__ out, int n, int Lq, int H, DropAttn da) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int qi = blockIdx.x / H, h = blockIdx.x - qi * H, inner = H * DKV, tid = threadIdx.x;
+  constexpr int NH = D / DKV;
+  const int qi = blockIdx.x / H, h = blockIdx.x - qi * H, inner = H * D, tid = threadIdx.x;
   const int PL = Lq + 1, docs = n / da.L;
   float* Qs = sm;                     // [n][AST]
   float* Ks = Qs + n * AST;           // [Lq][AST]
   float* Vs = Ks + Lq * AST;
   float* Ps = Vs + Lq * AST;          // [n][PL]
   int* mk = reinterpret_cast<int*>(Ps + n * PL);   // [Lq]
-  for (int i = tid; i < n * 16; i += 256) {
-    const int r = i >> 4, c = (i & 15) * 4;
-    stage_row4(Qs + r * AST + c, q + ((size_t)qi * n + r) * inner + h * DKV + c);
-  }
-  for (int i = tid; i < Lq * 16; i += 256) {
-    const int j = i >> 4, c = (i & 15) * 4;
-    const size_t o = ((size_t)qi * Lq + j) * xld + h * DKV + c;
-    stage_row4(Ks + j * AST + c, xk + o); stage_row4(Vs + j * AST + c, xv + o);
-  }
+  auto stage = [&](int hf, bool with_qk, bool with_v) {   // columns 64 hf .. 64 hf + 63 of the head
+    if (with_qk)
+      for (int i = tid; i < n * 16; i += 256) {
+        const int r = i >> 4, c = (i & 15) * 4;
+        stage_row4(Qs + r * AST + c, q + ((size_t)qi * n + r) * inner + h * D + hf * DKV + c);
+      }
+    for (int i = tid; i < Lq * 16; i += 256) {
+      const int j = i >> 4, c = (i & 15) * 4;
+      const size_t o = ((size_t)qi * Lq + j) * xld + h * D + hf * DKV + c;
+      if (with_qk) stage_row4(Ks + j * AST + c, xk + o);
+      if (with_v) stage_row4(Vs + j * AST + c, xv + o);
+    }
+  };
+  stage(0, true, NH == 1);
   for (int j = tid; j < Lq; j += 256) mk[j] = mask[(size_t)qi * Lq + j];
   __syncthreads();
-  attn_probs_drop(Qs, Ks, n, Lq, Ps, PL, [&](int, int j) { return mk[j] != 0; }, [](int, int) { return 0.f; }, [&](int r, int g) {
+  auto ok = [&](int, int j) { return mk[j] != 0; };
+  auto bias = [](int, int) { return 0.f; };
+  auto keep4 = [&](int r, int g) {
     const int doc = r / da.L;
     return drop_keep4_attn(da.key, da.site, (uint32_t)(qi * docs + doc), h, r - doc * da.L, g);
-  }, da.key.scale);
+  };
+  if constexpr (NH == 1) {
+    attn_probs_drop(Qs, Ks, n, Lq, Ps, PL, ok, bias, keep4, da.key.scale);
+  } else {
+    attn_probs_drop<true, false>(Qs, Ks, n, Lq, Ps, PL, ok, bias, keep4, da.key.scale);
+    __syncthreads();
+    stage(1, true, true);
+    __syncthreads();
+    attn_probs_drop<false, true>(Qs, Ks, n, Lq, Ps, PL, ok, bias, keep4, da.key.scale);
+  }
   const int hr = (n + 1) >> 1, l16 = tid & 15;
-  for (int t = tid >> 4; t < hr; t += 16) {
-    const int r0 = t, r1 = (t + hr < n) ? t + hr : t;
-    float o0[4] = {}, o1[4] = {};
-    attn_rows_times(Ps, PL, r0, r1, Vs, Lq, l16, o0, o1);
-    attn_store16(out + ((size_t)qi * n + r0) * inner + h * DKV, l16, o0);
-    if (r1 != r0) attn_store16(out + ((size_t)qi * n + r1) * inner + h * DKV, l16, o1);
+#pragma unroll
+  for (int hf = NH - 1; hf >= 0; --hf) {   // O = P V for the staged 64 columns of V; 128-dim heads stage V's first half last
+    if (hf != NH - 1) { __syncthreads(); stage(hf, false, true); __syncthreads(); }
+    for (int t = tid >> 4; t < hr; t += 16) {
+      const int r0 = t, r1 = (t + hr < n) ? t + hr : t;
+      float o0[4] = {}, o1[4] = {};
+      attn_rows_times(Ps, PL, r0, r1, Vs, Lq, l16, o0, o1);
+      attn_store16(out + ((size_t)qi * n + r0) * inner + h * D + hf * DKV, l16, o0);
+      if (r1 != r0) attn_store16(out + ((size_t)qi * n + r1) * inner + h * D + hf * DKV, l16, o1);
+    }
   }
 }
 
 hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, const float* rel_bias, const int32_t* bucket, float* out,
-                                     int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s) {
+                                     int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s, int dkv) {
   const size_t smem = self_attn_bwd_smem(Ls, buckets);   // (the backward's carve holds this kernel's: the step was admitted by it)
-  if (smem > 160 * 1024 || buckets > 64 || Ls < 1 || Ls > MAX_LQ || (!causal && !mask)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(self_attn_drop_fwd_kernel, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets, causal,
-                     drop);
+  if (smem > 160 * 1024 || buckets > 64 || Ls < 1 || Ls > MAX_LQ || (!causal && !mask) || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
+  if (dkv == 128)
+    hipLaunchKernelGGL(self_attn_drop_fwd_kernel<128>, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets,
+                       causal, drop);
+  else
+    hipLaunchKernelGGL(self_attn_drop_fwd_kernel<DKV>, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets,
+                       causal, drop);
   return hipGetLastError();
 }
 hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
-                                      int n, int Lq, int H, const DropAttn& drop, hipStream_t s) {
+                                      int n, int Lq, int H, const DropAttn& drop, hipStream_t s, int dkv) {
   const size_t smem = cross_attn_bwd_smem(n, Lq);
-  if (smem > 160 * 1024 || drop.L < 1 || n % drop.L) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(cross_attn_drop_fwd_kernel, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
+  if (smem > 160 * 1024 || drop.L < 1 || n % drop.L || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
+  if (dkv == 128) hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<128>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
+  else hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<DKV>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
   return hipGetLastError();
 }
 
@@ -1625,7 +1747,10 @@ hipError_t init_train_kernel_attributes() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
   for (const void* k : {reinterpret_cast<const void*>(self_attn_bwd_kernel<true>), reinterpret_cast<const void*>(cross_attn_bwd_kernel<true>),
-                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel)}) {
+                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel<DKV>), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel<DKV>),
+                        reinterpret_cast<const void*>(self_attn_bwd_kernel<false, 128>), reinterpret_cast<const void*>(self_attn_bwd_kernel<true, 128>),
+                        reinterpret_cast<const void*>(cross_attn_bwd_kernel<false, 128>), reinterpret_cast<const void*>(cross_attn_bwd_kernel<true, 128>),
+                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel<128>), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel<128>)}) {
     e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
   }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised check of the ranking fine-tune step on the GPU (diagnostic; `python tools/fuzz_train.py [n_cases] [seed]`):
-mini-dims models, random batch shapes (bz 1..7, smtid length 8 / 16 / 32, codebook sizes 256 / 100 / 72, query lengths 6..30 with ragged padding), every
+mini-dims models (a quarter of them with 12 heads of d_kv = 128, the `wide` cases of tools/fuzz_parity.py), random batch shapes (bz 1..7, smtid length 8 / 16 / 32, codebook sizes 256 / 100 / 72, query lengths 6..30 with ragged padding), every
 GEMM arithmetic (f16x2, bf16, exact f32). HIP gradients of rpr_lngknp_backward against torch autograd through the CPU oracle
 (oracle/train_ref.py), tensor by tensor: split-precision and fp32 modes at rounding level (median tensor within 2e-5 of its scale,
 every tensor's cosine >= 0.9999, global norm within 1e-4; a ReLU-boundary flip may move single rows more and is reported),
@@ -36,9 +36,10 @@ for case in range(n_cases):
     bz, L, seed = rng.randint(1, 7), rng.choice([8, 16, 32]), rng.randint(1, 10_000)
     V, max_len = rng.choice([256, 256, 100, 72]), rng.randint(8, 30)
     enc_layers, d_ff = rng.choice([1, 2]), rng.choice([128, 256])
+    wide = rng.random() < 0.25                       # 128-dim heads: the two-half attention backward (inner 1536 = 2 d_model)
     if only is not None and case != only:
         continue
-    dims = synth.mini_dims(L=L, V=V, enc_layers=enc_layers, d_ff=d_ff)
+    dims = synth.mini_dims(L=L, V=V, enc_layers=enc_layers, d_ff=d_ff, **(dict(d_kv=128) if wide else {}))
     g = G()
     g.bz, g.L, g.V, g.dims, g.seed = bz, L, V, dims, seed
     g.state_dict = synth.make_state_dict(dims, seed=seed)
@@ -52,7 +53,7 @@ for case in range(n_cases):
     teacher = {k: z[k] for k in z.files if k.endswith("_scores") and "teacher" in k}
     losses_ref, total_ref, og, gn_ref = train_ref.train_step(t5_ref.T5Ref(g.state_dict, g.dims), ids, mask, z["pos_doc_encoding"],
                                                               z["neg_doc_encoding"], teacher)
-    line = [f"case {case:2d}: bz={bz} L={L} V={V} Lq={ids.shape[1]} enc={dims.num_layers} dff={dims.d_ff}"]
+    line = [f"case {case:2d}: bz={bz} L={L} V={V} Lq={ids.shape[1]} enc={dims.num_layers} dff={dims.d_ff} d_kv={dims.d_kv}"]
     for prec in precs:
         ctx.set_precision(prec)
         try:

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""Time the ranking fine-tune step (BASELINE config 5): t5-base dims, bz examples per step PER GPU, two teacher-forced
+"""Time the ranking fine-tune step (BASELINE config 5): t5-base dims (--dims t5-3b: d_model 1024, 32 heads of 128, d_ff 16384,
+24 + 24 layers, the dims of bench.py's secondary_t5_3b), bz examples per step PER GPU, two teacher-forced
 passes of L = 32 positions over queries of ~16 tokens, backward, gradient all-reduce (RCCL when launched on several
 ranks), AdamW. --loss seq2seq: the seq2seq docid cross-entropy step instead (one teacher-forced pass per query, the
 codebook-logit head). Rank 0 prints one JSON line (examples/s of the whole job, max step time over the ranks).
-Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq]
+--precision and --loss take comma-separated lists: one JSON line per (precision, loss) on ONE model load (t5-3b: 11 GB of
+weights to generate and upload). --embed: before the steps, time rpr_embed on 128 texts of ~16 tokens and 128 texts of 128
+tokens (one JSON line).
+Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq] [--dims t5-base|t5-3b] [--embed]
        python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/train_bench.py"""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -11,15 +15,33 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ripor_amd import engine as E
 from ripor_amd.utils import synth
 
+PRECISIONS, LOSSES = ["f16x2", "f32", "bf16"], ["lngknp", "seq2seq"]
+
+
+def listed(choices):
+    def parse(v):
+        got = v.split(",")
+        if any(x not in choices for x in got):
+            raise argparse.ArgumentTypeError(f"comma-separated values of {choices}")
+        return got
+    return parse
+
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--bz", type=int, default=128)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--len", type=int, default=32, dest="L")
-ap.add_argument("--precision", default="f16x2", choices=["f16x2", "f32", "bf16"])
-ap.add_argument("--loss", default="lngknp", choices=["lngknp", "seq2seq"])
+ap.add_argument("--precision", default=["f16x2"], type=listed(PRECISIONS))
+ap.add_argument("--loss", default=["lngknp"], type=listed(LOSSES))
+ap.add_argument("--dims", default="t5-base", choices=["t5-base", "t5-3b"])
+ap.add_argument("--embed", action="store_true")
 args = ap.parse_args()
 L, V, bz = args.L, 256, args.bz
-dims = synth.t5_base_dims(L=L, V=V)
+if args.dims == "t5-3b":
+    dims = synth.ModelDims(d_model=1024, d_kv=128, d_ff=16384, num_layers=24, num_decoder_layers=24, num_heads=32,
+                           decoder_vocab_sizes=[V] * L)
+else:
+    dims = synth.t5_base_dims(L=L, V=V)
 rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
 torch.cuda.set_device(local)
 if world > 1:
@@ -27,7 +49,7 @@ if world > 1:
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
 ctx = E.Context.get(local)
-ctx.set_precision(args.precision)
+ctx.set_precision(args.precision[0])
 model = E.DeviceModel(ctx, synth.make_state_dict(dims), dims)
 state = E.TrainState(model)
 ids, mask = synth.make_queries(bz * world, vocab_size=dims.vocab_size, seed=5, mean_len=16, std_len=5, min_len=6, max_len=64)
@@ -44,39 +66,66 @@ ids_t, mask_t, codes_t = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cu
 labels_t = codes_t[:, 0].contiguous()   # seq2seq: one smtid per query
 
 
-def step():   # backward with the bucketed gradient exchange overlapped (RPR_GRAD_OVERLAP=0: serial), clip, AdamW
-    if args.loss == "seq2seq":
-        return E.seq2seq_train_step(model, state, ids_t, mask_t, labels_t, lr=1e-6)
-    return E.train_step(model, state, ids_t, mask_t, codes_t, tp, tn, prefix, lr=1e-6)
+def embed_leg():   # dense embeddings (rpr_embed): 128 texts per call, queries of ~16 tokens and passages of 128
+    out = {"task": "rpr_embed, " + args.dims + " dims, 128 texts per call", "ms_per_call": {}}
+    for prec in [p for p in args.precision if p != "bf16"] or ["f16x2"]:   # (bf16 is the arithmetic of the training steps only)
+        ctx.set_precision(prec)
+        for name, kw in (("16_tokens", dict(mean_len=16, std_len=5, min_len=6, max_len=64)), ("128_tokens", dict(fixed_len=128))):
+            ei, em = synth.make_queries(128, vocab_size=dims.vocab_size, seed=5, **kw)
+            ei, em = torch.from_numpy(ei).cuda(), torch.from_numpy(em).cuda()
+            E.embed(model, ei, em); torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                E.embed(model, ei, em)
+            torch.cuda.synchronize()
+            out["ms_per_call"][f"{prec}/{name}"] = round((time.perf_counter() - t0) / args.steps * 1e3, 3)
+    ctx.set_precision(args.precision[0])
+    print(json.dumps(out), flush=True)
 
 
-first = step(); torch.cuda.synchronize()
-if world > 1: dist.barrier()
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(args.steps):
-    last = step()
-torch.cuda.synchronize()
-if world > 1: dist.barrier()
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / args.steps
-if world > 1:
-    t = torch.tensor([dt], device="cuda"); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t)
-ctx.profile_reset(); ctx.profile_enable(True)
-if args.loss == "seq2seq":
-    E.seq2seq_backward(model, state, ids_t, mask_t, labels_t)
-else:
-    E.lngknp_backward(model, state, ids_t, mask_t, codes_t, tp, tn, prefix)
-torch.cuda.synchronize()
-st = ctx.profile_get(); ctx.profile_enable(False)
-flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * 768 * 768 + 2 * 768 * 3072) + 12 * 2 * 768 * 768)
-                   + bz * (1 if args.loss == "seq2seq" else 2) * L * 12 * (6 * 768 * 768 + 2 * 768 * 3072)
-                   + (bz * L * V * 768 if args.loss == "seq2seq" else 0))
-if rank == 0:
-  task = ("seq2seq docid cross-entropy step" if args.loss == "seq2seq" else "lng_knp margin-MSE fine-tune step")
-  print(json.dumps({"task": task + " (forward + backward + gradient all-reduce + AdamW), t5-base dims", "loss": args.loss,
-                  "gemm_precision": args.precision, "n_gpus": world, "scaling": "weak", "bz_per_gpu": bz,
-                  "bz": bz, "L": L, "enc_len_padded": int(Lq), "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
-                  "loss_first": [float(x) for x in first], "loss_last": [float(x) for x in last],
-                  "params": state.total, "approx_tflops": 3 * flops_fwd / dt / 1e12,
-                  "backward_kernel_ms": {k: round(v["total_ms"], 3) for k, v in st.items()}}))
+def leg(precision, loss):
+    ctx.set_precision(precision)
+
+    def step():   # backward with the bucketed gradient exchange overlapped (RPR_GRAD_OVERLAP=0: serial), clip, AdamW
+        if loss == "seq2seq":
+            return E.seq2seq_train_step(model, state, ids_t, mask_t, labels_t, lr=1e-6)
+        return E.train_step(model, state, ids_t, mask_t, codes_t, tp, tn, prefix, lr=1e-6)
+
+    first = step(); torch.cuda.synchronize()
+    if world > 1: dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        last = step()
+    torch.cuda.synchronize()
+    if world > 1: dist.barrier()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / args.steps
+    if world > 1:
+        t = torch.tensor([dt], device="cuda"); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t)
+    ctx.profile_reset(); ctx.profile_enable(True)
+    if loss == "seq2seq":
+        E.seq2seq_backward(model, state, ids_t, mask_t, labels_t)
+    else:
+        E.lngknp_backward(model, state, ids_t, mask_t, codes_t, tp, tn, prefix)
+    torch.cuda.synchronize()
+    st = ctx.profile_get(); ctx.profile_enable(False)
+    dm, inner, dff, nd = dims.d_model, dims.inner, dims.d_ff, dims.num_decoder_layers
+    flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * dm * inner + 2 * dm * dff) + nd * 2 * dm * inner)
+                       + bz * (1 if loss == "seq2seq" else 2) * L * nd * (6 * dm * inner + 2 * dm * dff)
+                       + (bz * L * V * dm if loss == "seq2seq" else 0))
+    if rank == 0:
+        task = ("seq2seq docid cross-entropy step" if loss == "seq2seq" else "lng_knp margin-MSE fine-tune step")
+        print(json.dumps({"task": task + " (forward + backward + gradient all-reduce + AdamW), " + args.dims + " dims", "loss": loss,
+                          "gemm_precision": precision, "n_gpus": world, "scaling": "weak", "bz_per_gpu": bz,
+                          "bz": bz, "L": L, "enc_len_padded": int(Lq), "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
+                          "loss_first": [float(x) for x in first], "loss_last": [float(x) for x in last],
+                          "params": state.total, "approx_tflops": 3 * flops_fwd / dt / 1e12,
+                          "backward_kernel_ms": {k: round(v["total_ms"], 3) for k, v in st.items()}}), flush=True)
+
+
+if args.embed and rank == 0:
+    embed_leg()
+for precision in args.precision:
+    for loss in args.loss:
+        leg(precision, loss)
