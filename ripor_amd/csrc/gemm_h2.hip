@@ -306,15 +306,14 @@ __device__ __forceinline__ void h2_epilogue_strip(const GemmH2Args& g, typename 
                                                   int wm, int wn, const float* rs_tile, float acc_scale, int Mlim) {
   constexpr int SH = 64, SW = TN * 32;
   const int ncol = lane & 31, rsub = 4 * (lane >> 5);
-  if constexpr (M16) {   // the 16 x 16 C/D map: lane = column lane & 15, rows 4 (lane >> 4) + r of its tile
-    const int c16 = lane & 15, r16 = 4 * (lane >> 4);
+  if constexpr (M16) {   // the 16 x 16 C/D map with the fp32 column map of the body (column 4 c + j): lane = rows 4 (lane >> 4) + r,
+    const int c16 = lane & 15, r16 = 4 * (lane >> 4);   // its four tiles = four consecutive floats of a staged row
 #pragma unroll
     for (int ii = 0; ii < SH / 16; ++ii)
 #pragma unroll
-      for (int j = 0; j < 2 * TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          stg[(ii * 16 + r16 + r) * SW + j * 16 + c16] = acc[strip * (SH / 16) + ii][j][r];
+      for (int r = 0; r < 4; ++r)
+        *reinterpret_cast<f32x4*>(stg + (ii * 16 + r16 + r) * SW + 4 * c16) =
+            f32x4{acc[strip * (SH / 16) + ii][0][r], acc[strip * (SH / 16) + ii][1][r], acc[strip * (SH / 16) + ii][2][r], acc[strip * (SH / 16) + ii][3][r]};
   } else
 #pragma unroll
     for (int ii = 0; ii < SH / 32; ++ii)
@@ -546,7 +545,7 @@ __device__ __forceinline__ void h2_epilogue_strip(const GemmH2Args& g, typename 
     };
     if (BOUT && (g.out_b || g.out_bt)) {
       if (g.mask_src) bf16_path(std::true_type{}); else bf16_path(std::false_type{});
-    } else if (g.out_h) {
+    } else if (!M16 && g.out_h) {   // (M16: plane outputs never come here, h2_epilogue_256)
       if (g.resid_h) planes_path(std::true_type{}); else planes_path(std::false_type{});
     } else {
       if (g.rm_B) { if (g.resid) fp32_path(std::true_type{}, std::true_type{}); else fp32_path(std::false_type{}, std::true_type{}); }
@@ -554,6 +553,157 @@ __device__ __forceinline__ void h2_epilogue_strip(const GemmH2Args& g, typename 
       else fp32_path(std::false_type{}, std::false_type{});
     }
     __builtin_amdgcn_wave_barrier();                  // stg is rewritten by the next strip
+}
+
+// ---- register epilogue of the 16x16x32 body (gemm_h2_pp_kernel<FULL, false, true>): rows from the accumulators -------------
+// The 16 x 16 C/D map gives lane (c = lane & 15, gq = lane >> 4) rows 4 gq .. 4 gq + 3 of ONE column per tile — and which W
+// row a tile's column c is, is decided where the W rows are DMA'd into LDS (PP_SRC_SETUP, gemm_h2_pp_body.inc), not by the
+// product. The body loads them so that a lane's four W tiles j are neighbouring columns, and the per-element arithmetic below
+// (planes_path's / fp32_path's of h2_epilogue_strip) runs on the accumulators where they are: no LDS write, read-back or wave
+// barrier (the row scales still come from rs_tile), the same 32 16-byte stores per wave with the staged path's store pattern.
+//   fp32 outputs:  column 4 c + j. acc[it][0..3][r] are four consecutive floats of row 16 it + 4 gq + r; the 16 lanes of a
+//                  group write its 256 contiguous bytes, a store instruction four whole rows (as fp32_path: 16 lanes per row).
+//   plane outputs: column 8 (c & 7) + 4 (c >> 3) + j. Lanes c and c ^ 8 hold the two halves of the 8-column piece c & 7 in
+//                  every row; per row pair (2p, 2p + 1) they trade one half (DPP row_ror:8, no LDS): lane c < 8 ends with the
+//                  8 columns of row 2p, lane c >= 8 with those of row 2p + 1 — one 16-byte store per plane, eight lanes per
+//                  128-byte row, eight rows per instruction (as planes_path). The row sums are added over those eight lanes
+//                  in planes_path's order (lane xor 4, 2, 1), with DPP.
+// (Feeding the W fragment as the MFMA's FIRST operand instead — a lane then holds four consecutive columns of one row without
+// any of this — was built and measured first: neighbouring lanes then hold different ROWS, every lane's 16 bytes is a memory
+// request of its own, and the headline fell by 1.9 %; profiles/r17_direct_epilogue_ab.txt.)
+// Residual pieces (RES) are requested with unconditional clamped loads one A tile at a time and three tiles ahead: the wait
+// for a tile's pieces leaves the stores of the two tiles before it in flight (vmcnt counts loads and stores in issue order;
+// rule (1) of the strip's comment). Three tiles are 48 registers beside the 128 accumulators; four spilled.
+template <int CTRL>
+__device__ __forceinline__ float h2_dpp(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+}
+constexpr int DPP_ROR8 = 0x128, DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_XOR3 = 0x1B, DPP_HALF_MIRROR = 0x141;   // (half mirror = xor 7)
+
+template <bool FULL, bool RES>
+__device__ __forceinline__ void h2_direct16_planes(const GemmH2Args& g, f32x4 (&acc)[8][4], int lane, int bm, int bn, int wm, int wn,
+                                                   const float* rs_tile, float acc_scale, int Mlim) {
+  const int c = lane & 15, gq = lane >> 4;
+  const bool hi = c >= 8;                              // this lane ends with the odd row of a pair
+  const int lrow0 = wm * 128 + 4 * gq + (hi ? 1 : 0), mrow0 = bm + lrow0;   // row pair p of A tile it: + 16 it + 2 p
+  const int n0 = bn + wn * 64 + 8 * (c & 7);
+  const bool ncol_ok = FULL || (n0 < g.N);             // N % 32 == 0
+  const float ps = g.plane_scale;
+  float amax = 0.f;
+  float scs[16];   // row scales: read with the residual pieces, a batch ahead of their use
+  auto load = [&](auto it_c, uint4 (&q)[4]) __attribute__((always_inline)) {
+    constexpr int it = decltype(it_c)::value;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      scs[2 * it + p] = rs_tile ? rs_tile[lrow0 + 16 * it + 2 * p] : 1.0f;
+      if (RES) {
+        const int m = min(mrow0 + 16 * it + 2 * p, Mlim - 1), nc = ncol_ok ? n0 : 0;   // clamped, unconditional (see planes_path)
+        q[2 * p] = *reinterpret_cast<const uint4*>(g.resid_h + (size_t)m * g.ldrh + nc);
+        q[2 * p + 1] = *reinterpret_cast<const uint4*>(g.resid_h + g.r_ps + (size_t)m * g.ldrh + nc);
+      }
+    }
+  };
+  auto tile = [&](auto it_c, const uint4 (&q)[4]) __attribute__((always_inline)) {
+    constexpr int it = decltype(it_c)::value;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      // the half this lane does not keep goes to lane c ^ 8, whose other half comes back
+      f32x4 v0, v1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float got = h2_dpp<DPP_ROR8>(hi ? acc[it][j][2 * p] : acc[it][j][2 * p + 1]);
+        v0[j] = hi ? got : acc[it][j][2 * p];
+        v1[j] = hi ? acc[it][j][2 * p + 1] : got;
+      }
+      const int m = mrow0 + 16 * it + 2 * p;
+      const bool ok = ncol_ok && (FULL || m < Mlim);
+      const float sc = rs_tile ? acc_scale * scs[2 * it + p] : acc_scale;
+      f32x2 v[4] = {{v0[0], v0[1]}, {v0[2], v0[3]}, {v1[0], v1[1]}, {v1[2], v1[3]}};
+      f16x2 h[4], l[4];
+      f32x2 ss2 = {0.f, 0.f};
+      float am = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        f32x2 x = v[e] * sc;
+        if (g.relu) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); }
+        if (RES) {   // the residual from its planes: (hi + lo) / X_PLANE_SCALE, both steps exact in fp32
+          x += (__builtin_convertvector(reinterpret_cast<const f16x2*>(&q[2 * p])[e], f32x2) +
+                __builtin_convertvector(reinterpret_cast<const f16x2*>(&q[2 * p + 1])[e], f32x2)) * (1.0f / X_PLANE_SCALE);
+        }
+        ss2 += x * x;
+        f32x2 xs = x * ps;
+        am = fmaxf(am, fmaxf(fabsf(xs.x), fabsf(xs.y)));
+        xs.x = __builtin_amdgcn_fmed3f(xs.x, -65504.f, 65504.f);
+        xs.y = __builtin_amdgcn_fmed3f(xs.y, -65504.f, 65504.f);
+        h[e] = __builtin_convertvector(xs, f16x2);
+        l[e] = __builtin_convertvector(xs - __builtin_convertvector(h[e], f32x2), f16x2);
+      }
+      float ss = ss2.x + ss2.y;
+      if (ok) {
+        *reinterpret_cast<uint4*>(g.out_h + (size_t)m * g.ldoh + n0) = *reinterpret_cast<uint4*>(h);
+        *reinterpret_cast<uint4*>(g.out_h + g.o_ps + (size_t)m * g.ldoh + n0) = *reinterpret_cast<uint4*>(l);
+        amax = fmaxf(amax, am);
+      }
+      if (g.ssq_out) {   // the eight lanes c & 8 .. + 7 hold this wave's 64 columns of output row m
+        if (!ok) ss = 0.f;
+        ss += h2_dpp<DPP_XOR3>(h2_dpp<DPP_HALF_MIRROR>(ss));   // lane ^ 4
+        ss += h2_dpp<DPP_XOR2>(ss);
+        ss += h2_dpp<DPP_XOR1>(ss);
+        if ((c & 7) == 0 && (FULL || m < Mlim)) atomicAdd(g.ssq_out + m, ssq_to_fix(ss, g.sat));
+      }
+    }
+  };
+  // (amax is pinned after every tile: the compiler otherwise sinks each tile's range check to the single use of amax
+  // behind the last tile and keeps all 128 scaled values alive until then — they spilled)
+#define H2_PIN_AMAX() asm volatile("" : "+v"(amax)); __builtin_amdgcn_sched_barrier(0)
+  using std::integral_constant;
+  uint4 qa[4], qb[4], qc[4];   // three A tiles of residual pieces in flight
+#define H2_T(it, q) tile(integral_constant<int, it>{}, q); H2_PIN_AMAX()
+#define H2_L(it, q) load(integral_constant<int, it>{}, q); __builtin_amdgcn_sched_barrier(0)
+  H2_L(0, qa); H2_L(1, qb); H2_L(2, qc);
+  H2_T(0, qa); H2_L(3, qa);
+  H2_T(1, qb); H2_L(4, qb);
+  H2_T(2, qc); H2_L(5, qc);
+  H2_T(3, qa); H2_L(6, qa);
+  H2_T(4, qb); H2_L(7, qb);
+  H2_T(5, qc); H2_T(6, qa); H2_T(7, qb);
+#undef H2_T
+#undef H2_L
+#undef H2_PIN_AMAX
+  if (amax > 65504.f && g.sat) *g.sat = 1u;
+}
+
+// fp32 outputs without residual or K/V map (q / k / v of a fused-norm input): fp32_path's arithmetic and store pattern.
+template <bool FULL>
+__device__ __forceinline__ void h2_direct16_fp32(const GemmH2Args& g, f32x4 (&acc)[8][4], int lane, int bm, int bn, int wm, int wn,
+                                                 const float* rs_tile, float acc_scale, int Mlim) {
+  const int c = lane & 15, gq = lane >> 4;
+  const int lrow0 = wm * 128 + 4 * gq, mrow0 = bm + lrow0;   // row r of A tile it: + 16 it + r
+  const float relu_lo = g.relu ? 0.f : -INFINITY;
+  const int n0 = bn + wn * 64 + 4 * c;                  // first of this lane's 4 consecutive output columns
+  const bool ncol_ok = FULL || (n0 < g.N);
+  const int oi = ncol_ok ? n0 / g.split_n : 0, on = n0 - oi * g.split_n;
+  // (selects, not g.out[oi]: see fp32_path)
+  float* outp = (oi == 0 ? g.out[0] : oi == 1 ? g.out[1] : g.out[2]) + (size_t)blockIdx.y * g.part_stride;
+  const int ldo = oi == 0 ? g.ldo[0] : oi == 1 ? g.ldo[1] : g.ldo[2];
+#pragma unroll
+  for (int ib = 0; ib < 8; ib += 4) {
+    f32x4 scs[4];   // fused RMSNorm row scales of four A tiles: the lane's four rows of a tile are one 16-byte read
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      scs[k] = rs_tile ? *reinterpret_cast<const f32x4*>(rs_tile + lrow0 + 16 * (ib + k)) : f32x4{1.f, 1.f, 1.f, 1.f};
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = mrow0 + 16 * (ib + k) + r;
+        const float sc = acc_scale * scs[k][r];
+        f32x4 v = {acc[ib + k][0][r], acc[ib + k][1][r], acc[ib + k][2][r], acc[ib + k][3][r]};
+        v[0] = fmaxf(v[0] * sc, relu_lo); v[1] = fmaxf(v[1] * sc, relu_lo); v[2] = fmaxf(v[2] * sc, relu_lo); v[3] = fmaxf(v[3] * sc, relu_lo);
+        if (ncol_ok && (FULL || m < Mlim)) *reinterpret_cast<f32x4*>(outp + (size_t)m * ldo + on) = v;
+      }
+  }
 }
 
 template <bool FULL, int TM, int TN, int WM, int WN, int BM, int BN, bool BOUT, bool M16>
@@ -571,8 +721,27 @@ __device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, typename H2
   // cost a full memory latency per half), so the f16-plane outputs give a lane 8 consecutive columns = one 16-byte
   // store per plane, the row scales come from LDS (rs_tile, filled before the K-loop) and the saturation check is
   // one max per element plus one compare per half.
+  // That layout is a property of which W row sits in which column of an MFMA tile, not of the product: the 16x16x32 body
+  // (M16) has its W rows DMA'd into LDS in an order that puts a lane's four tiles side by side, and its outputs leave from
+  // the accumulators with the same row-wise 16-byte accesses and no strips (h2_direct16_planes / h2_direct16_fp32 above).
+  // The 32 x 32 map (a lane = one column, 16 rows per tile, two tiles per wave row) has no such order: two tiles give a lane
+  // two columns, and it carries the bits of the search's steps and of training — it keeps the strips.
   __syncthreads();                                   // all waves are done reading operand tiles
   const int Mlim = g.m_dev ? min(*g.m_dev - g.m_base, g.M) : g.M;   // packed encoder: rows past the live count are never stored
+  if constexpr (M16) {
+    // The 16x16x32 body chooses its output-column map so that the outputs a tail pass writes leave from registers (above).
+    // The K/V scatter and the fp32 residual (not used by a tail pass; rpr_op_linear_h2 can ask for them) take the strips
+    // below, from the fp32 column map.
+    if (g.out_h) {
+      if (g.resid_h) h2_direct16_planes<FULL, true>(g, acc, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
+      else h2_direct16_planes<FULL, false>(g, acc, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
+      return;
+    }
+    if (!g.rm_B && !g.resid) {
+      h2_direct16_fp32<FULL>(g, acc, lane, bm, bn, wm, wn, rs_tile, acc_scale, Mlim);
+      return;
+    }
+  }
   constexpr int SW = TN * 32;                         // staged row width (floats)
   constexpr int NS = TM * 32 / SH;                    // strips per wave
   float* stg = reinterpret_cast<float*>(smem) + wave * (SH * SW);

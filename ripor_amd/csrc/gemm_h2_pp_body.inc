@@ -80,6 +80,10 @@
     const int limit = is_a ? g.M : g.N;                                                                               \
     const size_t ld = is_a ? (size_t)g.lda : (size_t)g.ldw;                                                           \
     int trow = (is_a ? (bm_x) + lrow - (second ? BM : 0) : (bn_x) + lrow - 2 * BM - (second ? BN : 0));               \
+    if (M16 && !is_a) {   /* the output-column map of the register epilogue (acc16): LDS row 16 j + c of a wave's 64 = W tile j, lane c */ \
+      const int wrow = trow - (bn_x), wc = wrow & 15, wj = (wrow >> 4) & 3;                                           \
+      trow = (bn_x) + ((wrow & ~63) | (g.out_h ? 8 * (wc & 7) + 4 * (wc >> 3) + wj : 4 * wc + wj));                   \
+    }                                                                                                                 \
     if (!FULL && trow >= limit) trow = limit - 1;                                                                     \
     dst[j] = base + plane + (size_t)trow * ld + seg * 8 + (size_t)kbeg * KSTEP;                                       \
   }
@@ -105,13 +109,19 @@
   f16x8 ah0, ah1, al0, al1, bh0, bh1, bl0, bl1;
   f16x8 ah2, ah3, al2, al3;   // two-phase schedule: all four 32-row fragments of the wave's A rows per k-chunk
   // M16 (tail-pass launches, GemmH2Args::mfma16): the wave's 128 x 64 outputs as 8 x 4 tiles of 16 x 16, the same 128 registers.
+  // Lane (c, g) holds rows 4g .. 4g+3 of ONE column per tile, and which W row the DMA puts into LDS row 16 j + c of the wave's
+  // 64 is free (PP_SRC_SETUP): fp32 outputs take column 4 c + j, so the lane's four tiles are four consecutive columns and
+  // the 16 lanes of a group a row's 256 contiguous bytes; plane outputs take 8 (c & 7) + 4 (c >> 3) + j, so lanes c and c ^ 8
+  // hold the halves of an 8-column piece. The epilogue stores 16-byte row pieces from the accumulators (h2_direct16_*,
+  // gemm_h2.hip); the K-loop does not know the map.
   // Lane (c = lane & 15, g = lane >> 4) holds k = 8g .. 8g+7 of row base + c: ONE 16-byte segment of the row, at the
   // inverse of the DMA's swizzle (PP_SRC_SETUP: seg ^ ((row >> 2) & 3); tile bases are multiples of 16, so the term is the
   // lane's own) — the 16 lanes of a group read 16 different 16-byte slots of a 256-byte bank line.
   f32x4 acc16[8][4];
   f16x8 wh2, wh3, wl2, wl3;   // (with bh0, bh1, bl0, bl1: the four 16-row W fragments, kept over both phases of a K-tile)
-  const int a_row16 = wm * (BM / WM) + (lane & 15), w_row16 = 2 * BM + wn * (BN / WN) + (lane & 15);
-  const int so16 = ((lane >> 4) ^ ((lane >> 2) & 3)) * 8;
+  // (from the per-tile laundered lane index: recomputed per tile instead of living through the epilogue, which needs the registers)
+  const int a_row16 = wm * (BM / WM) + (lane_t & 15), w_row16 = 2 * BM + wn * (BN / WN) + (lane_t & 15);
+  const int so16 = ((lane_t >> 4) ^ ((lane_t >> 2) & 3)) * 8;
   if constexpr (M16) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -387,7 +397,8 @@
   if constexpr (M16) h2_epilogue_256<FULL, TM, TN, WM, WN, 256, 256, false, true>(g, acc16, smem, wave, lane_e, bm, bn, wm, wn, g.row_ssq ? rs_tile : nullptr, acc_scale);
   else
   h2_epilogue_256<FULL, TM, TN, WM, WN, 256, 256, BF16 && FULL>(g, acc, smem, wave, lane_e, bm, bn, wm, wn, g.row_ssq ? rs_tile : nullptr, acc_scale);
-  // The staging strips alias the operand buffers the next tile's LDS-DMA writes, and rs_tile is rewritten: every wave's LDS
+  // The staging strips (M16: only the K/V-scatter and fp32-residual variants have them) alias the operand buffers the next
+  // tile's LDS-DMA writes, and rs_tile is rewritten: every wave's LDS
   // reads must have returned (lgkmcnt(0)) before anyone goes on. NOT __syncthreads(): its fence also waits for vmcnt(0),
   // i.e. for every global store of this tile to be acknowledged by the L2 (2-5 us under load) — the stores take their data
   // from registers and drain under the next tile's prologue instead.
