@@ -369,10 +369,11 @@ int rpr_lngknp_forward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids,
  *   and overwrites flat_grads [dev, rpr_param_total]. fp32 activations and gradients; the matrix products follow the
  *   context's precision (rpr_set_precision): RPR_PREC_F16X2 (default) = split-precision f16 MFMA with per-tensor
  *   dynamic plane scales found on the device, RPR_PREC_F32 = exact-fp32 MFMA. Deterministic reductions in both.
- *   Lq <= 128, L <= the model's decoder length; d_kv 64 or 128. The attention backward holds one (sequence, head) in
- *   the 160 KB of LDS of a CU, 128-dim heads 64 columns at a time in the same carve, so the lengths admitted do not depend on
- *   d_kv: self-attention max(L, Lq) <= 91, cross-attention 130 (2 L + Lq) + 4 L (Lq + 1) + Lq <= 40960 floats (L 32 with
- *   Lq <= 91). A shape beyond is RPR_ERR_INVALID before anything is enqueued.
+ *   Lq <= 256, L <= the model's decoder length; d_kv 64 or 128. Up to self-attention max(L, Lq) <= 91 and cross-attention
+ *   130 (2 L + Lq) + 4 L (Lq + 1) + Lq <= 40960 floats (L 32 with Lq <= 91) the attention backward holds one (sequence,
+ *   head) in the 160 KB of LDS of a CU, 128-dim heads 64 columns at a time in the same carve. Beyond, 64-dim heads go on in
+ *   32-row tiles up to Lq = 256 (these passes too, and the dropped-out forward); 128-dim heads are RPR_ERR_INVALID there,
+ *   as is Lq > 256, before anything is enqueued.
  * rpr_adamw_step: global L2 norm of flat_grads (-> out_grad_norm [dev, 1], nullable), clip coefficient
  *   min(1, max_grad_norm / (norm + 1e-6)) (max_grad_norm <= 0: no clipping), AdamW update of every tensor with the
  *   bias corrections of `step` (1-based); the f16 weight planes of the search / inference paths are marked stale and
@@ -407,7 +408,7 @@ int rpr_lngknp_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* i
  * input codebook when shared), loss = nn.CrossEntropyLoss over the bz * L rows (their mean). The encoder / decoder GEMMs follow
  * rpr_set_precision like rpr_lngknp_backward; the head (logits, log-softmax, cross-entropy, its gradients) is exact fp32 in
  * every mode. Deterministic: two identical calls give bit-identical losses and gradients.
- *   input_ids, attention_mask: [dev] int32 [bz, Lq]   (Lq <= 128)
+ *   input_ids, attention_mask: [dev] int32 [bz, Lq]   (Lq <= 256)
  *   labels:      [dev] int32 [bz, L]   codes in [0, V): a label outside is RPR_ERR_INVALID (checked on the host before anything
  *                is enqueued: one copy of bz * L labels and a synchronisation of `stream`)
  *   out_loss:    [dev] float [1]

@@ -1137,7 +1137,355 @@ hipError_t run_self_attn_bwd_mfma(const AttnLaunch& p, const float* qkv, const f
   return hipGetLastError();
 }
 
+// ---- training attention in 32 x 32 tiles: heads too long for an LDS carve of their own --------------------------------------
+// The backward kernels above and in train_kernels.hip hold a whole head — Q, K, V, dO and the Ls x Ls matrices P and dS — in
+// LDS, which ends at 91 positions (self-attention) or at n (Lq + 65) ~ 20 000 floats (cross-attention). Here nothing of the
+// head is resident: one block of four waves per (sequence, head), the nq query rows and nk keys (both <= MAX_LQ = 256) in
+// 32-row tiles, a wave's tile pair of the moment in its two 32 x 64 strips (staged coalesced from global memory / L2: all
+// of K, V, Q, dO of a head at 256 positions is 256 KB and K | V alone 128 KB, which leaves no room for the strips of four
+// waves beside them), products on the fp32 matrix cores in the two layouts of train_self_attn_bwd_mfma_kernel. LDS:
+// attn_route.h, attn_tiled_smem (80 KB with a relative bias: two blocks per CU).
+//   phase 1, a wave per QUERY tile (a lane per query row, registers = 16 keys of the key tile):
+//     sweep 1 over the key tiles: running row maximum, row sum and sum_j dP_ij e_ij (rescaled when the maximum moves);
+//             then 1 / sum and rowsum(dP P) — to LDS for phase 2;
+//     sweep 2: P and dS = P (dP - rowsum) of each tile again, dQ += dS K in the accumulators; with a relative bias the
+//             63 diagonals of the dS tile are summed in row order and added to the wave's diagonals, key tiles ascending
+//             (rows ascending along a diagonal). After every round of four query tiles the block adds the waves'
+//             diagonals to its own in wave = tile order: every diagonal of dS is summed in row order.
+//   phase 2, a wave per KEY tile (a lane per key, registers = 16 queries of the query tile), query tiles ascending:
+//     P and dS from the statistics of phase 1, dK += dS^T Q, dV += P^T dO in the accumulators; stored once.
+// No atomics, no sum whose order depends on timing: two calls give the same bits. A masked key has P = dS = 0 exactly; rows
+// past nq / keys past nk of the last tiles are staged as zeros and never stored.
+// Self-attention: q = qkv, k = q + inner, v = k + inner (row stride 3 inner), nq = nk = Ls, bias by the diagonal j - i.
+// Cross-attention (BIAS = false): the n = docs L decoder rows of a query against its Lq encoder rows; dq / dxk / dxv as
+// cross_attn_bwd_kernel writes them. DROP: the mask of the forward, drawn again by position (dropout.h): a lane per query
+// owns whole groups of four keys (one Philox block each), a lane per key takes its bit out of the block of its group.
+__device__ __forceinline__ void stage_tile32(const float* base, int ld, int r0, int nrows, float* strip, int lane) {
+  const int g = lane >> 4, li = lane & 15;   // four coalesced 256-B rows per instruction; rows past the end are zero
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int jl = it * 4 + g, j = r0 + jl;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < nrows) v = *reinterpret_cast<const float4*>(base + (size_t)j * ld + li * 4);
+    *reinterpret_cast<float4*>(strip + jl * 64 + li * 4) = v;
+  }
+}
+
+// S^T tile, a lane per query: s[r] = score of this lane's query against key kt * 32 + kappa(r, half), -inf where masked
+template <bool BIAS>
+__device__ __forceinline__ void tiled_scores_q(const float* Kstrip, const float4 (&qreg)[8], int kt, int lane, const int* mk,
+                                               const float* brow, f32x16& s) {
+  const int half = lane >> 5;
+  float4 kreg[8];
+  load_row_pieces(Kstrip + (lane & 31) * 64, half, kreg);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s[r] = 0.f;
+  mfma_scores(kreg, qreg, s);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int j = kt * 32 + kappa(r, half);
+    s[r] = mk[j] != 0 ? s[r] + (BIAS ? brow[j] : 0.f) : -INFINITY;   // brow = bias of diagonal j - i of this lane's query
+  }
+}
+
+// keep bits of this lane's query row for its 16 keys of key tile kt: bit r = key kt * 32 + kappa(r, half)
+__device__ __forceinline__ uint32_t tiled_keep16(const DropAttn& da, uint32_t seq, int h, int qpos, int kt, int half) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) m |= drop_keep4_attn(da.key, da.site, seq, h, qpos, kt * 8 + 2 * q4 + half) << (4 * q4);
+  return m;
+}
+
+// one more key tile into the running softmax statistics of a lane's row: mx over both lane halves, sum / cq per half
+template <bool WITH_DP>
+__device__ __forceinline__ void tiled_running_stats(const f32x16& sc, const f32x16& dp, float& mx, float& sum, float& cq) {
+  float tm = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) tm = fmaxf(tm, sc[r]);
+  tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+  const float mnew = fmaxf(mx, tm);
+  if (mnew == -INFINITY) return;                       // nothing attended so far
+  const float f = mx == -INFINITY ? 0.f : expf(mx - mnew);
+  sum *= f; cq *= f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float e = (sc[r] == -INFINITY) ? 0.f : expf(sc[r] - mnew);
+    sum += e;
+    if (WITH_DP) cq = fmaf(dp[r], e, cq);
+  }
+  mx = mnew;
+}
+
+template <bool BIAS, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_kernel(AttnTiledArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int WAVE_FLOATS = TILED_STRIPS + (BIAS ? TILED_DIAGS : 0);
+  const int H = a.H, nq = a.nq, nk = a.nk, tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, half = lane >> 5, n = lane & 31;
+  const int s = blockIdx.x / H, h = blockIdx.x - s * H;
+  float* As = smem + wave * WAVE_FLOATS;               // K tile, then the dQ / dK tile on its way out | phase 2: Q tile
+  float* Bt = As + 32 * 64;                            // V tile, then the dS tile [32][33]            | phase 2: dO tile
+  float* wdiag = Bt + 32 * 64;                         // BIAS: [2 MAX_LQ] diagonals of this wave's query tile
+  float* st = smem + TILED_WAVES * WAVE_FLOATS;        // [3][MAX_LQ] row maximum, 1 / row sum, rowsum(dP P)
+  int* mk = reinterpret_cast<int*>(st + 3 * MAX_LQ);   // [MAX_LQ] key is attended
+  float* Bs = reinterpret_cast<float*>(mk + MAX_LQ);   // BIAS: [2 MAX_LQ] bias of diagonal t = j - i + nq - 1
+  float* diag = Bs + TILED_DIAGS;                      // BIAS: [2 MAX_LQ] sum of dS along it
+  const int nqt = (nq + 31) >> 5, nkt = (nk + 31) >> 5, nd = nq + nk - 1;
+  const float* qb = a.q + (size_t)s * nq * a.q_ld + h * DKV;
+  const float* dob = a.dO + (size_t)s * nq * a.do_ld + h * DKV;
+  const float* kb = a.k + (size_t)s * nk * a.kv_ld + h * DKV;
+  const float* vb = a.v + (size_t)s * nk * a.kv_ld + h * DKV;
+  const int docs = DROP ? nq / a.da.L : 1;
+  for (int j = tid; j < MAX_LQ; j += 256) mk[j] = (j < nk && a.mask[(size_t)s * nk + j] != 0) ? 1 : 0;
+  if constexpr (BIAS) {
+    for (int t = tid; t < TILED_DIAGS; t += 256) {
+      Bs[t] = t < nd ? a.rel_bias[a.bucket[t - (nq - 1) + (MAX_LQ - 1)] * H + h] : 0.f;
+      diag[t] = 0.f;
+    }
+    for (int t = lane; t < TILED_DIAGS; t += 64) wdiag[t] = 0.f;
+  }
+  __syncthreads();
+
+  // ---- phase 1: a wave per query tile ---------------------------------------------------------------------------------
+  for (int q0 = 0; q0 < nqt; q0 += TILED_WAVES) {
+    const int qt = q0 + wave;
+    if (qt < nqt) {                                    // wave-uniform
+      const int i = qt * 32 + n, iq = min(i, nq - 1);  // rows past nq: zero q and dO (dS = 0), never stored
+      float4 qreg[8], greg[8];
+      load_row_pieces(i < nq ? qb + (size_t)i * a.q_ld : nullptr, half, qreg);
+      load_row_pieces(i < nq ? dob + (size_t)i * a.do_ld : nullptr, half, greg);
+      const float* brow = Bs + (nq - 1 - iq);
+      const int doc = DROP ? iq / a.da.L : 0;
+      const uint32_t dseq = (uint32_t)(s * docs + doc);
+      const int qpos = DROP ? iq - doc * a.da.L : iq;
+      // dP^T tile of this lane's query (the gradient w.r.t. the probabilities: through the dropout mask)
+      auto dp_tile = [&](int kt, f32x16& dp) {
+        float4 vreg[8];
+        load_row_pieces(Bt + n * 64, half, vreg);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+        mfma_scores(vreg, greg, dp);
+        if constexpr (DROP) {
+          const uint32_t keep = tiled_keep16(a.da, dseq, h, qpos, kt, half);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dp[r] = ((keep >> r) & 1u) ? dp[r] * a.da.key.scale : 0.f;
+        }
+      };
+      float mx = -INFINITY, sum = 0.f, cq = 0.f;
+      for (int kt = 0; kt < nkt; ++kt) {
+        stage_tile32(kb, a.kv_ld, kt * 32, nk, As, lane);
+        stage_tile32(vb, a.kv_ld, kt * 32, nk, Bt, lane);
+        __builtin_amdgcn_wave_barrier();
+        f32x16 sc, dp;
+        tiled_scores_q<BIAS>(As, qreg, kt, lane, mk, brow, sc);
+        dp_tile(kt, dp);
+        tiled_running_stats<true>(sc, dp, mx, sum, cq);
+        __builtin_amdgcn_wave_barrier();               // the strips are restaged
+      }
+      sum += __shfl_xor(sum, 32, 64);
+      cq += __shfl_xor(cq, 32, 64);
+      const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+      cq *= inv;
+      if (half == 0 && i < nq) { st[i] = mx; st[MAX_LQ + i] = inv; st[2 * MAX_LQ + i] = cq; }
+      f32x16 o[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
+      for (int kt = 0; kt < nkt; ++kt) {
+        stage_tile32(kb, a.kv_ld, kt * 32, nk, As, lane);
+        stage_tile32(vb, a.kv_ld, kt * 32, nk, Bt, lane);
+        __builtin_amdgcn_wave_barrier();
+        f32x16 sc, ds[1];
+        tiled_scores_q<BIAS>(As, qreg, kt, lane, mk, brow, sc);
+        dp_tile(kt, ds[0]);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = (sc[r] == -INFINITY) ? 0.f : expf(sc[r] - mx) * inv;
+          ds[0][r] = p * (ds[0][r] - cq);
+        }
+        mfma_pv<1>(ds, As, lane, o);                   // dQ[query][d] += sum_key dS[query][key] K[key][d]
+        if constexpr (BIAS) {
+          __builtin_amdgcn_wave_barrier();             // the V pieces have been read
+#pragma unroll
+          for (int r = 0; r < 16; ++r) Bt[n * 33 + kappa(r, half)] = ds[0][r];
+          __builtin_amdgcn_wave_barrier();
+          if (lane < 63) {
+            const int off = lane - 31;                 // (j - i) within the tile pair
+            float acc = 0.f;
+            for (int il = 0; il < 32; ++il) { const int jl = il + off; if (jl >= 0 && jl < 32) acc += Bt[il * 33 + jl]; }
+            const int t = (kt - qt) * 32 + off + nq - 1;
+            if (t >= 0 && t < nd) wdiag[t] += acc;
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+      store_o_tile(o, As, lane, qt * 32, nq, (size_t)s * nq, a.dq_ld, h * DKV, a.dq, nullptr, 0, nullptr);
+    }
+    if constexpr (BIAS) {   // the round's four query tiles, in tile order, onto the block's diagonals
+      __syncthreads();
+      for (int t = tid; t < nd; t += 256) {
+        float acc = diag[t];
+        for (int w = 0; w < TILED_WAVES; ++w) {
+          float* wd = smem + w * WAVE_FLOATS + TILED_STRIPS;
+          acc += wd[t];
+          wd[t] = 0.f;
+        }
+        diag[t] = acc;
+      }
+      __syncthreads();
+    }
+  }
+  if constexpr (BIAS) {
+    // the diagonals of a bucket in diagonal order (bucket of each diagonal: in wave 0's diagonal slots, free by now)
+    int* bk = reinterpret_cast<int*>(smem + TILED_STRIPS);
+    for (int t = tid; t < nd; t += 256) bk[t] = a.bucket[t - (nq - 1) + (MAX_LQ - 1)];
+    __syncthreads();
+    if (tid < a.buckets) {
+      float acc = 0.f;
+      for (int t = 0; t < nd; ++t) if (bk[t] == tid) acc += diag[t];
+      a.dbias_part[(size_t)blockIdx.x * a.buckets + tid] = acc;
+    }
+  } else {
+    __syncthreads();                                   // st[] of every query tile
+  }
+
+  // ---- phase 2: a wave per key tile -----------------------------------------------------------------------------------
+  for (int kt = wave; kt < nkt; kt += TILED_WAVES) {
+    const int j = kt * 32 + n;
+    const bool kok = mk[j] != 0;
+    float4 kreg[8], vreg[8];
+    load_row_pieces(j < nk ? kb + (size_t)j * a.kv_ld : nullptr, half, kreg);
+    load_row_pieces(j < nk ? vb + (size_t)j * a.kv_ld : nullptr, half, vreg);
+    f32x16 odk[2], odv[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { odk[0][r] = 0.f; odk[1][r] = 0.f; odv[0][r] = 0.f; odv[1][r] = 0.f; }
+    for (int qt = 0; qt < nqt; ++qt) {
+      stage_tile32(qb, a.q_ld, qt * 32, nq, As, lane);
+      stage_tile32(dob, a.do_ld, qt * 32, nq, Bt, lane);
+      __builtin_amdgcn_wave_barrier();
+      float4 qreg[8], greg[8];
+      load_row_pieces(As + n * 64, half, qreg);
+      load_row_pieces(Bt + n * 64, half, greg);
+      f32x16 p2[1], ds2[1];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { p2[0][r] = 0.f; ds2[0][r] = 0.f; }
+      mfma_scores(qreg, kreg, p2[0]);                  // S[query][key]
+      mfma_scores(greg, vreg, ds2[0]);                 // dP[query][key]
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = qt * 32 + kappa(r, half);
+        const bool ok = kok && i < nq;
+        const int ic = ok ? i : 0;
+        const float bias = BIAS ? Bs[ok ? j - i + nq - 1 : 0] : 0.f;
+        const float pe = ok ? expf(p2[0][r] + bias - st[ic]) * st[MAX_LQ + ic] : 0.f;
+        float mul = 1.0f;
+        if constexpr (DROP) {
+          const int doc = ic / a.da.L;
+          const uint32_t k4 = drop_keep4_attn(a.da.key, a.da.site, (uint32_t)(s * docs + doc), h, ic - doc * a.da.L, j >> 2);
+          mul = ((k4 >> (j & 3)) & 1u) ? a.da.key.scale : 0.f;
+        }
+        ds2[0][r] = ok ? pe * (ds2[0][r] * mul - st[2 * MAX_LQ + ic]) : 0.f;
+        p2[0][r] = pe * mul;
+      }
+      mfma_pv<1>(ds2, As, lane, odk);                  // dK[key][d] += sum_query dS[query][key] Q[query][d]
+      mfma_pv<1>(p2, Bt, lane, odv);                   // dV[key][d] += sum_query P[query][key] dO[query][d]
+      __builtin_amdgcn_wave_barrier();
+    }
+    store_o_tile(odk, As, lane, kt * 32, nk, (size_t)s * nk, a.dkv_ld, h * DKV, a.dk, nullptr, 0, nullptr);
+    store_o_tile(odv, Bt, lane, kt * 32, nk, (size_t)s * nk, a.dkv_ld, h * DKV, a.dv, nullptr, 0, nullptr);
+  }
+}
+
+// The forward with dropped-out probabilities in the same tiles (self_attn_drop_fwd_kernel / cross_attn_drop_fwd_kernel hold the
+// head in LDS): a wave per query tile; sweep 1 over the key tiles for the row maximum and sum, sweep 2: O += (P mask scale) V.
+template <bool BIAS>
+__global__ __launch_bounds__(256, 2) void attn_drop_fwd_tiled_kernel(AttnTiledArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int H = a.H, nq = a.nq, nk = a.nk, tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, half = lane >> 5, n = lane & 31;
+  const int s = blockIdx.x / H, h = blockIdx.x - s * H;
+  float* As = smem + wave * TILED_STRIPS;              // K tile, then the output tile on its way out
+  float* Bt = As + 32 * 64;                            // V tile
+  int* mk = reinterpret_cast<int*>(smem + TILED_WAVES * TILED_STRIPS);   // [MAX_LQ]
+  float* Bs = reinterpret_cast<float*>(mk + MAX_LQ);   // BIAS: [2 MAX_LQ]
+  const int nqt = (nq + 31) >> 5, nkt = (nk + 31) >> 5, nd = nq + nk - 1, docs = nq / a.da.L;
+  const float* qb = a.q + (size_t)s * nq * a.q_ld + h * DKV;
+  const float* kb = a.k + (size_t)s * nk * a.kv_ld + h * DKV;
+  const float* vb = a.v + (size_t)s * nk * a.kv_ld + h * DKV;
+  for (int j = tid; j < MAX_LQ; j += 256) mk[j] = (j < nk && a.mask[(size_t)s * nk + j] != 0) ? 1 : 0;
+  if constexpr (BIAS)
+    for (int t = tid; t < TILED_DIAGS; t += 256) Bs[t] = t < nd ? a.rel_bias[a.bucket[t - (nq - 1) + (MAX_LQ - 1)] * H + h] : 0.f;
+  __syncthreads();
+  for (int qt = wave; qt < nqt; qt += TILED_WAVES) {
+    const int i = qt * 32 + n, iq = min(i, nq - 1);
+    float4 qreg[8];
+    load_row_pieces(i < nq ? qb + (size_t)i * a.q_ld : nullptr, half, qreg);
+    const float* brow = Bs + (nq - 1 - iq);
+    const int doc = iq / a.da.L;
+    const uint32_t dseq = (uint32_t)(s * docs + doc);
+    const int qpos = iq - doc * a.da.L;
+    float mx = -INFINITY, sum = 0.f, unused = 0.f;
+    for (int kt = 0; kt < nkt; ++kt) {
+      stage_tile32(kb, a.kv_ld, kt * 32, nk, As, lane);
+      __builtin_amdgcn_wave_barrier();
+      f32x16 sc;
+      tiled_scores_q<BIAS>(As, qreg, kt, lane, mk, brow, sc);
+      tiled_running_stats<false>(sc, sc, mx, sum, unused);
+      __builtin_amdgcn_wave_barrier();
+    }
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+    f32x16 o[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
+    for (int kt = 0; kt < nkt; ++kt) {
+      stage_tile32(kb, a.kv_ld, kt * 32, nk, As, lane);
+      stage_tile32(vb, a.kv_ld, kt * 32, nk, Bt, lane);
+      __builtin_amdgcn_wave_barrier();
+      f32x16 p[1];
+      tiled_scores_q<BIAS>(As, qreg, kt, lane, mk, brow, p[0]);
+      const uint32_t keep = tiled_keep16(a.da, dseq, h, qpos, kt, half);
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        p[0][r] = (p[0][r] != -INFINITY && ((keep >> r) & 1u)) ? expf(p[0][r] - mx) * inv * a.da.key.scale : 0.f;
+      mfma_pv<1>(p, Bt, lane, o);
+      __builtin_amdgcn_wave_barrier();
+    }
+    store_o_tile(o, As, lane, qt * 32, nq, (size_t)s * nq, a.out_ld, h * DKV, a.out, nullptr, 0, nullptr);
+  }
+}
+
+hipError_t run_attn_bwd_tiled(const AttnLaunch& p, const AttnTiledArgs& a, bool drop, hipStream_t s) {
+  const dim3 grid(p.grid_x), blk(p.block);
+  if (a.nq < 1 || a.nk < 1 || a.nq > MAX_LQ || a.nk > MAX_LQ || !a.mask) return hipErrorInvalidValue;
+  if (drop && (a.da.L < 1 || a.nq % a.da.L)) return hipErrorInvalidValue;
+  const bool bias = p.kernel == ATTN_TRAIN_SELF_BWD_TILED;
+  if (bias && (a.nq != a.nk || !a.dbias_part)) return hipErrorInvalidValue;
+  if (bias && drop) hipLaunchKernelGGL((attn_bwd_tiled_kernel<true, true>), grid, blk, p.smem, s, a);
+  else if (bias) hipLaunchKernelGGL((attn_bwd_tiled_kernel<true, false>), grid, blk, p.smem, s, a);
+  else if (drop) hipLaunchKernelGGL((attn_bwd_tiled_kernel<false, true>), grid, blk, p.smem, s, a);
+  else hipLaunchKernelGGL((attn_bwd_tiled_kernel<false, false>), grid, blk, p.smem, s, a);
+  return hipGetLastError();
+}
+
+hipError_t run_attn_drop_fwd_tiled(const AttnLaunch& p, const AttnTiledArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid_x), blk(p.block);
+  if (a.nq < 1 || a.nk < 1 || a.nq > MAX_LQ || a.nk > MAX_LQ || !a.mask || a.da.L < 1 || a.nq % a.da.L) return hipErrorInvalidValue;
+  if (p.kernel == ATTN_TRAIN_SELF_DROP_FWD_TILED) {
+    if (a.nq != a.nk) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attn_drop_fwd_tiled_kernel<true>, grid, blk, p.smem, s, a);
+  } else {
+    hipLaunchKernelGGL(attn_drop_fwd_tiled_kernel<false>, grid, blk, p.smem, s, a);
+  }
+  return hipGetLastError();
+}
+
 hipError_t init_attn_mfma_attributes() {
+  for (const void* k : {reinterpret_cast<const void*>(attn_bwd_tiled_kernel<true, true>), reinterpret_cast<const void*>(attn_bwd_tiled_kernel<true, false>),
+                        reinterpret_cast<const void*>(attn_bwd_tiled_kernel<false, true>), reinterpret_cast<const void*>(attn_bwd_tiled_kernel<false, false>),
+                        reinterpret_cast<const void*>(attn_drop_fwd_tiled_kernel<true>), reinterpret_cast<const void*>(attn_drop_fwd_tiled_kernel<false>)}) {
+    const hipError_t ek = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_tiled_smem(true, true));
+    if (ek != hipSuccess) return ek;
+  }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_self_attn_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)tail_self_attn_smem(MAX_DEC_LEN, 128));
   if (e != hipSuccess) return e;

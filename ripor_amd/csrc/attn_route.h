@@ -49,7 +49,9 @@ struct AttnTuning {
   /* step cross-attention: step_cross_attn_mfma16_kernel<false> / <true> */                                             \
   X(STEP_CROSS16_ONE) X(STEP_CROSS16_MULTI)                                                                              \
   /* training self-attention backward: the fp32-MFMA tile, self_attn_bwd_kernel<., 64>, <., 128> */                     \
-  X(TRAIN_BWD_MFMA) X(TRAIN_BWD_VALU) X(TRAIN_BWD_VALU128)
+  X(TRAIN_BWD_MFMA) X(TRAIN_BWD_VALU) X(TRAIN_BWD_VALU128)                                                              \
+  /* training attention beyond the one-head LDS carve: attn_bwd_tiled_kernel<bias>, attn_drop_fwd_tiled_kernel<bias> */ \
+  X(TRAIN_SELF_BWD_TILED) X(TRAIN_CROSS_BWD_TILED) X(TRAIN_SELF_DROP_FWD_TILED) X(TRAIN_CROSS_DROP_FWD_TILED)
 
 enum AttnKernel {
 #define X(n) ATTN_##n,
@@ -257,6 +259,47 @@ inline AttnLaunch plan_self_attn_bwd(const SelfAttnBwdIn& a) {
     return p;
   }
   return attn_launch(ATTN_TRAIN_BWD_VALU, (long)a.S * a.H, smem);
+}
+
+// ---- training attention beyond the one-head carve (attn_mfma.hip: attn_bwd_tiled_kernel, attn_drop_fwd_tiled_kernel) ---------
+// 64-dim heads, up to MAX_LQ query rows and MAX_LQ keys per (sequence, head), bidirectional; the launchers of train_kernels.hip
+// come here only when the plan above (self-attention) or the resident carve below (cross-attention) refuses the shape.
+// One block of four waves per (sequence, head); queries and keys in 32-row tiles, nothing of the head resident:
+//   per wave    two 32 x 64 strips (the tile pair of the moment: K | V, then Q | dO)       4096 floats
+//               backward with a relative bias: its query tile's 2 MAX_LQ diagonals of dS     512
+//   per block   row maximum, 1 / row sum, rowsum(dP P) of MAX_LQ queries                      768
+//               key mask [MAX_LQ]                                                              256
+//               with a relative bias: bias per diagonal and the diagonal sums, 2 x 512       1024
+// self backward 4 (4096 + 512) + 768 + 256 + 1024 = 20 480 floats = 81 920 B (two blocks per CU); cross backward
+// 4 x 4096 + 768 + 256 = 17 408 floats = 69 632 B; the forward needs no statistics: 4 x 4096 + 256 (+ 512) floats.
+constexpr int TILED_WAVES = 4, TILED_STRIPS = 2 * 32 * DKV, TILED_DIAGS = 2 * MAX_LQ;
+inline size_t attn_tiled_smem(bool bias, bool bwd) {
+  return ((size_t)TILED_WAVES * (TILED_STRIPS + (bias && bwd ? TILED_DIAGS : 0)) + (bwd ? 3 * MAX_LQ : 0) + MAX_LQ +
+          (bias ? (bwd ? 2 : 1) * TILED_DIAGS : 0)) * sizeof(float);
+}
+inline AttnLaunch plan_attn_tiled(int kernel, long S, int nq, int nk, int H, int buckets, int dkv, bool bias, bool bwd) {
+  if (dkv != DKV || nq < 1 || nk < 1 || nq > MAX_LQ || nk > MAX_LQ || buckets > 64 || S < 1 || H < 1) return attn_invalid();
+  return attn_launch(kernel, S * H, attn_tiled_smem(bias, bwd));   // block = 256 (AttnLaunch's default)
+}
+inline AttnLaunch plan_self_attn_bwd_tiled(const SelfAttnBwdIn& a) {
+  return plan_attn_tiled(ATTN_TRAIN_SELF_BWD_TILED, a.S, a.Ls, a.Ls, a.H, a.buckets, a.dkv, true, true);
+}
+inline AttnLaunch plan_self_attn_drop_fwd_tiled(const SelfAttnBwdIn& a) {
+  return plan_attn_tiled(ATTN_TRAIN_SELF_DROP_FWD_TILED, a.S, a.Ls, a.Ls, a.H, a.buckets, a.dkv, true, false);
+}
+// cross-attention of the training step: n = docs x L decoder rows of a query against its Lq encoder keys
+struct CrossAttnBwdIn { int bz = 0, n = 0, Lq = 0, H = 0, dkv = DKV; };
+// the carve of cross_attn_bwd_kernel / cross_attn_drop_fwd_kernel (train_kernels.hip: cross_attn_bwd_smem restates it): q, dO
+// [n][65], K, V [Lq][65], P, dS [n][Lq + 1], key mask [Lq]
+inline size_t cross_attn_bwd_carve(int n, int Lq) {
+  return ((size_t)2 * n * (DKV + 1) + 2 * (size_t)Lq * (DKV + 1) + 2 * (size_t)n * (Lq + 1) + (size_t)Lq) * sizeof(float);
+}
+inline bool cross_attn_bwd_resident(int n, int Lq) { return cross_attn_bwd_carve(n, Lq) <= LDS_MAX; }
+inline AttnLaunch plan_cross_attn_bwd_tiled(const CrossAttnBwdIn& a) {
+  return plan_attn_tiled(ATTN_TRAIN_CROSS_BWD_TILED, a.bz, a.n, a.Lq, a.H, 0, a.dkv, false, true);
+}
+inline AttnLaunch plan_cross_attn_drop_fwd_tiled(const CrossAttnBwdIn& a) {
+  return plan_attn_tiled(ATTN_TRAIN_CROSS_DROP_FWD_TILED, a.bz, a.n, a.Lq, a.H, 0, a.dkv, false, false);
 }
 
 }  // namespace rpr

@@ -752,6 +752,22 @@ hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, cons
                                      int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s, int dkv = DKV);
 hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
                                       int n, int Lq, int H, const DropAttn& drop, hipStream_t s, int dkv = DKV);
+// attn_mfma.hip: the tiled plans of the four launches above (attn_route.h: plan_*_tiled) for 64-dim heads whose shape is beyond
+// the LDS carve of the kernels that hold a head. Pointers at head 0 of row 0; sequence s owns query rows s nq .. s nq + nq - 1
+// (q, dO, dq, out) and key rows s nk .. s nk + nk - 1 (k, v, dk, dv, mask); self-attention: nq = nk, k = q + inner, v = k + inner
+struct AttnTiledArgs {
+  const float *q, *k, *v, *dO;
+  int q_ld, kv_ld, do_ld;             // row strides in floats
+  float *dq, *dk, *dv;                // backward
+  int dq_ld, dkv_ld;
+  float* out; int out_ld;             // forward with dropped-out probabilities
+  const int32_t* mask;                // [S][nk] key is attended
+  const float* rel_bias; const int32_t* bucket; float* dbias_part; int buckets;   // self-attention only
+  int nq, nk, H;
+  DropAttn da;                        // backward without dropout: unused
+};
+hipError_t run_attn_bwd_tiled(const AttnLaunch& p, const AttnTiledArgs& a, bool drop, hipStream_t s);
+hipError_t run_attn_drop_fwd_tiled(const AttnLaunch& p, const AttnTiledArgs& a, hipStream_t s);
 hipError_t launch_dropout_rows(const float* x, const float* resid, float* out, size_t n_seq, int n_pos, int n_feat, const DropKey& key,
                                int site, hipStream_t s);
 hipError_t launch_gold_rowdot(const float* hd, const float* out_embeds, const int32_t* out_idx, float* scores, const float* dscores,

@@ -857,13 +857,19 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
 // Checks and workspaces shared by the training passes: docs decoder sequences of L positions per query
 int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, TrainDims& D) {
   RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
-  RPR_REQUIRE(bz >= 1 && Lq >= 1 && Lq <= 128, "bz or Lq out of range (the training kernels hold Lq <= 128 keys in LDS)");
+  RPR_REQUIRE(bz >= 1 && Lq >= 1, "bz or Lq out of range");
+  RPR_REQUIRE(Lq <= MAX_LQ, "Lq out of range: the training passes take queries of at most 256 tokens");
   RPR_REQUIRE(m->d.d_kv == DKV || m->d.d_kv == 128, "d_kv must be 64 (t5-base / t5-large) or 128 (t5-3b)");
   RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_DEC_LEN, "smtid length exceeds the model's decoder length");
   RPR_HIP(hipSetDevice(c->device));
   const auto& d = m->d;
   D = train_dims(d, bz, Lq, L, docs);
-  RPR_REQUIRE(self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024,
+  // 64-dim heads beyond the carve of a whole head go on in tiles (attn_route.h: plan_*_tiled; L <= 64 always fits the decoder's
+  // causal self-attention, the docs L <= 128 decoder rows of a query the tiles); 128-dim heads stop at the carve
+  const bool tiled_ok = d.d_kv == DKV && !plan_cross_attn_bwd_tiled(CrossAttnBwdIn{bz, docs * L, Lq, d.num_heads, d.d_kv}).invalid &&
+                        !plan_self_attn_bwd_tiled(SelfAttnBwdIn{bz, Lq, d.num_heads, d.rel_buckets, d.d_kv}).invalid;
+  RPR_REQUIRE(tiled_ok ||
+              (self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024),
               "sequence lengths beyond the 160 KB of LDS the attention backward holds a head in: self-attention max(L, Lq) <= 91, "
               "cross-attention 130 (docs L + Lq) + 2 docs L (Lq + 1) + Lq floats <= 40960 (the same for 64- and 128-dim heads)");
   int e = alloc_train(c, m, D);

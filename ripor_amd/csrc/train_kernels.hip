@@ -634,7 +634,24 @@ hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
                                 hipStream_t s, const DropAttn* drop, int dkv) {
   const AttnLaunch p = plan_self_attn_bwd(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
-  if (p.invalid) return hipErrorInvalidValue;
+  if (p.invalid) {
+    // beyond the carve that holds a head (Ls > 91): 64-dim bidirectional heads go on in tiles (attn_mfma.hip), with or without
+    // the dropout mask; everything else stays refused
+    const AttnLaunch pt = plan_self_attn_bwd_tiled(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
+    if (pt.invalid || causal || self_attn_bwd_smem(Ls, buckets) <= LDS_MAX) return hipErrorInvalidValue;
+    const int inner = H * DKV;
+    AttnTiledArgs a{};
+    a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner; a.dO = dO;
+    a.q_ld = a.kv_ld = 3 * inner; a.do_ld = inner;
+    a.dq = dqkv; a.dk = dqkv + inner; a.dv = dqkv + 2 * inner; a.dq_ld = a.dkv_ld = 3 * inner;
+    a.mask = mask; a.rel_bias = rel_bias; a.bucket = bucket; a.dbias_part = dbias_part; a.buckets = buckets;
+    a.nq = a.nk = Ls; a.H = H;
+    if (drop) a.da = *drop;
+    const hipError_t e = run_attn_bwd_tiled(pt, a, drop != nullptr, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
+    return hipGetLastError();
+  }
   if (drop) {   // dropped-out probabilities: the VALU kernel at every length (the MFMA plan knows no mask)
     const size_t smem = self_attn_bwd_smem(Ls, buckets);
     if (smem > 160 * 1024 || Ls > 256) return hipErrorInvalidValue;   // (a lane carries the keep bits of <= 32 keys)
@@ -765,6 +782,17 @@ hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* x
                                  float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s, const DropAttn* drop,
                                  int dkv) {
   const size_t smem = cross_attn_bwd_smem(n, Lq);   // whatever the head dim: 128-dim heads go through the carve in two halves
+  if (smem > 160 * 1024 && dkv == DKV) {   // the query's rows and keys do not fit a CU: in tiles (attn_mfma.hip)
+    const AttnLaunch pt = plan_cross_attn_bwd_tiled(CrossAttnBwdIn{bz, n, Lq, H, dkv});
+    if (pt.invalid) return hipErrorInvalidValue;
+    AttnTiledArgs a{};
+    a.q = q; a.k = xk; a.v = xv; a.dO = dO;
+    a.q_ld = a.do_ld = a.dq_ld = H * DKV; a.kv_ld = a.dkv_ld = xld;
+    a.dq = dq; a.dk = dxk; a.dv = dxv;
+    a.mask = mask; a.nq = n; a.nk = Lq; a.H = H;
+    if (drop) a.da = *drop;
+    return run_attn_bwd_tiled(pt, a, drop != nullptr, s);
+  }
   if (smem > 160 * 1024 || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
   // (an fp32-MFMA version — one wave per (query, head), dK / dV accumulated over the row tiles in the matrix cores — measured
   // 91 us against this kernel's 88: one wave per SIMD by its 33 KB of strips; removed)
@@ -943,6 +971,17 @@ __global__ __launch_bounds__(256) void cross_attn_drop_fwd_kernel(const float* _
 hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, const float* rel_bias, const int32_t* bucket, float* out,
                                      int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s, int dkv) {
   const size_t smem = self_attn_bwd_smem(Ls, buckets);   // (the backward's carve holds this kernel's: the step was admitted by it)
+  if (smem > 160 * 1024 && dkv == DKV && !causal && mask) {   // Ls > 91: in tiles (attn_mfma.hip)
+    const AttnLaunch pt = plan_self_attn_drop_fwd_tiled(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
+    if (pt.invalid) return hipErrorInvalidValue;
+    const int inner = H * DKV;
+    AttnTiledArgs a{};
+    a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner; a.q_ld = a.kv_ld = 3 * inner;
+    a.out = out; a.out_ld = inner;
+    a.mask = mask; a.rel_bias = rel_bias; a.bucket = bucket; a.buckets = buckets;
+    a.nq = a.nk = Ls; a.H = H; a.da = drop;
+    return run_attn_drop_fwd_tiled(pt, a, s);
+  }
   if (smem > 160 * 1024 || buckets > 64 || Ls < 1 || Ls > MAX_LQ || (!causal && !mask) || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
   if (dkv == 128)
     hipLaunchKernelGGL(self_attn_drop_fwd_kernel<128>, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets,
@@ -955,6 +994,15 @@ hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, cons
 hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
                                       int n, int Lq, int H, const DropAttn& drop, hipStream_t s, int dkv) {
   const size_t smem = cross_attn_bwd_smem(n, Lq);
+  if (smem > 160 * 1024 && dkv == DKV) {   // in tiles (attn_mfma.hip)
+    const AttnLaunch pt = plan_cross_attn_drop_fwd_tiled(CrossAttnBwdIn{bz, n, Lq, H, dkv});
+    if (pt.invalid) return hipErrorInvalidValue;
+    AttnTiledArgs a{};
+    a.q = q; a.k = xk; a.v = xv; a.q_ld = H * DKV; a.kv_ld = xld;
+    a.out = out; a.out_ld = H * DKV;
+    a.mask = mask; a.nq = n; a.nk = Lq; a.H = H; a.da = drop;
+    return run_attn_drop_fwd_tiled(pt, a, s);
+  }
   if (smem > 160 * 1024 || drop.L < 1 || n % drop.L || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
   if (dkv == 128) hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<128>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
   else hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<DKV>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);

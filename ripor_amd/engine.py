@@ -1054,8 +1054,8 @@ def _s2s_args(model: DeviceModel, input_ids, attention_mask, labels):
     bz, Lq = ids.shape
     if lab.dim() != 2 or lab.shape[0] != bz:
         raise ValueError(f"labels must be [bz, L] with bz = {bz}, got {tuple(lab.shape)}")
-    if Lq > 128:
-        raise ValueError(f"queries of {Lq} tokens: the training kernels hold at most 128 encoder positions (use max_length <= 128)")
+    if Lq > 256:
+        raise ValueError(f"queries of {Lq} tokens: the training passes take at most 256 encoder positions (use max_length <= 256)")
     return ids, mask, lab, bz, Lq, int(lab.shape[1])
 
 

@@ -91,8 +91,8 @@ def main(argv=None):
         dist.init_process_group(backend=os.environ.get("RPR_DIST_BACKEND", "nccl"))
     if seq2seq:
         from .dataset.seq2seq import Seq2SeqForT5SeqAQCollator, Seq2SeqForT5SeqAQDataset
-        if args.max_length > 128:
-            raise SystemExit(f"--max_length {args.max_length}: the training kernels hold at most 128 query tokens")
+        if args.max_length > 256:
+            raise SystemExit(f"--max_length {args.max_length}: the training passes take at most 256 query tokens")
         dataset = Seq2SeqForT5SeqAQDataset(example_path=args.query_to_docid_path, docid_to_smtid_path=args.docid_to_smtid_path)
         collator = Seq2SeqForT5SeqAQCollator(args.model_name_or_path, max_length=args.max_length)
         model = T5SeqAQEncoderForSeq2Seq.from_pretrained(args.resume_from_checkpoint or args.pretrained_path,

@@ -4,10 +4,11 @@
 passes of L = 32 positions over queries of ~16 tokens, backward, gradient all-reduce (RCCL when launched on several
 ranks), AdamW. --loss seq2seq: the seq2seq docid cross-entropy step instead (one teacher-forced pass per query, the
 codebook-logit head). Rank 0 prints one JSON line (examples/s of the whole job, max step time over the ranks).
+--lq N: every query N tokens long (92 .. 256: the tiled attention backward) instead of the ~16 of the fine-tune data.
 --precision and --loss take comma-separated lists: one JSON line per (precision, loss) on ONE model load (t5-3b: 11 GB of
 weights to generate and upload). --embed: before the steps, time rpr_embed on 128 texts of ~16 tokens and 128 texts of 128
 tokens (one JSON line).
-Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq] [--dims t5-base|t5-3b] [--embed]
+Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq] [--dims t5-base|t5-3b] [--embed] [--lq N]
        python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/train_bench.py"""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -35,6 +36,7 @@ ap.add_argument("--precision", default=["f16x2"], type=listed(PRECISIONS))
 ap.add_argument("--loss", default=["lngknp"], type=listed(LOSSES))
 ap.add_argument("--dims", default="t5-base", choices=["t5-base", "t5-3b"])
 ap.add_argument("--embed", action="store_true")
+ap.add_argument("--lq", type=int, default=0, help="all queries this many tokens long (default: ~16, as the fine-tune data)")
 args = ap.parse_args()
 L, V, bz = args.L, 256, args.bz
 if args.dims == "t5-3b":
@@ -52,9 +54,10 @@ ctx = E.Context.get(local)
 ctx.set_precision(args.precision[0])
 model = E.DeviceModel(ctx, synth.make_state_dict(dims), dims)
 state = E.TrainState(model)
-ids, mask = synth.make_queries(bz * world, vocab_size=dims.vocab_size, seed=5, mean_len=16, std_len=5, min_len=6, max_len=64)
+qlen = dict(fixed_len=args.lq) if args.lq else dict(mean_len=16, std_len=5, min_len=6, max_len=64)
+ids, mask = synth.make_queries(bz * world, vocab_size=dims.vocab_size, seed=5, **qlen)
 ids, mask = ids[rank::world], mask[rank::world]          # every rank its own examples, one padded length for all
-Lq = (ids.shape[1] + 7) // 8 * 8
+Lq = ids.shape[1] if args.lq else (ids.shape[1] + 7) // 8 * 8
 ids = np.pad(ids, ((0, 0), (0, Lq - ids.shape[1]))); mask = np.pad(mask, ((0, 0), (0, Lq - mask.shape[1])))
 codes = synth.make_codes(2 * bz, L, V, seed=5).astype(np.int64).reshape(2, bz, L).transpose(1, 0, 2).copy()
 prefix = [L, 4, 8, 16][: {8: 2, 16: 3, 32: 4}[L]]
