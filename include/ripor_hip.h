@@ -137,7 +137,8 @@ int rpr_init(int device, rpr_ctx** out_ctx);
 void rpr_free_ctx(rpr_ctx* ctx);
 const char* rpr_last_error(void);
 /* Library/ABI version; bumped when a signature changes or a symbol is added (4: the seq2seq step). Version 4 has since gained
- * rpr_search_margins without a bump: a binding that needs it probes for the symbol (dlsym) rather than for a version. */
+ * rpr_search_margins and rpr_search_prefixes without a bump: a binding that needs one of them probes for the symbol (dlsym)
+ * rather than for a version. */
 int rpr_abi_version(void);
 /* Select the GEMM arithmetic (RPR_PREC_*); default RPR_PREC_F16X2, or RPR_PRECISION=f32|f16x2 in the
  * environment at rpr_init. Takes effect on the next rpr_search/rpr_encode/rpr_op_linear. */
@@ -240,6 +241,25 @@ int rpr_search_margins(rpr_ctx* ctx, rpr_model* model, rpr_trie* trie, const int
                        const int32_t* attention_mask, int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags,
                        int32_t* out_tokens, float* out_scores, int64_t* out_row_lo, int64_t* out_row_hi,
                        double* out_margin, const rpr_debug_taps* taps, void* stream);
+
+/* The same search plus its beams at up to three shorter PREFIX LENGTHS (the rank-data pass runs the search at 4, 8 and
+ * 16 tokens; beam search decides step by step, so the beams of a search of length p are what a longer search holds after
+ * its p-th selection step). n_depths: 1..3; depths: [host] strictly ascending, each in [1, L-1]. Per prefix length p =
+ * depths[k] (the four depth_* arguments are [host] arrays of n_depths [dev] pointers):
+ *   depth_tokens[k]: int32 [Q, B, p], depth_scores[k]: float32 [Q, B], depth_row_lo[k] / depth_row_hi[k]: int64 [Q, B]
+ * = what rpr_search(..., L = p) returns on the same trie: beams ranked by float64 sum / (p + 1), exact ties in reverse slot
+ * order, float32 store, the sorted-row range of each p-prefix. The ordinary outputs are those of rpr_search(L) under the
+ * same plan (same bits). Fork depths are those of the same (Q, B, L) without prefix lengths; no query is forced with
+ * extras (rpr_set_tail_extras does not apply), the call is never lane-split and takes no taps. Queries walking step by
+ * step at depth p are ranked by the finalize kernel on their beams; queries that left at a fork T < p by the tail pass's
+ * ranking stopped at p (score at T plus the first p - T gold scores, the same additions in the same order). In the
+ * optimistic forced-tail mode a call that raised RPR_STATUS_TAIL_LEFTOVER leaves these outputs unspecified too.
+ * Invalid depths (unsorted, repeated, out of range, more than three) or a NULL pointer: RPR_ERR_INVALID, nothing written. */
+int rpr_search_prefixes(rpr_ctx* ctx, rpr_model* model, rpr_trie* trie, const int32_t* input_ids,
+                        const int32_t* attention_mask, int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags,
+                        int32_t* out_tokens, float* out_scores, int64_t* out_row_lo, int64_t* out_row_hi,
+                        int32_t n_depths, const int32_t* depths, int32_t* const* depth_tokens, float* const* depth_scores,
+                        int64_t* const* depth_row_lo, int64_t* const* depth_row_hi, void* stream);
 
 /* Lane split of large batches. A call of rpr_search with at least `min_rows` decoder rows (queries x beams; default
  * 10240; 0 = never; env RPR_LANE_MIN_ROWS) runs as two halves on two internal HIP streams, each confined to half of the CUs

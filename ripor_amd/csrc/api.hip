@@ -598,13 +598,21 @@ bool ensure_lanes(rpr_ctx* c) {
 // The plan of one search on one workspace (lane -1: the ctx's): the ctx's settings (its base), the model's facts and the call handed to
 // plan_search, which asks for the trie's statistics when the automatic fork planner needs them (one pass over the sorted
 // codes, on the first such search of that length)
+// What rpr_search_prefixes asks for beyond rpr_search: the prefix lengths and where each one's beams go (device pointers)
+struct PrefixOuts {
+  int n = 0;
+  int depths[MAX_DEPTHS] = {0, 0, 0};
+  int32_t* tokens[MAX_DEPTHS]; float* scores[MAX_DEPTHS]; int64_t* lo[MAX_DEPTHS]; int64_t* hi[MAX_DEPTHS];
+};
+
 SearchPlan make_plan(rpr_ctx* c, const rpr_model* m, rpr_trie* tr, int Q, int Lq, int B, int L, unsigned flags, bool taps, bool margins,
-                     int lane) {
+                     int lane, const PrefixOuts* px = nullptr) {
   SearchModel f;
   f.logit_bound = m->logit_bound; f.V = m->d.V; f.f32_only = m->f32_only; f.l0_current = m->l0_ready(c);
   // the per-call debug switches of the selection / ranking kernels are part of the plan (tests flip them between calls)
   auto env_int = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
-  const SearchCall a{Q, Lq, B, L, flags, taps, margins, lane, env_int("RPR_TAIL_RANK_REPLAY", 0), env_int("RPR_SELECT_RADIX", -1)};
+  SearchCall a{Q, Lq, B, L, flags, taps, margins, lane, env_int("RPR_TAIL_RANK_REPLAY", 0), env_int("RPR_SELECT_RADIX", -1)};
+  if (px) { a.n_depths = px->n; for (int i = 0; i < px->n; ++i) a.depths[i] = px->depths[i]; }
   return plan_search(*c, f, a, [&] {
     auto it = tr->single_frac.find(L);
     if (it == tr->single_frac.end()) {
@@ -627,7 +635,7 @@ struct WsGuard {
 // one planned search on stream s, in the workspace of its plan, which search_entry has sized
 int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const SearchPlan& plan, const int32_t* input_ids, const int32_t* attention_mask,
                int32_t* out_tokens, float* out_scores, int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin,
-               const rpr_debug_taps* taps, hipStream_t s) {
+               const rpr_debug_taps* taps, hipStream_t s, const PrefixOuts* px = nullptr) {
   WsGuard ws_guard(c, plan.lane);
   PrecGuard prec_guard(c, plan.prec);
   const int Q = plan.Q, L = plan.L;
@@ -667,13 +675,21 @@ int search_one(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const SearchPlan& plan, c
   if (out_row_lo) RPR_HIP(hipMemcpyAsync(out_row_lo, w.o_lo.p, R * 8, hipMemcpyDeviceToDevice, s));
   if (out_row_hi) RPR_HIP(hipMemcpyAsync(out_row_hi, w.o_hi.p, R * 8, hipMemcpyDeviceToDevice, s));
   if (out_margin) RPR_HIP(hipMemcpyAsync(out_margin, w.o_margin.p, (size_t)Q * 8, hipMemcpyDeviceToDevice, s));
+  for (int k = 0; px && k < plan.n_depths; ++k) {   // the plan's prefix lengths are px's, in its order
+    RPR_HIP(hipMemcpyAsync(px->tokens[k], w.d_tokens[k].p, R * (size_t)plan.depths[k] * 4, hipMemcpyDeviceToDevice, s));
+    RPR_HIP(hipMemcpyAsync(px->scores[k], w.d_scores[k].p, R * 4, hipMemcpyDeviceToDevice, s));
+    RPR_HIP(hipMemcpyAsync(px->lo[k], w.d_lo[k].p, R * 8, hipMemcpyDeviceToDevice, s));
+    RPR_HIP(hipMemcpyAsync(px->hi[k], w.d_hi[k].p, R * 8, hipMemcpyDeviceToDevice, s));
+  }
   return RPR_OK;
 }
 
-// rpr_search (out_margin == nullptr) and rpr_search_margins: argument checks, weight planes, the plans, the lane split
+// rpr_search (out_margin == nullptr), rpr_search_margins and rpr_search_prefixes (px != nullptr, checked by its entry):
+// argument checks, weight planes, the plans, the lane split
 int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
                  int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
-                 int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, void* stream) {
+                 int64_t* out_row_lo, int64_t* out_row_hi, double* out_margin, const rpr_debug_taps* taps, void* stream,
+                 const PrefixOuts* px = nullptr) {
   RPR_REQUIRE(c && m && tr && input_ids && attention_mask && out_tokens && out_scores, "NULL argument");
   RPR_REQUIRE(m->ctx == c && tr->ctx == c, "model/trie belong to another ctx");
   RPR_REQUIRE(Q >= 1 && B >= 1 && B <= 65535, "Q or B out of range");
@@ -694,14 +710,15 @@ int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_id
   c->last_ws_mask = 0;
   // Large batches: two halves on the two CU-masked lanes, side by side (see Lane). Results are those of one call: every
   // query is processed on its own rows. The caller's stream waits for both lanes.
-  const bool split = c->lane_min_rows > 0 && (int64_t)Q * B >= c->lane_min_rows && Q >= 2 && !taps && ensure_lanes(c);
+  // (a call with prefix lengths runs on one workspace, like one with taps)
+  const bool split = c->lane_min_rows > 0 && (int64_t)Q * B >= c->lane_min_rows && Q >= 2 && !taps && !px && ensure_lanes(c);
   // Every workspace of the call is planned once and sized BEFORE anything is enqueued: growing a buffer drops every cached
   // graph of the ctx (ensure()), which must not happen while the other lane's graph is in flight — and an allocation failure
   // then leaves nothing running
   const int32_t Qh[2] = {split ? (Q + 1) / 2 : Q, Q / 2};
   SearchPlan plans[2];
   for (int i = 0; i < (split ? 2 : 1); ++i) {
-    plans[i] = make_plan(c, m, tr, Qh[i], Lq, B, L, flags, taps != nullptr, out_margin != nullptr, split ? i : -1);
+    plans[i] = make_plan(c, m, tr, Qh[i], Lq, B, L, flags, taps != nullptr, out_margin != nullptr, split ? i : -1, px);
     WsGuard ws_guard(c, plans[i].lane);
     const int e = alloc_workspace(c, m, plans[i]);
     if (e) return e;
@@ -726,7 +743,7 @@ int search_entry(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_id
     for (int i = 0; i < 2; ++i) RPR_HIP(hipStreamWaitEvent(s, c->lanes[i].done, 0));
     return RPR_OK;
   }
-  return search_one(c, m, tr, plans[0], input_ids, attention_mask, out_tokens, out_scores, out_row_lo, out_row_hi, out_margin, taps, s);
+  return search_one(c, m, tr, plans[0], input_ids, attention_mask, out_tokens, out_scores, out_row_lo, out_row_hi, out_margin, taps, s, px);
 }
 
 }  // namespace
@@ -746,6 +763,26 @@ int rpr_search_margins(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* in
   RPR_REQUIRE(out_margin != nullptr, "out_margin is NULL");
   return search_entry(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi,
                       out_margin, taps, stream);
+}
+
+int rpr_search_prefixes(rpr_ctx* c, rpr_model* m, rpr_trie* tr, const int32_t* input_ids, const int32_t* attention_mask,
+                        int32_t Q, int32_t Lq, int32_t B, int32_t L, uint32_t flags, int32_t* out_tokens, float* out_scores,
+                        int64_t* out_row_lo, int64_t* out_row_hi, int32_t n_depths, const int32_t* depths,
+                        int32_t* const* depth_tokens, float* const* depth_scores, int64_t* const* depth_row_lo,
+                        int64_t* const* depth_row_hi, void* stream) {
+  RPR_REQUIRE(n_depths >= 1 && n_depths <= MAX_DEPTHS, "n_depths out of range (1..3)");
+  RPR_REQUIRE(depths && depth_tokens && depth_scores && depth_row_lo && depth_row_hi, "NULL argument");
+  PrefixOuts px;
+  px.n = n_depths;
+  for (int k = 0; k < n_depths; ++k) {
+    RPR_REQUIRE(depths[k] >= 1 && depths[k] <= L - 1 && (k == 0 || depths[k] > depths[k - 1]),
+                "prefix lengths must be strictly ascending, each in [1, L-1]");
+    RPR_REQUIRE(depth_tokens[k] && depth_scores[k] && depth_row_lo[k] && depth_row_hi[k], "NULL output of a prefix length");
+    px.depths[k] = depths[k];
+    px.tokens[k] = depth_tokens[k]; px.scores[k] = depth_scores[k]; px.lo[k] = depth_row_lo[k]; px.hi[k] = depth_row_hi[k];
+  }
+  return search_entry(c, m, tr, input_ids, attention_mask, Q, Lq, B, L, flags, out_tokens, out_scores, out_row_lo, out_row_hi,
+                      nullptr, nullptr, stream, &px);
 }
 
 int rpr_set_lane_split(rpr_ctx* c, int32_t min_rows) {

@@ -686,6 +686,10 @@ struct TailRankArgs {
   // stage query Qcap + k; the code matrix, for the row range of a surviving sequence
   const int32_t* spare = nullptr; int pool = 0;
   const uint16_t* codes = nullptr; int Lc = 0;
+  // Report length (0 = L). A prefix length T < Lr < L (rpr_search_prefixes): the rule stopped after the first Lr - T of the
+  // remaining steps — the sums take gold[0 .. Lr - T), the ranking divides by Lr + 1 and out_tokens is [., B, Lr]; L stays
+  // the row stride of tokens and, as L - T, of gold. Never with spare entries (such a plan has no extras).
+  int Lr = 0;
 };
 hipError_t launch_tail_rank(const TailRankArgs& a, hipStream_t s);
 // max over the rows of |E[r] (*) w|_2 (w nullable): bound of the logits after the final RMSNorm (model load)

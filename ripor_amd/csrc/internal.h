@@ -187,6 +187,8 @@ struct Workspace {
   DevBuf score[2], lo[2], hi[2], tokens[2], anc[2];
   // staged outputs
   DevBuf o_tokens, o_scores, o_lo, o_hi;
+  // rpr_search_prefixes only: the same four per prefix length of the plan (SearchPlan::depths), tokens [Q, B, p]
+  DevBuf d_tokens[rpr::MAX_DEPTHS], d_scores[rpr::MAX_DEPTHS], d_lo[rpr::MAX_DEPTHS], d_hi[rpr::MAX_DEPTHS];
   // rpr_search_margins only: the child bitmap of the current step [Q, B * Vp / 64] (the selection's tap_valid export) and
   // the per-query pruning margins [Q] float64 (prune_margin.hip)
   DevBuf mg_valid, o_margin;

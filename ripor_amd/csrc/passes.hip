@@ -89,6 +89,9 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, const SearchPlan& plan) {
     E(w.tokens[i], Rv * (size_t)L * 2); E(w.anc[i], Rv * (size_t)L * 2);
   }
   E(w.o_tokens, R * (size_t)L * 4); E(w.o_scores, R * 4); E(w.o_lo, R * 8); E(w.o_hi, R * 8);
+  for (int k = 0; k < plan.n_depths; ++k) {   // rpr_search_prefixes: staged outputs per prefix length
+    E(w.d_tokens[k], R * (size_t)plan.depths[k] * 4); E(w.d_scores[k], R * 4); E(w.d_lo[k], R * 8); E(w.d_hi[k], R * 8);
+  }
   if (plan.margins) { E(w.mg_valid, R * (size_t)m->Vp() / 8); E(w.o_margin, (size_t)Q * 8); }
   const size_t hb = sizeof(__half) * 2;  // two planes
   E(w.eattn_h, T * inner * hb); E(w.eff_h, T * dff * hb); E(w.enc_out_h, T * dm * hb);
@@ -339,6 +342,12 @@ int live_count(Launcher& Ln, const int* dev, int rows) {
   return rows;
 }
 
+// index of prefix length p among the plan's (rpr_search_prefixes), -1 = not asked for
+int depth_index(const SearchPlan& plan, int p) {
+  for (int k = 0; k < plan.n_depths; ++k) if (plan.depths[k] == p) return k;
+  return -1;
+}
+
 int xkv_ld(const rpr_model* m) { return m->d.num_decoder_layers * 2 * m->inner(); }   // row of ws.xkv: K | V of every decoder layer
 
 // Decoder steps [t0, t1) of one stage: embed, nd x {self-attention over the beam's ancestry, cross-attention, FF},
@@ -441,6 +450,14 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
       MarginArgs ma{lg, cur.score, nxt.score, sa.tap_valid, tr->codes, tr->L, t, cur.lo, cur.hi, Q, B, Vp, V, sa.log_softmax,
                     sa.shared0, sv.nq_dev, sv.io.qmap, P<double>(w.o_margin)};
       Ln.run(RPR_K_SELECT, 0, (double)Ma * V * 4, [&] { return launch_prune_margin(ma, s); });
+    }
+    // a prefix length of the plan (rpr_search_prefixes): the beams of the queries walking in this stage after selection step
+    // t are those of a search of length t + 1 — finalize's rule on them, into that length's staged outputs (before a fork
+    // at this depth classifies: every query of the stage is still here)
+    if (const int k = depth_index(plan, t + 1); k >= 0) {
+      FinalizeArgs fa{nxt, Q, B, t + 1, P<int32_t>(w.d_tokens[k]), P<float>(w.d_scores[k]), P<int64_t>(w.d_lo[k]), P<int64_t>(w.d_hi[k]),
+                      sv.nq_dev, sv.io.qmap};
+      Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_finalize(fa, s); });
     }
   }
   Ln.account_live(nullptr, 0);   // the live counter of this stage scales THIS stage's records only (fork, tail, finalize follow)
@@ -598,6 +615,15 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
                   P<int32_t>(w.o_tokens), P<float>(w.o_scores), P<int64_t>(w.o_lo), P<int64_t>(w.o_hi)};
   ra.spare = P<int32_t>(tb.spare); ra.pool = pool; ra.codes = tr->codes; ra.Lc = tr->L;
   Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_tail_rank(ra, s); });
+  // the prefix lengths behind this fork (rpr_search_prefixes): the same rule stopped at p, on the same gold scores
+  for (int k = 0; k < plan.n_depths; ++k) {
+    if (plan.depths[k] <= T) continue;
+    TailRankArgs rp = ra;
+    rp.Lr = plan.depths[k];
+    rp.out_tokens = P<int32_t>(w.d_tokens[k]); rp.out_scores = P<float>(w.d_scores[k]);
+    rp.out_lo = P<int64_t>(w.d_lo[k]); rp.out_hi = P<int64_t>(w.d_hi[k]);
+    Ln.run(RPR_K_FORK, 0, 0, [&] { return launch_tail_rank(rp, s); });
+  }
   Ln.account_live(nullptr, 0);
 }
 

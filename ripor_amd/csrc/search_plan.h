@@ -13,6 +13,7 @@
 namespace rpr {
 
 constexpr int MAX_FORKS = 2;
+constexpr int MAX_DEPTHS = 3;   // prefix lengths one search may report besides its own (rpr_search_prefixes)
 
 struct SearchPlan {
   int Q = 0, Lq = 0, B = 0, L = 0;
@@ -27,15 +28,18 @@ struct SearchPlan {
   int n_forks = 0;               //   0 = plain search
   bool drop_last = false;        // no stage after the last fork (optimistic mode, see plan_forks): its caches are not needed
   int tail_rank_replay = 0, select_radix = -1;   // per-call test selectors of the ranking / selection launchers (tests flip them between calls)
+  int depths[MAX_DEPTHS] = {0, 0, 0};   // rpr_search_prefixes: prefix lengths whose beams are reported too (ascending, each in [1, L-1])
+  int n_depths = 0;                     //   0 = none: the plan, the launches and the key of a plain search
   bool log_softmax() const { return (flags & RPR_FLAG_LOG_SOFTMAX) != 0; }
   auto key() const {
     return std::tie(Q, Lq, B, L, flags, lane, cus, prec, margins, l0, mfma16, extras, pool, forks[0], forks[1], n_forks, drop_last,
-                    tail_rank_replay, select_radix);
+                    tail_rank_replay, select_radix, depths[0], depths[1], depths[2], n_depths);
   }
   bool operator<(const SearchPlan& o) const { return key() < o.key(); }
   bool operator==(const SearchPlan& o) const { return key() == o.key(); }
 };
 static_assert(MAX_FORKS == 2, "SearchPlan::key names every fork depth");
+static_assert(MAX_DEPTHS == 3, "SearchPlan::key names every prefix length");
 
 // the plan of a call that only sizes the shared buffers (rpr_encode, the training step): no forks, no margins
 inline SearchPlan plain_plan(int Q, int Lq, int B, int L) {
@@ -155,6 +159,8 @@ struct SearchCall {
   bool taps = false, margins = false;
   int lane = -1;
   int tail_rank_replay = 0, select_radix = -1;   // RPR_TAIL_RANK_REPLAY / RPR_SELECT_RADIX as the launchers will read them
+  int depths[MAX_DEPTHS] = {0, 0, 0};            // rpr_search_prefixes: the prefix lengths asked for (checked by the caller)
+  int n_depths = 0;
 };
 struct TrieStats { const double* single_frac; const double* extra_mean; };   // per depth 0..L (trie_single_frac)
 
@@ -170,6 +176,8 @@ SearchPlan plan_search(const SearchSettings& s, const SearchModel& m, const Sear
   p.l0 = s.l0_mode > 0 && m.l0_current && p.prec == RPR_PREC_F16X2 ? s.l0_mode : 0;
   p.mfma16 = s.gemm_mfma16 && p.prec == RPR_PREC_F16X2 ? 1 : 0;
   p.tail_rank_replay = a.tail_rank_replay ? 1 : 0; p.select_radix = a.select_radix;
+  p.n_depths = a.n_depths < MAX_DEPTHS ? a.n_depths : MAX_DEPTHS;
+  for (int i = 0; i < p.n_depths; ++i) p.depths[i] = a.depths[i];
   if (!s.forced_tail || a.taps || a.L < 3 || !std::isfinite(m.logit_bound)) return p;
   const double per_step = 2.0 * (double)m.logit_bound + (p.log_softmax() ? std::log((double)m.V) : 0.0);
   if (1e8 - a.L * per_step <= 1e7) return p;   // logits too large for the masked-candidate proof (passes.hip: enqueue_fork)
@@ -185,7 +193,10 @@ SearchPlan plan_search(const SearchSettings& s, const SearchModel& m, const Sear
     const TrieStats ts = stats();
     p.n_forks = plan_forks(ts.single_frac, ts.extra_mean, a.Q, a.B, a.L, s.forced_tail, E, pool, p.forks, &p.drop_last);
   }
-  if (p.n_forks > 0) { p.extras = E; p.pool = pool; }
+  // Prefix lengths: the forks stay where the same (Q, B, L) has them without (planned above with that call's extras), but
+  // no query is forced with extras — it would be pruned inside the tail, where its intermediate beam sets do not exist.
+  // In optimistic mode such a query raises the leftover flag instead.
+  if (p.n_forks > 0 && p.n_depths == 0) { p.extras = E; p.pool = pool; }
   return p;
 }
 

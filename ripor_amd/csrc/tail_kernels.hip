@@ -505,6 +505,7 @@ __global__ __launch_bounds__(1024) void tail_rank_kernel(TailRankArgs a) {
   if (i >= *a.nf_dev) return;
   if (a.pool > 0 && a.spare[i] >= 0) { tail_rank_extras(a, i, a.spare[i]); return; }   // block-uniform
   const int B = a.B, T = a.T, L = a.L, Lt = L - T;
+  const int Lr = a.Lr ? a.Lr : L, n = Lr - T;            // report length (TailRankArgs::Lr): the first n of the Lt remaining steps
   double* S = reinterpret_cast<double*>(smem_raw);       // [B] cumulative score of the beam that started in slot b
   int* pos = reinterpret_cast<int*>(S + B);              // [B] its current slot
   int* npos = pos + B;                                   // [B]
@@ -515,8 +516,8 @@ __global__ __launch_bounds__(1024) void tail_rank_kernel(TailRankArgs a) {
   for (int b = tid; b < B; b += nt) {
     double s = a.st.score[r0 + b];
     const float* g = a.gold + ((size_t)i * B + b) * Lt;
-    for (int t = 0; t < Lt; ++t) s = ((double)g[t] + 0.0) + s;
-    S[b] = s / (double)(L + 1);
+    for (int t = 0; t < n; ++t) s = ((double)g[t] + 0.0) + s;
+    S[b] = s / (double)(Lr + 1);
     pos[b] = b;
   }
   __syncthreads();
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(1024) void tail_rank_kernel(TailRankArgs a) {
   if (tie) {                                             // block-uniform: exact ties -> the full replay decides them
     for (int b = tid; b < B; b += nt) S[b] = a.st.score[r0 + b];
     __syncthreads();
-    for (int t = 0; t < Lt; ++t) {
+    for (int t = 0; t < n; ++t) {
       for (int b = tid; b < B; b += nt) S[b] = ((double)a.gold[((size_t)i * B + b) * Lt + t] + 0.0) + S[b];
       __syncthreads();
       for (int b = tid; b < B; b += nt) {
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(1024) void tail_rank_kernel(TailRankArgs a) {
       for (int b = tid; b < B; b += nt) pos[b] = npos[b];
       __syncthreads();
     }
-    for (int b = tid; b < B; b += nt) S[b] = S[b] / (double)(L + 1);
+    for (int b = tid; b < B; b += nt) S[b] = S[b] / (double)(Lr + 1);
     __syncthreads();
     for (int b = tid; b < B; b += nt) {
       const double s = S[b];
@@ -563,9 +564,9 @@ __global__ __launch_bounds__(1024) void tail_rank_kernel(TailRankArgs a) {
     a.out_lo[o0 + rk] = a.st.lo[r0 + b];
     a.out_hi[o0 + rk] = a.st.hi[r0 + b];
   }
-  for (int k = tid; k < B * L; k += nt) {
-    const int b = k / L, p = k - b * L;
-    a.out_tokens[(o0 + npos[b]) * L + p] = (int32_t)a.tokens[((size_t)i * B + b) * L + p];
+  for (int k = tid; k < B * Lr; k += nt) {
+    const int b = k / Lr, p = k - b * Lr;
+    a.out_tokens[(o0 + npos[b]) * Lr + p] = (int32_t)a.tokens[((size_t)i * B + b) * L + p];
   }
 }
 
@@ -575,6 +576,7 @@ hipError_t launch_tail_rank(const TailRankArgs& a_in, hipStream_t s) {
   TailRankArgs a = a_in;
   if (replay) a.replay = 1;
   if (a.pool > 0 && (a.B >= 32 || !a.spare || !a.codes)) return hipErrorInvalidValue;
+  if (a.Lr && (a.pool > 0 || a.Lr <= a.T || a.Lr > a.L)) return hipErrorInvalidValue;
   const size_t smem = (size_t)a.B * (sizeof(double) + 2 * sizeof(int)) + 16;
   hipLaunchKernelGGL(tail_rank_kernel, dim3(a.Qcap), dim3(a.B > 256 ? 1024 : 256), smem, s, a);
   return hipGetLastError();

@@ -561,6 +561,9 @@ class SearchResult:
     # still below eps is a near-tie of the reference's own arithmetic, nothing more can be done about it
     rerun: Optional[torch.Tensor] = None
     margins_f32: Optional[torch.Tensor] = None
+    # search(..., prefix_lengths=(4, 8)): prefix length p -> the beams of a search of length p (tokens [Q, B, p]; include/ripor_hip.h:
+    # rpr_search_prefixes)
+    prefixes: Optional[Dict[int, "SearchResult"]] = None
 
 
 def splice_rows(full, mask, sub):
@@ -589,10 +592,17 @@ def splice_rows(full, mask, sub):
 
 def search(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attention_mask: torch.Tensor,
            num_beams: int, max_new_tokens: int, apply_log_softmax_for_scores: bool = False,
-           use_graph: bool = True, taps: bool = False, margins: bool = False) -> SearchResult:
+           use_graph: bool = True, taps: bool = False, margins: bool = False,
+           prefix_lengths: Optional[Sequence[int]] = None) -> SearchResult:
     """One call of the hot path: encoder + L fused decode/select steps. Asynchronous on the
     current torch stream; results are device tensors. ``margins``: also the per-query pruning margin
-    (``rpr_search_margins``: one more kernel per selection step; tokens, scores and row ranges are the same bits)."""
+    (``rpr_search_margins``: one more kernel per selection step; tokens, scores and row ranges are the same bits).
+    ``prefix_lengths`` (up to three, strictly ascending, each below ``max_new_tokens``): also the beams the search holds
+    at those lengths, as ``result.prefixes[p]`` — what a search with ``max_new_tokens=p`` returns (``rpr_search_prefixes``);
+    not together with ``taps`` or ``margins``."""
+    depths = [int(p) for p in prefix_lengths] if prefix_lengths is not None else []
+    if depths and (taps or margins):
+        raise ValueError("prefix_lengths cannot be combined with taps or margins")
     ctx = model.ctx
     dev = ctx.device
     ids = input_ids.to(device=dev, dtype=torch.int32).contiguous()
@@ -627,7 +637,22 @@ def search(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attent
                                        "step_valid")])
     tap_arg = C.byref(tap_struct) if tap_struct is not None else None
     mg = None
-    if margins:
+    prefixes = None
+    if depths:
+        # (an invalid list — unsorted, out of range, more than three — is refused by the library before anything is written)
+        prefixes = {p: SearchResult(torch.empty((Q, B, max(p, 0)), dtype=torch.int32, device=dev),
+                                    torch.empty((Q, B), dtype=torch.float32, device=dev),
+                                    torch.empty((Q, B), dtype=torch.int64, device=dev),
+                                    torch.empty((Q, B), dtype=torch.int64, device=dev)) for p in depths}
+        if len(prefixes) != len(depths):
+            raise ValueError("prefix_lengths must be strictly ascending")
+        n = len(depths)
+        ptrs = lambda f: (C.c_void_p * n)(*[getattr(prefixes[p], f).data_ptr() for p in depths])
+        check(ctx.lib.rpr_search_prefixes(ctx.handle, model.handle, trie.handle, ids.data_ptr(), mask.data_ptr(), Q, Lq, B, L,
+                                          flags, tokens.data_ptr(), scores.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                          n, (C.c_int32 * n)(*depths), ptrs("tokens"), ptrs("scores"), ptrs("row_lo"),
+                                          ptrs("row_hi"), _stream_ptr(dev)), "rpr_search_prefixes")
+    elif margins:
         mg = torch.empty((Q,), dtype=torch.float64, device=dev)
         check(ctx.lib.rpr_search_margins(ctx.handle, model.handle, trie.handle, ids.data_ptr(), mask.data_ptr(), Q, Lq, B, L,
                                          flags, tokens.data_ptr(), scores.data_ptr(), lo.data_ptr(), hi.data_ptr(),
@@ -637,7 +662,7 @@ def search(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attent
                                  tokens.data_ptr(), scores.data_ptr(), lo.data_ptr(), hi.data_ptr(),
                                  tap_arg, _stream_ptr(dev)), "rpr_search")
     # ids/mask must stay alive until the async D2D staging copies have been enqueued (they have).
-    return SearchResult(tokens, scores, lo, hi, tap_out, margins=mg)
+    return SearchResult(tokens, scores, lo, hi, tap_out, margins=mg, prefixes=prefixes)
 
 
 class GuardedSearch:
@@ -653,8 +678,10 @@ class GuardedSearch:
     whose margin is below eps on a ctx that is not already in f32 are searched again as ONE batch in exact fp32; their rows
     replace the split-precision ones (``splice_rows``), and the result carries ``margins``, ``rerun`` and ``margins_f32``."""
 
-    def __init__(self, model, trie, ids, mask, B, L, log_softmax, res, ticket, optimistic=False, margin_guard=None):
+    def __init__(self, model, trie, ids, mask, B, L, log_softmax, res, ticket, optimistic=False, margin_guard=None,
+                 prefix_lengths=None):
         self._args = (model, trie, ids, mask, B, L, log_softmax)
+        self._prefix_lengths = prefix_lengths    # a repeat asks for the same prefix lengths
         self._margin_guard = margin_guard
         # whether the search just issued ran in exact fp32 (the ctx setting, or a model pinned to it): nothing to re-run then
         self._ran_f32 = margin_guard is not None and (
@@ -734,7 +761,7 @@ class GuardedSearch:
             try:
                 ctx.status(clear=True)
                 self._res = search(model, trie, ids, mask, B, L, apply_log_softmax_for_scores=log_softmax,
-                                   margins=self._margin_guard is not None)
+                                   margins=self._margin_guard is not None, prefix_lengths=self._prefix_lengths)
                 ctx.status(clear=True)
             finally:
                 ctx.set_precision(saved_prec)
@@ -773,14 +800,20 @@ def _optimistic_allowed(ctx: Context) -> bool:
 
 def search_guarded(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor, attention_mask: torch.Tensor,
                    num_beams: int, max_new_tokens: int, apply_log_softmax_for_scores: bool = False,
-                   optimistic: Optional[bool] = None, margin_guard: Optional[float] = None) -> GuardedSearch:
+                   optimistic: Optional[bool] = None, margin_guard: Optional[float] = None,
+                   prefix_lengths: Optional[Sequence[int]] = None) -> GuardedSearch:
     """``search`` plus the status guards, checked when ``result()`` is called (see :class:`GuardedSearch`). With
     ``optimistic`` (default: on unless ``RPR_OPTIMISTIC_TAIL=0``) a ctx in the exact forced-tail mode runs this call in
     the optimistic mode — the last, almost always empty, step-by-step stage is not enqueued — and the guard repeats the
     batch exactly in the rare case a query needed it. ``margin_guard`` = eps (None: off, the same calls and the same bits
     as before): the near-tie guard of :class:`GuardedSearch`; 1e-3, the project's tolerance for cumulative scores at the
-    pruning boundary, is the suggested value."""
+    pruning boundary, is the suggested value. ``prefix_lengths``: as in ``search``, passed on to a repeat as well; not
+    together with ``margin_guard`` (margins are not computed for the shorter lengths)."""
     import os
+    if prefix_lengths is not None:
+        prefix_lengths = tuple(int(p) for p in prefix_lengths) or None
+    if prefix_lengths and margin_guard is not None:
+        raise ValueError("prefix_lengths cannot be combined with margin_guard")
     ctx = model.ctx
     if optimistic is None:
         optimistic = os.environ.get("RPR_OPTIMISTIC_TAIL", "1") != "0"
@@ -791,12 +824,14 @@ def search_guarded(model: DeviceModel, trie: DeviceTrie, input_ids: torch.Tensor
         ctx.set_forced_tail(2)
     try:
         res = search(model, trie, input_ids, attention_mask, num_beams, max_new_tokens,
-                     apply_log_softmax_for_scores=apply_log_softmax_for_scores, margins=margin_guard is not None)
+                     apply_log_softmax_for_scores=apply_log_softmax_for_scores, margins=margin_guard is not None,
+                     prefix_lengths=prefix_lengths)
     finally:
         ctx.set_forced_tail(mode)
     ticket = ctx.status_async(clear=True)
     return GuardedSearch(model, trie, input_ids, attention_mask, int(num_beams), int(max_new_tokens),
-                         bool(apply_log_softmax_for_scores), res, ticket, optimistic=went_optimistic, margin_guard=margin_guard)
+                         bool(apply_log_softmax_for_scores), res, ticket, optimistic=went_optimistic, margin_guard=margin_guard,
+                         prefix_lengths=prefix_lengths)
 
 
 def lngknp_forward(model: DeviceModel, input_ids: torch.Tensor, attention_mask: torch.Tensor, doc_codes: torch.Tensor,

@@ -247,13 +247,23 @@ def constrained_decode(model, dataloader, prefix_constrain_processor, smtid_to_d
 
 def constrained_decode_smtid(model, dataloader, prefix_constrain_processor, smtid_to_docids, max_new_token, device,
                              out_dir, local_rank, topk=100, apply_log_softmax_for_scores=False, write=True,
-                             near_tie_guard=None, near_tie=None):
+                             near_tie_guard=None, near_tie=None, prefix_out_dirs=None):
     """reference evaluate.py:134-178: nested ``{qid: {smtid: {docid: score}}}`` for the training-data
     generation pass (prefix search: max_new_token in {4, 8, 16, 32}, many docids per smtid) ->
     ``qid_smtid_rankdata_{rank}.json``. ``smtid_to_docids``: the reference's dict or a DocidTable.
-    ``near_tie_guard`` / ``near_tie``: as in :func:`constrained_decode_doc`."""
+    ``near_tie_guard`` / ``near_tie``: as in :func:`constrained_decode_doc`.
+    ``prefix_out_dirs`` ({prefix length p < max_new_token: directory}, extra of this implementation): the same search also
+    reports its beams at every p (``prefix_lengths`` of the generation call), and each directory gets the
+    ``qid_smtid_rankdata_{rank}.json`` of a run with ``max_new_token=p`` (score = rel_score * p) — one search instead of one
+    per length. Needs a DocidTable (the docids of a prefix are the rows of its range) and no near-tie guard. Returns the
+    rank data of ``max_new_token``; ``prefix_out_dirs`` given and ``write=False``: ``(that, {p: rank data of p})``."""
     out: Dict[int, Dict[str, Dict[str, float]]] = {}
     use_ranges = isinstance(smtid_to_docids, DocidTable)
+    depths = sorted(int(p) for p in (prefix_out_dirs or {}))
+    if depths and (not use_ranges or near_tie_guard is not None):
+        raise ValueError("prefix_out_dirs needs a DocidTable and cannot be combined with the near-tie guard")
+    prefix_dirs = {int(p): d for p, d in (prefix_out_dirs or {}).items()}
+    prefix_out: Dict[int, Dict[int, Dict[str, Dict[str, float]]]] = {p: {} for p in depths}
     for batch in dataloader:
         with torch.no_grad():
             inputs = {k: v.to(device) for k, v in batch.items() if k != "id"}
@@ -262,10 +272,23 @@ def constrained_decode_smtid(model, dataloader, prefix_constrain_processor, smti
                 attention_mask=inputs["attention_mask"].long(), max_new_tokens=max_new_token, output_scores=True,
                 return_dict=True, return_dict_in_generate=True, num_beams=topk, num_return_sequences=topk,
                 apply_log_softmax_for_scores=apply_log_softmax_for_scores,
-                **({} if near_tie_guard is None else {"near_tie_guard": near_tie_guard}))
+                **({} if near_tie_guard is None else {"near_tie_guard": near_tie_guard}),
+                **({"prefix_lengths": tuple(depths)} if depths else {}))
         batch_qids = batch["id"].cpu().tolist()
         if near_tie is not None and outputs.near_tie is not None:
             near_tie.note(batch_qids, *outputs.near_tie)
+        for p in depths:   # what the loop below does for max_new_token, on the beams of prefix length p
+            po = outputs.prefix_outputs[p]
+            p_smtids = convert_ptsmtids_to_strsmtid(po.sequences.view(-1, topk, p + 1), p)
+            p_perm = prefix_constrain_processor.trie(device).perm
+            for qid, ranked, rel, los, his in zip(batch_qids, p_smtids, po.sequences_scores.view(-1, topk).cpu().tolist(),
+                                                  po.row_lo.view(-1, topk).cpu().tolist(), po.row_hi.view(-1, topk).cpu().tolist()):
+                cur = prefix_out[p][qid] = {}
+                for smtid, rel_score, l, h in zip(ranked, rel, los, his):
+                    docs = cur[smtid] = {}
+                    score = rel_score if apply_log_softmax_for_scores else rel_score * p
+                    for row in p_perm[l:h]:
+                        docs[smtid_to_docids.docids[int(row)]] = score
         str_smtids = convert_ptsmtids_to_strsmtid(outputs.sequences.view(-1, topk, max_new_token + 1), max_new_token)
         relevant_scores = outputs.sequences_scores.view(-1, topk).cpu().tolist()
         lo = outputs.row_lo.view(-1, topk).cpu().tolist()
@@ -285,7 +308,43 @@ def constrained_decode_smtid(model, dataloader, prefix_constrain_processor, smti
     if write:
         with open(os.path.join(out_dir, f"qid_smtid_rankdata_{local_rank}.json"), "w") as fout:
             json.dump(out, fout)
+        for p in depths:
+            os.makedirs(prefix_dirs[p], exist_ok=True)
+            with open(os.path.join(prefix_dirs[p], f"qid_smtid_rankdata_{local_rank}.json"), "w") as fout:
+                json.dump(prefix_out[p], fout)
+    elif depths:
+        return out, prefix_out
     return out
+
+
+def parse_prefix_out_dirs(text, max_new_token) -> Dict[int, str]:
+    """``--prefix_out_dirs``: a JSON object {prefix length: directory}; lengths in {4, 8, 16} and below ``--max_new_token``.
+    SystemExit on anything else (checked before a model or a trie is loaded)."""
+    try:
+        raw = json.loads(text)
+    except ValueError as e:
+        raise SystemExit(f"--prefix_out_dirs is not JSON: {e}")
+    if not isinstance(raw, dict) or not raw:
+        raise SystemExit("--prefix_out_dirs must be a JSON object {prefix length: directory}")
+    out: Dict[int, str] = {}
+    for k, d in raw.items():
+        if str(k) not in ("4", "8", "16") or max_new_token is None or int(k) >= int(max_new_token):
+            raise SystemExit(f"--prefix_out_dirs: prefix length {k!r} must be one of 4, 8, 16 and below --max_new_token={max_new_token}")
+        if not isinstance(d, str) or not d:
+            raise SystemExit(f"--prefix_out_dirs: the directory of prefix length {k} must be a non-empty string")
+        out[int(k)] = d
+    return out
+
+
+def check_rankdata_flags(args) -> Optional[Dict[int, str]]:
+    """The rank-data task's --prefix_out_dirs, parsed and checked against the other flags (None = not given)."""
+    text = getattr(args, "prefix_out_dirs", None)
+    if text is None:
+        return None
+    if getattr(args, "near_tie_guard", None) is not None:
+        raise SystemExit("--prefix_out_dirs cannot be combined with --near_tie_guard (pruning margins are not computed for the "
+                         "shorter prefix lengths)")
+    return parse_prefix_out_dirs(text, args.max_new_token)
 
 
 class NearTieLog:
@@ -576,6 +635,7 @@ def merge_runs(out_dir: str, expected_files: Optional[int] = None) -> Dict[str, 
 def t5seq_aq_get_qid_to_smtid_rankdata(args):
     """reference evaluate.py:528-611 (train-query pass that produces the (query, smtid-prefix, docids)
     rank data): same search with ``--max_new_token`` in {4, 8, 16, 32} over ``--train_query_dir``."""
+    prefix_dirs = check_rankdata_flags(args)   # (--prefix_out_dirs: refused here, before anything is loaded)
     import torch.distributed as dist
     from transformers import AutoTokenizer
     from .dataset.sharding import shard_indices
@@ -605,7 +665,8 @@ def t5seq_aq_get_qid_to_smtid_rankdata(args):
     log = NearTieLog(eps) if eps is not None else None
     constrained_decode_smtid(model.base_model, loader, processor, table, args.max_new_token, device=local_rank,
                              out_dir=args.out_dir, local_rank=local_rank, topk=args.topk,
-                             apply_log_softmax_for_scores=args.apply_log_softmax_for_scores, near_tie_guard=eps, near_tie=log)
+                             apply_log_softmax_for_scores=args.apply_log_softmax_for_scores, near_tie_guard=eps, near_tie=log,
+                             **({} if prefix_dirs is None else {"prefix_out_dirs": prefix_dirs}))
     if log is not None:
         log.write(args.out_dir)
 
@@ -870,6 +931,11 @@ def get_args(argv=None):
     ap.add_argument("--near_tie_guard", type=float, default=argparse.SUPPRESS,
                     help="t5seq_aq_retrieve_docids / t5seq_aq_get_qid_to_smtid_rankdata: search queries whose pruning margin is "
                          "below this (suggested: 1e-3) again in exact fp32 and write near_tie.json")
+    # absent unless given: t5seq_aq_get_qid_to_smtid_rankdata also writes the rank data of shorter prefix lengths from the same search
+    ap.add_argument("--prefix_out_dirs", default=argparse.SUPPRESS,
+                    help='t5seq_aq_get_qid_to_smtid_rankdata: JSON {"4": DIR4, "8": DIR8} — the search to --max_new_token also '
+                         "reports its beams at these prefix lengths (4, 8, 16, each below --max_new_token) and writes each one's "
+                         "qid_smtid_rankdata_{rank}.json into its directory, as a run with that --max_new_token would")
     return ap.parse_args(argv)
 
 

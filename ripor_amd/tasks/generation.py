@@ -37,7 +37,7 @@ class BeamSearchEncoderDecoderOutput:
 
     def __init__(self, sequences=None, sequences_scores=None, scores=None, beam_indices=None, encoder_attentions=None,
                  encoder_hidden_states=None, decoder_attentions=None, cross_attentions=None, decoder_hidden_states=None,
-                 row_lo=None, row_hi=None, guard=None, _step_record=None, near_tie=None):
+                 row_lo=None, row_hi=None, guard=None, _step_record=None, near_tie=None, prefix_outputs=None):
         self.sequences, self.sequences_scores = sequences, sequences_scores
         self._scores, self._beam_indices = scores, beam_indices
         self.encoder_attentions, self.encoder_hidden_states = encoder_attentions, encoder_hidden_states
@@ -49,6 +49,9 @@ class BeamSearchEncoderDecoderOutput:
         self.guard = guard
         # with near_tie_guard (and without defer_status): (margins [Q] float64, rerun [Q] bool, margins_f32 [rerun.sum()])
         self.near_tie = near_tie
+        # with prefix_lengths: {p: output object of the same search stopped at p tokens (sequences [Q*B', p+1], sequences_scores,
+        # row_lo, row_hi)} — what a call with max_new_tokens=p returns
+        self.prefix_outputs = prefix_outputs
         self._step_record = _step_record      # callable -> (scores tuple, beam_indices tuple), or None
 
     def _materialise(self):
@@ -247,8 +250,12 @@ def generate_for_constrained_prefix_beam_search(
     # near_tie_guard = eps (extra of this implementation, default off): queries whose pruning margin is below eps are
     # searched again in exact fp32 (E.GuardedSearch); the output then carries .near_tie = (margins, rerun, margins_f32)
     near_tie_guard = model_kwargs.pop("near_tie_guard", None)
+    # prefix_lengths = (4, 8) (extra of this implementation, default none): the beams the search holds at those lengths come
+    # back as outputs.prefix_outputs[p] (E.search: rpr_search_prefixes); not together with near_tie_guard
+    prefix_lengths = model_kwargs.pop("prefix_lengths", None)
     guard = E.search_guarded(em, trie, input_ids, attention_mask, num_beams, L,
-                             apply_log_softmax_for_scores=bool(apply_log_softmax_for_scores), margin_guard=near_tie_guard)
+                             apply_log_softmax_for_scores=bool(apply_log_softmax_for_scores), margin_guard=near_tie_guard,
+                             **({"prefix_lengths": prefix_lengths} if prefix_lengths else {}))
     defer = bool(model_kwargs.pop("defer_status", False)) and bool(return_dict_in_generate)
     res = guard._res if defer else guard.result()
     Q, B, K = input_ids.shape[0], num_beams, num_return_sequences
@@ -256,6 +263,15 @@ def generate_for_constrained_prefix_beam_search(
     seqs = torch.cat([torch.zeros((Q, K, 1), dtype=torch.long, device=tok.device), tok], dim=2).reshape(Q * K, L + 1)
     if not return_dict_in_generate:
         return seqs
+    prefix_outputs = None
+    if res.prefixes is not None:
+        prefix_outputs = {}
+        for p, r in res.prefixes.items():
+            ptok = r.tokens[:, :K, :].to(torch.long)
+            prefix_outputs[p] = BeamSearchEncoderDecoderOutput(
+                sequences=torch.cat([torch.zeros((Q, K, 1), dtype=torch.long, device=ptok.device), ptok], dim=2).reshape(Q * K, p + 1),
+                sequences_scores=r.scores[:, :K].reshape(Q * K) if output_scores else None,
+                row_lo=r.row_lo[:, :K].reshape(Q * K), row_hi=r.row_hi[:, :K].reshape(Q * K))
     record = None
     if output_scores and em.V % 64 == 0:   # (the debug taps need a vocab size on the 64 grid)
         ids_keep, mask_keep, ls = input_ids, attention_mask, bool(apply_log_softmax_for_scores)
@@ -270,4 +286,5 @@ def generate_for_constrained_prefix_beam_search(
         sequences_scores=res.scores[:, :K].reshape(Q * K) if output_scores else None,
         row_lo=res.row_lo[:, :K].reshape(Q * K), row_hi=res.row_hi[:, :K].reshape(Q * K), guard=guard if defer else None,
         _step_record=record,
-        near_tie=(res.margins, res.rerun, res.margins_f32) if near_tie_guard is not None and not defer else None)
+        near_tie=(res.margins, res.rerun, res.margins_f32) if near_tie_guard is not None and not defer else None,
+        prefix_outputs=prefix_outputs)
