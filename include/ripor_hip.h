@@ -467,6 +467,12 @@ int rpr_set_train_dropout(rpr_ctx* ctx, float rate, uint64_t seed, uint64_t step
  *   Weights are checked at rpr_load_model: a model that does not fit is pinned to RPR_PREC_F32 (rpr_model_f32_only).
  * RPR_STATUS_EMPTY_QUERY: a query's attention mask has no attended position (its cross-attention output is defined
  *   as zero here; the reference would average the padded positions).
+ * RPR_STATUS_SMALL_STREAM: in RPR_PREC_F16X2 mode a row of the residual stream had an RMS under 2^-3 (0 < mean(x^2) < 2^-6)
+ *   at one of the pass's RMSNorm sites (tested once per pass over its row totals). The planes of the stream and its fixed-point row sums have ABSOLUTE resolutions (2^-21 per
+ *   element, 2^-17 per 16- to 256-column piece of a row) that were chosen for rows of RMS ~1 .. 1e5; under the floor the
+ *   normalised activations lose their fifth digit and beam scores leave the 1e-4 bar (measured: DESIGN.md, "Working range").
+ *   Nothing is clamped, but the results since the last clear are NOT trustworthy: repeat them with
+ *   rpr_set_precision(RPR_PREC_F32), as after RPR_STATUS_SATURATED (the Python boundaries do). Rows of zeros do not raise it.
  * rpr_get_status synchronises `stream`, returns the flags accumulated by the work enqueued so far and, if clear != 0,
  * resets them. */
 #define RPR_STATUS_SATURATED 1u
@@ -474,9 +480,10 @@ int rpr_set_train_dropout(rpr_ctx* ctx, float rate, uint64_t seed, uint64_t step
 /* RPR_STATUS_TAIL_LEFTOVER: a search in the optimistic forced-tail mode (rpr_set_forced_tail(ctx, 2)) met a query that
  *   was still unforced at its last fork; the outputs of that query are unspecified — repeat the call in mode 1. */
 #define RPR_STATUS_TAIL_LEFTOVER 4u
+#define RPR_STATUS_SMALL_STREAM 8u
 int rpr_get_status(rpr_ctx* ctx, void* stream, uint32_t* out_flags, int clear);
 /* The same words WITHOUT a synchronisation: enqueues on `stream` a copy of the four raw status words ([0] != 0:
- * SATURATED, [1] != 0: EMPTY_QUERY, [2] != 0: TAIL_LEFTOVER, [3] reserved) into host_words ([host], pinned, 16 bytes;
+ * SATURATED, [1] != 0: EMPTY_QUERY, [2] != 0: TAIL_LEFTOVER, [3] != 0: SMALL_STREAM) into host_words ([host], pinned, 16 bytes;
  * NULL = no copy) and, if clear != 0, their reset behind it. A caller that records an event after this call reads the
  * flags of exactly the work enqueued before it once the event has completed — the search loop of
  * ripor_amd/evaluate.py checks batch n this way while batch n + 1 runs (the reference loop synchronises >= 2*B*Q times

@@ -19,7 +19,9 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
  K_COUNT) = range(11)
 KERNEL_CLASS_NAMES = ["gemm", "dec_self_attn", "dec_cross_attn", "enc_attn", "rmsnorm", "select", "other", "gemm_small",
                       "tail_self_attn", "fork"]
-STATUS_SATURATED, STATUS_EMPTY_QUERY, STATUS_TAIL_LEFTOVER = 1, 2, 4
+STATUS_SATURATED, STATUS_EMPTY_QUERY, STATUS_TAIL_LEFTOVER, STATUS_SMALL_STREAM = 1, 2, 4, 8
+# either one: the split-precision results since the last clear are not trustworthy and the call is repeated in exact fp32
+STATUS_NEEDS_F32 = STATUS_SATURATED | STATUS_SMALL_STREAM
 ABI_VERSION = 4
 
 PREC_F32, PREC_F16X2, PREC_BF16 = 0, 1, 2

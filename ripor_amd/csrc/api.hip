@@ -1011,6 +1011,8 @@ int rpr_op_linear_h2(rpr_ctx* c, const float* A, const float* W, int32_t M, int3
     o.rm_B = rm_B; o.rm_slot = 64; o.rm_head = (size_t)rm_B * 64; o.rm_stride = (size_t)(split_n / 64) * rm_B * 64;
   } else if (mode == RPR_LIN_FUSED_NORM) {  // XStream::in: rows scaled by rsqrt(row_ssq / (K * SSQ_FIX) + eps)
     in.ssq = reinterpret_cast<const unsigned long long*>(row_ssq); in.inv_d_fix = 1.0f / ((float)K * SSQ_FIX); in.eps = eps;
+    // (the floor test a pass runs over its row totals, passes.hip Pass::check_ssq)
+    RPR_HIP(launch_ssq_floor(reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(row_ssq)), (size_t)M, in.inv_d_fix, c->status, false, s));
   }
   linear(Ln, in, {W, Wt.as<__half>(), N, K}, M, o, mode == RPR_LIN_LIVE_ROWS ? reinterpret_cast<const int*>(m_dev) : nullptr);
   RPR_HIP(hipStreamSynchronize(s));   // the temporaries are freed when this scope ends
@@ -1071,11 +1073,11 @@ int rpr_get_status(rpr_ctx* c, void* stream, uint32_t* out_flags, int clear) {
   RPR_REQUIRE(c && out_flags, "NULL argument");
   RPR_HIP(hipSetDevice(c->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  RPR_HIP(hipMemcpyAsync(c->status_host, c->status, 12, hipMemcpyDeviceToHost, s));
-  if (clear) RPR_HIP(hipMemsetAsync(c->status, 0, 12, s));
+  RPR_HIP(hipMemcpyAsync(c->status_host, c->status, 16, hipMemcpyDeviceToHost, s));
+  if (clear) RPR_HIP(hipMemsetAsync(c->status, 0, 16, s));
   RPR_HIP(hipStreamSynchronize(s));
   *out_flags = (c->status_host[0] ? RPR_STATUS_SATURATED : 0u) | (c->status_host[1] ? RPR_STATUS_EMPTY_QUERY : 0u) |
-               (c->status_host[2] ? RPR_STATUS_TAIL_LEFTOVER : 0u);
+               (c->status_host[2] ? RPR_STATUS_TAIL_LEFTOVER : 0u) | (c->status_host[STATUS_WORD_SMALL] ? RPR_STATUS_SMALL_STREAM : 0u);
   return RPR_OK;
 }
 

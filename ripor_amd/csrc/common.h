@@ -77,9 +77,23 @@ __host__ __device__ __forceinline__ float dyn_plane_scale(float amax) {
 // tiles of d_model = 1024), so the 64-bit total cannot wrap; a row stored whole by an embedding kernel is capped at 2^63
 // (1.4e14: RMS 4.3e5 at d = 768). A capped value raises the ctx's sticky saturation word like a clamped plane element does,
 // and the boundary repeats the batch in exact fp32. (Until round 5: 2^-20 units read back as a signed value — the sum wrapped
-// silently from sum x^2 = 8.8e12 on, RMS 1e5 at d = 768.) Partials are rounded to nearest: the error of a row total is
-// ~6e-5 absolute, 1e-7 of a row of RMS 1.
+// silently from sum x^2 = 8.8e12 on, RMS 1e5 at d = 768.) Partials are rounded to nearest: half a unit each, so the error of
+// a row total is ABSOLUTE — up to pieces x 2^-17 (48 pieces of 16 columns at d = 768: 3.7e-4; typically ~6e-5), 1e-7 of the
+// total of a row of RMS 1 but 1e-3 of it at RMS 0.01, and the planes' own absolute resolution (X_PLANE_SCALE below) shrinks
+// the same way. The working range therefore has a floor as well as a ceiling (tests/test_gpu_magnitude.py): a
+// row total whose mean square is under X_MS_FLOOR raises the ctx's sticky small-stream word, and the boundary repeats the
+// batch in exact fp32 as it does after a clamp. The totals are looked at by ONE small kernel per pass over all its sites
+// (launch_ssq_floor: behind the last layer of an encoder / tail / training pass, for the decoder steps folded into the
+// zeroing of the next step's slots) — in the readers themselves (ssq_rsqrt in four GEMM kernels) the same test cost the
+// headline search 0.5 %. A total of 0 is a row of zeros, or one past a device-side live count: every producer skips those
+// rows (m < Mlive / Mlim), so their slots keep the 0 the pass's zeroing wrote. No report for either.
 constexpr float SSQ_FIX = 65536.0f;
+constexpr float X_MS_FLOOR = 1.0f / 64.0f;              // mean(x^2) of a row of RMS 2^-3
+// The ctx's sticky status words (rpr_status_words_async): [0] saturated, [1] empty query, [2] tail leftover, [3] small stream.
+constexpr int STATUS_WORD_SMALL = 3;
+// n row totals (every site of a pass): a total with 0 < total * inv_d_fix < X_MS_FLOOR sets status[STATUS_WORD_SMALL];
+// zero: the slots are cleared behind the test (the next decoder step's zeroing)
+hipError_t launch_ssq_floor(unsigned long long* ssq, size_t n, float inv_d_fix, unsigned int* status, bool zero, hipStream_t s);
 constexpr float SSQ_PART_CAP = 2199023255552.0f;        // 2^41 = 2^57 units
 constexpr float SSQ_ROW_CAP = 140737488355328.0f;       // 2^47 = 2^63 units
 __device__ __forceinline__ unsigned long long ssq_to_fix(float ss, unsigned int* sat, float cap = SSQ_PART_CAP) {

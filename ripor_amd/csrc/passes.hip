@@ -187,8 +187,19 @@ struct Pass {
 
   void rows(int M_, int m_acc_) { M = M_; m_acc = m_acc_; }
   int site(int layer, int k) const { return layer * spl + k; }
-  void zero_ssq() {   // every ssq slot of the pass starts at zero (split mode; once per pass, the decoder steps once per step)
-    if (h2) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_zero_u64(xs.ssq, (size_t)(spl * layers + 1) * xs.rows, Ln.s); });
+  // every ssq slot of the pass starts at zero (split mode; once per pass, the decoder steps once per step). check: the slots
+  // hold the totals of THIS call's previous step — test them against the stream's floor before they go (never the first
+  // zeroing of a call: what it finds belongs to an earlier call, whose flags were read and cleared long ago)
+  void zero_ssq(bool check = false) {
+    if (!h2) return;
+    const size_t n = (size_t)(spl * layers + 1) * xs.rows;
+    if (check) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_ssq_floor(xs.ssq, n, 1.0f / ((float)dm * SSQ_FIX), Ln.c->status, true, Ln.s); });
+    else Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_zero_u64(xs.ssq, n, Ln.s); });
+  }
+  void check_ssq() {  // behind the last layer of a pass: a row total under the floor raises RPR_STATUS_SMALL_STREAM (common.h X_MS_FLOOR)
+    if (h2) Ln.run(RPR_K_OTHER, 0, 0, [&] {
+      return launch_ssq_floor(xs.ssq, (size_t)(spl * layers + 1) * xs.rows, 1.0f / ((float)dm * SSQ_FIX), Ln.c->status, false, Ln.s);
+    });
   }
   XOut embed_out() const { return h2 ? XOut{xs.x_h, xs.ps, xs.ssq, Ln.c->status} : XOut{}; }   // where the embedding kernel puts x
   const __half* x_planes() const { return h2 ? xs.x_h : nullptr; }                             // for the kernels that read x themselves
@@ -305,6 +316,7 @@ void enqueue_encoder(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int Q, int Lq
     return launch_rmsnorm(p.x, d.enc_final_ln, P<float>(w.enc_out), T, dm, p.xs.eps, s, 1.0f,
                           p.h2 ? P<__half>(w.enc_out_h) : nullptr, p.xs.ps, live, c->status, p.x_planes(), p.xs.ps);
   });
+  p.check_ssq();
   c->enc_rows_accounted = Ta;
   Ln.account_live(nullptr, 0);
 }
@@ -372,7 +384,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
     Bt = (t == 0 && shared0) ? 1 : B; Rt = Q * Bt;
     const int Ma = (Bt == B) ? Racc : Rt;
     p.rows(Rt, Ma);
-    p.zero_ssq();
+    p.zero_ssq(t > t0);
     Ln.run(RPR_K_OTHER, 0, 2.0 * Ma * dm * 4, [&] {
       return launch_dec_embed(d.start_embed, d.in_embeds, cur.tokens, L, p.x, Rt, dm, V, t, s, p.embed_out(), sv.nrows_dev);
     });
@@ -460,6 +472,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
       Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_finalize(fa, s); });
     }
   }
+  if (t1 > t0) p.check_ssq();    // the last step's totals (the earlier steps': zero_ssq)
   Ln.account_live(nullptr, 0);   // the live counter of this stage scales THIS stage's records only (fork, tail, finalize follow)
 }
 
@@ -585,6 +598,7 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
     p.attn_out(i, 1);
     p.ff_block(i, 2);
   }
+  p.check_ssq();
   if (plan.log_softmax()) {
     // the score of a position is the log-probability of its token: final RMSNorm of every row, the V logits of the rows
     // of one position per launch of the exact-fp32 GEMM (rows of a position are Lt apart; its codebook is out_embeds[pos]),
@@ -747,6 +761,7 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
     p.attn_out(i, 1);
     p.ff_block(i, 2);
   }
+  p.check_ssq();
   // decoder_last_hidden_state (final RMSNorm, scaleup factor) dotted with the gold codes' OUTPUT codebook rows — or, for
   // rpr_embed, written out as it is
   Ln.run(RPR_K_OTHER, 2.0 * R * dm, 4.0 * 2 * R * dm, [&] {

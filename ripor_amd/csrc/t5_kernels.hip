@@ -807,6 +807,22 @@ hipError_t launch_zero_u64(unsigned long long* p, size_t n, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the floor of the split-precision stream (common.h X_MS_FLOOR) on the row totals of a pass, optionally clearing them
+__global__ __launch_bounds__(256) void ssq_floor_kernel(unsigned long long* __restrict__ p, size_t n, float inv_d_fix,
+                                                        unsigned int* __restrict__ status, int zero) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float ms = (float)p[i] * inv_d_fix;
+  if (ms > 0.f && ms < X_MS_FLOOR) status[STATUS_WORD_SMALL] = 1u;   // benign race: every writer stores 1
+  if (zero) p[i] = 0ull;
+}
+
+hipError_t launch_ssq_floor(unsigned long long* ssq, size_t n, float inv_d_fix, unsigned int* status, bool zero, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ssq_floor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ssq, n, inv_d_fix, status, zero ? 1 : 0);
+  return hipGetLastError();
+}
+
 __global__ void mask_lengths_kernel(const int32_t* __restrict__ mask, int32_t* __restrict__ lens, int Q, int Lq,
                                     unsigned int* status) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;

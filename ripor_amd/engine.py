@@ -149,7 +149,8 @@ class Context:
     def status(self, clear: bool = True) -> int:
         """Synchronises the current stream and returns the sticky status flags of the work enqueued so far
         (``_lib.STATUS_SATURATED``: an activation left the f16 plane range in f16x2 mode and was clamped — the results
-        since the last clear must be recomputed in 'f32' precision; ``_lib.STATUS_EMPTY_QUERY``)."""
+        since the last clear must be recomputed in 'f32' precision, and so after ``_lib.STATUS_SMALL_STREAM``: a row of the
+        residual stream under the RMS floor of the f16 planes and the fixed-point row sums; ``_lib.STATUS_EMPTY_QUERY``)."""
         out = C.c_uint32(0)
         check(self.lib.rpr_get_status(self.handle, _stream_ptr(self.device), C.byref(out), 1 if clear else 0), "rpr_get_status")
         flags = int(out.value) | getattr(self, "_kept_status", 0)
@@ -239,7 +240,7 @@ class StatusTicket:
         self._event.synchronize()
         w = self._words
         return ((_lib.STATUS_SATURATED if int(w[0]) else 0) | (_lib.STATUS_EMPTY_QUERY if int(w[1]) else 0) |
-                (_lib.STATUS_TAIL_LEFTOVER if int(w[2]) else 0))
+                (_lib.STATUS_TAIL_LEFTOVER if int(w[2]) else 0) | (_lib.STATUS_SMALL_STREAM if int(w[3]) else 0))
 
 
 def rel_bucket(rel: int, bidirectional: bool, num_buckets: int = 32, max_distance: int = 128) -> int:
@@ -671,7 +672,8 @@ class GuardedSearch:
     ``result()`` waits for the status words copied right behind the search and, if a guard fired, repeats the batch
     synchronously with the safe settings before returning: ``STATUS_TAIL_LEFTOVER`` (optimistic forced-tail mode: a
     query was still unforced at the last fork) -> exact forced-tail mode; ``STATUS_SATURATED`` (an activation left the
-    f16 plane range of the split-precision GEMMs) -> exact fp32 MFMA. ``STATUS_EMPTY_QUERY`` raises ``ValueError``.
+    f16 plane range of the split-precision GEMMs) or ``STATUS_SMALL_STREAM`` (a residual row under the RMS floor of that
+    path) -> exact fp32 MFMA. ``STATUS_EMPTY_QUERY`` raises ``ValueError``.
     ``repeated`` tells whether the returned result is a second run (its tensors are then new ones).
 
     ``margin_guard`` (a threshold eps, None = off): the search also computes the per-query pruning margins, and queries
@@ -744,13 +746,14 @@ class GuardedSearch:
         st = self._ticket.flags()
         if st & _lib.STATUS_EMPTY_QUERY:
             raise ValueError("a query has an all-zero attention_mask (no token to attend to)")
-        if st & (_lib.STATUS_SATURATED | _lib.STATUS_TAIL_LEFTOVER):
+        if st & (_lib.STATUS_NEEDS_F32 | _lib.STATUS_TAIL_LEFTOVER):
             model, trie, ids, mask, B, L, log_softmax = self._args
             ctx = model.ctx
             saved_mode, saved_prec = ctx.forced_tail(), ctx.get_precision()
-            if (st & _lib.STATUS_SATURATED) and saved_prec != "f32":
+            if (st & _lib.STATUS_NEEDS_F32) and saved_prec != "f32":
                 import warnings
-                warnings.warn("activation outside the f16 plane range of the split-precision GEMMs: repeating this batch "
+                warnings.warn(("activation outside the f16 plane range" if st & _lib.STATUS_SATURATED else
+                               "residual stream under the RMS floor") + " of the split-precision GEMMs: repeating this batch "
                               "with exact fp32 MFMA (RPR_PRECISION=f32 avoids the retry)")
                 ctx.set_precision("f32")
                 self._ran_f32 = True

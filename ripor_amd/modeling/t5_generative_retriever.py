@@ -309,13 +309,15 @@ class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
         args = (em, pos_q["input_ids"], pos_q["attention_mask"], codes, tp, tn, [k for k, _ in self._PREFIXES[L]])
         losses, self.last_position_scores = E.lngknp_forward(*args)
         # same guard as the search path (tasks/generation.py): this forward runs on the static-scale f16 planes; an
-        # activation outside their range is clamped and flagged, and the pass is then repeated on the exact-fp32 GEMMs
+        # activation outside their range is clamped and flagged (a residual row under their RMS floor is flagged too), and the
+        # pass is then repeated on the exact-fp32 GEMMs
         st = ctx.status(clear=True)
         if st & E._lib.STATUS_EMPTY_QUERY:
             raise ValueError("a query has an all-zero attention_mask (no token to attend to)")
-        if (st & E._lib.STATUS_SATURATED) and ctx.get_precision() != "f32":
+        if (st & E._lib.STATUS_NEEDS_F32) and ctx.get_precision() != "f32":
             import warnings
-            warnings.warn("activation outside the f16 plane range of the split-precision GEMMs: repeating this forward "
+            warnings.warn(("activation outside the f16 plane range" if st & E._lib.STATUS_SATURATED else
+                           "residual stream under the RMS floor") + " of the split-precision GEMMs: repeating this forward "
                           "with exact fp32 MFMA (RPR_PRECISION=f32 avoids the retry)")
             saved = ctx.get_precision()   # "f16x2" or "bf16" (a training ctx): whatever it was comes back
             ctx.set_precision("f32")

@@ -78,12 +78,12 @@ def _per_step_record(em, trie, input_ids, attention_mask, B, L, K, log_softmax):
     ctx = em.ctx
     saved = ctx.get_precision()
     # the sticky words of the shared ctx may hold flags of a search nobody has checked yet (deferred guards): read and clear
-    # them before the tapped run (a stale SATURATED bit would trigger a needless fp32 rerun), hand them back afterwards
+    # them before the tapped run (a stale SATURATED or SMALL_STREAM bit would trigger a needless fp32 rerun), hand them back afterwards
     before = ctx.status(clear=True)
     try:
         res = E.search(em, trie, input_ids, attention_mask, B, L, apply_log_softmax_for_scores=log_softmax, taps=True)
         torch.cuda.synchronize(ctx.device)
-        if ctx.status(clear=True) & E._lib.STATUS_SATURATED and saved != "f32":
+        if ctx.status(clear=True) & E._lib.STATUS_NEEDS_F32 and saved != "f32":
             ctx.set_precision("f32")
             try:
                 res = E.search(em, trie, input_ids, attention_mask, B, L, apply_log_softmax_for_scores=log_softmax, taps=True)

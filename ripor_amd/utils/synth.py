@@ -182,7 +182,8 @@ def mini_dims(L: int = 8, V: int = 256, enc_layers: int = 2, d_ff: int = 256,
                      decoder_vocab_sizes=[V] * L, **kw)
 
 
-def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35, outliers: float = 0.0) -> Dict[str, np.ndarray]:
+def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35, outliers: float = 0.0,
+                    stream_scale: float = 1.0) -> Dict[str, np.ndarray]:
     """Seeded weights under the reference's state-dict key names (float32 numpy arrays).
 
     Scales follow HF's T5 init factors so activations stay O(1); layer-norm weights are
@@ -197,6 +198,12 @@ def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35
     (3) four hidden units per feed-forward block with 150 x larger input weights (the most the f16 weight planes carry) against
     tiny output weights. The residual stream then carries |x| of 0.4-0.6 x ``outliers`` from the embedding to the last block.
     The model is still an ordinary T5 state dict: the CPU oracle and the exact-fp32 path run it unchanged.
+
+    ``stream_scale`` (a power of two, so the product is exact): every tensor that writes into the residual stream — the three
+    embedding tables and every attention ``.o`` and feed-forward ``.wo`` — is multiplied by it. The stream is then
+    ``stream_scale`` times the unscaled model's from the embedding to the last block, and the RMSNorms undo it: the network
+    computes the same function up to the effect of the norms' eps. 1.0 leaves every array as it was. For the small end of the
+    split-precision mode's working range (tests/test_gpu_magnitude.py).
     """
     d, inner, dff = dims.d_model, dims.inner, dims.d_ff
     sd: Dict[str, np.ndarray] = {}
@@ -246,6 +253,13 @@ def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35
     u("start_token_embed", (1, 1, d), 1.0)
     if outliers > 0.0:
         _add_outliers(sd, dims, float(outliers), seed)
+    if stream_scale != 1.0:
+        m, e = np.frexp(float(stream_scale))
+        assert m == 0.5, f"stream_scale must be a power of two, got {stream_scale}"
+        for name in sd:
+            if (name in ("shared.weight", "start_token_embed") or name.startswith("list_decoder_embeds.")
+                    or name.endswith(".o.weight") or name.endswith(".wo.weight")):
+                sd[name] = (sd[name] * np.float32(stream_scale)).astype(np.float32)
     return sd
 
 
