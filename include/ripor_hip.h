@@ -71,7 +71,7 @@ typedef struct {
   const float* const* enc_qkv;   /*                    -> [dev] [3*inner, d_model]                 */
   const float* const* enc_o;     /*                    -> [dev] [d_model, inner]                   */
   const float* const* enc_ln1;
-  const float* const* enc_wi;    /* [d_ff, d_model] */
+  const float* const* enc_wi;    /* [d_ff, d_model]; a gated model (rpr_load_model_ext): [2 * d_ff, d_model], wi_0 over wi_1 */
   const float* const* enc_wo;    /* [d_model, d_ff] */
   const float* const* dec_ln0;   /* [host][num_decoder_layers] */
   const float* const* dec_qkv;   /* SelfAttention [3*inner, d_model] */
@@ -151,6 +151,19 @@ int rpr_rel_bucket(int rel, int bidirectional, int num_buckets, int max_distance
 
 /* ---- model (replaces T5SeqAQEncoder.from_pretrained(...).base_model, t5_generative_retriever.py:772-784) ---- */
 int rpr_load_model(rpr_ctx* ctx, const rpr_model_desc* desc, rpr_model** out_model);
+/* The same with what the desc, whose size is fixed, does not say. size = the size of this struct in bytes as the caller knows it.
+ * ff_kind, the feed-forward block of every layer (HF config.feed_forward_proj):
+ *   RPR_FF_RELU        "relu": wo(relu(wi x)), T5 v1.0 (DenseReluDense.wi / wo);
+ *   RPR_FF_GATED_GELU  "gated-gelu": wo(gelu_new(wi_0 x) * wi_1 x), T5 v1.1 / Flan-T5 / mT5 (T5DenseGatedActDense),
+ *                      gelu_new(g) = 0.5 g (1 + tanh(0.7978845608028654 (g + 0.044715 g^3))). enc_wi[i] / dec_wi[i] then point
+ *                      to [2 * d_ff, d_model]: rows 0 .. d_ff-1 = wi_0 (the gate), the next d_ff rows = wi_1, concatenated by the
+ *                      host like q/k/v; in rpr_param_info's order the W_in tensor of an FF sub-block is that tall tensor.
+ * ext == NULL or ff_kind == RPR_FF_RELU: exactly rpr_load_model (which is this call with ext == NULL). Every entry point
+ * that takes the model runs both kinds; a ReLU model enqueues what it always did. Probe for the symbol, not for a version. */
+#define RPR_FF_RELU 0
+#define RPR_FF_GATED_GELU 1
+typedef struct { int32_t size; int32_t ff_kind; } rpr_model_ext;
+int rpr_load_model_ext(rpr_ctx* ctx, const rpr_model_desc* desc, const rpr_model_ext* ext, rpr_model** out_model);
 void rpr_free_model(rpr_model* model);
 
 /* ---- trie (replaces list_smtid_to_nextids + PrefixConstrainLogitProcessorFastSparse(list, V),
@@ -541,6 +554,19 @@ int rpr_op_rmsnorm(rpr_ctx* ctx, const float* x, const float* w, float* out, int
  * the device mask against its numpy restatement (tests/dropout_mask.py). */
 int rpr_op_dropout(rpr_ctx* ctx, const float* x, float* out, int64_t n_seq, int32_t n_pos, int32_t n_feat, float rate,
                    uint64_t seed, uint64_t step, int32_t site, void* stream);
+/* The gate of a gated-GELU feed-forward block (RPR_FF_GATED_GELU), the kernel the passes launch behind the W_in product.
+ * gu: [dev] fp32 [M, 2F], columns 0..F-1 = g (the wi_0 half), F..2F-1 = u (the wi_1 half); y = gelu_new(g) * u, [M, F].
+ *   out_f32 (nullable): y as fp32 [M, F] (what the exact-fp32 mode writes);
+ *   out_planes (nullable): the two f16 planes [2][M][F] of y / 16 (the split mode's FF operand; a |y| beyond 1.05e6 is clamped
+ *                 and raises RPR_STATUS_SATURATED like the ReLU epilogue's planes);
+ *   m_dev (nullable): [dev] int32 live row count: rows from *m_dev on are neither read nor written.
+ * F % 4 == 0, M >= 1. */
+int rpr_op_gated_gelu(rpr_ctx* ctx, const float* gu, int32_t M, int32_t F, const int32_t* m_dev, float* out_f32, void* out_planes,
+                      void* stream);
+/* Its backward (training walk): dgu [M, 2F] = (dmid * u * gelu_new'(g) | dmid * gelu_new(g)) from gu [M, 2F] and dmid [M, F],
+ * gelu_new'(g) = 0.5 (1 + t) + 0.5 g (1 - t^2) c (1 + 3 * 0.044715 g^2), t = tanh(c (g + 0.044715 g^3)), c = 0.7978845608028654.
+ * fp32 in every precision mode, one thread per element group, no atomics: two calls give the same bits. */
+int rpr_op_gated_gelu_bwd(rpr_ctx* ctx, const float* gu, const float* dmid, int32_t M, int32_t F, float* dgu, void* stream);
 /* Encoder forward only (reference generation.py:132-137): out [Q, Lq, d_model]. */
 int rpr_encode(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
                int32_t Q, int32_t Lq, float* out, void* stream);

@@ -27,6 +27,8 @@ ABI_VERSION = 4
 PREC_F32, PREC_F16X2, PREC_BF16 = 0, 1, 2
 FLAG_LOG_SOFTMAX = 1
 FLAG_NO_GRAPH = 2
+# rpr_model_ext.ff_kind: wo(relu(wi x)) / wo(gelu_new(wi_0 x) * wi_1 x)
+FF_RELU, FF_GATED_GELU = 0, 1
 
 
 class RiporHipError(RuntimeError):
@@ -53,6 +55,11 @@ class ModelDesc(C.Structure):
         ("dec_ln1", C.POINTER(C.c_void_p)), ("dec_xq", C.POINTER(C.c_void_p)), ("dec_xo", C.POINTER(C.c_void_p)),
         ("dec_ln2", C.POINTER(C.c_void_p)), ("dec_wi", C.POINTER(C.c_void_p)), ("dec_wo", C.POINTER(C.c_void_p)),
     ]
+
+
+class ModelExt(C.Structure):
+    """``rpr_model_ext``: what rpr_load_model_ext takes beside the (size-pinned) ModelDesc."""
+    _fields_ = [("size", C.c_int32), ("ff_kind", C.c_int32)]
 
 
 class DebugTaps(C.Structure):
@@ -84,7 +91,10 @@ SIGNATURES = {
     "rpr_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "rpr_get_precision": (C.c_int, [C.c_void_p]),
     "rpr_load_model": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]),
+    "rpr_load_model_ext": (C.c_int, [C.c_void_p, C.POINTER(ModelDesc), C.POINTER(ModelExt), C.POINTER(C.c_void_p)]),
     "rpr_free_model": (None, [C.c_void_p]),
+    "rpr_op_gated_gelu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rpr_op_gated_gelu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rpr_build_trie": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "rpr_free_trie": (None, [C.c_void_p]),
     "rpr_trie_num_rows": (C.c_int64, [C.c_void_p]),

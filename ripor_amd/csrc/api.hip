@@ -215,8 +215,13 @@ int rpr_set_precision(rpr_ctx* c, int precision) {
 }
 int rpr_get_precision(const rpr_ctx* c) { return c ? c->precision : -1; }
 
-int rpr_load_model(rpr_ctx* c, const rpr_model_desc* d, rpr_model** out) {
+int rpr_load_model(rpr_ctx* c, const rpr_model_desc* d, rpr_model** out) { return rpr_load_model_ext(c, d, nullptr, out); }
+
+int rpr_load_model_ext(rpr_ctx* c, const rpr_model_desc* d, const rpr_model_ext* ext, rpr_model** out) {
   RPR_REQUIRE(c && d && out, "NULL argument");
+  RPR_REQUIRE(!ext || ext->size >= (int32_t)sizeof(rpr_model_ext), "rpr_model_ext.size is smaller than the struct");
+  const int ff_kind = ext ? ext->ff_kind : RPR_FF_RELU;
+  RPR_REQUIRE(ff_kind == RPR_FF_RELU || ff_kind == RPR_FF_GATED_GELU, "ff_kind must be 0 (ReLU) or 1 (gated GELU)");
   RPR_REQUIRE(d->d_kv == DKV || d->d_kv == 128, "d_kv must be 64 (t5-base / t5-large) or 128 (t5-3b)");
   RPR_REQUIRE(d->d_model % 32 == 0 && d->d_ff % 32 == 0, "d_model and d_ff must be multiples of 32");
   RPR_REQUIRE(d->V >= 2 && d->V <= 65536, "decoder vocab size out of range (2..65536)");
@@ -226,7 +231,7 @@ int rpr_load_model(rpr_ctx* c, const rpr_model_desc* d, rpr_model** out) {
   RPR_REQUIRE(d->shared && d->enc_rel_bias && d->dec_rel_bias && d->enc_final_ln && d->dec_final_ln &&
                   d->start_embed && d->in_embeds && d->out_embeds && d->dec_xkv, "NULL weight pointer");
   RPR_HIP(hipSetDevice(c->device));
-  auto m = std::make_unique<rpr_model>(c, *d);
+  auto m = std::make_unique<rpr_model>(c, *d, ff_kind);
   RPR_REQUIRE(m->params.fill(*d), "NULL per-layer weight pointer");
   // the desc's host arrays need not outlive this call
   for (int kind = K_ENC_LAYER; kind < K_END; ++kind) m->d.*layer_field(kind) = nullptr;
@@ -1066,6 +1071,24 @@ int rpr_op_rmsnorm(rpr_ctx* c, const float* x, const float* w, float* out, int32
   RPR_REQUIRE(rows >= 1 && d >= 4 && d % 4 == 0, "bad shape");
   RPR_HIP(hipSetDevice(c->device));
   RPR_HIP(launch_rmsnorm(x, w, out, rows, d, eps, reinterpret_cast<hipStream_t>(stream)));
+  return RPR_OK;
+}
+
+int rpr_op_gated_gelu(rpr_ctx* c, const float* gu, int32_t M, int32_t F, const int32_t* m_dev, float* out_f32, void* out_planes,
+                      void* stream) {
+  RPR_REQUIRE(c && gu && (out_f32 || out_planes), "NULL argument");
+  RPR_REQUIRE(M >= 1 && F >= 4 && F % 4 == 0, "bad shape");
+  RPR_HIP(hipSetDevice(c->device));
+  RPR_HIP(launch_gated_gelu(gu, M, F, m_dev, out_f32, reinterpret_cast<__half*>(out_planes), (size_t)M * F, c->status,
+                            reinterpret_cast<hipStream_t>(stream)));
+  return RPR_OK;
+}
+
+int rpr_op_gated_gelu_bwd(rpr_ctx* c, const float* gu, const float* dmid, int32_t M, int32_t F, float* dgu, void* stream) {
+  RPR_REQUIRE(c && gu && dmid && dgu, "NULL argument");
+  RPR_REQUIRE(M >= 1 && F >= 4 && F % 4 == 0, "bad shape");
+  RPR_HIP(hipSetDevice(c->device));
+  RPR_HIP(launch_gated_gelu_bwd(gu, dmid, M, F, dgu, reinterpret_cast<hipStream_t>(stream)));
   return RPR_OK;
 }
 

@@ -742,6 +742,12 @@ struct WSeg { const float* src; int R, C; unsigned long long off; };
 hipError_t launch_weights_bf16(const WSeg* segs, const int* pref, int nseg, int ntiles, void* plain, void* tr, hipStream_t s);
 hipError_t launch_transpose_pad(const float* in, float* out, int R, int C, int ldi, int Rpad, hipStream_t s);
 hipError_t launch_relu_bwd(float* dy, const float* act, size_t n, hipStream_t s);
+// gated-GELU feed-forward (gated_ff.hip): gu [M, 2F] = (g | u) -> gelu_new(g) * u as fp32 [M, F] (out_f) and / or f16 planes at
+// FF_PLANE_SCALE (out_h, plane stride o_ps; clamps raise *sat); rows from *m_dev on (nullable) are left alone. And its
+// backward: dgu [M, 2F] = (dmid u gelu_new'(g) | dmid gelu_new(g)). F % 4 == 0.
+hipError_t launch_gated_gelu(const float* gu, int M, int F, const int* m_dev, float* out_f, __half* out_h, size_t o_ps, unsigned int* sat,
+                             hipStream_t s);
+hipError_t launch_gated_gelu_bwd(const float* gu, const float* dmid, int M, int F, float* dgu, hipStream_t s);
 // bf16 mode: RMSNorm written as the plain bf16 rows [rows][d] and their transposed copy [d][ldt] (columns rows .. Rpad zero)
 hipError_t launch_rmsnorm_bf16_T(const float* x, const float* w, int rows, int d, float eps, float post, void* out_plain, void* out_t,
                                  int Rpad, int ldt, hipStream_t s);

@@ -96,7 +96,12 @@ struct rpr_model {
   // The forced-tail fork uses it to prove that no masked (-1e9) candidate can overtake a valid one (passes.hip: enqueue_fork).
   float logit_bound = INFINITY;
   int inner() const { return d.num_heads * d.d_kv; }
-  rpr_model(rpr_ctx* c, const rpr_model_desc& desc) : ctx(c), d(desc), params(desc), planes(params.slots.size(), nullptr) {}
+  // feed-forward kind (rpr_model_ext::ff_kind): RPR_FF_GATED_GELU = wo(gelu_new(wi_0 x) * wi_1 x), W_in of the FF sub-blocks
+  // holds wi_0 over wi_1 ([2 d_ff][d_model], the table in params says so) and the passes run the gate kernel behind it
+  const int ff_kind;
+  bool gated() const { return ff_kind == RPR_FF_GATED_GELU; }
+  rpr_model(rpr_ctx* c, const rpr_model_desc& desc, int ff_kind_ = RPR_FF_RELU)
+      : ctx(c), d(desc), params(desc, ff_kind_ == RPR_FF_GATED_GELU), planes(params.slots.size(), nullptr), ff_kind(ff_kind_) {}
   ~rpr_model() {   // device memory goes with the object, also on the error paths of rpr_load_model
     if (enc_bucket) (void)hipFree(enc_bucket);
     if (dec_bucket) (void)hipFree(dec_bucket);
@@ -195,6 +200,9 @@ struct Workspace {
   // f16 hi/lo planes of the GEMM inputs (split-precision mode): attention outputs, FF intermediates, the final
   // encoder states, and the UN-normalised residual streams (fused RMSNorm) with their row sums of squares
   DevBuf eattn_h, eff_h, enc_out_h, attn_h, ff_h, ex_h, x_h, ssq_e, ssq_d;
+  // gated feed-forward only (rpr_model::gated): the W_in product's fp32 result [rows, 2 d_ff] (gate | linear half) of the
+  // encoder, the decoder steps / teacher-forced forward and the tail pass; the gate kernel reads it into ff / ff_h
+  DevBuf egu, gu, t_gu;
   DevBuf tr_x, tr_misc;   // rpr_train_forward scratch (teacher-forced decoder)
   DevBuf part;            // split-K partial sums of the mid-size GEMM route (gemm_h2.hip): 9 M floats
   // forced-tail search: stages 1.. (stage 0 = the buffers above), one tail job per fork, and the activations of a tail

@@ -98,6 +98,8 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, const SearchPlan& plan) {
   E(w.attn_h, R * inner * hb); E(w.ff_h, R * dff * hb);
   E(w.ex_h, T * dm * hb); E(w.x_h, R * dm * hb);
   E(w.ssq_e, (2 * ne + 1) * T * 8); E(w.ssq_d, (3 * nd + 1) * R * 8);
+  // gated feed-forward: the fp32 result of the W_in product (gate | linear half), read by the gate kernel
+  if (m->gated()) { E(w.egu, T * 2 * dff * f); E(w.gu, R * 2 * dff * f); }
   E(w.part, (size_t)9 << 20 << 2);   // split-K partials of the mid-size GEMM route: < 256 tiles of 128 x 64, up to 4 splits
   // forced-tail search: one compacted stage and one tail job per fork, tail activations for the longest tail
   for (int k = 0; k < nf; ++k) {
@@ -126,6 +128,7 @@ int alloc_workspace(rpr_ctx* c, const rpr_model* m, const SearchPlan& plan) {
     } else {
       E(w.t_x, Rt * dm * f); E(w.t_h, Rt * dm * f); E(w.t_attn, Rt * inner * f); E(w.t_ff, Rt * dff * f);
     }
+    if (m->gated()) E(w.t_gu, Rt * 2 * dff * f);
     if (plan.log_softmax()) { E(w.t_h, Rt * dm * f); E(w.t_logits, Rt * (size_t)d.V * f); }   // normalised rows, V logits per row
   }
   return e;
@@ -156,7 +159,7 @@ struct XStream {
 };
 
 // Residual stream and layer intermediates of one pass (fp32 buffers of the exact mode, planes and row sums of the split mode)
-struct PassBufs { const DevBuf &x, &h, &attn, &ff, &x_h, &attn_h, &ff_h, &ssq; };
+struct PassBufs { const DevBuf &x, &h, &attn, &ff, &x_h, &attn_h, &ff_h, &ssq, &gu; };   // gu: gated models only
 
 // The transformer layer every pass walks, in both precision modes: how a normalised input reaches a projection, where a
 // residual projection lands, the FF block. A layer has `spl` norm sites (encoder 2: self-attention, FF; decoder 3: self-,
@@ -172,7 +175,7 @@ struct Pass {
                                                  //   the rows their profile records account
   const int norm_acc;                            // rows the RMSNorm records account: as constructed (the decoder steps state
                                                  //   the whole stage's on the shared step 0 too)
-  float *const x, *const h, *const attn, *const ff; __half *const attn_h, *const ff_h;
+  float *const x, *const h, *const attn, *const ff, *const gu; __half *const attn_h, *const ff_h;
   const size_t ps_i, ps_f;                       // plane strides of attn_h / ff_h (the x planes': xs.ps)
   const XStream xs;
   const float post;                              // scaleup_output_hidden: factor on the final norm of the decoder
@@ -180,7 +183,7 @@ struct Pass {
   Pass(Launcher& Ln_, const rpr_model* m_, const PassBufs& b, bool dec_, int layers_, int rows_cap, const int* m_dev_, int m_acc_)
       : Ln(Ln_), m(m_), dec(dec_), h2(Ln_.c->precision == RPR_PREC_F16X2), spl(dec_ ? 3 : 2), layers(layers_), dm(m->d.d_model),
         inner(m->inner()), dff(m->d.d_ff), M(rows_cap), m_dev(m_dev_), m_acc(m_acc_), norm_acc(m_acc_), x(P<float>(b.x)), h(P<float>(b.h)),
-        attn(P<float>(b.attn)), ff(P<float>(b.ff)), attn_h(P<__half>(b.attn_h)), ff_h(P<__half>(b.ff_h)),
+        attn(P<float>(b.attn)), ff(P<float>(b.ff)), gu(P<float>(b.gu)), attn_h(P<__half>(b.attn_h)), ff_h(P<__half>(b.ff_h)),
         ps_i((size_t)rows_cap * inner), ps_f((size_t)rows_cap * dff),
         xs{P<__half>(b.x_h), (size_t)rows_cap * dm, P<unsigned long long>(b.ssq), (size_t)rows_cap, dm, m->d.layer_norm_eps},
         post(m->d.scaleup_output_hidden ? (float)pow((double)dm, -0.5) : 1.0f) {}
@@ -229,6 +232,14 @@ struct Pass {
     project(LinIn{attn, attn_h, ps_i, inner}, m->weight(dec, layer, k, P_WOUT), residual(layer, k));
   }
   void ff_block(int layer, int k) {
+    if (m->gated()) {   // W_in = wi_0 over wi_1 into gu (fp32, both modes), the gate kernel makes the W_out operand from it
+      project_in(layer, k, out_f32(gu, 2 * dff, 2 * dff));
+      Ln.run(RPR_K_OTHER, 8.0 * m_acc * dff, 12.0 * m_acc * dff, [&] {
+        return launch_gated_gelu(gu, M, dff, m_dev, h2 ? nullptr : ff, h2 ? ff_h : nullptr, ps_f, Ln.c->status, Ln.s);
+      });
+      project(LinIn{ff, ff_h, ps_f, dff, FF_PLANE_SCALE}, m->weight(dec, layer, k, P_WOUT), residual(layer, k));
+      return;
+    }
     LinOut o = out_f32(ff, dff, dff, nullptr, 1);
     if (h2) { o.h = ff_h; o.ps = ps_f; o.ldh = dff; o.plane_scale = FF_PLANE_SCALE; }
     project_in(layer, k, o);
@@ -265,7 +276,7 @@ int ensure_l0_table(rpr_ctx* c, rpr_model* m, hipStream_t s) {
   c->precision = RPR_PREC_F16X2; c->profiling = false;
   const DevBuf none{}, xb{x_h.p, rows * dm * 2 * sizeof(__half)}, sb{ssq.p, rows * 8};
   Launcher Ln{c, s};
-  Pass p(Ln, m, {none, none, none, none, xb, none, none, sb}, true, 1, (int)rows, nullptr, (int)rows);
+  Pass p(Ln, m, {none, none, none, none, xb, none, none, sb, none}, true, 1, (int)rows, nullptr, (int)rows);
   Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_l0_table_embed(d.start_embed, d.in_embeds, (int)rows, (int)dm, s, p.embed_out()); });
   LinW w = m->weight(true, 0, 0, P_WIN);
   w.no_scratch = true; w.row_split_ok = true; w.force_pp = true;
@@ -295,7 +306,7 @@ void enqueue_encoder(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int Q, int Lq
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_pack_rows(P<int32_t>(w.last), P<int32_t>(w.offs), P<int32_t>(w.row_src), Q, Lq, s); });
   }
   Ln.account_live(live, T);   // profile pass: flops / bytes below are stated for T rows and scaled by the live count at flush
-  Pass p(Ln, m, {w.ex, w.eh, w.eattn, w.eff, w.ex_h, w.eattn_h, w.eff_h, w.ssq_e}, false, d.num_layers, T, live, Ta);
+  Pass p(Ln, m, {w.ex, w.eh, w.eattn, w.eff, w.ex_h, w.eattn_h, w.eff_h, w.ssq_e, w.egu}, false, d.num_layers, T, live, Ta);
   p.zero_ssq();
   Ln.run(RPR_K_OTHER, 0, 2.0 * Ta * dm * 4, [&] {
     return launch_embed_rows(d.shared, P<int32_t>(w.ids), p.x, T, dm, d.vocab_size, s,
@@ -375,7 +386,7 @@ void enqueue_steps(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie*
   const size_t layer_stride = sv.kv_layer(B, inner), kv_q = sv.kv_q(B, inner), kv_h = sv.kv_h(B), kv_pos = (size_t)B * sv.dkv, kv_slot = sv.dkv;
   int Rt = R, Bt = B;   // rows / beams per query of the current step's decoder pass
   const int Racc = live_count(Ln, sv.nrows_dev, R);   // rows the profile accounts for
-  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, true, nd, R, sv.nrows_dev, Racc);
+  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d, w.gu}, true, nd, R, sv.nrows_dev, Racc);
   if (Vp != V && !p.h2)   // exact-fp32 logits GEMM writes the V real columns of a row only: the padding must read as finite
     // (a kernel node: memset nodes captured into the search graph did not re-execute reliably on replay, see launch_zero_u64)
     Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_zero_u64(reinterpret_cast<unsigned long long*>(logits), (size_t)R * Vp / 2, s); });
@@ -551,7 +562,7 @@ void enqueue_tail(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const rpr_trie* 
   const int* nrows_dev = nf_dev + 2;
   const int Ra = live_count(Ln, nrows_dev, R);
   float *qkv = P<float>(w.t_qkv), *qb = P<float>(w.t_q);
-  Pass p(Ln, m, {w.t_x, w.t_h, w.t_attn, w.t_ff, w.t_x_h, w.t_attn_h, w.t_ff_h, w.t_ssq}, true, nd, R, nrows_dev, Ra);
+  Pass p(Ln, m, {w.t_x, w.t_h, w.t_attn, w.t_ff, w.t_x_h, w.t_attn_h, w.t_ff_h, w.t_ssq, w.t_gu}, true, nd, R, nrows_dev, Ra);
   p.zero_ssq();
   // MFMA shape of the pass's 256x256 GEMM launches (SearchPlan::mfma16). A tail pass scores sequences that are already chosen:
   // its rounding reaches the returned scores, never which sequences survive the steps — those launches (encoder, steps, the
@@ -737,7 +748,7 @@ void enqueue_train_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, int bz,
   Ln.no_row_split = 0;
 
   float *qkv = P<float>(w.tr_x), *qb = P<float>(w.q);
-  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d}, true, nd, R, nullptr, R);   // every row is live
+  Pass p(Ln, m, {w.x, w.h, w.attn, w.ff, w.x_h, w.attn_h, w.ff_h, w.ssq_d, w.gu}, true, nd, R, nullptr, R);   // every row is live
   p.zero_ssq();
   Ln.run(RPR_K_OTHER, 0, 2.0 * R * dm * 4, [&] {
     return launch_train_dec_embed(d.start_embed, d.in_embeds, codes, p.x, S, L, dm, V, s, p.embed_out());

@@ -158,6 +158,7 @@ struct TrainWs {
   // seq2seq head: the decoder's last hidden state (after the final norm), dlogits of every row, the row losses
   DevBuf hF, dlog, row_loss;
   // scratch
+  DevBuf dmid_ff;   // gated feed-forward only: the W_out product's input gradient [rows, d_ff] (the backward gate kernel's dmid)
   DevBuf h, dxa, dxb, dbig, dattn, dxkv, denc, tA, wT, w_part, bias_part, fix, gn_part, gn_out, amax, part, part2;
   WGradSide side;
   std::vector<hipEvent_t> bucket_ev;   // gradient buckets handed to the caller's communication stream (one event each)
@@ -381,9 +382,9 @@ int refresh_weight_cache(Launcher& Ln, rpr_ctx* c, rpr_model* m) {
           add(p[P_WIN], st.sub[j].n_in, st.dm); add(p[P_WOUT], st.dm, st.sub[j].k_out);
         }
     };
-    add_stack(StackLayout(false, 0, d.num_layers, d.d_model, m->inner(), d.d_ff));
+    add_stack(m->params.stack[0]);
     add(m->params.at(K_XKV), d.num_decoder_layers * 2 * m->inner(), d.d_model);
-    add_stack(StackLayout(true, 0, d.num_decoder_layers, d.d_model, m->inner(), d.d_ff));
+    add_stack(m->params.stack[1]);
     int e = tensure(c, w.wseg, segs.size() * sizeof(WSeg));
     if (!e) e = tensure(c, w.wpref, pref.size() * sizeof(int));
     if (!e) e = tensure(c, w.wc, m->params.total * sizeof(__half));
@@ -549,7 +550,7 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
   TrainWs& w = *c->tws;
   const size_t f = sizeof(float), R = D.R, T = D.T, dm = D.dm, inner = D.inner, dff = D.dff;
   const size_t rows = std::max(R, T), rp = ((int)rows + 63) & ~63;   // rows padded to the K-tile of the bf16 kernel (64) / the split kernel (32)
-  const size_t wide = std::max<size_t>(std::max<size_t>(dff, 3 * inner), (size_t)D.xld);
+  const size_t ffin = D.ff_in(), wide = std::max<size_t>(std::max<size_t>(ffin, 3 * inner), (size_t)D.xld);
   int e = 0;
   auto E = [&](DevBuf& b, size_t bytes) { if (!e) e = tensure(c, b, bytes); };
   const TrainLayout Y(D);
@@ -561,13 +562,14 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
   if (D.docs == 1) { E(w.hF, R * dm * f); E(w.dlog, R * (size_t)D.V * f); E(w.row_loss, R * f); }   // the seq2seq head
   if (c->train_drop.rate > 0.f) { E(w.hF, R * dm * f); E(w.drop_dy, rows * dm * f); }   // dropout: the ranking step keeps hF too
   E(w.h, rows * dm * f); E(w.dxa, rows * dm * f); E(w.dxb, rows * dm * f); E(w.dbig, rows * wide * f);
+  if (D.gated) E(w.dmid_ff, rows * dff * f);
   E(w.dattn, rows * inner * f); E(w.dxkv, T * (size_t)D.xld * f); E(w.denc, T * dm * f);
   E(w.tA, wide * rp * f);
   // grouped weight gradients (bf16 mode): dY^T of one layer's products, [N_out][pad64(rows)] bf16 each, 256-byte aligned
   const bool bf16 = c->precision == RPR_PREC_BF16;
   if (!e) e = w.side.create(c, wide * rp * f, bf16 ? Y.dyT_max() * sizeof(__half) + 8 * 256 : 0);
   if (bf16) { E(w.xT, Y.xt_total * sizeof(__half)); E(w.bfb, rp * dff * sizeof(__half)); }
-  E(w.wT, std::max<size_t>(std::max<size_t>(dff * dm, 3 * inner * dm), (size_t)D.xld * dm) * f);
+  E(w.wT, std::max<size_t>(std::max<size_t>(ffin * dm, 3 * inner * dm), (size_t)D.xld * dm) * f);
   E(w.w_part, ColsumSites::MAXS * ((rows + 3) / 4) * dm * f);   // the partials of up to four norm sites (Bwd::norm_bwd)
   E(w.bias_part, std::max<size_t>((size_t)D.S, (size_t)D.bz) * D.H * D.buckets * f);
   E(w.fix, std::max<size_t>((size_t)m->d.vocab_size, (size_t)m->d.L * D.V) * dm * 8);
@@ -614,7 +616,7 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
     const SubBlock& b = k.lay.sub[j];
     const ParamSlot* p = k.params(i, j);
     const int rows = k.lay.rows;
-    const bool ff = b.kind == SUB_FF;
+    const bool ff = b.kind == SUB_FF && !D.gated;   // the ReLU FF: activation and operand hand-over in the inner product's epilogue
     float *x = k.x(i, j), *in = k.in(i, j), *mid = k.mid(i, j);
     const void* ready = norm_gemm(x, p[P_LN].ptr, p[P_WIN].ptr, in, rows, b.n_in, ff, k.xt_in(i, j), ff && !drop.on ? k.xt_out(i, j) : nullptr);
     const int site_mid = drop_site_mid(k.lay.dec, i, j);
@@ -648,7 +650,14 @@ void forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, c
         Ln.run(RPR_K_DEC_CROSS_ATTN, 0, 0, [&] { return launch_tail_cross_attn(ca, s); });
         break;
       }
-      case SUB_FF:   // the ReLU ran in the inner product's epilogue
+      case SUB_FF:
+        if (D.gated) {   // in = (g | u) stays as the product left it; mid = gelu_new(g) * u, and the dropout masks that product
+          Ln.run(RPR_K_OTHER, 8.0 * rows * b.k_out, 12.0 * rows * b.k_out,
+                 [&] { return launch_gated_gelu(in, rows, b.k_out, nullptr, mid, nullptr, 0, nullptr, s); });
+          if (drop.on) drop.rows(Ln, k, mid, nullptr, mid, b.k_out, site_mid);
+          break;
+        }
+        // the ReLU ran in the inner product's epilogue
         if (drop.on) drop.rows(Ln, k, in, nullptr, in, b.n_in, site_mid);
         break;
     }
@@ -780,8 +789,9 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
     const ParamSlot* p = k.params(i, j);
     const int rows = k.lay.rows;
     float *x = k.x(i, j), *in = k.in(i, j);
-    const float* relu = b.kind == SUB_FF && bf16 ? in : nullptr;   // FF: in = relu(norm(x) Wi^T), the mask of its own gradient
-    float* dmid = b.kind == SUB_FF ? dbig : dattn;
+    const bool gated = b.kind == SUB_FF && D.gated;
+    const float* relu = b.kind == SUB_FF && bf16 && !gated ? in : nullptr;   // ReLU FF: in = relu(norm(x) Wi^T), the mask of its own gradient
+    float* dmid = gated ? P<float>(w.dmid_ff) : b.kind == SUB_FF ? dbig : dattn;
     // dropout: the W_out products see the masked dx, the residual path (norm_bwd below) the whole of it; the dropped-out `in` of
     // the FF block is positive exactly where its ReLU passed AND the element was kept, so it still gates its own gradient
     const int site_mid = drop_site_mid(k.lay.dec, i, j);
@@ -791,6 +801,11 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
     B.dxdw(dy, p[P_WOUT].ptr, k.mid(i, j), dmid, G + p[P_WOUT].offset, rows, dm, b.k_out, k.xt_out(i, j), nullptr, drop.on ? nullptr : relu);
     switch (b.kind) {
       case SUB_FF:
+        if (gated) {   // dmid (masked like the product it belongs to) -> dgu = (dg | du) in dbig, one ordinary dY for the W_in products
+          if (drop.on) drop.rows(Ln, k, dmid, nullptr, dmid, b.k_out, site_mid);
+          Ln.run(RPR_K_OTHER, 0, 20.0 * rows * b.k_out, [&] { return launch_gated_gelu_bwd(in, dmid, rows, b.k_out, dbig, s); });
+          break;
+        }
         if (drop.on) drop.rows(Ln, k, dbig, nullptr, dbig, b.n_in, site_mid);
         if (!bf16) Ln.run(RPR_K_OTHER, 0, 0, [&] { return launch_relu_bwd(dbig, in, (size_t)rows * b.n_in, s); });
         break;
@@ -863,7 +878,7 @@ int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int
   RPR_REQUIRE(L >= 1 && L <= m->d.L && L <= MAX_DEC_LEN, "smtid length exceeds the model's decoder length");
   RPR_HIP(hipSetDevice(c->device));
   const auto& d = m->d;
-  D = train_dims(d, bz, Lq, L, docs);
+  D = train_dims(d, bz, Lq, L, docs, m->gated());
   // 64-dim heads beyond the carve of a whole head go on in tiles (attn_route.h: plan_*_tiled; L <= 64 always fits the decoder's
   // causal self-attention, the docs L <= 128 decoder rows of a query the tiles); 128-dim heads stop at the carve
   const bool tiled_ok = d.d_kv == DKV && !plan_cross_attn_bwd_tiled(CrossAttnBwdIn{bz, docs * L, Lq, d.num_heads, d.d_kv}).invalid &&

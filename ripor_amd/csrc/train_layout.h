@@ -1,6 +1,7 @@
 // Layout of the training step (train_api.hip): what a T5 layer is, and every offset, stride and order that follows from it.
 // A layer is two residual sub-blocks in the encoder and three in the decoder, each y = x + mid(norm(x, ln) W_in^T) W_out^T
-// with mid = self-attention, cross-attention or ReLU. That is written ONCE here, as the table of a stack (StackLayout); the
+// with mid = self-attention, cross-attention or the feed-forward's activation (ReLU in place, or the gated GELU of T5 v1.1:
+// W_in stacks wi_0 over wi_1, n_in = 2 d_ff, and mid = gelu_new(gate half) * linear half is a slot of its own). That is written ONCE here, as the table of a stack (StackLayout); the
 // saved activations, the saved X^T slots, the dY^T room of a layer's weight-gradient group, the flat parameter order and a
 // layer's gradient bucket are derived from the table, so the encoder's and the decoder's answers are the same code. The
 // same order names a model's weights for the loader and the forward passes (api.hip, passes.hip): which field of the ABI's
@@ -26,13 +27,15 @@ inline int ldT(int rows) { return pad64(rows); }
 struct TrainDims {
   int bz, Lq, L, docs, S, R, T, dm, inner, dff, H, ne, nd, V, xld, buckets;   // docs: decoder sequences per query (S = bz docs)
   float eps, post;
+  bool gated;       // feed-forward kind: gated GELU (W_in of 2 d_ff rows) instead of ReLU
+  int ff_in() const { return gated ? 2 * dff : dff; }   // output width of the FF block's inner projection
 };
 // a batch of bz queries of Lq padded tokens, docs decoder sequences of L positions per query
-inline TrainDims train_dims(const rpr_model_desc& d, int bz, int Lq, int L, int docs) {
+inline TrainDims train_dims(const rpr_model_desc& d, int bz, int Lq, int L, int docs, bool gated = false) {
   TrainDims D{};
   D.bz = bz; D.Lq = Lq; D.L = L; D.docs = docs; D.S = bz * docs; D.R = D.S * L; D.T = bz * Lq; D.dm = d.d_model; D.inner = d.num_heads * d.d_kv;
   D.dff = d.d_ff; D.H = d.num_heads; D.ne = d.num_layers; D.nd = d.num_decoder_layers; D.V = d.V; D.xld = D.nd * 2 * D.inner;
-  D.buckets = d.rel_buckets;
+  D.buckets = d.rel_buckets; D.gated = gated;
   D.eps = d.layer_norm_eps; D.post = d.scaleup_output_hidden ? (float)pow((double)D.dm, -0.5) : 1.0f;
   return D;
 }
@@ -41,8 +44,10 @@ inline TrainDims train_dims(const rpr_model_desc& d, int bz, int Lq, int L, int 
 enum SubKind { SUB_SELF, SUB_CROSS, SUB_FF };
 // n_in: output width of the inner projection W_in [n_in][d_model]; k_out: reduction width of the outer one W_out [d_model][k_out]
 struct SubBlock { SubKind kind; int n_in, k_out; };
-inline SubBlock sub_block(SubKind kind, int inner, int dff) {
-  return kind == SUB_SELF ? SubBlock{kind, 3 * inner, inner} : kind == SUB_CROSS ? SubBlock{kind, inner, inner} : SubBlock{kind, dff, dff};
+// gated (SUB_FF only): W_in is wi_0 (the gate, through gelu_new) stacked over wi_1, [2 d_ff][d_model]
+inline SubBlock sub_block(SubKind kind, int inner, int dff, bool gated = false) {
+  return kind == SUB_SELF ? SubBlock{kind, 3 * inner, inner} : kind == SUB_CROSS ? SubBlock{kind, inner, inner}
+                                                                                  : SubBlock{kind, gated ? 2 * dff : dff, dff};
 }
 
 // Trainable tensors in the order of the flat gradient / optimizer-state buffers: the kinds in front of the layers, then per
@@ -52,8 +57,8 @@ enum ParamKind { K_SHARED, K_ENC_REL, K_DEC_REL, K_ENC_FLN, K_DEC_FLN, K_START, 
 enum ParamRole { P_LN, P_WIN, P_WOUT };
 
 // Where sub-block j keeps its tensors inside ONE layer of its stack. Saved activations (floats): the input stream x
-// [rows][d_model], the inner projection's output in [rows][n_in] and the middle op's output mid [rows][k_out] (FF has none:
-// its ReLU is applied in place, mid = in). Saved X^T slots (bf16 elements): the inner projection's input [d_model][ld] and
+// [rows][d_model], the inner projection's output in [rows][n_in] and the middle op's output mid [rows][k_out] (a ReLU FF has
+// none: its ReLU is applied in place, mid = in; a gated FF keeps both halves of in and the gate's product in mid). Saved X^T slots (bf16 elements): the inner projection's input [d_model][ld] and
 // the outer one's [k_out][ld].
 struct SubSlots { size_t x, in, mid, xt_in, xt_out; };
 
@@ -65,15 +70,15 @@ struct StackLayout {
   size_t act_stride, xt_stride, dyT_elems;   // floats / X^T elements of one layer; dY^T elements of one layer's group
   size_t xt_base = 0;                        // the stack's first X^T slot (TrainLayout places the stacks)
 
-  StackLayout(bool dec_, int rows_, int layers_, int dm_, int inner, int dff)
+  StackLayout(bool dec_, int rows_, int layers_, int dm_, int inner, int dff, bool gated = false)
       : dec(dec_), rows(rows_), ld(ldT(rows_)), layers(layers_), nsub(dec_ ? 3 : 2), dm(dm_), kind0(dec_ ? K_DEC_LAYER : K_ENC_LAYER) {
     const SubKind kinds[2][3] = {{SUB_SELF, SUB_FF}, {SUB_SELF, SUB_CROSS, SUB_FF}};
     size_t act = 0, xt = 0, dy = 0;
     for (int j = 0; j < nsub; ++j) {
-      const SubBlock b = sub[j] = sub_block(kinds[dec][j], inner, dff);
+      const SubBlock b = sub[j] = sub_block(kinds[dec][j], inner, dff, gated);
       at[j].x = act; act += (size_t)rows * dm;
       at[j].in = at[j].mid = act; act += (size_t)rows * b.n_in;
-      if (b.kind != SUB_FF) { at[j].mid = act; act += (size_t)rows * b.k_out; }
+      if (b.kind != SUB_FF || gated) { at[j].mid = act; act += (size_t)rows * b.k_out; }
       at[j].xt_in = xt; xt += (size_t)ld * dm;
       at[j].xt_out = xt; xt += (size_t)ld * b.k_out;
       dy += (size_t)ld * (b.n_in + dm);   // dY^T of the W_out product [d_model][ld] and of the W_in product [n_in][ld]
@@ -94,7 +99,7 @@ struct TrainLayout {
   StackLayout enc, dec;
   size_t xt_xkv, xt_total;
   size_t dyT_xkv;   // dY^T elements of the cross-K/V product [xld][ldT(T)]: a group of its own
-  explicit TrainLayout(const TrainDims& D) : enc(false, D.T, D.ne, D.dm, D.inner, D.dff), dec(true, D.R, D.nd, D.dm, D.inner, D.dff) {
+  explicit TrainLayout(const TrainDims& D) : enc(false, D.T, D.ne, D.dm, D.inner, D.dff, D.gated), dec(true, D.R, D.nd, D.dm, D.inner, D.dff, D.gated) {
     xt_xkv = enc.xt_stride * D.ne;
     dec.xt_base = xt_xkv + (size_t)enc.ld * D.dm;
     xt_total = dec.xt_base + dec.xt_stride * D.nd;
@@ -129,10 +134,10 @@ struct ParamOrder {
   int ne;
   StackLayout stack[2];   // encoder, decoder: the tables of sub-blocks only (no rows)
 
-  explicit ParamOrder(const rpr_model_desc& d)
+  explicit ParamOrder(const rpr_model_desc& d, bool gated = false)
       : own_out(d.out_embeds != d.in_embeds), ne(d.num_layers),
-        stack{StackLayout(false, 0, d.num_layers, d.d_model, d.num_heads * d.d_kv, d.d_ff),
-              StackLayout(true, 0, d.num_decoder_layers, d.d_model, d.num_heads * d.d_kv, d.d_ff)} {
+        stack{StackLayout(false, 0, d.num_layers, d.d_model, d.num_heads * d.d_kv, d.d_ff, gated),
+              StackLayout(true, 0, d.num_decoder_layers, d.d_model, d.num_heads * d.d_kv, d.d_ff, gated)} {
     const size_t dm = d.d_model, inner = (size_t)d.num_heads * d.d_kv, nd = d.num_decoder_layers;
     auto add = [&](int kind, int layer, size_t n) { slots.push_back({kind, layer, nullptr, n, total}); total += n; };
     add(K_SHARED, -1, (size_t)d.vocab_size * dm);

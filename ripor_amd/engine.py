@@ -342,7 +342,9 @@ def _ptr_array(tensors: Sequence[torch.Tensor]):
 class DeviceModel:
     """Binds a ``T5ForDocIDGeneration`` state dict (reference checkpoint key names, SURVEY.md §8
     row a14) to an ``rpr_model``: q/k/v are concatenated, codebooks and cross-attention k/v stacked,
-    everything float32 on the device."""
+    everything float32 on the device. The feed-forward kind is ``cfg.feed_forward_proj`` where the config object has one
+    (``"relu"`` or ``"gated-gelu"``), else what the state dict holds (``wi`` or ``wi_0`` / ``wi_1``); a gated block's two
+    input matrices are concatenated like q/k/v (rows 0..d_ff-1 = wi_0, the gate)."""
 
     def __init__(self, ctx: Context, state_dict: Dict[str, torch.Tensor], cfg):
         self.ctx, self.cfg = ctx, cfg
@@ -378,6 +380,21 @@ class DeviceModel:
                 N(f"{prefix}.{w}.weight", t, slice(j * n, (j + 1) * n))
             return t
 
+        has_gate = "encoder.block.0.layer.1.DenseReluDense.wi_0.weight" in state_dict
+        kind = getattr(cfg, "feed_forward_proj", "gated-gelu" if has_gate else "relu")
+        if kind not in ("relu", "gated-gelu"):
+            raise ValueError(f"feed_forward_proj={kind!r} is not supported: the feed-forward block is one of 'relu', 'gated-gelu'")
+        self.gated_ff = kind == "gated-gelu"
+
+        def ff_wi(prefix):
+            if not self.gated_ff:
+                return N(prefix + ".wi.weight", K(g(prefix + ".wi.weight")))
+            t = K(torch.cat([g(prefix + ".wi_0.weight"), g(prefix + ".wi_1.weight")], 0).contiguous())
+            n = t.shape[0] // 2
+            for j in range(2):
+                N(f"{prefix}.wi_{j}.weight", t, slice(j * n, (j + 1) * n))
+            return t
+
         ne, nd = cfg.num_layers, cfg.num_decoder_layers
         enc = dict(ln0=[], qkv=[], o=[], ln1=[], wi=[], wo=[])
         for i in range(ne):
@@ -386,7 +403,7 @@ class DeviceModel:
             enc["qkv"].append(attn_qkv(p + ".0.SelfAttention"))
             enc["o"].append(N(p + ".0.SelfAttention.o.weight", K(g(p + ".0.SelfAttention.o.weight"))))
             enc["ln1"].append(N(p + ".1.layer_norm.weight", K(g(p + ".1.layer_norm.weight"))))
-            enc["wi"].append(N(p + ".1.DenseReluDense.wi.weight", K(g(p + ".1.DenseReluDense.wi.weight"))))
+            enc["wi"].append(ff_wi(p + ".1.DenseReluDense"))
             enc["wo"].append(N(p + ".1.DenseReluDense.wo.weight", K(g(p + ".1.DenseReluDense.wo.weight"))))
         dec = dict(ln0=[], qkv=[], o=[], ln1=[], xq=[], xo=[], ln2=[], wi=[], wo=[])
         xkv = []
@@ -400,7 +417,7 @@ class DeviceModel:
             xkv += [g(p + ".1.EncDecAttention.k.weight"), g(p + ".1.EncDecAttention.v.weight")]
             dec["xo"].append(N(p + ".1.EncDecAttention.o.weight", K(g(p + ".1.EncDecAttention.o.weight"))))
             dec["ln2"].append(N(p + ".2.layer_norm.weight", K(g(p + ".2.layer_norm.weight"))))
-            dec["wi"].append(N(p + ".2.DenseReluDense.wi.weight", K(g(p + ".2.DenseReluDense.wi.weight"))))
+            dec["wi"].append(ff_wi(p + ".2.DenseReluDense"))
             dec["wo"].append(N(p + ".2.DenseReluDense.wo.weight", K(g(p + ".2.DenseReluDense.wo.weight"))))
         self.shared = N("shared.weight", K(g("shared.weight")))
         self.enc_rel = N("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", K(g("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight")))
@@ -443,8 +460,10 @@ class DeviceModel:
             setattr(d, "dec_" + k, self._arrays["dec_" + k])
         h = C.c_void_p()
         torch.cuda.synchronize(dev)
-        check(ctx.lib.rpr_load_model(ctx.handle, C.byref(d), C.byref(h)), "rpr_load_model")
+        ext = _lib.ModelExt(size=C.sizeof(_lib.ModelExt), ff_kind=_lib.FF_GATED_GELU if self.gated_ff else _lib.FF_RELU)
+        check(ctx.lib.rpr_load_model_ext(ctx.handle, C.byref(d), C.byref(ext), C.byref(h)), "rpr_load_model_ext")
         self.handle = h
+        self._desc = d   # (the per-layer arrays it points to are kept in self._arrays)
         self.L, self.V, self.d_model = L, V, cfg.d_model
         # a weight outside the range of the f16 planes pins the model to the exact-fp32 kernels (rpr_load_model)
         self.f32_only = bool(ctx.lib.rpr_model_f32_only(h))

@@ -493,7 +493,8 @@ def search_batch_size(cfg, batch_size: int, topk: int, max_new_token: int, flag:
         return flag
     nd, inner = cfg.num_decoder_layers, cfg.num_heads * cfg.d_kv
     per_query = 2 * nd * max_new_token * topk * inner * 4                       # K and V cache
-    per_query += topk * (6 * cfg.d_model + 4 * inner + 3 * cfg.d_ff) * 4          # activations + f16 planes of a step
+    ff_rows = 5 if getattr(cfg, "is_gated_ff", False) else 3                    # a gated block keeps the fp32 (gate | linear) row too
+    per_query += topk * (6 * cfg.d_model + 4 * inner + ff_rows * cfg.d_ff) * 4    # activations + f16 planes of a step
     per_query += topk * max(cfg.decoder_vocab_sizes) * 8 + 64 * 1024            # logits, trie bounds, encoder side
     try:
         free, _ = torch.cuda.mem_get_info(device)

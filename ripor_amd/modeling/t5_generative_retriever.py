@@ -18,6 +18,10 @@ import numpy as np
 import torch
 
 
+# config.feed_forward_proj values the device paths run: T5 v1.0's DenseReluDense and v1.1's T5DenseGatedActDense with gelu_new
+FEED_FORWARD_KINDS = ("relu", "gated-gelu")
+
+
 class T5forDocIDConfig:
     """Fields of the reference config (T5Config + docid extras, reference :45-65)."""
 
@@ -52,8 +56,14 @@ class T5forDocIDConfig:
         self.max_decoder_length = len(self.decoder_vocab_sizes)
         self.extra = dict(kwargs)
         assert self.apply_decoder_t5_stack == False  # noqa: E712  (reference :67)
-        if feed_forward_proj != "relu":
-            raise ValueError(f"feed_forward_proj={feed_forward_proj!r}: only the non-gated ReLU T5 v1.0 block is supported")
+        if feed_forward_proj not in FEED_FORWARD_KINDS:
+            raise ValueError(f"feed_forward_proj={feed_forward_proj!r} is not supported: the feed-forward block is one of "
+                             f"{', '.join(repr(k) for k in FEED_FORWARD_KINDS)}")
+
+    @property
+    def is_gated_ff(self) -> bool:
+        """wo(gelu_new(wi_0 x) * wi_1 x) (T5 v1.1, Flan-T5, mT5) instead of wo(relu(wi x))."""
+        return self.feed_forward_proj == "gated-gelu"
 
     @classmethod
     def from_pretrained(cls, path: str) -> "T5forDocIDConfig":
@@ -74,7 +84,8 @@ class T5forDocIDConfig:
                    relative_attention_max_distance=dims.relative_attention_max_distance,
                    layer_norm_epsilon=dims.layer_norm_epsilon,
                    shared_output_input_embeds=dims.shared_output_input_embeds,
-                   scaleup_output_hidden=dims.scaleup_output_hidden)
+                   scaleup_output_hidden=dims.scaleup_output_hidden,
+                   feed_forward_proj=getattr(dims, "feed_forward_proj", "relu"))
 
     def to_dict(self) -> dict:
         d = {k: v for k, v in self.__dict__.items() if k != "extra"}
@@ -93,7 +104,9 @@ _IGNORED_KEYS = ("encoder.embed_tokens.weight", "decoder.embed_tokens.weight", "
 
 
 def expected_keys(cfg: T5forDocIDConfig) -> List[str]:
-    """State-dict keys the search path reads."""
+    """State-dict keys the search path reads. A gated feed-forward has wi_0 (the gate) and wi_1 where
+    the ReLU block has wi (HF keeps the module name DenseReluDense for both)."""
+    wi = ["wi_0", "wi_1"] if cfg.is_gated_ff else ["wi"]
     keys = ["shared.weight", "encoder.final_layer_norm.weight", "decoder.final_layer_norm.weight", "start_token_embed",
             "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight",
             "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"]
@@ -101,13 +114,13 @@ def expected_keys(cfg: T5forDocIDConfig) -> List[str]:
         p = f"encoder.block.{i}.layer"
         keys += [f"{p}.0.SelfAttention.{w}.weight" for w in "qkvo"]
         keys += [f"{p}.0.layer_norm.weight", f"{p}.1.layer_norm.weight",
-                 f"{p}.1.DenseReluDense.wi.weight", f"{p}.1.DenseReluDense.wo.weight"]
+                 *[f"{p}.1.DenseReluDense.{w}.weight" for w in wi], f"{p}.1.DenseReluDense.wo.weight"]
     for i in range(cfg.num_decoder_layers):
         p = f"decoder.block.{i}.layer"
         keys += [f"{p}.0.SelfAttention.{w}.weight" for w in "qkvo"]
         keys += [f"{p}.1.EncDecAttention.{w}.weight" for w in "qkvo"]
         keys += [f"{p}.0.layer_norm.weight", f"{p}.1.layer_norm.weight", f"{p}.2.layer_norm.weight",
-                 f"{p}.2.DenseReluDense.wi.weight", f"{p}.2.DenseReluDense.wo.weight"]
+                 *[f"{p}.2.DenseReluDense.{w}.weight" for w in wi], f"{p}.2.DenseReluDense.wo.weight"]
     for i in range(len(cfg.decoder_vocab_sizes)):
         keys.append(f"list_decoder_embeds.{i}.weight")
         if not cfg.shared_output_input_embeds:

@@ -182,8 +182,14 @@ def mini_dims(L: int = 8, V: int = 256, enc_layers: int = 2, d_ff: int = 256,
                      decoder_vocab_sizes=[V] * L, **kw)
 
 
+def t5_v11_base_dims(L: int = 32, V: int = 256, **kw) -> ModelDims:
+    """google/t5-v1_1-base, flan-t5-base, mt5-base (but for its vocabulary): the t5-base stack with d_ff 2048 and the gated-GELU
+    feed-forward (``make_state_dict(dims, feed_forward_proj="gated-gelu")``; the kind is not a field of ModelDims)."""
+    return ModelDims(d_ff=2048, decoder_vocab_sizes=[V] * L, **kw)
+
+
 def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35, outliers: float = 0.0,
-                    stream_scale: float = 1.0) -> Dict[str, np.ndarray]:
+                    stream_scale: float = 1.0, feed_forward_proj: str = "relu") -> Dict[str, np.ndarray]:
     """Seeded weights under the reference's state-dict key names (float32 numpy arrays).
 
     Scales follow HF's T5 init factors so activations stay O(1); layer-norm weights are
@@ -204,7 +210,15 @@ def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35
     ``stream_scale`` times the unscaled model's from the embedding to the last block, and the RMSNorms undo it: the network
     computes the same function up to the effect of the norms' eps. 1.0 leaves every array as it was. For the small end of the
     split-precision mode's working range (tests/test_gpu_magnitude.py).
+
+    ``feed_forward_proj``: "relu" (``DenseReluDense.wi``) or "gated-gelu" (T5 v1.1: ``wi_0``, the gate, and ``wi_1`` in its
+    place, each of wi's shape and scale; every other array is the same). ``outliers`` is for the ReLU block only.
     """
+    if feed_forward_proj not in ("relu", "gated-gelu"):
+        raise ValueError(f"feed_forward_proj={feed_forward_proj!r}: 'relu' or 'gated-gelu'")
+    if feed_forward_proj != "relu" and outliers > 0.0:
+        raise ValueError("outliers are built for the ReLU feed-forward block")
+    wi_names = ("wi",) if feed_forward_proj == "relu" else ("wi_0", "wi_1")
     d, inner, dff = dims.d_model, dims.inner, dims.d_ff
     sd: Dict[str, np.ndarray] = {}
     r3 = 3.0 ** 0.5  # uniform[-a,a) has std a/sqrt(3)
@@ -230,7 +244,8 @@ def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35
         p = f"encoder.block.{i}.layer"
         attn(p + ".0.SelfAttention", i == 0)
         ln(p + ".0.layer_norm.weight")
-        u(p + ".1.DenseReluDense.wi.weight", (dff, d), d ** -0.5)
+        for wi in wi_names:
+            u(p + f".1.DenseReluDense.{wi}.weight", (dff, d), d ** -0.5)
         u(p + ".1.DenseReluDense.wo.weight", (d, dff), dff ** -0.5)
         ln(p + ".1.layer_norm.weight")
     ln("encoder.final_layer_norm.weight")
@@ -241,7 +256,8 @@ def make_state_dict(dims: ModelDims, seed: int = SEED, logit_scale: float = 0.35
         ln(p + ".0.layer_norm.weight")
         attn(p + ".1.EncDecAttention", False)
         ln(p + ".1.layer_norm.weight")
-        u(p + ".2.DenseReluDense.wi.weight", (dff, d), d ** -0.5)
+        for wi in wi_names:
+            u(p + f".2.DenseReluDense.{wi}.weight", (dff, d), d ** -0.5)
         u(p + ".2.DenseReluDense.wo.weight", (d, dff), dff ** -0.5)
         ln(p + ".2.layer_norm.weight")
     ln("decoder.final_layer_norm.weight")
@@ -389,14 +405,14 @@ def make_codes_fast(N: int, L: int, V: int, seed: int = SEED, zipf: Optional[flo
     return out
 
 
-def patterned_state_dict(dims: ModelDims) -> Dict[str, np.ndarray]:
+def patterned_state_dict(dims: ModelDims, feed_forward_proj: str = "relu") -> Dict[str, np.ndarray]:
     """A state dict of the checkpoint's tensor names with low-entropy, exactly representable values: element i of tensor
     `name` = ((crc32(name) % 7) + (i % 11) - 8) / 16. For fixtures that store a checkpoint DIRECTORY (tests/golden/
     c9_ref_checkpoint.zip, written by the reference's save_pretrained): the zip stays small and a reader can be checked
     tensor by tensor against the formula."""
     import zlib
     out = {}
-    for name, arr in make_state_dict(dims, seed=1).items():
+    for name, arr in make_state_dict(dims, seed=1, feed_forward_proj=feed_forward_proj).items():
         n = int(np.prod(arr.shape))
         v = ((zlib.crc32(name.encode()) % 7) + (np.arange(n, dtype=np.int64) % 11) - 8).astype(np.float32) / 16.0
         out[name] = v.reshape(arr.shape)

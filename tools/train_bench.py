@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time the ranking fine-tune step (BASELINE config 5): t5-base dims (--dims t5-3b: d_model 1024, 32 heads of 128, d_ff 16384,
-24 + 24 layers, the dims of bench.py's secondary_t5_3b), bz examples per step PER GPU, two teacher-forced
+24 + 24 layers, the dims of bench.py's secondary_t5_3b; --dims t5-v1.1-base: the t5-base stack with d_ff 2048 and the gated-GELU
+feed-forward of T5 v1.1 / Flan-T5 / mT5), bz examples per step PER GPU, two teacher-forced
 passes of L = 32 positions over queries of ~16 tokens, backward, gradient all-reduce (RCCL when launched on several
 ranks), AdamW. --loss seq2seq: the seq2seq docid cross-entropy step instead (one teacher-forced pass per query, the
 codebook-logit head). Rank 0 prints one JSON line (examples/s of the whole job, max step time over the ranks).
@@ -8,7 +9,7 @@ codebook-logit head). Rank 0 prints one JSON line (examples/s of the whole job, 
 --precision and --loss take comma-separated lists: one JSON line per (precision, loss) on ONE model load (t5-3b: 11 GB of
 weights to generate and upload). --embed: before the steps, time rpr_embed on 128 texts of ~16 tokens and 128 texts of 128
 tokens (one JSON line).
-Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq] [--dims t5-base|t5-3b] [--embed] [--lq N]
+Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq] [--dims t5-base|t5-3b|t5-v1.1-base] [--embed] [--lq N]
        python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/train_bench.py"""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -34,7 +35,7 @@ ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--len", type=int, default=32, dest="L")
 ap.add_argument("--precision", default=["f16x2"], type=listed(PRECISIONS))
 ap.add_argument("--loss", default=["lngknp"], type=listed(LOSSES))
-ap.add_argument("--dims", default="t5-base", choices=["t5-base", "t5-3b"])
+ap.add_argument("--dims", default="t5-base", choices=["t5-base", "t5-3b", "t5-v1.1-base"])
 ap.add_argument("--embed", action="store_true")
 ap.add_argument("--lq", type=int, default=0, help="all queries this many tokens long (default: ~16, as the fine-tune data)")
 args = ap.parse_args()
@@ -42,8 +43,12 @@ L, V, bz = args.L, 256, args.bz
 if args.dims == "t5-3b":
     dims = synth.ModelDims(d_model=1024, d_kv=128, d_ff=16384, num_layers=24, num_decoder_layers=24, num_heads=32,
                            decoder_vocab_sizes=[V] * L)
+elif args.dims == "t5-v1.1-base":
+    dims = synth.t5_v11_base_dims(L=L, V=V)
 else:
     dims = synth.t5_base_dims(L=L, V=V)
+ff_kind = "gated-gelu" if args.dims == "t5-v1.1-base" else "relu"
+ff_mats = 3 if ff_kind == "gated-gelu" else 2          # d_model x d_ff matrices of a feed-forward block
 rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
 torch.cuda.set_device(local)
 if world > 1:
@@ -52,7 +57,7 @@ if world > 1:
     dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
 ctx = E.Context.get(local)
 ctx.set_precision(args.precision[0])
-model = E.DeviceModel(ctx, synth.make_state_dict(dims), dims)
+model = E.DeviceModel(ctx, synth.make_state_dict(dims, feed_forward_proj=ff_kind), dims)
 state = E.TrainState(model)
 qlen = dict(fixed_len=args.lq) if args.lq else dict(mean_len=16, std_len=5, min_len=6, max_len=64)
 ids, mask = synth.make_queries(bz * world, vocab_size=dims.vocab_size, seed=5, **qlen)
@@ -114,8 +119,8 @@ def leg(precision, loss):
     torch.cuda.synchronize()
     st = ctx.profile_get(); ctx.profile_enable(False)
     dm, inner, dff, nd = dims.d_model, dims.inner, dims.d_ff, dims.num_decoder_layers
-    flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * dm * inner + 2 * dm * dff) + nd * 2 * dm * inner)
-                       + bz * (1 if loss == "seq2seq" else 2) * L * nd * (6 * dm * inner + 2 * dm * dff)
+    flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * dm * inner + ff_mats * dm * dff) + nd * 2 * dm * inner)
+                       + bz * (1 if loss == "seq2seq" else 2) * L * nd * (6 * dm * inner + ff_mats * dm * dff)
                        + (bz * L * V * dm if loss == "seq2seq" else 0))
     if rank == 0:
         task = ("seq2seq docid cross-entropy step" if loss == "seq2seq" else "lng_knp margin-MSE fine-tune step")
