@@ -567,6 +567,86 @@ int rpr_op_gated_gelu(rpr_ctx* ctx, const float* gu, int32_t M, int32_t F, const
  * gelu_new'(g) = 0.5 (1 + t) + 0.5 g (1 - t^2) c (1 + 3 * 0.044715 g^2), t = tanh(c (g + 0.044715 g^3)), c = 0.7978845608028654.
  * fp32 in every precision mode, one thread per element group, no atomics: two calls give the same bits. */
 int rpr_op_gated_gelu_bwd(rpr_ctx* ctx, const float* gu, const float* dmid, int32_t M, int32_t F, float* dgu, void* stream);
+/* ---- attention test hooks: one launch of an attention site of the search path, routed by the site's own launcher ----
+ * Every hook fills the site's argument struct from the descriptor, asks the site's planner and runs the site's launcher, so
+ * the shape takes the kernel a search would give it; *out_kernel (nullable) receives the AttnKernel the plan chose (its name:
+ * rpr_attn_kernel_name). A shape the planner refuses returns RPR_ERR_INVALID with a message and launches nothing. All
+ * pointers are [dev]; the relative-position bucket tables are built from num_buckets / max_distance as at model load.
+ * Output: fp32 `out`, or — when out_planes is set — the two f16 planes of out * 16 at out_planes and out_planes +
+ * plane_stride (elements), rows laid out as the fp32 output; a clamped plane value raises RPR_STATUS_SATURATED on the ctx.
+ * Scores are unscaled: softmax(q . k + bias[bucket(rel)]) . v over the attended keys. dkv = 64 or 128. */
+typedef struct rpr_enc_attn_op {
+  const float* qkv;         /* [rows, 3 * H * dkv]: q | k | v; padded: rows = Q * Lq; packed: row offs[q] + i */
+  const int32_t* mask;      /* [Q, Lq] key mask (NULL with causal) */
+  const float* rel_bias;    /* [num_buckets, H] */
+  const int32_t* offs;      /* nullable (packed rows): first row of query q ... */
+  const int32_t* lens;      /*   ... and its row count (index of the last attended key + 1) */
+  float* out;               /* [rows, H * dkv] */
+  void* out_planes;
+  int64_t plane_stride;
+  int32_t num_buckets, max_distance, Q, Lq, H, dkv;
+  int32_t causal;           /* 1: key j <= query i only, unidirectional buckets (teacher-forced decoder), Lq <= 64 */
+  int32_t mfma;             /* EncAttnArgs::mfma of the training forward */
+} rpr_enc_attn_op;
+int rpr_op_enc_attn(rpr_ctx* ctx, const rpr_enc_attn_op* op, int32_t* out_kernel, void* stream);
+/* Self-attention of sequential step t: row r = q * B + b attends to positions 0..t of its ancestry; the dkv floats of
+ * (query, head, position p, slot) start at q * q_stride + head * h_stride + p * pos_stride + slot * slot_stride, slot =
+ * anc[r * anc_ld + p] for p < t and b for p = t. Queries from *nq_dev on (nullable) are skipped. */
+typedef struct rpr_dec_self_attn_op {
+  const float* q;           /* [Q * B, H * dkv] */
+  const float* kcache;
+  const float* vcache;
+  const uint16_t* anc;
+  const float* rel_bias;    /* [num_buckets, H] */
+  const int32_t* nq_dev;
+  float* out;               /* [Q * B, H * dkv] */
+  void* out_planes;
+  int64_t plane_stride, q_stride, h_stride, pos_stride, slot_stride;
+  int32_t anc_ld, num_buckets, max_distance, Q, B, H, t, dkv;
+} rpr_dec_self_attn_op;
+int rpr_op_dec_self_attn(rpr_ctx* ctx, const rpr_dec_self_attn_op* op, int32_t* out_kernel, void* stream);
+/* Cross-attention of B rows per query against the query's Lq encoder rows. site: RPR_CROSS_SITE_BLOCK = the block kernel's
+ * launcher (training forward), _STEP = a sequential step (B = beams), _TAIL = the tail pass (B = beams x tail positions).
+ * The index of the last attended key + 1 of every query is computed by the hook as a search does (into ctx scratch), so a
+ * query without an attended key raises RPR_STATUS_EMPTY_QUERY and gets zeros. */
+#define RPR_CROSS_SITE_BLOCK 0
+#define RPR_CROSS_SITE_STEP 1
+#define RPR_CROSS_SITE_TAIL 2
+typedef struct rpr_cross_attn_op {
+  const float* q;           /* [Q * B, H * dkv] */
+  const float* xk;          /* K row (query, j) at xk + (query * Lq + j) * xld, or (offs[query] + j) * xld */
+  const float* xv;
+  const int32_t* mask;      /* [Q, Lq] */
+  const int32_t* offs;      /* nullable (packed encoder rows) */
+  const int32_t* nq_dev;    /* nullable */
+  float* out;               /* [Q * B, H * dkv] */
+  void* out_planes;
+  int64_t plane_stride;
+  int32_t site, xld, Q, B, H, Lq, dkv;
+} rpr_cross_attn_op;
+int rpr_op_cross_attn(rpr_ctx* ctx, const rpr_cross_attn_op* op, int32_t* out_kernel, void* stream);
+/* Self-attention of the tail pass: sequence s = entry * B + b (s < *nseq_dev) has L - T rows (positions T..L-1) in qkv;
+ * positions < T come from the cache of stage query kvq[entry] (NULL: flist[entry]) through the ancestry row
+ * flist[entry] * B + b, positions >= T from the sequence's own rows, causally. */
+typedef struct rpr_tail_self_attn_op {
+  const float* qkv;         /* [nseq_cap * (L - T), 3 * H * dkv] */
+  const float* kcache;
+  const float* vcache;
+  const uint16_t* anc;
+  const int32_t* flist;
+  const int32_t* kvq;       /* nullable */
+  const int32_t* nseq_dev;
+  const float* rel_bias;    /* [num_buckets, H] */
+  float* out;               /* [nseq_cap * (L - T), H * dkv] */
+  void* out_planes;
+  int64_t plane_stride, q_stride, h_stride, pos_stride, slot_stride;
+  int32_t anc_ld, num_buckets, max_distance, nseq_cap, B, H, T, L, dkv;
+} rpr_tail_self_attn_op;
+int rpr_op_tail_self_attn(rpr_ctx* ctx, const rpr_tail_self_attn_op* op, int32_t* out_kernel, void* stream);
+/* Name of an AttnKernel value (csrc/attn_route.h RPR_ATTN_KERNELS), NULL when out of range. Host only. */
+const char* rpr_attn_kernel_name(int kernel);
+/* Number of AttnKernel values (names 0 .. n - 1). Host only. */
+int rpr_attn_kernel_count(void);
 /* Encoder forward only (reference generation.py:132-137): out [Q, Lq, d_model]. */
 int rpr_encode(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
                int32_t Q, int32_t Lq, float* out, void* stream);

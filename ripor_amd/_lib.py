@@ -81,8 +81,46 @@ class XencDesc(C.Structure):
                                            "pool_w", "pool_b", "cls_w", "cls_b")])
 
 
+def _op_struct(ptrs, i64s, i32s):
+    return [(n, C.c_void_p) for n in ptrs] + [(n, C.c_int64) for n in i64s] + [(n, C.c_int32) for n in i32s]
+
+
+class EncAttnOp(C.Structure):
+    """``rpr_enc_attn_op`` (attention test hook; device pointers as integers)."""
+    _fields_ = _op_struct(("qkv", "mask", "rel_bias", "offs", "lens", "out", "out_planes"), ("plane_stride",),
+                          ("num_buckets", "max_distance", "Q", "Lq", "H", "dkv", "causal", "mfma"))
+
+
+class DecSelfAttnOp(C.Structure):
+    """``rpr_dec_self_attn_op``."""
+    _fields_ = _op_struct(("q", "kcache", "vcache", "anc", "rel_bias", "nq_dev", "out", "out_planes"),
+                          ("plane_stride", "q_stride", "h_stride", "pos_stride", "slot_stride"),
+                          ("anc_ld", "num_buckets", "max_distance", "Q", "B", "H", "t", "dkv"))
+
+
+class CrossAttnOp(C.Structure):
+    """``rpr_cross_attn_op``."""
+    _fields_ = _op_struct(("q", "xk", "xv", "mask", "offs", "nq_dev", "out", "out_planes"), ("plane_stride",),
+                          ("site", "xld", "Q", "B", "H", "Lq", "dkv"))
+
+
+class TailSelfAttnOp(C.Structure):
+    """``rpr_tail_self_attn_op``."""
+    _fields_ = _op_struct(("qkv", "kcache", "vcache", "anc", "flist", "kvq", "nseq_dev", "rel_bias", "out", "out_planes"),
+                          ("plane_stride", "q_stride", "h_stride", "pos_stride", "slot_stride"),
+                          ("anc_ld", "num_buckets", "max_distance", "nseq_cap", "B", "H", "T", "L", "dkv"))
+
+
+CROSS_SITE_BLOCK, CROSS_SITE_STEP, CROSS_SITE_TAIL = 0, 1, 2
+
 # every symbol include/ripor_hip.h declares: (restype, argtypes)
 SIGNATURES = {
+    "rpr_op_enc_attn": (C.c_int, [C.c_void_p, C.POINTER(EncAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_dec_self_attn": (C.c_int, [C.c_void_p, C.POINTER(DecSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_cross_attn": (C.c_int, [C.c_void_p, C.POINTER(CrossAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_tail_self_attn": (C.c_int, [C.c_void_p, C.POINTER(TailSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_attn_kernel_name": (C.c_char_p, [C.c_int]),
+    "rpr_attn_kernel_count": (C.c_int, []),
     "rpr_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "rpr_free_ctx": (None, [C.c_void_p]),
     "rpr_last_error": (C.c_char_p, []),

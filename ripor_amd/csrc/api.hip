@@ -46,6 +46,24 @@ int rel_bucket(int rel, int bidirectional, int num_buckets, int max_distance) {
   return bucket + large;
 }
 
+// The bucket tables the attention kernels index, as device arrays the caller owns (hipFree): enc [2 MAX_LQ - 1], bucket of
+// rel = key - query at rel + MAX_LQ - 1 (bidirectional); dec [MAX_DEC_LEN], bucket of rel = -n (unidirectional). One place
+// for a model's tables (rpr_load_model_ext) and the attention test hooks (rpr_op_*_attn). Either output may be null.
+int make_bucket_tables(int num_buckets, int max_distance, int32_t** enc, int32_t** dec) {
+  std::vector<int32_t> eb(2 * MAX_LQ - 1), db(MAX_DEC_LEN);
+  for (int rel = -(MAX_LQ - 1); rel <= MAX_LQ - 1; ++rel) eb[rel + MAX_LQ - 1] = rel_bucket(rel, 1, num_buckets, max_distance);
+  for (int n = 0; n < MAX_DEC_LEN; ++n) db[n] = rel_bucket(-n, 0, num_buckets, max_distance);
+  if (enc) {
+    RPR_HIP(hipMalloc(enc, eb.size() * 4));
+    RPR_HIP(hipMemcpy(*enc, eb.data(), eb.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (dec) {
+    RPR_HIP(hipMalloc(dec, db.size() * 4));
+    RPR_HIP(hipMemcpy(*dec, db.data(), db.size() * 4, hipMemcpyHostToDevice));
+  }
+  return RPR_OK;
+}
+
 // |logit| <= sqrt(d_model) * max_row |E_out[r] * ln_final| * scaleup factor for ANY decoder state (Cauchy-Schwarz on the
 // RMS-normalised hidden state): the bound behind the forced-tail fork's masked-candidate proof (passes.hip: enqueue_fork).
 int compute_logit_bound(rpr_ctx* c, rpr_model* m, hipStream_t s, float* out) {
@@ -235,14 +253,7 @@ int rpr_load_model_ext(rpr_ctx* c, const rpr_model_desc* d, const rpr_model_ext*
   RPR_REQUIRE(m->params.fill(*d), "NULL per-layer weight pointer");
   // the desc's host arrays need not outlive this call
   for (int kind = K_ENC_LAYER; kind < K_END; ++kind) m->d.*layer_field(kind) = nullptr;
-  std::vector<int32_t> eb(2 * MAX_LQ - 1), db(MAX_DEC_LEN);
-  for (int rel = -(MAX_LQ - 1); rel <= MAX_LQ - 1; ++rel)
-    eb[rel + MAX_LQ - 1] = rel_bucket(rel, 1, d->rel_buckets, d->rel_max_distance);
-  for (int n = 0; n < MAX_DEC_LEN; ++n) db[n] = rel_bucket(-n, 0, d->rel_buckets, d->rel_max_distance);
-  RPR_HIP(hipMalloc(&m->enc_bucket, eb.size() * 4));
-  RPR_HIP(hipMalloc(&m->dec_bucket, db.size() * 4));
-  RPR_HIP(hipMemcpy(m->enc_bucket, eb.data(), eb.size() * 4, hipMemcpyHostToDevice));
-  RPR_HIP(hipMemcpy(m->dec_bucket, db.data(), db.size() * 4, hipMemcpyHostToDevice));
+  if (const int e = make_bucket_tables(d->rel_buckets, d->rel_max_distance, &m->enc_bucket, &m->dec_bucket)) return e;
   // hi/lo f16 planes of every GEMM weight for the split-precision kernels
   {
     const size_t dm = d->d_model;
@@ -1091,6 +1102,127 @@ int rpr_op_gated_gelu_bwd(rpr_ctx* c, const float* gu, const float* dmid, int32_
   RPR_HIP(launch_gated_gelu_bwd(gu, dmid, M, F, dgu, reinterpret_cast<hipStream_t>(stream)));
   return RPR_OK;
 }
+
+// ---- attention test hooks: the descriptor -> the site's argument struct -> the site's planner (reported) and launcher ----
+}  // extern "C"
+
+namespace {
+
+// the device bucket table of one hook call, freed on every return path
+struct BucketTmp {
+  int32_t* p = nullptr;
+  ~BucketTmp() { if (p) (void)hipFree(p); }
+};
+
+int attn_op_common(const void* out, const void* out_planes, int64_t plane_stride, int num_buckets, int max_distance, int H, int dkv) {
+  RPR_REQUIRE((out != nullptr) != (out_planes != nullptr), "exactly one of out and out_planes");
+  RPR_REQUIRE(!out_planes || plane_stride > 0, "plane_stride");
+  RPR_REQUIRE(num_buckets >= 2 && num_buckets <= 64 && max_distance > num_buckets, "num_buckets / max_distance out of range");
+  RPR_REQUIRE(H >= 1 && (dkv == DKV || dkv == 128), "H >= 1, dkv 64 or 128");
+  return RPR_OK;
+}
+
+int attn_op_plan(const AttnLaunch& p, int32_t* out_kernel, const char* site) {
+  if (out_kernel) *out_kernel = p.invalid ? (int32_t)ATTN_NONE : (int32_t)p.kernel;
+  if (p.invalid || p.kernel == ATTN_NONE) {
+    set_error(std::string("invalid argument: the attention planner refuses this shape (") + site + ")");
+    return RPR_ERR_INVALID;
+  }
+  return RPR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rpr_op_enc_attn(rpr_ctx* c, const rpr_enc_attn_op* o, int32_t* out_kernel, void* stream) {
+  RPR_REQUIRE(c && o && o->qkv && o->rel_bias, "NULL argument");
+  if (const int e = attn_op_common(o->out, o->out_planes, o->plane_stride, o->num_buckets, o->max_distance, o->H, o->dkv)) return e;
+  RPR_REQUIRE(o->Q >= 1 && o->Lq >= 1 && o->Lq <= MAX_LQ, "bad shape");
+  RPR_REQUIRE(o->causal ? o->Lq <= MAX_DEC_LEN : o->mask != nullptr, "causal: Lq <= 64; bidirectional: a key mask");
+  RPR_REQUIRE((o->offs != nullptr) == (o->lens != nullptr) && !(o->offs && o->causal), "offs and lens go together (bidirectional only)");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  BucketTmp bt;
+  if (const int e = o->causal ? make_bucket_tables(o->num_buckets, o->max_distance, nullptr, &bt.p)
+                              : make_bucket_tables(o->num_buckets, o->max_distance, &bt.p, nullptr)) return e;
+  EncAttnArgs a{o->qkv, o->mask, o->rel_bias, bt.p, o->out, o->Q, o->Lq, o->H, o->num_buckets,
+                reinterpret_cast<__half*>(o->out_planes), (size_t)o->plane_stride, o->offs, o->lens, c->status, o->causal ? 1 : 0, o->mfma ? 1 : 0,
+                o->dkv};
+  if (const int e = attn_op_plan(plan_enc_attn(enc_attn_in(a), g_attn_tuning), out_kernel, "launch_enc_attn")) return e;
+  RPR_HIP(launch_enc_attn(a, s));
+  RPR_HIP(hipStreamSynchronize(s));   // the bucket table is freed when this scope ends
+  return RPR_OK;
+}
+
+int rpr_op_dec_self_attn(rpr_ctx* c, const rpr_dec_self_attn_op* o, int32_t* out_kernel, void* stream) {
+  RPR_REQUIRE(c && o && o->q && o->kcache && o->vcache && o->anc && o->rel_bias, "NULL argument");
+  if (const int e = attn_op_common(o->out, o->out_planes, o->plane_stride, o->num_buckets, o->max_distance, o->H, o->dkv)) return e;
+  RPR_REQUIRE(o->Q >= 1 && o->B >= 1 && o->B <= 65536 && o->t >= 0 && o->t < MAX_DEC_LEN && o->anc_ld > o->t, "bad shape");
+  RPR_REQUIRE(o->q_stride > 0 && o->h_stride > 0 && o->pos_stride > 0 && o->slot_stride >= o->dkv &&
+                  ((o->q_stride | o->h_stride | o->pos_stride | o->slot_stride) & 3) == 0, "cache strides: positive multiples of 4 floats");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  BucketTmp bt;
+  if (const int e = make_bucket_tables(o->num_buckets, o->max_distance, nullptr, &bt.p)) return e;
+  DecSelfAttnArgs a{o->q, o->kcache, o->vcache, (size_t)o->q_stride, (size_t)o->h_stride, (size_t)o->pos_stride, (size_t)o->slot_stride,
+                    o->anc, o->anc_ld, o->rel_bias, bt.p, o->out, o->Q, o->B, o->H, o->t,
+                    reinterpret_cast<__half*>(o->out_planes), (size_t)o->plane_stride, c->status, o->nq_dev};
+  a.dkv = o->dkv;
+  if (const int e = attn_op_plan(plan_dec_self_attn(dec_self_attn_in(a)), out_kernel, "launch_dec_self_attn")) return e;
+  RPR_HIP(launch_dec_self_attn(a, s));
+  RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
+int rpr_op_cross_attn(rpr_ctx* c, const rpr_cross_attn_op* o, int32_t* out_kernel, void* stream) {
+  RPR_REQUIRE(c && o && o->q && o->xk && o->xv && o->mask, "NULL argument");
+  if (const int e = attn_op_common(o->out, o->out_planes, o->plane_stride, 32, 128, o->H, o->dkv)) return e;
+  RPR_REQUIRE(o->site >= RPR_CROSS_SITE_BLOCK && o->site <= RPR_CROSS_SITE_TAIL, "site");
+  RPR_REQUIRE(o->Q >= 1 && o->B >= 1 && o->Lq >= 1 && o->Lq <= MAX_LQ && o->xld >= o->H * o->dkv && (o->xld & 3) == 0, "bad shape");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // index of the last attended key + 1 of every query, as a search computes it (and its empty-query report)
+  if (const int e = ensure(c, c->ws.last, (size_t)o->Q * sizeof(int32_t))) return e;
+  RPR_HIP(launch_mask_lengths(o->mask, P<int32_t>(c->ws.last), o->Q, o->Lq, s, c->status + 1));
+  DecCrossAttnArgs a{o->q, o->xk, o->xv, o->xld, o->mask, o->out, o->Q, o->B, o->H, o->Lq,
+                     reinterpret_cast<__half*>(o->out_planes), (size_t)o->plane_stride, P<int32_t>(c->ws.last), o->offs, 0, c->status, o->nq_dev};
+  a.dkv = o->dkv;
+  const CrossAttnIn in = cross_attn_in(a);
+  const AttnLaunch p = o->site == RPR_CROSS_SITE_BLOCK ? plan_cross_block(in)
+                       : o->site == RPR_CROSS_SITE_STEP ? plan_step_cross_attn(in, g_attn_tuning) : plan_tail_cross_attn(in, g_attn_tuning);
+  if (const int e = attn_op_plan(p, out_kernel, o->site == RPR_CROSS_SITE_BLOCK ? "launch_dec_cross_attn"
+                                                : o->site == RPR_CROSS_SITE_STEP ? "launch_step_cross_attn" : "launch_tail_cross_attn")) return e;
+  const hipError_t launched = o->site == RPR_CROSS_SITE_BLOCK ? launch_dec_cross_attn(a, s)
+                              : o->site == RPR_CROSS_SITE_STEP ? launch_step_cross_attn(a, s) : launch_tail_cross_attn(a, s);
+  RPR_HIP(launched);
+  RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
+int rpr_op_tail_self_attn(rpr_ctx* c, const rpr_tail_self_attn_op* o, int32_t* out_kernel, void* stream) {
+  RPR_REQUIRE(c && o && o->qkv && o->kcache && o->vcache && o->anc && o->flist && o->nseq_dev && o->rel_bias, "NULL argument");
+  if (const int e = attn_op_common(o->out, o->out_planes, o->plane_stride, o->num_buckets, o->max_distance, o->H, o->dkv)) return e;
+  RPR_REQUIRE(o->nseq_cap >= 1 && o->B >= 1 && o->nseq_cap % o->B == 0 && o->L >= 1 && o->anc_ld >= o->L, "bad shape");   // T and L: the planner
+  RPR_REQUIRE(o->q_stride > 0 && o->h_stride > 0 && o->pos_stride > 0 && o->slot_stride >= o->dkv &&
+                  ((o->q_stride | o->h_stride | o->pos_stride | o->slot_stride) & 3) == 0, "cache strides: positive multiples of 4 floats");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  BucketTmp bt;
+  if (const int e = make_bucket_tables(o->num_buckets, o->max_distance, nullptr, &bt.p)) return e;
+  TailSelfAttnArgs a{o->qkv, o->kcache, o->vcache, (size_t)o->q_stride, (size_t)o->h_stride, (size_t)o->pos_stride, (size_t)o->slot_stride,
+                     o->anc, o->anc_ld, o->flist, o->nseq_dev, o->rel_bias, bt.p, o->out, reinterpret_cast<__half*>(o->out_planes),
+                     (size_t)o->plane_stride, c->status, o->nseq_cap, o->B, o->H, o->T, o->L};
+  a.dkv = o->dkv;
+  a.kvq = o->kvq;
+  if (const int e = attn_op_plan(plan_tail_self_attn(tail_self_attn_in(a), g_attn_tuning), out_kernel, "launch_tail_self_attn")) return e;
+  RPR_HIP(launch_tail_self_attn(a, s));
+  RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
+const char* rpr_attn_kernel_name(int kernel) { return kernel >= 0 && kernel < ATTN_KERNEL_COUNT ? attn_kernel_name(kernel) : nullptr; }
+int rpr_attn_kernel_count(void) { return ATTN_KERNEL_COUNT; }
 
 int rpr_get_status(rpr_ctx* c, void* stream, uint32_t* out_flags, int clear) {
   RPR_REQUIRE(c && out_flags, "NULL argument");

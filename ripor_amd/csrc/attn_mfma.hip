@@ -682,6 +682,15 @@ __global__ __launch_bounds__(256, 4) void enc_attn_mfma_v2_kernel(EncAttnArgs a,
   const bool kok = ln < nrow && a.mask[(size_t)qi * a.Lq + lnc] != 0;
   const unsigned okm = (unsigned)(__ballot(kok) & 0xffffffffull);   // bit j: key j is attended
   const unsigned okh = half ? okm >> 4 : okm;             // key kappa(kk, 0) + 4 half
+  const size_t obase = row0 * inner + h * DKV;
+  unsigned long long bad = 0ull;
+  if (okm == 0u) {   // wave-uniform: no attended key (an empty query in the padded layout). softmax_row16 needs one: zeros, as every attention kernel writes
+    f32x16 o[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
+    store_o_tile_v2(o, Os, lane, nrow, inner, a.out ? a.out + obase : nullptr, a.out_h ? a.out_h + obase : nullptr, a.o_ps, bad);
+    return;
+  }
   const int kk_end = nrow > 24 ? 16 : nrow > 16 ? 12 : nrow > 8 ? 8 : 4;
   float v0[16], v1[16];
 #pragma unroll
@@ -713,8 +722,6 @@ __global__ __launch_bounds__(256, 4) void enc_attn_mfma_v2_kernel(EncAttnArgs a,
   softmax_row16(sc, kk_end);
   f32x16 o[2];
   mfma_pv_regs(sc, v0, v1, kk_end, o);
-  unsigned long long bad = 0ull;
-  const size_t obase = row0 * inner + h * DKV;
   store_o_tile_v2(o, Os, lane, nrow, inner, a.out ? a.out + obase : nullptr, a.out_h ? a.out_h + obase : nullptr, a.o_ps, bad);
   if (bad != 0ull && a.sat && lane == 0) *a.sat = 1u;
 }
@@ -901,11 +908,11 @@ static hipError_t run_cross_attn(const AttnLaunch& p, const DecCrossAttnArgs& a,
 }
 
 hipError_t launch_tail_cross_attn(const DecCrossAttnArgs& a, hipStream_t s) {
-  return run_cross_attn(plan_tail_cross_attn(CrossAttnIn{a.Q, a.B, a.H, a.Lq, a.dkv}, g_attn_tuning), a, s);
+  return run_cross_attn(plan_tail_cross_attn(cross_attn_in(a), g_attn_tuning), a, s);
 }
 
 hipError_t launch_step_cross_attn(const DecCrossAttnArgs& a, hipStream_t s) {
-  return run_cross_attn(plan_step_cross_attn(CrossAttnIn{a.Q, a.B, a.H, a.Lq, a.dkv}, g_attn_tuning), a, s);
+  return run_cross_attn(plan_step_cross_attn(cross_attn_in(a), g_attn_tuning), a, s);
 }
 
 // Self-attention of the training forward (teacher-forced decoder: causal, bias by distance i - j; encoder: key padding
@@ -1495,7 +1502,7 @@ hipError_t init_attn_mfma_attributes() {
 }
 
 hipError_t launch_tail_self_attn(const TailSelfAttnArgs& a, hipStream_t s) {
-  const AttnLaunch p = plan_tail_self_attn(TailSelfAttnIn{a.nseq_cap, a.B, a.H, a.T, a.L, a.dkv}, g_attn_tuning);
+  const AttnLaunch p = plan_tail_self_attn(tail_self_attn_in(a), g_attn_tuning);
   const dim3 grid(p.grid_x), blk(p.block);
   switch (p.kernel) {
     case ATTN_TAIL_SELF_VALU128: hipLaunchKernelGGL(tail_self_attn_kernel<128>, grid, blk, p.smem, s, a); break;

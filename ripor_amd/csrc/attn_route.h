@@ -58,6 +58,9 @@ enum AttnKernel {
   RPR_ATTN_KERNELS(X)
 #undef X
 };
+#define X(n) +1
+constexpr int ATTN_KERNEL_COUNT = 0 RPR_ATTN_KERNELS(X);
+#undef X
 inline const char* attn_kernel_name(int k) {
   static const char* const names[] = {
 #define X(n) #n,

@@ -447,6 +447,13 @@ struct EncAttnArgs {
                            //   forward; the search encoder keeps the summation order of enc_attn_kernel)
   int dkv = 0;             // head dim (0 = 64); 128 (t5-3b) takes enc_attn_kernel<128>
 };
+// what the planner is asked for these arguments (the launcher and the test hook rpr_op_enc_attn ask the same question)
+inline EncAttnIn enc_attn_in(const EncAttnArgs& a) {
+  EncAttnIn in;
+  in.Q = a.Q; in.Lq = a.Lq; in.H = a.H; in.buckets = a.buckets; in.dkv = a.dkv;
+  in.causal = a.causal != 0; in.mask = a.mask != nullptr; in.offs = a.offs != nullptr; in.out_h = a.out_h != nullptr; in.mfma = a.mfma != 0;
+  return in;
+}
 hipError_t launch_enc_attn(const EncAttnArgs& a, hipStream_t s);
 // attn_mfma.hip: runs the plans of launch_enc_attn whose kernels live there (ENC_V2, TRAIN_SELF_MFMA) ...
 hipError_t run_enc_attn_mfma(const AttnLaunch& p, const EncAttnArgs& a, hipStream_t s);
@@ -473,6 +480,7 @@ struct DecSelfAttnArgs {
   unsigned b_magic = 0, h_magic = 0;   // set by the launcher: reciprocals of B and H (kernel_utils.h udiv_magic)
   int dkv = 0;             // head dim (0 = 64); 128 (t5-3b) takes the generic kernel dec_attn_kernel<true, 128>
 };
+inline DecSelfAttnIn dec_self_attn_in(const DecSelfAttnArgs& a) { return DecSelfAttnIn{a.Q, a.B, a.H, a.t, a.dkv}; }
 hipError_t launch_dec_self_attn(const DecSelfAttnArgs& a, hipStream_t s);
 
 struct DecCrossAttnArgs {
@@ -491,6 +499,7 @@ struct DecCrossAttnArgs {
   const int* nq_dev;       // nullable: live query count on the device; queries past it are skipped
   int dkv = 0;             // head dim (0 = 64); 128 (t5-3b) takes the generic kernel dec_attn_kernel<false, 128>
 };
+inline CrossAttnIn cross_attn_in(const DecCrossAttnArgs& a) { return CrossAttnIn{a.Q, a.B, a.H, a.Lq, a.dkv}; }
 hipError_t launch_dec_cross_attn(const DecCrossAttnArgs& a, hipStream_t s);
 // t5_kernels.hip: runs a block cross-attention plan (CROSS_BLOCK64 / 128, CROSS_WAVE128), also for the tail and step launchers
 hipError_t run_cross_block(const AttnLaunch& p, const DecCrossAttnArgs& a, hipStream_t s);
@@ -676,6 +685,7 @@ struct TailSelfAttnArgs {
   int dkv = 0;               // head dim (0 = 64); 128 (t5-3b) takes the VALU kernel tail_self_attn_kernel<128>
   const int32_t* kvq = nullptr;   // tail query -> the stage query whose cache it reads (null = flist: no spare entries)
 };
+inline TailSelfAttnIn tail_self_attn_in(const TailSelfAttnArgs& a) { return TailSelfAttnIn{a.nseq_cap, a.B, a.H, a.T, a.L, a.dkv}; }
 hipError_t launch_tail_self_attn(const TailSelfAttnArgs& a, hipStream_t s);
 // cross-attention of the tail rows (a.B = rows per query): fp32-MFMA tiles for Lq <= 64, else the block kernel
 hipError_t launch_tail_cross_attn(const DecCrossAttnArgs& a, hipStream_t s);

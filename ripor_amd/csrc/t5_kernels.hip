@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(EncAttnArgs a) {
     for (int c = 0; c < MAX_LQ / 64; ++c) {
       if (c >= nchunk) break;
       const int j = c * 64 + lane;
-      if (j < nrow) P[j] = sc[c] / sum;
+      if (j < nrow) P[j] = sum > 0.f ? sc[c] / sum : 0.f;   // no attended key (an empty query, padded layout): zeros, like every other attention kernel
     }
     __builtin_amdgcn_wave_barrier();
     float o[NV];
@@ -350,10 +350,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(EncAttnArgs a) {
 }
 
 hipError_t launch_enc_attn(const EncAttnArgs& a, hipStream_t s) {
-  EncAttnIn in;
-  in.Q = a.Q; in.Lq = a.Lq; in.H = a.H; in.buckets = a.buckets; in.dkv = a.dkv;
-  in.causal = a.causal != 0; in.mask = a.mask != nullptr; in.offs = a.offs != nullptr; in.out_h = a.out_h != nullptr; in.mfma = a.mfma != 0;
-  const AttnLaunch p = plan_enc_attn(in, g_attn_tuning);
+  const AttnLaunch p = plan_enc_attn(enc_attn_in(a), g_attn_tuning);
   const dim3 grid(p.grid_x), blk(p.block);
   switch (p.kernel) {
     case ATTN_ENC_VALU64: hipLaunchKernelGGL(enc_attn_kernel<64>, grid, blk, p.smem, s, a); break;
@@ -599,7 +596,7 @@ __global__ __launch_bounds__(256) void dec_self_attn_fast_kernel(DecSelfAttnArgs
 hipError_t launch_dec_self_attn(const DecSelfAttnArgs& a_in, hipStream_t s) {
   DecSelfAttnArgs a = a_in;
   a.b_magic = div_magic(a.B); a.h_magic = div_magic(a.H);
-  const AttnLaunch p = plan_dec_self_attn(DecSelfAttnIn{a.Q, a.B, a.H, a.t, a.dkv});
+  const AttnLaunch p = plan_dec_self_attn(dec_self_attn_in(a));
   const dim3 grid(p.grid_x), blk(p.block);
   switch (p.kernel) {
     case ATTN_SELF_FAST2: hipLaunchKernelGGL(dec_self_attn_fast_kernel<2>, grid, blk, 0, s, a); break;
@@ -790,7 +787,7 @@ hipError_t run_cross_block(const AttnLaunch& p, const DecCrossAttnArgs& a_in, hi
 }
 
 hipError_t launch_dec_cross_attn(const DecCrossAttnArgs& a, hipStream_t s) {
-  return run_cross_block(plan_cross_block(CrossAttnIn{a.Q, a.B, a.H, a.Lq, a.dkv}), a, s);
+  return run_cross_block(plan_cross_block(cross_attn_in(a)), a, s);
 }
 
 // zeroes the per-site row sums of a pass (a kernel node rather than a memset node: memset nodes captured into the

@@ -229,6 +229,44 @@ class Context:
                                       eps, _stream_ptr(x.device)), "rpr_op_rmsnorm")
         return out
 
+    # -- attention test hooks (rpr_op_*_attn): one launch of a search's attention site into the caller's buffers; every
+    #    method returns the name of the kernel the site's planner chose. Tensors are device tensors (None = NULL pointer).
+    def _attn_op(self, fn_name: str, op, dev) -> str:
+        k = C.c_int32(-1)
+        check(getattr(self.lib, fn_name)(self.handle, C.byref(op), C.byref(k), _stream_ptr(dev)), fn_name)
+        return self.lib.rpr_attn_kernel_name(int(k.value)).decode()
+
+    def enc_attn(self, qkv, mask, rel_bias, Q, Lq, H, dkv=64, num_buckets=32, max_distance=128, causal=False, mfma=False,
+                 offs=None, lens=None, out=None, out_planes=None, plane_stride=0) -> str:
+        p = lambda t: t.data_ptr() if t is not None else None
+        op = _lib.EncAttnOp(p(qkv), p(mask), p(rel_bias), p(offs), p(lens), p(out), p(out_planes), int(plane_stride),
+                            num_buckets, max_distance, Q, Lq, H, dkv, 1 if causal else 0, 1 if mfma else 0)
+        return self._attn_op("rpr_op_enc_attn", op, qkv.device)
+
+    def dec_self_attn(self, q, kcache, vcache, strides, anc, rel_bias, Q, B, H, t, dkv=64, num_buckets=32, max_distance=128,
+                      nq_dev=None, out=None, out_planes=None, plane_stride=0) -> str:
+        """strides = (q_stride, h_stride, pos_stride, slot_stride) in floats; anc: uint16 rows as int16 storage [Q * B, anc_ld]."""
+        p = lambda t_: t_.data_ptr() if t_ is not None else None
+        op = _lib.DecSelfAttnOp(p(q), p(kcache), p(vcache), p(anc), p(rel_bias), p(nq_dev), p(out), p(out_planes), int(plane_stride),
+                                *[int(x) for x in strides], anc.shape[1], num_buckets, max_distance, Q, B, H, t, dkv)
+        return self._attn_op("rpr_op_dec_self_attn", op, q.device)
+
+    def cross_attn(self, site, q, xk, xv, xld, mask, Q, B, H, Lq, dkv=64, offs=None, nq_dev=None, out=None, out_planes=None,
+                   plane_stride=0) -> str:
+        """site: _lib.CROSS_SITE_BLOCK / _STEP / _TAIL."""
+        p = lambda t: t.data_ptr() if t is not None else None
+        op = _lib.CrossAttnOp(p(q), p(xk), p(xv), p(mask), p(offs), p(nq_dev), p(out), p(out_planes), int(plane_stride),
+                              int(site), xld, Q, B, H, Lq, dkv)
+        return self._attn_op("rpr_op_cross_attn", op, q.device)
+
+    def tail_self_attn(self, qkv, kcache, vcache, strides, anc, flist, kvq, nseq_dev, rel_bias, nseq_cap, B, H, T, L, dkv=64,
+                       num_buckets=32, max_distance=128, out=None, out_planes=None, plane_stride=0) -> str:
+        p = lambda t: t.data_ptr() if t is not None else None
+        op = _lib.TailSelfAttnOp(p(qkv), p(kcache), p(vcache), p(anc), p(flist), p(kvq), p(nseq_dev), p(rel_bias), p(out), p(out_planes),
+                                 int(plane_stride), *[int(x) for x in strides], anc.shape[1], num_buckets, max_distance, nseq_cap,
+                                 B, H, T, L, dkv)
+        return self._attn_op("rpr_op_tail_self_attn", op, qkv.device)
+
 
 class StatusTicket:
     """Status words of a ctx as of one point of a stream (``Context.status_async``)."""

@@ -36,6 +36,32 @@ def test_struct_layout_matches_header():
     assert C.sizeof(_lib.DebugTaps) == 6 * C.sizeof(C.c_void_p)
     # 12 int32 + float (52 bytes, padded to 56) + 9 + 15 pointers
     assert C.sizeof(_lib.ModelDesc) == 56 + 24 * 8
+    # the attention test hooks' descriptors: pointers, then int64 strides, then int32 (padded to 8 bytes)
+    assert C.sizeof(_lib.EncAttnOp) == 7 * 8 + 1 * 8 + 8 * 4
+    assert C.sizeof(_lib.DecSelfAttnOp) == 8 * 8 + 5 * 8 + 8 * 4
+    assert C.sizeof(_lib.CrossAttnOp) == 8 * 8 + 1 * 8 + 7 * 4 + 4
+    assert C.sizeof(_lib.TailSelfAttnOp) == 10 * 8 + 5 * 8 + 9 * 4 + 4
+
+
+def test_attention_hook_descriptors_match_header():
+    """Field names and order of the four rpr_*_attn_op structs in include/ripor_hip.h against the ctypes mirrors."""
+    from ripor_amd import _lib
+    hdr = open(os.path.join(REPO, "include", "ripor_hip.h")).read()
+    for cname, cls in (("rpr_enc_attn_op", _lib.EncAttnOp), ("rpr_dec_self_attn_op", _lib.DecSelfAttnOp),
+                       ("rpr_cross_attn_op", _lib.CrossAttnOp), ("rpr_tail_self_attn_op", _lib.TailSelfAttnOp)):
+        body = hdr[hdr.index("typedef struct " + cname + " {"):hdr.index("} " + cname + ";")].split("{", 1)[1]
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if not decl:
+                continue
+            typ = "ptr" if "*" in decl else "i64" if decl.startswith("int64_t") else "i32"
+            assert typ != "i32" or decl.startswith("int32_t"), decl
+            names = decl.replace("*", " ").split(None, 2 if decl.startswith("const") else 1)[-1]
+            fields += [(n.strip(), typ) for n in names.split(",")]
+        want = [(n, {C.c_void_p: "ptr", C.c_int64: "i64", C.c_int32: "i32"}[t]) for n, t in cls._fields_]
+        assert fields == want, (cname, fields, want)
 
 
 def test_rel_bucket_table_matches_torch_expression(lib):
