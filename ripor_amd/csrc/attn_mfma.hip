@@ -1461,27 +1461,27 @@ __global__ __launch_bounds__(256, 2) void attn_drop_fwd_tiled_kernel(AttnTiledAr
   }
 }
 
+// the tiled plans of the training launchers (train_kernels.hip); the shapes were checked by the planner (attn_route.h)
 hipError_t run_attn_bwd_tiled(const AttnLaunch& p, const AttnTiledArgs& a, bool drop, hipStream_t s) {
   const dim3 grid(p.grid_x), blk(p.block);
-  if (a.nq < 1 || a.nk < 1 || a.nq > MAX_LQ || a.nk > MAX_LQ || !a.mask) return hipErrorInvalidValue;
-  if (drop && (a.da.L < 1 || a.nq % a.da.L)) return hipErrorInvalidValue;
-  const bool bias = p.kernel == ATTN_TRAIN_SELF_BWD_TILED;
-  if (bias && (a.nq != a.nk || !a.dbias_part)) return hipErrorInvalidValue;
-  if (bias && drop) hipLaunchKernelGGL((attn_bwd_tiled_kernel<true, true>), grid, blk, p.smem, s, a);
-  else if (bias) hipLaunchKernelGGL((attn_bwd_tiled_kernel<true, false>), grid, blk, p.smem, s, a);
-  else if (drop) hipLaunchKernelGGL((attn_bwd_tiled_kernel<false, true>), grid, blk, p.smem, s, a);
-  else hipLaunchKernelGGL((attn_bwd_tiled_kernel<false, false>), grid, blk, p.smem, s, a);
+  switch (p.kernel) {
+    case ATTN_TRAIN_SELF_BWD_TILED:
+      hipLaunchKernelGGL((drop ? attn_bwd_tiled_kernel<true, true> : attn_bwd_tiled_kernel<true, false>), grid, blk, p.smem, s, a);
+      break;
+    case ATTN_TRAIN_CROSS_BWD_TILED:
+      hipLaunchKernelGGL((drop ? attn_bwd_tiled_kernel<false, true> : attn_bwd_tiled_kernel<false, false>), grid, blk, p.smem, s, a);
+      break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
 hipError_t run_attn_drop_fwd_tiled(const AttnLaunch& p, const AttnTiledArgs& a, hipStream_t s) {
   const dim3 grid(p.grid_x), blk(p.block);
-  if (a.nq < 1 || a.nk < 1 || a.nq > MAX_LQ || a.nk > MAX_LQ || !a.mask || a.da.L < 1 || a.nq % a.da.L) return hipErrorInvalidValue;
-  if (p.kernel == ATTN_TRAIN_SELF_DROP_FWD_TILED) {
-    if (a.nq != a.nk) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attn_drop_fwd_tiled_kernel<true>, grid, blk, p.smem, s, a);
-  } else {
-    hipLaunchKernelGGL(attn_drop_fwd_tiled_kernel<false>, grid, blk, p.smem, s, a);
+  switch (p.kernel) {
+    case ATTN_TRAIN_SELF_DROP_FWD_TILED: hipLaunchKernelGGL(attn_drop_fwd_tiled_kernel<true>, grid, blk, p.smem, s, a); break;
+    case ATTN_TRAIN_CROSS_DROP_FWD_TILED: hipLaunchKernelGGL(attn_drop_fwd_tiled_kernel<false>, grid, blk, p.smem, s, a); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

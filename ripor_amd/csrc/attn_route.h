@@ -1,7 +1,12 @@
 // Route policy of the attention launches (t5_kernels.hip, attn_mfma.hip, train_kernels.hip): which kernel instantiation a
-// shape takes, with which grid, block, dynamic LDS and scalar arguments. Plain host arithmetic — no HIP types, so
-// tests/test_attn_route.py compiles it with the host compiler and checks the shape -> kernel table without a GPU. Every
-// launch_* of an attention site fills the site's input struct, asks its planner and runs one switch over AttnLaunch::kernel.
+// shape takes, with which grid, block, dynamic LDS and scalar arguments. Plain host arithmetic — no HIP types, so the tests
+// compile it with the host compiler and check the shape -> kernel table without a GPU (tests/test_attn_route.py the search
+// sites, tests/test_attn_route_train.py the training step's). Every launch_* of an attention site fills the site's input struct,
+// asks its planner and runs one switch over AttnLaunch::kernel:
+//   search         launch_enc_attn, launch_dec_self_attn, launch_dec_cross_attn, launch_step_cross_attn, launch_tail_self_attn,
+//                  launch_tail_cross_attn
+//   training step  launch_enc_attn (mfma), launch_self_attn_bwd, launch_cross_attn_bwd, launch_self_attn_drop_fwd,
+//                  launch_cross_attn_drop_fwd; train_setup admits a step by the same planners (train_attn_admitted)
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -51,7 +56,11 @@ struct AttnTuning {
   /* training self-attention backward: the fp32-MFMA tile, self_attn_bwd_kernel<., 64>, <., 128> */                     \
   X(TRAIN_BWD_MFMA) X(TRAIN_BWD_VALU) X(TRAIN_BWD_VALU128)                                                              \
   /* training attention beyond the one-head LDS carve: attn_bwd_tiled_kernel<bias>, attn_drop_fwd_tiled_kernel<bias> */ \
-  X(TRAIN_SELF_BWD_TILED) X(TRAIN_CROSS_BWD_TILED) X(TRAIN_SELF_DROP_FWD_TILED) X(TRAIN_CROSS_DROP_FWD_TILED)
+  X(TRAIN_SELF_BWD_TILED) X(TRAIN_CROSS_BWD_TILED) X(TRAIN_SELF_DROP_FWD_TILED) X(TRAIN_CROSS_DROP_FWD_TILED)           \
+  /* training attention that holds a head in LDS: cross_attn_bwd_kernel<., 64>, <., 128>, self_attn_drop_fwd_kernel<64>, <128>, */ \
+  /* cross_attn_drop_fwd_kernel<64>, <128> (appended: the ids above keep their values) */                               \
+  X(TRAIN_CROSS_BWD) X(TRAIN_CROSS_BWD128) X(TRAIN_SELF_DROP_FWD) X(TRAIN_SELF_DROP_FWD128)                              \
+  X(TRAIN_CROSS_DROP_FWD) X(TRAIN_CROSS_DROP_FWD128)
 
 enum AttnKernel {
 #define X(n) ATTN_##n,
@@ -243,7 +252,8 @@ inline AttnLaunch plan_tail_self_attn(const TailSelfAttnIn& a, const AttnTuning&
                    : attn_launch(ATTN_TAIL_SELF_G1_NKT2, grid, 4 * (64 * 64 + 64 + 32 * 64) * sizeof(float));
 }
 
-// ---- training self-attention backward (launch_self_attn_bwd) ----------------------------------------------------------------
+// ---- the attention of the training step: the pieces (the planners of its four sites follow) ---------------------------------
+// the resident plan of the self-attention backward without dropout
 struct SelfAttnBwdIn { int S = 0, Ls = 0, H = 0, buckets = 0, dkv = DKV; };
 // LDS of the VALU kernel (self_attn_bwd_kernel: rows padded to DKV + 1 floats); the training step is admitted by it whatever
 // the kernel (train_api.hip). buckets <= 64: fixed slot. 128-dim heads (t5-3b) go through the same carve 64 columns at a time
@@ -265,8 +275,8 @@ inline AttnLaunch plan_self_attn_bwd(const SelfAttnBwdIn& a) {
 }
 
 // ---- training attention beyond the one-head carve (attn_mfma.hip: attn_bwd_tiled_kernel, attn_drop_fwd_tiled_kernel) ---------
-// 64-dim heads, up to MAX_LQ query rows and MAX_LQ keys per (sequence, head), bidirectional; the launchers of train_kernels.hip
-// come here only when the plan above (self-attention) or the resident carve below (cross-attention) refuses the shape.
+// 64-dim heads, up to MAX_LQ query rows and MAX_LQ keys per (sequence, head), bidirectional; the planners of the sites come here
+// only when the plan above (self-attention) or the resident carve below (cross-attention) refuses the shape.
 // One block of four waves per (sequence, head); queries and keys in 32-row tiles, nothing of the head resident:
 //   per wave    two 32 x 64 strips (the tile pair of the moment: K | V, then Q | dO)       4096 floats
 //               backward with a relative bias: its query tile's 2 MAX_LQ diagonals of dS     512
@@ -292,8 +302,7 @@ inline AttnLaunch plan_self_attn_drop_fwd_tiled(const SelfAttnBwdIn& a) {
 }
 // cross-attention of the training step: n = docs x L decoder rows of a query against its Lq encoder keys
 struct CrossAttnBwdIn { int bz = 0, n = 0, Lq = 0, H = 0, dkv = DKV; };
-// the carve of cross_attn_bwd_kernel / cross_attn_drop_fwd_kernel (train_kernels.hip: cross_attn_bwd_smem restates it): q, dO
-// [n][65], K, V [Lq][65], P, dS [n][Lq + 1], key mask [Lq]
+// the carve of cross_attn_bwd_kernel / cross_attn_drop_fwd_kernel: q, dO [n][65], K, V [Lq][65], P, dS [n][Lq + 1], key mask [Lq]
 inline size_t cross_attn_bwd_carve(int n, int Lq) {
   return ((size_t)2 * n * (DKV + 1) + 2 * (size_t)Lq * (DKV + 1) + 2 * (size_t)n * (Lq + 1) + (size_t)Lq) * sizeof(float);
 }
@@ -303,6 +312,83 @@ inline AttnLaunch plan_cross_attn_bwd_tiled(const CrossAttnBwdIn& a) {
 }
 inline AttnLaunch plan_cross_attn_drop_fwd_tiled(const CrossAttnBwdIn& a) {
   return plan_attn_tiled(ATTN_TRAIN_CROSS_DROP_FWD_TILED, a.bz, a.n, a.Lq, a.H, 0, a.dkv, false, false);
+}
+
+
+// ---- the four attention sites of the training step (train_kernels.hip) -------------------------------------------------------
+// The self- and the cross-attention backward (launch_self_attn_bwd, launch_cross_attn_bwd) and, with dropout, the forward of both
+// (launch_self_attn_drop_fwd, launch_cross_attn_drop_fwd; without dropout the forward is launch_enc_attn / launch_dec_cross_attn
+// above). Each has a resident route, one block per (sequence or query, head) that holds the whole head in LDS, and beyond that
+// carve, for 64-dim heads, the 32-row tiles. The template booleans of a kernel (DROP, CAUSAL, BIAS) are read from the input struct
+// by the launcher's switch and have no names here.
+struct TrainSelfAttnIn {
+  int S = 0, Ls = 0, H = 0, buckets = 0, dkv = DKV;
+  bool causal = false, mask = false;   // mask: the key-mask pointer is set
+  bool drop = false;                   // backward: the probabilities were dropped out (the drop-forward always drops)
+  int drop_L = 0;                      // DropAttn::L, positions per sequence of the mask's coordinates
+};
+struct TrainCrossAttnIn {
+  int bz = 0, n = 0, Lq = 0, H = 0, dkv = DKV;
+  bool mask = false, drop = false;
+  int drop_L = 0;
+};
+inline SelfAttnBwdIn self_shape(const TrainSelfAttnIn& a) { return SelfAttnBwdIn{a.S, a.Ls, a.H, a.buckets, a.dkv}; }
+inline CrossAttnBwdIn cross_shape(const TrainCrossAttnIn& a) { return CrossAttnBwdIn{a.bz, a.n, a.Lq, a.H, a.dkv}; }
+inline bool train_dkv_ok(int dkv) { return dkv == DKV || dkv == 128; }
+// what the tiles ask beyond their shape: a key mask and, with dropout, query rows that are whole sequences of drop_L positions (the
+// coordinates the mask is drawn by)
+inline AttnLaunch tiled_if(const AttnLaunch& p, bool mask, bool drop, int drop_L, int nq) {
+  return !mask || (drop && (drop_L < 1 || nq % drop_L)) ? attn_invalid() : p;
+}
+
+// Self-attention backward: the resident plan; with dropped-out probabilities the VALU kernel in place of the MFMA tile, which knows
+// no mask; where the carve refuses a bidirectional launch (Ls > 91), the tiles.
+inline AttnLaunch plan_train_self_attn_bwd(const TrainSelfAttnIn& a) {
+  const AttnLaunch p = plan_self_attn_bwd(self_shape(a));
+  const size_t smem = self_attn_bwd_smem(a.Ls, a.buckets);
+  if (p.invalid) return a.causal || smem <= LDS_MAX ? p : tiled_if(plan_self_attn_bwd_tiled(self_shape(a)), a.mask, a.drop, a.drop_L, a.Ls);
+  return a.drop && p.kernel == ATTN_TRAIN_BWD_MFMA ? attn_launch(ATTN_TRAIN_BWD_VALU, (long)a.S * a.H, smem) : p;
+}
+
+// Self-attention forward with dropped-out probabilities. The resident kernel asks for the backward's carve (the step was admitted
+// by it, and the request sets how many blocks share a CU) and draws its mask whatever drop_L is.
+inline AttnLaunch plan_train_self_attn_drop_fwd(const TrainSelfAttnIn& a) {
+  const size_t smem = self_attn_bwd_smem(a.Ls, a.buckets);
+  if (smem > LDS_MAX && a.dkv == DKV && !a.causal && a.mask) return tiled_if(plan_self_attn_drop_fwd_tiled(self_shape(a)), a.mask, true, a.drop_L, a.Ls);
+  if (smem > LDS_MAX || a.buckets > 64 || a.Ls < 1 || a.Ls > MAX_LQ || (!a.causal && !a.mask) || !train_dkv_ok(a.dkv)) return attn_invalid();
+  return attn_launch(a.dkv == 128 ? ATTN_TRAIN_SELF_DROP_FWD128 : ATTN_TRAIN_SELF_DROP_FWD, (long)a.S * a.H, smem);
+}
+
+// Cross-attention, backward (fwd = false) or forward with dropped-out probabilities. Row r of a query is position r % drop_L of its
+// decoder sequence r / drop_L; the resident backward's lanes carry the keep bits of 32 keys each, of MAX_LQ keys at most.
+inline AttnLaunch plan_train_cross_attn(const TrainCrossAttnIn& a, bool fwd) {
+  const size_t smem = cross_attn_bwd_carve(a.n, a.Lq);
+  const bool drop = fwd || a.drop;
+  if (smem > LDS_MAX)
+    return a.dkv != DKV ? attn_invalid()
+                        : tiled_if(fwd ? plan_cross_attn_drop_fwd_tiled(cross_shape(a)) : plan_cross_attn_bwd_tiled(cross_shape(a)), a.mask, drop,
+                                   a.drop_L, a.n);
+  if (!train_dkv_ok(a.dkv) || (drop && (a.drop_L < 1 || a.n % a.drop_L)) || (!fwd && drop && a.Lq > MAX_LQ)) return attn_invalid();
+  const int k = fwd ? (a.dkv == 128 ? ATTN_TRAIN_CROSS_DROP_FWD128 : ATTN_TRAIN_CROSS_DROP_FWD)
+                    : (a.dkv == 128 ? ATTN_TRAIN_CROSS_BWD128 : ATTN_TRAIN_CROSS_BWD);
+  return attn_launch(k, (long)a.bz * a.H, smem);
+}
+inline AttnLaunch plan_train_cross_attn_bwd(const TrainCrossAttnIn& a) { return plan_train_cross_attn(a, false); }
+inline AttnLaunch plan_train_cross_attn_drop_fwd(const TrainCrossAttnIn& a) { return plan_train_cross_attn(a, true); }
+
+// A training step (train_api.hip: train_setup) is admitted when every attention launch it will make has a plan, with and without
+// dropout: the encoder's self-attention over bz queries of Lq tokens (bidirectional, key mask), the decoder's over bz x docs
+// sequences of L codes (causal) and the cross-attention of a query's docs x L rows against its Lq keys.
+inline bool train_attn_admitted(int bz, int Lq, int L, int docs, int H, int buckets, int dkv) {
+  for (const bool drop : {false, true}) {
+    const TrainSelfAttnIn enc{bz, Lq, H, buckets, dkv, false, true, drop, Lq}, dec{bz * docs, L, H, buckets, dkv, true, false, drop, L};
+    const TrainCrossAttnIn cross{bz, docs * L, Lq, H, dkv, true, drop, L};
+    if (plan_train_self_attn_bwd(enc).invalid || plan_train_self_attn_bwd(dec).invalid || plan_train_cross_attn_bwd(cross).invalid) return false;
+    if (drop && (plan_train_self_attn_drop_fwd(enc).invalid || plan_train_self_attn_drop_fwd(dec).invalid ||
+                 plan_train_cross_attn_drop_fwd(cross).invalid))
+      return false;
+  }
+  return true;
 }
 
 }  // namespace rpr

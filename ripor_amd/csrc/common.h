@@ -774,7 +774,6 @@ hipError_t launch_colsum_multi(const ColsumSites& p, int d, hipStream_t s);
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
                                 hipStream_t s, const DropAttn* drop = nullptr, int dkv = DKV);
-size_t cross_attn_bwd_smem(int n, int Lq);
 hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, const float* dO,
                                  float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s,
                                  const DropAttn* drop = nullptr, int dkv = DKV);

@@ -879,12 +879,9 @@ int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int
   RPR_HIP(hipSetDevice(c->device));
   const auto& d = m->d;
   D = train_dims(d, bz, Lq, L, docs, m->gated());
-  // 64-dim heads beyond the carve of a whole head go on in tiles (attn_route.h: plan_*_tiled; L <= 64 always fits the decoder's
-  // causal self-attention, the docs L <= 128 decoder rows of a query the tiles); 128-dim heads stop at the carve
-  const bool tiled_ok = d.d_kv == DKV && !plan_cross_attn_bwd_tiled(CrossAttnBwdIn{bz, docs * L, Lq, d.num_heads, d.d_kv}).invalid &&
-                        !plan_self_attn_bwd_tiled(SelfAttnBwdIn{bz, Lq, d.num_heads, d.rel_buckets, d.d_kv}).invalid;
-  RPR_REQUIRE(tiled_ok ||
-              (self_attn_bwd_smem(std::max(L, Lq), d.rel_buckets) <= 160 * 1024 && cross_attn_bwd_smem(docs * L, Lq) <= 160 * 1024),
+  // every attention launch of the step has a plan (attn_route.h, the training sites): 64-dim heads beyond the carve of a whole head
+  // go on in tiles, 128-dim heads stop at the carve
+  RPR_REQUIRE(train_attn_admitted(bz, Lq, L, docs, d.num_heads, d.rel_buckets, d.d_kv),
               "sequence lengths beyond the 160 KB of LDS the attention backward holds a head in: self-attention max(L, Lq) <= 91, "
               "cross-attention 130 (docs L + Lq) + 2 docs L (Lq + 1) + Lq floats <= 40960 (the same for 64- and 128-dim heads)");
   int e = alloc_train(c, m, D);

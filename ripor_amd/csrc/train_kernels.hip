@@ -633,51 +633,37 @@ __global__ __launch_bounds__(512) void bias_reduce_kernel(const float* __restric
 hipError_t launch_self_attn_bwd(const float* qkv, const float* dO, const int32_t* mask, const float* rel_bias, const int32_t* bucket,
                                 float* dqkv, float* dbias_part, float* dbias, int S, int Ls, int H, int buckets, int causal,
                                 hipStream_t s, const DropAttn* drop, int dkv) {
-  const AttnLaunch p = plan_self_attn_bwd(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
-  if (p.invalid) {
-    // beyond the carve that holds a head (Ls > 91): 64-dim bidirectional heads go on in tiles (attn_mfma.hip), with or without
-    // the dropout mask; everything else stays refused
-    const AttnLaunch pt = plan_self_attn_bwd_tiled(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
-    if (pt.invalid || causal || self_attn_bwd_smem(Ls, buckets) <= LDS_MAX) return hipErrorInvalidValue;
-    const int inner = H * DKV;
-    AttnTiledArgs a{};
-    a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner; a.dO = dO;
-    a.q_ld = a.kv_ld = 3 * inner; a.do_ld = inner;
-    a.dq = dqkv; a.dk = dqkv + inner; a.dv = dqkv + 2 * inner; a.dq_ld = a.dkv_ld = 3 * inner;
-    a.mask = mask; a.rel_bias = rel_bias; a.bucket = bucket; a.dbias_part = dbias_part; a.buckets = buckets;
-    a.nq = a.nk = Ls; a.H = H;
-    if (drop) a.da = *drop;
-    const hipError_t e = run_attn_bwd_tiled(pt, a, drop != nullptr, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
-    return hipGetLastError();
-  }
-  if (drop) {   // dropped-out probabilities: the VALU kernel at every length (the MFMA plan knows no mask)
-    const size_t smem = self_attn_bwd_smem(Ls, buckets);
-    if (smem > 160 * 1024 || Ls > 256) return hipErrorInvalidValue;   // (a lane carries the keep bits of <= 32 keys)
-    if (dkv == 128)
-      hipLaunchKernelGGL((self_attn_bwd_kernel<true, 128>), dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv,
-                         dbias_part, S, Ls, H, buckets, causal, *drop);
-    else
-      hipLaunchKernelGGL(self_attn_bwd_kernel<true>, dim3(S * H), dim3(256), smem, s, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S,
-                         Ls, H, buckets, causal, *drop);
-    hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
-    return hipGetLastError();
-  }
-  switch (p.kernel) {
+  const AttnLaunch p =
+      plan_train_self_attn_bwd(TrainSelfAttnIn{S, Ls, H, buckets, dkv, causal != 0, mask != nullptr, drop != nullptr, drop ? drop->L : 0});
+  const dim3 grid(p.grid_x), blk(p.block);
+  const DropAttn da = drop ? *drop : DropAttn{};
+  switch (p.kernel) {   // a refused shape has no kernel
     case ATTN_TRAIN_BWD_MFMA: {   // attn_mfma.hip
       const hipError_t e = run_self_attn_bwd_mfma(p, qkv, dO, mask, rel_bias, bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, s);
       if (e != hipSuccess) return e;
       break;
     }
     case ATTN_TRAIN_BWD_VALU:
-      hipLaunchKernelGGL(self_attn_bwd_kernel<false>, dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket, dqkv,
-                         dbias_part, S, Ls, H, buckets, causal, DropAttn{});
+      hipLaunchKernelGGL((drop ? self_attn_bwd_kernel<true, DKV> : self_attn_bwd_kernel<false, DKV>), grid, blk, p.smem, s, qkv, dO, mask, rel_bias,
+                         bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, da);
       break;
     case ATTN_TRAIN_BWD_VALU128:
-      hipLaunchKernelGGL((self_attn_bwd_kernel<false, 128>), dim3(p.grid_x), dim3(p.block), p.smem, s, qkv, dO, mask, rel_bias, bucket,
-                         dqkv, dbias_part, S, Ls, H, buckets, causal, DropAttn{});
+      hipLaunchKernelGGL((drop ? self_attn_bwd_kernel<true, 128> : self_attn_bwd_kernel<false, 128>), grid, blk, p.smem, s, qkv, dO, mask, rel_bias,
+                         bucket, dqkv, dbias_part, S, Ls, H, buckets, causal, da);
       break;
+    case ATTN_TRAIN_SELF_BWD_TILED: {   // attn_mfma.hip: beyond the carve that holds a head (Ls > 91)
+      if (!dbias_part) return hipErrorInvalidValue;
+      const int inner = H * DKV;
+      AttnTiledArgs a{};
+      a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner; a.dO = dO;
+      a.q_ld = a.kv_ld = 3 * inner; a.do_ld = inner;
+      a.dq = dqkv; a.dk = dqkv + inner; a.dv = dqkv + 2 * inner; a.dq_ld = a.dkv_ld = 3 * inner;
+      a.mask = mask; a.rel_bias = rel_bias; a.bucket = bucket; a.dbias_part = dbias_part; a.buckets = buckets;
+      a.nq = a.nk = Ls; a.H = H; a.da = da;
+      const hipError_t e = run_attn_bwd_tiled(p, a, drop != nullptr, s);
+      if (e != hipSuccess) return e;
+      break;
+    }
     default: return hipErrorInvalidValue;
   }
   hipLaunchKernelGGL(bias_reduce_kernel, dim3(H), dim3(512), 0, s, dbias_part, dbias, S, H, buckets);
@@ -774,41 +760,32 @@ __global__ __launch_bounds__(256) void cross_attn_bwd_kernel(const float* __rest
   }
 }
 
-size_t cross_attn_bwd_smem(int n, int Lq) {
-  return ((size_t)2 * n * AST + 2 * (size_t)Lq * AST + 2 * (size_t)n * (Lq + 1) + (size_t)Lq) * sizeof(float);
-}
-
 hipError_t launch_cross_attn_bwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, const float* dO,
                                  float* dq, float* dxk, float* dxv, int bz, int n, int Lq, int H, hipStream_t s, const DropAttn* drop,
                                  int dkv) {
-  const size_t smem = cross_attn_bwd_smem(n, Lq);   // whatever the head dim: 128-dim heads go through the carve in two halves
-  if (smem > 160 * 1024 && dkv == DKV) {   // the query's rows and keys do not fit a CU: in tiles (attn_mfma.hip)
-    const AttnLaunch pt = plan_cross_attn_bwd_tiled(CrossAttnBwdIn{bz, n, Lq, H, dkv});
-    if (pt.invalid) return hipErrorInvalidValue;
-    AttnTiledArgs a{};
-    a.q = q; a.k = xk; a.v = xv; a.dO = dO;
-    a.q_ld = a.do_ld = a.dq_ld = H * DKV; a.kv_ld = a.dkv_ld = xld;
-    a.dq = dq; a.dk = dxk; a.dv = dxv;
-    a.mask = mask; a.nq = n; a.nk = Lq; a.H = H;
-    if (drop) a.da = *drop;
-    return run_attn_bwd_tiled(pt, a, drop != nullptr, s);
-  }
-  if (smem > 160 * 1024 || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
-  // (an fp32-MFMA version — one wave per (query, head), dK / dV accumulated over the row tiles in the matrix cores — measured
-  // 91 us against this kernel's 88: one wave per SIMD by its 33 KB of strips; removed)
-  if (drop) {
-    if (drop->L < 1 || n % drop->L || Lq > 256) return hipErrorInvalidValue;
-    if (dkv == 128)
-      hipLaunchKernelGGL((cross_attn_bwd_kernel<true, 128>), dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq,
-                         H, *drop);
-    else
-      hipLaunchKernelGGL(cross_attn_bwd_kernel<true>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H, *drop);
-  } else if (dkv == 128) {
-    hipLaunchKernelGGL((cross_attn_bwd_kernel<false, 128>), dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq,
-                       H, DropAttn{});
-  } else {
-    hipLaunchKernelGGL(cross_attn_bwd_kernel<false>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, dO, dq, dxk, dxv, n, Lq, H,
-                       DropAttn{});
+  const AttnLaunch p = plan_train_cross_attn_bwd(TrainCrossAttnIn{bz, n, Lq, H, dkv, mask != nullptr, drop != nullptr, drop ? drop->L : 0});
+  const dim3 grid(p.grid_x), blk(p.block);
+  const DropAttn da = drop ? *drop : DropAttn{};
+  // (an fp32-MFMA version of the resident kernel — one wave per (query, head), dK / dV accumulated over the row tiles in the matrix
+  // cores — measured 91 us against this kernel's 88: one wave per SIMD by its 33 KB of strips; removed)
+  switch (p.kernel) {   // a refused shape has no kernel
+    case ATTN_TRAIN_CROSS_BWD:
+      hipLaunchKernelGGL((drop ? cross_attn_bwd_kernel<true, DKV> : cross_attn_bwd_kernel<false, DKV>), grid, blk, p.smem, s, q, xk, xv, xld, mask, dO,
+                         dq, dxk, dxv, n, Lq, H, da);
+      break;
+    case ATTN_TRAIN_CROSS_BWD128:
+      hipLaunchKernelGGL((drop ? cross_attn_bwd_kernel<true, 128> : cross_attn_bwd_kernel<false, 128>), grid, blk, p.smem, s, q, xk, xv, xld, mask, dO,
+                         dq, dxk, dxv, n, Lq, H, da);
+      break;
+    case ATTN_TRAIN_CROSS_BWD_TILED: {   // attn_mfma.hip: the query's rows and keys do not fit a CU
+      AttnTiledArgs a{};
+      a.q = q; a.k = xk; a.v = xv; a.dO = dO;
+      a.q_ld = a.do_ld = a.dq_ld = H * DKV; a.kv_ld = a.dkv_ld = xld;
+      a.dq = dq; a.dk = dxk; a.dv = dxv;
+      a.mask = mask; a.nq = n; a.nk = Lq; a.H = H; a.da = da;
+      return run_attn_bwd_tiled(p, a, drop != nullptr, s);
+    }
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
@@ -970,42 +947,48 @@ __global__ __launch_bounds__(256) void cross_attn_drop_fwd_kernel(const float* _
 
 hipError_t launch_self_attn_drop_fwd(const float* qkv, const int32_t* mask, const float* rel_bias, const int32_t* bucket, float* out,
                                      int S, int Ls, int H, int buckets, int causal, const DropAttn& drop, hipStream_t s, int dkv) {
-  const size_t smem = self_attn_bwd_smem(Ls, buckets);   // (the backward's carve holds this kernel's: the step was admitted by it)
-  if (smem > 160 * 1024 && dkv == DKV && !causal && mask) {   // Ls > 91: in tiles (attn_mfma.hip)
-    const AttnLaunch pt = plan_self_attn_drop_fwd_tiled(SelfAttnBwdIn{S, Ls, H, buckets, dkv});
-    if (pt.invalid) return hipErrorInvalidValue;
-    const int inner = H * DKV;
-    AttnTiledArgs a{};
-    a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner; a.q_ld = a.kv_ld = 3 * inner;
-    a.out = out; a.out_ld = inner;
-    a.mask = mask; a.rel_bias = rel_bias; a.bucket = bucket; a.buckets = buckets;
-    a.nq = a.nk = Ls; a.H = H; a.da = drop;
-    return run_attn_drop_fwd_tiled(pt, a, s);
+  const AttnLaunch p = plan_train_self_attn_drop_fwd(TrainSelfAttnIn{S, Ls, H, buckets, dkv, causal != 0, mask != nullptr, true, drop.L});
+  const dim3 grid(p.grid_x), blk(p.block);
+  switch (p.kernel) {   // a refused shape has no kernel
+    case ATTN_TRAIN_SELF_DROP_FWD:
+      hipLaunchKernelGGL(self_attn_drop_fwd_kernel<DKV>, grid, blk, p.smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets, causal, drop);
+      break;
+    case ATTN_TRAIN_SELF_DROP_FWD128:
+      hipLaunchKernelGGL(self_attn_drop_fwd_kernel<128>, grid, blk, p.smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets, causal, drop);
+      break;
+    case ATTN_TRAIN_SELF_DROP_FWD_TILED: {   // attn_mfma.hip: Ls > 91
+      const int inner = H * DKV;
+      AttnTiledArgs a{};
+      a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner; a.q_ld = a.kv_ld = 3 * inner;
+      a.out = out; a.out_ld = inner;
+      a.mask = mask; a.rel_bias = rel_bias; a.bucket = bucket; a.buckets = buckets;
+      a.nq = a.nk = Ls; a.H = H; a.da = drop;
+      return run_attn_drop_fwd_tiled(p, a, s);
+    }
+    default: return hipErrorInvalidValue;
   }
-  if (smem > 160 * 1024 || buckets > 64 || Ls < 1 || Ls > MAX_LQ || (!causal && !mask) || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
-  if (dkv == 128)
-    hipLaunchKernelGGL(self_attn_drop_fwd_kernel<128>, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets,
-                       causal, drop);
-  else
-    hipLaunchKernelGGL(self_attn_drop_fwd_kernel<DKV>, dim3(S * H), dim3(256), smem, s, qkv, mask, rel_bias, bucket, out, Ls, H, buckets,
-                       causal, drop);
   return hipGetLastError();
 }
 hipError_t launch_cross_attn_drop_fwd(const float* q, const float* xk, const float* xv, int xld, const int32_t* mask, float* out, int bz,
                                       int n, int Lq, int H, const DropAttn& drop, hipStream_t s, int dkv) {
-  const size_t smem = cross_attn_bwd_smem(n, Lq);
-  if (smem > 160 * 1024 && dkv == DKV) {   // in tiles (attn_mfma.hip)
-    const AttnLaunch pt = plan_cross_attn_drop_fwd_tiled(CrossAttnBwdIn{bz, n, Lq, H, dkv});
-    if (pt.invalid) return hipErrorInvalidValue;
-    AttnTiledArgs a{};
-    a.q = q; a.k = xk; a.v = xv; a.q_ld = H * DKV; a.kv_ld = xld;
-    a.out = out; a.out_ld = H * DKV;
-    a.mask = mask; a.nq = n; a.nk = Lq; a.H = H; a.da = drop;
-    return run_attn_drop_fwd_tiled(pt, a, s);
+  const AttnLaunch p = plan_train_cross_attn_drop_fwd(TrainCrossAttnIn{bz, n, Lq, H, dkv, mask != nullptr, true, drop.L});
+  const dim3 grid(p.grid_x), blk(p.block);
+  switch (p.kernel) {   // a refused shape has no kernel
+    case ATTN_TRAIN_CROSS_DROP_FWD:
+      hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<DKV>, grid, blk, p.smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
+      break;
+    case ATTN_TRAIN_CROSS_DROP_FWD128:
+      hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<128>, grid, blk, p.smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
+      break;
+    case ATTN_TRAIN_CROSS_DROP_FWD_TILED: {   // attn_mfma.hip
+      AttnTiledArgs a{};
+      a.q = q; a.k = xk; a.v = xv; a.q_ld = H * DKV; a.kv_ld = xld;
+      a.out = out; a.out_ld = H * DKV;
+      a.mask = mask; a.nq = n; a.nk = Lq; a.H = H; a.da = drop;
+      return run_attn_drop_fwd_tiled(p, a, s);
+    }
+    default: return hipErrorInvalidValue;
   }
-  if (smem > 160 * 1024 || drop.L < 1 || n % drop.L || (dkv != DKV && dkv != 128)) return hipErrorInvalidValue;
-  if (dkv == 128) hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<128>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
-  else hipLaunchKernelGGL(cross_attn_drop_fwd_kernel<DKV>, dim3(bz * H), dim3(256), smem, s, q, xk, xv, xld, mask, out, n, Lq, H, drop);
   return hipGetLastError();
 }
 
@@ -1792,21 +1775,19 @@ hipError_t launch_s2s_head_bwd(const float* hF, const float* E, const float* dlo
 }
 
 hipError_t init_train_kernel_attributes() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  for (const void* k : {reinterpret_cast<const void*>(self_attn_bwd_kernel<true>), reinterpret_cast<const void*>(cross_attn_bwd_kernel<true>),
-                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel<DKV>), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel<DKV>),
+  // the resident training attention: every instantiation may ask for the whole LDS of a CU
+  for (const void* k : {reinterpret_cast<const void*>(self_attn_bwd_kernel<false>), reinterpret_cast<const void*>(self_attn_bwd_kernel<true>),
                         reinterpret_cast<const void*>(self_attn_bwd_kernel<false, 128>), reinterpret_cast<const void*>(self_attn_bwd_kernel<true, 128>),
+                        reinterpret_cast<const void*>(cross_attn_bwd_kernel<false>), reinterpret_cast<const void*>(cross_attn_bwd_kernel<true>),
                         reinterpret_cast<const void*>(cross_attn_bwd_kernel<false, 128>), reinterpret_cast<const void*>(cross_attn_bwd_kernel<true, 128>),
-                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel<128>), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel<128>)}) {
-    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                        reinterpret_cast<const void*>(self_attn_drop_fwd_kernel<DKV>), reinterpret_cast<const void*>(self_attn_drop_fwd_kernel<128>),
+                        reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel<DKV>), reinterpret_cast<const void*>(cross_attn_drop_fwd_kernel<128>)}) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
     if (e != hipSuccess) return e;
   }
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(rmsnorm_bf16_T_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rmsnorm_bf16_T_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(s2s_head_fwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(s2s_head_fwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
 }
 
 }  // namespace rpr

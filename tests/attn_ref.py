@@ -629,7 +629,8 @@ CASES = build_cases()
 # every name of RPR_ATTN_KERNELS except: NONE; the training backward and its tiled forward (checked against autograd by
 # test_gpu_train.py / test_gpu_long_queries.py); TAIL_CROSS_G1_NKT1 (reachable only with a development switch)
 OUT_OF_SCOPE = {"NONE", "TAIL_CROSS_G1_NKT1", "TRAIN_BWD_MFMA", "TRAIN_BWD_VALU", "TRAIN_BWD_VALU128", "TRAIN_SELF_BWD_TILED",
-                "TRAIN_CROSS_BWD_TILED", "TRAIN_SELF_DROP_FWD_TILED", "TRAIN_CROSS_DROP_FWD_TILED"}
+                "TRAIN_CROSS_BWD_TILED", "TRAIN_SELF_DROP_FWD_TILED", "TRAIN_CROSS_DROP_FWD_TILED", "TRAIN_CROSS_BWD", "TRAIN_CROSS_BWD128",
+                "TRAIN_SELF_DROP_FWD", "TRAIN_SELF_DROP_FWD128", "TRAIN_CROSS_DROP_FWD", "TRAIN_CROSS_DROP_FWD128"}
 
 
 def planner_query(case: Case) -> Tuple[str, Dict[str, int]]:
