@@ -458,13 +458,41 @@ int rpr_seq2seq_backward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_id
 int rpr_seq2seq_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
                                  int32_t bz, int32_t Lq, const int32_t* labels, int32_t L, float* out_loss, float* flat_grads,
                                  void* stream, void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user);
+/* ---- the dense first-stage step (loss_type t5seq_pretrain_margin_mse; the first model of the RIPOR pipeline) ----------------
+ * Replaces T5SeqPretrainEncoder.forward (modeling/t5_generative_retriever.py:708-757) in the case its training scripts run:
+ * decoder_input_ids = [-1], no commit loss. rep(x) = decoder_last_hidden_state[:, 0] of the encoder plus one decoder position
+ * fed with the start embedding (final RMSNorm and scaleup_output_hidden included: what rpr_embed computes),
+ *   margin_b = <rep(q_b), rep(d+_b)> - <rep(q_b), rep(d-_b)>,  loss = mean_b (margin_b - (teacher_pos_b - teacher_neg_b))^2.
+ * The query is encoded once and receives both gradient contributions (the reference passes the same text twice).
+ *   input_ids, attention_mask: [dev] int32 [3, bz, Lt]: group 0 the queries, 1 the positive, 2 the negative documents, all
+ *                      padded to one Lt <= 256; a sequence with an all-zero mask sets the empty-query status bit
+ *   teacher_pos, teacher_neg: [dev] float [bz]
+ *   out_loss:          [dev] float [1]
+ *   out_scores:        [dev] float [bz, 2], nullable: the two dot products of every example
+ *   out_reps:          [dev] float [3 bz, d_model], nullable: the representations, in the order of input_ids
+ * Limits: bz >= 1, d_kv 64 (Lt <= 256) or 128 (Lt <= 91), else RPR_ERR_INVALID before anything is enqueued. The head is exact
+ * fp32 in every precision mode and deterministic.
+ * rpr_dense_mse_forward: evaluation mode. rpr_dense_mse_backward: forward + backward, overwrites flat_grads [dev,
+ * rpr_param_total] (layout and optimizer step of the other training steps; the codebooks get exactly zero);
+ * rpr_set_train_dropout applies. rpr_dense_mse_backward_buckets: the same with the gradient buckets of
+ * rpr_lngknp_backward_buckets. (Added to ABI version 4 without a bump, as rpr_search_margins was: probe for the symbol.) */
+int rpr_dense_mse_forward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+                          int32_t Lt, const float* teacher_pos, const float* teacher_neg, float* out_loss, float* out_scores,
+                          float* out_reps, void* stream);
+int rpr_dense_mse_backward(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+                           int32_t Lt, const float* teacher_pos, const float* teacher_neg, float* out_loss, float* flat_grads,
+                           void* stream);
+int rpr_dense_mse_backward_buckets(rpr_ctx* ctx, rpr_model* model, const int32_t* input_ids, const int32_t* attention_mask,
+                                   int32_t bz, int32_t Lt, const float* teacher_pos, const float* teacher_neg, float* out_loss,
+                                   float* flat_grads, void* stream, void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user);
 int rpr_adamw_step(rpr_ctx* ctx, rpr_model* model, const float* flat_grads, float* exp_avg, float* exp_avg_sq, int64_t step,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
                    float* out_grad_norm, void* stream);
 /* Dropout of the two training steps (the reference trains in model.train(): every dropout of HF T5Stack is live at the
  * checkpoint's dropout_rate — stack input, attention probabilities, sub-block outputs, the feed-forward's inner activation,
- * stack output; both stacks). Applies to the rpr_lngknp_backward[_buckets] and rpr_seq2seq_backward[_buckets] calls that follow,
- * until set again; rpr_lngknp_forward, rpr_seq2seq_forward, rpr_search*, rpr_encode and rpr_embed stay in evaluation mode.
+ * stack output; both stacks). Applies to the rpr_lngknp_backward[_buckets], rpr_seq2seq_backward[_buckets] and
+ * rpr_dense_mse_backward[_buckets] calls that follow, until set again; rpr_lngknp_forward, rpr_seq2seq_forward,
+ * rpr_dense_mse_forward, rpr_search*, rpr_encode and rpr_embed stay in evaluation mode.
  * 0 <= rate < 1, else RPR_ERR_INVALID; the default, rate 0, is off: a training call then enqueues exactly what it enqueues
  * without this call. The mask of an element is a stateless function of (seed, step, site, logical coordinates) — Philox4x32-10,
  * csrc/dropout.h, DESIGN.md "Dropout in the training step" — so the same (seed, step) gives the same bits in every precision

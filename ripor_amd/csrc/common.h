@@ -822,6 +822,12 @@ hipError_t launch_s2s_head_fwd(const float* hF, const float* E, const int32_t* l
                                float* loss, int bz, int L, int d, int V, hipStream_t s);
 hipError_t launch_s2s_head_bwd(const float* hF, const float* E, const float* dlogits, float* dH, float* dE, int bz, int L, int d, int V,
                                hipStream_t s);
+// dense first-stage head (dense_head.hip, exact fp32): hF [3 bz, d] = queries | positive documents | negative documents.
+// Forward: scores [bz, 2] = (<q, d+>, <q, d->), margins [bz], g [bz] = 2 (margin - (t+ - t-)) / bz, loss[0] = the margin MSE.
+// Backward: dhF [3 bz, d] = (g (d+ - d-) | g q | -g q).
+hipError_t launch_dense_mse_head_fwd(const float* hF, const float* teacher_pos, const float* teacher_neg, float* scores, float* margins,
+                                     float* g, float* loss, int bz, int d, hipStream_t s);
+hipError_t launch_dense_mse_head_bwd(const float* hF, const float* g, float* dhF, int bz, int d, hipStream_t s);
 hipError_t launch_grad_norm(const float* g, size_t n, double* part, int nparts, float max_norm, float* out, hipStream_t s);
 // AdamW over every parameter tensor in one launch: segs[i] = {tensor, offset of its gradient / moments in the flat buffers, elements,
 // decays?}; pref = exclusive prefix sums of ceil(n / 4096)

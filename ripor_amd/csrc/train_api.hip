@@ -157,6 +157,7 @@ struct TrainWs {
   DevBuf enc_act, dec_act, enc_out, xkv, x_last, scores, margins, dscores, in_idx, out_idx;
   // seq2seq head: the decoder's last hidden state (after the final norm), dlogits of every row, the row losses
   DevBuf hF, dlog, row_loss;
+  DevBuf dense_codes;   // dense head: the zero codes the one-position decoder pass is indexed by (it reads none of them)
   // scratch
   DevBuf dmid_ff;   // gated feed-forward only: the W_out product's input gradient [rows, d_ff] (the backward gate kernel's dmid)
   DevBuf h, dxa, dxb, dbig, dattn, dxkv, denc, tA, wT, w_part, bias_part, fix, gn_part, gn_out, amax, part, part2;
@@ -545,7 +546,11 @@ struct Bwd {
   }
 };
 
-int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
+// What follows the decoder stream: the ranking step's gold-code scores, the seq2seq cross-entropy head, or the dense first
+// stage's dot products of the query and document representations (dense_head.hip)
+enum Head { HEAD_GOLD, HEAD_CE, HEAD_DENSE };
+
+int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D, Head head) {
   if (!c->tws) c->tws = new TrainWs();
   TrainWs& w = *c->tws;
   const size_t f = sizeof(float), R = D.R, T = D.T, dm = D.dm, inner = D.inner, dff = D.dff;
@@ -559,7 +564,8 @@ int alloc_train(rpr_ctx* c, const rpr_model* m, const TrainDims& D) {
   E(w.enc_out, T * dm * f); E(w.xkv, T * (size_t)D.xld * f); E(w.x_last, R * dm * f);
   E(w.scores, R * f); E(w.margins, 8 * (size_t)D.bz * f); E(w.dscores, R * f);
   E(w.in_idx, R * 4); E(w.out_idx, R * 4);
-  if (D.docs == 1) { E(w.hF, R * dm * f); E(w.dlog, R * (size_t)D.V * f); E(w.row_loss, R * f); }   // the seq2seq head
+  if (head == HEAD_CE) { E(w.hF, R * dm * f); E(w.dlog, R * (size_t)D.V * f); E(w.row_loss, R * f); }   // the seq2seq head
+  if (head == HEAD_DENSE) { E(w.hF, R * dm * f); E(w.dense_codes, R * 4); }   // the dense head: dhF goes to dxa (rows x d_model, below)
   if (c->train_drop.rate > 0.f) { E(w.hF, R * dm * f); E(w.drop_dy, rows * dm * f); }   // dropout: the ranking step keeps hF too
   E(w.h, rows * dm * f); E(w.dxa, rows * dm * f); E(w.dxb, rows * dm * f); E(w.dbig, rows * wide * f);
   if (D.gated) E(w.dmid_ff, rows * dff * f);
@@ -729,9 +735,10 @@ struct BucketHook {
   rpr_grad_bucket_cb cb; void* user; hipStream_t comm; int next = 0;
 };
 
-// ce_head: the seq2seq cross-entropy head (s2s_head_forward ran) instead of the ranking step's gold scores
+// head: HEAD_CE, the seq2seq cross-entropy head (s2s_head_forward ran) instead of the ranking step's gold scores; HEAD_DENSE, the
+// dense head (dense_head_forward ran): dhF comes from the margins it kept, no codebook is touched
 void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const int32_t* ids, const int32_t* mask, float* G,
-              const Drop& drop, BucketHook* hook = nullptr, bool ce_head = false) {
+              const Drop& drop, BucketHook* hook = nullptr, Head head = HEAD_GOLD) {
   TrainWs& w = *c->tws;
   const auto& d = m->d;
   hipStream_t s = Ln.s;
@@ -762,7 +769,10 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
   unsigned long long* fix = P<unsigned long long>(w.fix);
 
   float* g_out = d.out_embeds != d.in_embeds ? g(K_OUT_EMB) : g(K_IN_EMB);
-  if (ce_head) {
+  if (head == HEAD_DENSE) {
+    // ---- dense head: dhF = (g (d+ - d-) | g q | -g q) from the hF the forward kept -> final RMSNorm backward
+    Ln.run(RPR_K_OTHER, 0, 24.0 * R * dm, [&] { return launch_dense_mse_head_bwd(P<float>(w.hF), P<float>(w.dscores), dxa, D.bz / 3, dm, s); });
+  } else if (head == HEAD_CE) {
     // ---- cross-entropy head: dhF_i = dlogits_i E_i -> dxa, dE_i = dlogits_i^T hF_i stored into the codebook gradient (the
     // flat buffer is zero; with shared codebooks the input-embedding rows are added to it later) -> final RMSNorm backward
     Ln.run(RPR_K_OTHER, 4.0 * R * (double)D.V * dm, 4.0 * (2.0 * R * D.V + 2.0 * R * dm + 2.0 * (double)D.L * D.V * dm), [&] {
@@ -870,7 +880,7 @@ void backward(Launcher& Ln, rpr_ctx* c, rpr_model* m, const TrainDims& D, const 
 }
 
 // Checks and workspaces shared by the training passes: docs decoder sequences of L positions per query
-int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, TrainDims& D) {
+int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int docs, TrainDims& D, Head head) {
   RPR_REQUIRE(m->ctx == c, "model belongs to another ctx");
   RPR_REQUIRE(bz >= 1 && Lq >= 1, "bz or Lq out of range");
   RPR_REQUIRE(Lq <= MAX_LQ, "Lq out of range: the training passes take queries of at most 256 tokens");
@@ -884,7 +894,7 @@ int train_setup(rpr_ctx* c, rpr_model* m, int32_t bz, int32_t Lq, int32_t L, int
   RPR_REQUIRE(train_attn_admitted(bz, Lq, L, docs, d.num_heads, d.rel_buckets, d.d_kv),
               "sequence lengths beyond the 160 KB of LDS the attention backward holds a head in: self-attention max(L, Lq) <= 91, "
               "cross-attention 130 (docs L + Lq) + 2 docs L (Lq + 1) + Lq floats <= 40960 (the same for 64- and 128-dim heads)");
-  int e = alloc_train(c, m, D);
+  int e = alloc_train(c, m, D, head);
   if (e) return e;
   // the forward's cross-attention kernel needs the per-query key counts: reuse the search workspace's small buffers
   return ensure(c, c->ws.last, (size_t)bz * 4);
@@ -946,7 +956,7 @@ int rpr_lngknp_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_i
                   flat_grads, "NULL argument");
   RPR_REQUIRE(n_prefix >= 1 && n_prefix <= 8, "n_prefix out of range (1..8)");
   TrainDims D{};
-  int e = train_setup(c, m, bz, Lq, L, 2, D);
+  int e = train_setup(c, m, bz, Lq, L, 2, D, HEAD_GOLD);
   if (e) return e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   TrainWs& w = *c->tws;
@@ -975,7 +985,7 @@ static int seq2seq_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const
   RPR_REQUIRE(s2s_head_smem_ok(m->d.V) && m->d.d_model % 32 == 0,
               "the cross-entropy head needs a codebook size V with V % 64 == 0 and V <= 1024, and d_model % 32 == 0");
   TrainDims D{};
-  int e = train_setup(c, m, bz, Lq, L, 1, D);
+  int e = train_setup(c, m, bz, Lq, L, 1, D, HEAD_CE);
   if (e) return e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   {  // labels outside [0, V) would index past a codebook: refused before anything is enqueued (one small copy + synchronisation)
@@ -993,7 +1003,7 @@ static int seq2seq_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const
   s2s_head_forward(Ln, c, m, D, labels, out_loss, out_label_lp, drop);
   if (Ln.err || !flat_grads) return Ln.err;
   BucketHook hook{on_bucket, user, reinterpret_cast<hipStream_t>(comm_stream)};
-  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, drop, on_bucket ? &hook : nullptr, true);
+  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, drop, on_bucket ? &hook : nullptr, HEAD_CE);
   return Ln.err;
 }
 
@@ -1015,6 +1025,74 @@ int rpr_seq2seq_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_
   RPR_REQUIRE(flat_grads, "NULL argument");
   return seq2seq_run(c, m, input_ids, attention_mask, bz, Lq, labels, L, out_loss, nullptr, flat_grads, stream, comm_stream, on_bucket,
                      user);
+}
+
+// ---- dense first-stage step (reference T5SeqPretrainEncoder, modeling/t5_generative_retriever.py:558-615 and :708-757 with one
+// decoder position: decoder_input_ids = [-1], no commit loss) ----
+// One teacher-forced pass over S = 3 bz sequences (queries | positive documents | negative documents), one decoder sequence of
+// one position each, and the dense head in place of the gold scores. The query is encoded once and takes both gradient
+// contributions (the reference encodes the same text twice).
+static void dense_head_forward(Launcher& Ln, rpr_ctx* c, const rpr_model* m, const TrainDims& D, const float* teacher_pos,
+                               const float* teacher_neg, float* out_loss, const Drop& drop) {
+  TrainWs& w = *c->tws;
+  hipStream_t s = Ln.s;
+  Ln.run(RPR_K_RMSNORM, 0, 8.0 * D.R * D.dm, [&] {
+    return launch_rmsnorm(P<float>(w.x_last), m->d.dec_final_ln, P<float>(w.hF), D.R, D.dm, D.eps, s, D.post);
+  });
+  if (drop.on) drop.rows(Ln, D.S, D.L, P<float>(w.hF), nullptr, P<float>(w.hF), D.dm, drop_site_output(1));
+  Ln.run(RPR_K_OTHER, 4.0 * D.R * D.dm, 4.0 * D.R * D.dm, [&] {
+    return launch_dense_mse_head_fwd(P<float>(w.hF), teacher_pos, teacher_neg, P<float>(w.scores), P<float>(w.margins), P<float>(w.dscores),
+                                     out_loss, D.bz / 3, D.dm, s);
+  });
+}
+
+static int dense_run(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lt,
+                     const float* teacher_pos, const float* teacher_neg, float* out_loss, float* out_scores, float* out_reps,
+                     float* flat_grads, void* stream, void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user) {
+  RPR_REQUIRE(c && m && input_ids && attention_mask && teacher_pos && teacher_neg && out_loss, "NULL argument");
+  RPR_REQUIRE(bz >= 1 && bz <= (1 << 20), "bz out of range");
+  TrainDims D{};
+  int e = train_setup(c, m, 3 * bz, Lt, 1, 1, D, HEAD_DENSE);
+  if (e) return e;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  TrainWs& w = *c->tws;
+  if (flat_grads) RPR_HIP(hipMemsetAsync(flat_grads, 0, m->params.total * sizeof(float), s));
+  RPR_HIP(hipMemsetAsync(w.dense_codes.p, 0, (size_t)D.R * 4, s));
+  Launcher Ln{c, s};
+  e = train_begin(Ln, c, m);
+  if (e) return e;
+  const Drop drop = flat_grads ? Drop(c) : Drop();   // rpr_dense_mse_forward stays in evaluation mode
+  forward(Ln, c, m, D, input_ids, attention_mask, P<int32_t>(w.dense_codes), P<int32_t>(c->ws.last), drop, false);
+  dense_head_forward(Ln, c, m, D, teacher_pos, teacher_neg, out_loss, drop);
+  if (Ln.err) return Ln.err;
+  if (out_scores) RPR_HIP(hipMemcpyAsync(out_scores, w.scores.p, (size_t)2 * bz * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (out_reps) RPR_HIP(hipMemcpyAsync(out_reps, w.hF.p, (size_t)D.R * D.dm * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (!flat_grads) return RPR_OK;
+  BucketHook hook{on_bucket, user, reinterpret_cast<hipStream_t>(comm_stream)};
+  backward(Ln, c, m, D, input_ids, attention_mask, flat_grads, drop, on_bucket ? &hook : nullptr, HEAD_DENSE);
+  return Ln.err;
+}
+
+int rpr_dense_mse_forward(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lt,
+                          const float* teacher_pos, const float* teacher_neg, float* out_loss, float* out_scores, float* out_reps,
+                          void* stream) {
+  return dense_run(c, m, input_ids, attention_mask, bz, Lt, teacher_pos, teacher_neg, out_loss, out_scores, out_reps, nullptr, stream,
+                   nullptr, nullptr, nullptr);
+}
+
+int rpr_dense_mse_backward(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz, int32_t Lt,
+                           const float* teacher_pos, const float* teacher_neg, float* out_loss, float* flat_grads, void* stream) {
+  RPR_REQUIRE(flat_grads, "NULL argument");
+  return dense_run(c, m, input_ids, attention_mask, bz, Lt, teacher_pos, teacher_neg, out_loss, nullptr, nullptr, flat_grads, stream,
+                   nullptr, nullptr, nullptr);
+}
+
+int rpr_dense_mse_backward_buckets(rpr_ctx* c, rpr_model* m, const int32_t* input_ids, const int32_t* attention_mask, int32_t bz,
+                                   int32_t Lt, const float* teacher_pos, const float* teacher_neg, float* out_loss, float* flat_grads,
+                                   void* stream, void* comm_stream, rpr_grad_bucket_cb on_bucket, void* user) {
+  RPR_REQUIRE(flat_grads, "NULL argument");
+  return dense_run(c, m, input_ids, attention_mask, bz, Lt, teacher_pos, teacher_neg, out_loss, nullptr, nullptr, flat_grads, stream,
+                   comm_stream, on_bucket, user);
 }
 
 int rpr_set_train_dropout(rpr_ctx* c, float rate, uint64_t seed, uint64_t step) {

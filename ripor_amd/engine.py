@@ -1210,6 +1210,82 @@ def seq2seq_train_step(model: DeviceModel, state: TrainState, input_ids, attenti
     return loss
 
 
+# ---- dense first-stage step (loss_type t5seq_pretrain_margin_mse; reference T5SeqPretrainEncoder, decoder length 1) --------
+def _dense_args(model: DeviceModel, input_ids, attention_mask, teacher_pos, teacher_neg):
+    dev = model.ctx.device
+    ids = input_ids.to(device=dev, dtype=torch.int32).contiguous()
+    mask = attention_mask.to(device=dev, dtype=torch.int32).contiguous()
+    if ids.dim() != 3 or ids.shape[0] != 3 or tuple(mask.shape) != tuple(ids.shape):
+        raise ValueError(f"input_ids and attention_mask must be [3, bz, Lt] (queries, positive documents, negative documents), "
+                         f"got {tuple(ids.shape)} and {tuple(mask.shape)}")
+    _, bz, Lt = ids.shape
+    if Lt > 256:
+        raise ValueError(f"sequences of {Lt} tokens: the training passes take at most 256 encoder positions (use max_length <= 256)")
+    tp = teacher_pos.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    tn = teacher_neg.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    if tp.numel() != bz or tn.numel() != bz:
+        raise ValueError(f"teacher scores must be [bz] with bz = {bz}, got {tuple(teacher_pos.shape)} and {tuple(teacher_neg.shape)}")
+    return ids, mask, tp, tn, int(bz), int(Lt)
+
+
+def dense_mse_forward(model: DeviceModel, input_ids, attention_mask, teacher_pos, teacher_neg):
+    """Forward of the dense first-stage step (``rpr_dense_mse_forward``): ``input_ids`` / ``attention_mask`` ``[3, bz, Lt]`` hold
+    the queries, the positive and the negative documents padded to one length. Returns ``(loss [1], scores [bz, 2], reps
+    [3 * bz, d_model])``, float32 device tensors, asynchronous on the current stream; evaluation mode."""
+    ctx = model.ctx
+    ids, mask, tp, tn, bz, Lt = _dense_args(model, input_ids, attention_mask, teacher_pos, teacher_neg)
+    loss = torch.empty((1,), dtype=torch.float32, device=ctx.device)
+    scores = torch.empty((bz, 2), dtype=torch.float32, device=ctx.device)
+    reps = torch.empty((3 * bz, model.d_model), dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.rpr_dense_mse_forward(ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lt, tp.data_ptr(), tn.data_ptr(),
+                                        loss.data_ptr(), scores.data_ptr(), reps.data_ptr(), _stream_ptr(ctx.device)),
+          "rpr_dense_mse_forward")
+    return loss, scores, reps
+
+
+def dense_mse_backward(model: DeviceModel, state: TrainState, input_ids, attention_mask, teacher_pos, teacher_neg,
+                       exchange: Optional[GradExchange] = None, global_step: Optional[int] = None) -> torch.Tensor:
+    """Forward + backward of the dense margin-MSE (``rpr_dense_mse_backward``): fills ``state.grads`` (the codebooks get exactly
+    zero) and returns the loss ``[1]`` (device tensor). ``exchange`` and dropout as in :func:`lngknp_backward`."""
+    ctx = model.ctx
+    state.apply_dropout(global_step)
+    ids, mask, tp, tn, bz, Lt = _dense_args(model, input_ids, attention_mask, teacher_pos, teacher_neg)
+    loss = torch.empty((1,), dtype=torch.float32, device=ctx.device)
+    if exchange is not None and exchange.active:
+        check(ctx.lib.rpr_dense_mse_backward_buckets(ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lt, tp.data_ptr(),
+                                                     tn.data_ptr(), loss.data_ptr(), state.grads.data_ptr(), _stream_ptr(ctx.device),
+                                                     exchange.comm_stream_ptr(), exchange.callback(), None),
+              "rpr_dense_mse_backward_buckets")
+        exchange.raise_pending()
+    else:
+        check(ctx.lib.rpr_dense_mse_backward(ctx.handle, model.handle, ids.data_ptr(), mask.data_ptr(), bz, Lt, tp.data_ptr(),
+                                             tn.data_ptr(), loss.data_ptr(), state.grads.data_ptr(), _stream_ptr(ctx.device)),
+              "rpr_dense_mse_backward")
+    return loss
+
+
+def dense_mse_train_step(model: DeviceModel, state: TrainState, input_ids, attention_mask, teacher_pos, teacher_neg, lr: float,
+                         betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 1.0,
+                         dropout_rate: Optional[float] = None, dropout_seed: Optional[int] = None,
+                         global_step: Optional[int] = None) -> torch.Tensor:
+    """:func:`train_step` for the dense margin-MSE: backward with the gradient exchange (bucketed and overlapped unless
+    ``RPR_GRAD_OVERLAP=0``), clip_grad_norm_, AdamW. Returns the loss ``[1]`` before the update."""
+    import os
+    if dropout_rate is not None:
+        state.set_dropout(dropout_rate, state.dropout_seed if dropout_seed is None else dropout_seed)
+    if os.environ.get("RPR_GRAD_OVERLAP", "1") == "0":
+        loss = dense_mse_backward(model, state, input_ids, attention_mask, teacher_pos, teacher_neg, global_step=global_step)
+        allreduce_grads(state)
+    else:
+        ex = getattr(state, "_exchange", None)
+        if ex is None or ex.grads is not state.grads:
+            ex = state._exchange = GradExchange(state.grads)
+        loss = dense_mse_backward(model, state, input_ids, attention_mask, teacher_pos, teacher_neg, exchange=ex, global_step=global_step)
+        ex.finish()
+    adamw_step(model, state, lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    return loss
+
+
 def allreduce_grads(state: TrainState, bucket_elems: int = 64 << 20) -> None:
     """Serial data-parallel gradient exchange (``RPR_GRAD_OVERLAP=0``; the default is :class:`GradExchange`, overlapped
     with the backward pass): sum ``state.grads`` over the ranks in a few large chunks after the backward and divide by

@@ -139,6 +139,28 @@ def _load_checkpoint(path: str) -> Dict[str, torch.Tensor]:
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {path}")
 
 
+def plain_t5_state_dict(sd: Dict[str, torch.Tensor], cfg: T5forDocIDConfig, decoder_start_token_path: str,
+                        codebook_seed: int = 0) -> Dict[str, torch.Tensor]:
+    """The state dict of a docid-generation model on top of a plain HF T5 checkpoint (reference T5ForDocIDGeneration.__init__
+    :80-135 followed by from_pretrained of "t5-base"): the T5 tensors as they are, ``start_token_embed`` [1, 1, d_model] from the
+    ``.npy`` file, the codebooks N(0, 1) like a fresh ``nn.Embedding`` from a generator seeded with ``codebook_seed``."""
+    if not decoder_start_token_path or not os.path.exists(decoder_start_token_path):
+        raise FileNotFoundError(f"a plain T5 checkpoint has no start_token_embed: decoder_start_token_path "
+                                f"{decoder_start_token_path!r} must name the .npy file that holds it, [1, 1, {cfg.d_model}] "
+                                f"(pass decoder_start_token_path, or set it in config.json)")
+    start = torch.from_numpy(np.load(decoder_start_token_path)).float()
+    if start.numel() != cfg.d_model:
+        raise ValueError(f"{decoder_start_token_path}: {tuple(start.shape)}, expected [1, 1, {cfg.d_model}]")
+    out = {k: v for k, v in sd.items() if k.split(".")[0] in ("shared", "encoder", "decoder")}
+    out["start_token_embed"] = start.reshape(1, 1, cfg.d_model)
+    gen = torch.Generator().manual_seed(int(codebook_seed))
+    for i, V in enumerate(cfg.decoder_vocab_sizes):
+        out[f"list_decoder_embeds.{i}.weight"] = torch.randn((int(V), cfg.d_model), generator=gen)
+        if not cfg.shared_output_input_embeds:
+            out[f"list_output_embeds.{i}.weight"] = torch.randn((int(V), cfg.d_model), generator=gen)
+    return out
+
+
 class T5ForDocIDGeneration:
     """Weights of the docid-generation T5 (reference :70-135) bound lazily to the HIP engine."""
 
@@ -282,11 +304,96 @@ class T5AQEncoder(T5SeqAQEncoder):
 
 
 class T5SeqPretrainEncoder(T5SeqAQEncoder):
-    """reference :558-: the dense first-stage model (inference surface only). ``doc_encode`` and ``query_encode`` are the
-    same pass: the encoder plus one decoder position fed with the start embedding."""
+    """reference :558-769: the dense first-stage model. ``doc_encode`` and ``query_encode`` are the same pass: the encoder plus
+    one decoder position fed with the start embedding. ``forward(**inputs) -> {"rank": loss}`` is the margin-MSE of loss_type
+    ``t5seq_pretrain_margin_mse`` on the batches of ``MarginMSEforPretrainCollator``, in the case the reference's training
+    scripts run: ``decoder_input_ids = [-1]`` (no ``--docid_to_smtid_path``). The commit-loss branch (decoder length > 1) is not
+    built. The whole pass runs in ``rpr_dense_mse_forward`` / ``rpr_dense_mse_backward`` (engine.py); no autograd graph is
+    attached to the returned loss. ``last_scores`` keeps the two dot products of every example, ``[bz, 2]``."""
+
+    def __init__(self, model_name_or_path, model_args=None, decoder_start_token_path=None, codebook_seed=0):
+        config = T5forDocIDConfig.from_pretrained(model_name_or_path)
+        config.decoding = False
+        sd = _load_checkpoint(model_name_or_path)
+        if "start_token_embed" not in sd:   # a plain HF T5 directory (what the first training round starts from)
+            sd = plain_t5_state_dict(sd, config, decoder_start_token_path or config.decoder_start_token_path, codebook_seed)
+        self.base_model = T5ForDocIDGeneration(config, sd)
+        self.config = config
+        self.model_args = model_args
+
+    @classmethod
+    def from_pretrained(cls, model_name_or_path=None, model_args=None, decoder_start_token_path=None, codebook_seed=0):
+        """A checkpoint directory of this project's format, or a plain HF T5 directory (``config.json`` of a T5 and its
+        ``shared`` / ``encoder.*`` / ``decoder.*`` tensors; ``lm_head`` is ignored). The latter has no ``start_token_embed``: it is
+        read from the ``.npy`` named by ``decoder_start_token_path`` (argument, else the config field), and the codebooks —
+        which this model never reads — are drawn from a normal seeded with ``codebook_seed``."""
+        return cls(model_name_or_path, model_args, decoder_start_token_path, codebook_seed)
 
     def doc_encode(self, **inputs):
         return self.query_encode(**inputs)
+
+    def _batch(self, inputs):
+        pq, nq = inputs["tokenized_pos_query"], inputs["tokenized_neg_query"]
+        pd, nd = inputs["tokenized_pos_doc"], inputs["tokenized_neg_doc"]
+        if not (torch.equal(pq["input_ids"], nq["input_ids"]) and torch.equal(pq["attention_mask"], nq["attention_mask"])):
+            # dataset.py:618-682 builds both from the same query text; two different texts would need two encoder passes
+            raise ValueError("tokenized_pos_query and tokenized_neg_query must carry the same query tokens")
+        for name, t in (("tokenized_pos_query", pq), ("tokenized_neg_query", nq), ("tokenized_pos_doc", pd), ("tokenized_neg_doc", nd)):
+            di = t.get("decoder_input_ids")
+            if di is not None and (di.dim() != 2 or di.shape[1] != 1 or bool((di != -1).any())):
+                raise ValueError(f"{name}: decoder_input_ids must be [-1] (one decoder position fed with the start embedding); the "
+                                 "commit-loss branch of the reference (decoder length > 1, --docid_to_smtid_path) is not built")
+        if "pos_prev_smtids" in inputs or "neg_prev_smtids" in inputs:
+            raise ValueError("pos_prev_smtids / neg_prev_smtids: the commit-loss branch of the reference is not built")
+        groups = (pq, pd, nd)
+        bz = pq["input_ids"].shape[0]
+        Lt = max(int(t["input_ids"].shape[1]) for t in groups)
+        ids = torch.zeros((3, bz, Lt), dtype=torch.int32)
+        mask = torch.zeros((3, bz, Lt), dtype=torch.int32)
+        for k, t in enumerate(groups):   # one length for the three groups: padded on the host
+            if t["input_ids"].shape[0] != bz:
+                raise ValueError("queries, positive and negative documents must have the same batch size")
+            n = t["input_ids"].shape[1]
+            ids[k, :, :n] = t["input_ids"].cpu().to(torch.int32)
+            mask[k, :, :n] = t["attention_mask"].cpu().to(torch.int32)
+        return ids, mask, inputs["teacher_pos_score"].float().reshape(-1), inputs["teacher_neg_score"].float().reshape(-1)
+
+    def forward(self, **inputs):
+        from .. import engine as E
+        ids, mask, tp, tn = self._batch(inputs)
+        em = self.base_model.engine_model()
+        em.ctx.clear_status_async()
+        loss, self.last_scores, self.last_reps = E.dense_mse_forward(em, ids, mask, tp, tn)
+        if em.ctx.status(clear=True) & E._lib.STATUS_EMPTY_QUERY:
+            raise ValueError("a query or a document has an all-zero attention_mask (no token to attend to)")
+        return {"rank": loss[0]}
+
+    __call__ = forward
+
+    def train_state(self):
+        from .. import engine as E
+        if getattr(self, "_train_state", None) is None or self._train_state.model is not self.base_model.engine_model():
+            self._train_state = E.TrainState(self.base_model.engine_model())
+        return self._train_state
+
+    def backward(self, **inputs):
+        """loss.backward() of ``forward``: fills ``train_state().grads``; returns ``{"rank": loss}``."""
+        from .. import engine as E
+        ids, mask, tp, tn = self._batch(inputs)
+        loss = E.dense_mse_backward(self.base_model.engine_model(), self.train_state(), ids, mask, tp, tn)
+        return {"rank": loss[0]}
+
+    def training_step(self, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, dropout_rate=None,
+                      dropout_seed=None, global_step=None, **inputs):
+        """One optimisation step (same contract as ``T5SeqAQEncoderForLngKnpMarginMSE.training_step``): backward with the
+        data-parallel gradient exchange overlapped, clip_grad_norm_, AdamW in place on the device. Returns ``{"rank": loss}``
+        of the batch before the update."""
+        from .. import engine as E
+        ids, mask, tp, tn = self._batch(inputs)
+        loss = E.dense_mse_train_step(self.base_model.engine_model(), self.train_state(), ids, mask, tp, tn, lr, betas=betas, eps=eps,
+                                      weight_decay=weight_decay, max_grad_norm=max_grad_norm, dropout_rate=dropout_rate,
+                                      dropout_seed=dropout_seed, global_step=global_step)
+        return {"rank": loss[0]}
 
 
 class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):

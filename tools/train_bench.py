@@ -9,7 +9,11 @@ codebook-logit head). Rank 0 prints one JSON line (examples/s of the whole job, 
 --precision and --loss take comma-separated lists: one JSON line per (precision, loss) on ONE model load (t5-3b: 11 GB of
 weights to generate and upload). --embed: before the steps, time rpr_embed on 128 texts of ~16 tokens and 128 texts of 128
 tokens (one JSON line).
-Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq] [--dims t5-base|t5-3b|t5-v1.1-base] [--embed] [--lq N]
+--step dense (--step is --loss by another name): the dense first-stage step (t5seq_pretrain_margin_mse; the reference trains it
+with --bz 64): bz queries of the usual ~16-token mix, bz positive and bz negative documents of --doc_len (128) tokens, all padded
+to the document length in one encoder batch of 3 bz sequences, one decoder position each. Its JSON line also reports
+query_padding_share: the share of the 3 bz x doc_len encoder rows that are padding behind a query.
+Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq|dense] [--dims t5-base|t5-3b|t5-v1.1-base] [--embed] [--lq N]
        python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/train_bench.py"""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -17,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ripor_amd import engine as E
 from ripor_amd.utils import synth
 
-PRECISIONS, LOSSES = ["f16x2", "f32", "bf16"], ["lngknp", "seq2seq"]
+PRECISIONS, LOSSES = ["f16x2", "f32", "bf16"], ["lngknp", "seq2seq", "dense"]
 
 
 def listed(choices):
@@ -34,7 +38,8 @@ ap.add_argument("--bz", type=int, default=128)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--len", type=int, default=32, dest="L")
 ap.add_argument("--precision", default=["f16x2"], type=listed(PRECISIONS))
-ap.add_argument("--loss", default=["lngknp"], type=listed(LOSSES))
+ap.add_argument("--loss", "--step", dest="loss", default=["lngknp"], type=listed(LOSSES))
+ap.add_argument("--doc_len", type=int, default=128, help="--step dense: tokens per document (at most 256)")
 ap.add_argument("--dims", default="t5-base", choices=["t5-base", "t5-3b", "t5-v1.1-base"])
 ap.add_argument("--embed", action="store_true")
 ap.add_argument("--lq", type=int, default=0, help="all queries this many tokens long (default: ~16, as the fine-tune data)")
@@ -72,6 +77,13 @@ ids_t, mask_t, codes_t = torch.from_numpy(ids).cuda(), torch.from_numpy(mask).cu
 
 
 labels_t = codes_t[:, 0].contiguous()   # seq2seq: one smtid per query
+if "dense" in args.loss:   # [3, bz, doc_len]: the queries (padded to the document length), the positive and the negative documents
+    Ld = max(args.doc_len, ids.shape[1])
+    d_ids, d_mask = synth.make_queries(2 * bz, vocab_size=dims.vocab_size, seed=6 + rank, fixed_len=args.doc_len)
+    pad = lambda a: np.pad(a, ((0, 0), (0, Ld - a.shape[1])))   # noqa: E731
+    dense_ids = torch.from_numpy(np.stack([pad(ids), pad(d_ids[:bz]), pad(d_ids[bz:])])).cuda()
+    dense_mask = torch.from_numpy(np.stack([pad(mask), pad(d_mask[:bz]), pad(d_mask[bz:])])).cuda()
+    dense_tp, dense_tn = torch.from_numpy(synth.uniform_f32("tb/dp", (bz,), 30.0)), torch.from_numpy(synth.uniform_f32("tb/dn", (bz,), 30.0))
 
 
 def embed_leg():   # dense embeddings (rpr_embed): 128 texts per call, queries of ~16 tokens and passages of 128
@@ -97,6 +109,8 @@ def leg(precision, loss):
     def step():   # backward with the bucketed gradient exchange overlapped (RPR_GRAD_OVERLAP=0: serial), clip, AdamW
         if loss == "seq2seq":
             return E.seq2seq_train_step(model, state, ids_t, mask_t, labels_t, lr=1e-6)
+        if loss == "dense":
+            return E.dense_mse_train_step(model, state, dense_ids, dense_mask, dense_tp, dense_tn, lr=1e-6)
         return E.train_step(model, state, ids_t, mask_t, codes_t, tp, tn, prefix, lr=1e-6)
 
     first = step(); torch.cuda.synchronize()
@@ -114,6 +128,8 @@ def leg(precision, loss):
     ctx.profile_reset(); ctx.profile_enable(True)
     if loss == "seq2seq":
         E.seq2seq_backward(model, state, ids_t, mask_t, labels_t)
+    elif loss == "dense":
+        E.dense_mse_backward(model, state, dense_ids, dense_mask, dense_tp, dense_tn)
     else:
         E.lngknp_backward(model, state, ids_t, mask_t, codes_t, tp, tn, prefix)
     torch.cuda.synchronize()
@@ -122,11 +138,19 @@ def leg(precision, loss):
     flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * dm * inner + ff_mats * dm * dff) + nd * 2 * dm * inner)
                        + bz * (1 if loss == "seq2seq" else 2) * L * nd * (6 * dm * inner + ff_mats * dm * dff)
                        + (bz * L * V * dm if loss == "seq2seq" else 0))
+    extra = {}
+    if loss == "dense":   # real tokens of the 3 bz sequences through the encoder and the cross K/V, one decoder row per sequence
+        tokens = float(dense_mask.sum())
+        flops_fwd = 2.0 * (tokens * (dims.num_layers * (4 * dm * inner + ff_mats * dm * dff) + nd * 2 * dm * inner)
+                           + 3 * bz * nd * (6 * dm * inner + ff_mats * dm * dff))
+        rows = float(dense_mask.numel())
+        extra = {"doc_len": args.doc_len, "encoder_rows": int(rows), "padding_share": round(1.0 - tokens / rows, 4),
+                 "query_padding_share": round(float((1 - dense_mask[0]).sum()) / rows, 4)}
     if rank == 0:
-        task = ("seq2seq docid cross-entropy step" if loss == "seq2seq" else "lng_knp margin-MSE fine-tune step")
+        task = {"seq2seq": "seq2seq docid cross-entropy step", "dense": "dense first-stage margin-MSE step"}.get(loss, "lng_knp margin-MSE fine-tune step")
         print(json.dumps({"task": task + " (forward + backward + gradient all-reduce + AdamW), " + args.dims + " dims", "loss": loss,
                           "gemm_precision": precision, "n_gpus": world, "scaling": "weak", "bz_per_gpu": bz,
-                          "bz": bz, "L": L, "enc_len_padded": int(Lq), "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
+                          "bz": bz, "L": L, "enc_len_padded": int(dense_ids.shape[2] if loss == "dense" else Lq), **extra, "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
                           "loss_first": [float(x) for x in first], "loss_last": [float(x) for x in last],
                           "params": state.total, "approx_tflops": 3 * flops_fwd / dt / 1e12,
                           "backward_kernel_ms": {k: round(v["total_ms"], 3) for k, v in st.items()}}), flush=True)
