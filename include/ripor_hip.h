@@ -671,6 +671,53 @@ typedef struct rpr_tail_self_attn_op {
   int32_t anc_ld, num_buckets, max_distance, nseq_cap, B, H, T, L, dkv;
 } rpr_tail_self_attn_op;
 int rpr_op_tail_self_attn(rpr_ctx* ctx, const rpr_tail_self_attn_op* op, int32_t* out_kernel, void* stream);
+/* ---- attention test hooks of the training step: the backward of both attention sites and their forward with dropped-out
+ * probabilities, each through the site's own planner (plan_train_*) and launcher, reported and refused as above. fp32 only.
+ * The dropout of the probabilities is the step's (DESIGN.md "Dropout in the training step"): the key is built from rate,
+ * seed and step as rpr_set_train_dropout's is, `site` is the 16-bit site of the probabilities and L the positions per
+ * sequence of the mask's coordinates (query row r of a block is position r % L of sequence block * (rows / L) + r / L;
+ * self-attention: L = Ls). rate = 0: no dropout (the two backward hooks; the two drop-forward hooks refuse it). */
+typedef struct rpr_attn_drop {
+  uint64_t seed, step;
+  float rate;               /* 0 <= rate < 1 */
+  int32_t site, L;
+} rpr_attn_drop;
+/* Self-attention over S sequences of Ls rows (encoder: bidirectional buckets, key mask; causal: the teacher-forced decoder).
+ * rpr_op_train_self_attn_bwd (launch_self_attn_bwd) reads qkv, dO and writes dqkv and dbias += the relative-bias gradient
+ * (its per-(sequence, head) parts go through ctx scratch as in the step); rpr_op_train_self_attn_drop_fwd
+ * (launch_self_attn_drop_fwd) reads qkv and writes out. */
+typedef struct rpr_train_self_attn_op {
+  const float* qkv;         /* [S * Ls, 3 * H * dkv]: q | k | v */
+  const float* dO;          /* [S * Ls, H * dkv] (backward) */
+  const int32_t* mask;      /* [S, Ls] key mask; NULL with causal */
+  const float* rel_bias;    /* [num_buckets, H] */
+  float* dqkv;              /* [S * Ls, 3 * H * dkv] (backward) */
+  float* dbias;             /* [num_buckets, H], added to (backward) */
+  float* out;               /* [S * Ls, H * dkv] (drop-forward) */
+  rpr_attn_drop drop;
+  int32_t num_buckets, max_distance, S, Ls, H, dkv, causal;
+} rpr_train_self_attn_op;
+int rpr_op_train_self_attn_bwd(rpr_ctx* ctx, const rpr_train_self_attn_op* op, int32_t* out_kernel, void* stream);
+int rpr_op_train_self_attn_drop_fwd(rpr_ctx* ctx, const rpr_train_self_attn_op* op, int32_t* out_kernel, void* stream);
+/* Cross-attention of the n = docs x L decoder rows of each of bz queries against the query's Lq encoder rows (K row
+ * (query, j) at xk + (query * Lq + j) * xld, V likewise at xv). rpr_op_train_cross_attn_bwd (launch_cross_attn_bwd) reads q,
+ * dO and writes dq and, in the layout of xk / xv, dxk and dxv (the head's dkv columns of every row, nothing else of the row);
+ * rpr_op_train_cross_attn_drop_fwd (launch_cross_attn_drop_fwd) reads q and writes out. The key mask is required. */
+typedef struct rpr_train_cross_attn_op {
+  const float* q;           /* [bz * n, H * dkv] */
+  const float* dO;          /* [bz * n, H * dkv] (backward) */
+  const float* xk;
+  const float* xv;
+  const int32_t* mask;      /* [bz, Lq] */
+  float* dq;                /* [bz * n, H * dkv] (backward) */
+  float* dxk;               /* rows of xld floats (backward) */
+  float* dxv;
+  float* out;               /* [bz * n, H * dkv] (drop-forward) */
+  rpr_attn_drop drop;
+  int32_t xld, bz, n, Lq, H, dkv;
+} rpr_train_cross_attn_op;
+int rpr_op_train_cross_attn_bwd(rpr_ctx* ctx, const rpr_train_cross_attn_op* op, int32_t* out_kernel, void* stream);
+int rpr_op_train_cross_attn_drop_fwd(rpr_ctx* ctx, const rpr_train_cross_attn_op* op, int32_t* out_kernel, void* stream);
 /* Name of an AttnKernel value (csrc/attn_route.h RPR_ATTN_KERNELS), NULL when out of range. Host only. */
 const char* rpr_attn_kernel_name(int kernel);
 /* Number of AttnKernel values (names 0 .. n - 1). Host only. */

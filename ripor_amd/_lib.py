@@ -111,6 +111,23 @@ class TailSelfAttnOp(C.Structure):
                           ("anc_ld", "num_buckets", "max_distance", "nseq_cap", "B", "H", "T", "L", "dkv"))
 
 
+class AttnDrop(C.Structure):
+    """``rpr_attn_drop``: the dropout of the probabilities of a training attention hook (rate 0 = none)."""
+    _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("rate", C.c_float), ("site", C.c_int32), ("L", C.c_int32)]
+
+
+class TrainSelfAttnOp(C.Structure):
+    """``rpr_train_self_attn_op`` (rpr_op_train_self_attn_bwd, rpr_op_train_self_attn_drop_fwd)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("qkv", "dO", "mask", "rel_bias", "dqkv", "dbias", "out")] + [("drop", AttnDrop)] +
+                [(n, C.c_int32) for n in ("num_buckets", "max_distance", "S", "Ls", "H", "dkv", "causal")])
+
+
+class TrainCrossAttnOp(C.Structure):
+    """``rpr_train_cross_attn_op`` (rpr_op_train_cross_attn_bwd, rpr_op_train_cross_attn_drop_fwd)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("q", "dO", "xk", "xv", "mask", "dq", "dxk", "dxv", "out")] + [("drop", AttnDrop)] +
+                [(n, C.c_int32) for n in ("xld", "bz", "n", "Lq", "H", "dkv")])
+
+
 CROSS_SITE_BLOCK, CROSS_SITE_STEP, CROSS_SITE_TAIL = 0, 1, 2
 
 # every symbol include/ripor_hip.h declares: (restype, argtypes)
@@ -119,6 +136,10 @@ SIGNATURES = {
     "rpr_op_dec_self_attn": (C.c_int, [C.c_void_p, C.POINTER(DecSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
     "rpr_op_cross_attn": (C.c_int, [C.c_void_p, C.POINTER(CrossAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
     "rpr_op_tail_self_attn": (C.c_int, [C.c_void_p, C.POINTER(TailSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_train_self_attn_bwd": (C.c_int, [C.c_void_p, C.POINTER(TrainSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_train_self_attn_drop_fwd": (C.c_int, [C.c_void_p, C.POINTER(TrainSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_train_cross_attn_bwd": (C.c_int, [C.c_void_p, C.POINTER(TrainCrossAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_train_cross_attn_drop_fwd": (C.c_int, [C.c_void_p, C.POINTER(TrainCrossAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
     "rpr_attn_kernel_name": (C.c_char_p, [C.c_int]),
     "rpr_attn_kernel_count": (C.c_int, []),
     "rpr_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),

@@ -1221,6 +1221,113 @@ int rpr_op_tail_self_attn(rpr_ctx* c, const rpr_tail_self_attn_op* o, int32_t* o
   return RPR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// the dropout block of a training attention hook -> the DropAttn the step hands its launchers (dropout.h); *on = rate > 0
+int attn_op_drop(const rpr_attn_drop& d, DropAttn* da, bool* on) {
+  RPR_REQUIRE(d.rate >= 0.f && d.rate < 1.f, "dropout rate in [0, 1)");
+  *on = d.rate > 0.f;
+  RPR_REQUIRE(!*on || (d.site >= 0 && d.site < 65536 && d.L >= 0 && d.L <= 65536), "dropout site / L out of range");
+  *da = drop_attn(drop_key(d.rate, d.seed, d.step), d.site, d.L);
+  return RPR_OK;
+}
+
+int train_self_attn_op_common(const rpr_ctx* c, const rpr_train_self_attn_op* o) {
+  RPR_REQUIRE(c && o && o->qkv && o->rel_bias, "NULL argument");
+  RPR_REQUIRE(o->num_buckets >= 2 && o->num_buckets <= 64 && o->max_distance > o->num_buckets, "num_buckets / max_distance out of range");
+  RPR_REQUIRE(o->H >= 1 && (o->dkv == DKV || o->dkv == 128), "H >= 1, dkv 64 or 128");
+  RPR_REQUIRE(o->S >= 1 && o->Ls >= 1 && o->Ls <= MAX_LQ, "bad shape");
+  RPR_REQUIRE(o->causal ? o->mask == nullptr : o->mask != nullptr, "causal: no mask; bidirectional: a key mask");
+  RPR_REQUIRE(!o->causal || o->Ls <= MAX_DEC_LEN, "causal: Ls <= 64 (the unidirectional bucket table)");
+  return RPR_OK;
+}
+
+int train_cross_attn_op_common(const rpr_ctx* c, const rpr_train_cross_attn_op* o) {
+  RPR_REQUIRE(c && o && o->q && o->xk && o->xv && o->mask, "NULL argument");
+  RPR_REQUIRE(o->H >= 1 && (o->dkv == DKV || o->dkv == 128), "H >= 1, dkv 64 or 128");
+  RPR_REQUIRE(o->bz >= 1 && o->n >= 1 && o->Lq >= 1 && o->Lq <= MAX_LQ && o->xld >= o->H * o->dkv && (o->xld & 3) == 0, "bad shape");
+  return RPR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rpr_op_train_self_attn_bwd(rpr_ctx* c, const rpr_train_self_attn_op* o, int32_t* out_kernel, void* stream) {
+  if (const int e = train_self_attn_op_common(c, o)) return e;
+  RPR_REQUIRE(o->dO && o->dqkv && o->dbias, "NULL argument");
+  DropAttn da;
+  bool drop;
+  if (const int e = attn_op_drop(o->drop, &da, &drop)) return e;
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const TrainSelfAttnIn in{o->S, o->Ls, o->H, o->num_buckets, o->dkv, o->causal != 0, o->mask != nullptr, drop, drop ? da.L : 0};
+  if (const int e = attn_op_plan(plan_train_self_attn_bwd(in), out_kernel, "launch_self_attn_bwd")) return e;
+  BucketTmp bt;
+  if (const int e = o->causal ? make_bucket_tables(o->num_buckets, o->max_distance, nullptr, &bt.p)
+                              : make_bucket_tables(o->num_buckets, o->max_distance, &bt.p, nullptr)) return e;
+  // the per-(sequence, head) parts of the bias gradient, as the step keeps them
+  if (const int e = ensure(c, c->ws.tr_misc, (size_t)o->S * o->H * o->num_buckets * sizeof(float))) return e;
+  RPR_HIP(launch_self_attn_bwd(o->qkv, o->dO, o->mask, o->rel_bias, bt.p, o->dqkv, P<float>(c->ws.tr_misc), o->dbias, o->S, o->Ls, o->H,
+                               o->num_buckets, o->causal ? 1 : 0, s, drop ? &da : nullptr, o->dkv));
+  RPR_HIP(hipStreamSynchronize(s));   // the bucket table is freed when this scope ends
+  return RPR_OK;
+}
+
+int rpr_op_train_self_attn_drop_fwd(rpr_ctx* c, const rpr_train_self_attn_op* o, int32_t* out_kernel, void* stream) {
+  if (const int e = train_self_attn_op_common(c, o)) return e;
+  RPR_REQUIRE(o->out, "NULL argument");
+  DropAttn da;
+  bool drop;
+  if (const int e = attn_op_drop(o->drop, &da, &drop)) return e;
+  RPR_REQUIRE(drop, "the forward with dropped-out probabilities needs a rate > 0");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const TrainSelfAttnIn in{o->S, o->Ls, o->H, o->num_buckets, o->dkv, o->causal != 0, o->mask != nullptr, true, da.L};
+  if (const int e = attn_op_plan(plan_train_self_attn_drop_fwd(in), out_kernel, "launch_self_attn_drop_fwd")) return e;
+  BucketTmp bt;
+  if (const int e = o->causal ? make_bucket_tables(o->num_buckets, o->max_distance, nullptr, &bt.p)
+                              : make_bucket_tables(o->num_buckets, o->max_distance, &bt.p, nullptr)) return e;
+  RPR_HIP(launch_self_attn_drop_fwd(o->qkv, o->mask, o->rel_bias, bt.p, o->out, o->S, o->Ls, o->H, o->num_buckets, o->causal ? 1 : 0, da, s,
+                                    o->dkv));
+  RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
+int rpr_op_train_cross_attn_bwd(rpr_ctx* c, const rpr_train_cross_attn_op* o, int32_t* out_kernel, void* stream) {
+  if (const int e = train_cross_attn_op_common(c, o)) return e;
+  RPR_REQUIRE(o->dO && o->dq && o->dxk && o->dxv, "NULL argument");
+  DropAttn da;
+  bool drop;
+  if (const int e = attn_op_drop(o->drop, &da, &drop)) return e;
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const TrainCrossAttnIn in{o->bz, o->n, o->Lq, o->H, o->dkv, true, drop, drop ? da.L : 0};
+  if (const int e = attn_op_plan(plan_train_cross_attn_bwd(in), out_kernel, "launch_cross_attn_bwd")) return e;
+  RPR_HIP(launch_cross_attn_bwd(o->q, o->xk, o->xv, o->xld, o->mask, o->dO, o->dq, o->dxk, o->dxv, o->bz, o->n, o->Lq, o->H, s,
+                                drop ? &da : nullptr, o->dkv));
+  RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
+int rpr_op_train_cross_attn_drop_fwd(rpr_ctx* c, const rpr_train_cross_attn_op* o, int32_t* out_kernel, void* stream) {
+  if (const int e = train_cross_attn_op_common(c, o)) return e;
+  RPR_REQUIRE(o->out, "NULL argument");
+  DropAttn da;
+  bool drop;
+  if (const int e = attn_op_drop(o->drop, &da, &drop)) return e;
+  RPR_REQUIRE(drop, "the forward with dropped-out probabilities needs a rate > 0");
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const TrainCrossAttnIn in{o->bz, o->n, o->Lq, o->H, o->dkv, true, true, da.L};
+  if (const int e = attn_op_plan(plan_train_cross_attn_drop_fwd(in), out_kernel, "launch_cross_attn_drop_fwd")) return e;
+  RPR_HIP(launch_cross_attn_drop_fwd(o->q, o->xk, o->xv, o->xld, o->mask, o->out, o->bz, o->n, o->Lq, o->H, da, s, o->dkv));
+  RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
 const char* rpr_attn_kernel_name(int kernel) { return kernel >= 0 && kernel < ATTN_KERNEL_COUNT ? attn_kernel_name(kernel) : nullptr; }
 int rpr_attn_kernel_count(void) { return ATTN_KERNEL_COUNT; }
 

@@ -16,6 +16,7 @@
 // (after the final norm), 8 + 8 layer + 2 j = the middle of sub-block j (attention probabilities, or the feed-forward's
 // relu(h Wi^T)), 8 + 8 layer + 2 j + 1 = the sub-block's output before the residual is added.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -34,6 +35,16 @@ struct DropKey {
 // what an attention kernel is handed: the site of its probabilities; L = decoder positions per sequence (cross-attention, whose
 // blocks hold all the decoder rows of a query: row r is position r % L of sequence query * n_docs + r / L)
 struct DropAttn { DropKey key; int site, L; };
+
+// the key of one pass (host): 0 <= rate < 1, checked by the entry points
+inline DropKey drop_key(float rate, uint64_t seed, uint64_t step) {
+  DropKey key{};
+  key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(step >> 32); key.step_lo = (uint32_t)step;
+  key.thr = (uint32_t)llrint((double)rate * 4294967296.0);
+  key.scale = 1.0f / (1.0f - rate);
+  return key;
+}
+inline DropAttn drop_attn(const DropKey& key, int site, int L) { return DropAttn{key, site, L}; }
 
 RPR_HD int drop_site(int dec, int code) { return (dec << 11) | code; }
 RPR_HD int drop_site_input(int dec) { return drop_site(dec, 0); }

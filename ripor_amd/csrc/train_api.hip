@@ -342,11 +342,7 @@ struct Drop {
   DropKey key{};
   bool on = false;
   Drop() = default;
-  Drop(float rate, uint64_t seed, uint64_t step) : on(rate > 0.f) {   // 0 <= rate < 1 (checked by the entry points)
-    key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(step >> 32); key.step_lo = (uint32_t)step;
-    key.thr = (uint32_t)llrint((double)rate * 4294967296.0);
-    key.scale = 1.0f / (1.0f - rate);
-  }
+  Drop(float rate, uint64_t seed, uint64_t step) : key(drop_key(rate, seed, step)), on(rate > 0.f) {}   // dropout.h
   explicit Drop(const rpr_ctx* c) : Drop(c->train_drop.rate, c->train_drop.seed, c->train_drop.step) {}
   // out = (resid +) mask(x) over the rows [nseq * len][nfeat] of nseq sequences of len positions
   void rows(Launcher& Ln, int nseq, int len, const float* x, const float* resid, float* out, int nfeat, int site) const {
@@ -356,7 +352,7 @@ struct Drop {
   void rows(Launcher& Ln, const Stack& k, const float* x, const float* resid, float* out, int nfeat, int site) const {
     rows(Ln, k.nseq, k.len, x, resid, out, nfeat, site);
   }
-  DropAttn attn(int site, int L) const { return DropAttn{key, site, L}; }
+  DropAttn attn(int site, int L) const { return drop_attn(key, site, L); }
 };
 
 // bf16 copies of every GEMM weight, refreshed at the start of each pass (the weights change between passes: AdamW, or the

@@ -267,6 +267,44 @@ class Context:
                                  B, H, T, L, dkv)
         return self._attn_op("rpr_op_tail_self_attn", op, qkv.device)
 
+    # -- the training step's attention (rpr_op_train_*_attn_*): drop = None or (rate, seed, step, site, L)
+    @staticmethod
+    def _attn_drop(drop):
+        if drop is None:
+            return _lib.AttnDrop(0, 0, 0.0, 0, 0)
+        rate, seed, step, site, L = drop
+        return _lib.AttnDrop(int(seed), int(step), float(rate), int(site), int(L))
+
+    def _train_self_attn_op(self, qkv, dO, mask, rel_bias, dqkv, dbias, out, S, Ls, H, dkv, num_buckets, max_distance, causal, drop):
+        p = lambda t: t.data_ptr() if t is not None else None
+        return _lib.TrainSelfAttnOp(p(qkv), p(dO), p(mask), p(rel_bias), p(dqkv), p(dbias), p(out), self._attn_drop(drop),
+                                    num_buckets, max_distance, S, Ls, H, dkv, 1 if causal else 0)
+
+    def train_self_attn_bwd(self, qkv, dO, mask, rel_bias, dqkv, dbias, S, Ls, H, dkv=64, num_buckets=32, max_distance=128,
+                            causal=False, drop=None) -> str:
+        """dqkv is written, dbias [num_buckets, H] is added to."""
+        op = self._train_self_attn_op(qkv, dO, mask, rel_bias, dqkv, dbias, None, S, Ls, H, dkv, num_buckets, max_distance, causal, drop)
+        return self._attn_op("rpr_op_train_self_attn_bwd", op, qkv.device)
+
+    def train_self_attn_drop_fwd(self, qkv, mask, rel_bias, out, S, Ls, H, drop, dkv=64, num_buckets=32, max_distance=128,
+                                 causal=False) -> str:
+        op = self._train_self_attn_op(qkv, None, mask, rel_bias, None, None, out, S, Ls, H, dkv, num_buckets, max_distance, causal, drop)
+        return self._attn_op("rpr_op_train_self_attn_drop_fwd", op, qkv.device)
+
+    def _train_cross_attn_op(self, q, dO, xk, xv, xld, mask, dq, dxk, dxv, out, bz, n, Lq, H, dkv, drop):
+        p = lambda t: t.data_ptr() if t is not None else None
+        return _lib.TrainCrossAttnOp(p(q), p(dO), p(xk), p(xv), p(mask), p(dq), p(dxk), p(dxv), p(out), self._attn_drop(drop),
+                                     xld, bz, n, Lq, H, dkv)
+
+    def train_cross_attn_bwd(self, q, dO, xk, xv, xld, mask, dq, dxk, dxv, bz, n, Lq, H, dkv=64, drop=None) -> str:
+        """dxk / dxv: rows of xld floats like xk / xv; only the head columns of a row are written."""
+        op = self._train_cross_attn_op(q, dO, xk, xv, xld, mask, dq, dxk, dxv, None, bz, n, Lq, H, dkv, drop)
+        return self._attn_op("rpr_op_train_cross_attn_bwd", op, q.device)
+
+    def train_cross_attn_drop_fwd(self, q, xk, xv, xld, mask, out, bz, n, Lq, H, drop, dkv=64) -> str:
+        op = self._train_cross_attn_op(q, None, xk, xv, xld, mask, None, None, None, out, bz, n, Lq, H, dkv, drop)
+        return self._attn_op("rpr_op_train_cross_attn_drop_fwd", op, q.device)
+
 
 class StatusTicket:
     """Status words of a ctx as of one point of a stream (``Context.status_async``)."""

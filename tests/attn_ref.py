@@ -63,6 +63,31 @@ def bucket_of(rel: np.ndarray, bidirectional: bool, num_buckets: int = NB, max_d
 
 
 # ---------------------------------------------------------------------------------------------- the operation itself
+def softmax_eps(q, K, bias, ok, qk, dtype=np.float64, want_eps=True):
+    """The weights of `attend` and their relative error bound: (p [R, n], eps_p [R] or None, attended keys [R]); qk(a, b) is
+    the product of q rows with K rows in K's layout. Shared with tests/attn_train_ref.py, whose bound starts from eps_p."""
+    D = q.shape[1]
+    q = q.astype(dtype)
+    s = qk(q, K)
+    if bias is not None:
+        s = s + bias.astype(dtype)
+    has = ok.any(axis=1)
+    neg = np.where(ok, s, -np.inf)
+    mx = np.where(has, neg.max(axis=1, initial=-np.inf), 0).astype(dtype)
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.where(ok, np.exp(np.where(ok, s, 0) - mx[:, None]), 0).astype(dtype)
+    sm = e.sum(axis=1)
+    p = np.where(has[:, None], e / np.where(sm > 0, sm, 1)[:, None], 0).astype(dtype)
+    cnt = ok.sum(axis=1)
+    if not want_eps:
+        return p, None, cnt
+    A = qk(np.abs(q), np.abs(K)) + (np.abs(bias) if bias is not None else 0)
+    ds = (D + 2) * U * np.where(ok, A, 0).max(axis=1, initial=0)
+    spread = np.where(has, mx - np.where(ok, s, np.inf).min(axis=1, initial=np.inf), 0)
+    eps = 2 * ds + 2 * U * np.minimum(spread, 104) + (cnt + 8) * U
+    return p, eps, cnt
+
+
 def attend(q, K, V, bias, ok, dtype=np.float64, want_bound=True):
     """q [R, D]; K, V [R or 1, n, D]; bias [R, n] or None; ok [R, n] bool (attended). Returns (out [R, D], bound [R, D]);
     dtype float32 is the plain numpy fp32 evaluation of the same expression (its bound is not meaningful)."""
@@ -79,25 +104,10 @@ def attend(q, K, V, bias, ok, dtype=np.float64, want_bound=True):
         V = np.where(okb, np.broadcast_to(V, (R, n, D)), 0).astype(dtype)
         qk = lambda a, b: np.einsum("rd,rnd->rn", a, b)
         pv = lambda a, b: np.einsum("rn,rnd->rd", a, b)
-    q = q.astype(dtype)
-    s = qk(q, K)
-    if bias is not None:
-        s = s + bias.astype(dtype)
-    has = ok.any(axis=1)
-    neg = np.where(ok, s, -np.inf)
-    mx = np.where(has, neg.max(axis=1, initial=-np.inf), 0).astype(dtype)
-    with np.errstate(over="ignore", invalid="ignore"):
-        e = np.where(ok, np.exp(np.where(ok, s, 0) - mx[:, None]), 0).astype(dtype)
-    sm = e.sum(axis=1)
-    p = np.where(has[:, None], e / np.where(sm > 0, sm, 1)[:, None], 0).astype(dtype)
+    p, eps, cnt = softmax_eps(q, K, bias, ok, qk, dtype, want_bound)
     out = pv(p, V)
     if not want_bound:
         return out, None
-    A = qk(np.abs(q), np.abs(K)) + (np.abs(bias) if bias is not None else 0)
-    ds = (D + 2) * U * np.where(ok, A, 0).max(axis=1, initial=0)
-    spread = np.where(has, mx - np.where(ok, s, np.inf).min(axis=1, initial=np.inf), 0)
-    cnt = ok.sum(axis=1)
-    eps = 2 * ds + 2 * U * np.minimum(spread, 104) + (cnt + 8) * U
     absV = np.abs(V)
     bound = pv(p, absV) * (eps + (cnt + 1) * U)[:, None] + 2.0 ** -120 * pv(ok.astype(dtype), absV)
     return out, bound
@@ -626,8 +636,9 @@ def build_cases() -> List[Case]:
 
 
 CASES = build_cases()
-# every name of RPR_ATTN_KERNELS except: NONE; the training backward and its tiled forward (checked against autograd by
-# test_gpu_train.py / test_gpu_long_queries.py); TAIL_CROSS_G1_NKT1 (reachable only with a development switch)
+# every name of RPR_ATTN_KERNELS except: NONE; TAIL_CROSS_G1_NKT1 (reachable only with a development switch); the training
+# backward and the forward with dropped-out probabilities, 13 kernels, which tests/test_gpu_attn_train_direct.py takes one by
+# one against tests/attn_train_ref.py (and test_gpu_train.py / test_gpu_long_queries.py through whole steps against autograd)
 OUT_OF_SCOPE = {"NONE", "TAIL_CROSS_G1_NKT1", "TRAIN_BWD_MFMA", "TRAIN_BWD_VALU", "TRAIN_BWD_VALU128", "TRAIN_SELF_BWD_TILED",
                 "TRAIN_CROSS_BWD_TILED", "TRAIN_SELF_DROP_FWD_TILED", "TRAIN_CROSS_DROP_FWD_TILED", "TRAIN_CROSS_BWD", "TRAIN_CROSS_BWD128",
                 "TRAIN_SELF_DROP_FWD", "TRAIN_SELF_DROP_FWD128", "TRAIN_CROSS_DROP_FWD", "TRAIN_CROSS_DROP_FWD128"}

@@ -1,6 +1,7 @@
 // Prints the launch plan of an attention site (ripor_amd/csrc/attn_route.h) for tests/test_attn_route.py.
 //   site key=value ...      one JSON object: the plan for these inputs / tuning overrides (gen, enc_mfma, step_cross)
-//   sites: enc, dec_self, cross_block, tail_self, tail_cross, step_cross, bwd
+//   sites: enc, dec_self, cross_block, tail_self, tail_cross, step_cross, bwd, and the four of the training step:
+//          train_self_bwd, train_self_drop_fwd, train_cross_bwd, train_cross_drop_fwd
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,8 @@ int main(int argc, char** argv) {
   CrossAttnIn c;
   TailSelfAttnIn ts;
   SelfAttnBwdIn b;
+  TrainSelfAttnIn tsf;
+  TrainCrossAttnIn tc;
   AttnTuning t;
   for (int i = 2; i < argc; ++i) {
     const char* eq = strchr(argv[i], '=');
@@ -32,6 +35,12 @@ int main(int argc, char** argv) {
     if (site == "cross_block" || site == "tail_cross" || site == "step_cross") { F(c, Q) F(c, B) F(c, H) F(c, Lq) F(c, dkv) }
     if (site == "tail_self") { F(ts, nseq_cap) F(ts, B) F(ts, H) F(ts, T) F(ts, L) F(ts, dkv) }
     if (site == "bwd") { F(b, S) F(b, Ls) F(b, H) F(b, buckets) }
+    if (site == "train_self_bwd" || site == "train_self_drop_fwd") {
+      F(tsf, S) F(tsf, Ls) F(tsf, H) F(tsf, buckets) F(tsf, dkv) F(tsf, causal) F(tsf, mask) F(tsf, drop) F(tsf, drop_L)
+    }
+    if (site == "train_cross_bwd" || site == "train_cross_drop_fwd") {
+      F(tc, bz) F(tc, n) F(tc, Lq) F(tc, H) F(tc, dkv) F(tc, mask) F(tc, drop) F(tc, drop_L)
+    }
 #undef F
     if (!ok) { fprintf(stderr, "bad argument %s\n", argv[i]); return 2; }
   }
@@ -43,6 +52,10 @@ int main(int argc, char** argv) {
   else if (site == "step_cross") p = plan_step_cross_attn(c, t);
   else if (site == "tail_self") p = plan_tail_self_attn(ts, t);
   else if (site == "bwd") p = plan_self_attn_bwd(b);
+  else if (site == "train_self_bwd") p = plan_train_self_attn_bwd(tsf);
+  else if (site == "train_self_drop_fwd") p = plan_train_self_attn_drop_fwd(tsf);
+  else if (site == "train_cross_bwd") p = plan_train_cross_attn_bwd(tc);
+  else if (site == "train_cross_drop_fwd") p = plan_train_cross_attn_drop_fwd(tc);
   else return 2;
   printf("{\"kernel\": \"%s\", \"invalid\": %d, \"grid\": [%u, %u], \"block\": %d, \"smem\": %zu, \"HB\": %d, \"groups\": %d, \"tpw\": %d, "
          "\"tiles\": %d, \"bchunk\": %d}\n",

@@ -41,14 +41,21 @@ def test_struct_layout_matches_header():
     assert C.sizeof(_lib.DecSelfAttnOp) == 8 * 8 + 5 * 8 + 8 * 4
     assert C.sizeof(_lib.CrossAttnOp) == 8 * 8 + 1 * 8 + 7 * 4 + 4
     assert C.sizeof(_lib.TailSelfAttnOp) == 10 * 8 + 5 * 8 + 9 * 4 + 4
+    # the training hooks: pointers, the dropout block (two uint64, a float, two int32, padded to 32 bytes), then int32
+    assert C.sizeof(_lib.AttnDrop) == 2 * 8 + 4 + 2 * 4 + 4
+    assert C.sizeof(_lib.TrainSelfAttnOp) == 7 * 8 + 32 + 7 * 4 + 4
+    assert C.sizeof(_lib.TrainCrossAttnOp) == 9 * 8 + 32 + 6 * 4
 
 
 def test_attention_hook_descriptors_match_header():
-    """Field names and order of the four rpr_*_attn_op structs in include/ripor_hip.h against the ctypes mirrors."""
+    """Field names and order of the rpr_*_attn_op structs in include/ripor_hip.h (the four of the search path, the two of the
+    training step and their dropout block) against the ctypes mirrors."""
     from ripor_amd import _lib
     hdr = open(os.path.join(REPO, "include", "ripor_hip.h")).read()
     for cname, cls in (("rpr_enc_attn_op", _lib.EncAttnOp), ("rpr_dec_self_attn_op", _lib.DecSelfAttnOp),
-                       ("rpr_cross_attn_op", _lib.CrossAttnOp), ("rpr_tail_self_attn_op", _lib.TailSelfAttnOp)):
+                       ("rpr_cross_attn_op", _lib.CrossAttnOp), ("rpr_tail_self_attn_op", _lib.TailSelfAttnOp),
+                       ("rpr_attn_drop", _lib.AttnDrop), ("rpr_train_self_attn_op", _lib.TrainSelfAttnOp),
+                       ("rpr_train_cross_attn_op", _lib.TrainCrossAttnOp)):
         body = hdr[hdr.index("typedef struct " + cname + " {"):hdr.index("} " + cname + ";")].split("{", 1)[1]
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
@@ -56,11 +63,13 @@ def test_attention_hook_descriptors_match_header():
             decl = decl.strip()
             if not decl:
                 continue
-            typ = "ptr" if "*" in decl else "i64" if decl.startswith("int64_t") else "i32"
+            typ = ("ptr" if "*" in decl else "i64" if decl.startswith("int64_t") else "u64" if decl.startswith("uint64_t") else
+                   "f32" if decl.startswith("float") else "drop" if decl.startswith("rpr_attn_drop") else "i32")
             assert typ != "i32" or decl.startswith("int32_t"), decl
             names = decl.replace("*", " ").split(None, 2 if decl.startswith("const") else 1)[-1]
             fields += [(n.strip(), typ) for n in names.split(",")]
-        want = [(n, {C.c_void_p: "ptr", C.c_int64: "i64", C.c_int32: "i32"}[t]) for n, t in cls._fields_]
+        want = [(n, {C.c_void_p: "ptr", C.c_int64: "i64", C.c_int32: "i32", C.c_uint64: "u64", C.c_float: "f32", _lib.AttnDrop: "drop"}[t])
+                for n, t in cls._fields_]
         assert fields == want, (cname, fields, want)
 
 

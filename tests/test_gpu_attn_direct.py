@@ -18,8 +18,10 @@ definition lies 30x or more beyond the bound on every (query, head) it applies t
 
 Out of scope, so that the uncovered names are explicit (attn_ref.OUT_OF_SCOPE): TAIL_CROSS_G1_NKT1 is reachable only with a
 development switch; TRAIN_BWD_MFMA / _VALU / _VALU128, TRAIN_CROSS_BWD(128), TRAIN_SELF_DROP_FWD(128), TRAIN_CROSS_DROP_FWD(128)
-and the four *_TILED kernels are the training backward and the forward with dropout, which test_gpu_train.py, test_gpu_dropout.py,
-test_gpu_heads128.py and test_gpu_long_queries.py check against autograd and test_gpu_train_bits.py holds bit for bit. The last test of the file asserts
+and the four *_TILED kernels are the training backward and the forward with dropout: tests/test_gpu_attn_train_direct.py takes
+each of them through a hook of its own against the fp64 definition of tests/attn_train_ref.py (test_gpu_train.py, test_gpu_dropout.py,
+test_gpu_heads128.py and test_gpu_long_queries.py check them through whole steps against autograd, test_gpu_train_bits.py holds
+the steps bit for bit). The last test of the file asserts
 that every other name of RPR_ATTN_KERNELS was reported by a case of this run and prints the worst |got - ref| / bound per
 kernel (run with -s)."""
 import numpy as np
