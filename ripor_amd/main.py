@@ -17,7 +17,7 @@ import torch
 
 
 def base_parser(loss_type, run_name):
-    """The flags every training entry point takes (this module and main_dense)."""
+    """The flags every training entry point takes (this module, main_dense and main_rank)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--loss_type", default=loss_type)
     ap.add_argument("--model_type", default="t5_docid_gen_encoder")
@@ -119,7 +119,8 @@ def main(argv=None):
     built = ("t5seq_aq_encoder_lng_knp_margin_mse", "t5seq_aq_encoder_seq2seq")
     if args.loss_type not in built or args.model_type != "t5_docid_gen_encoder":
         raise NotImplementedError(f"loss_type {args.loss_type!r} is outside this repository's path (SURVEY.md §2); "
-                                  f"built: {', '.join(built)} (t5seq_pretrain_margin_mse: python -m t5_pretrainer.main_dense)")
+                                  f"built: {', '.join(built)} (t5seq_pretrain_margin_mse: python -m t5_pretrainer.main_dense; "
+                                  f"t5seq_aq_encoder_margin_mse: python -m t5_pretrainer.main_rank)")
     seq2seq = args.loss_type == "t5seq_aq_encoder_seq2seq"
     need = ("query_to_docid_path", "docid_to_smtid_path") if seq2seq else ("teacher_score_path", "queries_path")
     missing = [f"--{n}" for n in need if not getattr(args, n)]

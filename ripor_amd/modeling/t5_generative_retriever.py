@@ -294,6 +294,65 @@ class T5SeqAQEncoder:
         embeds = torch.stack([sd[f"{name}.{i}.weight"].cpu()[enc[:, i]] for i in range(enc.shape[1])], dim=1)
         return embeds.sum(dim=1) if summation else embeds
 
+    def _position_pass(self, input_ids, attention_mask, codes, teacher_pos=None, teacher_neg=None, prefix_lens=None):
+        """``engine.lngknp_forward`` of ``codes [bz, n_docs, L]`` under the guard of the search path (tasks/generation.py): the
+        pass runs on the static-scale f16 planes; an activation outside their range is clamped and flagged (a residual row under
+        their RMS floor is flagged too), and the pass is then repeated on the exact-fp32 GEMMs.
+        -> (losses [n_prefix] or None, position scores [bz, n_docs, L])."""
+        from .. import engine as E
+        em = self.base_model.engine_model()
+        ctx = em.ctx
+        ctx.clear_status_async()
+        args = (em, input_ids, attention_mask, codes, teacher_pos, teacher_neg, prefix_lens)
+        out = E.lngknp_forward(*args)
+        st = ctx.status(clear=True)
+        if st & E._lib.STATUS_EMPTY_QUERY:
+            raise ValueError("a query has an all-zero attention_mask (no token to attend to)")
+        if (st & E._lib.STATUS_NEEDS_F32) and ctx.get_precision() != "f32":
+            import warnings
+            warnings.warn(("activation outside the f16 plane range" if st & E._lib.STATUS_SATURATED else
+                           "residual stream under the RMS floor") + " of the split-precision GEMMs: repeating this forward "
+                          "with exact fp32 MFMA (RPR_PRECISION=f32 avoids the retry)")
+            saved = ctx.get_precision()   # "f16x2" or "bf16" (a training ctx): whatever it was comes back
+            ctx.set_precision("f32")
+            try:
+                out = E.lngknp_forward(*args)
+                ctx.status(clear=True)
+            finally:
+                ctx.set_precision(saved)
+        return out
+
+    def rerank_forward(self, **inputs):
+        """reference :794-798: the score of one smtid per query, ``sum_i <decoder_last_hidden_state[:, i], E_out[i][c_i]>``, for
+        ``tokenized_query`` (with ``decoder_input_ids`` = the encoding shifted right) and ``doc_encoding [bz, L]``
+        -> fp32 ``[bz]``. One teacher-forced pass of ``rpr_lngknp_forward`` without a loss.
+
+        The smtid goes into both document slots of the pass a training forward makes, and the first is read: a score is then
+        bit for bit what ``forward`` gives the same (query, smtid) pair as its positive or its negative. With one slot the
+        decoder GEMMs would see half the rows, and the split-precision GEMM picks its kernel, and with it the order of its
+        sums, by the row count (gemm_route.h: 32 rows and fewer go to the skinny kernel): the last bit of a score would depend
+        on whether bz * L crosses that line."""
+        tq, codes = inputs["tokenized_query"], inputs["doc_encoding"]
+        _check_smtid_length(codes.size(1), self.config)
+        _check_shifted_right("tokenized_query", tq["decoder_input_ids"], codes)
+        _, pos_scores = self._position_pass(tq["input_ids"], tq["attention_mask"], torch.stack([codes, codes], dim=1))
+        return pos_scores[:, 0].sum(dim=-1)
+
+
+def _check_shifted_right(name, decoder_input_ids, codes):
+    if not torch.equal(decoder_input_ids[:, 1:].to(codes.device), codes[:, :-1]):
+        raise ValueError(f"{name}: decoder_input_ids must be the doc encoding shifted right (dataset.py:497-500)")
+
+
+def _check_smtid_length(L, config):
+    """An smtid of any length the decoder has positions for. One code alone (the dense view, query_encode) is not a case of
+    the teacher-forced passes."""
+    n = len(config.decoder_vocab_sizes)
+    if L == 1:
+        raise ValueError("smtid length 1 is not built: the teacher-forced passes take smtids of 2 codes or more")
+    if not 2 <= L <= n:
+        raise ValueError(f"not valid length: {L} (the model decodes {n} positions)")
+
 
 class T5AQEncoder(T5SeqAQEncoder):
     """reference :886-900: the dense view of the same model — ``query_encode`` as above, ``decode`` summed over the levels
@@ -396,74 +455,39 @@ class T5SeqPretrainEncoder(T5SeqAQEncoder):
         return {"rank": loss[0]}
 
 
-class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
-    """reference :902-966 — forward of the prefix-oriented ranking fine-tune step (SURVEY.md §8 row f4), same
-    ``forward(**inputs)`` dict interface and return keys (``rank``, ``rank_4``, ``rank_8``, ``rank_16``). The whole
-    pass runs in ``rpr_lngknp_forward`` (teacher-forced decoder over all positions of the positive and the negative
-    smtid at once, one encoder pass per query). Forward only: no autograd graph is attached to the returned losses."""
+class _MarginMSEOverPrefixes(T5SeqAQEncoder):
+    """What the two margin-MSE ranking steps share: the batch guards, the forward through ``rpr_lngknp_forward`` and the training
+    step through ``rpr_lngknp_backward`` + ``rpr_adamw_step``. A subclass says which prefixes of the smtid carry a loss:
+    ``_prefixes(L) -> [(prefix length, prefix of the teacher-score keys), ...]``, the full length first."""
 
-    _PREFIXES = {8: [(8, ""), (4, "smtid_4_")], 16: [(16, ""), (4, "smtid_4_"), (8, "smtid_8_")],
-                 32: [(32, ""), (4, "smtid_4_"), (8, "smtid_8_"), (16, "smtid_16_")]}
+    def _prefixes(self, L):
+        raise NotImplementedError
 
-    def forward(self, **inputs):
-        from .. import engine as E
+    def _batch(self, inputs, check_shift=False):
         pos_q, neg_q = inputs["pos_tokenized_query"], inputs["neg_tokenized_query"]
         pos_codes, neg_codes = inputs["pos_doc_encoding"], inputs["neg_doc_encoding"]
         L = pos_codes.size(1)
-        if L not in self._PREFIXES:
-            raise ValueError("not valid length: {}".format(L))
-        if not (torch.equal(pos_q["input_ids"], neg_q["input_ids"])):
+        prefixes = self._prefixes(L)
+        if not torch.equal(pos_q["input_ids"], neg_q["input_ids"]):
             # dataset.py:502-503 builds both from the same query text; two different texts would need two encoder passes
             raise ValueError("pos_tokenized_query and neg_tokenized_query must carry the same query tokens")
-        for side, q, codes in (("pos", pos_q, pos_codes), ("neg", neg_q, neg_codes)):
-            di = q["decoder_input_ids"]
-            if not torch.equal(di[:, 1:].to(codes.device), codes[:, :-1]):
-                raise ValueError(f"{side}: decoder_input_ids must be the doc encoding shifted right (dataset.py:497-500)")
-        names = ["rank" if k == L else f"rank_{k}" for k, _ in self._PREFIXES[L]]
-        tp = torch.stack([inputs[p + "teacher_pos_scores"] for _, p in self._PREFIXES[L]]).float()
-        tn = torch.stack([inputs[p + "teacher_neg_scores"] for _, p in self._PREFIXES[L]]).float()
-        codes = torch.stack([pos_codes, neg_codes], dim=1)
-        em = self.base_model.engine_model()
-        ctx = em.ctx
-        ctx.clear_status_async()
-        args = (em, pos_q["input_ids"], pos_q["attention_mask"], codes, tp, tn, [k for k, _ in self._PREFIXES[L]])
-        losses, self.last_position_scores = E.lngknp_forward(*args)
-        # same guard as the search path (tasks/generation.py): this forward runs on the static-scale f16 planes; an
-        # activation outside their range is clamped and flagged (a residual row under their RMS floor is flagged too), and the
-        # pass is then repeated on the exact-fp32 GEMMs
-        st = ctx.status(clear=True)
-        if st & E._lib.STATUS_EMPTY_QUERY:
-            raise ValueError("a query has an all-zero attention_mask (no token to attend to)")
-        if (st & E._lib.STATUS_NEEDS_F32) and ctx.get_precision() != "f32":
-            import warnings
-            warnings.warn(("activation outside the f16 plane range" if st & E._lib.STATUS_SATURATED else
-                           "residual stream under the RMS floor") + " of the split-precision GEMMs: repeating this forward "
-                          "with exact fp32 MFMA (RPR_PRECISION=f32 avoids the retry)")
-            saved = ctx.get_precision()   # "f16x2" or "bf16" (a training ctx): whatever it was comes back
-            ctx.set_precision("f32")
-            try:
-                losses, self.last_position_scores = E.lngknp_forward(*args)
-                ctx.status(clear=True)
-            finally:
-                ctx.set_precision(saved)
+        if check_shift:
+            for side, q, codes in (("pos", pos_q, pos_codes), ("neg", neg_q, neg_codes)):
+                _check_shifted_right(side, q["decoder_input_ids"], codes)
+        names = ["rank" if k == L else f"rank_{k}" for k, _ in prefixes]
+        tp = torch.stack([inputs[p + "teacher_pos_scores"] for _, p in prefixes]).float()
+        tn = torch.stack([inputs[p + "teacher_neg_scores"] for _, p in prefixes]).float()
+        return pos_q, torch.stack([pos_codes, neg_codes], dim=1), tp, tn, [k for k, _ in prefixes], names
+
+    def forward(self, **inputs):
+        pos_q, codes, tp, tn, prefix_lens, names = self._batch(inputs, check_shift=True)
+        losses, self.last_position_scores = self._position_pass(pos_q["input_ids"], pos_q["attention_mask"], codes, tp, tn,
+                                                                prefix_lens)
         return {n: losses[i] for i, n in enumerate(names)}
 
     __call__ = forward
 
     # ---- training (backward pass + optimizer on the device; reference: HF Trainer around this forward) -----------------
-    def _batch(self, inputs):
-        pos_q, neg_q = inputs["pos_tokenized_query"], inputs["neg_tokenized_query"]
-        pos_codes, neg_codes = inputs["pos_doc_encoding"], inputs["neg_doc_encoding"]
-        L = pos_codes.size(1)
-        if L not in self._PREFIXES:
-            raise ValueError("not valid length: {}".format(L))
-        if not torch.equal(pos_q["input_ids"], neg_q["input_ids"]):
-            raise ValueError("pos_tokenized_query and neg_tokenized_query must carry the same query tokens")
-        names = ["rank" if k == L else f"rank_{k}" for k, _ in self._PREFIXES[L]]
-        tp = torch.stack([inputs[p + "teacher_pos_scores"] for _, p in self._PREFIXES[L]]).float()
-        tn = torch.stack([inputs[p + "teacher_neg_scores"] for _, p in self._PREFIXES[L]]).float()
-        return pos_q, torch.stack([pos_codes, neg_codes], dim=1), tp, tn, [k for k, _ in self._PREFIXES[L]], names
-
     def train_state(self):
         from .. import engine as E
         if getattr(self, "_train_state", None) is None or self._train_state.model is not self.base_model.engine_model():
@@ -493,6 +517,33 @@ class T5SeqAQEncoderForLngKnpMarginMSE(T5SeqAQEncoder):
                               global_step=global_step)
         losses = {n: losses[i] for i, n in enumerate(names)}
         return losses
+
+
+class T5SeqAQEncoderForLngKnpMarginMSE(_MarginMSEOverPrefixes):
+    """reference :902-966 — forward of the prefix-oriented ranking fine-tune step (SURVEY.md §8 row f4), same
+    ``forward(**inputs)`` dict interface and return keys (``rank``, ``rank_4``, ``rank_8``, ``rank_16``). The whole
+    pass runs in ``rpr_lngknp_forward`` (teacher-forced decoder over all positions of the positive and the negative
+    smtid at once, one encoder pass per query). Forward only: no autograd graph is attached to the returned losses."""
+
+    _PREFIXES = {8: [(8, ""), (4, "smtid_4_")], 16: [(16, ""), (4, "smtid_4_"), (8, "smtid_8_")],
+                 32: [(32, ""), (4, "smtid_4_"), (8, "smtid_8_"), (16, "smtid_16_")]}
+
+    def _prefixes(self, L):
+        if L not in self._PREFIXES:
+            raise ValueError("not valid length: {}".format(L))
+        return self._PREFIXES[L]
+
+
+class T5SeqAQEncoderForMarginMSE(_MarginMSEOverPrefixes):
+    """reference :857-884 — the rank-oriented step (loss_type ``t5seq_aq_encoder_margin_mse``): one margin-MSE over the whole
+    smtid, ``forward(**inputs) -> {"rank": loss}`` on the batches of ``MarginMSEforT5SeqAQCollator``. It is the lng_knp step
+    with the single prefix ``[L]``: the same device passes, the same training step. The reference has no table of lengths:
+    any smtid length from 2 up to the model's decoder length runs (4 codes on a model of 32 positions is the first rung of
+    the prefix curriculum, full_lng_knp_train_pipline.sh:5-45)."""
+
+    def _prefixes(self, L):
+        _check_smtid_length(L, self.config)
+        return [(L, "")]
 
 
 class T5SeqAQEncoderForSeq2Seq(T5SeqAQEncoder):

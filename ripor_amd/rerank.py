@@ -7,6 +7,14 @@ Built tasks, with the reference's ``RerankArguments`` flag names (reference argu
   ``{qid: {smtid: [docids]}}`` with ``CrossEncoder`` and writes ``{qid: {smtid: [[docid, score], ...]}}``.
 * ``--task=cross_encoder_rerank_for_qid_smtid_docids_2`` (:625-654): merges the shards found in ``--out_dir`` into
   ``qid_smtid_docids_teacher_score.train.json`` and deletes them.
+* ``--task=rerank_for_create_trainset`` (:41-65): scores every (query, passage) pair of ``--run_json_path``
+  (``--json_type=json``: ``{qid: {docid: score}}``; ``jsonl``: lines of ``{"qid", "docids"}``) and writes
+  ``<out_dir>/rerank_<rank>.json`` = ``{qid: {docid: score}}``. The pairs are sharded by qid like the task above (the
+  reference shards the pairs with a ``DistributedSampler``, which pads the last ranks with repeated pairs).
+* ``--task=rerank_for_create_trainset_2`` (:67-105): merges the ``rerank_<rank>.json`` shards of ``--out_dir``, sorts every
+  query's passages by score (descending, stable), keeps the first 200 and writes one ``{"qid", "docids", "scores"}`` line per
+  query to ``qid_docids_teacher_scores.train.json`` — what ``aq_preprocess/add_qrel_to_rerank_run.py`` turns into the
+  examples of the rank-oriented training stage — then deletes the shards.
 
 Differences by design:
 
@@ -28,10 +36,12 @@ import os
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 MERGED_NAME = "qid_smtid_docids_teacher_score.train.json"
-BUILT_TASKS = ("cross_encoder_rerank_for_qid_smtid_docids", "cross_encoder_rerank_for_qid_smtid_docids_2")
+TRAINSET_NAME = "qid_docids_teacher_scores.train.json"
+TRAINSET_TOPK = 200   # passages kept per query (reference rerank.py:96-98)
+BUILT_TASKS = ("cross_encoder_rerank_for_qid_smtid_docids", "cross_encoder_rerank_for_qid_smtid_docids_2",
+               "rerank_for_create_trainset", "rerank_for_create_trainset_2")
 # the other branches of the reference's dispatch (rerank.py:660-691)
-UNBUILT_TASKS = ("rerank_for_eval", "rerank_for_create_trainset", "rerank_for_create_trainset_2", "rerank_for_evaluate_2",
-                 "assign_scores_for_pseudo_queries", "assign_scores_for_pseudo_queries_2", "query_to_docid_rerank_for_qid_smtids",
+UNBUILT_TASKS = ("rerank_for_eval", "rerank_for_evaluate_2", "assign_scores_for_pseudo_queries", "assign_scores_for_pseudo_queries_2", "query_to_docid_rerank_for_qid_smtids",
                  "query_to_docid_rerank_for_qid_smtids_2", "teacher_rerank_for_qid_smtids", "teacher_rerank_for_qid_smtids_2",
                  "cross_encoder_rerank_for_same_prefix_docid", "cross_encoder_rerank_for_same_prefix_docid_2",
                  "cross_encoder_rerank_for_same_reldocid_hard_docids", "cross_encoder_rerank_for_same_reldocid_hard_docids_2")
@@ -102,9 +112,9 @@ def score_triples(triples: Sequence[Triple], qid_to_query: Dict[str, str], docid
     return scores
 
 
-def cross_encoder_rerank_for_qid_smtid_docids(args):
+def start_teacher(args):
+    """Joins the process group and binds the cross-encoder on this rank's device -> (model, precision, rank, world)."""
     import torch.distributed as dist
-    from transformers import AutoTokenizer
     from .evaluate import _device_index, ddp_setup
     from .modeling.cross_encoder import CrossEncoder
     ddp_setup()
@@ -118,6 +128,12 @@ def cross_encoder_rerank_for_qid_smtid_docids(args):
     model = CrossEncoder(args.model_name_or_path, precision=precision)
     model.to(_device_index(local_rank))
     model.eval()
+    return model, precision, rank, world
+
+
+def cross_encoder_rerank_for_qid_smtid_docids(args):
+    from transformers import AutoTokenizer
+    model, precision, rank, world = start_teacher(args)
     with open(args.qid_smtid_docids_path) as fin:
         qid_to_smtid_to_docids = json.load(fin)
     print("qid_smtid_docids_path: ", args.qid_smtid_docids_path)
@@ -165,6 +181,90 @@ def cross_encoder_rerank_for_qid_smtid_docids_2(args):
     return merge_shards(args.out_dir)
 
 
+def read_run(run_json_path: str, json_type: str) -> Dict[str, List[str]]:
+    """reference dataset.py:19-38 (RerankDataset): the docids of every qid in file order. ``jsonl``: lines of ``{"qid",
+    "docids"}`` (a qid on several lines keeps all of them); anything else: one ``{qid: {docid: score}}`` object."""
+    run: Dict[str, List[str]] = {}
+    with open(run_json_path) as fin:
+        if json_type == "jsonl":
+            for line in fin:
+                if line.strip():
+                    ex = json.loads(line)
+                    run.setdefault(str(ex["qid"]), []).extend(str(d) for d in ex["docids"])
+        else:
+            for qid, rankdata in json.load(fin).items():
+                run[str(qid)] = [str(d) for d in rankdata]
+    return run
+
+
+def pair_ids_to_json_output(scores: Sequence[float], triples: Sequence[Triple]) -> Dict[str, Dict[str, float]]:
+    """reference tasks/reranker.py (pair_ids_to_json_output): ``{qid: {docid: score}}``."""
+    out: Dict[str, Dict[str, float]] = {}
+    assert len(scores) == len(triples)
+    for s, (qid, docid, _) in zip(scores, triples):
+        out.setdefault(str(qid), {})[str(docid)] = float(s)
+    return out
+
+
+def rerank_for_create_trainset(args):
+    from transformers import AutoTokenizer
+    from .dataset.lng_knp import CollectionDatasetPreLoad
+    model, precision, rank, world = start_teacher(args)
+    run = read_run(args.run_json_path, args.json_type)
+    sampled = shard_qids(run, world, rank)
+    print("size of sampled_data = {}, original data = {}".format(len(sampled), len(run)))
+    triples = [(qid, docid, "") for qid, docids in sampled.items() for docid in docids]
+    queries = CollectionDatasetPreLoad(args.q_collection_path, id_style="content_id").data_dict
+    docs = CollectionDatasetPreLoad(args.collection_path, id_style="content_id").data_dict
+    tokenizer = AutoTokenizer.from_pretrained(args.model_name_or_path)
+    scores = score_triples(triples, queries, docs, tokenizer, lambda kw: model.rerank_forward(kw)["scores"], args.batch_size,
+                           args.max_length, require_finite=precision == "f16")
+    os.makedirs(args.out_dir, exist_ok=True)
+    out_path = os.path.join(args.out_dir, f"rerank_{rank}.json")
+    qid_to_rankdata = pair_ids_to_json_output(scores, triples)
+    print("Write reranking to path: {}".format(out_path))
+    with open(out_path, "w") as fout:
+        json.dump(qid_to_rankdata, fout)
+    return out_path
+
+
+def is_rerank_shard(name: str) -> bool:
+    """``rerank_<rank>.json``. (The reference takes every file with "rerank" in its name for a shard.)"""
+    stem, ext = os.path.splitext(name)
+    return ext == ".json" and stem.startswith("rerank_") and stem[len("rerank_"):].isdigit()
+
+
+def merge_rerank_shards(out_dir: str, topk: int = TRAINSET_TOPK) -> List[dict]:
+    """reference rerank.py:67-105 without the device-count assertion: a qid present in several shards gets the union of its
+    passages; per qid the passages sorted by score, descending, with Python's stable sort (equal scores keep the order in
+    which they were read); the first ``topk``."""
+    merged_path = os.path.join(out_dir, TRAINSET_NAME)
+    if os.path.exists(merged_path):
+        print(f"old {TRAINSET_NAME} exists.")
+        os.remove(merged_path)
+    shards = sorted((p for p in os.listdir(out_dir) if is_rerank_shard(p)), key=lambda p: int(p[len("rerank_"):-len(".json")]))
+    qid_to_rankdata: Dict[str, Dict[str, float]] = {}
+    for sub in shards:
+        with open(os.path.join(out_dir, sub)) as fin:
+            for qid, rankdata in json.load(fin).items():
+                qid_to_rankdata.setdefault(qid, {}).update(rankdata)
+    print("length of qids in qid_to_rankdata: {}".format(len(qid_to_rankdata)))
+    examples = []
+    for qid, rankdata in qid_to_rankdata.items():
+        ranked = sorted(rankdata.items(), key=lambda x: x[1], reverse=True)[:topk]
+        examples.append({"qid": qid, "docids": [d for d, _ in ranked], "scores": [s for _, s in ranked]})
+    with open(merged_path, "w") as fout:
+        for ex in examples:
+            fout.write(json.dumps(ex) + "\n")
+    for sub in shards:
+        os.remove(os.path.join(out_dir, sub))
+    return examples
+
+
+def rerank_for_create_trainset_2(args):
+    return merge_rerank_shards(args.out_dir)
+
+
 def get_args(argv=None):
     """The reference's RerankArguments (arguments.py:215-248), same names and defaults where they are not site paths."""
     ap = argparse.ArgumentParser()
@@ -204,6 +304,10 @@ def main(argv=None):
         cross_encoder_rerank_for_qid_smtid_docids(args)
     elif args.task == "cross_encoder_rerank_for_qid_smtid_docids_2":
         cross_encoder_rerank_for_qid_smtid_docids_2(args)
+    elif args.task == "rerank_for_create_trainset":
+        rerank_for_create_trainset(args)
+    elif args.task == "rerank_for_create_trainset_2":
+        rerank_for_create_trainset_2(args)
     else:
         raise NotImplementedError(f"rerank task {args.task!r} is not built; built tasks: {', '.join(BUILT_TASKS)}")
 

@@ -13,7 +13,10 @@ tokens (one JSON line).
 with --bz 64): bz queries of the usual ~16-token mix, bz positive and bz negative documents of --doc_len (128) tokens, all padded
 to the document length in one encoder batch of 3 bz sequences, one decoder position each. Its JSON line also reports
 query_padding_share: the share of the 3 bz x doc_len encoder rows that are padding behind a query.
-Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq|dense] [--dims t5-base|t5-3b|t5-v1.1-base] [--embed] [--lq N]
+--step rank: the rank-oriented step (t5seq_aq_encoder_margin_mse): the lng_knp step with the single prefix [L]. --L 32,4: one leg
+per smtid length on the model of --len positions (4 codes on 32 positions is the first rung of the prefix curriculum).
+Usage: python tools/train_bench.py [--bz 128] [--steps 5] [--loss lngknp|seq2seq|dense|rank] [--L 32,4] [--dims t5-base|t5-3b|t5-v1.1-base]
+                                   [--embed] [--lq N]
        python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/train_bench.py"""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -21,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ripor_amd import engine as E
 from ripor_amd.utils import synth
 
-PRECISIONS, LOSSES = ["f16x2", "f32", "bf16"], ["lngknp", "seq2seq", "dense"]
+PRECISIONS, LOSSES = ["f16x2", "f32", "bf16"], ["lngknp", "seq2seq", "dense", "rank"]
 
 
 def listed(choices):
@@ -39,12 +42,17 @@ ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--len", type=int, default=32, dest="L")
 ap.add_argument("--precision", default=["f16x2"], type=listed(PRECISIONS))
 ap.add_argument("--loss", "--step", dest="loss", default=["lngknp"], type=listed(LOSSES))
+ap.add_argument("--L", dest="rank_L", default=None, type=lambda v: [int(x) for x in v.split(",")],
+                help="--step rank: smtid lengths, comma-separated, each from 2 to --len (default: --len)")
 ap.add_argument("--doc_len", type=int, default=128, help="--step dense: tokens per document (at most 256)")
 ap.add_argument("--dims", default="t5-base", choices=["t5-base", "t5-3b", "t5-v1.1-base"])
 ap.add_argument("--embed", action="store_true")
 ap.add_argument("--lq", type=int, default=0, help="all queries this many tokens long (default: ~16, as the fine-tune data)")
 args = ap.parse_args()
 L, V, bz = args.L, 256, args.bz
+rank_Ls = args.rank_L or [L]
+if any(not 2 <= k <= L for k in rank_Ls):
+    ap.error(f"--L: smtid lengths from 2 to --len ({L})")
 if args.dims == "t5-3b":
     dims = synth.ModelDims(d_model=1024, d_kv=128, d_ff=16384, num_layers=24, num_decoder_layers=24, num_heads=32,
                            decoder_vocab_sizes=[V] * L)
@@ -103,14 +111,19 @@ def embed_leg():   # dense embeddings (rpr_embed): 128 texts per call, queries o
     print(json.dumps(out), flush=True)
 
 
-def leg(precision, loss):
+def leg(precision, loss, Lr=None):
+    """Lr: the smtid length of a rank leg (the first Lr codes of every smtid, one loss over all of them)."""
     ctx.set_precision(precision)
+    if loss == "rank":
+        r_codes, r_prefix, r_tp, r_tn = codes_t[:, :, :Lr].contiguous(), [Lr], tp[:1], tn[:1]
 
     def step():   # backward with the bucketed gradient exchange overlapped (RPR_GRAD_OVERLAP=0: serial), clip, AdamW
         if loss == "seq2seq":
             return E.seq2seq_train_step(model, state, ids_t, mask_t, labels_t, lr=1e-6)
         if loss == "dense":
             return E.dense_mse_train_step(model, state, dense_ids, dense_mask, dense_tp, dense_tn, lr=1e-6)
+        if loss == "rank":
+            return E.train_step(model, state, ids_t, mask_t, r_codes, r_tp, r_tn, r_prefix, lr=1e-6)
         return E.train_step(model, state, ids_t, mask_t, codes_t, tp, tn, prefix, lr=1e-6)
 
     first = step(); torch.cuda.synchronize()
@@ -130,13 +143,16 @@ def leg(precision, loss):
         E.seq2seq_backward(model, state, ids_t, mask_t, labels_t)
     elif loss == "dense":
         E.dense_mse_backward(model, state, dense_ids, dense_mask, dense_tp, dense_tn)
+    elif loss == "rank":
+        E.lngknp_backward(model, state, ids_t, mask_t, r_codes, r_tp, r_tn, r_prefix)
     else:
         E.lngknp_backward(model, state, ids_t, mask_t, codes_t, tp, tn, prefix)
     torch.cuda.synchronize()
     st = ctx.profile_get(); ctx.profile_enable(False)
     dm, inner, dff, nd = dims.d_model, dims.inner, dims.d_ff, dims.num_decoder_layers
+    Lpos = Lr if loss == "rank" else L     # decoder positions per document
     flops_fwd = 2.0 * (bz * float(mask.sum(1).mean()) * (dims.num_layers * (4 * dm * inner + ff_mats * dm * dff) + nd * 2 * dm * inner)
-                       + bz * (1 if loss == "seq2seq" else 2) * L * nd * (6 * dm * inner + ff_mats * dm * dff)
+                       + bz * (1 if loss == "seq2seq" else 2) * Lpos * nd * (6 * dm * inner + ff_mats * dm * dff)
                        + (bz * L * V * dm if loss == "seq2seq" else 0))
     extra = {}
     if loss == "dense":   # real tokens of the 3 bz sequences through the encoder and the cross K/V, one decoder row per sequence
@@ -147,10 +163,11 @@ def leg(precision, loss):
         extra = {"doc_len": args.doc_len, "encoder_rows": int(rows), "padding_share": round(1.0 - tokens / rows, 4),
                  "query_padding_share": round(float((1 - dense_mask[0]).sum()) / rows, 4)}
     if rank == 0:
-        task = {"seq2seq": "seq2seq docid cross-entropy step", "dense": "dense first-stage margin-MSE step"}.get(loss, "lng_knp margin-MSE fine-tune step")
+        task = {"seq2seq": "seq2seq docid cross-entropy step", "dense": "dense first-stage margin-MSE step",
+                "rank": "rank-oriented margin-MSE step"}.get(loss, "lng_knp margin-MSE fine-tune step")
         print(json.dumps({"task": task + " (forward + backward + gradient all-reduce + AdamW), " + args.dims + " dims", "loss": loss,
                           "gemm_precision": precision, "n_gpus": world, "scaling": "weak", "bz_per_gpu": bz,
-                          "bz": bz, "L": L, "enc_len_padded": int(dense_ids.shape[2] if loss == "dense" else Lq), **extra, "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
+                          "bz": bz, "L": Lpos, "model_positions": L, "enc_len_padded": int(dense_ids.shape[2] if loss == "dense" else Lq), **extra, "ms_per_step": dt * 1e3, "examples_per_s": world * bz / dt,
                           "loss_first": [float(x) for x in first], "loss_last": [float(x) for x in last],
                           "params": state.total, "approx_tflops": 3 * flops_fwd / dt / 1e12,
                           "backward_kernel_ms": {k: round(v["total_ms"], 3) for k, v in st.items()}}), flush=True)
@@ -160,4 +177,5 @@ if args.embed and rank == 0:
     embed_leg()
 for precision in args.precision:
     for loss in args.loss:
-        leg(precision, loss)
+        for Lr in (rank_Ls if loss == "rank" else [None]):
+            leg(precision, loss, Lr)
