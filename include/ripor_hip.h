@@ -138,7 +138,7 @@ void rpr_free_ctx(rpr_ctx* ctx);
 const char* rpr_last_error(void);
 /* Library/ABI version; bumped when a signature changes or a symbol is added (4: the seq2seq step). Version 4 has since gained
  * rpr_search_margins and rpr_search_prefixes without a bump: a binding that needs one of them probes for the symbol (dlsym)
- * rather than for a version. */
+ * rather than for a version. 5: rpr_op_train_rows, the test hook of the training step's row-wise kernels. */
 int rpr_abi_version(void);
 /* Select the GEMM arithmetic (RPR_PREC_*); default RPR_PREC_F16X2, or RPR_PRECISION=f32|f16x2 in the
  * environment at rpr_init. Takes effect on the next rpr_search/rpr_encode/rpr_op_linear. */
@@ -718,6 +718,69 @@ typedef struct rpr_train_cross_attn_op {
 } rpr_train_cross_attn_op;
 int rpr_op_train_cross_attn_bwd(rpr_ctx* ctx, const rpr_train_cross_attn_op* op, int32_t* out_kernel, void* stream);
 int rpr_op_train_cross_attn_drop_fwd(rpr_ctx* ctx, const rpr_train_cross_attn_op* op, int32_t* out_kernel, void* stream);
+/* ---- test hook of the row-wise kernels of the training step: one launcher of train_kernels.hip / dense_head.hip on the
+ * caller's device buffers, through the launch_* function the step itself calls (its grid arithmetic lives there alone).
+ * One flat descriptor: op selects the launcher; src / dst are [dev] pointers, dims and f the launcher's integer and float
+ * arguments, all in the order listed per op below (unused entries 0 / NULL; "?" = nullable). A refused shape returns
+ * RPR_ERR_INVALID and launches nothing. The hook returns after the stream has drained. Shapes: every row width (d, C) is a
+ * multiple of 4 floats, as in the step.
+ *   RPR_TR_RMSNORM_BWD     launch_rmsnorm_bwd. src x [rows,d], w [d], dh [rows,d], dres? [rows,d]; dst dx [rows,d],
+ *                          w_part [ceil(rows/16), d], dw? [d]; dims rows, d (<= 4096), accumulate_dw; f eps, post
+ *   RPR_TR_COLSUM_MULTI    launch_colsum_multi. src part_i [nparts_i, d] (i < n <= 4); dst out_i [d]; dims d, n, nparts_0..3
+ *   RPR_TR_GOLD_SCORES     launch_gold_scores. src x? [S L, d] fp32, ln [d], out_embeds [L,V,d], codes? [S,L], x_planes?
+ *                          ([2] f16 planes of x / 16, plane stride dims[4] elements; exactly one of x, x_planes);
+ *                          dst scores? [S L], hidden? [S L, d] (exactly one; hidden: the normalised rows, no codes);
+ *                          dims S, L, d, V, plane_stride; f eps, post
+ *   RPR_TR_GOLD_SCORE_BWD  launch_gold_score_bwd. src x, ln, out_embeds, out_idx [rows] (rows of out_embeds, caller-checked),
+ *                          dscores [rows]; dst dh [rows,d], de [rows,d]; dims rows, d; f eps, post
+ *   RPR_TR_GOLD_ROWDOT     launch_gold_rowdot. src hd [rows,d], out_embeds, out_idx, dscores? (NULL: forward);
+ *                          dst scores (forward), dh, de (backward); dims rows, d
+ *   RPR_TR_MARGIN_MSE      launch_margin_mse. src scores [bz,2,L], teacher_pos [np,bz], teacher_neg [np,bz], prefix_lens [np];
+ *                          dst losses [np], margins? [np,bz]; dims np, bz, L
+ *   RPR_TR_MARGIN_MSE_BWD  launch_margin_mse_bwd. src margins [np,bz], teacher_pos, teacher_neg, prefix_lens;
+ *                          dst dscores [bz,2,L]; dims np, bz, L
+ *   RPR_TR_DENSE_MSE_FWD   launch_dense_mse_head_fwd. src hF [3 bz, d], teacher_pos [bz], teacher_neg [bz];
+ *                          dst scores [bz,2], margins [bz], g [bz], loss [1]; dims bz, d
+ *   RPR_TR_DENSE_MSE_BWD   launch_dense_mse_head_bwd. src hF, g [bz]; dst dhF [3 bz, d]; dims bz, d
+ *   RPR_TR_RELU_BWD        launch_relu_bwd. src act [n]; dst dy [n] (in place); dims n (n % 4 == 0)
+ *   RPR_TR_DEC_EMBED       launch_train_dec_embed. src start [d], in_embeds [L,V,d], codes [S,L]; dst out? [S L, d] fp32,
+ *                          planes? ([2] f16, plane stride dims[4]; exactly one of out, planes), ssq? [S L] uint64;
+ *                          dims S, L, d, V, plane_stride
+ *   RPR_TR_TRAIN_INDICES   launch_train_indices. src codes [S,L]; dst in_idx [S L], out_idx [S L]; dims S, L, V
+ *   RPR_TR_SCATTER_FIX     launch_scatter_rows_fix. src rows [rows,d], idx [rows] (< 0: skipped; table rows caller-checked);
+ *                          dst acc (int64 [table, d], 2^-32 fixed point, added to); dims rows, d
+ *   RPR_TR_FIX_FLUSH       launch_fix_flush. dst acc [n] (zeroed), table [n] fp32 (added to); dims n
+ *   RPR_TR_SUM_SELECTED    launch_sum_selected_rows. src rows [rows,d], sel [rows]; dst out [d] (added to); dims rows, d
+ *   RPR_TR_S2S_HEAD_FWD    launch_s2s_head_fwd. src hF [bz L, d], E [L,V,d], labels [bz L]; dst dlogits [bz L, V],
+ *                          row_loss [bz L], label_lp? [bz L], loss [1]; dims bz, L, d, V (d % 32 == 0, V % 64 == 0, V <= 1024)
+ *   RPR_TR_S2S_HEAD_BWD    launch_s2s_head_bwd. src hF, E, dlogits; dst dH [bz L, d], dE [L,V,d]; dims bz, L, d, V
+ *   RPR_TR_ABSMAX2         launch_absmax2. src x0 [n0], x1? [n1]; dst out [2] (bit-pattern maximum with what is there:
+ *                          the caller zeroes it); dims n0, n1
+ *   RPR_TR_SPLIT_DYN       launch_split_dyn. src x [R, ldi], amax [1]; dst out [2][R][C] f16; dims R, C, ldi
+ *   RPR_TR_SPLIT_DYN_T     launch_split_dyn_T. src x, amax; dst out_t [2][C][Rpad] f16, out_plain? [2][R][C];
+ *                          dims R, C, ldi, Rpad (Rpad even, >= R)
+ *   RPR_TR_TO_BF16         launch_to_bf16. src x [R, ldi]; dst out [R][C] bf16; dims R, C, ldi
+ *   RPR_TR_TO_BF16_T       launch_to_bf16_T. src x, relu_act? [R, ldi]; dst out_t [C][ldt] bf16 (columns < Rpad written),
+ *                          out_plain? [R][C]; dims R, C, ldi, Rpad, ldt (0 = Rpad)
+ *   RPR_TR_RMSNORM_BF16_T  launch_rmsnorm_bf16_T. src x [rows,d], w [d]; dst out_plain [rows][d] bf16, out_t [d][ldt] bf16;
+ *                          dims rows, d, Rpad, ldt (d <= 1024, d % 8 == 0, Rpad % 32 == 0); f eps, post
+ *   RPR_TR_WEIGHTS_BF16    launch_weights_bf16. src seg_i [R_i, C_i] (i < n <= 5; R_i even, C_i % 4 == 0); dst plain, tr (bf16,
+ *                          segment i at element offset sum_{j<i} R_j C_j: [R_i][C_i] and [C_i][R_i]); dims n, R_0, C_0, R_1, ...
+ *   RPR_TR_TRANSPOSE_PAD   launch_transpose_pad. src in [R, ldi]; dst out [C][Rpad]; dims R, C, ldi, Rpad */
+enum { RPR_TR_RMSNORM_BWD = 0, RPR_TR_COLSUM_MULTI = 1, RPR_TR_GOLD_SCORES = 2, RPR_TR_GOLD_SCORE_BWD = 3, RPR_TR_GOLD_ROWDOT = 4,
+       RPR_TR_MARGIN_MSE = 5, RPR_TR_MARGIN_MSE_BWD = 6, RPR_TR_DENSE_MSE_FWD = 7, RPR_TR_DENSE_MSE_BWD = 8, RPR_TR_RELU_BWD = 9,
+       RPR_TR_DEC_EMBED = 10, RPR_TR_TRAIN_INDICES = 11, RPR_TR_SCATTER_FIX = 12, RPR_TR_FIX_FLUSH = 13, RPR_TR_SUM_SELECTED = 14,
+       RPR_TR_S2S_HEAD_FWD = 15, RPR_TR_S2S_HEAD_BWD = 16, RPR_TR_ABSMAX2 = 17, RPR_TR_SPLIT_DYN = 18, RPR_TR_SPLIT_DYN_T = 19,
+       RPR_TR_TO_BF16 = 20, RPR_TR_TO_BF16_T = 21, RPR_TR_RMSNORM_BF16_T = 22, RPR_TR_WEIGHTS_BF16 = 23, RPR_TR_TRANSPOSE_PAD = 24,
+       RPR_TR_COUNT = 25 };
+typedef struct rpr_train_rows_op {
+  const void* src[6];
+  void* dst[6];
+  int32_t op;
+  int32_t dims[11];
+  float f[4];
+} rpr_train_rows_op;
+int rpr_op_train_rows(rpr_ctx* ctx, const rpr_train_rows_op* op, void* stream);
 /* Name of an AttnKernel value (csrc/attn_route.h RPR_ATTN_KERNELS), NULL when out of range. Host only. */
 const char* rpr_attn_kernel_name(int kernel);
 /* Number of AttnKernel values (names 0 .. n - 1). Host only. */

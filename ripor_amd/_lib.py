@@ -22,7 +22,7 @@ KERNEL_CLASS_NAMES = ["gemm", "dec_self_attn", "dec_cross_attn", "enc_attn", "rm
 STATUS_SATURATED, STATUS_EMPTY_QUERY, STATUS_TAIL_LEFTOVER, STATUS_SMALL_STREAM = 1, 2, 4, 8
 # either one: the split-precision results since the last clear are not trustworthy and the call is repeated in exact fp32
 STATUS_NEEDS_F32 = STATUS_SATURATED | STATUS_SMALL_STREAM
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 PREC_F32, PREC_F16X2, PREC_BF16 = 0, 1, 2
 FLAG_LOG_SOFTMAX = 1
@@ -130,6 +130,18 @@ class TrainCrossAttnOp(C.Structure):
 
 CROSS_SITE_BLOCK, CROSS_SITE_STEP, CROSS_SITE_TAIL = 0, 1, 2
 
+
+class TrainRowsOp(C.Structure):
+    """``rpr_train_rows_op`` (rpr_op_train_rows): one launcher of the training step's row-wise kernels."""
+    _fields_ = [("src", C.c_void_p * 6), ("dst", C.c_void_p * 6), ("op", C.c_int32), ("dims", C.c_int32 * 11), ("f", C.c_float * 4)]
+
+
+# RPR_TR_* of include/ripor_hip.h, in enum order
+TRAIN_ROWS_OPS = {n: i for i, n in enumerate((
+    "RMSNORM_BWD", "COLSUM_MULTI", "GOLD_SCORES", "GOLD_SCORE_BWD", "GOLD_ROWDOT", "MARGIN_MSE", "MARGIN_MSE_BWD", "DENSE_MSE_FWD",
+    "DENSE_MSE_BWD", "RELU_BWD", "DEC_EMBED", "TRAIN_INDICES", "SCATTER_FIX", "FIX_FLUSH", "SUM_SELECTED", "S2S_HEAD_FWD",
+    "S2S_HEAD_BWD", "ABSMAX2", "SPLIT_DYN", "SPLIT_DYN_T", "TO_BF16", "TO_BF16_T", "RMSNORM_BF16_T", "WEIGHTS_BF16", "TRANSPOSE_PAD"))}
+
 # every symbol include/ripor_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "rpr_op_enc_attn": (C.c_int, [C.c_void_p, C.POINTER(EncAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
@@ -140,6 +152,7 @@ SIGNATURES = {
     "rpr_op_train_self_attn_drop_fwd": (C.c_int, [C.c_void_p, C.POINTER(TrainSelfAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
     "rpr_op_train_cross_attn_bwd": (C.c_int, [C.c_void_p, C.POINTER(TrainCrossAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
     "rpr_op_train_cross_attn_drop_fwd": (C.c_int, [C.c_void_p, C.POINTER(TrainCrossAttnOp), C.POINTER(C.c_int32), C.c_void_p]),
+    "rpr_op_train_rows": (C.c_int, [C.c_void_p, C.POINTER(TrainRowsOp), C.c_void_p]),
     "rpr_attn_kernel_name": (C.c_char_p, [C.c_int]),
     "rpr_attn_kernel_count": (C.c_int, []),
     "rpr_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),

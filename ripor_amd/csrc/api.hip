@@ -145,7 +145,7 @@ int flush_profile(rpr_ctx* c) {
 
 extern "C" {
 
-int rpr_abi_version(void) { return 4; }
+int rpr_abi_version(void) { return 5; }
 const char* rpr_last_error(void) { return g_err.c_str(); }
 
 int rpr_rel_bucket(int rel, int bidirectional, int num_buckets, int max_distance) {
@@ -1325,6 +1325,191 @@ int rpr_op_train_cross_attn_drop_fwd(rpr_ctx* c, const rpr_train_cross_attn_op* 
   if (const int e = attn_op_plan(plan_train_cross_attn_drop_fwd(in), out_kernel, "launch_cross_attn_drop_fwd")) return e;
   RPR_HIP(launch_cross_attn_drop_fwd(o->q, o->xk, o->xv, o->xld, o->mask, o->out, o->bz, o->n, o->Lq, o->H, da, s, o->dkv));
   RPR_HIP(hipStreamSynchronize(s));
+  return RPR_OK;
+}
+
+// ---- the row-wise kernels of the training step: the descriptor -> the launcher the step calls (include/ripor_hip.h) ----
+int rpr_op_train_rows(rpr_ctx* c, const rpr_train_rows_op* o, void* stream) {
+  RPR_REQUIRE(c && o, "NULL argument");
+  RPR_REQUIRE(o->op >= 0 && o->op < RPR_TR_COUNT, "unknown op");
+  const int32_t* n = o->dims;
+  const float eps = o->f[0], post = o->f[1];
+  auto F = [&](int i) { return reinterpret_cast<const float*>(o->src[i]); };
+  auto I = [&](int i) { return reinterpret_cast<const int32_t*>(o->src[i]); };
+  auto OF = [&](int i) { return reinterpret_cast<float*>(o->dst[i]); };
+  auto OI = [&](int i) { return reinterpret_cast<int32_t*>(o->dst[i]); };
+  auto OH = [&](int i) { return reinterpret_cast<__half*>(o->dst[i]); };
+  auto OU = [&](int i) { return reinterpret_cast<unsigned long long*>(o->dst[i]); };
+  auto have = [&](int ns, int nd) {
+    for (int i = 0; i < ns; ++i) if (!o->src[i]) return false;
+    for (int i = 0; i < nd; ++i) if (!o->dst[i]) return false;
+    return true;
+  };
+  auto pos = [&](int k) { for (int i = 0; i < k; ++i) if (n[i] < 1) return false; return true; };
+  RPR_HIP(hipSetDevice(c->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  DevTmp t0, t1;
+  switch (o->op) {
+    case RPR_TR_RMSNORM_BWD:
+      RPR_REQUIRE(have(3, 2), "NULL argument");
+      RPR_REQUIRE(pos(2) && n[1] % 4 == 0 && n[1] <= 4096, "bad shape (rows >= 1, d a multiple of 4, d <= 4096: four rows of d floats in 64 KB of LDS)");
+      RPR_HIP(launch_rmsnorm_bwd(F(0), F(1), F(2), F(3), OF(0), OF(1), OF(2), n[0], n[1], eps, post, n[2] ? 1 : 0, s));
+      break;
+    case RPR_TR_COLSUM_MULTI: {
+      RPR_REQUIRE(n[0] >= 1 && n[1] >= 1 && n[1] <= ColsumSites::MAXS, "bad shape (d >= 1, 1 .. 4 sites)");
+      ColsumSites p{};
+      p.n = n[1];
+      for (int i = 0; i < p.n; ++i) {
+        RPR_REQUIRE(o->src[i] && o->dst[i] && n[2 + i] >= 1, "NULL argument / nparts < 1");
+        p.part[i] = F(i); p.out[i] = OF(i); p.nparts[i] = n[2 + i];
+      }
+      RPR_HIP(launch_colsum_multi(p, n[0], s));
+      break;
+    }
+    case RPR_TR_GOLD_SCORES: {
+      const bool hid = o->dst[1] != nullptr;
+      RPR_REQUIRE(o->src[1] && o->src[2] && (o->src[0] != nullptr) != (o->src[4] != nullptr), "ln, out_embeds and exactly one of x, x_planes");
+      RPR_REQUIRE((o->dst[0] != nullptr) != hid && (hid || o->src[3]), "exactly one of scores (with codes) and hidden");
+      RPR_REQUIRE(pos(4) && n[2] % 4 == 0 && (!o->src[4] || n[4] >= n[0] * n[1] * n[2]), "bad shape");
+      // hidden mode forms no score, but the kernel still loads row (i, 0) of out_embeds (rpr_embed passes the model's codebook)
+      RPR_HIP(launch_gold_scores(F(0), F(1), F(2), I(3), OF(0), n[0], n[1], n[2], n[3], eps, post, s,
+                                 reinterpret_cast<const __half*>(o->src[4]), (size_t)n[4], OF(1)));
+      break;
+    }
+    case RPR_TR_GOLD_SCORE_BWD:
+      RPR_REQUIRE(have(5, 2), "NULL argument");
+      RPR_REQUIRE(pos(2) && n[1] % 4 == 0, "bad shape");
+      RPR_HIP(launch_gold_score_bwd(F(0), F(1), F(2), I(3), F(4), OF(0), OF(1), n[0], n[1], eps, post, s));
+      break;
+    case RPR_TR_GOLD_ROWDOT:
+      RPR_REQUIRE(have(3, 0) && (o->src[3] ? (o->dst[1] && o->dst[2]) : o->dst[0] != nullptr), "NULL argument");
+      RPR_REQUIRE(pos(2) && n[1] % 4 == 0, "bad shape");
+      RPR_HIP(launch_gold_rowdot(F(0), F(1), I(2), OF(0), F(3), OF(1), OF(2), n[0], n[1], s));
+      break;
+    case RPR_TR_MARGIN_MSE:
+      RPR_REQUIRE(have(4, 1), "NULL argument");
+      RPR_REQUIRE(pos(3), "bad shape");
+      RPR_HIP(launch_margin_mse(F(0), F(1), F(2), I(3), n[0], n[1], n[2], OF(0), OF(1), s));
+      break;
+    case RPR_TR_MARGIN_MSE_BWD:
+      RPR_REQUIRE(have(4, 1), "NULL argument");
+      RPR_REQUIRE(pos(3), "bad shape");
+      RPR_HIP(launch_margin_mse_bwd(F(0), F(1), F(2), I(3), n[0], n[1], n[2], OF(0), s));
+      break;
+    case RPR_TR_DENSE_MSE_FWD:
+      RPR_REQUIRE(have(3, 4), "NULL argument");
+      RPR_REQUIRE(pos(2), "bad shape");
+      RPR_HIP(launch_dense_mse_head_fwd(F(0), F(1), F(2), OF(0), OF(1), OF(2), OF(3), n[0], n[1], s));
+      break;
+    case RPR_TR_DENSE_MSE_BWD:
+      RPR_REQUIRE(have(2, 1), "NULL argument");
+      RPR_REQUIRE(pos(2), "bad shape");
+      RPR_HIP(launch_dense_mse_head_bwd(F(0), F(1), OF(0), n[0], n[1], s));
+      break;
+    case RPR_TR_RELU_BWD:
+      RPR_REQUIRE(have(1, 1), "NULL argument");
+      RPR_REQUIRE(n[0] >= 4 && n[0] % 4 == 0, "bad shape (n a multiple of 4)");
+      RPR_HIP(launch_relu_bwd(OF(0), F(0), (size_t)n[0], s));
+      break;
+    case RPR_TR_DEC_EMBED: {
+      RPR_REQUIRE(have(3, 0) && (o->dst[0] != nullptr) != (o->dst[1] != nullptr), "NULL argument / exactly one of out and planes");
+      RPR_REQUIRE(pos(4) && n[2] % 4 == 0 && (!o->dst[1] || n[4] >= n[0] * n[1] * n[2]), "bad shape");
+      XOut xo{};
+      xo.x_h = OH(1); xo.x_ps = (size_t)n[4]; xo.ssq = OU(2); xo.sat = c->status;
+      RPR_HIP(launch_train_dec_embed(F(0), F(1), I(2), OF(0), n[0], n[1], n[2], n[3], s, xo));
+      break;
+    }
+    case RPR_TR_TRAIN_INDICES:
+      RPR_REQUIRE(have(1, 2), "NULL argument");
+      RPR_REQUIRE(pos(3), "bad shape");
+      RPR_HIP(launch_train_indices(I(0), OI(0), OI(1), n[0], n[1], n[2], s));
+      break;
+    case RPR_TR_SCATTER_FIX:
+      RPR_REQUIRE(have(2, 1), "NULL argument");
+      RPR_REQUIRE(pos(2), "bad shape");
+      RPR_HIP(launch_scatter_rows_fix(F(0), I(1), OU(0), n[0], n[1], s));
+      break;
+    case RPR_TR_FIX_FLUSH:
+      RPR_REQUIRE(have(0, 2), "NULL argument");
+      RPR_REQUIRE(pos(1), "bad shape");
+      RPR_HIP(launch_fix_flush(OU(0), OF(1), (size_t)n[0], s));
+      break;
+    case RPR_TR_SUM_SELECTED:
+      RPR_REQUIRE(have(2, 1), "NULL argument");
+      RPR_REQUIRE(pos(2), "bad shape");
+      RPR_HIP(launch_sum_selected_rows(F(0), I(1), OF(0), n[0], n[1], s));
+      break;
+    case RPR_TR_S2S_HEAD_FWD:
+      RPR_REQUIRE(have(3, 2) && o->dst[3], "NULL argument");
+      RPR_REQUIRE(pos(4) && n[2] % 32 == 0 && s2s_head_smem_ok(n[3]), "bad shape (d % 32 == 0, V % 64 == 0, V <= 1024)");
+      RPR_HIP(launch_s2s_head_fwd(F(0), F(1), I(2), OF(0), OF(1), OF(2), OF(3), n[0], n[1], n[2], n[3], s));
+      break;
+    case RPR_TR_S2S_HEAD_BWD:
+      RPR_REQUIRE(have(3, 2), "NULL argument");
+      RPR_REQUIRE(pos(4) && n[2] % 32 == 0 && s2s_head_smem_ok(n[3]), "bad shape (d % 32 == 0, V % 64 == 0, V <= 1024)");
+      RPR_HIP(launch_s2s_head_bwd(F(0), F(1), F(2), OF(0), OF(1), n[0], n[1], n[2], n[3], s));
+      break;
+    case RPR_TR_ABSMAX2:
+      RPR_REQUIRE(have(1, 1), "NULL argument");
+      RPR_REQUIRE(n[0] >= 1 && (!o->src[1] || n[1] >= 1), "bad shape");
+      RPR_HIP(launch_absmax2(F(0), (size_t)n[0], F(1), o->src[1] ? (size_t)n[1] : 0, OF(0), s));
+      break;
+    case RPR_TR_SPLIT_DYN:
+      RPR_REQUIRE(have(2, 1), "NULL argument");
+      RPR_REQUIRE(pos(3) && n[1] % 4 == 0 && n[2] % 4 == 0 && n[2] >= n[1], "bad shape");
+      RPR_HIP(launch_split_dyn(F(0), n[0], n[1], n[2], OH(0), F(1), s));
+      break;
+    case RPR_TR_SPLIT_DYN_T:
+      RPR_REQUIRE(have(2, 1), "NULL argument");
+      RPR_REQUIRE(pos(4) && n[1] % 4 == 0 && n[2] % 4 == 0 && n[2] >= n[1] && n[3] % 2 == 0 && n[3] >= n[0], "bad shape");
+      RPR_HIP(launch_split_dyn_T(F(0), n[0], n[1], n[2], n[3], OH(0), OH(1), F(1), s));
+      break;
+    case RPR_TR_TO_BF16:
+      RPR_REQUIRE(have(1, 1), "NULL argument");
+      RPR_REQUIRE(pos(3) && n[1] % 4 == 0 && n[2] % 4 == 0 && n[2] >= n[1], "bad shape");
+      RPR_HIP(launch_to_bf16(F(0), n[0], n[1], n[2], o->dst[0], s));
+      break;
+    case RPR_TR_TO_BF16_T:
+      RPR_REQUIRE(have(1, 1), "NULL argument");
+      RPR_REQUIRE(pos(4) && n[1] % 4 == 0 && n[2] % 4 == 0 && n[2] >= n[1] && n[3] % 2 == 0 && n[3] >= n[0] &&
+                      (n[4] == 0 || (n[4] % 2 == 0 && n[4] >= n[3])), "bad shape");
+      RPR_HIP(launch_to_bf16_T(F(0), n[0], n[1], n[2], n[3], o->dst[0], o->dst[1], s, F(1), n[4]));
+      break;
+    case RPR_TR_RMSNORM_BF16_T:
+      RPR_REQUIRE(have(2, 2), "NULL argument");
+      RPR_REQUIRE(pos(4) && n[1] <= 1024 && n[1] % 8 == 0 && n[2] % 32 == 0 && n[2] >= n[0] && n[3] % 8 == 0 && n[3] >= n[2],
+                  "bad shape (d <= 1024, d % 8 == 0, Rpad % 32 == 0, Rpad >= rows, ldt % 8 == 0, ldt >= Rpad)");
+      RPR_HIP(launch_rmsnorm_bf16_T(F(0), F(1), n[0], n[1], eps, post, o->dst[0], o->dst[1], n[2], n[3], s));
+      break;
+    case RPR_TR_WEIGHTS_BF16: {
+      RPR_REQUIRE(o->dst[0] && o->dst[1] && n[0] >= 1 && n[0] <= 5, "NULL argument / 1 .. 5 segments");
+      WSeg segs[5];
+      int pref[5], tiles = 0;
+      unsigned long long off = 0;
+      for (int i = 0; i < n[0]; ++i) {    // the table the step builds in bf16_weights (train_api.hip)
+        const int R = n[1 + 2 * i], Cc = n[2 + 2 * i];
+        RPR_REQUIRE(o->src[i] && R >= 2 && Cc >= 4 && !(R & 1) && !(Cc & 3), "segment: R even, C a multiple of 4");
+        segs[i] = WSeg{F(i), R, Cc, off};
+        pref[i] = tiles;
+        tiles += ((R + 63) / 64) * ((Cc + 63) / 64);
+        off += (unsigned long long)R * Cc;
+      }
+      RPR_HIP(t0.alloc(sizeof(segs)));
+      RPR_HIP(t1.alloc(sizeof(pref)));
+      RPR_HIP(hipMemcpyAsync(t0.p, segs, n[0] * sizeof(WSeg), hipMemcpyHostToDevice, s));
+      RPR_HIP(hipMemcpyAsync(t1.p, pref, n[0] * sizeof(int), hipMemcpyHostToDevice, s));
+      RPR_HIP(hipStreamSynchronize(s));
+      RPR_HIP(launch_weights_bf16(t0.as<WSeg>(), t1.as<int>(), n[0], tiles, o->dst[0], o->dst[1], s));
+      break;
+    }
+    case RPR_TR_TRANSPOSE_PAD:
+      RPR_REQUIRE(have(1, 1), "NULL argument");
+      RPR_REQUIRE(pos(4) && n[2] >= n[1] && n[3] >= n[0], "bad shape");
+      RPR_HIP(launch_transpose_pad(F(0), OF(0), n[0], n[1], n[2], n[3], s));
+      break;
+    default: RPR_REQUIRE(false, "unknown op");
+  }
+  RPR_HIP(hipStreamSynchronize(s));   // the temporaries are freed when this scope ends
   return RPR_OK;
 }
 

@@ -305,6 +305,27 @@ class Context:
         op = self._train_cross_attn_op(q, None, xk, xv, xld, mask, None, None, None, out, bz, n, Lq, H, dkv, drop)
         return self._attn_op("rpr_op_train_cross_attn_drop_fwd", op, q.device)
 
+    def train_rows(self, op_name: str, src=(), dst=(), dims=(), f=()):
+        """Test hook of the training step's row-wise kernels (``rpr_op_train_rows``): launcher ``op_name`` (a key of
+        _lib.TRAIN_ROWS_OPS) on device tensors src / dst (None = NULL) with the integer / float arguments dims / f, each in the
+        order include/ripor_hip.h lists for the op."""
+        op = _lib.TrainRowsOp()
+        dev = None
+        for arr, ts in ((op.src, src), (op.dst, dst)):
+            assert len(ts) <= len(arr)
+            for i, t in enumerate(ts):
+                if t is not None:
+                    assert t.is_cuda
+                    dev = dev or t.device
+                    arr[i] = t.data_ptr()
+        op.op = _lib.TRAIN_ROWS_OPS[op_name]
+        assert len(dims) <= len(op.dims) and len(f) <= len(op.f)
+        for i, v in enumerate(dims):
+            op.dims[i] = int(v)
+        for i, v in enumerate(f):
+            op.f[i] = float(v)
+        check(self.lib.rpr_op_train_rows(self.handle, C.byref(op), _stream_ptr(dev)), "rpr_op_train_rows " + op_name)
+
 
 class StatusTicket:
     """Status words of a ctx as of one point of a stream (``Context.status_async``)."""

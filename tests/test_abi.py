@@ -73,6 +73,35 @@ def test_attention_hook_descriptors_match_header():
         assert fields == want, (cname, fields, want)
 
 
+def test_train_rows_descriptor_matches_header(lib):
+    """rpr_train_rows_op (the test hook of the training step's row-wise kernels): size, field order, array lengths and the op enum
+    of include/ripor_hip.h against the ctypes mirror; ABI version 5 is the one that has the hook."""
+    from ripor_amd import _lib
+    hdr = open(os.path.join(REPO, "include", "ripor_hip.h")).read()
+    body = hdr[hdr.index("typedef struct rpr_train_rows_op {"):hdr.index("} rpr_train_rows_op;")].split("{", 1)[1]
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            m = re.fullmatch(r"(const void\*|void\*|int32_t|float)\s+(\w+)(?:\[(\d+)\])?", decl)
+            assert m, decl
+            fields.append((m.group(2), {"const void*": C.c_void_p, "void*": C.c_void_p, "int32_t": C.c_int32, "float": C.c_float}[m.group(1)],
+                           int(m.group(3) or 0)))
+    want = [(n, getattr(t, "_type_", t) if hasattr(t, "_length_") else t, getattr(t, "_length_", 0)) for n, t in _lib.TrainRowsOp._fields_]
+    assert fields == want, (fields, want)
+    assert [f[0] for f in fields] == ["src", "dst", "op", "dims", "f"]
+    assert C.sizeof(_lib.TrainRowsOp) == 6 * 8 + 6 * 8 + 4 + 11 * 4 + 4 * 4 == 160
+    assert _lib.TrainRowsOp.op.offset == 96 and _lib.TrainRowsOp.dims.offset == 100 and _lib.TrainRowsOp.f.offset == 144
+    enum = hdr[hdr.index("enum { RPR_TR_RMSNORM_BWD"):]
+    enum = enum[:enum.index("}")]
+    names = {m.group(1): int(m.group(2)) for m in re.finditer(r"RPR_TR_(\w+) = (\d+)", enum)}
+    assert names.pop("COUNT") == len(names) == len(_lib.TRAIN_ROWS_OPS)
+    assert names == _lib.TRAIN_ROWS_OPS
+    assert lib.rpr_abi_version() == _lib.ABI_VERSION == 5
+    # without a ctx nothing is launched: the hook refuses
+    assert lib.rpr_op_train_rows(None, C.byref(_lib.TrainRowsOp()), None) == -1 and b"NULL argument" in lib.rpr_last_error()
+
+
 def test_rel_bucket_table_matches_torch_expression(lib):
     from oracle import t5_ref
     enc = t5_ref.bucket_table(True, 256)

@@ -59,7 +59,7 @@ def test_signature_in_header_and_binding_and_the_scratch_constant():
     assert "rpr_flat_search" in _lib.SIGNATURES and len(_lib.SIGNATURES["rpr_flat_search"][1]) == 12
     m = re.search(r"\bint rpr_flat_search\(([^;]*)\);", header)
     assert m and m.group(1).count(",") + 1 == 12
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
     common = open(os.path.join(REPO, "ripor_amd", "csrc", "common.h")).read()
     m = re.search(r"FLAT_SCRATCH_BYTES = \(size_t\)(\d+) << (\d+);", common)
     assert m and int(m.group(1)) << int(m.group(2)) == E.FLAT_SCRATCH_BYTES

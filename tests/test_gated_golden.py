@@ -230,7 +230,7 @@ def test_abi_exports_the_new_symbols():
     hdr = open(os.path.join(os.path.dirname(GOLDEN_DIR), "..", "include", "ripor_hip.h")).read()
     for name, nargs in (("rpr_load_model_ext", 4), ("rpr_op_gated_gelu", 8), ("rpr_op_gated_gelu_bwd", 7)):
         assert hasattr(lib, name) and name in hdr and len(_lib.SIGNATURES[name][1]) == nargs
-    assert lib.rpr_abi_version() == 4 == _lib.ABI_VERSION
+    assert lib.rpr_abi_version() == 5 == _lib.ABI_VERSION
     assert C.sizeof(_lib.ModelExt) == 8 and (_lib.FF_RELU, _lib.FF_GATED_GELU) == (0, 1)
     assert "#define RPR_FF_RELU 0" in hdr and "#define RPR_FF_GATED_GELU 1" in hdr
     assert C.sizeof(_lib.ModelDesc) == 56 + 24 * 8   # unchanged

@@ -80,11 +80,11 @@ def test_depths_are_part_of_the_key(driver):
 
 def test_abi_exports_the_symbol_and_keeps_its_version():
     from ripor_amd import _lib
-    assert "rpr_search_prefixes" in _lib.SIGNATURES and _lib.ABI_VERSION == 4
+    assert "rpr_search_prefixes" in _lib.SIGNATURES and _lib.ABI_VERSION == 5
     res, args = _lib.SIGNATURES["rpr_search_prefixes"]
     assert len(args) == len(_lib.SIGNATURES["rpr_search"][1]) - 1 + 6      # rpr_search's without the taps + n, depths, 4 arrays
     lib = _lib.load()
-    assert hasattr(lib, "rpr_search_prefixes") and lib.rpr_abi_version() == 4
+    assert hasattr(lib, "rpr_search_prefixes") and lib.rpr_abi_version() == 5
     header = open(os.path.join(REPO, "include", "ripor_hip.h")).read()
     assert "int rpr_search_prefixes(" in header
 

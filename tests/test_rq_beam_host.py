@@ -42,7 +42,7 @@ def test_symbol_exported_and_declared():
     assert "rpr_rq_encode_beam" in _lib.SIGNATURES
     assert re.search(r"\bint rpr_rq_encode_beam\(", hdr)
     assert hasattr(C.CDLL(ge.LIB), "rpr_rq_encode_beam")
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
 
 
 def test_entry_point_fails_cleanly_without_a_context():

@@ -60,7 +60,7 @@ def test_rq_symbols_exported_and_declared():
         assert re.search(r"\bint " + name + r"\(", hdr), name
     lib = C.CDLL(ge.LIB)
     assert hasattr(lib, "rpr_rq_train") and hasattr(lib, "rpr_rq_encode")
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
 
 
 def test_rq_entry_points_fail_cleanly_without_a_context():

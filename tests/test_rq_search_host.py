@@ -54,7 +54,7 @@ def test_signatures_in_header_and_binding():
         assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == nargs
         m = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
         assert m and m.group(1).count(",") + 1 == nargs
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
 
 
 def test_cli_accepts_the_aq_evaluate_flags():

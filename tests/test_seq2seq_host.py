@@ -164,7 +164,7 @@ def test_abi_exports_the_seq2seq_step():
     ge.build()
     from ripor_amd import _lib
     lib = _lib.load()
-    assert lib.rpr_abi_version() == _lib.ABI_VERSION == 4
+    assert lib.rpr_abi_version() == _lib.ABI_VERSION == 5
     for name in ("rpr_seq2seq_forward", "rpr_seq2seq_backward", "rpr_seq2seq_backward_buckets"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
     hdr = open(os.path.join(os.path.dirname(GOLDEN_DIR), "..", "include", "ripor_hip.h")).read()

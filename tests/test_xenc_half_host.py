@@ -59,7 +59,7 @@ def test_new_symbols_declared_bound_and_exported():
     for name in ("rpr_xenc_set_precision", "rpr_xenc_get_precision"):
         assert re.search(r"\b" + name + r"\s*\(", hdr) and name in _lib.SIGNATURES and hasattr(lib, name)
     assert re.search(r"#define\s+RPR_XENC_F32\s+0\b", hdr) and re.search(r"#define\s+RPR_XENC_F16\s+1\b", hdr)
-    assert lib.rpr_abi_version() == 4 and _lib.ABI_VERSION == 4
+    assert lib.rpr_abi_version() == 5 and _lib.ABI_VERSION == 5
     from ripor_amd import engine as E
     assert E.XENC_PRECISIONS == {"f32": 0, "f16": 1}
     assert "xenc_half.hip" in ge.SOURCES

@@ -232,7 +232,7 @@ def test_abi_symbols_and_desc_layout():
     lib = _lib.load()
     for name in ("rpr_xenc_load", "rpr_xenc_free", "rpr_xenc_score"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.rpr_abi_version() == 4
+    assert lib.rpr_abi_version() == 5
     hdr = open(os.path.join(REPO, "include", "ripor_hip.h")).read()
     body = re.search(r"typedef struct rpr_xenc_desc \{(.*?)\} rpr_xenc_desc;", hdr, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
