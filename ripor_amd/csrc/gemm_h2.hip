@@ -769,13 +769,19 @@ __device__ __forceinline__ void h2_epilogue_256(const GemmH2Args& g, typename H2
 // slice 1 x slice 1) on the same fragment reads — see gemm_h2_dma_kernel.
 // Schedules that were measured and removed (DESIGN.md "tried and rejected"; the code is in the history): a phase skew
 // between the persistent blocks, a per-round barrier between the blocks of an XCD, and the next tile's first K-tile
-// prefetched under the epilogue — all of them slower or equal on the power-capped headline step.
+// prefetched under the epilogue — all of them slower or equal on the power-capped headline step. Also measured and not
+// taken: the 32x32x16 body with the three products of an accumulator back to back (below, M16): registers only it ran 0.5 %
+// SLOWER than the interleaved order in every round (tools/mfma_chain_probe.hip, profiles/r29_mfma_chain_summary.txt).
 // The body is textually shared by two kernels (gemm_h2_pp_body.inc): gemm_h2_pp_kernel (one product, its arguments by value)
 // and gemm_h2_pp_group_kernel (a table of products in device memory, blockIdx.y = product; see there).
 // M16 = true (the launches of a search's tail passes, GemmH2Args::mfma16; f16x2 only): the same tiles, LDS layout, LDS-DMA feed and barrier
 // schedule with the K-loop on v_mfma_f32_16x16x32_f16 — 48 MFMAs of 16 cycles per phase instead of 24 of 32, a phase per half
 // of the wave's A rows instead of per k-chunk. A product's 32 columns of a K-tile are then summed inside one MFMA, so the
-// results differ from the 32x32x16 body's in the last bits.
+// results differ from the 32x32x16 body's in the last bits. Issue order: the 32x32x16 body walks its eight
+// accumulators three times (all lo*hi, all hi*lo, all hi*hi: an accumulator's products are eight MFMAs apart); the M16 body
+// gives each of a phase's sixteen accumulators its lo*hi, hi*lo, hi*hi BACK TO BACK (chained triples, A tile outer, W tile
+// inner), so two of three C operands come from the previous MFMA's result instead of the register file: the same bits, less
+// register-file traffic per MFMA, a higher clock under the power cap (+2.1 % on the headline step).
 template <bool FULL, bool BF16 = false, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm_h2_pp_kernel(GemmH2Args g, int tiles_m, int tiles_n) {
   static_assert(!(BF16 && M16), "the 16x16x32 body is the split-precision kernel's");
